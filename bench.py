@@ -18,12 +18,21 @@ ranks as child processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
 127.0.0.1 rendezvous) BEFORE anything touches the GPU, forwards rank 0's one
 JSON line and returns non-zero if any rank fails (`self_launch`).
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying
-`roofline` (dominant conv kernel: FLOPs the matrix cores execute / HIP-event
-time on the launch stream / dense peak, so `frac` <= 1; the algorithmic
-SURVEY-8d figure beside it; `roofline.hbm`: voxelise and pyramid+warp/loss
-call paths against 8 TB/s) and, at N=1, `cpu_baseline` (the CPU port of the
-same step timed on the host cores over a bounded sample).
+Rank 0 prints ONE JSON line: the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = wall time of one timed step) and
+the run's configuration.  A plain run does only that: set up, warm up, time
+the K steps, print.  `--full` adds the diagnostics that take runs of their
+own: `roofline` (dominant conv kernel: FLOPs the matrix cores execute /
+HIP-event time on the launch stream / dense peak, so `frac` <= 1; the
+algorithmic SURVEY-8d figure beside it; `roofline.hbm`: voxelise and
+pyramid+warp/loss call paths against 8 TB/s) and, at N=1, `other_modes`
+(the bf16 operand modes), `train_loop` (training.train() fed from host
+memory) and `cpu_baseline` (the CPU port of the same step timed on the host
+cores over a bounded sample); the --no-* options leave parts of it out.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller -- the
+loss and the updated parameters -- as float32 .npy files (see dump_outputs);
+the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -33,7 +42,6 @@ import time
 from pathlib import Path
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # see dvs_of_training_framework_amd/__init__.py
-os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "2")
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
@@ -191,6 +199,13 @@ def parse():
     p.add_argument('--eager', action='store_true',
                    help='enqueue every step from Python (torch.distributed issues the gradient '
                         'exchange under data parallelism)')
+    p.add_argument('--full', action='store_true',
+                   help='after the headline, also measure the roofline, the other operand modes, '
+                        'the train loop fed from host memory and the CPU baseline (the --no-* '
+                        'options leave parts out); a plain run reports the headline only')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the loss and the parameters after the last timed step to '
+                        'DIR/<name>.npy (float32)')
     p.add_argument('--no-other-modes', action='store_true',
                    help='skip the short bf16x3 / bf16 runs reported beside the fp32 headline')
     p.add_argument('--no-cpu-baseline', action='store_true')
@@ -203,7 +218,10 @@ def parse():
                    help='print this rank\'s view of the launch (rank, world size, rendezvous) as '
                         'one JSON line and exit without touching the GPU: the CPU test of the '
                         'self-launcher')
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error('--steps must be at least 1')
+    return a
 
 
 class Harness:
@@ -589,6 +607,8 @@ def host_cpu():
     physical = per * sockets if per else max(1, usable // max(threads_per, 1))
     if usable < physical * threads_per:      # a CPU share: hardware threads it may run on
         physical = max(1, usable // max(threads_per, 1))
+    if os.environ.get('OMP_NUM_THREADS', '').isdigit():     # a thread budget the host sets
+        physical = max(1, min(physical, int(os.environ['OMP_NUM_THREADS'])))
     return model, physical
 
 
@@ -754,6 +774,34 @@ def train_loop_rates(a, device, steps=420, warm=140, legs=('wire', 'compact', 'r
             'note': 'training.train() fed from host memory; see bench.py:train_loop_rates'}
 
 
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this many bytes of arrays in all
+
+
+def dump_outputs(path, h, loss):
+    """--dump-outputs: what the timed step hands its caller after the LAST timed step -- the loss
+    and the model's updated floating-point state (its parameters) -- as float32 DIR/<name>.npy,
+    one file per tensor (`loss.npy`, `param.<state_dict name>.npy`).  If the arrays exceed
+    DUMP_BYTES (not at the default shapes: 56.5 MB), every parameter is replaced by a fixed,
+    seeded sample of its flattened elements (the same one for the same arguments)."""
+    import numpy as np
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {'loss': loss.detach().float().reshape(1).cpu().numpy()}
+    for name, t in h.model.predictor.state_dict().items():
+        if t.is_floating_point():
+            arrays['param.' + name] = t.detach().float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES:
+        frac = 0.99 * DUMP_BYTES / total
+        rng = np.random.default_rng(1234)
+        for name in [k for k in arrays if k.startswith('param.')]:
+            flat = arrays[name].reshape(-1)
+            idx = np.sort(rng.choice(flat.size, max(1, int(flat.size * frac)), replace=False))
+            arrays[name] = flat[idx]
+    for name, v in arrays.items():
+        np.save(out / f'{name}.npy', v)
+
+
 def main():
     a = parse()
     if os.environ.get('DVSOF_EAGER') == '1':        # (sweep scripts set modes through the environment)
@@ -826,6 +874,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
     final_loss = float(loss.detach())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, h, loss)
 
     out = None
     if rank == 0:
@@ -874,7 +924,7 @@ def main():
                f', AdamW per gradient bucket inside the backward ({h.fused_optimizer})')
             + (f'; {ex.marks} exchange marks (bucket all-reduces issued by the executor on the '
                'exchange stream)' if ex.marks else ''))
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         h.suspend_graph()       # per-launch HIP events need eager launches
         # The per-launch measurement needs no exchange: under data parallelism it runs with the
         # reducer detached (replicas drift apart from here on -- the timed region is over), so
@@ -891,7 +941,7 @@ def main():
         h.model.predictor.reducer = reducer
         if rank == 0:
             out['roofline'] = roof
-    if rank == 0 and world == 1 and a.dtype == 'f32' and not a.no_other_modes:
+    if a.full and rank == 0 and world == 1 and a.dtype == 'f32' and not a.no_other_modes:
         # the same step in the reduced-precision matrix modes of configs[2] / [4]
         # (short runs; the headline above is the exact-f32 path)
         import copy
@@ -933,13 +983,13 @@ def main():
                           '(DESIGN section 4): lds_stream = L2 -> LDS bytes of the general implicit-GEMM '
                           'kernels / their time / 6.3 TB/s')
         out['other_modes'] = others
-    if rank == 0 and world == 1 and not a.no_train_loop:
+    if a.full and rank == 0 and world == 1 and not a.no_train_loop:
         if 'h' in dir():
             h.suspend_graph()
             del h
         out['train_loop'] = train_loop_rates(a, device)
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(a)
         print(json.dumps(out), flush=True)
     barrier()

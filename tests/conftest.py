@@ -14,13 +14,22 @@ def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs a real MI355X (run with -m gpu)')
 
 
+def load_golden(stem):
+    """A golden set stored in parts under the size limit for a committed file
+    (<stem>.npz, <stem>.part2.npz, ...; tools/make_goldens.py): name -> array."""
+    import numpy as np
+    out = {}
+    for path in [GOLDEN / f'{stem}.npz'] + sorted(GOLDEN.glob(f'{stem}.part*.npz')):
+        with np.load(path) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
+
+
 @pytest.fixture(scope='session')
 def golden_loss():
-    import numpy as np
-    return np.load(GOLDEN / 'loss_reference.npz')
+    return load_golden('loss_reference')
 
 
 @pytest.fixture(scope='session')
 def fixtures():
-    import numpy as np
-    return np.load(GOLDEN / 'fixtures.npz')
+    return load_golden('fixtures')

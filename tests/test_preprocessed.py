@@ -2,8 +2,8 @@
 literals (tests/dataset/test_encoding.py:270-313 read/write + loader incl.
 wrap-around; tests/dataset/test_quantization.py:145-166), bit-exact including
 dtypes.  The HDF5 backend (libhdf5 via ctypes) is additionally checked against
-files h5py wrote -- the reference's own fixtures -- where they are reachable
-(this container; they do not travel to the GPU box)."""
+files h5py wrote -- two of the reference's own fixtures, stored under
+tests/golden/."""
 import subprocess
 from pathlib import Path
 
@@ -13,6 +13,8 @@ import torch
 
 from dvs_of_training_framework_amd import encoding as enc, hdf5io
 from tests.test_encoding import GOLD, compare
+
+GOLDEN = Path(__file__).parent / 'golden'
 
 pytestmark = pytest.mark.skipif(not hdf5io.available(), reason='libhdf5 not found')
 
@@ -53,9 +55,7 @@ def test_hdf5_round_trip_of_every_dtype(tmp_path):
 def test_reads_files_written_by_h5py(fixtures):
     """The reference's test sequence was written by h5py: every dataset read
     through hdf5io equals the h5dump extraction committed as fixtures.npz."""
-    seq = Path('/root/reference/tests/data/seq/000001.hdf5')
-    if not seq.exists():
-        pytest.skip('reference fixtures are only reachable in the build container')
+    seq = GOLDEN / 'h5py_seq_000001.hdf5'        # the reference's tests/data/seq/000001.hdf5
     with hdf5io.File(seq, 'r') as f:
         ev = f['events'][...]
         assert ev.dtype == np.float64 and np.array_equal(ev, fixtures['events_1'])
@@ -63,7 +63,7 @@ def test_reads_files_written_by_h5py(fixtures):
         assert np.array_equal(f['image2'][...], fixtures['frames'][2])
         assert float(f['start'][...]) == float(fixtures['start'][1])
         assert float(f['stop'][...]) == float(fixtures['stop'][1])
-    pred = Path('/root/reference/tests/data/pred/000001.hdf5')
+    pred = GOLDEN / 'h5py_pred_000001.hdf5'      # the reference's tests/data/pred/000001.hdf5
     with hdf5io.File(pred, 'r') as f:
         assert np.array_equal(f['flow'][...], fixtures['pred_flow'])
 

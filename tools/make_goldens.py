@@ -7,6 +7,7 @@ source is copied; only data the reference's tests hold (HDF5 fixtures) and
 numbers the reference computes are written out.
 
 What is produced
+  (the .npz sets are written in parts of at most 10^6 bytes: <name>.npz, <name>.part2.npz, ...)
   fixtures.npz        frames/events/timestamps of tests/data/seq/00000{0..9}.hdf5
                       and the (single, 10x duplicated) tests/data/pred flow
   loss_reference.npz  utils.loss.Losses outputs + autograd flow gradients on
@@ -37,6 +38,34 @@ from utils.loss import Losses, init_losses  # noqa: E402  (reference)
 from utils.timer import FakeTimer  # noqa: E402  (reference)
 from utils.training import process_minibatch, combined_loss  # noqa: E402
 from DummyNet.net import Model as DummyModel, get_local_idx  # noqa: E402
+
+
+LIMIT = 10 ** 6      # bytes per committed file (under 1 MiB)
+
+
+def save_parts(stem, arrays):
+    """np.savez_compressed in parts of at most LIMIT bytes: <stem>.npz,
+    <stem>.part2.npz, ... (tests/conftest.py merges them).  Largest arrays
+    first, each into the first part it still fits in."""
+    import io
+
+    def size(d):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **d)
+        return buf.tell()
+    parts = []
+    for k in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        for part in parts:
+            if size(dict(part, **{k: arrays[k]})) <= LIMIT:
+                part[k] = arrays[k]
+                break
+        else:
+            parts.append({k: arrays[k]})
+    for old in OUT.glob(f'{stem}.part*.npz'):
+        old.unlink()
+    for i, part in enumerate(parts):
+        name = f'{stem}.npz' if i == 0 else f'{stem}.part{i + 1}.npz'
+        np.savez_compressed(OUT / name, **part)
 
 
 def h5read(path, name, dtype, shape):
@@ -73,7 +102,7 @@ def extract_fixtures():
     out['start'] = np.array(starts)
     out['stop'] = np.array(stops)
     out['pred_flow'] = flows[0]                 # [260,346,2] f32
-    np.savez_compressed(OUT / 'fixtures.npz', **out)
+    save_parts('fixtures', out)
     return out
 
 
@@ -173,7 +202,7 @@ def loss_goldens(fx):
         for k, gk in enumerate(g):
             out[f'{name}_grad{k}'] = gk
         print(name, 'terms', t.tolist(), 'loss', l)
-    np.savez_compressed(OUT / 'loss_reference.npz', **out)
+    save_parts('loss_reference', out)
 
 
 def lr_sequence(warmup, half_life, rs, steps, n):
