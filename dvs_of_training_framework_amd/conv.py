@@ -61,6 +61,7 @@ _lib.register('dvsof_act_bwd', _i, [_vp, _vp, _i, _vp, _sz, _vp])
 _lib.register('dvsof_conv2d_tile_id', _i, [_P(ConvDesc), _i])
 _lib.register('dvsof_conv2d_kernel_generation', _i, [_P(ConvDesc), _i])
 _lib.register('dvsof_conv2d_last_patch', _i, [_i])
+_lib.register('dvsof_conv2d_last_kernel', _i, [_i])
 _lib.register('dvsof_conv2d_fwd_weight_elems', _sz, [_P(ConvDesc)])
 _lib.register('dvsof_conv2d_dgrad_weight_elems', _sz, [_P(ConvDesc)])
 _lib.register('dvsof_conv2d_prepare', _i, [_P(ConvDesc), _vp, _vp, _vp, _vp])
@@ -113,6 +114,21 @@ def to_bf16_many(tensors):
 
 
 UP_NONE, UP_NEAREST, UP_ZERO = 0, 1, 2     # dvsof_conv_desc_t.upsample
+
+# kernel families (include/dvsof.h DVSOF_KERNEL_*), as dvsof_conv2d_last_kernel reports them
+(K_NONE, K_GENERAL_V1, K_GENERAL_V2, K_FLAT_VALU, K_FIRST, K_WINO2, K_WINO4, K_FWD_MIN4,
+ K_FWD_MIN8, K_FWD_PATCH, K_DGRAD_MIN0, K_DGRAD_MIN1, K_DGRAD_MIN2, K_WGRAD_PATCH, K_WGRAD_MIN,
+ K_TRANSPOSED, K_STRIDE2_PHASED) = range(17)
+KERNEL_NAMES = ('none', 'general_v1', 'general_v2', 'flat_valu', 'first', 'wino2', 'wino4',
+                'fwd_min4', 'fwd_min8', 'fwd_patch', 'dgrad_min0', 'dgrad_min1', 'dgrad_min2',
+                'wgrad_patch', 'wgrad_min', 'transposed', 'stride2_phased')
+
+
+def last_kernel(kind):
+    """-> (family, effective operand mode) of what this thread's last conv_fwd
+    (kind 0) / conv_dgrad (1) / conv_wgrad (2) launched (dvsof_conv2d_last_kernel)."""
+    v = _lib.lib().dvsof_conv2d_last_kernel(kind)
+    return v & 255, v >> 8
 
 
 def make_desc(srcs, B, H, W, Cout, ksize=3, stride=1, pad=1, upsample=False,

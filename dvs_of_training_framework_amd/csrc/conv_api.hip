@@ -35,9 +35,24 @@ size_t first_wgrad_workspace_floats(int B, int C, int H, int W);
 int first_wgrad_launch(const float *x, int B, int C, int H, int W, const float *gout, float *dW,
                        float *dbias, float *ws, size_t ws_floats, hipStream_t st);
 
-// set by the launches below / read by dvsof_conv2d_last_patch (profiling tools)
-static thread_local int t_last_patch[3] = {0, 0, 0};
-void conv_note_patch(int kind, int what) { t_last_patch[kind] = what; }
+// family | mode << 8 of what the calling thread's last fwd (0) / dgrad (1) / wgrad (2) launched
+// (dvsof_conv2d_last_kernel; dvsof_conv2d_last_patch is derived from it), noted by the launcher
+// that ran; t_kind = the entry point in progress
+static thread_local int t_last_kernel[3] = {0, 0, 0};
+static thread_local int t_kind = 0;
+void conv_note_kernel(int family, int mode) { t_last_kernel[t_kind] = family | mode << 8; }
+static void conv_begin(int kind)
+{
+    t_kind = kind;
+    t_last_kernel[kind] = DVSOF_KERNEL_NONE;
+}
+// the layer-level family of a launch that ran on the general kernels (the phase forms), in the
+// mode the kernel noted
+static int conv_retag(int rc, int family)
+{
+    if (rc == DVSOF_OK && t_last_kernel[t_kind]) conv_note_kernel(family, t_last_kernel[t_kind] >> 8);
+    return rc;
+}
 
 // fwd_patch.hip: forward of the finest decoder stage in the bf16-twins mode (patch in LDS,
 // weights in registers)
@@ -736,7 +751,7 @@ int dvsof_conv2d_fwd(const dvsof_conv_desc_t *d, const float *weight, const floa
                      const float *residual, float *y, float *z, void *stream)
 {
     int Ctot, Ho, Wo;
-    t_last_patch[0] = 0;
+    conv_begin(0);
     if (!desc_ok(d, Ctot, Ho, Wo) || !weight || !y) return DVSOF_EINVAL;
     if (is_first_layer(d) && !residual)     // exact f32 in every operand mode
         return first_fwd_launch(d->src[0].p, d->B, Ctot, d->H, d->W, weight, bias, d->act, y, z,
@@ -814,15 +829,12 @@ int dvsof_conv2d_fwd(const dvsof_conv_desc_t *d, const float *weight, const floa
         return wino_launch(P, (float *)d->scratch, d->scratch_bytes / sizeof(float), ch, as_stream(stream));
     }
     if (d->winograd_pre || d->winograd_next || d->winograd_next_gout) return DVSOF_EINVAL;
-    if (is_min9(d)) {   // `weight` is the prepared Wt[9][Cout][Ctot]
-        t_last_patch[0] = 2;
+    if (is_min9(d))     // `weight` is the prepared Wt[9][Cout][Ctot]
         return fwd_min_launch(P, as_stream(stream));
-    }
-    if (is_subpixel(d) && fwd_patch_eligible(P)) {  // finest decoder stage: fwd_patch.hip
-        t_last_patch[0] = 1;
+    if (is_subpixel(d) && fwd_patch_eligible(P))    // finest decoder stage: fwd_patch.hip
         return fwd_patch_launch(P, as_stream(stream));
-    }
-    return gconv_launch(P, 0, as_stream(stream));
+    const int rc = gconv_launch(P, 0, as_stream(stream));
+    return is_transposed(d) ? conv_retag(rc, DVSOF_KERNEL_TRANSPOSED) : rc;
 }
 
 static bool head_fold_ok(const dvsof_conv_desc_t *d)
@@ -856,6 +868,7 @@ int dvsof_conv2d_dgrad(const dvsof_conv_desc_t *d, const float *weight_t, const 
                        const dvsof_grad_dst_t *dst, int bwd_act, void *stream)
 {
     int Ctot, Ho, Wo;
+    conv_begin(1);
     if (!desc_ok(d, Ctot, Ho, Wo) || !weight_t || !gout || !dst) return DVSOF_EINVAL;
     GConvParams P = {};
     P.nsrc = 1;
@@ -958,17 +971,15 @@ int dvsof_conv2d_dgrad(const dvsof_conv_desc_t *d, const float *weight_t, const 
         P.quad = 0;
     }
     P.M = d->B * P.Ho * P.Wo;
-    t_last_patch[1] = 0;
-    if (is_min9_dgrad(d)) {  // weight_t is the prepared W'[9][Ctot][Cout]
-        t_last_patch[1] = 2;
+    if (is_min9_dgrad(d))    // weight_t is the prepared W'[9][Ctot][Cout]
         return dgrad_min_launch(P, as_stream(stream));
-    }
     if (is_wino(d)) {  // weight_t is the prepared U'[16][Ctot][Cout]
         const WinoChain ch = {d->winograd_pre, d->winograd_next, d->winograd_next_gout};
         return wino_launch(P, (float *)d->scratch, d->scratch_bytes / sizeof(float), ch, as_stream(stream));
     }
     if (d->winograd_pre || d->winograd_next || d->winograd_next_gout) return DVSOF_EINVAL;
-    return gconv_launch(P, 0, as_stream(stream));
+    const int rc = gconv_launch(P, 0, as_stream(stream));
+    return is_stride2_phased(d) ? conv_retag(rc, DVSOF_KERNEL_STRIDE2_PHASED) : rc;
 }
 
 size_t dvsof_conv2d_scratch_bytes(const dvsof_conv_desc_t *d)
@@ -1038,7 +1049,7 @@ int dvsof_conv2d_wgrad(const dvsof_conv_desc_t *d, const float *gout, float *dwe
                        void *ws, size_t ws_bytes, void *stream)
 {
     int Ctot, Ho, Wo;
-    t_last_patch[2] = 0;
+    conv_begin(2);
     if (!desc_ok(d, Ctot, Ho, Wo) || !gout || !dweight) return DVSOF_EINVAL;
     if (is_transposed(d)) {
         if (dbias && d->Cout > 256) return DVSOF_EINVAL;
@@ -1258,9 +1269,24 @@ int dvsof_conv2d_kernel_generation(const dvsof_conv_desc_t *d, int kind)
     return 1;
 }
 
+int dvsof_conv2d_last_kernel(int kind)
+{
+    return (kind >= 0 && kind <= 2) ? t_last_kernel[kind] : 0;
+}
+
 int dvsof_conv2d_last_patch(int kind)
 {
-    return (kind >= 0 && kind <= 2) ? t_last_patch[kind] : 0;
+    switch (dvsof_conv2d_last_kernel(kind) & 255) {
+    case DVSOF_KERNEL_FWD_MIN4:
+    case DVSOF_KERNEL_FWD_MIN8:
+    case DVSOF_KERNEL_DGRAD_MIN0:
+    case DVSOF_KERNEL_DGRAD_MIN1:
+    case DVSOF_KERNEL_DGRAD_MIN2:
+    case DVSOF_KERNEL_WGRAD_MIN: return 2;
+    case DVSOF_KERNEL_FWD_PATCH:
+    case DVSOF_KERNEL_WGRAD_PATCH: return 1;
+    default: return 0;
+    }
 }
 
 int dvsof_conv2d_tile_id(const dvsof_conv_desc_t *d, int kind)

@@ -486,6 +486,7 @@ int dgrad_min_launch(const GConvParams &P, hipStream_t st)
         }
         hipLaunchKernelGGL(dgrad_min_f32_kernel<0>, dim3(256), dim3(DM_NT), DM_LDS, st, P, (int)total);
         DVSOF_LAUNCH_CHECK();
+        conv_note_kernel(DVSOF_KERNEL_DGRAD_MIN0, 0);
         return DVSOF_OK;
     }
     if (ipw == 2)
@@ -493,5 +494,6 @@ int dgrad_min_launch(const GConvParams &P, hipStream_t st)
     else
         hipLaunchKernelGGL(dgrad_min_f32_kernel<1>, dim3((unsigned)total), dim3(DM_NT), DM_LDS, st, P, (int)total);
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(ipw == 2 ? DVSOF_KERNEL_DGRAD_MIN2 : DVSOF_KERNEL_DGRAD_MIN1, 0);
     return DVSOF_OK;
 }

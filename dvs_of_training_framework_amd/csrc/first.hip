@@ -389,6 +389,7 @@ int first_fwd_launch(const float *x, int B, int C, int H, int W, const float *w,
     }
     hipLaunchKernelGGL(first_fwd_kernel, dim3(P.ntiles), dim3(CONV_NT), lds, st, P);
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(DVSOF_KERNEL_FIRST, y16 ? 3 : 0);     // f32 arithmetic; 3: the twin written
     return DVSOF_OK;
 }
 
@@ -437,5 +438,6 @@ int first_wgrad_launch(const float *x, int B, int C, int H, int W, const float *
     hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((nout + kWave - 1) / kWave), dim3(RED_WAVES * kWave), 0, st,
                        (const float *)ws, G, ncb * 32, P.K, dW, dbias);
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(DVSOF_KERNEL_FIRST, 0);
     return DVSOF_OK;
 }

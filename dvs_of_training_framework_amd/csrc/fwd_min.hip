@@ -400,6 +400,7 @@ static int fm_launch(const GConvParams &P, int grid, hipStream_t st)
     }
     hipLaunchKernelGGL((fwd_min_f32_kernel<NR, ZOUT>), dim3(grid), dim3(FM_NT), G::LDS, st, P);
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(NR == 8 ? DVSOF_KERNEL_FWD_MIN8 : DVSOF_KERNEL_FWD_MIN4, 0);
     return DVSOF_OK;
 }
 

@@ -568,6 +568,7 @@ static int fp_launch(const GConvParams &P, int nblocks, int bpw, int grid, hipSt
     }
     hipLaunchKernelGGL((fwd_patch_twins_kernel<TWIN, ZOUT>), dim3(grid), dim3(CONV_NT), LDS, st, P, nblocks, bpw);
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(DVSOF_KERNEL_FWD_PATCH, 3);
     return DVSOF_OK;
 }
 
@@ -583,6 +584,7 @@ static int fq_launch(const GConvParams &P, int nblocks, int bpw, int grid, hipSt
     }
     hipLaunchKernelGGL((fwd_patch_f32_kernel<ZOUT>), dim3(grid), dim3(FQ_NT), LDS, st, P, nblocks, bpw);
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(DVSOF_KERNEL_FWD_PATCH, 0);
     return DVSOF_OK;
 }
 

@@ -265,6 +265,7 @@ int launch(const GConvParams &P, hipStream_t st)
     hipLaunchKernelGGL((gconv_kernel<WROWS, WCOLS, TM, TN>), grid, dim3(CONV_NT), 0, st, P,
                        count_steps(P));
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(DVSOF_KERNEL_GENERAL_V1, 0);     // exact f32 in every operand mode
     return DVSOF_OK;
 }
 

@@ -571,6 +571,7 @@ int launch2x(const GConvParams &P, int nflat, int nvec, hipStream_t st)
     hipLaunchKernelGGL((gconv2_kernel<WROWS, WCOLS, TM, TN, KSUB, NS, KSPLIT, BF16, TAG>), grid,
                        dim3(CONV_NT * KSPLIT), LDS, st, Q, nflat, nvec);
     DVSOF_LAUNCH_CHECK();
+    conv_note_kernel(DVSOF_KERNEL_GENERAL_V2, BF16);
     return DVSOF_OK;
 }
 

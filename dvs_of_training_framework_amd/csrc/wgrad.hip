@@ -895,7 +895,6 @@ bool wgrad_patch_shape_ok(const WGradParams &P);
 bool wgrad_patch_eligible(const WGradParams &P);
 int wgrad_patch_splits(const WGradParams &P);
 int wgrad_patch_launch(const WGradParams &P, hipStream_t st);
-void conv_note_patch(int kind, int what);     // conv_api.hip
 bool wgrad_min_ok(const WGradParams &P);  // wgrad_min.hip
 
 // Number of K splits used for this problem (deterministic in the shape).
@@ -949,6 +948,7 @@ int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_fl
     int want_flat = -1;  // v1 MFMA tiles for everything ...
     int rc = DVSOF_OK;
     bool bias_in_kernel = false, patch_folded = false;
+    int fam = DVSOF_KERNEL_NONE, fam_mode = 0;     // the vector members' kernel (dvsof_conv2d_last_kernel)
     if (!force_v1 && wgrad2_eligible(P)) {  // ... or v2 for the vector members
         int bm, bn;
         tile_dims(tile, bm, bn);
@@ -961,11 +961,12 @@ int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_fl
             }
             // (flat members on the v1 tiles would write phase-form columns into the same slabs)
             if (!direct && wgrad_patch_eligible(P) && (flat_valu || nflat == 0)) {
-                conv_note_patch(2, (!P.twins && P.mfma_bf16 == 0 && wgrad_min_ok(P)) ? 2 : 1);
-                patch_folded = true;    // its slabs are [S][Cout][3][3][Cin_tot] already
+                patch_folded = true;    // its slabs are [S][Cout][3][3][Cin_tot] already (it notes its kernel)
                 rc = wgrad_patch_launch(P, st);
             } else {
                 rc = wgrad2_launch(P, tile, nt, st);
+                fam = DVSOF_KERNEL_GENERAL_V2;
+                fam_mode = P.twins ? 3 : P.mfma_bf16;
             }
             P.dbias = nullptr;
         }
@@ -984,6 +985,7 @@ int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_fl
         default: rc = launch<1, 4, 1, 1>(P, want_flat, st); break;
         }
         if (rc) return rc;
+        if (fam == DVSOF_KERNEL_NONE) fam = DVSOF_KERNEL_GENERAL_V1;    // exact f32 in every mode
     }
     // flat-only layer on the matrix-core flat kernel: the bias gradient is one more output
     // column of that kernel (no pass over gout of its own)
@@ -1042,7 +1044,9 @@ int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_fl
             if (rc) return rc;
             part += (size_t)FLAT_BLOCKS * flat[i].Cout * (flat[i].ncol + 1);
         }
+        if (fam == DVSOF_KERNEL_NONE && !patch_folded) fam = DVSOF_KERNEL_FLAT_VALU;
     }
+    if (!patch_folded) conv_note_kernel(fam, fam_mode);
     return DVSOF_OK;
 }
 

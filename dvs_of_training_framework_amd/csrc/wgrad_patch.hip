@@ -649,8 +649,15 @@ static int wp_launch_f32(WGradParams &P, hipStream_t st)
 int wgrad_patch_launch(const WGradParams &P0, hipStream_t st)
 {
     WGradParams P = P0;
-    if (wp_f32(P) && wgrad_min_ok(P)) return wgrad_min_launch(P, st);
+    if (wp_f32(P) && wgrad_min_ok(P)) {
+        const int rc = wgrad_min_launch(P, st);
+        if (rc == DVSOF_OK) conv_note_kernel(DVSOF_KERNEL_WGRAD_MIN, 0);
+        return rc;
+    }
     const int ct = wp_channel_tile(P);
-    if (wp_f32(P)) return ct == 64 ? wp_launch_f32<64>(P, st) : wp_launch_f32<32>(P, st);
-    return ct == 64 ? wp_launch<64>(P, st) : wp_launch<32>(P, st);
+    int rc;
+    if (wp_f32(P)) rc = ct == 64 ? wp_launch_f32<64>(P, st) : wp_launch_f32<32>(P, st);
+    else rc = ct == 64 ? wp_launch<64>(P, st) : wp_launch<32>(P, st);
+    if (rc == DVSOF_OK) conv_note_kernel(DVSOF_KERNEL_WGRAD_PATCH, P.twins ? 3 : P.mfma_bf16);
+    return rc;
 }

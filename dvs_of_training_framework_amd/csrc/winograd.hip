@@ -743,7 +743,9 @@ int wino_launch(const GConvParams &P, float *scratch, size_t scratch_floats, con
         return DVSOF_ENOSPACE;
     const int f = wino_tile(P.B, P.Hv, P.Wv, P.mfma_bf16);
     if (f == 0) return DVSOF_EINVAL;
-    return f == 4 ? wino_launch_f<4>(P, scratch, ch, st) : wino_launch_f<2>(P, scratch, ch, st);
+    const int rc = f == 4 ? wino_launch_f<4>(P, scratch, ch, st) : wino_launch_f<2>(P, scratch, ch, st);
+    if (rc == DVSOF_OK) conv_note_kernel(f == 4 ? DVSOF_KERNEL_WINO4 : DVSOF_KERNEL_WINO2, P.mfma_bf16);
+    return rc;
 }
 
 // ---- weight gradient
@@ -874,6 +876,8 @@ int wino_wgrad_launch(const GSrc &X, const float *V_in, const float *Z_in, const
     const int f = wino_wgrad_tile(B, H, W, mfma_bf16);
     if (f == 0) return DVSOF_EINVAL;
     if (!ws || ws_floats < wino_wgrad_workspace_floats(B, H, W, C, N, mfma_bf16)) return DVSOF_ENOSPACE;
-    return f == 4 ? wino_wgrad_f<4>(X, V_in, Z_in, gout, dW, dbias, B, H, W, C, N, mfma_bf16, ws, st)
-                  : wino_wgrad_f<2>(X, V_in, Z_in, gout, dW, dbias, B, H, W, C, N, mfma_bf16, ws, st);
+    const int rc = f == 4 ? wino_wgrad_f<4>(X, V_in, Z_in, gout, dW, dbias, B, H, W, C, N, mfma_bf16, ws, st)
+                          : wino_wgrad_f<2>(X, V_in, Z_in, gout, dW, dbias, B, H, W, C, N, mfma_bf16, ws, st);
+    if (rc == DVSOF_OK) conv_note_kernel(f == 4 ? DVSOF_KERNEL_WINO4 : DVSOF_KERNEL_WINO2, mfma_bf16);
+    return rc;
 }

@@ -401,6 +401,9 @@ int dvsof_conv2d_winograd_chain(const dvsof_conv_desc_t *desc, int kind);
  * another stream).  (Sixteen-product form only: weight == NULL means "w_fwd
  * already holds the phase kernels of an earlier call" and w_dgrad is derived
  * from them -- DVSOF_EINVAL for a layer whose forward form is Wt.)
+ * Once Wt / W' are prepared the layer is bound to the nine-product kernels:
+ * the pointers passed to dvsof_conv2d_fwd / _dgrad must then be 16-byte
+ * aligned and the forward takes no residual (DVSOF_EINVAL otherwise, see there).
  */
 size_t dvsof_conv2d_fwd_weight_elems(const dvsof_conv_desc_t *desc);
 size_t dvsof_conv2d_dgrad_weight_elems(const dvsof_conv_desc_t *desc);
@@ -408,7 +411,11 @@ int dvsof_conv2d_prepare(const dvsof_conv_desc_t *desc, const float *weight,
                          float *w_fwd, float *w_dgrad, void *stream);
 
 /* weight = prepared forward weights (see above).
- * y (and z = pre-activation, optional, for Mish backward) are NHWC. */
+ * y (and z = pre-activation, optional, for Mish backward) are NHWC.
+ * Nine-product layers (forward form Wt, see above) have no other kernel to
+ * fall back to once the weights are prepared: DVSOF_EINVAL, before any launch
+ * and with y / z untouched, when a source, y, z, weight, bias or bias_cls is
+ * not 16-byte aligned, or when a residual is given. */
 int dvsof_conv2d_fwd(const dvsof_conv_desc_t *desc, const float *weight,
                      const float *bias, const float *residual, float *y,
                      float *z, void *stream);
@@ -419,7 +426,12 @@ typedef struct {
     const float *addend2; /* optional second addend */
     const float *actsrc; /* optional: p *= act'(actsrc), the producer's y
                             (ReLU) or z (Mish): yields its dz directly */
-    void *p16;           /* optional bf16 twin of p, written (mode 3) */
+    void *p16;           /* optional bf16 twin of p, written (mode 3; NHWC
+                            members only).  In mode 3 the vector members'
+                            gradients multiply the twins of gout and of the
+                            weights; a planar (NCHW or narrow) member's
+                            gradient is computed from the f32 gout and f32
+                            weights, as that member's forward reads f32. */
     /* optional, only where dvsof_conv2d_dgrad_fuses_head(desc) says so (the
      * nine-product data gradient, csrc/dgrad_min.hip): the flow head that hangs
      * on this source is folded into the epilogue,
@@ -454,6 +466,9 @@ int dvsof_conv2d_dgrad_fuses_head(const dvsof_conv_desc_t *desc);
 int dvsof_conv2d_dgrad_head_rows(const dvsof_conv_desc_t *desc);
 /* dw [2][C], dbias [2] (may be NULL) = column sums of part [rows][2 C + 2] */
 int dvsof_flow_head_reduce(const float *part, int rows, int C, float *dw, float *dbias, void *stream);
+/* Nine-product data gradient (form W', see dvsof_conv2d_prepare): DVSOF_EINVAL,
+ * before any launch and with every dst untouched, when gout, weight_t or a
+ * dst's p / addend / addend2 / actsrc / head_w is not 16-byte aligned. */
 int dvsof_conv2d_dgrad(const dvsof_conv_desc_t *desc, const float *weight_t,
                        const float *gout, const dvsof_grad_dst_t *dst,
                        int bwd_act, void *stream);
@@ -483,8 +498,40 @@ int dvsof_conv2d_kernel_generation(const dvsof_conv_desc_t *desc, int kind);
  * nine-product minimal form (csrc/fwd_min.hip, dgrad_min.hip, wgrad_min.hip:
  * exact f32; 9 instead of 16 matrix products per low-resolution pixel).  The
  * choice depends on operand mode, twins and shape (profiling tools: bench.py
- * names its roofline groups and counts executed FLOPs with it) */
+ * names its roofline groups and counts executed FLOPs with it).  Derived from
+ * the record dvsof_conv2d_last_kernel reads. */
 int dvsof_conv2d_last_patch(int kind);
+/* Kernel families of the conv stack (dvsof_conv2d_last_kernel). */
+enum {
+    DVSOF_KERNEL_NONE = 0,          /* nothing launched (refused call) */
+    DVSOF_KERNEL_GENERAL_V1 = 1,    /* csrc/gconv.hip, wgrad.hip: register-staged, exact f32 */
+    DVSOF_KERNEL_GENERAL_V2 = 2,    /* csrc/gconv2.hip, wgrad2.hip: LDS-DMA ring */
+    DVSOF_KERNEL_FLAT_VALU = 3,     /* weight gradient of flat (planar / narrow) members only */
+    DVSOF_KERNEL_FIRST = 4,         /* csrc/first.hip */
+    DVSOF_KERNEL_WINO2 = 5,         /* csrc/winograd.hip, F(2x2,3x3) */
+    DVSOF_KERNEL_WINO4 = 6,         /* csrc/winograd.hip, F(4x4,3x3) */
+    DVSOF_KERNEL_FWD_MIN4 = 7,      /* csrc/fwd_min.hip, 4-row blocks */
+    DVSOF_KERNEL_FWD_MIN8 = 8,      /* csrc/fwd_min.hip, 8-row blocks */
+    DVSOF_KERNEL_FWD_PATCH = 9,     /* csrc/fwd_patch.hip (f32 or twins) */
+    DVSOF_KERNEL_DGRAD_MIN0 = 10,   /* csrc/dgrad_min.hip <0>: resident weights, persistent */
+    DVSOF_KERNEL_DGRAD_MIN1 = 11,   /* <1>: one item per workgroup */
+    DVSOF_KERNEL_DGRAD_MIN2 = 12,   /* <2>: two items per workgroup */
+    DVSOF_KERNEL_WGRAD_PATCH = 13,  /* csrc/wgrad_patch.hip */
+    DVSOF_KERNEL_WGRAD_MIN = 14,    /* csrc/wgrad_min.hip */
+    DVSOF_KERNEL_TRANSPOSED = 15,   /* transposed layer (upsample 2): output-parity phases */
+    DVSOF_KERNEL_STRIDE2_PHASED = 16 /* stride-2 data gradient as four input-parity phases */
+};
+/* What the calling thread's LAST dvsof_conv2d_fwd (kind 0) / _dgrad (1) / _wgrad
+ * (2) launched: family | effective_mode << 8.  family is a DVSOF_KERNEL_* value
+ * (DVSOF_KERNEL_NONE when the call launched nothing); effective_mode is the
+ * operand mode after every fallback (0 exact f32, 1 bf16-rounded operands,
+ * 2 bf16x3, 3 bf16 twins streamed).  Mode 3 silently becomes 1 where a twin is
+ * missing or a channel count does not fit; this record tells the two apart.
+ * The first-layer kernels compute in f32 in every mode: their mode is 3 when
+ * the forward wrote y16, else 0.  A weight gradient with flat and vector
+ * members records the vector members' kernel.  Set after the launch (recorded
+ * by the launcher that ran, not by the planning predicates). */
+int dvsof_conv2d_last_kernel(int kind);
 
 /* wt[ci][k*k-1-tap][co] = w[co][tap][ci] */
 int dvsof_weight_flip_transpose(const float *w, float *wt, int Cout, int ksize,

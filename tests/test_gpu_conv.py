@@ -31,65 +31,115 @@ def wphys(w):  # OIHW -> [O][kh][kw][I] on the GPU
 
 CASES = [
     # B, H, W, chans(list, layouts), Cout, k, stride, up, act
-    dict(B=2, H=16, W=16, src=[(5, 'nchw')], Cout=64, stride=2),
-    dict(B=1, H=13, W=19, src=[(3, 'nchw')], Cout=32, stride=2),
-    dict(B=2, H=12, W=20, src=[(64, 'nhwc')], Cout=128, stride=2),
-    dict(B=3, H=8, W=8, src=[(32, 'nhwc')], Cout=32, stride=1, residual=True),
+    dict(B=2, H=16, W=16, src=[(5, 'nchw')], Cout=64, stride=2,
+         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
+    dict(B=1, H=13, W=19, src=[(3, 'nchw')], Cout=32, stride=2,
+         path=('general_v1 general_v2 flat_valu', 'general_v1 general_v2 flat_valu', 'general_v1 general_v2 flat_valu')),
+    dict(B=2, H=12, W=20, src=[(64, 'nhwc')], Cout=128, stride=2,
+         path=('general_v2 stride2_phased general_v1', 'general_v2 stride2_phased general_v1', 'general_v2 stride2_phased general_v1')),
+    dict(B=3, H=8, W=8, src=[(32, 'nhwc')], Cout=32, stride=1, residual=True,
+         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
     dict(B=2, H=8, W=12, src=[(32, 'nhwc'), (16, 'nhwc'), (2, 'nchw')], Cout=32,
-         up=True),
-    dict(B=1, H=4, W=4, src=[(512, 'nhwc'), (512, 'nhwc')], Cout=256, up=True),
-    dict(B=2, H=9, W=7, src=[(20, 'nhwc')], Cout=48, stride=1, k=5, pad=2),
+         up=True,
+         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
+    dict(B=1, H=4, W=4, src=[(512, 'nhwc'), (512, 'nhwc')], Cout=256, up=True,
+         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
+    dict(B=2, H=9, W=7, src=[(20, 'nhwc')], Cout=48, stride=1, k=5, pad=2,
+         path=('general_v1 general_v2 general_v1', 'general_v1 general_v2 general_v1', 'general_v1 general_v2 general_v1')),
     dict(B=2, H=16, W=16, src=[(64, 'nhwc'), (64, 'nhwc'), (2, 'nchw')], Cout=32,
-         up=True, act='mish'),
+         up=True, act='mish',
+         path=('general_v2 general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
     # wide 3x3 stride-1 layers with enough tiles: Winograd.  F(2x2,3x3) (W % 4 != 0),
     # forward, data and weight gradient
-    dict(B=4, H=8, W=18, src=[(256, 'nhwc')], Cout=320, stride=1, residual=True, wino=True),
+    dict(B=4, H=8, W=18, src=[(256, 'nhwc')], Cout=320, stride=1, residual=True, wino=True,
+         path=('wino2 wino2 wino2', 'general_v2 general_v2 general_v1', 'wino2 wino2 wino2')),
     # F(4x4,3x3) forward / data gradient (64 tiles), F(2x2) weight gradient
-    dict(B=8, H=8, W=16, src=[(320, 'nhwc')], Cout=256, stride=1, act='mish', wino=True),
+    dict(B=8, H=8, W=16, src=[(320, 'nhwc')], Cout=256, stride=1, act='mish', wino=True,
+         path=('wino4 wino4 wino2', 'general_v2 general_v2 general_v2', 'wino2 wino2 wino2')),
     # fewer than 64 4x4 tiles: the 2x2 form on a 4-aligned image
-    dict(B=6, H=8, W=16, src=[(256, 'nhwc')], Cout=384, stride=1, wino=True),
+    dict(B=6, H=8, W=16, src=[(256, 'nhwc')], Cout=384, stride=1, wino=True,
+         path=('wino2 wino2 wino2', 'general_v2 general_v2 general_v2', 'wino2 wino2 wino2')),
     # >= 128 4x4 tiles: the weight gradient takes the F(4x4,3x3) form too and
     # reuses the forward's transformed input
-    dict(B=8, H=16, W=16, src=[(256, 'nhwc')], Cout=256, stride=1, wino=True),
+    dict(B=8, H=16, W=16, src=[(256, 'nhwc')], Cout=256, stride=1, wino=True,
+         path=('wino4 wino4 wino4', 'general_v2 general_v2 general_v2', 'wino2 wino2 wino2')),
     # large up-sampling layer with a flow member: four-lanes-per-pixel flow-gradient rows
     # and the matrix-core flat-member weight gradient
-    dict(B=8, H=64, W=64, src=[(32, 'nhwc'), (32, 'nhwc'), (2, 'nchw')], Cout=64, up=True),
+    dict(B=8, H=64, W=64, src=[(32, 'nhwc'), (32, 'nhwc'), (2, 'nchw')], Cout=64, up=True,
+         path=('general_v2 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
     # too few tiles: the direct kernel (transformed weights would dominate)
-    dict(B=1, H=8, W=8, src=[(256, 'nhwc')], Cout=256, stride=1),
+    dict(B=1, H=8, W=8, src=[(256, 'nhwc')], Cout=256, stride=1,
+         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
     # the first encoder layer's own kernels (csrc/first.hip: planar input, 64 outputs,
     # 8 x 32-pixel tiles, K = 9 C): ragged tiles in both directions, every column-block
     # count of the weight gradient (K + 1 = 28 .. 145 columns), Mish with its z copy
-    dict(B=2, H=20, W=72, src=[(5, 'nchw')], Cout=64, stride=2, first=True),
-    dict(B=1, H=16, W=64, src=[(12, 'nchw')], Cout=64, stride=2, act='mish', first=True),
-    dict(B=3, H=34, W=18, src=[(9, 'nchw')], Cout=64, stride=2, first=True),
-    dict(B=1, H=8, W=8, src=[(16, 'nchw')], Cout=64, stride=2, first=True),
-    dict(B=1, H=8, W=8, src=[(3, 'nchw')], Cout=64, stride=2, first=True),
-    dict(B=8, H=128, W=128, src=[(5, 'nchw')], Cout=64, stride=2, first=True),   # 256 tiles: one per group
-    # decoder stages whose weight gradient takes the patch-resident f32 kernel
-    # (csrc/wgrad_patch.hip): 64 input channels per workgroup (swapped halves of odd patch
-    # slots), 144 blocks over 64 splits with a flat member beside the vector members
-    dict(B=4, H=32, W=32, src=[(128, 'nhwc'), (128, 'nhwc')], Cout=64, up=True),
-    dict(B=3, H=32, W=48, src=[(64, 'nhwc'), (192, 'nhwc'), (2, 'nchw')], Cout=64, up=True),
+    dict(B=2, H=20, W=72, src=[(5, 'nchw')], Cout=64, stride=2, first=True,
+         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
+    dict(B=1, H=16, W=64, src=[(12, 'nchw')], Cout=64, stride=2, act='mish', first=True,
+         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
+    dict(B=3, H=34, W=18, src=[(9, 'nchw')], Cout=64, stride=2, first=True,
+         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
+    dict(B=1, H=8, W=8, src=[(16, 'nchw')], Cout=64, stride=2, first=True,
+         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
+    dict(B=1, H=8, W=8, src=[(3, 'nchw')], Cout=64, stride=2, first=True,
+         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
+    dict(B=8, H=128, W=128, src=[(5, 'nchw')], Cout=64, stride=2, first=True,
+         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),   # 256 tiles: one per group
+    # decoder stages whose weight gradient takes the patch-resident kernel in the twins mode
+    # (csrc/wgrad_patch.hip, test_wgrad_on_bf16_twins_... below) and, every vector member
+    # 64 | C, the nine-product wgrad_min in exact f32: 64 input channels per workgroup
+    # (swapped halves of odd patch slots), 144 blocks over 64 splits with a flat member
+    # beside the vector members
+    dict(B=4, H=32, W=32, src=[(128, 'nhwc'), (128, 'nhwc')], Cout=64, up=True,
+         path=('fwd_min4 dgrad_min1 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=3, H=32, W=48, src=[(64, 'nhwc'), (192, 'nhwc'), (2, 'nchw')], Cout=64, up=True,
+         path=('general_v2 general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
     # the finest decoder stage with its flow member folded away (two members of 64 -> 32):
     # forward by csrc/fwd_patch.hip (weights in registers, patch in LDS)
-    dict(B=1, H=2, W=16, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),
-    dict(B=3, H=10, W=48, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish'),
-    dict(B=2, H=64, W=64, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),
+    dict(B=1, H=2, W=16, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True,
+         path=('fwd_patch general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=3, H=10, W=48, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish',
+         path=('fwd_patch general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=2, H=62, W=64, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True,
+         path=('fwd_patch general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
     # decoder stages whose exact-f32 forward is the nine-product form (csrc/fwd_min.hip: 4 | H,
     # 16 | W, two NHWC members of multiples of 32 channels): 4-row blocks with the K split over
     # the waves / 8-row blocks, members of different widths, Mish with its pre-activation copy,
     # blocks on every border of the frame, the coarsest benchmark stage's channel counts
-    dict(B=2, H=12, W=32, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish'),
-    dict(B=1, H=8, W=16, src=[(32, 'nhwc'), (96, 'nhwc')], Cout=64, up=True),
-    dict(B=3, H=24, W=48, src=[(64, 'nhwc'), (32, 'nhwc')], Cout=96, up=True, act='none'),
-    dict(B=8, H=16, W=16, src=[(256, 'nhwc'), (256, 'nhwc')], Cout=128, up=True),
-    dict(B=16, H=16, W=32, src=[(32, 'nhwc'), (32, 'nhwc')], Cout=32, up=True),
+    dict(B=2, H=12, W=32, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish',
+         path=('fwd_min4 general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=1, H=8, W=16, src=[(32, 'nhwc'), (96, 'nhwc')], Cout=64, up=True,
+         path=('fwd_min4 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=3, H=24, W=48, src=[(64, 'nhwc'), (32, 'nhwc')], Cout=96, up=True, act='none',
+         path=('fwd_min4 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=8, H=16, W=16, src=[(256, 'nhwc'), (256, 'nhwc')], Cout=128, up=True,
+         path=('fwd_min4 dgrad_min1 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=16, H=64, W=32, src=[(32, 'nhwc'), (32, 'nhwc')], Cout=32, up=True,
+         path=('fwd_min8 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
     # the coarsest and the finest decoder stage EXACTLY as benchmarked (batch 8, 256 x 256
     # input): 512 + 512 -> 256 at 16 x 16 (4-row blocks, K split over the waves, 32 chunks)
     # and 64 + 64 -> 32 at 128 x 128 (8-row blocks, 1 024 workgroups)
-    dict(B=8, H=16, W=16, src=[(512, 'nhwc'), (512, 'nhwc')], Cout=256, up=True),
-    dict(B=8, H=128, W=128, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),
+    dict(B=8, H=16, W=16, src=[(512, 'nhwc'), (512, 'nhwc')], Cout=256, up=True,
+         path=('fwd_min4 dgrad_min1 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    dict(B=8, H=128, W=128, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True,
+         path=('fwd_min8 dgrad_min0 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
 ]
+
+
+# kernels that compute in exact f32 whatever the operand mode (dvsof_conv2d_last_kernel
+# reports mode 0 for them)
+F32_ONLY = {'first', 'general_v1', 'flat_valu', 'fwd_min4', 'fwd_min8', 'dgrad_min0',
+            'dgrad_min1', 'dgrad_min2', 'wgrad_min'}
+
+
+def assert_path(kind, family, mode):
+    """The last conv call of `kind` (0 fwd, 1 dgrad, 2 wgrad) ran `family` in operand mode
+    `mode` (after every fallback; the f32-only kernels report 0, the first layer's forward 3
+    when it wrote the twin of y)."""
+    from dvs_of_training_framework_amd import conv as C
+    fam, m = C.last_kernel(kind)
+    want = mode if family not in F32_ONLY else 3 if (family == 'first' and kind == 0 and mode == 3) else 0
+    assert (C.KERNEL_NAMES[fam], m) == (family, want), (kind, C.KERNEL_NAMES[fam], m, family, want)
 
 
 def build(case, seed=0):
@@ -163,6 +213,9 @@ def test_conv_fwd_dgrad_wgrad(ci, mfma, close=close):
     y, z = C.conv_fwd(desc, w_fwd, b.cuda(), 'cuda',
                       nhwc(res) if res is not None else None, want_z=True,
                       keep_input_transform=bool(case.get('wino')))
+    mi = ['f32', 'bf16', 'bf16x3'].index(mfma)
+    fam = case['path'][mi].split()
+    assert_path(0, fam[0], mi)
     close(from_nhwc(y), y_ref)
     close(from_nhwc(z), z_ref)
     # backward w.r.t. the pre-activation output
@@ -177,18 +230,20 @@ def test_conv_fwd_dgrad_wgrad(ci, mfma, close=close):
         holders.append((buf, lay))
         dsts.append(dict(p=buf))
     C.conv_dgrad(desc, wt, gz_d, dsts)
+    assert_path(1, fam[1], mi)
     for (buf, lay), x in zip(holders, xs):
         close(buf if lay == 'nchw' else from_nhwc(buf), x.grad)
     dw = torch.empty(case['Cout'], o['k'], o['k'], ctot, device='cuda')
     db = torch.empty(case['Cout'], device='cuda')
     C.conv_wgrad(desc, gz_d, dw, db)
+    assert_path(2, fam[2], mi)
     close(dw.permute(0, 3, 1, 2), w.grad)
     close(db, b.grad)
 
 
 @pytest.mark.parametrize('case', [
     dict(B=2, H=16, W=32, src=[(64, 'nhwc')], Cout=64, stride=1),
-    dict(B=3, H=16, W=16, src=[(32, 'nhwc')], Cout=128, stride=2),        # odd number of 16-pixel groups per split
+    dict(B=3, H=32, W=32, src=[(32, 'nhwc')], Cout=128, stride=2),        # odd number of 16-pixel groups per split
     dict(B=2, H=16, W=16, src=[(64, 'nhwc'), (32, 'nhwc'), (2, 'nchw')], Cout=32, up=True),   # sub-pixel phases + a flat member
     dict(B=8, H=64, W=64, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),                # 32 x 128 tile, many K splits
     dict(B=4, H=16, W=16, src=[(256, 'nhwc')], Cout=256, stride=1),                          # direct wide layer (no Winograd in mode 3)
@@ -227,29 +282,41 @@ def test_wgrad_on_bf16_twins_equals_the_operand_mode(case):
     of gout and of the sources through LDS (ds_read_b64_tr_b16 transposed
     fragment reads, K = pixels).  Mode 1 rounds the same f32 values to bf16 in
     registers, so both multiply identical operands: equal up to f32 summation
-    order.  Bias gradient: sums of the bf16-rounded gout (2^-9 per element)."""
+    order.  Bias gradient: sums of the bf16-rounded gout (2^-9 per element).
+    The twins are really read: built from OTHER tensors, the result is mode 1's
+    on those tensors rounded to bf16 (the planar flow member has no twin)."""
     C, xs, w, b, desc, act, o = build(case, seed=11)
     ho, wo = C.out_size(desc)
     g = torch.Generator().manual_seed(5)
     gz = torch.randn(case['B'], case['Cout'], ho, wo, generator=g)
     gz_d = nhwc(gz)
     ctot = sum(c for c, _ in case['src'])
+    fam3 = 'wgrad_patch' if case.get('up') else 'general_v2'
+    alt = [torch.randn(t.shape, generator=g).cuda() if lay == 'nhwc' else t
+           for t, (_, lay) in zip(desc._keepalive, case['src'])]
+    gz_alt = torch.randn(gz_d.shape, generator=g).cuda()
 
-    def run(mode, twins):
+    def run(mode, twins, f32=None, t16=None, gout=None, gout16=None):
+        f32 = desc._keepalive if f32 is None else f32
+        t16 = f32 if t16 is None else t16
         srcs = []
-        for t, (c, lay) in zip(desc._keepalive, case['src']):
-            t16 = t.to(torch.bfloat16) if (twins and lay == 'nhwc') else None
-            srcs.append((t, c, C.NCHW if lay == 'nchw' else C.NHWC, t16))
+        for t, u, (c, lay) in zip(f32, t16, case['src']):
+            u16 = u.to(torch.bfloat16) if (twins and lay == 'nhwc') else None
+            srcs.append((t, c, C.NCHW if lay == 'nchw' else C.NHWC, u16))
         d = C.make_desc(srcs, case['B'], case['H'], case['W'], case['Cout'], o['k'], o['stride'],
                         o['pad'], o['up'], act, mode)
         d._keep = srcs
         dw = torch.empty(case['Cout'], o['k'], o['k'], ctot, device='cuda')
         db = torch.empty(case['Cout'], device='cuda')
-        C.conv_wgrad(d, gz_d, dw, db, gz_d.to(torch.bfloat16) if twins else None)
+        gout = gz_d if gout is None else gout
+        gout16 = gout if gout16 is None else gout16
+        C.conv_wgrad(d, gout, dw, db, gout16.to(torch.bfloat16) if twins else None)
         torch.cuda.synchronize()
         return dw, db
     dw1, db1 = run(C.MFMA_BF16, False)
+    assert_path(2, 'general_v2', 1)
     dw3, db3 = run(C.MFMA_BF16_TWINS, True)
+    assert_path(2, fam3, 3)
     close(dw3, dw1, 1e-5)
     close(db3, db1, 1e-2)
     dw3b, _ = run(C.MFMA_BF16_TWINS, True)
@@ -257,6 +324,17 @@ def test_wgrad_on_bf16_twins_equals_the_operand_mode(case):
     # and both stay within the bf16 bound of the exact gradient
     dwx, _ = run(C.MFMA_F32, False)
     close(dw3, dwx, BF16_RTOL)
+    # twins of other tensors: the vector members' columns follow the twins, the flat ones x
+    dwd, _ = run(C.MFMA_BF16_TWINS, True, t16=alt, gout16=gz_alt)
+    assert_path(2, fam3, 3)
+    rounded = [t.to(torch.bfloat16).float() if lay == 'nhwc' else t
+               for t, (_, lay) in zip(alt, case['src'])]
+    dwr, _ = run(C.MFMA_BF16, False, f32=rounded, gout=gz_alt.to(torch.bfloat16).float())
+    col = 0
+    for t, (c, lay) in zip(alt, case['src']):
+        if lay == 'nhwc':
+            close(dwd[..., col:col + c], dwr[..., col:col + c], 1e-5)
+        col += c
 
 
 @pytest.mark.parametrize('B,H,W,act,cls,want_z', [
@@ -281,20 +359,25 @@ def test_finest_decoder_forward_on_bf16_twins_equals_the_operand_mode(B, H, W, a
     b_cls = (torch.randn(9, 32, generator=g).cuda() * 0.3) if cls else None
     a = {'relu': C.ACT_RELU, 'mish': C.ACT_MISH}[act]
 
-    def run(mode):
+    def run(mode, srcs=(x, sk), twin_srcs=None, w_twin=None, w_f32=w):
         twins = mode == C.MFMA_BF16_TWINS
-        srcs = [(t, 64, C.NHWC, t.to(torch.bfloat16) if twins else None) for t in (x, sk)]
-        d = C.make_desc(srcs, B, H, W, 32, 3, 1, 1, True, a, mode)
-        d._keep = srcs
+        twin_srcs = srcs if twin_srcs is None else twin_srcs
+        s = [(t, 64, C.NHWC, u.to(torch.bfloat16) if twins else None) for t, u in zip(srcs, twin_srcs)]
+        d = C.make_desc(s, B, H, W, 32, 3, 1, 1, True, a, mode)
+        d._keep = s
         if twins:
-            w_f, _, w_f16, _ = C.prepare(d, w, False, want16=True)
+            w_f, _, w_f16, _ = C.prepare(d, w_f32, False, want16=True)
+            if w_twin is not None:      # the twin of another weight's forward form
+                w_f16 = C.prepare(d, w_twin, False, want16=True)[2]
         else:
-            (w_f, _), w_f16 = C.prepare(d, w, False), None
+            (w_f, _), w_f16 = C.prepare(d, w_f32, False), None
         y, z = C.conv_fwd(d, w_f, b, 'cuda', None, want_z=want_z, weight16=w_f16, bias_cls=b_cls)
         torch.cuda.synchronize()
         return y, z, d._y16
     y1, z1, _ = run(C.MFMA_BF16)
+    assert_path(0, 'general_v2', 1)
     y3, z3, y16 = run(C.MFMA_BF16_TWINS)
+    assert_path(0, 'fwd_patch', 3)
     close(y3, y1, 1e-5)
     if want_z:
         close(z3, z1, 1e-5)
@@ -303,6 +386,18 @@ def test_finest_decoder_forward_on_bf16_twins_equals_the_operand_mode(B, H, W, a
     assert torch.equal(y3, y3b)
     yx, _, _ = run(C.MFMA_F32)
     close(y3, yx, BF16_RTOL)
+    # twins of OTHER tensors (sources and weights): the result follows the twins -- mode 1 on
+    # the twins' values (the weight form of w2 rounds to the same bf16 in both)
+    x2, sk2 = (nhwc(torch.randn(B, 64, H, W, generator=g)) for _ in range(2))
+    w2 = wphys(torch.randn(32, 128, 3, 3, generator=g) / (128 * 9) ** 0.5)
+    yd, zd, yd16 = run(C.MFMA_BF16_TWINS, twin_srcs=(x2, sk2), w_twin=w2)
+    assert_path(0, 'fwd_patch', 3)
+    yr, zr, _ = run(C.MFMA_BF16, srcs=(x2.to(torch.bfloat16).float(), sk2.to(torch.bfloat16).float()),
+                    w_f32=w2)
+    close(yd, yr, 1e-5)
+    if want_z:
+        close(zd, zr, 1e-5)
+    assert torch.equal(yd16.view(yd.shape), yd.to(torch.bfloat16))
 
 
 @pytest.mark.parametrize('B,H,W,Cx,Cs,Cout', [
@@ -407,6 +502,7 @@ def test_transposed_conv_layer(B, H, W, Cin, Cout, act):
     w_fwd, w_dg = C.prepare(desc, wphys(w.detach()), True)
     assert w_fwd.numel() == 16 * Cout * Cin and w_dg.numel() == 9 * Cout * Cin
     y, z = C.conv_fwd(desc, w_fwd, b.detach().cuda(), 'cuda', None, want_z=True)
+    assert_path(0, 'transposed', 0)
     close(from_nhwc(z), z_ref)
     close(from_nhwc(y), y_ref)
     gz = torch.randn(z_ref.shape, generator=g)
@@ -414,6 +510,7 @@ def test_transposed_conv_layer(B, H, W, Cin, Cout, act):
     gz_d = nhwc(gz)
     gx = torch.empty(B, H, W, Cin, device='cuda')
     C.conv_dgrad(desc, w_dg, gz_d, [dict(p=gx)])
+    assert_path(1, 'general_v2', 0)       # a plain stride-2 convolution of gout
     close(from_nhwc(gx), x.grad)
     dw = torch.empty(Cout, 3, 3, Cin, device='cuda')
     db = torch.empty(Cout, device='cuda')
@@ -642,3 +739,167 @@ def test_predictor_vs_torch_reference(mish, shape):
     for name, p in net.named_parameters():
         assert p.grad is not None, name
         close(p.grad, state[name].grad, 1e-3)
+
+
+TWIN_LAYERS = [
+    # (case, fwd family, dgrad family): what mode 3 runs in the predictor
+    (dict(B=2, H=32, W=32, src=[(64, 'nhwc')], Cout=128, stride=2), 'general_v2', 'stride2_phased'),
+    (dict(B=2, H=16, W=16, src=[(256, 'nhwc')], Cout=256, stride=1, residual=True),   # no Winograd
+     'general_v2', 'general_v2'),
+    (dict(B=2, H=16, W=16, src=[(64, 'nhwc'), (64, 'nhwc'), (2, 'nchw')], Cout=32, up=True,
+          act='mish'), 'general_v2', 'general_v2'),
+    (dict(B=2, H=16, W=16, src=[(128, 'nhwc'), (128, 'nhwc')], Cout=64, up=True),
+     'general_v2', 'general_v2'),
+]
+
+
+@pytest.mark.parametrize('ci', range(len(TWIN_LAYERS)))
+def test_layer_on_bf16_twins(ci):
+    """Mode 3 (bf16 twins), forward and data gradient of the layers the predictor runs
+    on the general kernels: (a) the kernel ran in mode 3 (no silent fallback to mode 1);
+    (b) equal to mode 1 on the same f32 tensors up to summation order; (c) every twin
+    output is its f32 output rounded to nearest even; (d) twins built from OTHER tensors
+    (sources, gout, weights) are what the vector members read -- the result is mode 1's
+    on the twins' values, the planar flow member reads its f32 tensor; (e) within the
+    bf16 bound of float64.  Data gradient with addend and act'(actsrc) in the epilogue."""
+    from dvs_of_training_framework_amd import conv as C
+    case, ffam, dfam = TWIN_LAYERS[ci]
+    _, xs, w, b, desc, act, o = build(case, seed=40 + ci)
+    B, H, W, Cout = case['B'], case['H'], case['W'], case['Cout']
+    g = torch.Generator().manual_seed(70 + ci)
+    vec = [lay == 'nhwc' for _, lay in case['src']]
+    ho, wo = C.out_size(desc)
+    res = torch.randn(B, Cout, ho, wo, generator=g) if case.get('residual') else None
+    res_d = nhwc(res) if res is not None else None
+    bias = b.cuda()
+    f32 = desc._keepalive
+    alt = [nhwc(torch.randn(x.shape, generator=g)) if v else d for x, d, v in zip(xs, f32, vec)]
+    w2 = torch.randn(w.shape, generator=g) / w[0].numel() ** 0.5
+    rnd = lambda t: t.to(torch.bfloat16).float()          # noqa: E731
+
+    def desc_for(mode, srcs, twins=None):
+        twins = srcs if twins is None else twins
+        s = [(t, c, C.NHWC if v else C.NCHW, u.to(torch.bfloat16) if (mode == 3 and v) else None)
+             for t, u, (c, _), v in zip(srcs, twins, case['src'], vec)]
+        d = C.make_desc(s, B, H, W, Cout, o['k'], o['stride'], o['pad'], o['up'], act, mode)
+        d._keep = s
+        return d
+
+    def fwd(mode, srcs=f32, twins=None, wf=w, w16=None):
+        d = desc_for(mode, srcs, twins)
+        w_f, _, w_f16, _ = C.prepare(d, wphys(wf), True, want16=True)
+        if w16 is not None:
+            w_f16 = C.prepare(d, wphys(w16), True, want16=True)[2]
+        y, z = C.conv_fwd(d, w_f, bias, 'cuda', res_d, want_z=True,
+                          weight16=w_f16 if mode == 3 else None)
+        torch.cuda.synchronize()
+        return y, z, d._y16
+    y1, z1, _ = fwd(C.MFMA_BF16)
+    assert_path(0, ffam, 1)
+    y3, z3, y16 = fwd(C.MFMA_BF16_TWINS)
+    assert_path(0, ffam, 3)                                              # (a)
+    close(y3, y1, 1e-5)                                                  # (b)
+    close(z3, z1, 1e-5)
+    assert torch.equal(y16.view(y3.shape), y3.to(torch.bfloat16))       # (c)
+    yd, zd, yd16 = fwd(C.MFMA_BF16_TWINS, twins=alt, w16=w2)             # (d)
+    assert_path(0, ffam, 3)
+    yr, zr, _ = fwd(C.MFMA_BF16, srcs=[rnd(t) if v else t for t, v in zip(alt, vec)], wf=w2)
+    close(yd, yr, 1e-5)
+    close(zd, zr, 1e-5)
+    assert torch.equal(yd16.view(yd.shape), yd.to(torch.bfloat16))
+    xs64 = [x.double().requires_grad_(True) for x in xs]
+    y_ref, z_ref = torch_fwd(xs64, w.double(), b.double(), o, act, C,
+                             res.double() if res is not None else None)
+    close(from_nhwc(y3), y_ref, BF16_RTOL)                               # (e)
+
+    # data gradient: addend + act' on every member, bf16 twins of the NHWC gradients
+    gz = torch.randn(z_ref.shape, generator=g)
+    gz2 = nhwc(torch.randn(z_ref.shape, generator=g))
+    adds = [torch.randn(x.shape, generator=g) for x in xs]
+    acts = [torch.randn(x.shape, generator=g) for x in xs]
+    dev = lambda t, v: nhwc(t) if v else t.cuda().contiguous()       # noqa: E731
+    adds_d = [dev(t, v) for t, v in zip(adds, vec)]
+    acts_d = [dev(t, v) for t, v in zip(acts, vec)]
+    gz_d = nhwc(gz)
+
+    def dgrad(mode, gout=gz_d, gout16=None, wf=w, w16=None):
+        d = desc_for(mode, f32)
+        _, w_dg, _, w_dg16 = C.prepare(d, wphys(wf), True, want16=True)
+        if w16 is not None:
+            w_dg16 = C.prepare(d, wphys(w16), True, want16=True)[3]
+        bufs, dsts = [], []
+        for x, v, a_, s_ in zip(xs, vec, adds_d, acts_d):
+            p = torch.full(s_.shape, float('nan'), device='cuda')
+            p16 = torch.empty(s_.shape, dtype=torch.bfloat16, device='cuda') if v else None
+            bufs.append((p, p16))
+            dsts.append(dict(p=p, p16=p16, addend=a_, actsrc=s_))
+        g16 = (gout if gout16 is None else gout16).to(torch.bfloat16) if mode == 3 else None
+        C.conv_dgrad(d, w_dg, gout, dsts, C.ACT_RELU, weight16=w_dg16 if mode == 3 else None,
+                     gout16=g16)
+        torch.cuda.synchronize()
+        return bufs
+    g1 = dgrad(C.MFMA_BF16)
+    assert_path(1, dfam, 1)
+    g3 = dgrad(C.MFMA_BF16_TWINS)
+    assert_path(1, dfam, 3)                                              # (a)
+    for (p1, _), (p3, p16), v in zip(g1, g3, vec):
+        close(p3, p1, 1e-5)                                              # (b)
+        if v:
+            assert torch.equal(p16, p3.to(torch.bfloat16))              # (c)
+    gd = dgrad(C.MFMA_BF16_TWINS, gout16=gz2, w16=w2)                    # (d)
+    assert_path(1, dfam, 3)
+    gr = dgrad(C.MFMA_BF16, gout=rnd(gz2), wf=w2)
+    for (pd, pd16), (pr, _), (p3, _), v in zip(gd, gr, g3, vec):
+        if v:
+            close(pd, pr, 1e-5)
+            assert torch.equal(pd16, pd.to(torch.bfloat16))
+        else:   # a planar member's gradient: from the f32 gout and f32 weights (dvsof.h)
+            assert torch.equal(pd, p3)
+    z_ref.backward(gz.double())
+    for (p3, _), x, a_, s_, v in zip(g3, xs64, adds, acts, vec):         # (e)
+        want = (x.grad + a_.double()) * (s_.double() > 0)
+        close(from_nhwc(p3) if v else p3, want, BF16_RTOL)
+
+
+@pytest.mark.parametrize('Cc', [64, 128])
+def test_flow_head_backward_bf16_twin_of_gx(Cc):
+    """dvsof_flow_head_bwd with gx16 (mode 3: the twin the next data gradient reads):
+    the twin is gx rounded to nearest even, gx within 1e-4 of float64."""
+    from dvs_of_training_framework_amd import conv as C
+    B, H, W = 2, 12, 20
+    g = torch.Generator().manual_seed(Cc)
+    x = torch.randn(B, Cc, H, W, generator=g, dtype=torch.float64).float()
+    w = torch.randn(2, Cc, generator=g).float() / Cc ** 0.5
+    gf, gx_in, zsrc = (torch.randn(s, generator=g) for s in ((B, 2, H, W), x.shape, x.shape))
+    want = (torch.einsum('kc,bkyx->bcyx', w.double(), gf.double()) + gx_in.double()) * \
+        (zsrc.double() > 0)
+    gx = torch.full((B, H, W, Cc), float('nan'), device='cuda')
+    gx16 = torch.empty((B, H, W, Cc), dtype=torch.bfloat16, device='cuda')
+    dw, db = torch.empty(2, Cc, device='cuda'), torch.empty(2, device='cuda')
+    C.head_bwd(nhwc(x), w.cuda().contiguous(), gf.cuda(), nhwc(gx_in), nhwc(zsrc), C.ACT_RELU, gx, dw,
+               db, B, H, W, Cc, gx16=gx16)
+    torch.cuda.synchronize()
+    close(from_nhwc(gx), want)
+    assert torch.equal(gx16, gx.to(torch.bfloat16))
+    close(dw, torch.einsum('bkyx,bcyx->kc', gf.double(), x.double()))
+
+
+def test_first_layer_writes_the_bf16_twin_of_y():
+    """csrc/first.hip in mode 3: exact f32 arithmetic, y16 = y rounded (nearest even),
+    the witness reports the twin written."""
+    from dvs_of_training_framework_amd import conv as C
+    case = dict(B=2, H=32, W=48, src=[(5, 'nchw')], Cout=64, stride=2, act='mish')
+    _, xs, w, b, d0, act, o = build(case, seed=9)
+    d = C.make_desc([(d0._keepalive[0], 5, C.NCHW)], 2, 32, 48, 64, 3, 2, 1, False, act, 3)
+    d._keep = d0._keepalive
+    y, z = C.conv_fwd(d, wphys(w), b.cuda(), 'cuda', None, want_z=True)
+    torch.cuda.synchronize()
+    assert_path(0, 'first', 3)
+    assert torch.equal(d._y16.view(y.shape), y.to(torch.bfloat16))
+    y_ref, z_ref = torch_fwd([x.double() for x in xs], w.double(), b.double(), o, act, C)
+    close(from_nhwc(z), z_ref)
+    close(from_nhwc(y), y_ref)
+    d.mfma = C.MFMA_F32
+    yf, _ = C.conv_fwd(d, wphys(w), b.cuda(), 'cuda', None)
+    assert_path(0, 'first', 0)
+    assert torch.equal(yf, y)
