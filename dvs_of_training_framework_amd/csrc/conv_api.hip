@@ -1420,8 +1420,8 @@ int dvsof_flow_head_bwd(const float *x, const float *w, const float *gflow, cons
 
 int dvsof_to_bf16(const float *src, void *dst, size_t n, void *stream)
 {
+    if (n == 0) return DVSOF_OK;      // an empty tensor may have NULL storage
     if (!src || !dst) return DVSOF_EINVAL;
-    if (n == 0) return DVSOF_OK;
     size_t nb = (n + 2047) / 2048;
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), src,
@@ -1438,7 +1438,7 @@ int dvsof_to_bf16_many(const float *const *src, void *const *dst, const size_t *
     Bf16Many J = {};
     size_t blocks = 0;
     for (int i = 0; i < count; ++i) {
-        if (!src[i] || !dst[i]) return DVSOF_EINVAL;
+        if (n[i] && (!src[i] || !dst[i])) return DVSOF_EINVAL;
         J.src[i] = src[i];
         J.dst[i] = (unsigned short *)dst[i];
         J.n[i] = n[i];

@@ -308,7 +308,30 @@ typedef struct {
                  f32 tensor (y16, dst[i].p16, dvsof_flow_head_bwd's gx16); the
                  weight gradient, the heads and the loss keep reading f32.
                  Needs every NHWC source channel count % 32 == 0, else the
-                 call runs as mode 1. */
+                 call runs as mode 1.
+                 Rounding contract (tests/test_gpu_conv_exact.py emulates it
+                 in float64): every product a*b of a pass is
+                   modes 1, 3: RNE_bf16(a) * RNE_bf16(b)
+                   mode 2:     hi(a)hi(b) + hi(a)lo(b) + lo(a)hi(b),
+                               hi = RNE_bf16(a), lo = RNE_bf16(a - hi)
+                 of the f32 operands, accumulated in f32:
+                   forward:  input (every member, planar ones included)
+                             x the forward weight form -- of an up-sampling
+                             layer the sub-pixel phase sums of taps, made in
+                             f32 and then rounded;
+                   data gradient: gout x the data-gradient form (the same
+                             values); the gradient of a planar (NCHW) member
+                             is exact f32 in every mode;
+                   weight gradient: gout x input on the (up-sampled) frame,
+                             the raw taps' sums; the columns of a planar
+                             member are exact f32; the bias gradient sums the
+                             f32 gout (mode 3 with a twin-reading kernel: the
+                             twin, i.e. RNE(gout)).
+                 The f32-only families (dvsof_conv2d_last_kernel reports mode
+                 0) and the Winograd forms, whose mode 2 rounds TRANSFORMED
+                 operands, are outside this list.  Bias, residual, addends,
+                 border-class bias, act / act' and the folded flow head stay
+                 f32 in every mode. */
     void *scratch;        /* device scratch for layers that run as Winograd */
     size_t scratch_bytes; /* F(2x2,3x3) (dvsof_conv2d_scratch_bytes > 0); read by
                              dvsof_conv2d_fwd / _dgrad only, which return
@@ -568,7 +591,10 @@ int dvsof_flow_head_bwd(const float *x, const float *w, const float *gflow,
                         void *stream);
 
 /* dst[i] = bf16(src[i]) (round to nearest even), n elements: the bf16 twins of
- * the prepared weights for mfma mode 3 */
+ * the prepared weights for mfma mode 3.  Bit for bit torch's .to(bfloat16): ties
+ * to even, finite values past the largest bf16 become +-inf, NaN stays NaN,
+ * subnormals are rounded, not flushed.  n == 0 (a NULL pointer allowed) does
+ * nothing; so does a tensor of n == 0 in dvsof_to_bf16_many. */
 int dvsof_to_bf16(const float *src, void *dst, size_t n, void *stream);
 /* up to 16 tensors in ONE launch (host arrays of device pointers / sizes) */
 int dvsof_to_bf16_many(const float *const *host_src, void *const *host_dst,

@@ -6,6 +6,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.conv_cases import (CASES, F32_ONLY, TWIN_LAYERS, WGRAD_TWIN_CASES,  # noqa: F401
+                              assert_path, build, from_nhwc, nhwc, torch_fwd, wphys)
+
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 
@@ -15,163 +18,6 @@ def close(got, want, rtol=RTOL):
     err = (got - want).abs().max().item()
     ref = want.abs().max().item()
     assert err <= rtol * ref + 1e-7, (err, ref)
-
-
-def nhwc(t):   # logical NCHW -> dense NHWC buffer on the GPU
-    return t.permute(0, 2, 3, 1).contiguous().cuda()
-
-
-def from_nhwc(t):
-    return t.permute(0, 3, 1, 2)
-
-
-def wphys(w):  # OIHW -> [O][kh][kw][I] on the GPU
-    return w.permute(0, 2, 3, 1).contiguous().cuda()
-
-
-CASES = [
-    # B, H, W, chans(list, layouts), Cout, k, stride, up, act
-    dict(B=2, H=16, W=16, src=[(5, 'nchw')], Cout=64, stride=2,
-         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
-    dict(B=1, H=13, W=19, src=[(3, 'nchw')], Cout=32, stride=2,
-         path=('general_v1 general_v2 flat_valu', 'general_v1 general_v2 flat_valu', 'general_v1 general_v2 flat_valu')),
-    dict(B=2, H=12, W=20, src=[(64, 'nhwc')], Cout=128, stride=2,
-         path=('general_v2 stride2_phased general_v1', 'general_v2 stride2_phased general_v1', 'general_v2 stride2_phased general_v1')),
-    dict(B=3, H=8, W=8, src=[(32, 'nhwc')], Cout=32, stride=1, residual=True,
-         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
-    dict(B=2, H=8, W=12, src=[(32, 'nhwc'), (16, 'nhwc'), (2, 'nchw')], Cout=32,
-         up=True,
-         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
-    dict(B=1, H=4, W=4, src=[(512, 'nhwc'), (512, 'nhwc')], Cout=256, up=True,
-         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
-    dict(B=2, H=9, W=7, src=[(20, 'nhwc')], Cout=48, stride=1, k=5, pad=2,
-         path=('general_v1 general_v2 general_v1', 'general_v1 general_v2 general_v1', 'general_v1 general_v2 general_v1')),
-    dict(B=2, H=16, W=16, src=[(64, 'nhwc'), (64, 'nhwc'), (2, 'nchw')], Cout=32,
-         up=True, act='mish',
-         path=('general_v2 general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    # wide 3x3 stride-1 layers with enough tiles: Winograd.  F(2x2,3x3) (W % 4 != 0),
-    # forward, data and weight gradient
-    dict(B=4, H=8, W=18, src=[(256, 'nhwc')], Cout=320, stride=1, residual=True, wino=True,
-         path=('wino2 wino2 wino2', 'general_v2 general_v2 general_v1', 'wino2 wino2 wino2')),
-    # F(4x4,3x3) forward / data gradient (64 tiles), F(2x2) weight gradient
-    dict(B=8, H=8, W=16, src=[(320, 'nhwc')], Cout=256, stride=1, act='mish', wino=True,
-         path=('wino4 wino4 wino2', 'general_v2 general_v2 general_v2', 'wino2 wino2 wino2')),
-    # fewer than 64 4x4 tiles: the 2x2 form on a 4-aligned image
-    dict(B=6, H=8, W=16, src=[(256, 'nhwc')], Cout=384, stride=1, wino=True,
-         path=('wino2 wino2 wino2', 'general_v2 general_v2 general_v2', 'wino2 wino2 wino2')),
-    # >= 128 4x4 tiles: the weight gradient takes the F(4x4,3x3) form too and
-    # reuses the forward's transformed input
-    dict(B=8, H=16, W=16, src=[(256, 'nhwc')], Cout=256, stride=1, wino=True,
-         path=('wino4 wino4 wino4', 'general_v2 general_v2 general_v2', 'wino2 wino2 wino2')),
-    # large up-sampling layer with a flow member: four-lanes-per-pixel flow-gradient rows
-    # and the matrix-core flat-member weight gradient
-    dict(B=8, H=64, W=64, src=[(32, 'nhwc'), (32, 'nhwc'), (2, 'nchw')], Cout=64, up=True,
-         path=('general_v2 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    # too few tiles: the direct kernel (transformed weights would dominate)
-    dict(B=1, H=8, W=8, src=[(256, 'nhwc')], Cout=256, stride=1,
-         path=('general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1', 'general_v2 general_v2 general_v1')),
-    # the first encoder layer's own kernels (csrc/first.hip: planar input, 64 outputs,
-    # 8 x 32-pixel tiles, K = 9 C): ragged tiles in both directions, every column-block
-    # count of the weight gradient (K + 1 = 28 .. 145 columns), Mish with its z copy
-    dict(B=2, H=20, W=72, src=[(5, 'nchw')], Cout=64, stride=2, first=True,
-         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
-    dict(B=1, H=16, W=64, src=[(12, 'nchw')], Cout=64, stride=2, act='mish', first=True,
-         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
-    dict(B=3, H=34, W=18, src=[(9, 'nchw')], Cout=64, stride=2, first=True,
-         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
-    dict(B=1, H=8, W=8, src=[(16, 'nchw')], Cout=64, stride=2, first=True,
-         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
-    dict(B=1, H=8, W=8, src=[(3, 'nchw')], Cout=64, stride=2, first=True,
-         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),
-    dict(B=8, H=128, W=128, src=[(5, 'nchw')], Cout=64, stride=2, first=True,
-         path=('first stride2_phased first', 'first stride2_phased first', 'first stride2_phased first')),   # 256 tiles: one per group
-    # decoder stages whose weight gradient takes the patch-resident kernel in the twins mode
-    # (csrc/wgrad_patch.hip, test_wgrad_on_bf16_twins_... below) and, every vector member
-    # 64 | C, the nine-product wgrad_min in exact f32: 64 input channels per workgroup
-    # (swapped halves of odd patch slots), 144 blocks over 64 splits with a flat member
-    # beside the vector members
-    dict(B=4, H=32, W=32, src=[(128, 'nhwc'), (128, 'nhwc')], Cout=64, up=True,
-         path=('fwd_min4 dgrad_min1 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=3, H=32, W=48, src=[(64, 'nhwc'), (192, 'nhwc'), (2, 'nchw')], Cout=64, up=True,
-         path=('general_v2 general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    # the finest decoder stage with its flow member folded away (two members of 64 -> 32):
-    # forward by csrc/fwd_patch.hip (weights in registers, patch in LDS)
-    dict(B=1, H=2, W=16, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True,
-         path=('fwd_patch general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=3, H=10, W=48, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish',
-         path=('fwd_patch general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=2, H=62, W=64, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True,
-         path=('fwd_patch general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    # decoder stages whose exact-f32 forward is the nine-product form (csrc/fwd_min.hip: 4 | H,
-    # 16 | W, two NHWC members of multiples of 32 channels): 4-row blocks with the K split over
-    # the waves / 8-row blocks, members of different widths, Mish with its pre-activation copy,
-    # blocks on every border of the frame, the coarsest benchmark stage's channel counts
-    dict(B=2, H=12, W=32, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish',
-         path=('fwd_min4 general_v2 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=1, H=8, W=16, src=[(32, 'nhwc'), (96, 'nhwc')], Cout=64, up=True,
-         path=('fwd_min4 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=3, H=24, W=48, src=[(64, 'nhwc'), (32, 'nhwc')], Cout=96, up=True, act='none',
-         path=('fwd_min4 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=8, H=16, W=16, src=[(256, 'nhwc'), (256, 'nhwc')], Cout=128, up=True,
-         path=('fwd_min4 dgrad_min1 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=16, H=64, W=32, src=[(32, 'nhwc'), (32, 'nhwc')], Cout=32, up=True,
-         path=('fwd_min8 general_v2 wgrad_patch', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    # the coarsest and the finest decoder stage EXACTLY as benchmarked (batch 8, 256 x 256
-    # input): 512 + 512 -> 256 at 16 x 16 (4-row blocks, K split over the waves, 32 chunks)
-    # and 64 + 64 -> 32 at 128 x 128 (8-row blocks, 1 024 workgroups)
-    dict(B=8, H=16, W=16, src=[(512, 'nhwc'), (512, 'nhwc')], Cout=256, up=True,
-         path=('fwd_min4 dgrad_min1 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-    dict(B=8, H=128, W=128, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True,
-         path=('fwd_min8 dgrad_min0 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
-]
-
-
-# kernels that compute in exact f32 whatever the operand mode (dvsof_conv2d_last_kernel
-# reports mode 0 for them)
-F32_ONLY = {'first', 'general_v1', 'flat_valu', 'fwd_min4', 'fwd_min8', 'dgrad_min0',
-            'dgrad_min1', 'dgrad_min2', 'wgrad_min'}
-
-
-def assert_path(kind, family, mode):
-    """The last conv call of `kind` (0 fwd, 1 dgrad, 2 wgrad) ran `family` in operand mode
-    `mode` (after every fallback; the f32-only kernels report 0, the first layer's forward 3
-    when it wrote the twin of y)."""
-    from dvs_of_training_framework_amd import conv as C
-    fam, m = C.last_kernel(kind)
-    want = mode if family not in F32_ONLY else 3 if (family == 'first' and kind == 0 and mode == 3) else 0
-    assert (C.KERNEL_NAMES[fam], m) == (family, want), (kind, C.KERNEL_NAMES[fam], m, family, want)
-
-
-def build(case, seed=0):
-    from dvs_of_training_framework_amd import conv as C
-    g = torch.Generator().manual_seed(seed)
-    B, H, W = case['B'], case['H'], case['W']
-    k, stride = case.get('k', 3), case.get('stride', 1)
-    pad, up = case.get('pad', 1), case.get('up', False)
-    act = {'relu': C.ACT_RELU, 'mish': C.ACT_MISH, 'none': C.ACT_NONE}[
-        case.get('act', 'relu')]
-    xs = [torch.randn(B, c, H, W, generator=g) for c, _ in case['src']]
-    ctot = sum(c for c, _ in case['src'])
-    w = torch.randn(case['Cout'], ctot, k, k, generator=g) / (ctot * k * k) ** 0.5
-    b = torch.randn(case['Cout'], generator=g)
-    dev = [(x.cuda().contiguous() if lay == 'nchw' else nhwc(x))
-           for x, (_, lay) in zip(xs, case['src'])]
-    srcs = [(d, c, C.NCHW if lay == 'nchw' else C.NHWC)
-            for d, (c, lay) in zip(dev, case['src'])]
-    desc = C.make_desc(srcs, B, H, W, case['Cout'], k, stride, pad, up, act)
-    desc._keepalive = dev   # the descriptor only holds raw pointers
-    return C, xs, w, b, desc, act, dict(k=k, stride=stride, pad=pad, up=up)
-
-
-def torch_fwd(xs, w, b, o, act, C, residual=None):
-    inp = torch.cat(xs, 1)
-    if o['up']:
-        inp = F.interpolate(inp, scale_factor=2, mode='nearest')
-    z = F.conv2d(inp, w, b, stride=o['stride'], padding=o['pad'])
-    if residual is not None:
-        z = z + residual
-    y = F.relu(z) if act == C.ACT_RELU else F.mish(z) if act == C.ACT_MISH else z
-    return y, z
 
 
 # bf16 mode: operands rounded to bf16 (2^-9 relative) inside the MFMA kernels,
@@ -241,42 +87,7 @@ def test_conv_fwd_dgrad_wgrad(ci, mfma, close=close):
     close(db, b.grad)
 
 
-@pytest.mark.parametrize('case', [
-    dict(B=2, H=16, W=32, src=[(64, 'nhwc')], Cout=64, stride=1),
-    dict(B=3, H=32, W=32, src=[(32, 'nhwc')], Cout=128, stride=2),        # odd number of 16-pixel groups per split
-    dict(B=2, H=16, W=16, src=[(64, 'nhwc'), (32, 'nhwc'), (2, 'nchw')], Cout=32, up=True),   # sub-pixel phases + a flat member
-    dict(B=8, H=64, W=64, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),                # 32 x 128 tile, many K splits
-    dict(B=4, H=16, W=16, src=[(256, 'nhwc')], Cout=256, stride=1),                          # direct wide layer (no Winograd in mode 3)
-    # the patch-resident decoder kernel (csrc/wgrad_patch.hip; the 64 x 64 case above too):
-    # 16-pixel rows (every group is its own row: top / bottom / left / right borders in one
-    # group), two output-channel tiles, unequal members, an odd number of groups per split
-    dict(B=3, H=16, W=16, src=[(64, 'nhwc'), (32, 'nhwc')], Cout=64, up=True),
-    dict(B=2, H=8, W=32, src=[(32, 'nhwc')], Cout=32, up=True),
-    dict(B=1, H=16, W=48, src=[(96, 'nhwc'), (32, 'nhwc')], Cout=96, up=True),
-    # 64 input channels per workgroup (members of 64 | C and >= 512 workgroups): 128-byte
-    # pixel slots with the swizzled halves; 144 blocks over 64 splits (empty splits write zeros)
-    dict(B=4, H=32, W=32, src=[(128, 'nhwc'), (128, 'nhwc')], Cout=64, up=True),
-    dict(B=3, H=32, W=48, src=[(64, 'nhwc'), (192, 'nhwc'), (2, 'nchw')], Cout=64, up=True),
-    # the finest decoder stage with its flow member folded away (two members of 64 -> 32):
-    # forward by csrc/fwd_patch.hip (weights in registers, patch in LDS)
-    dict(B=1, H=2, W=16, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),
-    dict(B=3, H=10, W=48, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish'),
-    dict(B=2, H=64, W=64, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),
-    # decoder stages whose exact-f32 forward is the nine-product form (csrc/fwd_min.hip: 4 | H,
-    # 16 | W, two NHWC members of multiples of 32 channels): 4-row blocks with the K split over
-    # the waves / 8-row blocks, members of different widths, Mish with its pre-activation copy,
-    # blocks on every border of the frame, the coarsest benchmark stage's channel counts
-    dict(B=2, H=12, W=32, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, act='mish'),
-    dict(B=1, H=8, W=16, src=[(32, 'nhwc'), (96, 'nhwc')], Cout=64, up=True),
-    dict(B=3, H=24, W=48, src=[(64, 'nhwc'), (32, 'nhwc')], Cout=96, up=True, act='none'),
-    dict(B=8, H=16, W=16, src=[(256, 'nhwc'), (256, 'nhwc')], Cout=128, up=True),
-    dict(B=16, H=16, W=32, src=[(32, 'nhwc'), (32, 'nhwc')], Cout=32, up=True),
-    # the coarsest and the finest decoder stage EXACTLY as benchmarked (batch 8, 256 x 256
-    # input): 512 + 512 -> 256 at 16 x 16 (4-row blocks, K split over the waves, 32 chunks)
-    # and 64 + 64 -> 32 at 128 x 128 (8-row blocks, 1 024 workgroups)
-    dict(B=8, H=16, W=16, src=[(512, 'nhwc'), (512, 'nhwc')], Cout=256, up=True),
-    dict(B=8, H=128, W=128, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True),
-])
+@pytest.mark.parametrize('case', WGRAD_TWIN_CASES)
 def test_wgrad_on_bf16_twins_equals_the_operand_mode(case):
     """mfma mode 3: the vector members' weight gradient streams the bf16 TWINS
     of gout and of the sources through LDS (ds_read_b64_tr_b16 transposed
@@ -739,18 +550,6 @@ def test_predictor_vs_torch_reference(mish, shape):
     for name, p in net.named_parameters():
         assert p.grad is not None, name
         close(p.grad, state[name].grad, 1e-3)
-
-
-TWIN_LAYERS = [
-    # (case, fwd family, dgrad family): what mode 3 runs in the predictor
-    (dict(B=2, H=32, W=32, src=[(64, 'nhwc')], Cout=128, stride=2), 'general_v2', 'stride2_phased'),
-    (dict(B=2, H=16, W=16, src=[(256, 'nhwc')], Cout=256, stride=1, residual=True),   # no Winograd
-     'general_v2', 'general_v2'),
-    (dict(B=2, H=16, W=16, src=[(64, 'nhwc'), (64, 'nhwc'), (2, 'nchw')], Cout=32, up=True,
-          act='mish'), 'general_v2', 'general_v2'),
-    (dict(B=2, H=16, W=16, src=[(128, 'nhwc'), (128, 'nhwc')], Cout=64, up=True),
-     'general_v2', 'general_v2'),
-]
 
 
 @pytest.mark.parametrize('ci', range(len(TWIN_LAYERS)))
