@@ -4,7 +4,7 @@ The reference's loop body (utils/training.py:138-167: batch to device, model,
 loss, ``backward()``, [``optimizer.step()``]) is ~120 kernel launches here; at
 batch 8 the host needs ~2 ms to enqueue what the GPU runs in ~3 ms.
 ``CapturedTrainStep`` records that body once -- voxelise, predictor forward,
-fused loss, the two-stream backward, [gradient exchange, AdamW] -- for a fixed
+fused loss, the two-stream backward, [gradient exchange, optimizer] -- for a fixed
 batch signature (batch size, frame size, event capacity) and replays it:
 
   * inputs live in static device buffers; a batch is copied in, its events
@@ -17,8 +17,10 @@ batch signature (batch size, frame size, event capacity) and replays it:
     scratch comes from the graph's private pool, gradient buckets and
     optimizer tables are the persistent ones the eager warm-up step made;
   * what changes per step is read from device memory: the scheduled learning
-    rate and Adam's bias corrections (``FusedAdamW.advance`` refreshes a
-    3-float table before each replay), so LambdaLR keeps working.
+    rate and what the step count decides -- Adam's bias corrections; RAdam's
+    step size and rectification, Ranger's Lookahead synchronisation (the
+    optimizer's ``advance`` refreshes a 4-float row per parameter group before
+    each replay), so LambdaLR keeps working.
 
 ROLES -- gradient accumulation (utils/options.py:318-325: ``bs // mbs``
 micro-batches per optimizer step, utils/training.py:156-167).  A micro-batch
@@ -57,7 +59,7 @@ import torch
 from . import _lib, voxel
 from .loss import unit_backward
 from .timer import FakeTimer
-from .training import TermReadback, _timed, process_minibatch
+from .training import CAPTURE_PROTOCOL, TermReadback, _timed, process_minibatch
 
 EVENT_KEYS = ('x', 'y', 'timestamp', 'polarity', 'element_index',
               'sample_index')
@@ -220,8 +222,10 @@ class CapturedTrainStep:
         role, accumulation_steps:  see the module docstring
         share:    another CapturedTrainStep of the same signature whose input
                   buffers this one reads (the roles of one loop)"""
-        assert hasattr(optimizer, 'begin_capture'), \
-            'the captured step needs optim.FusedAdamW (device-resident lr table)'
+        assert all(hasattr(optimizer, m) for m in CAPTURE_PROTOCOL), \
+            'the captured step needs an optimizer with begin_capture / advance / ' \
+            'end_capture (optim.FusedAdamW, FusedRAdam, FusedRanger: what changes per ' \
+            'step is read from a device table)'
         assert role in ROLES and (role == 'full') == (accumulation_steps == 1)
         # (optim.fuse_into_backward: the bucket updates are kernels of the capture like any
         # other; under data parallelism each follows its bucket's exchange mark and the

@@ -208,11 +208,22 @@ __device__ __forceinline__ void radam_elem(float &p, float g, float &m, float &v
     }
 }
 
+// dyn (optional, device): {lr, step size, rectified, Lookahead-sync-now} of THIS step, as
+// floats (the two decisions 0 / 1), for a step captured in a hipGraph -- see adamw_kernel.
+// All four are uniform over the launch: on a non-sync step no lane touches the slow buffer.
 __global__ __launch_bounds__(256) void radam_kernel(const uint64_t *__restrict__ ptrs,
                                                     const int64_t *__restrict__ sizes,
                                                     const int32_t *__restrict__ chunks,
-                                                    const RAdamArgs a, const int use_slow)
+                                                    const RAdamArgs a_in, const int use_slow,
+                                                    const float *__restrict__ dyn)
 {
+    RAdamArgs a = a_in;
+    if (dyn) {
+        a.lr = dyn[0];
+        a.step_size = dyn[1];
+        a.rectified = dyn[2] != 0.f;
+        a.lookahead = dyn[3] != 0.f;
+    }
     const int t = chunks[2 * blockIdx.x], c = chunks[2 * blockIdx.x + 1];
     float *p = (float *)ptrs[5 * t + 0];
     const float *g = (const float *)ptrs[5 * t + 1];
@@ -248,11 +259,11 @@ __global__ __launch_bounds__(256) void radam_kernel(const uint64_t *__restrict__
     }
 }
 
-// Gradient centralisation: g[r][:] -= mean(g[r][:]), one workgroup per row.
-__global__ __launch_bounds__(256) void grad_centralize_kernel(float *g, int row_len)
+// Gradient centralisation: row[:] -= mean(row[:]) by one workgroup of 256: per-thread strided
+// double sums, then the wave, then the four waves in a fixed order.
+__device__ __forceinline__ void centralize_row(float *row, int row_len)
 {
     __shared__ double red[4];
-    float *row = g + (size_t)blockIdx.x * row_len;
     double s = 0;
     for (int i = threadIdx.x; i < row_len; i += 256) s += (double)row[i];
     s = wave_sum(s);
@@ -260,6 +271,37 @@ __global__ __launch_bounds__(256) void grad_centralize_kernel(float *g, int row_
     __syncthreads();
     const float mean = (float)(((red[0] + red[1]) + (red[2] + red[3])) / (double)row_len);
     for (int i = threadIdx.x; i < row_len; i += 256) row[i] -= mean;
+}
+
+// g[r][:] -= mean(g[r][:]), one workgroup per row of ONE tensor.
+__global__ __launch_bounds__(256) void grad_centralize_kernel(float *g, int row_len)
+{
+    centralize_row(g + (size_t)blockIdx.x * row_len, row_len);
+}
+
+// The same for the rows of MANY tensors in one launch: rows[2r] = address of row r,
+// rows[2r+1] = its length; one workgroup per row.
+__global__ __launch_bounds__(256) void grad_centralize_multi_kernel(const int64_t *__restrict__ rows)
+{
+    centralize_row((float *)(uint64_t)rows[2 * blockIdx.x], (int)rows[2 * blockIdx.x + 1]);
+}
+
+// What a RAdam / Ranger step takes from the step count, in double like the Python references.
+// degenerate_to_sgd: the flag word of dvsof_radam_step.  step_size -1: no update.
+void radam_rectify(float beta1, float beta2, int step, float nsma_threshold, int degenerate_to_sgd,
+                   int *rectified, float *step_size)
+{
+    const double b2t = pow((double)beta2, (double)step);
+    const double nmax = 2.0 / (1.0 - (double)beta2) - 1.0;
+    const double nsma = nmax - 2.0 * step * b2t / (1.0 - b2t);
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    *rectified = (degenerate_to_sgd & 2) ? nsma >= (double)nsma_threshold   // RAdam: ">="
+                                         : nsma > (double)nsma_threshold;   // Ranger: ">"
+    if (*rectified)
+        *step_size = (float)(sqrt((1.0 - b2t) * (nsma - 4.0) / (nmax - 4.0) * (nsma - 2.0) / nsma *
+                                  nmax / (nmax - 2.0)) / bc1);
+    else
+        *step_size = (degenerate_to_sgd & 1) ? (float)(1.0 / bc1) : -1.f;
 }
 
 }  // namespace
@@ -279,22 +321,51 @@ int dvsof_radam_step(const uint64_t *ptrs, const int64_t *sizes, const int32_t *
     a.beta2 = beta2;
     a.eps = eps;
     a.weight_decay = weight_decay;
-    // rectification term in double, like the Python references
-    const double b2t = pow((double)beta2, (double)step);
-    const double nmax = 2.0 / (1.0 - (double)beta2) - 1.0;
-    const double nsma = nmax - 2.0 * step * b2t / (1.0 - b2t);
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    a.rectified = (degenerate_to_sgd & 2) ? nsma >= (double)nsma_threshold   // RAdam: ">="
-                                          : nsma > (double)nsma_threshold;   // Ranger: ">"
-    if (a.rectified)
-        a.step_size = (float)(sqrt((1.0 - b2t) * (nsma - 4.0) / (nmax - 4.0) * (nsma - 2.0) / nsma *
-                                   nmax / (nmax - 2.0)) / bc1);
-    else
-        a.step_size = (degenerate_to_sgd & 1) ? (float)(1.0 / bc1) : -1.f;
+    radam_rectify(beta1, beta2, step, nsma_threshold, degenerate_to_sgd, &a.rectified, &a.step_size);
     a.lookahead = lookahead_now;
     a.la_alpha = lookahead_alpha;
     hipLaunchKernelGGL(radam_kernel, dim3(num_chunks), dim3(256), 0, as_stream(stream), ptrs, sizes,
-                       chunks, a, lookahead_alpha > 0.f ? 1 : 0);
+                       chunks, a, lookahead_alpha > 0.f ? 1 : 0, (const float *)nullptr);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+void dvsof_radam_dynamic(float lr, float beta1, float beta2, int step, float nsma_threshold,
+                         int degenerate_to_sgd, int lookahead_k, float *host_out4)
+{
+    int rectified = 0;
+    float step_size = 0.f;
+    radam_rectify(beta1, beta2, step, nsma_threshold, degenerate_to_sgd, &rectified, &step_size);
+    host_out4[0] = lr;
+    host_out4[1] = step_size;
+    host_out4[2] = rectified ? 1.f : 0.f;
+    host_out4[3] = (lookahead_k > 0 && step % lookahead_k == 0) ? 1.f : 0.f;
+}
+
+int dvsof_radam_step_dyn(const uint64_t *ptrs, const int64_t *sizes, const int32_t *chunks,
+                         int num_chunks, const float *dyn, float beta1, float beta2, float eps,
+                         float weight_decay, float lookahead_alpha, void *stream)
+{
+    if (!ptrs || !sizes || !chunks || !dyn || num_chunks < 0) return DVSOF_EINVAL;
+    if (num_chunks == 0) return DVSOF_OK;
+    RAdamArgs a = {};   // lr, step_size, rectified, lookahead: from dyn
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.eps = eps;
+    a.weight_decay = weight_decay;
+    a.la_alpha = lookahead_alpha;
+    hipLaunchKernelGGL(radam_kernel, dim3(num_chunks), dim3(256), 0, as_stream(stream), ptrs, sizes,
+                       chunks, a, lookahead_alpha > 0.f ? 1 : 0, dyn);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int dvsof_grad_centralize_multi(const int64_t *rows, int num_rows, void *stream)
+{
+    if (!rows || num_rows < 0) return DVSOF_EINVAL;
+    if (num_rows == 0) return DVSOF_OK;
+    hipLaunchKernelGGL(grad_centralize_multi_kernel, dim3(num_rows), dim3(256), 0, as_stream(stream),
+                       rows);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }

@@ -22,12 +22,19 @@ _lib.register('dvsof_adamw_step_dyn', _i, [_vp, _vp, _vp, _i, _vp, _f, _f, _f,
                                            _f, _i, _vp])
 _lib.register('dvsof_radam_step', _i, [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f,
                                        _i, _f, _i, _i, _f, _vp])
+_lib.register('dvsof_radam_dynamic', None, [_f, _f, _f, _i, _f, _i, _i,
+                                            ctypes.POINTER(_f)])
+_lib.register('dvsof_radam_step_dyn', _i, [_vp, _vp, _vp, _i, _vp, _f, _f, _f,
+                                           _f, _f, _vp])
 _lib.register('dvsof_grad_centralize', _i, [_vp, _i, _i, _vp])
+_lib.register('dvsof_grad_centralize_multi', _i, [_vp, _i, _vp])
 
 
 class _FusedBase(torch.optim.Optimizer):
     """Shared machinery: per-group device tables of {param, grad, state...}
-    pointers, element counts and (tensor, chunk) work items."""
+    pointers, element counts and (tensor, chunk) work items; the protocol of
+    a step captured in a hipGraph (``begin_capture`` / ``advance`` /
+    ``end_capture``: what changes per step travels in a device table)."""
     STATE = ()          # names of the 3 state tensors after param and grad
 
     def __init__(self, params, defaults):
@@ -73,7 +80,12 @@ class _FusedBase(torch.optim.Optimizer):
                     st['step'] = int(st['step'])
         self._tables = {}
 
-    def _table(self, gi, plist):
+    def _extra_table(self, group, plist):
+        """A class's own device table for these tensors (cached and kept alive
+        with the pointer tables); handed to ``_launch`` as ``tables[4]``."""
+        return None
+
+    def _table(self, gi, plist, group=None):
         """Device tables for group gi; rebuilt only when a pointer moved."""
         key = tuple((p.data_ptr(), p.grad.data_ptr()) for p in plist)
         cached = self._tables.get(gi)
@@ -92,11 +104,12 @@ class _FusedBase(torch.optim.Optimizer):
             chunks += [(t, c) for c in range((p.numel() + chunk - 1) // chunk)]
         dev = plist[0].device
         # uint64 pointers travel as int64 bit patterns
-        t_ptrs = torch.tensor([x - (1 << 64) if x >= (1 << 63) else x
-                               for x in ptrs], dtype=torch.int64, device=dev)
+        t_ptrs = torch.tensor([_as_int64(x) for x in ptrs], dtype=torch.int64,
+                              device=dev)
         t_sizes = torch.tensor(sizes, dtype=torch.int64, device=dev)
         t_chunks = torch.tensor(chunks, dtype=torch.int32, device=dev)
-        self._tables[gi] = (key, t_ptrs, t_sizes, t_chunks, len(chunks))
+        self._tables[gi] = (key, t_ptrs, t_sizes, t_chunks, len(chunks),
+                            self._extra_table(group, plist))
         return self._tables[gi][1:]
 
     def _launch(self, group, tables, step, plist):
@@ -114,7 +127,47 @@ class _FusedBase(torch.optim.Optimizer):
                 st['step'] = int(st['step']) + 1
             steps.add(st['step'])
         assert len(steps) == 1, 'tensors of one group step together'
-        self._launch(group, self._table(key, plist), max(steps.pop(), 1), plist)
+        self._launch(group, self._table(key, plist, group), max(steps.pop(), 1), plist)
+
+    # ---- a step captured in a hipGraph (capture.CapturedTrainStep) ---------
+    def _dyn_row(self, group, step, out4):
+        """Fill the host float[4] of ``group`` at step count ``step``."""
+        raise NotImplementedError
+
+    def _dyn_ptr(self, group):
+        gi = next(i for i, g in enumerate(self.param_groups) if g is group)
+        return self._dyn[gi].data_ptr()
+
+    def begin_capture(self, device):
+        """From now on ``step()`` enqueues the dyn-table kernel and leaves the
+        step counters alone (capturing enqueues nothing; ``advance`` counts).
+        The table is allocated once: a captured graph keeps its address."""
+        if getattr(self, '_dyn', None) is None:
+            ng = len(self.param_groups)
+            self._dyn = torch.zeros(ng, 4, dtype=torch.float32, device=device)
+        self._use_dyn = True
+
+    def advance(self):
+        """Before every replay: count the step and refresh the row of every
+        group (one tiny kernel carrying the values as arguments:
+        dvsof_adamw_set_dynamic)."""
+        ng = len(self.param_groups)
+        buf, rows = (ctypes.c_float * 4)(), (ctypes.c_float * (4 * ng))()
+        for gi, group in enumerate(self.param_groups):
+            steps = set()
+            for p in group['params']:
+                st = self._state(p)
+                st['step'] = int(st['step']) + 1
+                steps.add(st['step'])
+            assert len(steps) == 1
+            self._dyn_row(group, steps.pop(), buf)
+            rows[4 * gi:4 * gi + 4] = buf[:]
+        _lib.check(_lib.lib().dvsof_adamw_set_dynamic(
+            self._dyn.data_ptr(), rows, 4 * ng, _lib.stream()), 'dvsof_adamw_set_dynamic')
+
+    def end_capture(self):
+        """Back to eager steps (the table stays: a graph may still use it)."""
+        self._use_dyn = False
 
     # ---- update fused into the backward ------------------------------------
     def fuse_into_backward(self, predictor, flush_at=None):
@@ -186,13 +239,12 @@ class FusedAdamW(_FusedBase):
                                       amsgrad=amsgrad))
 
     def _launch(self, group, tables, step, plist):
-        t_ptrs, t_sizes, t_chunks, n = tables
+        t_ptrs, t_sizes, t_chunks, n = tables[:4]
         b1, b2 = group['betas']
         if getattr(self, '_use_dyn', False):     # captured step: lr and bias corrections from the device table
-            gi = next(i for i, g in enumerate(self.param_groups) if g is group)
             _lib.check(_lib.lib().dvsof_adamw_step_dyn(
                 t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
-                self._dyn[gi].data_ptr(), float(b1), float(b2),
+                self._dyn_ptr(group), float(b1), float(b2),
                 float(group['eps']), float(group['weight_decay']),
                 1 if group['amsgrad'] else 0, _lib.stream()),
                 'dvsof_adamw_step_dyn')
@@ -203,47 +255,54 @@ class FusedAdamW(_FusedBase):
             float(group['weight_decay']), step,
             1 if group['amsgrad'] else 0, _lib.stream()), 'dvsof_adamw_step')
 
-    # ---- a step captured in a hipGraph (capture.CapturedTrainStep) ---------
-    def begin_capture(self, device):
-        """From now on ``step()`` enqueues the dyn-table kernel and leaves the
-        step counters alone (capturing enqueues nothing; ``advance`` counts).
-        The table is allocated once: a captured graph keeps its address."""
-        if getattr(self, '_dyn', None) is None:
-            ng = len(self.param_groups)
-            self._dyn = torch.zeros(ng, 4, dtype=torch.float32, device=device)
-        self._use_dyn = True
-
-    def advance(self):
-        """Before every replay: count the step and refresh {lr, lr/bc1,
-        sqrt(bc2)} of every group (one tiny kernel carrying the values as
-        arguments: dvsof_adamw_set_dynamic)."""
-        ng = len(self.param_groups)
-        buf, rows = (ctypes.c_float * 3)(), (ctypes.c_float * (4 * ng))()
-        for gi, group in enumerate(self.param_groups):
-            steps = set()
-            for p in group['params']:
-                st = self._state(p)
-                st['step'] = int(st['step']) + 1
-                steps.add(st['step'])
-            assert len(steps) == 1
-            b1, b2 = group['betas']
-            _lib.lib().dvsof_adamw_dynamic(float(group['lr']), float(b1),
-                                           float(b2), steps.pop(), buf)
-            rows[4 * gi], rows[4 * gi + 1], rows[4 * gi + 2] = buf[0], buf[1], buf[2]
-        _lib.check(_lib.lib().dvsof_adamw_set_dynamic(
-            self._dyn.data_ptr(), rows, 4 * ng, _lib.stream()), 'dvsof_adamw_set_dynamic')
-
-    def end_capture(self):
-        """Back to eager steps (the table stays: a graph may still use it)."""
-        self._use_dyn = False
+    def _dyn_row(self, group, step, out4):
+        """{lr, lr/bc1, sqrt(bc2), 0}"""
+        b1, b2 = group['betas']
+        out4[3] = 0.0
+        _lib.lib().dvsof_adamw_dynamic(float(group['lr']), float(b1), float(b2),
+                                       step, out4)
 
 
-class FusedRAdam(_FusedBase):
+class _RAdamKind(_FusedBase):
+    """RAdam and Ranger share one kernel; a class says what is constant for a
+    group: ``_consts`` -> (N_sma threshold, flag word of dvsof_radam_step,
+    Lookahead k or 0, Lookahead alpha or 0)."""
+    STATE = ('exp_avg', 'exp_avg_sq', 'slow_buffer')
+
+    def _consts(self, group):
+        raise NotImplementedError
+
+    def _launch(self, group, tables, step, plist):
+        t_ptrs, t_sizes, t_chunks, n = tables[:4]
+        b1, b2 = group['betas']
+        thr, flags, k, alpha = self._consts(group)
+        if getattr(self, '_use_dyn', False):     # captured step: lr, step size and the two decisions from the device table
+            _lib.check(_lib.lib().dvsof_radam_step_dyn(
+                t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
+                self._dyn_ptr(group), float(b1), float(b2),
+                float(group['eps']), float(group['weight_decay']), alpha,
+                _lib.stream()), 'dvsof_radam_step_dyn')
+            return
+        _lib.check(_lib.lib().dvsof_radam_step(
+            t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
+            float(group['lr']), float(b1), float(b2), float(group['eps']),
+            float(group['weight_decay']), step, thr, flags,
+            1 if k and step % k == 0 else 0, alpha, _lib.stream()),
+            'dvsof_radam_step')
+
+    def _dyn_row(self, group, step, out4):
+        """{lr, step size (-1: no update), rectified, Lookahead sync now}"""
+        b1, b2 = group['betas']
+        thr, flags, k, _ = self._consts(group)
+        _lib.lib().dvsof_radam_dynamic(float(group['lr']), float(b1), float(b2),
+                                       step, thr, flags, k, out4)
+
+
+class FusedRAdam(_RAdamKind):
     """Rectified Adam (Liu et al., ICLR 2020) with the defaults of the
     ``RAdam.radam.RAdam`` class the reference builds for ``--optimizer RADAM``
     (train_flownet.py:62-64; upstream submodule absent: parity unpinned,
     oracle/ref_optim.py restates the published algorithm)."""
-    STATE = ('exp_avg', 'exp_avg_sq', 'slow_buffer')
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0, degenerated_to_sgd=True):
@@ -256,23 +315,15 @@ class FusedRAdam(_FusedBase):
         st['exp_avg_sq'] = torch.zeros_like(p)
         st['slow_buffer'] = st['exp_avg']      # unused by the kernel
 
-    def _launch(self, group, tables, step, plist):
-        t_ptrs, t_sizes, t_chunks, n = tables
-        b1, b2 = group['betas']
-        _lib.check(_lib.lib().dvsof_radam_step(
-            t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
-            float(group['lr']), float(b1), float(b2), float(group['eps']),
-            float(group['weight_decay']), step, 5.0,
-            2 | (1 if group['degenerated_to_sgd'] else 0), 0, 0.0,
-            _lib.stream()), 'dvsof_radam_step')
+    def _consts(self, group):
+        return 5.0, 2 | (1 if group['degenerated_to_sgd'] else 0), 0, 0.0
 
 
-class FusedRanger(_FusedBase):
+class FusedRanger(_RAdamKind):
     """Ranger = RAdam + Lookahead (k, alpha) + gradient centralisation, with
     the defaults of lessw2020's ``ranger.Ranger`` which the reference builds
     for its DEFAULT ``--optimizer RANGER`` (train_flownet.py:65-71,
     utils/options.py:254-257; upstream submodule absent: parity unpinned)."""
-    STATE = ('exp_avg', 'exp_avg_sq', 'slow_buffer')
 
     def __init__(self, params, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5,
                  betas=(.95, 0.999), eps=1e-5, weight_decay=0, use_gc=True,
@@ -287,25 +338,46 @@ class FusedRanger(_FusedBase):
         st['exp_avg_sq'] = torch.zeros_like(p)
         st['slow_buffer'] = p.detach().clone()
 
+    def _consts(self, group):
+        return float(group['N_sma_threshhold']), 1, int(group['k']), \
+            float(group['alpha'])
+
+    def _extra_table(self, group, plist):
+        """Row table of the gradient centralisation: {address, length} of
+        every row (everything but dim 0) of every eligible gradient."""
+        if not group['use_gc']:
+            return None, 0
+        gc_dim = 3 if group['gc_conv_only'] else 1
+        return centralize_rows([p.grad for p in plist if p.dim() > gc_dim])
+
     def _launch(self, group, tables, step, plist):
-        lib = _lib.lib()
-        if group['use_gc']:
-            gc_dim = 3 if group['gc_conv_only'] else 1
-            for p in plist:
-                if p.dim() > gc_dim:     # mean over everything but dim 0
-                    assert p.grad.stride() == p.stride()
-                    _lib.check(lib.dvsof_grad_centralize(
-                        p.grad.data_ptr(), p.shape[0], p.numel() // p.shape[0],
-                        _lib.stream()), 'dvsof_grad_centralize')
-        t_ptrs, t_sizes, t_chunks, n = tables
-        b1, b2 = group['betas']
-        _lib.check(lib.dvsof_radam_step(
-            t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
-            float(group['lr']), float(b1), float(b2), float(group['eps']),
-            float(group['weight_decay']), step,
-            float(group['N_sma_threshhold']), 1,
-            1 if step % group['k'] == 0 else 0, float(group['alpha']),
-            _lib.stream()), 'dvsof_radam_step')
+        t_rows, n_rows = tables[4]
+        if n_rows:      # ONE launch for the group's (bucket's) tensors, a workgroup per row
+            _lib.check(_lib.lib().dvsof_grad_centralize_multi(
+                t_rows.data_ptr(), n_rows, _lib.stream()),
+                'dvsof_grad_centralize_multi')
+        super()._launch(group, tables, step, plist)
+
+
+def centralize_rows(grads):
+    """-> (device int64 [rows, 2] of {row address, row length}, rows) for
+    dvsof_grad_centralize_multi: the rows of dim 0 of every tensor in
+    ``grads`` (float32, dim 0 outermost in memory: contiguous or
+    channels_last)."""
+    rows = []
+    for g in grads:
+        assert g.dtype == torch.float32 and g.is_cuda and _dense(g)
+        n = g.numel() // g.shape[0]
+        assert g.shape[0] == 1 or g.stride(0) == n, 'dim 0 must be outermost'
+        rows += [(_as_int64(g.data_ptr() + 4 * r * n), n) for r in range(g.shape[0])]
+    if not rows:
+        return None, 0
+    return torch.tensor(rows, dtype=torch.int64, device=grads[0].device), len(rows)
+
+
+def _as_int64(x):
+    """A uint64 pointer as the int64 of the same bits."""
+    return x - (1 << 64) if x >= (1 << 63) else x
 
 
 def _dense(t):

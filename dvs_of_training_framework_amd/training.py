@@ -239,6 +239,20 @@ class _StepClock:
 
 
 # -------------------------------------------------------------------- loops
+# what capture.CapturedTrainStep asks of an optimizer (optim._FusedBase)
+CAPTURE_PROTOCOL = ('begin_capture', 'advance', 'end_capture')
+
+
+def capture_refusal(optimizer, is_raw):
+    """Why ``train(capture=True)`` cannot replay its steps (None: it can)."""
+    if not all(hasattr(optimizer, m) for m in CAPTURE_PROTOCOL):
+        return (f'optimizer {type(optimizer).__name__} has no begin_capture / advance / '
+                'end_capture (optim.FusedAdamW, FusedRAdam and FusedRanger do)')
+    if not is_raw:
+        return 'is_raw=False batches (preprocessed voxel grids) are not captured'
+    return None
+
+
 def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           evaluator, weights=[0.5, 1, 1], is_raw=True, accumulation_steps=1,
           timers=None, hooks={}, init_step=0, init_samples_passed=0,
@@ -259,7 +273,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                gradient exchange is then issued by the executor).  A batch of
                another signature runs the same body eagerly; more events than
                the captured buffers hold re-records at a larger capacity; if
-               recording fails training continues eagerly
+               recording fails training continues eagerly.  An optimizer
+               without begin_capture / advance / end_capture, or
+               is_raw=False, runs the eager loop and says so on stderr
     """
     if timers is None:
         on_gpu = torch.device(device).type == 'cuda'
@@ -268,7 +284,11 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                        init_samples_passed)
     sums = ScaleSums()
     captured = None
-    if capture and is_raw and hasattr(optimizer, 'begin_capture'):
+    refused = capture_refusal(optimizer, is_raw) if capture else None
+    if refused:
+        import sys
+        print(f'capture: not used, the loop runs eagerly: {refused}', file=sys.stderr)
+    elif capture:
         from .capture import CapturedLoop
         captured = CapturedLoop(model, evaluator, optimizer, weights, device,
                                 accumulation_steps, reducer)

@@ -677,8 +677,37 @@ int dvsof_radam_step(const uint64_t *ptrs, const int64_t *sizes,
                      int step, float nsma_threshold, int degenerate_to_sgd,
                      int lookahead_now, float lookahead_alpha, void *stream);
 
+/*
+ * The same update for a CAPTURED step (see dvsof_adamw_step_dyn): what the
+ * step count and the learning-rate schedule decide is read from `dyn`, device
+ * float[4] = {lr, step size, rectified (0/1), Lookahead-sync-now (0/1)}.  The
+ * two decisions are uniform over the launch: a step that does not synchronise
+ * neither reads nor writes the slow buffer (28 B per parameter, else 36).
+ * dvsof_radam_dynamic fills a HOST float[4] with exactly the values
+ * dvsof_radam_step would use (one code path for the double-precision
+ * rectification term; step size -1 = "no update": un-rectified without
+ * degenerate_to_sgd bit 0), the sync decision being lookahead_k > 0 &&
+ * step % lookahead_k == 0; dvsof_adamw_set_dynamic puts it into `dyn`.
+ */
+void dvsof_radam_dynamic(float lr, float beta1, float beta2, int step,
+                         float nsma_threshold, int degenerate_to_sgd,
+                         int lookahead_k, float *host_out4);
+int dvsof_radam_step_dyn(const uint64_t *ptrs, const int64_t *sizes,
+                         const int32_t *chunks, int num_chunks,
+                         const float *dyn, float beta1, float beta2, float eps,
+                         float weight_decay, float lookahead_alpha,
+                         void *stream);
+
 /* Gradient centralisation (Ranger): grad[r][:] -= mean(grad[r][:]). */
 int dvsof_grad_centralize(float *grad, int rows, int row_len, void *stream);
+/*
+ * The rows of many tensors in one launch (one workgroup per row), bit for bit
+ * what dvsof_grad_centralize gives tensor by tensor.
+ *   rows    device int64[2*num_rows]: {address of the row (float32, contiguous),
+ *           row length}
+ */
+int dvsof_grad_centralize_multi(const int64_t *rows, int num_rows,
+                                void *stream);
 
 /* ------------------------------------------------------------------ *
  * The flow member of a decoder stage in weight space (csrc/flowfold.hip).

@@ -8,6 +8,8 @@
 #   conv [ENV=VAL ...]                per-launch conv table of one step, one stream
 #   variants <name> [<name> ...]      `conv` under variant libraries built by tools/variant.sh
 #   hbm [ENV=VAL ...]                 voxeliser / loss call paths at the BASELINE.json sizes
+#   optim [optim_bench.py args]       Ranger / AdamW step, eager loop against executor replay, f32 and bf16s,
+#                                     then the update and centralisation kernels alone (tools/optim_bench.py)
 #   lossprobe B H W bits...           loss path under the probe build's DVSOF_LOSS_DBG bits
 #   timeline [bench args]             rocprofv3 kernel trace of a short run -> one step per queue
 #   feedtrace [wire|compact]          kernel + memory-copy trace of the train loop fed from host memory
@@ -46,6 +48,9 @@ variants)
   done ;;
 hbm)
   timeout -k 10 300 env "${envs[@]}" python tools/hbm_bench.py 2>&1 | tee $O/hbm.txt ;;
+optim)
+  timeout -k 10 840 env "${envs[@]}" python tools/optim_bench.py "$@" > $O/optim.jsonl 2> $O/optim.err
+  echo "optim rc=$?"; cut -c1-420 $O/optim.jsonl; tail -3 $O/optim.err ;;
 lossprobe)
   B=$1; H=$2; W=$3; shift 3
   for bits in "$@"; do echo -n "DBG=$bits: "; DVSOF_LOSS_DBG=$bits DVSOF_PROBE_LIB=1 timeout -k 10 120 python tools/loss_probe.py $B $H $W 2>&1 | tail -1; done ;;
