@@ -139,7 +139,10 @@ constexpr int VPX_MAX = 1024;
 constexpr int64_t EPT8_FROM = 1 << 21;
 // 16 from ~4 M events: half the bucket-cursor atomics, twice as long record runs per tile
 constexpr int64_t EPT16_FROM = 3 << 20;
-constexpr int V2_MAX_TILES = 8192;    // LDS histogram + base of the bucket pass: 8 bytes per tile (64 KiB)
+// LDS histogram + base of the bucket pass: 8 bytes per tile.  At 8192 tiles that is 64 KiB dynamic
+// + 8 bytes static: measured on gfx950 (160 KiB LDS per workgroup), the launch needs no raised
+// dynamic-LDS limit (tests/test_gpu_voxel_exact.py, tiles8192)
+constexpr int V2_MAX_TILES = 8192;
 
 struct VoxV2 {
     // wire format (int64 columns) ...

@@ -273,7 +273,7 @@ void orc_count_image(const int64_t *x, const int64_t *y, int64_t n, int H, int W
  * VOXEL_SPEC (docs/VOXEL_SPEC.md): polarity-signed event volume, bilinear in
  * time, nearest in space.  For event i of sample b with window [t0_b, t1_b]:
  *   dt = t1-t0;  tn = dt > 0 ? ((t - t0) / dt) * (C-1) : 0          (all fp32)
- *   dropped if t < t0, t > t1, or x,y outside the frame
+ *   dropped unless t0 <= t <= t1 (so a NaN timestamp is dropped), or x,y outside the frame
  *   c0 = (int)floorf(tn), f = tn - c0
  *   V[b,c0,y,x] += s*(1-f);   if (c0+1 < C) V[b,c0+1,y,x] += s*f,  s = sign(p)
  * bin0[i] receives c0 (or -1 when dropped) and lin0[i] the linear index of
@@ -304,7 +304,7 @@ void orc_voxelize(const int64_t *x, const int64_t *y, const float *t,
         if (lin0) lin0[i] = -1;
         if (b < 0 || b >= B || x[i] < 0 || x[i] >= W || y[i] < 0 || y[i] >= H) continue;
         const float ts = t[i];
-        if (ts < t0[b] || ts > t1[b]) continue;
+        if (!(ts >= t0[b] && ts <= t1[b])) continue;    /* also a NaN timestamp */
         const float dt = t1[b] - t0[b];
         const float tn = dt > 0.f ? ((ts - t0[b]) / dt) * (float)(C - 1) : 0.f;
         int c0 = (int)floorf(tn);
