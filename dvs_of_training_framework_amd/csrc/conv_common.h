@@ -19,11 +19,6 @@ constexpr int CONV_NT = 256;  // 4 waves
 constexpr int BK = 16;        // K elements per LDS stage
 constexpr int LDK = BK + 4;   // row stride (floats): conflict-free ds_read_b128
 
-// conv_api.hip: the calling thread's record of what its current dvsof_conv2d_fwd / _dgrad /
-// _wgrad launched (dvsof_conv2d_last_kernel): a launcher notes its DVSOF_KERNEL_* family and
-// the operand mode it ran in, after every fallback, once its kernel is enqueued
-void conv_note_kernel(int family, int mode);
-
 // One member of the (virtual) channel concatenation a conv reads.
 struct GSrc {
     const float *p;

@@ -33,7 +33,7 @@
 // channel tile belongs to: + addend(s), + a folded flow head's term, x act'(actsrc).
 // Finest stage (32 output channels = two chunks): the weights stay in LDS and a
 // workgroup walks the pixel blocks of its channel tile (IPW = 0 below).
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 
 namespace {

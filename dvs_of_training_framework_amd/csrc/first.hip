@@ -26,7 +26,7 @@
 //             bias gradient.  Waves split the tile's pixels, workgroups keep
 //             their accumulators over several tiles, partial sums are added by
 //             a second kernel in FIXED order: bitwise reproducible.
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 
 namespace {

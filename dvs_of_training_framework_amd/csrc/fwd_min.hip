@@ -32,7 +32,7 @@
 // the transposition to pixel-major meet in LDS, 8 lanes store one output
 // pixel's 128 bytes: bias, border-class bias (flow fold), pre-activation copy,
 // activation -- the epilogue of fwd_patch_f32_kernel.
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 
 namespace {

@@ -33,7 +33,7 @@
 //
 // Same products as gconv2_kernel in the bf16-twins mode (bf16 x bf16, f32
 // accumulate); the f32 summation order differs.
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 
 namespace {

@@ -27,7 +27,7 @@
 // double buffered with register prefetch, one barrier per slice.  Lane half
 // h = lane>>5 reads k = 8j + 4h .. +3 as one b128 and feeds 4 consecutive
 // MFMAs; A and B use the same k permutation, so the sum is unchanged.
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 
 namespace {
@@ -443,9 +443,6 @@ __global__ __launch_bounds__(256) void gconv_flat_rows_quad_kernel(const GConvPa
     }
 }
 }  // namespace
-
-bool gconv2_eligible(const GConvParams &P, long long max_src_bytes, long long w_bytes);
-int gconv2_launch(const GConvParams &P, int tile, hipStream_t st);
 
 // Internal entry (not part of the C ABI): picks the tile shape and launches.
 int gconv_launch(const GConvParams &P, int tile_hint, hipStream_t st)

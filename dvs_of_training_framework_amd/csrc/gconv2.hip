@@ -25,7 +25,7 @@
 //
 // Same GConvParams / epilogue semantics as gconv.hip (v1), which stays as the
 // fallback for shapes this kernel does not take (see gconv2_eligible).
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 #include <type_traits>
 

@@ -13,13 +13,9 @@
 // LDS holds [k][row] slices written with ds_write_b128 and read one float per
 // lane (consecutive lanes -> consecutive banks); at 64 cycles per MFMA the
 // reads are far off the critical path.
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdio.h>
 #include <stdlib.h>
-
-size_t wgrad_flat_workspace_floats(const FlatWG *flat, int nflat);
-bool wgrad2_eligible(const WGradParams &P);
-int wgrad2_launch(const WGradParams &P, int tile, int ntiles, hipStream_t st);
 
 
 namespace {
@@ -889,13 +885,6 @@ int pick_tile_and_splits(const WGradParams &P, int *S_out)
 }
 
 }  // namespace
-
-// wgrad_patch.hip: the decoder stages in the bf16-twins mode, input patch resident in LDS
-bool wgrad_patch_shape_ok(const WGradParams &P);
-bool wgrad_patch_eligible(const WGradParams &P);
-int wgrad_patch_splits(const WGradParams &P);
-int wgrad_patch_launch(const WGradParams &P, hipStream_t st);
-bool wgrad_min_ok(const WGradParams &P);  // wgrad_min.hip
 
 // Number of K splits used for this problem (deterministic in the shape).
 int wgrad_splits(const WGradParams &P0, int *tile_out)

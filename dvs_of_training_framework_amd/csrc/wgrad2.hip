@@ -13,7 +13,7 @@
 // scalar (SGPR soffset), the per-lane part of the gout offset is a constant
 // and the per-lane part of the input offset needs only the column bound
 // check (left/right image border) per slice.
-#include "conv_common.h"
+#include "conv_host.h"
 
 namespace {
 constexpr int WNS = 4;  // ring stages

@@ -39,7 +39,7 @@
 // applies G^T . G in registers and writes the 3 x 3 gradient slab
 // [split][Cout][3][3][Cin_tot] that the plain slab reduce consumes -- the
 // layout wgrad_patch's fold writes.
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 
 namespace {

@@ -29,7 +29,7 @@
 // the layout wgrad2 writes (the same fold / bias tail consumes them); K splits
 // are workgroups.  Same products as the twins kernel, f32 summation order
 // differs.
-#include "conv_common.h"
+#include "conv_host.h"
 #include <stdlib.h>
 
 namespace {
@@ -570,11 +570,6 @@ static int wp_channel_tile(const WGradParams &P)
     // bound on the K splits leaves the 64-channel form with 224-256 workgroups
     return 32;
 }
-
-// wgrad_min.hip: the nine-product form of the same gradient (exact f32)
-bool wgrad_min_ok(const WGradParams &P);
-int wgrad_min_splits(const WGradParams &P);
-int wgrad_min_launch(WGradParams &P, hipStream_t st);
 
 // K splits for this kernel: enough workgroups for two per CU
 int wgrad_patch_splits(const WGradParams &P)

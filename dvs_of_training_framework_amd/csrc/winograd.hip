@@ -38,12 +38,7 @@
 // and stay in the 256 MiB memory-side cache between the launches.
 // Accuracy in f32 (tests/test_gpu_conv.py, tools/winograd_error.py): F(2x2) ~1e-6,
 // F(4x4) ~1e-5 of the output peak (direct kernel: ~3e-7); the parity bar is 1e-3.
-#include "conv_common.h"
-
-bool gconv2_eligible(const GConvParams &P, long long max_src_bytes, long long w_bytes);
-int gconv2_launch(const GConvParams &P, int tile, hipStream_t st);
-bool wgrad2_eligible(const WGradParams &P);
-int wgrad2_launch(const WGradParams &P, int tile, int ntiles, hipStream_t st);
+#include "conv_host.h"
 
 namespace {
 
