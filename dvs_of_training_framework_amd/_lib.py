@@ -66,6 +66,14 @@ _SIGNATURES = {
                                     ctypes.POINTER(_i), _i,
                                     ctypes.POINTER(_i)]),
     'dvsof_count_image': (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
+    'dvsof_gt_flow_propagate': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
+                                     _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
+                                     _vp]),
+    'dvsof_flow_error_workspace_bytes': (_sz, [_i, _i, _i]),
+    'dvsof_flow_error': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp,
+                              _sz, _vp]),
+    'dvsof_count_image_batched': (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i,
+                                       _i, _vp, _vp]),
     'dvsof_voxelize_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                 _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'dvsof_voxelize_workspace_bytes': (_sz, [_i64, _i, _i, _i, _i]),

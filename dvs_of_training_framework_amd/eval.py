@@ -1,0 +1,231 @@
+"""Evaluation against ground-truth flow on the device (HIP, csrc/eval.hip;
+arithmetic in docs/EVAL_SPEC.md).
+
+``flow_error_dense`` and ``estimate_corresponding_gt_flow`` keep the
+reference's names and arguments (utils/eval.py:6-50, 84-184): numpy in, numpy
+out, the work done by the kernels.  The batched device functions underneath
+(``propagate``, ``flow_error``, ``count_image_batched``) are what
+``testing.evaluate`` drives; ``plan_gt_steps`` is the host-side part of the
+propagation (which maps, which scale factors) and needs no GPU.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+
+F32, F64 = 0, 1         # DVSOF_EVAL_F32 / DVSOF_EVAL_F64
+DIRECT, PROPAGATE = 1, 0
+CAR_ROWS = 190          # utils/eval.py:18-19: the hood of the car is below
+
+# dvsof_eval_result_t
+RESULT_DTYPE = np.dtype([('sum_ee', '<f8'), ('n_points', '<i8'),
+                         ('n_below', '<i8'), ('pred_max', '<f4'),
+                         ('pred_min', '<f4')])
+assert RESULT_DTYPE.itemsize == 32
+
+
+def plan_gt_steps(gt_timestamps, start, stop):
+    """Which ground-truth maps the interval [start, stop] walks through and
+    by how much of each (utils/eval.py:118-172, literally: searchsorted
+    'right' - 1, the strict ``<`` of the loop, float64 scale factors).
+
+    -> (mode, maps, scales).  PROPAGATE: one entry per ``prop_flow`` call.
+    DIRECT (the interval is shorter than the ground-truth gap it starts in):
+    maps = [k, k], scales = [dt, gt_dt]."""
+    ts = np.asarray(gt_timestamps)
+    k = int(np.searchsorted(ts, start, side='right')) - 1
+    if k < 0:
+        raise ValueError('the interval starts before the first ground-truth '
+                         'timestamp')
+    gap = ts[k + 1] - ts[k]
+    span = stop - start
+    if gap > span:
+        return DIRECT, [k, k], [float(span), float(gap)]
+    # the rest of the gap the interval starts in, whole gaps, a last share
+    maps, scales = [k], [float((ts[k + 1] - start) / gap)]
+    k += 1
+    while ts[k + 1] < stop:
+        maps.append(k)
+        scales.append(1.0)
+        k += 1
+    maps.append(k)
+    scales.append(float((stop - ts[k]) / (ts[k + 1] - ts[k])))
+    return PROPAGATE, maps, scales
+
+
+def step_table(plans, map_offset=0):
+    """Plans of F frames -> the kernel's table: frame_step_begin int32[F+1],
+    step_map int32[S] (minus ``map_offset``, the first map that is on the
+    device), step_scale float64[S], frame_mode int32[F]."""
+    begin = np.zeros(len(plans) + 1, np.int32)
+    begin[1:] = np.cumsum([len(p[1]) for p in plans])
+    maps = np.array([m - map_offset for p in plans for m in p[1]], np.int32)
+    scales = np.array([s for p in plans for s in p[2]], np.float64)
+    mode = np.array([p[0] for p in plans], np.int32)
+    return begin, maps, scales, mode
+
+
+def map_dtype(t):
+    if t.dtype == torch.float32:
+        return F32
+    if t.dtype == torch.float64:
+        return F64
+    raise TypeError(f'ground-truth maps are float32 or float64, not {t.dtype}')
+
+
+class StepTable:
+    """The step table of a batch on the device, sent in ONE copy: the int32
+    parts ride in front of the float64 scales in one byte buffer.  ``begin``,
+    ``maps``, ``scales``, ``mode`` are the device addresses the C ABI takes;
+    F frames, S table entries."""
+
+    def __init__(self, plans, map_offset, device):
+        begin, maps, scales, mode = step_table(plans, map_offset)
+        self.F, self.S = len(plans), len(maps)
+        ints = np.concatenate([begin, mode, maps])
+        pad = (-ints.nbytes) % 8
+        raw = ints.tobytes() + b'\0' * pad + scales.tobytes()
+        self.buffer = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+        base = self.buffer.data_ptr()
+        self.begin = base
+        self.mode = base + 4 * (self.F + 1)
+        self.maps = base + 4 * (2 * self.F + 1)
+        self.scales = base + ints.nbytes + pad
+
+
+def propagate(x_flow, y_flow, plans, window=None, map_offset=0):
+    """x_flow, y_flow: device tensors [K,H,W] (float32 or float64), map
+    ``map_offset + k`` of the sequence at index k; plans: one
+    ``plan_gt_steps`` result per frame; window: (y0, x0, h, w) on the full
+    frame, default the full frame.  -> u, v float32 [F,h,w] on the device."""
+    _lib.require_cuda(x_flow, y_flow)
+    x_flow, y_flow = x_flow.contiguous(), y_flow.contiguous()
+    assert x_flow.dim() == 3 and x_flow.shape == y_flow.shape \
+        and x_flow.dtype == y_flow.dtype
+    K, H, W = x_flow.shape
+    y0, x0, h, w = (0, 0, H, W) if window is None else map(int, window)
+    dev = x_flow.device
+    table = StepTable(plans, map_offset, dev)
+    u = torch.empty(table.F, max(h, 0), max(w, 0), dtype=torch.float32, device=dev)
+    v = torch.empty_like(u)
+    rc = _lib.lib().dvsof_gt_flow_propagate(
+        x_flow.data_ptr(), y_flow.data_ptr(), map_dtype(x_flow), K, H, W,
+        table.begin, table.maps, table.scales, table.mode, table.F, table.S,
+        y0, x0, h, w, u.data_ptr(), v.data_ptr(), _lib.stream())
+    _lib.check(rc, 'dvsof_gt_flow_propagate')
+    return u, v
+
+
+def flow_error(gt_u, gt_v, pred, count=None, max_row=None):
+    """gt_u, gt_v float32 [F,h,w]; pred float32 [F,2,h,w]; count uint32/int32
+    [F,h,w] or None (dense); max_row default h.  -> device uint8 [F,32], one
+    dvsof_eval_result_t per frame (``read_results`` copies it to the host)."""
+    _lib.require_cuda(gt_u, gt_v, pred, count)
+    gt_u, gt_v, pred = gt_u.contiguous(), gt_v.contiguous(), pred.contiguous()
+    for t in (gt_u, gt_v, pred):
+        assert t.dtype == torch.float32
+    F, h, w = gt_u.shape
+    assert gt_v.shape == gt_u.shape and tuple(pred.shape) == (F, 2, h, w), \
+        (gt_u.shape, gt_v.shape, pred.shape)
+    if count is not None:
+        count = count.contiguous()
+        assert tuple(count.shape) == (F, h, w) and count.element_size() == 4
+    max_row = h if max_row is None else int(max_row)
+    lib = _lib.lib()
+    out = torch.empty(F, RESULT_DTYPE.itemsize, dtype=torch.uint8,
+                      device=gt_u.device)
+    nbytes = lib.dvsof_flow_error_workspace_bytes(F, h, w)
+    ws = torch.empty(max(nbytes, 32), dtype=torch.uint8, device=gt_u.device)
+    _lib.check(lib.dvsof_flow_error(
+        gt_u.data_ptr(), gt_v.data_ptr(), pred.data_ptr(), _lib.ptr(count),
+        F, h, w, max_row, out.data_ptr(), ws.data_ptr(), nbytes,
+        _lib.stream()), 'dvsof_flow_error')
+    return out
+
+
+def read_results(results):
+    """Device rows of ``flow_error`` -> numpy structured array [F]
+    (RESULT_DTYPE): the one device-to-host copy of a batch."""
+    return results.cpu().numpy().view(RESULT_DTYPE).reshape(-1)
+
+
+def derive(res):
+    """-> (AEE, percent_AEE) float64 arrays of per-frame results: AEE =
+    sum_ee / n_points (NaN for an empty mask, the reference's mean of
+    nothing), percent_AEE = n_below / (n_points + 1e-5)."""
+    n = res['n_points'].astype(np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        aee = res['sum_ee'] / n
+    return aee, res['n_below'].astype(np.float64) / (n + 1e-5)
+
+
+def count_image_batched(x, y, frame_event_begin, shape, box=None):
+    """x, y: int64 device columns of a batch of frames; frame_event_begin:
+    int64[F+1] (device or host), the first event of every frame; box:
+    (y0, x0, h, w) with EventCrop's semantics (utils/data.py:24-42), default
+    (0, 0) + shape.  Events outside the box are dropped.
+    -> int32 device tensor [F,h,w] holding the uint32 counts."""
+    _lib.require_cuda(x, y)
+    x, y = x.contiguous(), y.contiguous()
+    assert x.dtype == torch.long and y.dtype == torch.long \
+        and x.numel() == y.numel()
+    begin = torch.as_tensor(frame_event_begin, dtype=torch.long) \
+        .to(x.device).contiguous()
+    F = begin.numel() - 1
+    h, w = int(shape[0]), int(shape[1])
+    y0, x0 = (0, 0) if box is None else (int(box[0]), int(box[1]))
+    if box is not None:
+        assert (int(box[2]), int(box[3])) == (h, w), (box, shape)
+    out = torch.empty(max(F, 0), h, w, dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().dvsof_count_image_batched(
+        x.data_ptr(), y.data_ptr(), x.numel(), begin.data_ptr(), F, y0, x0,
+        h, w, out.data_ptr(), _lib.stream()), 'dvsof_count_image_batched')
+    return out
+
+
+def _upload_maps(a, device):
+    a = np.asarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def flow_error_dense(flow_gt, flow_pred, event_img, is_car=False,
+                     is_dense=False, device='cuda'):
+    """utils/eval.py:6-50 on the device: flow_gt, flow_pred [h,w,2],
+    event_img [h,w] event counts -> (AEE, percent_AEE, n_points)."""
+    flow_gt, flow_pred = np.asarray(flow_gt), np.asarray(flow_pred)
+    h, w = flow_gt.shape[:2]
+    with np.errstate(over='ignore'):
+        gt = torch.from_numpy(np.ascontiguousarray(
+            np.moveaxis(flow_gt, 2, 0), dtype=np.float32)).to(device)
+        pred = torch.from_numpy(np.ascontiguousarray(
+            np.moveaxis(flow_pred, 2, 0), dtype=np.float32)).to(device)
+    count = None
+    if not is_dense:
+        mask = np.squeeze(np.asarray(event_img)).reshape(h, w) > 0
+        count = torch.from_numpy(mask.astype(np.int32)[None]).to(device)
+    res = read_results(flow_error(gt[0:1], gt[1:2], pred[None], count,
+                                  min(CAR_ROWS, h) if is_car else h))
+    aee, percent = derive(res)
+    return aee[0], float(percent[0]), int(res['n_points'][0])
+
+
+def estimate_corresponding_gt_flow(x_flow_in, y_flow_in, gt_timestamps,
+                                   start_time, end_time, device='cuda'):
+    """utils/eval.py:84-184 on the device -> (x_shift, y_shift) numpy [H,W].
+    Only the maps the interval touches are uploaded.  The values are the
+    kernel's float32; on the direct-scale branch, where the reference returns
+    the maps' own dtype, they are widened to it."""
+    mode, maps, scales = plan = plan_gt_steps(gt_timestamps, start_time,
+                                              end_time)
+    lo, hi = min(maps), max(maps) + 1
+    H, W = np.squeeze(x_flow_in[lo]).shape
+    xd = _upload_maps(np.reshape(x_flow_in[lo:hi], (hi - lo, H, W)), device)
+    yd = _upload_maps(np.reshape(y_flow_in[lo:hi], (hi - lo, H, W)), device)
+    u, v = propagate(xd, yd, [plan], None, lo)
+    u, v = u[0].cpu().numpy(), v[0].cpu().numpy()
+    if mode == DIRECT:
+        dt = np.result_type(np.asarray(x_flow_in[lo]).dtype, np.float64)
+        return u.astype(dt), v.astype(dt)
+    return u, v

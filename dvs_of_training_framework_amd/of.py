@@ -52,6 +52,18 @@ class OpticalFlow:
                 flow, _, _ = self._net(ev, ts, sidx, self.imsize)
             return self._postprocess(flow, return_all)
 
+    def flow_device(self, events, start, stop):
+        """Same arguments as ``__call__``; -> the finest flow as a DEVICE tensor
+        ``[B,2,H,W]`` (the network's own layout, no copy to the host):
+        what ``testing.evaluate`` hands to the error kernel."""
+        with torch.no_grad():
+            ev, ts, sidx = self._collate(events, start, stop)
+            if self._use_graph:
+                # the graph's output buffer is rewritten by the next replay
+                return self._replay(ev, ts, sidx, len(start))[-1].clone()
+            flow, _, _ = self._net(ev, ts, sidx, self.imsize)
+            return flow[-1].contiguous()
+
     def _replay(self, ev, ts, sidx, B):
         n = ev['x'].numel()
         g = self._graphs.get(B)

@@ -1,0 +1,256 @@
+"""``evaluate`` with the reference's signature (utils/testing.py:10-108), the
+per-frame work done on the device in batches of frames: one batched
+inference, one count-image launch, one ground-truth propagation, one error
+launch and one device-to-host copy per batch (kernels: csrc/eval.hip).
+``frame_generator`` (utils/data.py:139-152), ``read_config`` and
+``ravel_config`` (utils/testing.py:111-153) are restated beside it."""
+import itertools
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import eval as dev_eval
+
+
+def frame_generator(events, frames):
+    """Cut a recording into frames.  events: the columns [x, y, t, p], sorted
+    by t; frames: (start, stop) timestamp pairs.  Yields (columns of the
+    frame, start, stop); a frame holds the events with start < t <= stop."""
+    windows = np.asarray(frames).reshape(-1, 2)
+    cuts = np.searchsorted(events[2], windows, side='right')
+    for (t_begin, t_end), (lo, hi) in zip(windows, cuts):
+        yield [column[lo:hi] for column in events], t_begin, t_end
+
+
+def read_config(filename):
+    """The YAML test grid as a dict; a malformed file raises yaml.YAMLError."""
+    import yaml
+    with open(filename) as stream:
+        return yaml.safe_load(stream)
+
+
+# axes of the test grid, slowest first
+GRID_KEYS = ('start', 'stop', 'step', 'test_shape', 'crop_type', 'is_car')
+
+
+def _grid_axis(key, value):
+    """Values one grid axis runs over: a scalar is an axis of one; a test
+    shape is itself a list, so only a list of lists is an axis of several."""
+    if key != 'test_shape':
+        return value if isinstance(value, list) else [value]
+    if not isinstance(value, list) or not value:
+        raise TypeError(f'test_shape is a [h, w] list or a list of them, not {value!r}')
+    return value if isinstance(value[0], list) else [value]
+
+
+def ravel_config(config):
+    """Every combination of the grid's axes as a namespace with the fields
+    GRID_KEYS, the last axis varying fastest."""
+    axes = [_grid_axis(key, config[key]) for key in GRID_KEYS]
+    for combination in itertools.product(*axes):
+        yield SimpleNamespace(**dict(zip(GRID_KEYS, combination)))
+
+
+def fold_box(fun, frame_shape):
+    """The (y0, x0, h, w) window of a reference-style box crop (an object with
+    a ``.box``, utils/data.py:24-42, 78-86) that lies inside the frame, as
+    ints; None for anything else (applied on the host instead)."""
+    box = getattr(fun, 'box', None)
+    if box is None or len(box) != 4:
+        return None
+    try:
+        y0, x0, h, w = (int(b) for b in box)
+    except (TypeError, ValueError):
+        return None
+    if [y0, x0, h, w] != [b for b in box]:      # fractional boxes: not ours
+        return None
+    H, W = frame_shape
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+        return None
+    return y0, x0, h, w
+
+
+class MapWindow:
+    """The ground-truth maps [lo, hi) of a sequence on the device.  A batch
+    asks for the range its frames touch; maps already there (consecutive
+    batches overlap in at least one) are kept, only the new ones are
+    uploaded.  ``uploaded`` counts maps sent to the device."""
+
+    def __init__(self, x_maps, y_maps, device):
+        self.src = (x_maps, y_maps)
+        self.device = device
+        self.lo = self.hi = 0
+        self.dev = None
+        self.uploaded = 0
+
+    def _send(self, a, dst):
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        dst.copy_(torch.from_numpy(np.ascontiguousarray(a)).reshape(dst.shape))
+
+    def ensure(self, lo, hi):
+        """-> (x, y, map_offset): device tensors [K,H,W] holding at least the
+        maps [lo, hi), the first being map ``map_offset``."""
+        if self.dev is not None and self.lo <= lo and hi <= self.hi:
+            return self.dev[0], self.dev[1], self.lo
+        first = np.asarray(self.src[0][lo])
+        H, W = np.squeeze(first).shape
+        dtype = torch.float32 if first.dtype == np.float32 else torch.float64
+        k_lo, k_hi = max(lo, self.lo), min(hi, self.hi)     # kept maps
+        new = []
+        for src, old in zip(self.src, self.dev or (None, None)):
+            t = torch.empty(hi - lo, H, W, dtype=dtype, device=self.device)
+            if old is not None and k_lo < k_hi:
+                t[k_lo - lo:k_hi - lo].copy_(old[k_lo - self.lo:k_hi - self.lo])
+                if lo < k_lo:
+                    self._send(src[lo:k_lo], t[:k_lo - lo])
+                if k_hi < hi:
+                    self._send(src[k_hi:hi], t[k_hi - lo:])
+            else:
+                self._send(src[lo:hi], t)
+            new.append(t)
+        kept = max(k_hi - k_lo, 0) if self.dev is not None else 0
+        self.uploaded += hi - lo - kept
+        self.dev, self.lo, self.hi = tuple(new), lo, hi
+        return new[0], new[1], lo
+
+
+def _device_of(of):
+    return torch.device(getattr(of, '_device', 'cuda'))
+
+
+def _check_in_frame(x, y, shape):
+    # np.ravel_multi_index of the reference's get_count_image raises for these
+    if x.size and (x.min() < 0 or x.max() >= shape[1] or
+                   y.min() < 0 or y.max() >= shape[0]):
+        raise ValueError('invalid entry in coordinates array')
+
+
+def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
+                    pred_postproc_fun=None, gt_proc_fun=None, is_car=False,
+                    batch_size=8, fold=True):
+    """The per-frame results behind ``evaluate``: a numpy structured array
+    (eval.RESULT_DTYPE: sum_ee, n_points, n_below, pred_max, pred_min), one
+    row per frame.  fold=False applies box crops on the host like any other
+    callable (same results; for tests)."""
+    device = _device_of(of)
+    frames = np.array(frames)
+    if frames.size == 0:
+        return np.zeros(0, dev_eval.RESULT_DTYPE)
+    frames = frames.reshape(-1, 2)
+    batch_size = max(int(batch_size), 1)
+    t = events[2]
+    idx = np.searchsorted(t, frames.ravel(), side='right').reshape(-1, 2)
+    xg, yg, ts = gt['x_flow_dist'], gt['y_flow_dist'], gt['timestamps']
+    H, W = np.squeeze(xg[0]).shape
+    gt_box = fold_box(gt_proc_fun, (H, W)) if fold else None
+    ev_box = fold_box(event_preproc_fun, (H, W)) if fold else None
+    post_box = None
+    maps = MapWindow(xg, yg, device)
+    out = []
+    for b0 in range(0, len(frames), batch_size):
+        fr = frames[b0:b0 + batch_size]
+        starts, stops = list(fr[:, 0]), list(fr[:, 1])
+        raw = [[p[i0:i1] for p in events] for i0, i1 in idx[b0:b0 + batch_size]]
+        # events as the network sees them (utils/testing.py:66)
+        if event_preproc_fun is None:
+            evs = [np.array(e) for e in raw]
+        else:
+            evs = [event_preproc_fun(np.array(e).T).T for e in raw]
+
+        # one batched inference -> pred [F,2,h,w] on the device
+        if hasattr(of, 'flow_device'):
+            pred = of.flow_device(evs, starts, stops)
+        else:
+            pred = torch.from_numpy(np.ascontiguousarray(np.transpose(
+                np.asarray(of(evs, starts, stops), dtype=np.float32),
+                (0, 3, 1, 2)))).to(device)
+        if pred_postproc_fun is not None:
+            if fold:
+                post_box = fold_box(pred_postproc_fun, pred.shape[-2:])
+            if post_box is not None:
+                y0, x0, h, w = post_box
+                pred = pred[:, :, y0:y0 + h, x0:x0 + w]
+            else:
+                host = np.transpose(pred.cpu().numpy(), (0, 2, 3, 1))
+                host = np.stack([pred_postproc_fun(f) for f in host])
+                pred = torch.from_numpy(np.ascontiguousarray(np.transpose(
+                    host, (0, 3, 1, 2)), dtype=np.float32)).to(device)
+        pred = pred.to(torch.float32).contiguous()
+
+        # ground truth over each frame's interval
+        plans = [dev_eval.plan_gt_steps(ts, a, b) for a, b in zip(starts, stops)]
+        lo = min(min(p[1]) for p in plans)
+        hi = max(max(p[1]) for p in plans) + 1
+        xd, yd, off = maps.ensure(lo, hi)
+        if gt_proc_fun is None or gt_box is not None:
+            gt_u, gt_v = dev_eval.propagate(xd, yd, plans, gt_box, off)
+        else:
+            u, v = dev_eval.propagate(xd, yd, plans, None, off)
+            u, v = u.cpu().numpy(), v.cpu().numpy()
+            host = np.stack([gt_proc_fun(np.dstack((a, b)))
+                             for a, b in zip(u, v)])
+            gt_u = torch.from_numpy(np.ascontiguousarray(host[..., 0])).to(device)
+            gt_v = torch.from_numpy(np.ascontiguousarray(host[..., 1])).to(device)
+        h, w = gt_u.shape[-2:]
+
+        # event mask: count image of the frame's events
+        if ev_box is not None and ev_box[2:] == (h, w):
+            cols, box = raw, ev_box         # the kernel drops and shifts
+        else:
+            cols, box = evs, None
+            for e in evs:
+                _check_in_frame(np.asarray(e[0]).astype(np.int64),
+                                np.asarray(e[1]).astype(np.int64), (h, w))
+        begin = np.zeros(len(cols) + 1, np.int64)
+        begin[1:] = np.cumsum([len(e[0]) for e in cols])
+        xy = np.empty((2, begin[-1]), np.int64)
+        for e, i0, i1 in zip(cols, begin[:-1], begin[1:]):
+            xy[0, i0:i1] = np.asarray(e[0]).astype(int)
+            xy[1, i0:i1] = np.asarray(e[1]).astype(int)
+        xy = torch.from_numpy(xy).to(device)
+        count = dev_eval.count_image_batched(xy[0], xy[1], begin, (h, w), box)
+
+        res = dev_eval.flow_error(gt_u, gt_v, pred, count,
+                                  min(dev_eval.CAR_ROWS, h) if is_car else h)
+        out.append(dev_eval.read_results(res))      # the batch's one copy back
+    return np.concatenate(out)
+
+
+def evaluate(of, events, frames, gt, event_preproc_fun=None,
+             pred_postproc_fun=None, gt_proc_fun=None, is_car=False,
+             log=False, batch_size=8):
+    """Quality of the optical flow ``of`` on a sequence: (mean AEE, mean share
+    of pixels with an endpoint error under 3 px) over the frames, like the
+    reference's ``evaluate``.
+
+    of: ``OpticalFlow`` (its ``flow_device`` keeps the flow on the device) or
+    any callable with the reference contract (events, start, stop) -> numpy
+    [B,H,W,2]; events: [x, y, t, p] sorted by t; frames: [(start, stop)];
+    gt: dict with 'timestamps', 'x_flow_dist', 'y_flow_dist'.  The three
+    optional functions pre-/post-process events [n,4], predicted flow [H,W,2]
+    and ground-truth flow [H,W,2]; box crops (objects with ``.box``) are
+    folded into the kernels.  batch_size: frames per launch (the reference
+    runs one)."""
+    rows = evaluate_frames(of, events, frames, gt, event_preproc_fun,
+                           pred_postproc_fun, gt_proc_fun, is_car, batch_size)
+    if len(rows) == 0:
+        raise ValueError('evaluate needs at least one frame')
+    aee, percent = dev_eval.derive(rows)
+    # running sums in frame order, so that a NaN (a frame without a counted
+    # pixel) spoils the mean from there on, as it does in the reference
+    count = np.arange(1, len(rows) + 1)
+    mean_aee, mean_percent = np.cumsum(aee) / count, np.cumsum(percent) / count
+    if log:
+        mean_max = np.cumsum(rows['pred_max'], dtype=np.float64) / count
+        mean_min = np.cumsum(rows['pred_min'], dtype=np.float64) / count
+        for k in range(99, len(rows), 100):
+            print(f'[{k + 1} frames] AEE {mean_aee[k]:.2f}  share under 3 px '
+                  f'{mean_percent[k]:.2f}  points in the last frame '
+                  f'{rows["n_points"][k]}  flow range {mean_min[k]:.2f} .. '
+                  f'{mean_max[k]:.2f} (means over the frames so far)')
+        print(f'done: {len(rows)} frames, AEE {mean_aee[-1]:.6f}, '
+              f'share under 3 px {mean_percent[-1]:.6f}')
+    return float(mean_aee[-1]), float(mean_percent[-1])

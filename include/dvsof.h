@@ -155,6 +155,84 @@ int dvsof_augment_events(const int64_t *x, const int64_t *y,
                          int64_t *x_out, int64_t *y_out, void *stream);
 
 /* ------------------------------------------------------------------ *
+ * Evaluation against ground-truth flow (csrc/eval.hip, docs/EVAL_SPEC.md):
+ * the per-frame body of evaluate, utils/testing.py:64-93, for a BATCH of F
+ * frames per launch.
+ * ------------------------------------------------------------------ */
+
+/*
+ * Ground-truth flow over each frame's interval.  Replaces
+ * estimate_corresponding_gt_flow / prop_flow, utils/eval.py:53-184.
+ *   x_flow, y_flow     [K,H,W] displacement maps, float32 (DVSOF_EVAL_F32) or
+ *                      float64 (DVSOF_EVAL_F64, what MVSEC stores); inf allowed;
+ *                      H, W <= 32767
+ *   frame_step_begin   int32[F+1]: steps of frame f are [begin[f], begin[f+1])
+ *   step_map           int32[S]: map index of every step (0 <= index < K; a step
+ *                      with another index samples 0)
+ *   step_scale         double[S]: scale factor of every step
+ *   frame_mode         int32[F]: 0 = propagate through the steps; 1 = direct
+ *                      scale (utils/eval.py:127-128): TWO table entries naming
+ *                      the same map, step_scale = {dt, gt_dt},
+ *                      result = (float)((flow * dt) / gt_dt) in float64
+ *   (y0, x0, h, w)     output window on the full frame: pixel (i, j) starts at
+ *                      (x0 + j, y0 + i), i.e. propagate on the full frame, then
+ *                      crop; DVSOF_EINVAL when it leaves the frame
+ *   u, v               float32[F,h,w]
+ * Per step: ix = rint(x), iy = rint(y) (ties to even; outside the map, beyond
+ * the int16 range or not finite: the sample is 0), a sampled 0 clears that
+ * component's mask for good, x = (float)((double)x + (double)fx * scale);
+ * u = x - x_start or 0 where the mask is cleared.
+ */
+#define DVSOF_EVAL_F32 0
+#define DVSOF_EVAL_F64 1
+int dvsof_gt_flow_propagate(const void *x_flow, const void *y_flow,
+                            int flow_dtype, int K, int H, int W,
+                            const int32_t *frame_step_begin,
+                            const int32_t *step_map, const double *step_scale,
+                            const int32_t *frame_mode, int F, int S, int y0,
+                            int x0, int h, int w, float *u, float *v,
+                            void *stream);
+
+/* one row per frame, 32 bytes */
+typedef struct {
+    double sum_ee;    /* sum of the endpoint errors of the counted pixels */
+    int64_t n_points; /* counted pixels */
+    int64_t n_below;  /* ... with an endpoint error < 3 */
+    float pred_max;   /* max / min of the prediction over the whole [2,h,w] */
+    float pred_min;   /* window (a NaN wins, as in numpy) */
+} dvsof_eval_result_t;
+
+/*
+ * Masked endpoint error.  Replaces flow_error_dense, utils/eval.py:6-50.
+ *   gt_u, gt_v   float32[F,h,w]
+ *   pred         float32[F,2,h,w], the model's NCHW output
+ *   count        uint32[F,h,w] event counts, or NULL (is_dense)
+ *   max_row      rows >= max_row are not counted (is_car: min(190, h), else h)
+ * A pixel counts when count > 0, neither ground-truth component is infinite
+ * and sqrt(u^2 + v^2) > 0 in float32; EE = sqrt(du^2 + dv^2) in float32, summed
+ * in float64 in a fixed order (per-block partials in `workspace`, then one
+ * closing pass; no floating-point atomics): same input, same bits.
+ */
+size_t dvsof_flow_error_workspace_bytes(int F, int h, int w);
+int dvsof_flow_error(const float *gt_u, const float *gt_v, const float *pred,
+                     const uint32_t *count, int F, int h, int w, int max_row,
+                     dvsof_eval_result_t *result, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/*
+ * dvsof_count_image for F frames at once: events [begin[f], begin[f+1]) of the
+ * columns x, y (n_events entries) belong to frame f.  (y0, x0, h, w) is a crop
+ * box with the semantics of EventCrop, utils/data.py:24-42: events outside it
+ * are dropped, the rest shifted by (x0, y0).  out uint32[F,h,w] is zeroed by
+ * the call.
+ */
+int dvsof_count_image_batched(const int64_t *x, const int64_t *y,
+                              int64_t n_events,
+                              const int64_t *frame_event_begin, int F, int y0,
+                              int x0, int h, int w, uint32_t *out,
+                              void *stream);
+
+/* ------------------------------------------------------------------ *
  * Multi-scale warp / Charbonnier / smoothness / out-of-border loss
  * ------------------------------------------------------------------ */
 

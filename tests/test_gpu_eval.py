@@ -1,0 +1,372 @@
+"""Device evaluation (csrc/eval.hip, eval.py, testing.py) against the
+reference-generated goldens of tools/make_goldens_eval.py and the float64
+restatement of tests/eval_cases.py; arithmetic and tolerances in
+docs/EVAL_SPEC.md.  Propagation and counts are bitwise / exact; AEE carries
+the float32 rounding of each endpoint error only."""
+import numpy as np
+import pytest
+import torch
+
+from dvs_of_training_framework_amd import _lib, testing
+from dvs_of_training_framework_amd import eval as dev_eval
+from tests import eval_cases as ec
+from tests.conftest import load_golden
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+
+
+@pytest.fixture(scope='module')
+def golden():
+    return load_golden('eval_reference')
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+# ---------------------------------------------------------------------------
+# propagation
+# ---------------------------------------------------------------------------
+def prop_plans(golden):
+    return [dev_eval.plan_gt_steps(golden['prop_ts'], a, b) for a, b in golden['prop_frames']]
+
+
+@pytest.mark.parametrize('crop', [False, True], ids=['full', 'window'])
+@pytest.mark.parametrize('dtype', [np.float32, np.float64], ids=['f32', 'f64'])
+@pytest.mark.parametrize('shape', ec.SHAPES, ids=lambda s: f'{s[0]}x{s[1]}')
+def test_propagation_matches_the_reference_bitwise(golden, shape, dtype, crop):
+    key = ec.prop_key(shape, dtype)
+    xm, ym = dev(golden[f'{key}_x']), dev(golden[f'{key}_y'])
+    plans = prop_plans(golden)
+    assert [p[0] for p in plans] == [1, 0, 0, 0, 0]
+    window = ec.WINDOWS[shape] if crop else None
+    y0, x0, h, w = window or (0, 0) + shape
+    if crop:    # odd corner, touching the right and the bottom edge
+        assert y0 % 2 == 1 and x0 % 2 == 1 and (y0 + h, x0 + w) == shape
+    u, v = dev_eval.propagate(xm, ym, plans, window)
+    u, v = u.cpu().numpy(), v.cpu().numpy()
+    assert u.shape == v.shape == (len(plans), h, w) and u.dtype == np.float32
+    classes = set()
+    for f in range(len(plans)):
+        for got, name in ((u[f], 'u'), (v[f], 'v')):
+            # the direct-scale golden is float64 (the reference's type): one rounding
+            want = golden[f'{key}_{name}{f}'][y0:y0 + h, x0:x0 + w].astype(np.float32)
+            assert ec.same_bits(got, want), (key, name, f, np.argwhere(bits(got) != bits(want))[:5])
+            classes |= {'inf'} if np.isinf(want).any() else set()
+            classes |= {'masked'} if (want == 0).any() else set()
+    assert 'masked' in classes and (crop or 'inf' in classes)
+    # all frames in one launch == one launch per frame
+    for f, plan in enumerate(plans):
+        u1, v1 = dev_eval.propagate(xm, ym, [plan], window)
+        assert np.array_equal(bits(u1[0].cpu().numpy()), bits(u[f]))
+        assert np.array_equal(bits(v1[0].cpu().numpy()), bits(v[f]))
+
+
+def test_propagation_reads_maps_through_the_offset(golden):
+    """Only the maps a batch touches need to be on the device."""
+    key = ec.prop_key((37, 70), np.float64)
+    x, y = golden[f'{key}_x'], golden[f'{key}_y']
+    plans = prop_plans(golden)[2:3]                 # maps 4, 5
+    u0, v0 = dev_eval.propagate(dev(x), dev(y), plans)
+    u1, v1 = dev_eval.propagate(dev(x[4:]), dev(y[4:]), plans, None, 4)
+    assert torch.equal(u0, u1) and torch.equal(v0, v1)
+
+
+@pytest.mark.parametrize('f', [0, 4], ids=['direct', 'three_gaps'])
+def test_reference_shaped_estimate_corresponding_gt_flow(golden, f):
+    key = ec.prop_key((12, 20), np.float64)
+    start, stop = golden['prop_frames'][f]
+    u, v = dev_eval.estimate_corresponding_gt_flow(
+        golden[f'{key}_x'], golden[f'{key}_y'], golden['prop_ts'], start, stop)
+    want_u, want_v = golden[f'{key}_u{f}'], golden[f'{key}_v{f}']
+    assert u.dtype == want_u.dtype and v.dtype == want_v.dtype     # f64 direct, f32 propagated
+    assert ec.same_bits(u.astype(np.float32), want_u.astype(np.float32))
+    assert ec.same_bits(v.astype(np.float32), want_v.astype(np.float32))
+
+
+# ---------------------------------------------------------------------------
+# endpoint error
+# ---------------------------------------------------------------------------
+def error_inputs(golden, case):
+    gt, pred = golden[f'err_{case}_gt'], golden[f'err_{case}_pred']
+    return gt, pred, golden[f'err_{case}_count'].astype(np.int32)
+
+
+def launch_error(gt, pred, count, is_car, is_dense):
+    h = gt.shape[0]
+    res = dev_eval.flow_error(
+        dev(gt[None, ..., 0]), dev(gt[None, ..., 1]), dev(np.moveaxis(pred, 2, 0)[None]),
+        None if is_dense else dev(count[None]), min(190, h) if is_car else h)
+    return dev_eval.read_results(res)
+
+
+@pytest.mark.parametrize('variant', ec.ERROR_VARIANTS, ids=lambda v: v[0])
+@pytest.mark.parametrize('case', [c[0] for c in ec.ERROR_CASES])
+def test_flow_error_matches_restatement_and_reference(golden, case, variant):
+    vname, is_car, is_dense = variant
+    gt, pred, count = error_inputs(golden, case)
+    h, w = gt.shape[:2]
+    assert (count == 0).mean() > 0.4 and np.isinf(gt).any()
+    assert (~gt.any(axis=2)).any()                       # zero vectors
+    # the inputs keep the counts exact and the tolerances meaningful
+    ee = ec.endpoint_error64(gt, pred)
+    fin = np.isfinite(ee)
+    assert (np.abs(ee[fin] - 3.0) >= 1e-3).all()
+    assert ee[fin].mean() >= 0.1 * np.linalg.norm(gt.astype(np.float64), axis=2)[fin].mean()
+
+    want_aee, want_pct, want_n = ec.flow_error64(gt, pred, count, is_car, is_dense)
+    ref_aee, ref_pct, ref_n = golden[f'err_{case}_{vname}']
+    m = ec.error_mask(gt, count, is_car, is_dense)
+    want_below = int((ee[m] < 3.0).sum())
+
+    res = launch_error(gt, pred, count, is_car, is_dense)
+    again = launch_error(gt, pred, count, is_car, is_dense)
+    aee, pct = dev_eval.derive(res)
+    print(case, vname, 'n', res['n_points'][0], 'below', res['n_below'][0], 'AEE', aee[0],
+          'restated', want_aee, 'reference', ref_aee)
+    assert res['n_points'][0] == want_n == int(ref_n)
+    assert res['n_below'][0] == want_below
+    assert abs(pct[0] - want_below / (want_n + 1e-5)) <= 1e-12
+    assert abs(pct[0] - ref_pct) <= 1e-12
+    if want_n == 0:
+        assert case == 'empty' and np.isnan(aee[0]) and np.isnan(ref_aee) and pct[0] == 0.0
+        assert res['sum_ee'][0] == 0.0
+    else:
+        assert abs(aee[0] - want_aee) <= 1e-6 * want_aee
+        assert abs(aee[0] - ref_aee) <= 5e-6 * ref_aee
+    assert res['sum_ee'].tobytes() == again['sum_ee'].tobytes()
+    assert res['pred_max'][0] == pred.max() and res['pred_min'][0] == pred.min()
+    if case == '260x346':       # is_car cuts real rows here, min(190, h) = h on the small shapes
+        assert (want_n < ec.flow_error64(gt, pred, count, False, is_dense)[2]) == is_car
+
+
+def test_flow_error_batch_equals_single_frames(golden):
+    """Three frames of one shape in one launch, the empty one in the middle."""
+    cases = ['37x70', 'empty', '37x70']
+    ins = [error_inputs(golden, c) for c in cases]
+    ins[2] = (ins[2][0], ins[2][1][::-1].copy(), ins[2][2])       # another prediction
+    gt = np.stack([i[0] for i in ins])
+    pred = np.stack([np.moveaxis(i[1], 2, 0) for i in ins])
+    count = np.stack([i[2] for i in ins])
+    res = dev_eval.read_results(dev_eval.flow_error(
+        dev(gt[..., 0]), dev(gt[..., 1]), dev(pred), dev(count)))
+    singles = np.concatenate([launch_error(*i, False, False) for i in ins])
+    assert res.tobytes() == singles.tobytes()
+    assert res['n_points'][1] == 0 and res['n_points'][0] > 0
+
+
+def test_reference_shaped_flow_error_dense(golden):
+    gt, pred, count = error_inputs(golden, '260x346')
+    aee, pct, n = dev_eval.flow_error_dense(gt, pred, count.astype(np.uint64), is_car=True)
+    ref_aee, ref_pct, ref_n = golden['err_260x346_car']
+    assert isinstance(pct, float) and isinstance(n, int)
+    assert n == int(ref_n) and abs(pct - ref_pct) <= 1e-12 and abs(aee - ref_aee) <= 5e-6 * ref_aee
+    gt, pred, count = error_inputs(golden, 'empty')
+    aee, pct, n = dev_eval.flow_error_dense(gt, pred, count)
+    assert np.isnan(aee) and pct == 0.0 and n == 0
+
+
+# ---------------------------------------------------------------------------
+# count image
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize('box', [None, (5, 11, 32, 59)], ids=['frame', 'box'])
+def test_count_image_batched_equals_add_at(box):
+    H, W = 37, 70
+    rng = np.random.default_rng(5)
+    sizes = [900, 1300, 0, 2590, 1]                     # an empty frame in the middle
+    begin = np.concatenate([[0], np.cumsum(sizes)])
+    n = int(begin[-1])
+    x, y = rng.integers(0, W, n), rng.integers(0, H, n)
+    x[:40], y[:40] = 69, 36                             # a crowded pixel: atomics on one address
+    y0, x0, h, w = box or (0, 0, H, W)
+    got = dev_eval.count_image_batched(dev(x), dev(y), begin, (h, w), box).cpu().numpy()
+    assert got.shape == (len(sizes), h, w)
+    for f in range(len(sizes)):
+        xs, ys = x[begin[f]:begin[f + 1]] - x0, y[begin[f]:begin[f + 1]] - y0
+        keep = (xs >= 0) & (xs < w) & (ys >= 0) & (ys < h)
+        want = np.zeros((h, w), np.int64)
+        np.add.at(want, (ys[keep], xs[keep]), 1)
+        assert np.array_equal(got[f], want), f
+    assert not got[2].any() and got.sum() > 0
+    if box:
+        assert got.sum() < n                            # the box dropped events
+
+
+# ---------------------------------------------------------------------------
+# evaluate
+# ---------------------------------------------------------------------------
+class DeviceFlow(ec.FakeFlow):
+    """The same prescribed flows through the ``flow_device`` contract."""
+
+    def flow_device(self, events, start, stop):
+        return dev(np.transpose(self(events, start, stop), (0, 3, 1, 2)))
+
+
+def eval_args(golden):
+    gt = dict(timestamps=golden['eval_ts'], x_flow_dist=golden['eval_x_maps'],
+              y_flow_dist=golden['eval_y_maps'])
+    return list(golden['eval_events']), [tuple(f) for f in golden['eval_frames']], gt
+
+
+@pytest.mark.parametrize('kind', [ec.FakeFlow, DeviceFlow], ids=['numpy', 'flow_device'])
+def test_evaluate_matches_the_reference(golden, kind):
+    events, frames, gt = eval_args(golden)
+    crops = dict(event_preproc_fun=ec.EventCrop(ec.EVAL_BOX), gt_proc_fun=ec.ImageCrop(ec.EVAL_BOX))
+    want = golden['eval_mean']
+    rows = {}
+    for bs in (1, 3, 8):                                # 3: a ragged last batch of one frame
+        of = kind(frames, golden['eval_flows'])
+        aee, pct = testing.evaluate(of, events, frames, gt, batch_size=bs, **crops)
+        print(kind.__name__, 'batch', bs, aee, pct, 'reference', want)
+        assert of.batches == [min(bs, len(frames) - i) for i in range(0, len(frames), bs)]
+        assert abs(aee - want[0]) <= 5e-6 * want[0] and abs(pct - want[1]) <= 1e-9
+        rows[bs] = testing.evaluate_frames(kind(frames, golden['eval_flows']), events, frames,
+                                           gt, batch_size=bs, **crops)
+    assert rows[1].tobytes() == rows[3].tobytes() == rows[8].tobytes()
+    ref = golden['eval_frame_results']
+    assert np.array_equal(rows[8]['n_points'], ref[:, 2])
+    assert np.array_equal(rows[8]['pred_max'], ref[:, 3]) and np.array_equal(rows[8]['pred_min'], ref[:, 4])
+    np.testing.assert_allclose(dev_eval.derive(rows[8])[0], ref[:, 0], rtol=5e-6, atol=0)
+    # box folded into the kernels == crops applied on the host
+    host = dict(event_preproc_fun=ec.Opaque(crops['event_preproc_fun']),
+                gt_proc_fun=ec.Opaque(crops['gt_proc_fun']))
+    for variant in (dict(crops, fold=False), host):
+        got = testing.evaluate_frames(kind(frames, golden['eval_flows']), events, frames, gt,
+                                      batch_size=3, **variant)
+        assert got.tobytes() == rows[3].tobytes()
+
+
+def test_evaluate_postprocesses_the_prediction(golden):
+    """pred_postproc_fun as a box crop (sliced on the device) and as an opaque
+    callable (applied on the host) give the same rows."""
+    events, frames, gt = eval_args(golden)
+    y0, x0, h, w = ec.EVAL_BOX
+    wide = np.zeros((len(frames), 37, 70, 2), np.float32)
+    wide[:, y0:y0 + h, x0:x0 + w] = golden['eval_flows']
+    crop = ec.ImageCrop(ec.EVAL_BOX)
+    kw = dict(event_preproc_fun=ec.EventCrop(ec.EVAL_BOX), gt_proc_fun=crop, batch_size=4)
+    want = testing.evaluate_frames(DeviceFlow(frames, golden['eval_flows']), events, frames, gt, **kw)
+    for post in (crop, ec.Opaque(crop)):
+        got = testing.evaluate_frames(DeviceFlow(frames, wide), events, frames, gt,
+                                      pred_postproc_fun=post, **kw)
+        assert got.tobytes() == want.tobytes()
+
+
+def test_map_window_uploads_every_map_once(golden):
+    x, y = golden['eval_x_maps'], golden['eval_y_maps']
+    win = testing.MapWindow(x, y, DEV)
+    for lo, hi in ((0, 2), (1, 2), (1, 3), (2, 4), (3, 4), (4, 6), (5, 6)):
+        xd, yd, off = win.ensure(lo, hi)
+        assert off <= lo and off + xd.shape[0] >= hi
+        assert np.array_equal(bits(xd.cpu().numpy()[lo - off:hi - off].view(np.float32)),
+                              bits(x[lo:hi].view(np.float32)))
+        assert torch.equal(yd[lo - off:hi - off].cpu(), torch.from_numpy(y[lo:hi]))
+    assert win.uploaded == 6
+
+
+def test_evaluate_with_the_real_network():
+    from dvs_of_training_framework_amd.of import OpticalFlow
+    H, W = 32, 48
+    rng = np.random.default_rng(3)
+    xm, ym = ec.make_maps((H, W), np.float64, 7)
+    frames = [tuple(f) for f in ec.EVAL_FRAMES[:5]]
+    n = 4000
+    t = np.sort(rng.uniform(frames[0][0], frames[-1][1], n))
+    events = [rng.integers(0, W, n).astype(np.float64), rng.integers(0, H, n).astype(np.float64),
+              t, rng.choice([-1.0, 1.0], n)]
+    gt = dict(timestamps=ec.GT_TS, x_flow_dist=xm, y_flow_dist=ym)
+    of = OpticalFlow((H, W), model=None, device=torch.device(DEV), event_representation_depth=5)
+    flow = of.flow_device([events], [frames[0][0]], [frames[-1][1]])
+    assert flow.is_cuda and tuple(flow.shape) == (1, 2, H, W)
+    # (the voxeliser's float sums may differ in their last bits between two calls)
+    assert np.allclose(np.transpose(flow.cpu().numpy(), (0, 2, 3, 1)),
+                       of([events], [frames[0][0]], [frames[-1][1]]), rtol=1e-4, atol=1e-5)
+    one = testing.evaluate_frames(of, events, frames, gt, batch_size=1)
+    four = testing.evaluate_frames(of, events, frames, gt, batch_size=4)
+    assert np.array_equal(one['n_points'], four['n_points']) and (one['n_points'] > 0).all()
+    for rows in (one, four):
+        aee, pct = dev_eval.derive(rows)
+        assert np.isfinite(aee).all() and np.isfinite(pct).all()
+        assert np.isfinite(rows['pred_max']).all() and np.isfinite(rows['pred_min']).all()
+    res = testing.evaluate(of, events, frames, gt, batch_size=4)
+    assert np.isfinite(res).all()
+
+
+# ---------------------------------------------------------------------------
+# C ABI
+# ---------------------------------------------------------------------------
+def test_abi_argument_errors_and_no_ops():
+    lib = _lib.lib()
+    EINVAL, ENOSPACE = -1, -2
+    H, W, F = 12, 20, 2
+    maps = torch.zeros(2, H, W, device=DEV)
+    table = torch.zeros(64, dtype=torch.int32, device=DEV)
+    scale = torch.ones(8, dtype=torch.float64, device=DEV)
+    u = torch.full((F, H, W), 7.0, device=DEV)
+    v = torch.full((F, H, W), 7.0, device=DEV)
+    p = torch.Tensor.data_ptr
+
+    def prop(xp, yp, F=F, win=(0, 0, H, W), dtype=0):
+        return lib.dvsof_gt_flow_propagate(xp, yp, dtype, 2, H, W, p(table), p(table), p(scale),
+                                           p(table), F, 0, *win, p(u), p(v), None)
+    assert prop(None, p(maps)) == EINVAL and prop(p(maps), None) == EINVAL
+    for win in ((0, 0, H + 1, W), (1, 0, H, W), (0, 1, H, W), (-1, 0, 4, 4), (0, 0, 0, W)):
+        assert prop(p(maps), p(maps), win=win) == EINVAL, win
+    assert prop(p(maps), p(maps), dtype=2) == EINVAL
+    assert prop(None, None, F=0) == 0                       # zero frames: nothing to do
+    torch.cuda.synchronize()
+    assert (u == 7).all() and (v == 7).all()                # nothing was launched
+    assert prop(p(maps), p(maps)) == 0                      # frames without steps: zero flow
+    torch.cuda.synchronize()
+    assert not u.any() and not v.any()
+
+    h, w = 37, 70
+    gt = torch.zeros(F, h, w, device=DEV)
+    pred = torch.zeros(F, 2, h, w, device=DEV)
+    out = torch.full((F, 32), 9, dtype=torch.uint8, device=DEV)
+    need = lib.dvsof_flow_error_workspace_bytes(F, h, w)
+    assert need > 0 and need % 32 == 0
+    ws = torch.zeros(need, dtype=torch.uint8, device=DEV)
+
+    def err(gp=p(gt), F=F, nbytes=need, max_row=h, wsp=p(ws)):
+        return lib.dvsof_flow_error(gp, p(gt), p(pred), None, F, h, w, max_row, p(out), wsp,
+                                    nbytes, None)
+    assert err(gp=None) == EINVAL and err(max_row=h + 1) == EINVAL and err(max_row=-1) == EINVAL
+    assert err(nbytes=need - 1) == ENOSPACE and err(wsp=None) == ENOSPACE
+    assert err(F=0, nbytes=0, wsp=None) == 0
+    torch.cuda.synchronize()
+    assert (out == 9).all()
+    assert err() == 0
+
+    cnt = torch.full((F, h, w), 5, dtype=torch.int32, device=DEV)
+    xy = torch.zeros(10, dtype=torch.long, device=DEV)
+    begin = torch.tensor([0, 4, 10], device=DEV)
+
+    def count(xp=p(xy), n=10, F=F, box=(0, 0, h, w), bp=p(begin)):
+        return lib.dvsof_count_image_batched(xp, p(xy), n, bp, F, *box, p(cnt), None)
+    assert count(xp=None) == EINVAL and count(bp=None) == EINVAL
+    assert count(box=(0, 0, 0, w)) == EINVAL and count(box=(-1, 0, h, w)) == EINVAL
+    assert count(F=0) == 0
+    torch.cuda.synchronize()
+    assert (cnt == 5).all()
+    assert count(xp=None, n=0) == 0                         # zero events: zeroed images
+    torch.cuda.synchronize()
+    assert not cnt.any()
+    assert count() == 0
+    torch.cuda.synchronize()
+    assert cnt[:, 0, 0].tolist() == [4, 6] and int(cnt.sum()) == 10
+
+
+def test_cpu_tensors_are_refused():
+    z = torch.zeros
+    with pytest.raises(RuntimeError, match='no CPU implementation'):
+        dev_eval.flow_error(z(1, 4, 4), z(1, 4, 4), z(1, 2, 4, 4))
+    with pytest.raises(RuntimeError, match='no CPU implementation'):
+        dev_eval.propagate(z(2, 4, 4), z(2, 4, 4), [(0, [0, 1], [0.5, 0.5])])
+    with pytest.raises(RuntimeError, match='no CPU implementation'):
+        dev_eval.count_image_batched(z(3, dtype=torch.long), z(3, dtype=torch.long), [0, 3], (4, 4))

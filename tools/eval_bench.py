@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""Throughput of testing.evaluate on a synthetic MVSEC-shaped sequence, one
+JSON line (profiles/eval/README.md).
+
+Sequence: 260x346 float64 ground-truth maps at 20 Hz, frames at 45 Hz
+(--frames of them, each spanning --step image intervals: 1 = the direct-scale
+branch, 4 = propagation over two to three maps), central 256x256 crop, about
+--events events per frame, untrained OpticalFlow.  Reported:
+  evaluate_fps        frames/s of testing.evaluate at batch_size 1 and 8
+  host_fps            the same frames through the per-frame structure of the
+                      reference: batch-1 inference, copy to the host, float64
+                      restatement of propagation / count image / error
+                      (tests/eval_cases.py) -- never the device path against itself
+  kernels             the three kernels alone at F = 8, HIP-event timed,
+                      bytes from the shapes
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from dvs_of_training_framework_amd import _lib, eval as dev_eval, testing  # noqa: E402
+from dvs_of_training_framework_amd.of import OpticalFlow  # noqa: E402
+from tests import eval_cases as ec  # noqa: E402
+
+H, W, CROP = 260, 346, 256
+GT_HZ, FRAME_HZ = 20.0, 45.0
+
+
+def sequence(n_frames, step, per_frame, seed=0):
+    rng = np.random.default_rng(seed)
+    t0 = 100.0
+    image_ts = t0 + 0.01 + np.arange(n_frames + step + 1) / FRAME_HZ
+    frames = list(zip(image_ts[:n_frames], image_ts[step:step + n_frames]))
+    K = int((image_ts[-1] - t0) * GT_HZ) + 3
+    ts = t0 + np.arange(K) / GT_HZ
+    x = rng.uniform(-3, 3, (K, H, W))
+    y = rng.uniform(-3, 3, (K, H, W))
+    x[rng.random(x.shape) < 0.1] = 0.0
+    n = per_frame * (n_frames + step)
+    t = np.sort(rng.uniform(image_ts[0], image_ts[-1], n))
+    events = [rng.integers(0, W, n).astype(np.float64), rng.integers(0, H, n).astype(np.float64),
+              t, rng.choice([-1.0, 1.0], n)]
+    return events, frames, dict(timestamps=ts, x_flow_dist=x, y_flow_dist=y)
+
+
+def timed(fn, reps=50):
+    """us per call of fn, which only enqueues work (HIP events around reps calls)."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps
+
+
+def kernels_alone(events, frames, gt, box, F=8):
+    """The three C ABI calls alone: inputs, step table, outputs and scratch are
+    made once; the timed loop holds nothing but the calls (back to back on one
+    stream, so a call's launch overhead hides behind the kernel in front)."""
+    dev = 'cuda'
+    lib, stream = _lib.lib(), _lib.stream()
+    y0, x0, h, w = box
+    plans = [dev_eval.plan_gt_steps(gt['timestamps'], a, b) for a, b in frames[:F]]
+    lo, hi = min(min(p[1]) for p in plans), max(max(p[1]) for p in plans) + 1
+    xd = torch.from_numpy(gt['x_flow_dist'][lo:hi]).to(dev)
+    yd = torch.from_numpy(gt['y_flow_dist'][lo:hi]).to(dev)
+    table = dev_eval.StepTable(plans, lo, dev)
+    u = torch.empty(F, h, w, device=dev)
+    v = torch.empty_like(u)
+    steps = sum(1 if p[0] else len(p[1]) for p in plans)
+    out = {}
+
+    def run_propagate():
+        rc = lib.dvsof_gt_flow_propagate(
+            xd.data_ptr(), yd.data_ptr(), dev_eval.F64, hi - lo, H, W, table.begin, table.maps,
+            table.scales, table.mode, F, table.S, y0, x0, h, w, u.data_ptr(), v.data_ptr(), stream)
+        assert rc == 0, rc
+    us = timed(run_propagate)
+    nbytes = steps * h * w * 2 * 8 + F * h * w * 2 * 4     # two f64 samples per step, u and v out
+    out['propagate'] = dict(us=round(us, 2), steps=steps, bytes=nbytes, GBps=round(nbytes / us / 1e3, 1))
+
+    idx = np.searchsorted(events[2], np.array(frames[:F]).ravel(), side='right').reshape(-1, 2)
+    cols = [np.concatenate([events[c][i0:i1] for i0, i1 in idx]).astype(np.int64) for c in (0, 1)]
+    begin = np.concatenate([[0], np.cumsum(idx[:, 1] - idx[:, 0])])
+    n = int(begin[-1])
+    xe, ye = torch.from_numpy(cols[0]).to(dev), torch.from_numpy(cols[1]).to(dev)
+    bd = torch.from_numpy(begin).to(dev)
+    count = torch.empty(F, h, w, dtype=torch.int32, device=dev)
+
+    def run_count():
+        rc = lib.dvsof_count_image_batched(xe.data_ptr(), ye.data_ptr(), n, bd.data_ptr(), F,
+                                           y0, x0, h, w, count.data_ptr(), stream)
+        assert rc == 0, rc
+    us = timed(run_count)
+    nbytes = n * 16 + F * h * w * 4 + n * 4                # columns in, zero fill, one atomic per event
+    out['count_image'] = dict(us=round(us, 2), events=n, bytes=nbytes, GBps=round(nbytes / us / 1e3, 1))
+
+    pred = torch.randn(F, 2, h, w, device=dev)
+    rows = torch.empty(F, 32, dtype=torch.uint8, device=dev)
+    need = lib.dvsof_flow_error_workspace_bytes(F, h, w)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+    def run_error():
+        rc = lib.dvsof_flow_error(u.data_ptr(), v.data_ptr(), pred.data_ptr(), count.data_ptr(),
+                                  F, h, w, h, rows.data_ptr(), ws.data_ptr(), need, stream)
+        assert rc == 0, rc
+    us = timed(run_error)
+    nbytes = F * h * w * 5 * 4
+    out['flow_error'] = dict(us=round(us, 2), bytes=nbytes, GBps=round(nbytes / us / 1e3, 1))
+    return out
+
+
+def host_reference_structure(of, events, frames, gt, box):
+    """One frame at a time, off the device after the inference."""
+    ev_crop, im_crop = ec.EventCrop(box), ec.ImageCrop(box)
+    aee_sum = 0.0
+    for e, start, stop in ec.frame_generator(events, frames):
+        e = ev_crop(np.array(e).T).T
+        flow = of([e], [start], [stop])[0]
+        u, v = ec.propagate64(gt['x_flow_dist'], gt['y_flow_dist'], gt['timestamps'], start, stop)
+        gt_flow = im_crop(np.dstack((u, v)))
+        aee_sum += ec.flow_error64(gt_flow, flow, ec.get_count_image(e, gt_flow.shape[:2]))[0]
+    return aee_sum / len(frames)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, default=200)
+    ap.add_argument('--events', type=int, default=30000)
+    ap.add_argument('--steps', type=int, nargs='+', default=[1, 4])
+    ap.add_argument('--host-frames', type=int, default=40)
+    args = ap.parse_args()
+    box = [(H - CROP) // 2, (W - CROP) // 2, CROP, CROP]
+    of = OpticalFlow((CROP, CROP), model=None, event_representation_depth=5)
+    crops = dict(event_preproc_fun=ec.EventCrop(box), gt_proc_fun=ec.ImageCrop(box))
+    result = dict(frames=args.frames, events_per_frame=args.events, shape=[H, W], crop=CROP, runs=[])
+    for step in args.steps:
+        events, frames, gt = sequence(args.frames, step, args.events)
+        run = dict(step=step, direct_frames=sum(
+            dev_eval.plan_gt_steps(gt['timestamps'], a, b)[0] for a, b in frames))
+        for bs in (1, 8):
+            testing.evaluate(of, events, frames[:2 * bs], gt, batch_size=bs, **crops)     # warm-up
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = testing.evaluate(of, events, frames, gt, batch_size=bs, **crops)
+            torch.cuda.synchronize()
+            run[f'evaluate_fps_batch{bs}'] = round(len(frames) / (time.perf_counter() - t), 1)
+            run[f'mean_aee_batch{bs}'] = res[0]
+        sub = frames[:args.host_frames]
+        host_reference_structure(of, events, sub[:2], gt, box)
+        t = time.perf_counter()
+        run['host_mean_aee'] = host_reference_structure(of, events, sub, gt, box)
+        run['host_fps'] = round(len(sub) / (time.perf_counter() - t), 1)
+        run['host_frames'] = len(sub)
+        run['kernels_F8'] = kernels_alone(events, frames, gt, box)
+        result['runs'].append(run)
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()
