@@ -74,6 +74,9 @@ _SIGNATURES = {
                               _sz, _vp]),
     'dvsof_count_image_batched': (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i,
                                        _i, _vp, _vp]),
+    'dvsof_event_windows': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _i64, _i64, _vp]),
     'dvsof_voxelize_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                 _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'dvsof_voxelize_workspace_bytes': (_sz, [_i64, _i, _i, _i, _i]),

@@ -24,6 +24,13 @@ RESULT_DTYPE = np.dtype([('sum_ee', '<f8'), ('n_points', '<i8'),
 assert RESULT_DTYPE.itemsize == 32
 
 
+def check_in_frame(x, y, shape):
+    # np.ravel_multi_index of the reference's get_count_image raises for these
+    if x.size and (x.min() < 0 or x.max() >= shape[1] or
+                   y.min() < 0 or y.max() >= shape[0]):
+        raise ValueError('invalid entry in coordinates array')
+
+
 def plan_gt_steps(gt_timestamps, start, stop):
     """Which ground-truth maps the interval [start, stop] walks through and
     by how much of each (utils/eval.py:118-172, literally: searchsorted

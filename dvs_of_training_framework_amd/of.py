@@ -64,16 +64,53 @@ class OpticalFlow:
             flow, _, _ = self._net(ev, ts, sidx, self.imsize)
             return flow[-1].contiguous()
 
-    def _replay(self, ev, ts, sidx, B):
-        n = ev['x'].numel()
+    def _graph_slot(self, B, n, dtypes):
+        """The static inputs (and, once captured, the graph) of batch size B
+        with room for n events; dtypes: of the event columns."""
         g = self._graphs.get(B)
         if g is None or n > g['cap']:
             cap = max(4096, 1 << max(n - 1, 1).bit_length())
-            st = {k: torch.zeros(cap, dtype=v.dtype, device=self._device)
-                  for k, v in ev.items()}
-            g = dict(cap=cap, ev=st, ts=torch.zeros_like(ts),
-                     sidx=sidx.clone(), graph=None, flow=None)
+            st = {k: torch.zeros(cap, dtype=dt, device=self._device)
+                  for k, dt in dtypes.items()}
+            g = dict(cap=cap, ev=st,
+                     ts=torch.zeros(2 * B, dtype=torch.float32, device=self._device),
+                     sidx=torch.zeros(2 * B, dtype=torch.long, device=self._device),
+                     graph=None, flow=None)
             self._graphs[B] = g
+        return g
+
+    def flow_sequence(self, seq, starts, stops, box=None, return_events=False):
+        """The finest flow ``[F,2,H,W]`` of the frames (start_i, stop_i] of a
+        device-resident ``sequence.EventSequence``, on the device like
+        ``flow_device``'s; the events never visit the host: one window-kernel
+        launch collates them (box = (y0, x0, h, w): cropped as by EventCrop,
+        the events outside it stay in their slots as x = y = -1).  With
+        graph=True the kernel writes the graph's static inputs directly and
+        pads them to their capacity.  return_events: -> (flow, the collated
+        batch: sequence.EventSequence.collate_frames)."""
+        from .sequence import _OUT_DTYPES
+        with torch.no_grad():
+            B = len(starts)
+            if self._use_graph:
+                def static_columns(n):
+                    g = self._graph_slot(B, n, _OUT_DTYPES)
+                    if _GRAPH_SYNC and g.get('done') is not None:
+                        g['done'].synchronize()
+                    return g['cap'], g['ev']
+                c = seq.collate_frames(starts, stops, box, buffers=static_columns)
+                g = self._graphs[B]
+                g['ts'].copy_(c.timestamps)
+                g['sidx'].copy_(c.sample_idx)
+                flow = self._launch(g, B)[-1].clone()
+            else:
+                c = seq.collate_frames(starts, stops, box)
+                flow = self._net(c.events, c.timestamps, c.sample_idx,
+                                 self.imsize)[0][-1].contiguous()
+            return (flow, c) if return_events else flow
+
+    def _replay(self, ev, ts, sidx, B):
+        n = ev['x'].numel()
+        g = self._graph_slot(B, n, {k: v.dtype for k, v in ev.items()})
         assert ts.numel() == g['ts'].numel()
         # Replays, and the copies into the static inputs between them, are
         # ordered on one stream; no host synchronisation is needed.  The graph
@@ -90,6 +127,10 @@ class OpticalFlow:
         g['ev']['sample_index'][n:] = 0
         g['ts'].copy_(ts)
         g['sidx'].copy_(sidx)
+        return self._launch(g, B)
+
+    def _launch(self, g, B):
+        """Capture (first call) and replay the graph over the static inputs."""
         if g['graph'] is None:
             # one validated eager call (host-side assertions, lazy inits), then
             # capture without them

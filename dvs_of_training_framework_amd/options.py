@@ -159,6 +159,13 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         help='with --preprocessed-dataset-path: hand raw '
                              'events to the device voxeliser in their 9 B/event '
                              'encoded columns (no int64 wire columns)')
+    parser.add_argument('--sequence', dest='sequence', default=None, type=Path,
+                        help='train from ONE recorded sequence kept on the device: a '
+                             'directory of the per-frame <number>.hdf5 files (events, '
+                             'image1, image2, start, stop); batches are cut by '
+                             'sequence.SequenceLoader (collapse length -cl, sequence '
+                             'length prefix + suffix + 1, random flip / rotation / crop '
+                             'to --height x --width)')
     parser.add_argument('--synthetic', action='store_true',
                         help='train on seeded synthetic batches (no dataset)')
     parser.add_argument('--synthetic-events', dest='synthetic_events',

@@ -121,11 +121,7 @@ def _device_of(of):
     return torch.device(getattr(of, '_device', 'cuda'))
 
 
-def _check_in_frame(x, y, shape):
-    # np.ravel_multi_index of the reference's get_count_image raises for these
-    if x.size and (x.min() < 0 or x.max() >= shape[1] or
-                   y.min() < 0 or y.max() >= shape[0]):
-        raise ValueError('invalid entry in coordinates array')
+_check_in_frame = dev_eval.check_in_frame
 
 
 def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
@@ -134,15 +130,38 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
     """The per-frame results behind ``evaluate``: a numpy structured array
     (eval.RESULT_DTYPE: sum_ee, n_points, n_below, pred_max, pred_min), one
     row per frame.  fold=False applies box crops on the host like any other
-    callable (same results; for tests)."""
+    callable (same results; for tests).
+
+    events: the columns [x, y, t, p], or a ``sequence.EventSequence`` holding
+    them on the device: a batch of frames is then one window-kernel launch in
+    front of the inference (``of.flow_sequence``), and the count image is made
+    of the same collated columns; nothing but the window table is uploaded.
+    ``event_preproc_fun`` must then be None or a box crop.  The events stay on
+    the device, so whether one lies outside the ground-truth frame is decided
+    by the shapes alone: a sensor (or box) larger than the ground truth raises
+    the ValueError of the numpy-events path even when no event does."""
+    from .sequence import EventSequence
+    on_device = isinstance(events, EventSequence)
+    if on_device:
+        seq_box = fold_box(event_preproc_fun, events.shape)
+        if event_preproc_fun is not None and seq_box is None:
+            raise TypeError(
+                'with an EventSequence event_preproc_fun is None or a box crop '
+                '(an object with a .box inside the frame); any other callable '
+                'needs the numpy-events path: pass events as [x, y, t, p]')
+        if not hasattr(of, 'flow_sequence'):
+            raise TypeError(
+                'an EventSequence needs an `of` with flow_sequence '
+                '(OpticalFlow); other callables take the numpy-events path')
     device = _device_of(of)
     frames = np.array(frames)
     if frames.size == 0:
         return np.zeros(0, dev_eval.RESULT_DTYPE)
     frames = frames.reshape(-1, 2)
     batch_size = max(int(batch_size), 1)
-    t = events[2]
-    idx = np.searchsorted(t, frames.ravel(), side='right').reshape(-1, 2)
+    if not on_device:
+        t = events[2]
+        idx = np.searchsorted(t, frames.ravel(), side='right').reshape(-1, 2)
     xg, yg, ts = gt['x_flow_dist'], gt['y_flow_dist'], gt['timestamps']
     H, W = np.squeeze(xg[0]).shape
     gt_box = fold_box(gt_proc_fun, (H, W)) if fold else None
@@ -153,15 +172,19 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
     for b0 in range(0, len(frames), batch_size):
         fr = frames[b0:b0 + batch_size]
         starts, stops = list(fr[:, 0]), list(fr[:, 1])
-        raw = [[p[i0:i1] for p in events] for i0, i1 in idx[b0:b0 + batch_size]]
-        # events as the network sees them (utils/testing.py:66)
-        if event_preproc_fun is None:
-            evs = [np.array(e) for e in raw]
-        else:
-            evs = [event_preproc_fun(np.array(e).T).T for e in raw]
+        if not on_device:
+            raw = [[p[i0:i1] for p in events] for i0, i1 in idx[b0:b0 + batch_size]]
+            # events as the network sees them (utils/testing.py:66)
+            if event_preproc_fun is None:
+                evs = [np.array(e) for e in raw]
+            else:
+                evs = [event_preproc_fun(np.array(e).T).T for e in raw]
 
         # one batched inference -> pred [F,2,h,w] on the device
-        if hasattr(of, 'flow_device'):
+        if on_device:
+            pred, collated = of.flow_sequence(events, starts, stops, box=seq_box,
+                                              return_events=True)
+        elif hasattr(of, 'flow_device'):
             pred = of.flow_device(evs, starts, stops)
         else:
             pred = torch.from_numpy(np.ascontiguousarray(np.transpose(
@@ -197,6 +220,19 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
         h, w = gt_u.shape[-2:]
 
         # event mask: count image of the frame's events
+        if on_device:
+            # the collated columns are already cropped and shifted; the -1
+            # slots (outside the box, padding) fall outside (0, 0, h, w)
+            eh, ew = seq_box[2:] if seq_box is not None else events.shape
+            if eh > h or ew > w:    # events could lie outside the ground truth
+                raise ValueError('invalid entry in coordinates array')
+            count = dev_eval.count_image_batched(
+                collated.events['x'], collated.events['y'], collated.win_out,
+                (h, w), (0, 0, h, w))
+            res = dev_eval.flow_error(gt_u, gt_v, pred, count,
+                                      min(dev_eval.CAR_ROWS, h) if is_car else h)
+            out.append(dev_eval.read_results(res))
+            continue
         if ev_box is not None and ev_box[2:] == (h, w):
             cols, box = raw, ev_box         # the kernel drops and shifts
         else:
@@ -228,7 +264,9 @@ def evaluate(of, events, frames, gt, event_preproc_fun=None,
 
     of: ``OpticalFlow`` (its ``flow_device`` keeps the flow on the device) or
     any callable with the reference contract (events, start, stop) -> numpy
-    [B,H,W,2]; events: [x, y, t, p] sorted by t; frames: [(start, stop)];
+    [B,H,W,2]; events: [x, y, t, p] sorted by t, or a
+    ``sequence.EventSequence`` of them (device-resident: see
+    ``evaluate_frames``); frames: [(start, stop)];
     gt: dict with 'timestamps', 'x_flow_dist', 'y_flow_dist'.  The three
     optional functions pre-/post-process events [n,4], predicted flow [H,W,2]
     and ground-truth flow [H,W,2]; box crops (objects with ``.box``) are

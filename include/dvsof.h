@@ -233,6 +233,47 @@ int dvsof_count_image_batched(const int64_t *x, const int64_t *y,
                               void *stream);
 
 /* ------------------------------------------------------------------ *
+ * Device-resident event sequence -> wire-format batch
+ * (docs/SEQUENCE_SPEC.md)
+ * ------------------------------------------------------------------ */
+
+/*
+ * W windows cut from one resident, time-sorted sequence, collated into the
+ * wire format in one launch.  Replaces the per-frame slicing, cropping and
+ * collation of utils/testing.py:64-66 + DummyNet/of.py:76-115 and the event
+ * side of DatasetImpl.__getitem__ / collate_wrapper, utils/dataset.py:714-751,
+ * 961-1020.
+ *   x, y, t, p     the sequence: int16 coordinates, float64 timestamps sorted
+ *                  ascending, int8 polarity; n_events entries
+ *   win_begin/end  int64[W]: window k holds the events [begin[k], end[k])
+ *   win_out        int64[W+1]: first output slot of every window, the prefix
+ *                  sum of the lengths; win_out[W] = n_out
+ *   win_origin     double[W]: subtracted from t in float64
+ *   win_sample, win_element  int32[W]: sample_index / element_index of the window
+ *   (y0, x0, h, w) crop box with the semantics of EventCrop,
+ *                  utils/data.py:24-42; h == w == 0: no crop
+ *   *_out          `capacity` >= n_out slots each
+ * Slot win_out[k] + j holds event i = win_begin[k] + j:
+ *   t_out = (float)(t[i] - win_origin[k]); inside the box x_out = x - x0,
+ *   y_out = y - y0, outside it x_out = y_out = -1 (the slot stays: no
+ *   compaction); polarity, sample and element as given.
+ * Slots [n_out, capacity): x = y = -1, t = 0, polarity = sample = element = 0.
+ * Windows may be empty, overlap, repeat and come in any order; W = 0 and
+ * n_out = 0 are valid.  Every output element is written exactly once; one
+ * kernel launch, no memset.  The window table is trusted (its Python wrapper
+ * validates it on the host); a wrong one reads nothing outside the sequence.
+ */
+int dvsof_event_windows(const int16_t *x, const int16_t *y, const double *t,
+                        const int8_t *p, int64_t n_events,
+                        const int64_t *win_begin, const int64_t *win_end,
+                        const int64_t *win_out, const double *win_origin,
+                        const int32_t *win_sample, const int32_t *win_element,
+                        int W, int y0, int x0, int h, int w, int64_t *x_out,
+                        int64_t *y_out, float *t_out, int64_t *polarity_out,
+                        int64_t *sample_out, int64_t *element_out,
+                        int64_t n_out, int64_t capacity, void *stream);
+
+/* ------------------------------------------------------------------ *
  * Multi-scale warp / Charbonnier / smoothness / out-of-border loss
  * ------------------------------------------------------------------ */
 

@@ -13,6 +13,13 @@ branch, 4 = propagation over two to three maps), central 256x256 crop, about
                       (tests/eval_cases.py) -- never the device path against itself
   kernels             the three kernels alone at F = 8, HIP-event timed,
                       bytes from the shapes
+  sequence_fps        the same frames with the events resident on the device
+                      (sequence.EventSequence): per batch a window table and one
+                      dvsof_event_windows launch instead of numpy slicing,
+                      cropping, collation and the upload of the columns; the
+                      numpy-events figures of the same run are the comparison
+  event_windows       that one C ABI call alone at F = 8 (13 B/event in,
+                      44 B/event out, share of 8 TB/s)
 """
 import argparse
 import json
@@ -26,6 +33,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from dvs_of_training_framework_amd import _lib, eval as dev_eval, testing  # noqa: E402
 from dvs_of_training_framework_amd.of import OpticalFlow  # noqa: E402
+from dvs_of_training_framework_amd.sequence import EventSequence  # noqa: E402
 from tests import eval_cases as ec  # noqa: E402
 
 H, W, CROP = 260, 346, 256
@@ -120,6 +128,34 @@ def kernels_alone(events, frames, gt, box, F=8):
     return out
 
 
+def window_kernel_alone(seq, frames, box, F=8):
+    """dvsof_event_windows alone: table, inputs and outputs made once, the timed
+    loop holds the call only.  Bytes from the shapes: 13 B per event read, 44 B
+    per slot written (the table is noise)."""
+    lib, stream = _lib.lib(), _lib.stream()
+    starts, stops = [a for a, _ in frames[:F]], [b for _, b in frames[:F]]
+    c = seq.collate_frames(starts, stops, box)
+    ranges = seq.frame_ranges(np.stack([starts, stops], 1))
+    cols, _, _, table = seq.windows(ranges[:, 0], ranges[:, 1], np.full(F, min(starts)),
+                                    np.arange(F), np.zeros(F), box=box)
+    for k in cols:
+        assert torch.equal(cols[k], c.events[k]), k
+    n = c.n_out
+    tb, te, to, tor, tsa, tel = (t.data_ptr() for t in table)
+    args = (seq.x.data_ptr(), seq.y.data_ptr(), seq.t_dev.data_ptr(), seq.p.data_ptr(), seq.n_events,
+            tb, te, to, tor, tsa, tel, F, *box, cols['x'].data_ptr(), cols['y'].data_ptr(),
+            cols['timestamp'].data_ptr(), cols['polarity'].data_ptr(), cols['sample_index'].data_ptr(),
+            cols['element_index'].data_ptr(), n, n, stream)
+
+    def run():
+        rc = lib.dvsof_event_windows(*args)
+        assert rc == 0, rc
+    us = timed(run)
+    nbytes = n * (13 + 44)
+    return dict(us=round(us, 2), events=n, bytes=nbytes, GBps=round(nbytes / us / 1e3, 1),
+                share_of_8TBps=round(nbytes / us / 1e3 / 8000, 3))
+
+
 def host_reference_structure(of, events, frames, gt, box):
     """One frame at a time, off the device after the inference."""
     ev_crop, im_crop = ec.EventCrop(box), ec.ImageCrop(box)
@@ -156,6 +192,21 @@ def main():
             torch.cuda.synchronize()
             run[f'evaluate_fps_batch{bs}'] = round(len(frames) / (time.perf_counter() - t), 1)
             run[f'mean_aee_batch{bs}'] = res[0]
+        # the same frames, the events resident on the device (upload not timed: it happens once
+        # per recording; reported on its own)
+        t = time.perf_counter()
+        seq = EventSequence(events, (H, W))
+        torch.cuda.synchronize()
+        run['sequence_upload_ms'] = round((time.perf_counter() - t) * 1e3, 1)
+        for bs in (1, 8):
+            testing.evaluate(of, seq, frames[:2 * bs], gt, batch_size=bs, **crops)        # warm-up
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = testing.evaluate(of, seq, frames, gt, batch_size=bs, **crops)
+            torch.cuda.synchronize()
+            run[f'sequence_fps_batch{bs}'] = round(len(frames) / (time.perf_counter() - t), 1)
+            run[f'sequence_mean_aee_batch{bs}'] = res[0]
+        run['event_windows_F8'] = window_kernel_alone(seq, frames, box)
         sub = frames[:args.host_frames]
         host_reference_structure(of, events, sub[:2], gt, box)
         t = time.perf_counter()

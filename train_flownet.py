@@ -2,7 +2,8 @@
 """Training entry point with the reference's flags and wiring
 (train_flownet.py:31-217): model plugin -> optimizer + LambdaLR ->
 ``init_losses`` -> ``train``.  Additions: one process per GPU under torchrun
-(RCCL gradient all-reduce overlapped with backward) and ``--synthetic``.
+(RCCL gradient all-reduce overlapped with backward), ``--synthetic`` and
+``--sequence DIR`` (one recorded sequence kept on the device).
 
 The reference's HDF5 data pipeline, TensorBoard writer, serializer and hooks
 are outside this build's scope: when this file is
@@ -179,6 +180,19 @@ def main(argv=None):
     if args.synthetic:
         loader = SyntheticLoader(args, rank,
                                  args.training_steps * args.accum_step)
+    elif getattr(args, 'sequence', None) is not None:
+        # one recorded sequence, resident on the device: batches are a window
+        # table and one gather launch each (sequence.py); ranks draw different
+        # permutations
+        import numpy as np
+        from dvs_of_training_framework_amd.sequence import FrameSequence, \
+            SequenceLoader
+        loader = SequenceLoader(
+            FrameSequence.from_directory(args.sequence, device), args.shape,
+            args.mbs, augmentation=True, collapse_length=args.cl,
+            seq_length=args.prefix_length + args.suffix_length + 1,
+            rng=np.random.default_rng(1234 + rank),
+            steps=args.training_steps * args.accum_step)
     elif getattr(args, 'preprocessed_dataset_path', None) is not None:
         # utils/dataloader.py:89-100: the preprocessed (encoded / quantized)
         # dataset; --compact-events keeps raw events in their 9 B/event columns
