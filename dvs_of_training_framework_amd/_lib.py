@@ -87,6 +87,18 @@ _SIGNATURES = {
     'dvsof_voxelize_encoded': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                     _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz,
                                     _i, _vp]),
+    'dvsof_learned_voxelize_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                                        _vp, _vp, _i, _i, _i, _i, _i, _i, _vp,
+                                        _vp]),
+    'dvsof_learned_voxelize_encoded': (_i, [_vp, _vp, _vp, _vp, _vp, _i64,
+                                            _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                            _i, _vp, _vp]),
+    'dvsof_learned_voxelize_bwd_workspace_bytes': (_sz, [_i64, _i, _i]),
+    'dvsof_learned_voxelize_bwd_blocks': (_i, [_i64]),
+    'dvsof_learned_voxelize_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64,
+                                        _vp, _vp, _i, _i, _i, _i, _i, _i, _vp,
+                                        _vp, _vp, _sz, _vp]),
+    'dvsof_first_dgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'dvsof_resize_bilinear_ac': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'dvsof_loss_workspace_bytes': (_sz, [ctypes.POINTER(LossScale), _i, _i]),
     'dvsof_loss_fwd': (_i, [ctypes.POINTER(LossScale), _i, _i, _vp, _vp, _vp,

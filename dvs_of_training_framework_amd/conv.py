@@ -389,6 +389,24 @@ def conv_wgrad(desc, gout, dweight, dbias, gout16=None, skip_flat=False,
     _chain(desc)
 
 
+def first_dgrad(gz, weight, B, C, H, W):
+    """Data gradient of enc.0 (dvsof_first_dgrad): gz [B,H/2,W/2,64] NHWC is
+    the gradient with respect to the layer's PRE-activation (what its weight
+    gradient consumes), weight the channels_last [64,C,3,3] parameter.
+    -> gradient of the planar voxel grid [B,C,H,W]."""
+    _lib.require_cuda(gz, weight)
+    assert gz.dtype == torch.float32 and gz.is_contiguous()
+    assert gz.numel() == B * (H // 2) * (W // 2) * 64
+    assert tuple(weight.shape) == (64, C, 3, 3) and \
+        weight.permute(0, 2, 3, 1).is_contiguous(), \
+        'enc.0 weight: channels_last [64,C,3,3]'
+    out = torch.empty(B, C, H, W, dtype=torch.float32, device=gz.device)
+    _lib.check(_lib.lib().dvsof_first_dgrad(
+        gz.data_ptr(), weight.data_ptr(), B, C, H, W, out.data_ptr(),
+        _lib.stream()), 'dvsof_first_dgrad')
+    return out
+
+
 def head_fwd(x, w, bias, B, H, W, C):
     flow = torch.empty(B, 2, H, W, dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().dvsof_flow_head_fwd(

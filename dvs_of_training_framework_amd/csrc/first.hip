@@ -1,6 +1,7 @@
 // The first encoder layer as kernels of its own: 3x3 / stride 2 / pad 1 over
 // the PLANAR voxel grid [B][C][H][W] (C = event bins, 3..16) into 64 NHWC
-// channels, forward and weight gradient.  (EV_FlowNet predictor, reference
+// channels, forward, weight gradient and (for a learnable event representation,
+// docs/LEARNED_VOXEL_SPEC.md) data gradient.  (EV_FlowNet predictor, reference
 // call site utils/training.py:59-64; docs/MODEL_SPEC.md enc.0.)
 //
 // Why: K = 9 C is 27..144 and the input is planar, so the general LDS-DMA
@@ -26,6 +27,8 @@
 //             bias gradient.  Waves split the tile's pixels, workgroups keep
 //             their accumulators over several tiles, partial sums are added by
 //             a second kernel in FIXED order: bitwise reproducible.
+// The data gradient (first_dgrad_kernel, at the end of this file) is shaped by
+// bandwidth, not by the matrix pipe, and runs on the vector ALUs.
 #include "conv_host.h"
 #include <stdlib.h>
 
@@ -439,5 +442,107 @@ int first_wgrad_launch(const float *x, int B, int C, int H, int W, const float *
                        (const float *)ws, G, ncb * 32, P.K, dW, dbias);
     DVSOF_LAUNCH_CHECK();
     conv_note_kernel(DVSOF_KERNEL_FIRST, 0);
+    return DVSOF_OK;
+}
+
+// ===========================================================================
+// Data gradient: gV[b][c][iy][ix] = sum over (ky, kx, cout) of
+// gz[b][oy][ox][cout] * w[cout][ky][kx][c] with 2 oy - 1 + ky = iy and
+// 2 ox - 1 + kx = ix.  gz is the tensor first_wgrad_kernel consumes: the
+// gradient with respect to the layer's PRE-activation (the activation's
+// derivative was applied by the data gradient of the layer above).
+//
+// Stride 2 splits the input pixels by parity: an (even, even) pixel has one
+// contributing output pixel (the centre tap), (even, odd) and (odd, even) two,
+// (odd, odd) four -- times 64 channels.  33.5 MB read and 10.5 MB written at
+// batch 8, 256 x 256 x 5 against 0.75 GFLOP: the kernel is shaped by bandwidth
+// and uses plain f32 FMAs (exact f32 in every operand mode of the stack).
+// A thread owns the 2 x 2 input pixels (2 qy + {0,1}, 2 qx + {0,1}) of all C
+// planes: it reads the four output pixels (qy + {0,1}, qx + {0,1}) once, 16
+// bytes at a time, and the weights through wave-uniform addresses (one fetch
+// per wave).  Channels are added in ascending order: bitwise reproducible.
+// ===========================================================================
+namespace {
+
+constexpr int DG_NT = 256;
+
+template <int C>
+__global__ __launch_bounds__(DG_NT) void first_dgrad_kernel(const float *__restrict__ gz,
+                                                            const float *__restrict__ w, int B, int Ho,
+                                                            int Wo, float *__restrict__ gV)
+{
+    const int64_t q = (int64_t)blockIdx.x * DG_NT + threadIdx.x;
+    if (q >= (int64_t)B * Ho * Wo) return;
+    const int qx = (int)(q % Wo), qy = (int)((q / Wo) % Ho), b = (int)(q / ((int64_t)Wo * Ho));
+    const bool right = qx + 1 < Wo, below = qy + 1 < Ho;
+    // (a pixel outside the frame: the clamped address is read, zeros are used)
+    const float *g00 = gz + (((size_t)b * Ho + qy) * Wo + qx) * F_N;
+    const float *g01 = g00 + (right ? F_N : 0);
+    const float *g10 = g00 + (below ? (size_t)Wo * F_N : 0);
+    const float *g11 = g10 + (right ? F_N : 0);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    float a00[C], a01[C], a10[C], a11[C];       // input pixel (2 qy + i, 2 qx + j)
+#pragma unroll
+    for (int c = 0; c < C; ++c) a00[c] = a01[c] = a10[c] = a11[c] = 0.f;
+    for (int co4 = 0; co4 < F_N; co4 += 4) {
+        const f32x4 v00 = *(const f32x4 *)(g00 + co4);
+        const f32x4 v01 = right ? *(const f32x4 *)(g01 + co4) : zero;
+        const f32x4 v10 = below ? *(const f32x4 *)(g10 + co4) : zero;
+        const f32x4 v11 = right && below ? *(const f32x4 *)(g11 + co4) : zero;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float *wc = w + (size_t)(co4 + e) * 9 * C;    // [ky][kx][c], the same for the whole wave
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                // tap (ky, kx) = wc[(3 ky + kx) C + c]
+                a00[c] = __builtin_fmaf(v00[e], wc[4 * C + c], a00[c]);     // (1,1)
+                a01[c] = __builtin_fmaf(v00[e], wc[5 * C + c], a01[c]);     // (1,2) from ox = qx
+                a01[c] = __builtin_fmaf(v01[e], wc[3 * C + c], a01[c]);     // (1,0) from ox = qx + 1
+                a10[c] = __builtin_fmaf(v00[e], wc[7 * C + c], a10[c]);     // (2,1) from oy = qy
+                a10[c] = __builtin_fmaf(v10[e], wc[1 * C + c], a10[c]);     // (0,1) from oy = qy + 1
+                a11[c] = __builtin_fmaf(v00[e], wc[8 * C + c], a11[c]);     // (2,2)
+                a11[c] = __builtin_fmaf(v01[e], wc[6 * C + c], a11[c]);     // (2,0)
+                a11[c] = __builtin_fmaf(v10[e], wc[2 * C + c], a11[c]);     // (0,2)
+                a11[c] = __builtin_fmaf(v11[e], wc[0 * C + c], a11[c]);     // (0,0)
+            }
+        }
+    }
+    const int H = 2 * Ho, W = 2 * Wo;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        float *o = gV + (((size_t)b * C + c) * H + 2 * qy) * W + 2 * qx;   // 8-byte aligned: W, 2 qx even
+        *(f32x2 *)o = f32x2{a00[c], a01[c]};
+        *(f32x2 *)(o + W) = f32x2{a10[c], a11[c]};
+    }
+}
+
+template <int C>
+void first_dgrad_go(const float *gz, const float *w, int B, int Ho, int Wo, float *gV, hipStream_t st)
+{
+    const int64_t nq = (int64_t)B * Ho * Wo;
+    hipLaunchKernelGGL(first_dgrad_kernel<C>, dim3((unsigned)((nq + DG_NT - 1) / DG_NT)), dim3(DG_NT), 0, st,
+                       gz, w, B, Ho, Wo, gV);
+}
+
+}  // namespace
+
+extern "C" int dvsof_first_dgrad(const float *gz, const float *weight, int B, int C, int H, int W,
+                                 float *gV, void *stream)
+{
+    if (!gz || !weight || !gV || B < 1 || C < 1 || C > F_MAXC || H < 2 || W < 2 || (H & 1) || (W & 1))
+        return DVSOF_EINVAL;
+    if ((int64_t)B * (H / 2) * (W / 2) > (int64_t)0x7fffffff * DG_NT) return DVSOF_EINVAL;
+    if (((uintptr_t)gz & 15) || ((uintptr_t)gV & 7)) return DVSOF_EINVAL;
+    hipStream_t st = as_stream(stream);
+#define FIRST_DG(C_) case C_: first_dgrad_go<C_>(gz, weight, B, H / 2, W / 2, gV, st); break;
+    switch (C) {
+        FIRST_DG(1) FIRST_DG(2) FIRST_DG(3) FIRST_DG(4) FIRST_DG(5) FIRST_DG(6) FIRST_DG(7) FIRST_DG(8)
+        FIRST_DG(9) FIRST_DG(10) FIRST_DG(11) FIRST_DG(12) FIRST_DG(13) FIRST_DG(14) FIRST_DG(15)
+        FIRST_DG(16)
+    default: return DVSOF_EINVAL;
+    }
+#undef FIRST_DG
+    DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }

@@ -14,7 +14,7 @@ train_flownet.py:50-54,79-85 splits parameter groups on.
 import torch
 from torch import nn
 
-from . import voxel
+from . import learned_voxel, voxel
 from .predictor import Predictor
 
 
@@ -52,18 +52,44 @@ class VoxelGrid(nn.Module):
         return voxel.voxelize(events, t0, t1, batch, self.depth, height, width)
 
 
+class LearnedVoxelGrid(nn.Module):
+    """Learnable event representation (docs/LEARNED_VOXEL_SPEC.md): the voxel
+    grid with a learnable temporal kernel, a piecewise-linear lookup table of
+    ``2 * radius * knots_per_bin + 1`` knots (the form Gehrig et al., ICCV
+    2019, deploy their learned kernel in).  One parameter, ``kernel``,
+    initialised to the triangle kernel: an untrained layer gives ``VoxelGrid``.
+    Under ``no_grad`` (``Model.quantize``, offline quantisation, inference)
+    only the forward kernel runs."""
+
+    def __init__(self, depth, radius=2, knots_per_bin=8):
+        super().__init__()
+        self.depth, self.radius, self.knots_per_bin = depth, radius, knots_per_bin
+        self.kernel = nn.Parameter(
+            learned_voxel.initial_kernel(radius, knots_per_bin))
+
+    def forward(self, events, t0, t1, batch, height, width):
+        """events: the int64 wire columns or the compact 9 B/event columns."""
+        return learned_voxel.apply(self.kernel, events, t0, t1, self.radius,
+                                   self.knots_per_bin, batch, self.depth,
+                                   height, width)
+
+
 class Model(nn.Module):
     def __init__(self, device, prefix_length=0, suffix_length=0,
                  max_sequence_length=1, dynamic_sample_length=False,
                  event_representation_depth=9, activation=None,
-                 compute_dtype='f32'):
+                 compute_dtype='f32', learnable_representation=False,
+                 representation_radius=2, representation_knots=8):
         super().__init__()
         self.prefix_length = prefix_length
         self.suffix_length = suffix_length
         self.max_sequence_length = max_sequence_length
         self.dynamic_sample_length = dynamic_sample_length
         self.event_representation_depth = event_representation_depth
-        self.quantization_layer = VoxelGrid(event_representation_depth)
+        self.quantization_layer = LearnedVoxelGrid(
+            event_representation_depth, representation_radius,
+            representation_knots) if learnable_representation \
+            else VoxelGrid(event_representation_depth)
         self.predictor = Predictor(event_representation_depth, activation,
                                    compute_dtype)
         # strict=True reproduces the reference's host-side assertions (one

@@ -132,6 +132,19 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'f32) or bf16s (bf16 twins of activations / gradients / '
                              'weight forms streamed through LDS; master weights, '
                              'gradients of weights and optimizer state stay f32)')
+    parser.add_argument('--learnable-representation',
+                        dest='learnable_representation', action='store_true',
+                        help='learn the temporal kernel of the event representation '
+                             '(docs/LEARNED_VOXEL_SPEC.md: a piecewise-linear lookup '
+                             'table, initialised to the fixed voxel grid; it gets its '
+                             'own parameter group, whose learning rate stays 0 until '
+                             '--representation-start of the training steps)')
+    parser.add_argument('--representation-radius', dest='representation_radius',
+                        default=2, type=int, choices=[1, 2, 3],
+                        help='support of the learnable kernel in bins')
+    parser.add_argument('--representation-knots', dest='representation_knots',
+                        default=8, type=int, choices=list(range(1, 17)),
+                        help='knots per bin of the learnable kernel')
     parser.add_argument('--capture', action='store_true',
                         help='replay the loop body from one C call per micro-batch '
                              'once a batch signature has been seen (capture.CapturedLoop '
@@ -207,4 +220,8 @@ def options2model_kwargs(parameters):      # utils/options.py:341-347
     # (model.init_model filters by signature, utils/model.py:10-23)
     if getattr(parameters, 'compute_dtype', 'f32') != 'f32':
         kwargs['compute_dtype'] = parameters.compute_dtype
+    if getattr(parameters, 'learnable_representation', False):
+        kwargs['learnable_representation'] = True
+        kwargs['representation_radius'] = parameters.representation_radius
+        kwargs['representation_knots'] = parameters.representation_knots
     return kwargs

@@ -316,6 +316,9 @@ class _PredictorFn(torch.autograd.Function):
             ctx.raw16 = raw16       # made on the second stream, read on this one: alive until backward
             ctx.params = params
             ctx.module = module
+            # a learnable event representation (net.LearnedVoxelGrid) below the
+            # predictor: the backward then ends with enc.0's data gradient
+            ctx.grid_grad = ctx.needs_input_grad[0]
         return tuple(flows)
 
     @staticmethod
@@ -549,8 +552,14 @@ class _PredictorFn(torch.autograd.Function):
         red_ = getattr(ctx.module, 'reducer', None)
         alone_ = red_ is None or not red_.active()   # (under the exchange marks 2 again: 2.72 vs 2.84 ms)
         n_side = int(os.environ.get('DVSOF_ENC_SIDE_FROM', '3' if ctx.module.mfma == 0 and alone_ else '2'))
+        g_grid = None
         for i in (3, 2, 1, 0):
             lay = enc_l[i]
+            if i == 0 and ctx.grid_grad:
+                # gz is d/d(pre-activation) of enc.0 (the layer above applied act'), the
+                # tensor the weight gradient below reads.  Ahead of that weight gradient:
+                # its bucket may be updated as soon as it closes (optim.fuse_into_backward)
+                g_grid = C.first_dgrad(gz, _phys(params[0]), B, Cin, H, W)
             item = (lay['desc'], gz, grads[2 * i], grads[2 * i + 1], ('enc', i),
                     gz16)
             if i >= n_side:
@@ -578,7 +587,7 @@ class _PredictorFn(torch.autograd.Function):
                 main.wait_stream(s_)
         del keep
         ctx.L = None
-        return (None,) * (3 + len(params))
+        return (g_grid,) + (None,) * (2 + len(params))
 
 
 class Predictor(nn.Module):
@@ -791,8 +800,8 @@ class Predictor(nn.Module):
         assert H % 16 == 0 and W % 16 == 0, \
             'the predictor needs H and W divisible by 16'
         params = self.param_list()
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad
-                                                    for p in params)
+        want_grad = torch.is_grad_enabled() and (
+            voxels.requires_grad or any(p.requires_grad for p in params))
         return _PredictorFn.apply(voxels.contiguous(), self, want_grad,
                                   *params)
 

@@ -243,13 +243,17 @@ class _StepClock:
 CAPTURE_PROTOCOL = ('begin_capture', 'advance', 'end_capture')
 
 
-def capture_refusal(optimizer, is_raw):
+def capture_refusal(optimizer, is_raw, model=None):
     """Why ``train(capture=True)`` cannot replay its steps (None: it can)."""
     if not all(hasattr(optimizer, m) for m in CAPTURE_PROTOCOL):
         return (f'optimizer {type(optimizer).__name__} has no begin_capture / advance / '
                 'end_capture (optim.FusedAdamW, FusedRAdam and FusedRanger do)')
     if not is_raw:
         return 'is_raw=False batches (preprocessed voxel grids) are not captured'
+    layer = getattr(model, 'quantization_layer', None)
+    if layer is not None and any(True for _ in layer.parameters()):
+        return ('the event representation has parameters (net.LearnedVoxelGrid): the '
+                'captured step does not carry their gradient and update')
     return None
 
 
@@ -274,8 +278,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                another signature runs the same body eagerly; more events than
                the captured buffers hold re-records at a larger capacity; if
                recording fails training continues eagerly.  An optimizer
-               without begin_capture / advance / end_capture, or
-               is_raw=False, runs the eager loop and says so on stderr
+               without begin_capture / advance / end_capture, is_raw=False
+               or a model whose event representation has parameters runs the
+               eager loop and says so on stderr
     """
     if timers is None:
         on_gpu = torch.device(device).type == 'cuda'
@@ -284,7 +289,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                        init_samples_passed)
     sums = ScaleSums()
     captured = None
-    refused = capture_refusal(optimizer, is_raw) if capture else None
+    refused = capture_refusal(optimizer, is_raw, model) if capture else None
     if refused:
         import sys
         print(f'capture: not used, the loop runs eagerly: {refused}', file=sys.stderr)

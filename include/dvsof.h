@@ -121,6 +121,84 @@ int dvsof_voxelize_encoded(const int16_t *x, const int16_t *y, const float *t,
                            int32_t *bin0, int64_t *lin0, void *workspace,
                            size_t workspace_bytes, int flags, void *stream);
 
+/*
+ * LEARNABLE event representation (csrc/learned_voxel.hip,
+ * docs/LEARNED_VOXEL_SPEC.md): the grid above with the triangle kernel replaced
+ * by a piecewise-linear lookup table theta[K], K = 2*R*S + 1 float32 knots
+ * (R = radius in bins, 1..3; S = knots per bin, 1..16; knot j at offset
+ * j/S - R bins).  Drop rule, windows, tn and the polarity sign are those of
+ * dvsof_voxelize_fwd; an event adds sign * (theta[j]*(1-g) + theta[j+1]*g) to
+ * every bin c with 0 <= u = ((tn - c) + R) * S < 2*R*S, j = floor(u), g = u - j.
+ * With theta[j] = max(0, 1 - |j/S - R|) that is the grid of dvsof_voxelize_fwd.
+ * Upstream's learnable quantization layer lives in the absent EV_FlowNet
+ * submodule (train_flownet.py:50-54,79-99 only splits its parameter group and
+ * schedules its learning rate): parity unpinned, the spec is this build's.
+ *
+ * out[B,C,H,W] is zeroed by the call (a fill kernel: a stream capture holds
+ * kernel nodes only), then one thread per event adds with memory-side float
+ * atomics: the sum of a voxel depends on the order of its addends, inside the
+ * bound the spec derives.  n_events may be 0 (zeros).  No workspace.
+ */
+int dvsof_learned_voxelize_fwd(const int64_t *x, const int64_t *y,
+                               const float *t, const int64_t *polarity,
+                               const int64_t *sample_index, int64_t n_events,
+                               const float *t0, const float *t1,
+                               const float *theta, int R, int S, int B, int C,
+                               int H, int W, float *out, void *stream);
+
+/* The same kernel body over the 9 B/event ENCODED columns and
+ * sample_event_offsets[B+1] (see dvsof_voxelize_encoded). */
+int dvsof_learned_voxelize_encoded(const int16_t *x, const int16_t *y,
+                                   const float *t, const uint8_t *polarity,
+                                   const int64_t *sample_event_offsets,
+                                   int64_t n_events, const float *t0,
+                                   const float *t1, const float *theta, int R,
+                                   int S, int B, int C, int H, int W,
+                                   float *out, void *stream);
+
+/*
+ * Gradient with respect to the table: for every kept (event, bin)
+ *   gtheta[j]   += sign * gV[b,c,y,x] * (1-g)
+ *   gtheta[j+1] += sign * gV[b,c,y,x] * g
+ * gV[B,C,H,W] is the gradient of the grid; gtheta[K] is WRITTEN (zeros for
+ * n_events = 0).  There is no gradient to events or timestamps.
+ * encoded = 0: x, y, polarity are the int64 wire columns and `sample` is
+ * sample_index[n]; encoded = 1: int16 x, int16 y, uint8 polarity and `sample`
+ * is sample_event_offsets[B+1].
+ * Fixed-order reduction, no float atomics, bitwise reproducible: a thread adds
+ * its events in ascending order, a wave's threads are combined by a shuffle
+ * tree, a block's waves in order into part[block][K] (the workspace), and a
+ * closing kernel adds the partials in block order in float64 and rounds once.
+ * dvsof_learned_voxelize_bwd_blocks(n) is the number of blocks (128 threads
+ * each) the call uses for n events: with it the longest chain of float32
+ * additions a term passes through is known to the caller (the spec's `m`).
+ */
+size_t dvsof_learned_voxelize_bwd_workspace_bytes(int64_t n_events, int R,
+                                                  int S);
+int dvsof_learned_voxelize_bwd_blocks(int64_t n_events);
+int dvsof_learned_voxelize_bwd(const void *x, const void *y, const float *t,
+                               const void *polarity, const int64_t *sample,
+                               int encoded, int64_t n_events, const float *t0,
+                               const float *t1, int R, int S, int B, int C,
+                               int H, int W, const float *gV, float *gtheta,
+                               void *workspace, size_t workspace_bytes,
+                               void *stream);
+
+/*
+ * Data gradient of the first encoder layer (enc.0: 3x3, stride 2, pad 1, C
+ * planar input channels, 1..16, 64 NHWC output channels; csrc/first.hip) --
+ * what a learnable representation needs below the predictor:
+ *   gV[b,c,iy,ix] = sum gz[b,oy,ox,co] * weight[co][ky][kx][c]
+ *   over 2*oy - 1 + ky = iy, 2*ox - 1 + kx = ix, co in [0,64).
+ * gz[B,H/2,W/2,64] is the gradient with respect to the layer's PRE-activation
+ * (the tensor its weight gradient consumes: the activation's derivative is
+ * already applied); weight is the physical [64][3][3][C] buffer; gV[B,C,H,W]
+ * is written, not accumulated.  H and W even; gz 16-byte aligned.  Exact f32
+ * FMAs in every operand mode, channels added in ascending order.
+ */
+int dvsof_first_dgrad(const float *gz, const float *weight, int B, int C,
+                      int H, int W, float *gV, void *stream);
+
 /* ------------------------------------------------------------------ *
  * Data augmentation on the device: horizontal
  * flip -> nearest-neighbour LUT rotation about the frame centre -> crop, the

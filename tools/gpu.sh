@@ -13,6 +13,8 @@
 #   eval [eval_bench.py args]        testing.evaluate on a synthetic MVSEC-shaped sequence: frames/s at batch 1 and 8,
 #                                     the reference's per-frame structure on the host, the three kernels alone
 #                                     the same frames from a device-resident EventSequence, the window kernel alone
+#   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
+#                                     enc.0 data gradient, eager step with and without it (tools/learned_voxel_bench.py)
 #   lossprobe B H W bits...           loss path under the probe build's DVSOF_LOSS_DBG bits
 #   timeline [bench args]             rocprofv3 kernel trace of a short run -> one step per queue
 #   feedtrace [wire|compact]          kernel + memory-copy trace of the train loop fed from host memory
@@ -57,6 +59,9 @@ optim)
 eval)
   timeout -k 10 560 env "${envs[@]}" python tools/eval_bench.py "$@" > $O/eval.json 2> $O/eval.err
   echo "eval rc=$?"; cut -c1-2600 $O/eval.json; tail -3 $O/eval.err ;;
+learned)
+  timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
+  echo "learned rc=$?"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err ;;
 lossprobe)
   B=$1; H=$2; W=$3; shift 3
   for bits in "$@"; do echo -n "DBG=$bits: "; DVSOF_LOSS_DBG=$bits DVSOF_PROBE_LIB=1 timeout -k 10 120 python tools/loss_probe.py $B $H $W 2>&1 | tail -1; done ;;

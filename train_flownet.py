@@ -157,6 +157,9 @@ def main(argv=None):
     timers = EventTimer() if (args.timers and device.type == 'cuda') \
         else FakeTimer()
 
+    if world > 1 and getattr(args, 'learnable_representation', False):
+        raise SystemExit('--learnable-representation trains in one process: its '
+                         'gradient is not part of the gradient exchange yet')
     model = init_model(args, device)
     parallel.broadcast_parameters(model)
     optimizer, scheduler = construct_train_tools(args, model)
