@@ -98,6 +98,10 @@ _SIGNATURES = {
     'dvsof_learned_voxelize_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64,
                                         _vp, _vp, _i, _i, _i, _i, _i, _i, _vp,
                                         _vp, _vp, _sz, _vp]),
+    'dvsof_learned_voxelize_bwd_into': (_i, [_vp, _vp, _vp, _vp, _vp, _i,
+                                             _i64, _vp, _vp, _i, _i, _i, _i,
+                                             _i, _i, _vp, _vp, _i, _vp, _sz,
+                                             _vp]),
     'dvsof_first_dgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'dvsof_resize_bilinear_ac': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'dvsof_loss_workspace_bytes': (_sz, [ctypes.POINTER(LossScale), _i, _i]),

@@ -16,6 +16,10 @@ batch signature (batch size, frame size, event capacity) and replays it:
     control words clean up after themselves, the loss needs no zero-fill), all
     scratch comes from the graph's private pool, gradient buckets and
     optimizer tables are the persistent ones the eager warm-up step made;
+    a learnable event representation is captured when it is RESIDENT
+    (net.LearnedVoxelGrid.make_resident: the gradient of its knots lives in
+    a persistent slot, its reduction scratch in a persistent workspace, and
+    under a reducer the slot is the step's last bucket);
   * what changes per step is read from device memory: the scheduled learning
     rate and what the step count decides -- Adam's bias corrections; RAdam's
     step size and rectification, Ranger's Lookahead synchronisation (the
@@ -337,6 +341,15 @@ class CapturedTrainStep:
         it is unset (after a replay Python does not know what the graph wrote;
         an eager accumulating micro-batch must find the buckets attached)."""
         self.model.predictor.attach_bucket_grads()
+        layer = self._resident_layer()
+        if layer is not None:
+            layer.attach_grad()     # ... and the knots' gradient slot
+
+    def _resident_layer(self):
+        """The event representation when it has parameters and keeps their
+        gradient resident (net.LearnedVoxelGrid.make_resident), else None."""
+        layer = getattr(self.model, 'quantization_layer', None)
+        return layer if getattr(layer, 'capture_ready', False) else None
 
     def _record(self, executor):
         model, optimizer, dev = self.model, self.optimizer, self.device
@@ -347,6 +360,12 @@ class CapturedTrainStep:
                       list(voxel._WORKSPACES.values()),
                       list(getattr(model.predictor, '_bucket_flat', [])),
                       dict(optimizer._tables), self.static]
+        layer = self._resident_layer()
+        if layer is not None:
+            # the reduction workspace grows HERE, eagerly, to what the input buffers hold;
+            # the recording then finds it large enough and takes its address
+            layer.resident.reserve(self.static['events']['x'].numel())
+            self._keep.append(layer.resident.tensors())
         optimizer.begin_capture(dev)
         self.graph = torch.cuda.CUDAGraph(keep_graph=True) if executor \
             else torch.cuda.CUDAGraph()

@@ -169,12 +169,10 @@ __global__ __launch_bounds__(BNT) void lv_bwd_kernel(const Cols cols, const LvP 
     }
 }
 
-// gtheta[k] = the partials of knot k added in block order in float64, rounded once
-__global__ __launch_bounds__(kWave) void lv_bwd_final_kernel(const float *__restrict__ part, int G,
-                                                             int K, float *__restrict__ gtheta)
+// the partials of knot k added in block order in float64, rounded once: the closing sum of
+// BOTH exports (their bitwise equality is this one function)
+__device__ __forceinline__ float block_order_sum(const float *__restrict__ part, int G, int K, int k)
 {
-    const int k = blockIdx.x * kWave + threadIdx.x;
-    if (k >= K) return;
     double s = 0.0;
     int g = 0;
     for (; g + 8 <= G; g += 8) {        // eight loads in flight, added in order
@@ -185,7 +183,29 @@ __global__ __launch_bounds__(kWave) void lv_bwd_final_kernel(const float *__rest
         for (int u = 0; u < 8; ++u) s += (double)v[u];
     }
     for (; g < G; ++g) s += (double)part[(size_t)g * K + k];
-    gtheta[k] = (float)s;
+    return (float)s;
+}
+
+__global__ __launch_bounds__(kWave) void lv_bwd_final_kernel(const float *__restrict__ part, int G,
+                                                             int K, float *__restrict__ gtheta)
+{
+    const int k = blockIdx.x * kWave + threadIdx.x;
+    if (k >= K) return;
+    gtheta[k] = block_order_sum(part, G, K, k);
+}
+
+// The closing kernel of the RESIDENT gradient slot (dvsof_learned_voxelize_bwd_into): the same
+// sum s, WRITTEN (accumulate = 0) or added to what the slot holds (accumulate = 1: one float32
+// add, the rounding of autograd's `grad += g`).  G = 0 (no events) writes zeros; the accumulating
+// call with no events is not launched at all, so that a slot holding -0.0 keeps its bits.
+__global__ __launch_bounds__(kWave) void lv_bwd_final_into_kernel(const float *__restrict__ part,
+                                                                  int G, int K, float *gtheta,
+                                                                  int accumulate)
+{
+    const int k = blockIdx.x * kWave + threadIdx.x;
+    if (k >= K) return;
+    const float r = block_order_sum(part, G, K, k);
+    gtheta[k] = accumulate ? gtheta[k] + r : r;
 }
 
 int fwd_blocks(int64_t n) { return (int)((n + NT - 1) / NT < 2048 ? (n + NT - 1) / NT : 2048); }
@@ -232,6 +252,29 @@ int launch_bwd(const Cols &cols, const LvP &P, const float *gV, float *gtheta, v
     DVSOF_LAUNCH_CHECK();
     hipLaunchKernelGGL(lv_bwd_final_kernel, dim3((K + kWave - 1) / kWave), dim3(kWave), 0, st,
                        (const float *)part, G, K, gtheta);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+// Kernels only (no fill, no memset, no copy): what a stream capture may hold.
+template <class Cols>
+int launch_bwd_into(const Cols &cols, const LvP &P, const float *gV, float *gtheta, int accumulate,
+                    void *workspace, size_t workspace_bytes, hipStream_t st)
+{
+    const int K = 2 * P.R * P.S + 1;
+    if (P.n == 0 && accumulate) return DVSOF_OK;       // gtheta + 0 would turn -0.0 into +0.0
+    int G = 0;
+    float *part = (float *)workspace;
+    if (P.n > 0) {
+        if (!workspace || workspace_bytes < dvsof_learned_voxelize_bwd_workspace_bytes(P.n, P.R, P.S))
+            return DVSOF_ENOSPACE;
+        G = bwd_blocks(P.n);
+        hipLaunchKernelGGL(lv_bwd_kernel<Cols>, dim3(G), dim3(BNT), sizeof(float) * BNT * K, st, cols,
+                           P, gV, part);
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lv_bwd_final_into_kernel, dim3((K + kWave - 1) / kWave), dim3(kWave), 0, st,
+                       (const float *)part, G, K, gtheta, accumulate ? 1 : 0);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
@@ -284,6 +327,23 @@ int dvsof_learned_voxelize_bwd(const void *x, const void *y, const float *t, con
                           P, gV, gtheta, workspace, workspace_bytes, as_stream(stream));
     return launch_bwd(WireCols{(const int64_t *)x, (const int64_t *)y, (const int64_t *)pol, sample}, P, gV,
                       gtheta, workspace, workspace_bytes, as_stream(stream));
+}
+
+int dvsof_learned_voxelize_bwd_into(const void *x, const void *y, const float *t, const void *pol,
+                                    const int64_t *sample, int encoded, int64_t n, const float *t0,
+                                    const float *t1, int R, int S, int B, int C, int H, int W,
+                                    const float *gV, float *gtheta, int accumulate, void *workspace,
+                                    size_t workspace_bytes, void *stream)
+{
+    if (!gV || !gtheta || !t0 || !t1 || bad_shape(n, B, C, H, W, R, S)) return DVSOF_EINVAL;
+    if (accumulate != 0 && accumulate != 1) return DVSOF_EINVAL;
+    if (n > 0 && (!x || !y || !t || !pol || !sample)) return DVSOF_EINVAL;
+    const LvP P = params(t, n, t0, t1, nullptr, B, C, H, W, R, S);
+    if (encoded)
+        return launch_bwd_into(EncodedCols{(const int16_t *)x, (const int16_t *)y, (const uint8_t *)pol, sample, B},
+                               P, gV, gtheta, accumulate, workspace, workspace_bytes, as_stream(stream));
+    return launch_bwd_into(WireCols{(const int64_t *)x, (const int64_t *)y, (const int64_t *)pol, sample}, P,
+                           gV, gtheta, accumulate, workspace, workspace_bytes, as_stream(stream));
 }
 
 }  // extern "C"

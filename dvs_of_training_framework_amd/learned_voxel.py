@@ -93,6 +93,37 @@ def voxelize_bwd(events, t0, t1, radius, knots_per_bin, grad_grid):
     return gtheta
 
 
+def workspace_floats(n_events, radius, knots_per_bin):
+    """Floats of reduction scratch ``voxelize_bwd_into`` needs for ``n_events``
+    (non-decreasing in ``n_events``)."""
+    nbytes = _lib.lib().dvsof_learned_voxelize_bwd_workspace_bytes(
+        int(n_events), radius, knots_per_bin)
+    return max(nbytes // 4, 4)
+
+
+def voxelize_bwd_into(events, t0, t1, radius, knots_per_bin, grad_grid, gtheta,
+                      accumulate, workspace):
+    """The gradient of ``voxelize_bwd`` into the caller's persistent
+    ``gtheta`` (float32[2*R*S+1]): written (``accumulate`` false: the bits of
+    ``voxelize_bwd``) or added to what it holds by one float32 add.
+    ``workspace``: float32 scratch of at least ``workspace_floats(n, R, S)``
+    elements, the caller's too.  Allocates nothing and enqueues kernels only."""
+    B, C, H, W = grad_grid.shape
+    _lib.require_cuda(grad_grid, t0, t1, gtheta, workspace)
+    x, y, t, p, s, encoded = _columns(events, t0.device)
+    _lib.require_cuda(x, y, t, p, s)
+    assert grad_grid.dtype == torch.float32 and grad_grid.is_contiguous()
+    assert gtheta.dtype == torch.float32 and gtheta.is_contiguous() and \
+        gtheta.numel() == num_knots(radius, knots_per_bin)
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous()
+    _lib.check(_lib.lib().dvsof_learned_voxelize_bwd_into(
+        x.data_ptr(), y.data_ptr(), t.data_ptr(), p.data_ptr(), s.data_ptr(),
+        encoded, x.numel(), t0.contiguous().data_ptr(), t1.contiguous().data_ptr(),
+        radius, knots_per_bin, B, C, H, W, grad_grid.data_ptr(), gtheta.data_ptr(),
+        1 if accumulate else 0, workspace.data_ptr(), workspace.numel() * 4,
+        _lib.stream()), 'dvsof_learned_voxelize_bwd_into')
+
+
 def reduction_chain(n_events, knots_per_bin):
     """``m`` of docs/LEARNED_VOXEL_SPEC.md: the longest chain of float32
     roundings a term of the table's gradient passes through."""
@@ -116,9 +147,92 @@ class _LearnedVoxelFn(torch.autograd.Function):
         return (g,) + (None,) * 9
 
 
-def apply(theta, events, t0, t1, radius, knots_per_bin, B, C, H, W):
+class ResidentGrad:
+    """Persistent home of the table's gradient (net.LearnedVoxelGrid.
+    make_resident): ``slot`` float32[K], the SAME tensor every step -- what
+    ``theta.grad`` is, what the optimizer's pointer table, a captured step and
+    the gradient exchange point at -- and the reduction ``workspace``, regrown
+    eagerly (never inside a stream capture) when a batch outgrows it."""
+
+    def __init__(self, radius, knots_per_bin, device, event_capacity=None):
+        self.radius, self.knots_per_bin = radius, knots_per_bin
+        self.slot = torch.zeros(num_knots(radius, knots_per_bin),
+                                dtype=torch.float32, device=device)
+        self.workspace, self.capacity = None, 0
+        self.reserve(event_capacity or 4096)
+
+    def reserve(self, n_events):
+        """Room for the reduction over ``n_events`` events."""
+        need = workspace_floats(n_events, self.radius, self.knots_per_bin)
+        if self.workspace is None or self.workspace.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(
+                    f'the resident reduction workspace holds {self.capacity} events and the '
+                    f'captured batch brings {n_events}: reserve() before recording')
+            self.workspace = torch.empty(need, dtype=torch.float32,
+                                         device=self.slot.device)
+        self.capacity = max(self.capacity, int(n_events))
+
+    def owns(self, grad):
+        return grad is not None and grad.data_ptr() == self.slot.data_ptr()
+
+    def attach(self, theta):
+        """``theta.grad`` = the slot where it is unset (Python's view of what a
+        replayed micro-batch that only wrote or accumulated gradients did)."""
+        if theta.grad is None:
+            theta.grad = self.slot
+
+    def tensors(self):
+        return [self.slot, self.workspace]
+
+    def backward(self, theta, events, t0, t1, grad_grid, reducer=None):
+        accumulate = self.owns(theta.grad)
+        assert accumulate or theta.grad is None, \
+            'a resident representation owns kernel.grad (found a foreign gradient tensor)'
+        self.reserve(events['x'].numel())
+        voxelize_bwd_into(events, t0, t1, self.radius, self.knots_per_bin,
+                          grad_grid.contiguous().float(), self.slot, accumulate,
+                          self.workspace)
+        if not accumulate:
+            theta.grad = self.slot
+        # the last bucket of the step, behind enc.0's: every rank hands it over in every
+        # launch mode (the reducer leaves a mark under capture), whatever its batch held
+        if reducer is not None and reducer.active():
+            reducer.bucket_ready(self.slot)
+
+
+class _ResidentVoxelFn(torch.autograd.Function):
+    """The learned grid with the table's gradient kept by ``resident``
+    (ResidentGrad): backward writes / accumulates ``theta.grad`` itself and
+    hands autograd nothing."""
+
+    @staticmethod
+    def forward(ctx, theta, resident, reducer_of, events, t0, t1, B, C, H, W):
+        ctx.args = (theta, resident, reducer_of, events, t0, t1)
+        return voxelize(events, t0, t1, theta.detach(), resident.radius,
+                        resident.knots_per_bin, B, C, H, W)
+
+    @staticmethod
+    def backward(ctx, grad_grid):
+        theta, resident, reducer_of, events, t0, t1 = ctx.args
+        if ctx.needs_input_grad[0]:
+            # the reducer in effect NOW, as the predictor's backward reads its own
+            reducer = reducer_of() if reducer_of is not None else None
+            resident.backward(theta, events, t0, t1, grad_grid, reducer)
+        return (None,) * 10
+
+
+def apply(theta, events, t0, t1, radius, knots_per_bin, B, C, H, W,
+          resident=None, reducer_of=None):
     """Differentiable with respect to ``theta`` only (no gradient to event
-    coordinates or timestamps).  Without grad mode only the forward runs."""
+    coordinates or timestamps).  Without grad mode only the forward runs.
+    resident: ResidentGrad -- the gradient goes to its persistent slot (and
+    from there to the parallel.GradReducer that ``reducer_of()`` returns when
+    the backward runs) instead of to autograd."""
+    if resident is not None and torch.is_grad_enabled() and theta.requires_grad:
+        assert (resident.radius, resident.knots_per_bin) == (radius, knots_per_bin)
+        return _ResidentVoxelFn.apply(theta, resident, reducer_of, events, t0, t1,
+                                      B, C, H, W)
     if torch.is_grad_enabled() and theta.requires_grad:
         return _LearnedVoxelFn.apply(theta, events, t0, t1, radius,
                                      knots_per_bin, B, C, H, W)

@@ -59,19 +59,88 @@ class LearnedVoxelGrid(nn.Module):
     2019, deploy their learned kernel in).  One parameter, ``kernel``,
     initialised to the triangle kernel: an untrained layer gives ``VoxelGrid``.
     Under ``no_grad`` (``Model.quantize``, offline quantisation, inference)
-    only the forward kernel runs."""
+    only the forward kernel runs.
+
+    RESIDENT mode (``make_resident``, off by default): ``kernel.grad`` lives in
+    one persistent device slot the backward kernel writes or accumulates into
+    (dvsof_learned_voxelize_bwd_into) instead of in a fresh tensor autograd
+    adds up.  That is what a captured step (capture.py) and the data-parallel
+    exchange need, and ``capture_ready`` says so.  The arithmetic is the
+    default mode's, bit for bit.  ``reducer`` (parallel.GradReducer) is read
+    when the backward runs, as the predictor reads its own: the layer's own
+    attribute, or -- inside a ``Model`` -- the predictor's (``exchange_with``)."""
+
+    capture_ready = False
 
     def __init__(self, depth, radius=2, knots_per_bin=8):
         super().__init__()
         self.depth, self.radius, self.knots_per_bin = depth, radius, knots_per_bin
         self.kernel = nn.Parameter(
             learned_voxel.initial_kernel(radius, knots_per_bin))
+        self.resident = None
+        self._reducer, self._exchange_owner = None, ()
+
+    def exchange_with(self, owner):
+        """The knots' gradient joins the exchange of ``owner.reducer`` (the
+        predictor: whatever reducer it has when the backward runs).  Kept in a
+        tuple: the owner is no submodule of this layer."""
+        self._exchange_owner = (owner,)
+
+    @property
+    def reducer(self):
+        """parallel.GradReducer the slot is handed to as the step's last bucket."""
+        for owner in self._exchange_owner:
+            return owner.reducer
+        return self._reducer
+
+    @reducer.setter
+    def reducer(self, value):
+        assert not self._exchange_owner, 'the reducer is the predictor\'s: set it there'
+        self._reducer = value
+
+    def make_resident(self, event_capacity=None):
+        """Allocate the gradient slot [K] and the reduction workspace (for
+        ``event_capacity`` events; regrown between steps when a batch brings
+        more) on the parameter's device, once.  -> self."""
+        if not self.kernel.is_cuda:
+            raise RuntimeError(
+                'the resident gradient of a learnable representation lives on the GPU '
+                f'(the layer is on {self.kernel.device}): there is no CPU implementation')
+        if self.resident is None:
+            self.resident = learned_voxel.ResidentGrad(
+                self.radius, self.knots_per_bin, self.kernel.device, event_capacity)
+            self.capture_ready = True
+        elif event_capacity:
+            self.resident.reserve(event_capacity)
+        return self
+
+    def attach_grad(self):
+        """``kernel.grad`` = the slot where it is unset: the counterpart of
+        ``Predictor.attach_bucket_grads`` for a replayed micro-batch."""
+        if self.resident is not None and self.kernel.requires_grad:
+            self.resident.attach(self.kernel)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        r = self.resident
+        if r is not None and r.slot.device != self.kernel.device:
+            # moved to another device: the slot follows (a gradient in flight does not);
+            # off the GPU there is no resident mode
+            self.kernel.grad = None
+            self.resident, self.capture_ready = None, False
+            if self.kernel.is_cuda:
+                self.make_resident(r.capacity)
+        return out
 
     def forward(self, events, t0, t1, batch, height, width):
         """events: the int64 wire columns or the compact 9 B/event columns."""
         return learned_voxel.apply(self.kernel, events, t0, t1, self.radius,
                                    self.knots_per_bin, batch, self.depth,
-                                   height, width)
+                                   height, width, resident=self.resident,
+                                   reducer_of=self._reducer_now)
+
+    def _reducer_now(self):
+        return self.reducer
 
 
 class Model(nn.Module):
@@ -79,7 +148,8 @@ class Model(nn.Module):
                  max_sequence_length=1, dynamic_sample_length=False,
                  event_representation_depth=9, activation=None,
                  compute_dtype='f32', learnable_representation=False,
-                 representation_radius=2, representation_knots=8):
+                 representation_radius=2, representation_knots=8,
+                 representation_resident=False):
         super().__init__()
         self.prefix_length = prefix_length
         self.suffix_length = suffix_length
@@ -98,6 +168,12 @@ class Model(nn.Module):
         self.last_frame_indices = None
         self._layout_cache, self._fast = {}, None
         self.to(device)
+        if representation_resident:
+            assert learnable_representation, \
+                'representation_resident needs learnable_representation'
+            self.quantization_layer.make_resident()
+            # its gradient joins the predictor's exchange (model.predictor.reducer)
+            self.quantization_layer.exchange_with(self.predictor)
 
     # ---- host/device bookkeeping -------------------------------------
     def _select(self, timestamps, sample_idx, batch):

@@ -145,6 +145,16 @@ def add_train_arguments(parser):           # utils/options.py:204-302
     parser.add_argument('--representation-knots', dest='representation_knots',
                         default=8, type=int, choices=list(range(1, 17)),
                         help='knots per bin of the learnable kernel')
+    parser.add_argument('--representation-resident',
+                        dest='representation_resident', action='store_true',
+                        help='with --learnable-representation: keep the gradient of '
+                             'the knots in a persistent device slot '
+                             '(net.LearnedVoxelGrid.make_resident).  Needed for '
+                             '--capture to replay such a model and for more than one '
+                             'process (the knots then join the gradient exchange); '
+                             'the learned forward sums with float atomics, so a '
+                             'replayed step equals its eager twin bit for bit only '
+                             'where no voxel receives two events')
     parser.add_argument('--capture', action='store_true',
                         help='replay the loop body from one C call per micro-batch '
                              'once a batch signature has been seen (capture.CapturedLoop '
@@ -224,4 +234,6 @@ def options2model_kwargs(parameters):      # utils/options.py:341-347
         kwargs['learnable_representation'] = True
         kwargs['representation_radius'] = parameters.representation_radius
         kwargs['representation_knots'] = parameters.representation_knots
+        if getattr(parameters, 'representation_resident', False):
+            kwargs['representation_resident'] = True
     return kwargs

@@ -110,9 +110,14 @@ class GradReducer:
         shares through the process group), created HERE -- a collective call,
         at a point every rank passes -- and used by the eager loop
         (``dvsof_allreduce_bucket`` on the exchange stream) and by the step
-        executor's marks alike.  Every closing micro-batch issues the same 8
+        executor's marks alike.  Every closing micro-batch issues the same
         bucket all-reduces in the same order whatever launch mode its rank is
-        in, which is all RCCL needs.
+        in, which is all RCCL needs: the predictor's 8 buckets
+        (Predictor.BUCKETS) and, with a resident learnable representation
+        (net.LearnedVoxelGrid.make_resident), a ninth -- the knots' gradient
+        slot, handed over by learned_voxel.ResidentGrad.backward after enc.0's
+        bucket whatever the batch held (an empty one included) and joined by
+        the same ``wait()``.
     direct=False  ``torch.distributed.all_reduce`` on the process group (gloo on
         the CPU tests; ``DVSOF_DIRECT_RCCL=0`` on a GPU for comparison runs --
         a captured step then switches the reducer to direct, see

@@ -251,7 +251,10 @@ def capture_refusal(optimizer, is_raw, model=None):
     if not is_raw:
         return 'is_raw=False batches (preprocessed voxel grids) are not captured'
     layer = getattr(model, 'quantization_layer', None)
-    if layer is not None and any(True for _ in layer.parameters()):
+    if layer is not None and any(True for _ in layer.parameters()) and \
+            not getattr(layer, 'capture_ready', False):
+        # (capture_ready: net.LearnedVoxelGrid.make_resident -- the gradient of the knots
+        # lives in a persistent slot the captured kernels write, strictly opt-in)
         return ('the event representation has parameters (net.LearnedVoxelGrid): the '
                 'captured step does not carry their gradient and update')
     return None
@@ -279,7 +282,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                the captured buffers hold re-records at a larger capacity; if
                recording fails training continues eagerly.  An optimizer
                without begin_capture / advance / end_capture, is_raw=False
-               or a model whose event representation has parameters runs the
+               or a model whose event representation has parameters (unless
+               it is resident: net.LearnedVoxelGrid.make_resident) runs the
                eager loop and says so on stderr
     """
     if timers is None:

@@ -185,6 +185,32 @@ int dvsof_learned_voxelize_bwd(const void *x, const void *y, const float *t,
                                void *stream);
 
 /*
+ * The same gradient into a RESIDENT slot gtheta[K] the caller keeps for the
+ * whole run (net.LearnedVoxelGrid.make_resident: the captured step and the
+ * gradient exchange need a gradient with a stable address).  The reduction is
+ * that of dvsof_learned_voxelize_bwd up to s = (float)(float64 block-order
+ * sum); the closing kernel then stores
+ *   accumulate = 0:  gtheta[j] = s            (the bits of ..._bwd)
+ *   accumulate = 1:  gtheta[j] = gtheta[j] + s   (ONE float32 add: the rounding
+ *                    of autograd's `grad += g` over micro-batches)
+ * Kernel launches only -- no memset, no copy, no float atomics -- so a stream
+ * capture holds nothing else.  n_events = 0: accumulate = 0 writes zeros,
+ * accumulate = 1 enqueues nothing (gtheta keeps its bits, -0.0 included).
+ * The workspace may be larger than needed (sized for a capacity with
+ * dvsof_learned_voxelize_bwd_workspace_bytes(capacity, R, S)): the number of
+ * blocks, and with it the order of the sum, follows n_events alone.
+ */
+int dvsof_learned_voxelize_bwd_into(const void *x, const void *y,
+                                    const float *t, const void *polarity,
+                                    const int64_t *sample, int encoded,
+                                    int64_t n_events, const float *t0,
+                                    const float *t1, int R, int S, int B,
+                                    int C, int H, int W, const float *gV,
+                                    float *gtheta, int accumulate,
+                                    void *workspace, size_t workspace_bytes,
+                                    void *stream);
+
+/*
  * Data gradient of the first encoder layer (enc.0: 3x3, stride 2, pad 1, C
  * planar input channels, 1..16, 64 NHWC output channels; csrc/first.hip) --
  * what a learnable representation needs below the predictor:

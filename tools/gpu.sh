@@ -14,7 +14,9 @@
 #                                     the reference's per-frame structure on the host, the three kernels alone
 #                                     the same frames from a device-resident EventSequence, the window kernel alone
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
-#                                     enc.0 data gradient, eager step with and without it (tools/learned_voxel_bench.py)
+#                                     enc.0 data gradient, eager step with and without it, executor replay of the
+#                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50
+#                                     (tools/learned_voxel_bench.py)
 #   lossprobe B H W bits...           loss path under the probe build's DVSOF_LOSS_DBG bits
 #   timeline [bench args]             rocprofv3 kernel trace of a short run -> one step per queue
 #   feedtrace [wire|compact]          kernel + memory-copy trace of the train loop fed from host memory
@@ -61,7 +63,11 @@ eval)
   echo "eval rc=$?"; cut -c1-2600 $O/eval.json; tail -3 $O/eval.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
-  echo "learned rc=$?"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err ;;
+  rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err
+  [ $rc -eq 0 ] || exit $rc       # nothing more on the GPU after a failed leg
+  # the resident model's replay against its eager loop under the loopback exchange (8 ranks, 50 us)
+  timeout -k 10 300 env "${envs[@]}" DVSOF_LOOPBACK=8:50 python tools/learned_voxel_bench.py --captured-only "$@" > $O/learned_loopback.json 2> $O/learned_loopback.err
+  echo "learned loopback rc=$?"; cut -c1-2000 $O/learned_loopback.json; tail -3 $O/learned_loopback.err ;;
 lossprobe)
   B=$1; H=$2; W=$3; shift 3
   for bits in "$@"; do echo -n "DBG=$bits: "; DVSOF_LOSS_DBG=$bits DVSOF_PROBE_LIB=1 timeout -k 10 120 python tools/loss_probe.py $B $H $W 2>&1 | tail -1; done ;;

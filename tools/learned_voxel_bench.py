@@ -1,13 +1,20 @@
 """Learnable event representation at the benchmark shape (batch 8, 256 x 256 x 5,
 65 536 events per sample), timed with HIP events: the learned forward against
 voxel.voxelize on the same events, the table-gradient kernel, dvsof_first_dgrad,
-and the eager training step with and without --learnable-representation.
+and the eager training step with and without --learnable-representation;
+``step_learnable_captured``: the RESIDENT model's step replayed by the step
+executor against the eager loop of an identical model, in alternating blocks
+(device time per step and host time to enqueue one).  With DVSOF_LOOPBACK=
+"world:delay_us" in the environment that leg runs under the loopback gradient
+exchange (``--captured-only`` runs nothing else).
 One JSON line on stdout.  ``--default-step-only`` measures just the default
 model's eager step: that part also runs on a checkout without the feature."""
 import argparse
 import json
+import os
 import statistics
 import sys
+import time
 from pathlib import Path
 
 import torch
@@ -63,6 +70,67 @@ def step_time(B, H, W, C, n, learnable, reps):
     return timed(step, reps, warmup=8)
 
 
+def captured_against_eager(B, H, W, C, n, reps, blocks=5):
+    """The resident learnable model: executor replay against its own eager
+    loop (two models from one seed, one resident batch), alternating blocks of
+    ``reps`` steps.  -> {'eager': ..., 'captured': ...}: median / min / max
+    device us per step and the host us it takes to enqueue a step."""
+    from dvs_of_training_framework_amd import parallel
+    from dvs_of_training_framework_amd.capture import CapturedTrainStep
+    from dvs_of_training_framework_amd.loss import unit_backward
+    red = parallel.GradReducer() if os.environ.get('DVSOF_LOOPBACK') else None
+    batch = synthetic.to_torch(synthetic.make_batch(1234, B, H, W, n), 'cuda')
+
+    def make():
+        torch.manual_seed(0)
+        model = Model('cuda', event_representation_depth=C, learnable_representation=True,
+                      representation_resident=True)
+        model.train()
+        model.predictor.reducer = red
+        return model, FusedRanger(model.parameters(), lr=1e-3), \
+            init_losses((H, W), B, model, 'cuda', sequence_length=1)
+    model_e, opt_e, ev_e = make()
+
+    def eager():
+        opt_e.zero_grad(set_to_none=True)
+        loss, _, _ = process_minibatch(model_e, batch, FakeTimer(), 'cuda', True, ev_e, [0.5, 1, 1])
+        unit_backward(loss)
+        model_e.strict = False
+        if red is not None:
+            red.wait()
+        opt_e.step()
+    model_c, opt_c, ev_c = make()
+    step = CapturedTrainStep(model_c, ev_c, opt_c, [0.5, 1, 1], 'cuda', batch, bind=True,
+                             reducer=red)
+    legs = (('eager', eager), ('captured', step))
+    for _ in range(12):         # calibration, then the executor settles on a lane plan
+        for _, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    dev, host = {k: [] for k, _ in legs}, {k: [] for k, _ in legs}
+    for _ in range(blocks):
+        for name, fn in legs:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t = time.perf_counter()
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            host[name].append((time.perf_counter() - t) * 1e6 / reps)
+            b.synchronize()
+            dev[name].append(a.elapsed_time(b) * 1e3 / reps)
+    out = {name: dict(us=round(statistics.median(dev[name]), 2), min=round(min(dev[name]), 2),
+                      max=round(max(dev[name]), 2),
+                      host_us=round(statistics.median(host[name]), 2)) for name, _ in legs}
+    out['plan'] = step.executor.plan()[0]
+    out['marks'] = step.executor.marks
+    out['exchange'] = os.environ.get('DVSOF_LOOPBACK') or None
+    step.close()
+    if red is not None:
+        red.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=8)
@@ -71,9 +139,14 @@ def main():
     ap.add_argument('--events', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--default-step-only', action='store_true')
+    ap.add_argument('--captured-only', action='store_true')
     a = ap.parse_args()
     B, H, W, C, n = a.batch, a.size, a.size, a.depth, a.events
     out = dict(shape=dict(B=B, H=H, W=W, C=C, events=B * n))
+    if a.captured_only:
+        out['step_learnable_captured'] = captured_against_eager(B, H, W, C, n, a.reps)
+        print(json.dumps(out))
+        return
     out['step_default'] = step_time(B, H, W, C, n, False, a.reps)
     if not a.default_step_only:
         from dvs_of_training_framework_amd import conv, learned_voxel as lv
@@ -96,6 +169,7 @@ def main():
         w = torch.randn(64, C, 3, 3, device='cuda').contiguous(memory_format=torch.channels_last)
         out['first_dgrad'] = share(timed(
             lambda: conv.first_dgrad(gz, w, B, C, H, W), a.reps), gz.numel() * 4 + grid_bytes)
+        out['step_learnable_captured'] = captured_against_eager(B, H, W, C, n, a.reps)
     print(json.dumps(out))
 
 

@@ -146,6 +146,22 @@ class _NullLogger:
         pass
 
 
+def check_representation_args(args, world):
+    """More than one process with a learnable representation needs the
+    resident gradient slot: that is what joins the gradient exchange."""
+    learn = getattr(args, 'learnable_representation', False)
+    resident = getattr(args, 'representation_resident', False)
+    if resident and not learn:
+        raise SystemExit('--representation-resident needs --learnable-representation')
+    if resident and torch.device(args.device).type != 'cuda':
+        raise SystemExit('--representation-resident keeps the gradient of the knots in a '
+                         f'device slot: it needs a GPU (--device {args.device})')
+    if world > 1 and learn and not resident:
+        raise SystemExit('--learnable-representation in more than one process needs '
+                         '--representation-resident: only the resident gradient of the '
+                         'knots is part of the gradient exchange')
+
+
 def main(argv=None):
     args = parse_args(sys.argv[1:] if argv is None else argv)
     device = torch.device(args.device)
@@ -157,9 +173,7 @@ def main(argv=None):
     timers = EventTimer() if (args.timers and device.type == 'cuda') \
         else FakeTimer()
 
-    if world > 1 and getattr(args, 'learnable_representation', False):
-        raise SystemExit('--learnable-representation trains in one process: its '
-                         'gradient is not part of the gradient exchange yet')
+    check_representation_args(args, world)
     model = init_model(args, device)
     parallel.broadcast_parameters(model)
     optimizer, scheduler = construct_train_tools(args, model)
