@@ -494,7 +494,7 @@ size_t dvsof_conv2d_wgrad_workspace_bytes(const dvsof_conv_desc_t *d)
     fill_wgrad(d, c, P);
     FlatWG F[3] = {};
     const int nflat = fill_flat(d, c, nullptr, F);
-    size_t n = wgrad_workspace_floats(P, true) + wgrad_flat_workspace_floats(F, nflat);
+    size_t n = wgrad_plan(P, F, nflat, true, true).total;
     if (c.wgrad == WG_FIRST) {
         const size_t nf = first_wgrad_workspace_floats(d->B, c.Ctot, d->H, d->W);
         if (nf > n) n = nf;
@@ -559,8 +559,7 @@ int dvsof_conv2d_wgrad(const dvsof_conv_desc_t *d, const float *gout, float *dwe
     P.gout = gout;
     FlatWG F[3] = {};
     const int nflat = skip_flat ? 0 : fill_flat(d, c, gout, F);
-    if (wgrad_workspace_floats(P, dbias != nullptr) + wgrad_flat_workspace_floats(F, nflat) > 0 && !ws)
-        return DVSOF_ENOSPACE;
+    // (a workspace that is missing or too small for this call's plan: DVSOF_ENOSPACE)
     return wgrad_launch(P, dweight, dbias, (float *)ws, ws_bytes / sizeof(float), F, nflat, st);
 }
 
@@ -601,6 +600,10 @@ int dvsof_conv2d_winograd_chain(const dvsof_conv_desc_t *d, int kind)
 // 2 when the LDS-DMA (v2) kernel serves this problem's vector members, else 1;
 // 3: the first-layer kernels (first.hip); 0: flat members only on the VALU kernel
 // (a property of the shape: a forward's residual is not known here)
+// kind 2 keeps a formula of its own, not the weight gradient's plan (wgrad_plan): the recorded
+// answers speak of the full-resolution frame of a sub-pixel layer (16 | 2 W, where the plan runs
+// v2 on its phases when 16 | W), answer 0 for every flat-only layer whether or not its members
+// take the flat kernels, and ignore what a call's pointers decide (patch-resident kernels)
 int dvsof_conv2d_kernel_generation(const dvsof_conv_desc_t *d, int kind)
 {
     const ConvClass c = conv_classify(d);
@@ -660,9 +663,7 @@ int dvsof_conv2d_tile_id(const dvsof_conv_desc_t *d, int kind)
     if (kind == 2) {
         WGradParams P = {};     // (unused member slots are zeros, not stack residue: _audit.audit_exchange reads these words)
         fill_wgrad(d, c, P);
-        int tile = 0;
-        wgrad_splits(P, &tile);
-        return tile;
+        return wgrad_plan(P, nullptr, 0, false, true).tile;
     }
     return DVSOF_EINVAL;
 }

@@ -16,7 +16,8 @@ enum ConvFwdForm { FWD_GENERAL, FWD_FIRST, FWD_WINO, FWD_MIN9, FWD_SUBPIXEL, FWD
 // layers), zero-inserted gout (other stride-2 layers), plain.
 enum ConvDgradForm { DG_PLAIN, DG_MIN9, DG_WINO, DG_SUBPIXEL, DG_PHASED2, DG_TRANSPOSED, DG_QUAD, DG_ZERO2 };
 // Weight gradient.  Precedence: transposed (through its adjoint) > Winograd > first layer >
-// general (wgrad_launch picks the kernel), as four phases for a sub-pixel layer.
+// general, as four phases for a sub-pixel layer.  What the general form launches is a WGradPlan
+// (below): wgrad_plan decides it once, wgrad_launch and the size queries read it.
 enum ConvWgradForm { WG_GENERAL, WG_TRANSPOSED, WG_WINO, WG_FIRST, WG_SUBPIXEL };
 
 struct ConvClass {
@@ -44,23 +45,65 @@ int gconv_pick_tile(long long m, long long n);
 bool gconv2_eligible(const GConvParams &P, long long max_src_bytes, long long w_bytes);
 int gconv2_launch(const GConvParams &P, int tile, hipStream_t st);
 
-// wgrad.hip / wgrad2.hip: the general weight gradient
+// ---- the general weight gradient: one plan per launch (wgrad_plan.hip) -----------------------
+enum WGVec { WGV_NONE, WGV_V1, WGV_V2, WGV_PATCH_TWINS, WGV_PATCH_F32, WGV_MIN9 };     // the vector members' kernel
+enum WGFlat { WGF_NONE, WGF_V1, WGF_OWN };     // the flat members: on the v1 tiles / kernels of their own (VALU or matrix cores)
+enum WGBias { WGB_NONE, WGB_VECTOR, WGB_COLSUM, WGB_FLAT };    // in the vector kernel (v2, patch, nine-product) /
+                                                               // column-sum pass / extra column of flat member 0
+enum WGReduce { WGR_NONE, WGR_SLABS, WGR_SUBPIXEL, WGR_PATCH };    // direct / slab sum / 2x2 phases -> 3x3 / 3x3 slabs
+constexpr int WG_COLSUM_BLOCKS = 512;   // most partial sums of the column-sum pass
+constexpr int WG_FLAT_BLOCKS = 512;     // ... and of a flat member's kernel
+constexpr int WG_MIN_CT = 64;           // input channels per workgroup of the nine-product kernel
+struct WGradPlan {
+    int rc;             // DVSOF_EINVAL: a vector member the kernels cannot read (the layout below is set all the same)
+    WGVec vec;
+    int tile, bn;       // v1 / v2: tile id (1..5) and its column width; the patch kernels: bn = their channel tile
+    int ntiles;         // column tiles of the vector members
+    int S, klen;        // K splits, pixels per split (multiple of BK)
+    WGFlat flat;
+    bool flat_mfma[3];  // WGF_OWN: flat member i takes the matrix-core kernel, else the VALU kernel
+    WGBias bias;
+    bool bias_tail;     // the vector kernel's per-slab bias partials ride on the reduce
+    WGReduce reduce;
+    int zg;             // WGR_SUBPIXEL: threads that share an output quad
+    // workspace, in floats: [slabs | bias or column-sum partials | flat member 0, 1, 2 partials]
+    size_t bias_off, flat_off[3], total;
+    int family, mode;   // what dvsof_conv2d_last_kernel reports
+};
+// Call mode (sizing = false) reads the call's pointers (twins bound, 16-byte alignment of gout and
+// the sources) and plans the launch.  Sizing mode knows the shape only: vec / flat / bias / reduce
+// stay unset, S is the largest any call of this shape can take, and total covers every such call.
+WGradPlan wgrad_plan(const WGradParams &P, const FlatWG *flat, int nflat, bool with_bias, bool sizing);
+// P.tile_begin = the column tiles, `width` columns each, of the chosen members (vector and / or
+// flat), cols_per_channel columns per channel; returns their number
+int wgrad_enumerate_tiles(WGradParams &P, int cols_per_channel, int width, bool vec, bool flat);
+bool wgrad_xcd_on();    // DVSOF_WGRAD_XCD != 0: XCD-aware workgroup order
+bool wgrad2_eligible(const WGradParams &P);      // what wgrad2_launch requires of its caller
+// wgrad.hip: runs the plan
 int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_floats,
                  const FlatWG *flat, int nflat, hipStream_t st);
-size_t wgrad_flat_workspace_floats(const FlatWG *flat, int nflat);
-size_t wgrad_workspace_floats(const WGradParams &P, bool with_bias);
-int wgrad_splits(const WGradParams &P0, int *tile_out);
-bool wgrad2_eligible(const WGradParams &P);
+// wgrad2.hip (also winograd.hip's component GEMMs, with their own split rule)
 int wgrad2_launch(const WGradParams &P, int tile, int ntiles, hipStream_t st);
-// wgrad_patch.hip: the decoder stages, input patch resident in LDS
-bool wgrad_patch_shape_ok(const WGradParams &P);
-bool wgrad_patch_eligible(const WGradParams &P);
-int wgrad_patch_splits(const WGradParams &P);
-int wgrad_patch_launch(const WGradParams &P, hipStream_t st);
+// wgrad_patch.hip: the decoder stages, input patch resident in LDS (twins or exact f32);
 // wgrad_min.hip: the nine-product form of the same gradient (exact f32)
-bool wgrad_min_ok(const WGradParams &P);
-int wgrad_min_splits(const WGradParams &P);
-int wgrad_min_launch(WGradParams &P, hipStream_t st);
+int wgrad_patch_launch(const WGradParams &P, bool f32, int ct, hipStream_t st);
+int wgrad_min_launch(const WGradParams &P, hipStream_t st);
+// the launch both share: KERNEL over (channel tiles of CT, Cout / 32, K splits)
+template <void (*KERNEL)(const WGradParams), int CT, int NT, int LDS>
+int wgrad_resident_launch(const WGradParams &P0, hipStream_t st)
+{
+    WGradParams P = P0;
+    const int nt = wgrad_enumerate_tiles(P, 1, CT, true, false);
+    static bool attr_set = false;
+    if (!attr_set) {
+        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        attr_set = true;
+    }
+    P.xcd = wgrad_xcd_on() ? 1 : 0;
+    hipLaunchKernelGGL(KERNEL, dim3(nt, P.Cout / 32, P.S), dim3(NT), LDS, st, P);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
 
 // winograd.hip: wide 3x3 stride-1 layers as F(2x2,3x3) / F(4x4,3x3)
 bool wino_eligible_shape(int nsrc, int layout_nhwc, int C, int N, int B, int H, int W, int ksize,

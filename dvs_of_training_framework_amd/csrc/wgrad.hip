@@ -14,7 +14,6 @@
 // lane (consecutive lanes -> consecutive banks); at 64 cycles per MFMA the
 // reads are far off the critical path.
 #include "conv_host.h"
-#include <stdio.h>
 #include <stdlib.h>
 
 
@@ -208,12 +207,10 @@ __global__ __launch_bounds__(CONV_NT) void wgrad_kernel(const WGradParams P)
     }
 }
 
-constexpr int COLSUM_MAX_BLOCKS = 512;
-
 int colsum_blocks(long long rows)
 {
     const long long nb = (rows + 127) / 128;
-    return (int)(nb < 1 ? 1 : nb > COLSUM_MAX_BLOCKS ? COLSUM_MAX_BLOCKS : nb);
+    return (int)(nb < 1 ? 1 : nb > WG_COLSUM_BLOCKS ? WG_COLSUM_BLOCKS : nb);
 }
 
 // part[block][c] = sum over this block's rows of g[row][c]   (g dense [rows][C]).
@@ -437,7 +434,6 @@ __global__ __launch_bounds__(256) void subpixel_fold_kernel(const float *__restr
 // needs neither the sub-pixel phases nor the MFMA tiles (an MFMA column tile
 // for 8..45 columns would run the whole K loop at <10 % utilisation).
 // HBM-bound: reads gout once.  part[block][co][NCOL], then a fixed-order sum.
-constexpr int FLAT_BLOCKS = 512;    // most partial sums of a flat member (workspace bound)
 constexpr int FLAT_PIX = 64;   // pixels staged per round
 
 
@@ -722,33 +718,16 @@ __global__ __launch_bounds__(256) void wgrad_flat_reduce_kernel(const float *__r
     }
 }
 
-bool flat_ncol_ok(int ncol)
-{
-    return ncol == 18 || ncol == 27 || ncol == 45 || ncol == 81 || ncol == 108;
-}
-
-// Does this flat member take the matrix-core kernel?
-// measured (batch 8): MFMA 33 vs VALU 46 us at M = 524288 / 18 columns, 39 vs 52 us at
-// M = 131072 / 45 columns; a tie at M = 131072 / 18 columns; VALU wins below
-bool flat_uses_mfma(const FlatWG &F)
-{
-    static const bool no_mfma = getenv("DVSOF_WGRAD_FLAT_VALU") != nullptr;
-    static const bool force_mfma = getenv("DVSOF_WGRAD_FLAT_MFMA") != nullptr;
-    const int ncb = (F.ncol + 31) / 32;
-    const bool big = F.M >= 262144 || (ncb == 2 && F.M >= 65536);
-    return !no_mfma && (big || force_mfma) && (F.Cout % 32) == 0 && ncb <= 2 && F.Wo >= 2;
-}
-
 // dbias != NULL (matrix-core kernel only, ncol % 32 != 0): the bias gradient comes out as
 // one more output column
-int flat_launch(const FlatWG &F, float *part, float *dW, float *dbias, hipStream_t st)
+int flat_launch(const FlatWG &F, bool mfma, float *part, float *dW, float *dbias, hipStream_t st)
 {
     const long long nbl = ((long long)F.M + FLAT_PIX - 1) / FLAT_PIX;
     int nb = (int)(nbl < 512 ? (nbl < 1 ? 1 : nbl) : 512);   // VALU kernel: 64 pixels per round
     const int ncb = (F.ncol + 31) / 32, nrb = F.Cout / 32;
     const int wb = dbias ? 1 : 0;
-    if (dbias && (!flat_uses_mfma(F) || (F.ncol % 32) == 0)) return DVSOF_EINVAL;
-    if (flat_uses_mfma(F)) {
+    if (dbias && (!mfma || (F.ncol % 32) == 0)) return DVSOF_EINVAL;
+    if (mfma) {
         // 8 waves per workgroup, >= PPW pixel pairs per wave, at most 512 partial sums
         static const int ppw = getenv("DVSOF_FLAT_PPW") ? atoi(getenv("DVSOF_FLAT_PPW")) : 32;
         const long long npair = ((long long)F.M + 1) / 2;
@@ -783,25 +762,11 @@ int flat_launch(const FlatWG &F, float *part, float *dW, float *dbias, hipStream
     return DVSOF_OK;
 }
 
-// column tiles of the members selected by `want_flat` (others get none)
-int enumerate_tiles(WGradParams &P, int bn, int want_flat /* -1: all */)
-{
-    const int taps = P.ks * P.ks;
-    int t = 0;
-    for (int s = 0; s < P.nsrc; ++s) {
-        P.tile_begin[s] = t;
-        if (want_flat < 0 || (P.src[s].flat != 0) == (want_flat != 0))
-            t += (taps * P.src[s].C + bn - 1) / bn;
-    }
-    P.tile_begin[P.nsrc] = t;
-    return t;
-}
-
 template <int WROWS, int WCOLS, int TM, int TN>
-int launch(WGradParams &P, int want_flat, hipStream_t st)
+int launch(WGradParams &P, bool vec, bool flat, hipStream_t st)
 {
     constexpr int BMc = WROWS * TM * 32, BN = WCOLS * TN * 32;
-    const int t = enumerate_tiles(P, BN, want_flat);
+    const int t = wgrad_enumerate_tiles(P, P.ks * P.ks, BN, vec, flat);
     if (t == 0) return DVSOF_OK;
     dim3 grid(t, (P.Cout + BMc - 1) / BMc, P.S * P.nph);
     hipLaunchKernelGGL((wgrad_kernel<WROWS, WCOLS, TM, TN>), grid, dim3(CONV_NT), 0, st, P);
@@ -809,178 +774,52 @@ int launch(WGradParams &P, int want_flat, hipStream_t st)
     return DVSOF_OK;
 }
 
-void tile_dims(int tile, int &bm, int &bn)
-{
-    switch (tile) {
-    case 1: bm = 128; bn = 128; break;
-    case 2: bm = 128; bn = 64; break;
-    case 3: bm = 64; bn = 64; break;
-    case 4: bm = 64; bn = 128; break;
-    default: bm = 32; bn = 128; break;
-    }
-}
-
-// (tile, K splits) by a small occupancy model.  A CU runs `slots` workgroups of a
-// tile at once (LDS ring footprint); workgroups are dealt round-robin to 256
-// CUs, so the launch ends when the fullest CU has worked through its k blocks:
-//   g(k) = full rounds of `slots` blocks + the last partial round, where a lone
-//   block on a CU only reaches ~80 % of the matrix rate.
-// Cost = (K steps per block + fixed prologue/epilogue) * g * step time / tile
-// efficiency + the slab write/read when there is more than one slab.
-// (Residual layers, 144 tiles of 128x128: S=4 -> 576 blocks on 512 slots ran
-// 123 us, S=3 -> 432 blocks 105 us.)
-int pick_tile_and_splits(const WGradParams &P, int *S_out)
-{
-    const int taps = P.ks * P.ks;
-    static const int cand[5] = {1, 4, 3, 5, 2};
-    static const int slots_of[6] = {0, 2, 3, 5, 3, 3};          // by tile id
-    // (64x64 is 2.6-3 % faster than 64x128 on the three wide decoder layers one at a time,
-    // tools/wgrad_sweep.sh, but beside the data-gradient stream the step then alternates
-    // between 2340 and 2470 samples/s from run to run; 64x128 gives a steady 2445)
-    static double eff_of[6] = {0, 0.85, 0.80, 0.70, 0.80, 0.65};
-    static bool eff_init = false;
-    if (!eff_init) {   // tuning: DVSOF_WGRAD_EFF="e1,e2,e3,e4,e5"
-        eff_init = true;
-        if (const char *e = getenv("DVSOF_WGRAD_EFF"))
-            sscanf(e, "%lf,%lf,%lf,%lf,%lf", &eff_of[1], &eff_of[2], &eff_of[3], &eff_of[4], &eff_of[5]);
-    }
-    int best = -1, bestS = 1;
-    double best_cost = 1e300;
-    const long long ksteps = (P.M + BK - 1) / BK;
-    for (int i = 0; i < 5; ++i) {
-        int bm, bn;
-        tile_dims(cand[i], bm, bn);
-        if (bm > 32 && bm / 2 >= P.Cout) continue;      // mostly padding rows
-        long long tiles = 0;
-        for (int s = 0; s < P.nsrc; ++s)
-            if (!P.src[s].flat) tiles += (taps * P.src[s].C + bn - 1) / bn;
-        if (tiles == 0)
-            for (int s = 0; s < P.nsrc; ++s) tiles += (taps * P.src[s].C + bn - 1) / bn;
-        const long long rows = (P.Cout + bm - 1) / bm;
-        tiles *= rows * P.nph;
-        const int slots = slots_of[cand[i]];
-        const double step_us = 2.0 * bm * bn * BK / (157.3e12 / 256) * 1e6 / eff_of[cand[i]];
-        int maxS = (int)((P.M + 511) / 512);              // >= 32 K steps per split
-        if (maxS > 64) maxS = 64;
-        if (maxS < 1) maxS = 1;
-        for (int S = 1; S <= maxS; ++S) {
-            const long long blocks = tiles * S;
-            const long long kmax = (blocks + 255) / 256;  // blocks on the fullest CU
-            const long long full = kmax / slots, r = kmax % slots;
-            const double g = (double)full * slots + (r == 1 ? 1.25 : (double)r);
-            const double steps = (double)((ksteps + S - 1) / S) + 4.0;
-            const double slab = (S * P.nph > 1)
-                                    ? 2.0 * S * P.nph * P.Cout * taps * (double)P.Cin_tot * 4.0 / 4e6
-                                    : 0.0;                 // us at ~4 TB/s
-            const double cost = steps * g * step_us + slab;
-            if (cost < best_cost) {
-                best_cost = cost;
-                best = cand[i];
-                bestS = S;
-            }
-        }
-    }
-    if (S_out) *S_out = bestS;
-    return best;
-}
-
 }  // namespace
 
-// Number of K splits used for this problem (deterministic in the shape).
-int wgrad_splits(const WGradParams &P0, int *tile_out)
-{
-    int S = 1;
-    int tile = pick_tile_and_splits(P0, &S);
-    if (wgrad_patch_eligible(P0)) {     // its own split rule (workgroups are K splits there)
-        if (tile_out) *tile_out = tile;
-        return wgrad_patch_splits(P0);
-    }
-    // tuning sweeps (tools/wgrad_sweep.sh): force the tile and / or the K splits
-    static const int tile_env = getenv("DVSOF_WGRAD_TILE") ? atoi(getenv("DVSOF_WGRAD_TILE")) : 0;
-    static const int s_env = getenv("DVSOF_WGRAD_SPLITS") ? atoi(getenv("DVSOF_WGRAD_SPLITS")) : 0;
-    if (tile_env >= 1 && tile_env <= 5) tile = tile_env;
-    if (s_env >= 1) {
-        const long long cap = (P0.M + BK - 1) / BK;
-        S = s_env > 64 ? 64 : s_env;
-        if (S > cap) S = (int)cap;
-    }
-    if (tile_out) *tile_out = tile;
-    return S;
-}
-
-// Internal entry: ws holds the nph*S slabs when needed, results go to dW/dbias.
-// In phase mode (nph = 4) dW is the folded [Cout][3][3][Cin_tot] gradient.
+// Internal entry: runs the plan of this call (wgrad_plan.hip) and decides nothing itself.  ws
+// holds the nph*S slabs when needed, results go to dW/dbias.  In phase mode (nph = 4) dW is the
+// folded [Cout][3][3][Cin_tot] gradient.
 int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_floats,
                  const FlatWG *flat, int nflat, hipStream_t st)
 {
-    for (int s = 0; s < P.nsrc; ++s)
-        if (!P.src[s].flat && (P.src[s].sc != 1 || (P.src[s].C & 3))) return DVSOF_EINVAL;
-    int tile;
-    const int S = wgrad_splits(P, &tile);
-    P.S = S;
-    const int nslab = S * P.nph;
-    const size_t wsize = (size_t)P.Cout * P.ks * P.ks * P.Cin_tot;
+    const WGradPlan pl = wgrad_plan(P, flat, nflat, dbias != nullptr, false);
+    if (pl.total > 0 && !ws) return DVSOF_ENOSPACE;
+    if (pl.rc) return pl.rc;
+    if (pl.total > ws_floats) return DVSOF_ENOSPACE;
+    P.S = pl.S;
+    P.klen = pl.klen;
+    const int nslab = pl.S * P.nph;
     const bool direct = nslab == 1;
-    const size_t need = (direct ? 0 : (size_t)nslab * wsize) +
-                        (dbias ? (size_t)COLSUM_MAX_BLOCKS * P.Cout : 0);
-    if (need + wgrad_flat_workspace_floats(flat, nflat) > ws_floats) return DVSOF_ENOSPACE;
-    P.klen = (((P.M + S - 1) / S) + BK - 1) / BK * BK;
+    float *bias_part = ws + pl.bias_off;    // [nslab][Cout] or colsum partials
     P.dW = direct ? dW : ws;
-    P.dbias = nullptr;
-    float *bias_part = ws + (direct ? 0 : (size_t)nslab * wsize);   // [nslab][Cout] or colsum partials
-    static const bool force_v1 = getenv("DVSOF_WGRAD_V1") != nullptr;
-    // flat members: dedicated VALU kernel when every one of them qualifies
-    bool flat_valu = nflat > 0 && !force_v1;
-    for (int i = 0; i < nflat; ++i) flat_valu = flat_valu && flat_ncol_ok(flat[i].ncol);
-    bool any_vec = false;
-    for (int s = 0; s < P.nsrc; ++s) any_vec = any_vec || !P.src[s].flat;
-    int want_flat = -1;  // v1 MFMA tiles for everything ...
     int rc = DVSOF_OK;
-    bool bias_in_kernel = false, patch_folded = false;
-    int fam = DVSOF_KERNEL_NONE, fam_mode = 0;     // the vector members' kernel (dvsof_conv2d_last_kernel)
-    if (!force_v1 && wgrad2_eligible(P)) {  // ... or v2 for the vector members
-        int bm, bn;
-        tile_dims(tile, bm, bn);
-        const int nt = enumerate_tiles(P, bn, 0);
-        if (nt > 0) {
-            // v2 also leaves the bias gradient: per-slab column sums of gout
-            if (dbias) {
-                P.dbias = direct ? dbias : bias_part;
-                bias_in_kernel = true;
-            }
-            // (flat members on the v1 tiles would write phase-form columns into the same slabs)
-            if (!direct && wgrad_patch_eligible(P) && (flat_valu || nflat == 0)) {
-                patch_folded = true;    // its slabs are [S][Cout][3][3][Cin_tot] already (it notes its kernel)
-                rc = wgrad_patch_launch(P, st);
-            } else {
-                rc = wgrad2_launch(P, tile, nt, st);
-                fam = DVSOF_KERNEL_GENERAL_V2;
-                fam_mode = P.twins ? 3 : P.mfma_bf16;
-            }
-            P.dbias = nullptr;
+    // the vector members' kernel; v2 and the patch kernels also leave the bias gradient:
+    // per-slab column sums of gout
+    P.dbias = pl.bias != WGB_VECTOR ? nullptr : direct ? dbias : bias_part;
+    switch (pl.vec) {
+    case WGV_V2:
+        wgrad_enumerate_tiles(P, P.ks * P.ks, pl.bn, true, false);
+        rc = wgrad2_launch(P, pl.tile, pl.ntiles, st);
+        break;
+    case WGV_PATCH_TWINS:
+    case WGV_PATCH_F32: rc = wgrad_patch_launch(P, pl.vec == WGV_PATCH_F32, pl.bn, st); break;
+    case WGV_MIN9: rc = wgrad_min_launch(P, st); break;
+    default: break;
+    }
+    if (rc) return rc;
+    P.dbias = nullptr;
+    if (pl.vec == WGV_V1 || pl.flat == WGF_V1) {
+        const bool vec = pl.vec == WGV_V1, fl = pl.flat == WGF_V1;
+        switch (pl.tile) {
+        case 1: rc = launch<2, 2, 2, 2>(P, vec, fl, st); break;
+        case 2: rc = launch<2, 2, 2, 1>(P, vec, fl, st); break;
+        case 3: rc = launch<2, 2, 1, 1>(P, vec, fl, st); break;
+        case 4: rc = launch<2, 2, 1, 2>(P, vec, fl, st); break;
+        default: rc = launch<1, 4, 1, 1>(P, vec, fl, st); break;
         }
         if (rc) return rc;
-        want_flat = 1;
-    } else if (flat_valu) {
-        want_flat = 0;   // v1 for the vector members only
     }
-    const bool run_v1 = !(want_flat == 1 && (flat_valu || nflat == 0)) && (want_flat != 0 || any_vec);
-    if (run_v1) {
-        switch (tile) {
-        case 1: rc = launch<2, 2, 2, 2>(P, want_flat, st); break;
-        case 2: rc = launch<2, 2, 2, 1>(P, want_flat, st); break;
-        case 3: rc = launch<2, 2, 1, 1>(P, want_flat, st); break;
-        case 4: rc = launch<2, 2, 1, 2>(P, want_flat, st); break;
-        default: rc = launch<1, 4, 1, 1>(P, want_flat, st); break;
-        }
-        if (rc) return rc;
-        if (fam == DVSOF_KERNEL_NONE) fam = DVSOF_KERNEL_GENERAL_V1;    // exact f32 in every mode
-    }
-    // flat-only layer on the matrix-core flat kernel: the bias gradient is one more output
-    // column of that kernel (no pass over gout of its own)
-    const bool bias_by_flat = dbias && !bias_in_kernel && flat_valu && nflat >= 1 &&
-                              flat_uses_mfma(flat[0]) && (flat[0].ncol % 32) != 0;
-    if (dbias && !bias_in_kernel && !bias_by_flat) {  // column sums of gout (all phases cover gout exactly once)
+    if (pl.bias == WGB_COLSUM) {  // column sums of gout (all phases cover gout exactly once)
         const long long rows = (long long)P.B * (P.g_sb / P.Cout);
         const int nb = colsum_blocks(rows);
         if (P.Cout & 3)
@@ -995,64 +834,31 @@ int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_fl
         DVSOF_LAUNCH_CHECK();
     }
     // the bias partials of the slabs ride along with the slab reduce / fold
-    const bool bias_tail_needed = bias_in_kernel && !direct;
-    const int nb_bias = bias_tail_needed ? (P.Cout + 255) / 256 : 0;
-    if (!direct && (any_vec || !flat_valu)) {
-        if (patch_folded) {
-            const size_t w9 = (size_t)P.Cout * 9 * P.Cin_tot;
-            const int nbm = (int)((w9 + 1023) / 1024);
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)(nbm + nb_bias)), dim3(256), 0, st,
-                               (const float *)ws, dW, w9, S, nbm, (const float *)bias_part, nslab,
-                               P.Cout, dbias);
-        } else if (P.nph == 4) {
-            const size_t n = (size_t)P.Cout * 9 * ((P.Cin_tot + 3) / 4);
-            const int zg = S <= 2 ? 1 : S <= 8 ? 4 : 16;
-            const int nbm = (int)((n + 256 / zg - 1) / (256 / zg));
-            auto kern = zg == 1 ? subpixel_fold_kernel<1> : zg == 4 ? subpixel_fold_kernel<4>
-                                                                    : subpixel_fold_kernel<16>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)(nbm + nb_bias)), dim3(256), 0, st,
-                               (const float *)ws, dW, P.Cout, P.Cin_tot, S, nbm,
-                               (const float *)bias_part, nslab, dbias);
-        } else {
-            const int nbm = (int)((wsize + 1023) / 1024);
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)(nbm + nb_bias)), dim3(256), 0, st,
-                               (const float *)ws, dW, wsize, S, nbm, (const float *)bias_part, nslab,
-                               P.Cout, dbias);
-        }
+    const int nb_bias = pl.bias_tail ? (P.Cout + 255) / 256 : 0;
+    if (pl.reduce == WGR_SUBPIXEL) {
+        const size_t n = (size_t)P.Cout * 9 * ((P.Cin_tot + 3) / 4);
+        const int nbm = (int)((n + 256 / pl.zg - 1) / (256 / pl.zg));
+        auto kern = pl.zg == 1 ? subpixel_fold_kernel<1> : pl.zg == 4 ? subpixel_fold_kernel<4>
+                                                                      : subpixel_fold_kernel<16>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(nbm + nb_bias)), dim3(256), 0, st,
+                           (const float *)ws, dW, P.Cout, P.Cin_tot, pl.S, nbm,
+                           (const float *)bias_part, nslab, dbias);
         DVSOF_LAUNCH_CHECK();
-    } else if (bias_tail_needed) {
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)nb_bias), dim3(256), 0, st,
-                           (const float *)nullptr, (float *)nullptr, (size_t)0, 0, 0,
-                           (const float *)bias_part, nslab, P.Cout, dbias);
+    } else if (pl.reduce != WGR_NONE) {
+        // (the patch kernels' slabs are [S][Cout][3][3][Cin_tot] already)
+        const size_t n = (size_t)P.Cout * (pl.reduce == WGR_PATCH ? 9 : P.ks * P.ks) * P.Cin_tot;
+        const int nbm = (int)((n + 1023) / 1024);
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)(nbm + nb_bias)), dim3(256), 0, st,
+                           (const float *)ws, dW, n, pl.S, nbm, (const float *)bias_part, nslab,
+                           P.Cout, dbias);
         DVSOF_LAUNCH_CHECK();
     }
-    if (flat_valu) {   // overwrites the flat members' columns of dW
-        float *part = bias_part + (dbias ? (size_t)COLSUM_MAX_BLOCKS * P.Cout : 0);
+    if (pl.flat == WGF_OWN)     // overwrites the flat members' columns of dW
         for (int i = 0; i < nflat; ++i) {
-            rc = flat_launch(flat[i], part, dW, (i == 0 && bias_by_flat) ? dbias : nullptr, st);
+            rc = flat_launch(flat[i], pl.flat_mfma[i], ws + pl.flat_off[i], dW,
+                             (i == 0 && pl.bias == WGB_FLAT) ? dbias : nullptr, st);
             if (rc) return rc;
-            part += (size_t)FLAT_BLOCKS * flat[i].Cout * (flat[i].ncol + 1);
         }
-        if (fam == DVSOF_KERNEL_NONE && !patch_folded) fam = DVSOF_KERNEL_FLAT_VALU;
-    }
-    if (!patch_folded) conv_note_kernel(fam, fam_mode);
+    conv_note_kernel(pl.family, pl.mode);
     return DVSOF_OK;
-}
-
-size_t wgrad_flat_workspace_floats(const FlatWG *flat, int nflat)
-{
-    size_t n = 0;
-    // (+ 1: room for the bias column of the matrix-core kernel's partial rows)
-    for (int i = 0; i < nflat; ++i) n += (size_t)FLAT_BLOCKS * flat[i].Cout * (flat[i].ncol + 1);
-    return n;
-}
-
-size_t wgrad_workspace_floats(const WGradParams &P, bool with_bias)
-{
-    int S = wgrad_splits(P, nullptr);
-    // the twins may not be bound yet when the workspace is sized: room for either kernel
-    if (wgrad_patch_shape_ok(P) && wgrad_patch_splits(P) > S) S = wgrad_patch_splits(P);
-    const int nslab = S * P.nph;
-    return (nslab <= 1 ? 0 : (size_t)nslab * P.Cout * P.ks * P.ks * P.Cin_tot) +
-           (with_bias ? (size_t)COLSUM_MAX_BLOCKS * P.Cout : 0);
 }

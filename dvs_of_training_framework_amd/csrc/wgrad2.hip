@@ -593,53 +593,23 @@ __global__ __launch_bounds__(CONV_NT) void wgrad2_twins_kernel(const WGradParams
 
 namespace {
 
-// XCD-aware tile order: DVSOF_WGRAD_XCD = 0 off (default: on; measured per launch at batch 8:
-// f32 -1..-3 %, bf16 operands up to -10 %, bf16 twins unchanged)
-inline int wgrad_xcd(dim3 grid, bool bf16)
+template <void (*KERNEL)(const WGradParams), int BMc, int BN>
+int launch_w2k(const WGradParams &P, int ntiles, hipStream_t st)
 {
-    static const int xe = getenv("DVSOF_WGRAD_XCD") ? atoi(getenv("DVSOF_WGRAD_XCD")) : -1;
+    constexpr int PA0 = BMc / 16, PB = BN / 16, PA = PA0 + ((4 - (PA0 + PB) % 4) % 4);
+    constexpr size_t LDS = (size_t)WNS * (PA + PB) * 1024;
+    static bool attr_set = false;
+    if (!attr_set) {
+        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+        attr_set = true;
+    }
+    dim3 grid(ntiles, (P.Cout + BMc - 1) / BMc, P.S * P.nph);
+    WGradParams Q = P;
+    // XCD-aware tile order: DVSOF_WGRAD_XCD = 0 off (default: on; measured per launch at batch 8:
+    // f32 -1..-3 %, bf16 operands up to -10 %, bf16 twins unchanged)
     const unsigned total = grid.x * grid.y * grid.z;
-    const bool want = xe != 0;
-    (void)bf16;
-    return (want && (total & 7u) == 0 && total >= 64) ? 1 : 0;
-}
-
-template <int WROWS, int WCOLS, int TM, int TN, int BF16, int TAG = 0>
-int launch_w2x(const WGradParams &P, int ntiles, hipStream_t st)
-{
-    constexpr int BMc = WROWS * TM * 32, BN = WCOLS * TN * 32;
-    constexpr int PA0 = BMc / 16, PB = BN / 16, PA = PA0 + ((4 - (PA0 + PB) % 4) % 4);
-    constexpr size_t LDS = (size_t)WNS * (PA + PB) * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)wgrad2_kernel<WROWS, WCOLS, TM, TN, BF16, TAG>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_set = true;
-    }
-    dim3 grid(ntiles, (P.Cout + BMc - 1) / BMc, P.S * P.nph);
-    WGradParams Q = P;
-    Q.xcd = wgrad_xcd(grid, P.mfma_bf16 != 0 || P.twins);
-    hipLaunchKernelGGL((wgrad2_kernel<WROWS, WCOLS, TM, TN, BF16, TAG>), grid, dim3(CONV_NT), LDS, st, Q);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
-}
-
-template <int WROWS, int WCOLS, int TM, int TN>
-int launch_w2t(const WGradParams &P, int ntiles, hipStream_t st)
-{
-    constexpr int BMc = WROWS * TM * 32, BN = WCOLS * TN * 32;
-    constexpr int PA0 = BMc / 16, PB = BN / 16, PA = PA0 + ((4 - (PA0 + PB) % 4) % 4);
-    constexpr size_t LDS = (size_t)WNS * (PA + PB) * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)wgrad2_twins_kernel<WROWS, WCOLS, TM, TN>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_set = true;
-    }
-    dim3 grid(ntiles, (P.Cout + BMc - 1) / BMc, P.S * P.nph);
-    WGradParams Q = P;
-    Q.xcd = wgrad_xcd(grid, P.mfma_bf16 != 0 || P.twins);
-    hipLaunchKernelGGL((wgrad2_twins_kernel<WROWS, WCOLS, TM, TN>), grid, dim3(CONV_NT), LDS, st, Q);
+    Q.xcd = (wgrad_xcd_on() && (total & 7u) == 0 && total >= 64) ? 1 : 0;
+    hipLaunchKernelGGL(KERNEL, grid, dim3(CONV_NT), LDS, st, Q);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
@@ -647,35 +617,22 @@ int launch_w2t(const WGradParams &P, int ntiles, hipStream_t st)
 template <int WROWS, int WCOLS, int TM, int TN>
 int launch_w2(const WGradParams &P, int ntiles, hipStream_t st)
 {
-    if (P.twins) return launch_w2t<WROWS, WCOLS, TM, TN>(P, ntiles, st);
-    if (P.mfma_bf16 == 2) return launch_w2x<WROWS, WCOLS, TM, TN, 2>(P, ntiles, st);
-    if (P.mfma_bf16 == 1) return launch_w2x<WROWS, WCOLS, TM, TN, 1>(P, ntiles, st);
-    return launch_w2x<WROWS, WCOLS, TM, TN, 0>(P, ntiles, st);
+    constexpr int BMc = WROWS * TM * 32, BN = WCOLS * TN * 32;
+    if (P.twins) return launch_w2k<wgrad2_twins_kernel<WROWS, WCOLS, TM, TN>, BMc, BN>(P, ntiles, st);
+    if (P.mfma_bf16 == 2) return launch_w2k<wgrad2_kernel<WROWS, WCOLS, TM, TN, 2>, BMc, BN>(P, ntiles, st);
+    if (P.mfma_bf16 == 1) return launch_w2k<wgrad2_kernel<WROWS, WCOLS, TM, TN, 1>, BMc, BN>(P, ntiles, st);
+    return launch_w2k<wgrad2_kernel<WROWS, WCOLS, TM, TN, 0>, BMc, BN>(P, ntiles, st);
 }
 
 }  // namespace
-
-// v2 handles the vector members when image rows are whole 16-pixel groups.
-bool wgrad2_eligible(const WGradParams &P)
-{
-    if (P.Wo % BK || P.klen % BK || P.up != UP_NONE) return false;
-    for (int s = 0; s < P.nsrc; ++s)
-        if (!P.src[s].flat && (P.src[s].sc != 1 || (P.src[s].C & 3))) return false;
-    long long bytes = (long long)P.B * P.g_sb * 4;
-    for (int s = 0; s < P.nsrc; ++s) {
-        const long long b = (long long)P.B * P.src[s].sb * 4;
-        bytes = b > bytes ? b : bytes;
-    }
-    return bytes < 0x7fffffffLL;
-}
 
 // P.tile_begin must already enumerate ONLY the vector members' column tiles
 // for the tile width of `tile`.
 int wgrad2_launch(const WGradParams &P, int tile, int ntiles, hipStream_t st)
 {
     if (P.src_ph_stride != 0 && tile == 3) {   // Winograd component GEMMs: own kernel name
-        if (P.mfma_bf16 == 2) return launch_w2x<2, 2, 1, 1, 2, 1>(P, ntiles, st);
-        if (P.mfma_bf16 == 0) return launch_w2x<2, 2, 1, 1, 0, 1>(P, ntiles, st);
+        if (P.mfma_bf16 == 2) return launch_w2k<wgrad2_kernel<2, 2, 1, 1, 2, 1>, 64, 64>(P, ntiles, st);
+        if (P.mfma_bf16 == 0) return launch_w2k<wgrad2_kernel<2, 2, 1, 1, 0, 1>, 64, 64>(P, ntiles, st);
     }
     switch (tile) {
     case 1: return launch_w2<2, 2, 2, 2>(P, ntiles, st);  // 128 x 128

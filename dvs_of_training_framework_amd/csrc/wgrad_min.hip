@@ -40,13 +40,12 @@
 // [split][Cout][3][3][Cin_tot] that the plain slab reduce consumes -- the
 // layout wgrad_patch's fold writes.
 #include "conv_host.h"
-#include <stdlib.h>
 
 namespace {
 
 constexpr unsigned WM_OOB = 0x80000000u;
 constexpr int WM_NT = 512;              // 8 waves
-constexpr int WM_CT = 64;               // input channels per workgroup
+constexpr int WM_CT = WG_MIN_CT;        // input channels per workgroup (64)
 constexpr int WM_PXB = 4 * WM_CT;       // bytes per patch pixel slot
 constexpr int WM_XP = 18;               // patch pieces: 72 slots x 256 B
 constexpr int WM_GP = 16;               // gradient planes: 4 phases x 32 px x 128 B
@@ -303,51 +302,7 @@ __global__ __launch_bounds__(WM_NT) void wgrad_min_f32_kernel(const WGradParams 
 
 }  // namespace
 
-// wgrad_patch.hip routes the exact-f32 decoder stages here when every vector member has a
-// multiple of 64 channels (DVSOF_NO_WGRAD_MIN=1: the sixteen-product patch kernel)
-bool wgrad_min_ok(const WGradParams &P)
+int wgrad_min_launch(const WGradParams &P, hipStream_t st)
 {
-    static const bool off = getenv("DVSOF_NO_WGRAD_MIN") != nullptr;
-    if (off || P.twins || P.mfma_bf16 != 0) return false;
-    for (int s = 0; s < P.nsrc; ++s)
-        if (!P.src[s].flat && (P.src[s].C & 63)) return false;
-    return true;
-}
-
-// K splits: one workgroup (8 waves) per CU; >= 2 blocks per split; <= 128 slabs
-int wgrad_min_splits(const WGradParams &P)
-{
-    long long tiles = 0;
-    for (int s = 0; s < P.nsrc; ++s)
-        if (!P.src[s].flat) tiles += P.src[s].C / WM_CT;
-    tiles *= P.Cout / 32;
-    static const int target = getenv("DVSOF_WGRAD_MIN_WGS") ? atoi(getenv("DVSOF_WGRAD_MIN_WGS")) : 256;
-    long long S = (target + tiles - 1) / (tiles > 0 ? tiles : 1);
-    const long long blocks = (long long)P.B * (P.Hv / 2) * (P.Wv / 16);
-    if (S > blocks / 2) S = blocks / 2;
-    if (S > 128) S = 128;
-    if (S < 1) S = 1;
-    return (int)S;
-}
-
-int wgrad_min_launch(WGradParams &P, hipStream_t st)
-{
-    int nt = 0;
-    for (int s = 0; s < P.nsrc; ++s) {
-        P.tile_begin[s] = nt;
-        if (!P.src[s].flat) nt += P.src[s].C / WM_CT;
-    }
-    P.tile_begin[P.nsrc] = nt;
-    static bool attr_set = false;
-    if (!attr_set) {
-        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_min_f32_kernel,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, WM_LDS));
-        attr_set = true;
-    }
-    dim3 grid(nt, P.Cout / 32, P.S);
-    static const bool xcd_off = getenv("DVSOF_WGRAD_XCD") && atoi(getenv("DVSOF_WGRAD_XCD")) == 0;
-    P.xcd = xcd_off ? 0 : 1;
-    hipLaunchKernelGGL(wgrad_min_f32_kernel, grid, dim3(WM_NT), WM_LDS, st, P);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return wgrad_resident_launch<wgrad_min_f32_kernel, WM_CT, WM_NT, WM_LDS>(P, st);
 }

@@ -30,7 +30,6 @@
 // are workgroups.  Same products as the twins kernel, f32 summation order
 // differs.
 #include "conv_host.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -490,169 +489,16 @@ __global__ __launch_bounds__(CONV_NT) void wgrad_patch_f32_kernel(const WGradPar
 
 }  // namespace
 
-// Decoder stages in the bf16-twins mode: four sub-pixel phases of 2x2 taps over vector members
-// whose channel counts are multiples of 32, 32 | Cout, 16 | width (DVSOF_NO_WGRAD_PATCH=1: the
-// column-tile kernel)
-// (the shape alone: what the workspace is sized for, whether or not the twins are bound yet)
-bool wgrad_patch_shape_ok(const WGradParams &P)
+// ct: 32 | 64 input channels per workgroup (the plan's choice, wgrad_plan.hip)
+int wgrad_patch_launch(const WGradParams &P, bool f32, int ct, hipStream_t st)
 {
-    static const bool off = getenv("DVSOF_NO_WGRAD_PATCH") != nullptr;
-    if (off || P.nph != 4 || P.ks != 2 || P.stride != 1 || P.up != UP_NONE) return false;
-    if (P.ph_pad != 1 || P.pad != 1 || P.src_ph_stride != 0) return false;
-    if ((P.Cout & 31) || (P.Wo % 16) || (P.Ho & 1) || P.Ho != P.Hv || P.Wo != P.Wv) return false;
-    // flat members (the 2-channel flow of a decoder stage) are not this kernel's: their
-    // columns belong to the caller (dvsof_flow_fold_grads) or to the flat-member kernels
-    int nvec = 0;
-    for (int s = 0; s < P.nsrc; ++s) {
-        if (P.src[s].flat) continue;
-        if (P.src[s].sc != 1 || (P.src[s].C & 31)) return false;
-        ++nvec;
-    }
-    return nvec >= 1;
-}
-
-// exact-f32 operand mode: wgrad_patch_f32_kernel (DVSOF_NO_WGRAD_PATCH_F32=1: wgrad2_kernel)
-static bool wp_f32(const WGradParams &P)
-{
-    static const bool off = getenv("DVSOF_NO_WGRAD_PATCH_F32") != nullptr;
-    return !off && !P.twins && P.mfma_bf16 == 0;
-}
-
-bool wgrad_patch_eligible(const WGradParams &P)
-{
-    if (!wgrad_patch_shape_ok(P)) return false;
-    if (wp_f32(P)) {
-        if (!P.gout || (reinterpret_cast<uintptr_t>(P.gout) & 15)) return false;
-        if ((P.g_sb | P.g_sy | P.g_sx | P.g_py | P.g_px) & 3) return false;
-        for (int s = 0; s < P.nsrc; ++s)
-            if (!P.src[s].flat && (!P.src[s].p || (reinterpret_cast<uintptr_t>(P.src[s].p) & 15) ||
-                                   ((P.src[s].sb | P.src[s].sy | P.src[s].sx) & 3)))
-                return false;
-        return true;
-    }
-    if (!P.twins || !P.gout16) return false;
-    for (int s = 0; s < P.nsrc; ++s)
-        if (!P.src[s].flat && !P.src[s].p16) return false;
-    return true;
-}
-
-// Bound on the K splits: >= 2 stages per split; a slab is a whole phase-form gradient -- at
-// most ~32 MB of partial sums per layer, and no more than DVSOF_WGRAD_PATCH_MAXS (64) slabs
-// per phase (the fold reads them all)
-static long long wp_max_splits(const WGradParams &P)
-{
-    const long long blocks = (long long)P.B * (P.Hv / 2) * (P.Wv / 16);
-    long long maxS = blocks / 2 > 0 ? blocks / 2 : 1;
-    const long long slab_bytes = 4LL * P.Cout * 4 * P.Cin_tot * 4;
-    long long capS = (32LL << 20) / (slab_bytes > 0 ? slab_bytes : 1);
-    static const int max_env = getenv("DVSOF_WGRAD_PATCH_MAXS") ? atoi(getenv("DVSOF_WGRAD_PATCH_MAXS")) : 64;
-    if (capS > max_env) capS = max_env;
-    if (capS < 1) capS = 1;
-    return maxS < capS ? maxS : capS;
-}
-
-// 64 input channels per workgroup halve the gradient planes' re-reads
-// (DVSOF_WGRAD_PATCH_CT = 32 | 64 forces one where every vector member allows it)
-static int wp_channel_tile(const WGradParams &P)
-{
-    static const int force = getenv("DVSOF_WGRAD_PATCH_CT") ? atoi(getenv("DVSOF_WGRAD_PATCH_CT")) : 0;
-    long long ct = 0;
-    for (int s = 0; s < P.nsrc; ++s) {
-        if (P.src[s].flat) continue;
-        if (P.src[s].C & 63) return 32;
-        ct += P.src[s].C / 64;
-    }
-    if (force == 32 || force == 64) return force;
-    // exact f32: matrix-bound once the planes are read half as often -- as long as one
-    // workgroup per CU remains
-    if (wp_f32(P)) return (P.Cout / 32) * ct * wp_max_splits(P) >= 256 ? 64 : 32;
-    // bf16 twins, measured (batch 8, the four decoder stages): 32 wins everywhere -- the slab
-    // bound on the K splits leaves the 64-channel form with 224-256 workgroups
-    return 32;
-}
-
-// K splits for this kernel: enough workgroups for two per CU
-int wgrad_patch_splits(const WGradParams &P)
-{
-    if (wp_f32(P) && wgrad_min_ok(P)) return wgrad_min_splits(P);
-    const int CT = wp_channel_tile(P);
-    long long tiles = (long long)(P.Cout / 32);
-    long long ct = 0;
-    for (int s = 0; s < P.nsrc; ++s)
-        if (!P.src[s].flat) ct += P.src[s].C / CT;
-    tiles *= ct;
-    static const int target16 = getenv("DVSOF_WGRAD_PATCH_WGS") ? atoi(getenv("DVSOF_WGRAD_PATCH_WGS")) : 512;
-    static const int target32 = getenv("DVSOF_WGRAD_PATCH_F32_WGS") ? atoi(getenv("DVSOF_WGRAD_PATCH_F32_WGS")) : 512;
-    const int target = wp_f32(P) ? target32 : target16;
-    long long S = (target + tiles - 1) / tiles;
-    const long long maxS = wp_max_splits(P);
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    return (int)S;
-}
-
-template <int CT>
-static int wp_launch(WGradParams &P, hipStream_t st)
-{
-    int nt = 0;
-    for (int s = 0; s < P.nsrc; ++s) {
-        P.tile_begin[s] = nt;
-        if (!P.src[s].flat) nt += P.src[s].C / CT;
-    }
-    P.tile_begin[P.nsrc] = nt;
-    constexpr size_t LDS0 = (size_t)WPGeom<CT>::NS * WPGeom<CT>::STAGE;
-    constexpr size_t LDS = LDS0 < 65536 ? 65536 : LDS0;     // the fold of the epilogue: 16 tiles of 4 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_patch_twins_kernel<CT>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_set = true;
-    }
-    dim3 grid(nt, P.Cout / 32, P.S);
-    static const bool xcd_off = getenv("DVSOF_WGRAD_XCD") && atoi(getenv("DVSOF_WGRAD_XCD")) == 0;
-    P.xcd = xcd_off ? 0 : 1;
-    hipLaunchKernelGGL(wgrad_patch_twins_kernel<CT>, grid, dim3(CONV_NT), LDS, st, P);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
-}
-
-template <int CT>
-static int wp_launch_f32(WGradParams &P, hipStream_t st)
-{
-    int nt = 0;
-    for (int s = 0; s < P.nsrc; ++s) {
-        P.tile_begin[s] = nt;
-        if (!P.src[s].flat) nt += P.src[s].C / CT;
-    }
-    P.tile_begin[P.nsrc] = nt;
-    constexpr size_t LDS0 = (size_t)WPGeomF<CT>::NS * WPGeomF<CT>::STAGE;
-    constexpr size_t LDS = LDS0 < 65536 ? 65536 : LDS0;     // the fold of the epilogue: 16 tiles of 4 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_patch_f32_kernel<CT>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_set = true;
-    }
-    dim3 grid(nt, P.Cout / 32, P.S);
-    static const bool xcd_off = getenv("DVSOF_WGRAD_XCD") && atoi(getenv("DVSOF_WGRAD_XCD")) == 0;
-    P.xcd = xcd_off ? 0 : 1;
-    hipLaunchKernelGGL(wgrad_patch_f32_kernel<CT>, grid, dim3(CONV_NT), LDS, st, P);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
-}
-
-int wgrad_patch_launch(const WGradParams &P0, hipStream_t st)
-{
-    WGradParams P = P0;
-    if (wp_f32(P) && wgrad_min_ok(P)) {
-        const int rc = wgrad_min_launch(P, st);
-        if (rc == DVSOF_OK) conv_note_kernel(DVSOF_KERNEL_WGRAD_MIN, 0);
-        return rc;
-    }
-    const int ct = wp_channel_tile(P);
-    int rc;
-    if (wp_f32(P)) rc = ct == 64 ? wp_launch_f32<64>(P, st) : wp_launch_f32<32>(P, st);
-    else rc = ct == 64 ? wp_launch<64>(P, st) : wp_launch<32>(P, st);
-    if (rc == DVSOF_OK) conv_note_kernel(DVSOF_KERNEL_WGRAD_PATCH, P.twins ? 3 : P.mfma_bf16);
-    return rc;
+    // (at least 64 KiB: the fold of the epilogue takes 16 tiles of 4 KiB)
+    constexpr int T32 = WPGeom<32>::NS * WPGeom<32>::STAGE, T64 = WPGeom<64>::NS * WPGeom<64>::STAGE;
+    constexpr int F32 = WPGeomF<32>::NS * WPGeomF<32>::STAGE, F64 = WPGeomF<64>::NS * WPGeomF<64>::STAGE;
+    constexpr int MIN = 65536;
+    if (f32)
+        return ct == 64 ? wgrad_resident_launch<wgrad_patch_f32_kernel<64>, 64, CONV_NT, (F64 < MIN ? MIN : F64)>(P, st)
+                        : wgrad_resident_launch<wgrad_patch_f32_kernel<32>, 32, CONV_NT, (F32 < MIN ? MIN : F32)>(P, st);
+    return ct == 64 ? wgrad_resident_launch<wgrad_patch_twins_kernel<64>, 64, CONV_NT, (T64 < MIN ? MIN : T64)>(P, st)
+                    : wgrad_resident_launch<wgrad_patch_twins_kernel<32>, 32, CONV_NT, (T32 < MIN ? MIN : T32)>(P, st);
 }

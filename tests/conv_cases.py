@@ -113,6 +113,26 @@ CASES = [
          path=('fwd_min4 dgrad_min1 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 wgrad_patch')),
     dict(B=8, H=128, W=128, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True,
          path=('fwd_min8 dgrad_min0 wgrad_min', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2', 'fwd_patch general_v2 wgrad_patch')),
+    # outcomes of the weight gradient's plan (csrc/wgrad_plan.hip) the layers above do not reach,
+    # each at the smallest size that takes it (tests/test_gpu_wgrad_plan.py):
+    # a 4-channel planar member beside a sub-pixel layer's vector members: its columns on the v1
+    # tiles beside v2, both into the phase slabs, with the patch kernels' split count
+    dict(B=1, H=8, W=16, src=[(32, 'nhwc'), (32, 'nhwc'), (4, 'nchw')], Cout=32, up=True,
+         path=('general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2', 'general_v2 general_v2 general_v2')),
+    # rows that are no whole 16-pixel groups: v1 tiles for the vector member, direct; the flow
+    # member on the VALU kernel; the bias by the scalar column-sum pass (Cout % 4 != 0)
+    dict(B=2, H=9, W=11, src=[(24, 'nhwc'), (2, 'nchw')], Cout=30,
+         path=('general_v1 general_v1 general_v1', 'general_v1 general_v1 general_v1', 'general_v1 general_v1 general_v1')),
+    # a flat-only layer of M = 262144 pixels: the matrix-core flat kernel, the bias gradient as
+    # its extra output column
+    dict(B=1, H=512, W=512, src=[(2, 'nchw')], Cout=32,
+         path=('general_v1 general_v2 flat_valu', 'general_v1 general_v2 flat_valu', 'general_v1 general_v2 flat_valu', 'general_v1 general_v2 flat_valu')),
+    # flat members no flat kernel takes (36 / 72 + 36 columns): on the v1 tiles, direct / over
+    # K-split slabs, the bias by the column-sum pass
+    dict(B=1, H=16, W=16, src=[(4, 'nchw')], Cout=32,
+         path=('general_v1 general_v2 general_v1', 'general_v1 general_v2 general_v1', 'general_v1 general_v2 general_v1', 'general_v1 general_v2 general_v1')),
+    dict(B=2, H=16, W=32, src=[(8, 'nhwc'), (4, 'nchw')], Cout=12,
+         path=('general_v1 general_v1 general_v1', 'general_v1 general_v1 general_v1', 'general_v1 general_v1 general_v1')),
 ]
 
 
