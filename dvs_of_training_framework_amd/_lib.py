@@ -102,6 +102,13 @@ _SIGNATURES = {
                                              _i64, _vp, _vp, _i, _i, _i, _i,
                                              _i, _i, _vp, _vp, _i, _vp, _sz,
                                              _vp]),
+    'dvsof_learned_voxelize_tiled_workspace_bytes': (_sz, [_i64, _i, _i, _i,
+                                                           _i, _i]),
+    'dvsof_learned_voxelize_tiled_control_bytes': (_sz, [_i64, _i, _i, _i,
+                                                         _i, _i]),
+    'dvsof_learned_voxelize_tiled': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64,
+                                          _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                          _i, _vp, _vp, _sz, _i, _vp]),
     'dvsof_first_dgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'dvsof_resize_bilinear_ac': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'dvsof_loss_workspace_bytes': (_sz, [ctypes.POINTER(LossScale), _i, _i]),

@@ -60,7 +60,7 @@ import ctypes
 
 import torch
 
-from . import _lib, voxel
+from . import _lib, learned_voxel, voxel
 from .loss import unit_backward
 from .timer import FakeTimer
 from .training import CAPTURE_PROTOCOL, TermReadback, _timed, process_minibatch
@@ -358,6 +358,7 @@ class CapturedTrainStep:
         # voxeliser workspace, gradient buckets, optimizer tables.
         self._keep = [dict(getattr(model, '_layout_cache', {})),
                       list(voxel._WORKSPACES.values()),
+                      list(learned_voxel._WORKSPACES.values()),
                       list(getattr(model.predictor, '_bucket_flat', [])),
                       dict(optimizer._tables), self.static]
         layer = self._resident_layer()

@@ -10,7 +10,7 @@ group ``quantization_layer``, its own LR factor that stays 0 until
 import torch
 
 from . import _lib
-from .voxel import is_compact
+from .voxel import WS_CLEAN, _WS_ROUND, is_compact
 
 MAX_RADIUS, MAX_KNOTS_PER_BIN = 3, 16
 
@@ -52,9 +52,51 @@ def _check(theta, radius, knots_per_bin, t0, t1, B):
     assert t0.numel() == B and t1.numel() == B
 
 
-def voxelize(events, t0, t1, theta, radius, knots_per_bin, B, C, H, W):
+# Workspaces of the order-independent forward (dvsof_learned_voxelize_tiled): the
+# pattern of voxel._workspace -- zero-filled once per shape and device, reused
+# with WS_CLEAN, forgotten after a failed call.
+_WORKSPACES = {}
+
+
+def _forget_workspace(ws):
+    for k in [k for k, v in _WORKSPACES.items() if v is ws]:
+        del _WORKSPACES[k]
+
+
+def _workspace(n, B, C, H, W, device):
+    """-> (tensor, nbytes, flags) for the order-independent forward.  Tiled
+    path: control words zero-filled ONCE, then WS_CLEAN (the kernels clean up
+    after themselves); a workspace first met inside a stream capture is
+    graph-owned scratch with flags 0 (a fill kernel node zeroes its control
+    words).  Three-kernel path: the int64 scratch grid, no control words.  One
+    call of a given shape at a time per device, as voxel._workspace."""
+    lib = _lib.lib()
+    control = lib.dvsof_learned_voxelize_tiled_control_bytes(n, B, C, H, W, 0)
+    n_up = (n + _WS_ROUND - 1) // _WS_ROUND * _WS_ROUND if control else n
+    nbytes = max(lib.dvsof_learned_voxelize_tiled_workspace_bytes(n_up, B, C, H, W, 0),
+                 lib.dvsof_learned_voxelize_tiled_workspace_bytes(n, B, C, H, W, 0))
+    flags = WS_CLEAN if control else 0
+    key = (n_up if control else 0, control, B, C, H, W, str(device))
+    ws = _WORKSPACES.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            return (torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device),
+                    nbytes, 0)
+        if len(_WORKSPACES) >= 16:
+            _WORKSPACES.pop(next(iter(_WORKSPACES)))    # forget the oldest
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        ws[:control].zero_()
+        _WORKSPACES[key] = ws
+    return ws, nbytes, flags
+
+
+def voxelize(events, t0, t1, theta, radius, knots_per_bin, B, C, H, W,
+             deterministic=False):
     """events: wire or compact columns on the device; t0/t1: float32[B];
-    theta: float32[2*R*S+1].  -> grid float32 [B,C,H,W]."""
+    theta: float32[2*R*S+1].  -> grid float32 [B,C,H,W].
+    deterministic: the order-independent forward (64-bit fixed-point sums,
+    LEARNED_VOXEL_SPEC "Order-independent forward"): the same events give the
+    same bits in any order.  Off: float atomics in arrival order."""
     _check(theta, radius, knots_per_bin, t0, t1, B)
     x, y, t, p, s, encoded = _columns(events, t0.device)
     _lib.require_cuda(x, y, t, p, s)
@@ -62,6 +104,18 @@ def voxelize(events, t0, t1, theta, radius, knots_per_bin, B, C, H, W):
         assert s.numel() == B + 1, 'one offset per sample plus the end'
     out = torch.empty(B, C, H, W, dtype=torch.float32, device=t0.device)
     lib = _lib.lib()
+    if deterministic:
+        n = x.numel()
+        ws, nbytes, flags = _workspace(n, B, C, H, W, t0.device) if n else (None, 0, 0)
+        rc = lib.dvsof_learned_voxelize_tiled(
+            x.data_ptr(), y.data_ptr(), t.data_ptr(), p.data_ptr(), s.data_ptr(),
+            encoded, n, t0.contiguous().data_ptr(), t1.contiguous().data_ptr(),
+            theta.data_ptr(), radius, knots_per_bin, B, C, H, W, out.data_ptr(),
+            _lib.ptr(ws), nbytes, flags, _lib.stream())
+        if rc != 0:
+            _forget_workspace(ws)
+        _lib.check(rc, 'dvsof_learned_voxelize_tiled')
+        return out
     fn, what = (lib.dvsof_learned_voxelize_encoded, 'dvsof_learned_voxelize_encoded') \
         if encoded else (lib.dvsof_learned_voxelize_fwd, 'dvsof_learned_voxelize_fwd')
     _lib.check(fn(x.data_ptr(), y.data_ptr(), t.data_ptr(), p.data_ptr(),
@@ -134,17 +188,18 @@ def reduction_chain(n_events, knots_per_bin):
 
 class _LearnedVoxelFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, theta, events, t0, t1, radius, knots_per_bin, B, C, H, W):
+    def forward(ctx, theta, events, t0, t1, radius, knots_per_bin, B, C, H, W,
+                deterministic=False):
         ctx.args = (events, t0, t1, radius, knots_per_bin)
         return voxelize(events, t0, t1, theta.detach(), radius, knots_per_bin,
-                        B, C, H, W)
+                        B, C, H, W, deterministic)
 
     @staticmethod
     def backward(ctx, grad_grid):
         events, t0, t1, radius, knots_per_bin = ctx.args
         g = voxelize_bwd(events, t0, t1, radius, knots_per_bin, grad_grid) \
             if ctx.needs_input_grad[0] else None
-        return (g,) + (None,) * 9
+        return (g,) + (None,) * 10
 
 
 class ResidentGrad:
@@ -207,10 +262,11 @@ class _ResidentVoxelFn(torch.autograd.Function):
     hands autograd nothing."""
 
     @staticmethod
-    def forward(ctx, theta, resident, reducer_of, events, t0, t1, B, C, H, W):
+    def forward(ctx, theta, resident, reducer_of, events, t0, t1, B, C, H, W,
+                deterministic=False):
         ctx.args = (theta, resident, reducer_of, events, t0, t1)
         return voxelize(events, t0, t1, theta.detach(), resident.radius,
-                        resident.knots_per_bin, B, C, H, W)
+                        resident.knots_per_bin, B, C, H, W, deterministic)
 
     @staticmethod
     def backward(ctx, grad_grid):
@@ -219,22 +275,24 @@ class _ResidentVoxelFn(torch.autograd.Function):
             # the reducer in effect NOW, as the predictor's backward reads its own
             reducer = reducer_of() if reducer_of is not None else None
             resident.backward(theta, events, t0, t1, grad_grid, reducer)
-        return (None,) * 10
+        return (None,) * 11
 
 
 def apply(theta, events, t0, t1, radius, knots_per_bin, B, C, H, W,
-          resident=None, reducer_of=None):
+          resident=None, reducer_of=None, deterministic=False):
     """Differentiable with respect to ``theta`` only (no gradient to event
     coordinates or timestamps).  Without grad mode only the forward runs.
     resident: ResidentGrad -- the gradient goes to its persistent slot (and
     from there to the parallel.GradReducer that ``reducer_of()`` returns when
-    the backward runs) instead of to autograd."""
+    the backward runs) instead of to autograd.
+    deterministic: the order-independent forward (``voxelize``); the backward
+    is fixed-order either way."""
     if resident is not None and torch.is_grad_enabled() and theta.requires_grad:
         assert (resident.radius, resident.knots_per_bin) == (radius, knots_per_bin)
         return _ResidentVoxelFn.apply(theta, resident, reducer_of, events, t0, t1,
-                                      B, C, H, W)
+                                      B, C, H, W, deterministic)
     if torch.is_grad_enabled() and theta.requires_grad:
         return _LearnedVoxelFn.apply(theta, events, t0, t1, radius,
-                                     knots_per_bin, B, C, H, W)
+                                     knots_per_bin, B, C, H, W, deterministic)
     return voxelize(events, t0, t1, theta.detach(), radius, knots_per_bin,
-                    B, C, H, W)
+                    B, C, H, W, deterministic)

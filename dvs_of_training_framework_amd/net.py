@@ -68,13 +68,20 @@ class LearnedVoxelGrid(nn.Module):
     exchange need, and ``capture_ready`` says so.  The arithmetic is the
     default mode's, bit for bit.  ``reducer`` (parallel.GradReducer) is read
     when the backward runs, as the predictor reads its own: the layer's own
-    attribute, or -- inside a ``Model`` -- the predictor's (``exchange_with``)."""
+    attribute, or -- inside a ``Model`` -- the predictor's (``exchange_with``).
+
+    ``deterministic`` (off by default): every forward of the layer -- training,
+    ``Model.quantize``, inference, evaluation -- sums in 64-bit fixed point
+    (dvsof_learned_voxelize_tiled): the same events give the same bits in any
+    order, so two runs from one seed, and a replayed step and its eager twin,
+    agree bit for bit on every input.  The backward is fixed-order already."""
 
     capture_ready = False
 
-    def __init__(self, depth, radius=2, knots_per_bin=8):
+    def __init__(self, depth, radius=2, knots_per_bin=8, deterministic=False):
         super().__init__()
         self.depth, self.radius, self.knots_per_bin = depth, radius, knots_per_bin
+        self.deterministic = bool(deterministic)
         self.kernel = nn.Parameter(
             learned_voxel.initial_kernel(radius, knots_per_bin))
         self.resident = None
@@ -137,7 +144,8 @@ class LearnedVoxelGrid(nn.Module):
         return learned_voxel.apply(self.kernel, events, t0, t1, self.radius,
                                    self.knots_per_bin, batch, self.depth,
                                    height, width, resident=self.resident,
-                                   reducer_of=self._reducer_now)
+                                   reducer_of=self._reducer_now,
+                                   deterministic=self.deterministic)
 
     def _reducer_now(self):
         return self.reducer
@@ -149,16 +157,20 @@ class Model(nn.Module):
                  event_representation_depth=9, activation=None,
                  compute_dtype='f32', learnable_representation=False,
                  representation_radius=2, representation_knots=8,
-                 representation_resident=False):
+                 representation_resident=False,
+                 representation_deterministic=False):
         super().__init__()
         self.prefix_length = prefix_length
         self.suffix_length = suffix_length
         self.max_sequence_length = max_sequence_length
         self.dynamic_sample_length = dynamic_sample_length
         self.event_representation_depth = event_representation_depth
+        assert learnable_representation or not representation_deterministic, \
+            'representation_deterministic needs learnable_representation'
         self.quantization_layer = LearnedVoxelGrid(
             event_representation_depth, representation_radius,
-            representation_knots) if learnable_representation \
+            representation_knots, representation_deterministic) \
+            if learnable_representation \
             else VoxelGrid(event_representation_depth)
         self.predictor = Predictor(event_representation_depth, activation,
                                    compute_dtype)

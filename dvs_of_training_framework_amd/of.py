@@ -145,8 +145,9 @@ class OpticalFlow:
             g['graph'] = graph
             # eager objects the graph's kernels point at (voxeliser workspace,
             # index vectors) must outlive it whatever their caches do later
-            from . import voxel
+            from . import learned_voxel, voxel
             g['keep'] = (list(voxel._WORKSPACES.values()),
+                         list(learned_voxel._WORKSPACES.values()),
                          dict(self._net._layout_cache))
         g['graph'].replay()
         if _GRAPH_SYNC:

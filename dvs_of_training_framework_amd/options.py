@@ -154,7 +154,16 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'process (the knots then join the gradient exchange); '
                              'the learned forward sums with float atomics, so a '
                              'replayed step equals its eager twin bit for bit only '
-                             'where no voxel receives two events')
+                             'where no voxel receives two events -- or, with '
+                             '--representation-deterministic, on every input')
+    parser.add_argument('--representation-deterministic',
+                        dest='representation_deterministic', action='store_true',
+                        help='with --learnable-representation: every forward of the '
+                             'layer sums in 64-bit fixed point '
+                             '(dvsof_learned_voxelize_tiled; docs/LEARNED_VOXEL_SPEC.md, '
+                             'Order-independent forward) instead of with float '
+                             'atomics: the same events give the same bits in any '
+                             'order, so two runs from one seed agree bit for bit')
     parser.add_argument('--capture', action='store_true',
                         help='replay the loop body from one C call per micro-batch '
                              'once a batch signature has been seen (capture.CapturedLoop '
@@ -211,6 +220,9 @@ def validate_train_args(args):             # utils/options.py:318-325
     assert args.bs % args.mbs == 0
     args.accum_step = args.bs // args.mbs
     assert args.permanent_interval % args.checkpointing_interval == 0
+    if getattr(args, 'representation_deterministic', False) and \
+            not getattr(args, 'learnable_representation', False):
+        raise SystemExit('--representation-deterministic needs --learnable-representation')
     return args
 
 
@@ -236,4 +248,6 @@ def options2model_kwargs(parameters):      # utils/options.py:341-347
         kwargs['representation_knots'] = parameters.representation_knots
         if getattr(parameters, 'representation_resident', False):
             kwargs['representation_resident'] = True
+        if getattr(parameters, 'representation_deterministic', False):
+            kwargs['representation_deterministic'] = True
     return kwargs

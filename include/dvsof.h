@@ -211,6 +211,55 @@ int dvsof_learned_voxelize_bwd_into(const void *x, const void *y,
                                     void *stream);
 
 /*
+ * ORDER-INDEPENDENT forward of the learnable representation (opt-in:
+ * learned_voxel.voxelize(..., deterministic=True)).  Drop rule, tn, u, j, g and
+ * w are those of dvsof_learned_voxelize_fwd; from w on
+ *   Q = (int64) trunc((double)(s*w) * 2^32)         toward zero
+ *   A[b,c,y,x] = sum of Q                            64-bit integers, any order
+ *   out[b,c,y,x] = (float)((double)A * 2^-32)        once per voxel
+ * so the same events give the same bits in whatever order they arrive
+ * (docs/LEARNED_VOXEL_SPEC.md, "Order-independent forward").  Defined while the
+ * sum of |w| of every voxel stays below 2^31; outside that range the result is
+ * unspecified (nothing is checked on the host, nothing faults).
+ * Where the plan of dvsof_voxelize_tiled applies (n_events >= 4096, at most 8192
+ * tiles, at most 37 bins) the call is its two launches -- bucket pass, tile pass
+ * with the table and the accumulators in LDS -- on a workspace of the same
+ * layout and contract (control words first, self-cleaning, DVSOF_VOX_WS_CLEAN).
+ * Elsewhere it is three kernels: zero an int64 scratch grid [B,C,H,W] in the
+ * workspace, one thread per event adding Q with 64-bit integer atomics, one
+ * conversion per voxel; the same bits.  Kernel launches only, no memset, no
+ * copy.  n_events = 0 zero-fills out and needs no workspace.
+ * Columns and `encoded`: as dvsof_learned_voxelize_bwd.  flags:
+ *   DVSOF_VOX_WS_CLEAN  as dvsof_voxelize_tiled (ignored where there are no
+ *                       control words)
+ *   DVSOF_LV_GLOBAL     take the three-kernel path whatever the size
+ *   DVSOF_LV_EPT8 / DVSOF_LV_EPT16  8 / 16 events per thread in the bucket pass
+ *                       whatever n_events (default: 4, 8 from 2 Mi, 16 from
+ *                       3 Mi events); not both
+ * The two size queries take the flags of the call they size.  DVSOF_ENOSPACE:
+ * workspace missing or too small (nothing is enqueued); DVSOF_EINVAL: bad
+ * shape, null pointer, unknown flag, workspace not 16-byte aligned.
+ */
+#define DVSOF_LV_GLOBAL 2
+#define DVSOF_LV_EPT8 4
+#define DVSOF_LV_EPT16 8
+size_t dvsof_learned_voxelize_tiled_workspace_bytes(int64_t n_events, int B,
+                                                    int C, int H, int W,
+                                                    int flags);
+/* 0 where the three-kernel path serves the call (no control words) */
+size_t dvsof_learned_voxelize_tiled_control_bytes(int64_t n_events, int B,
+                                                  int C, int H, int W,
+                                                  int flags);
+int dvsof_learned_voxelize_tiled(const void *x, const void *y, const float *t,
+                                 const void *polarity,
+                                 const void *sample_or_offsets, int encoded,
+                                 int64_t n_events, const float *t0,
+                                 const float *t1, const float *theta, int R,
+                                 int S, int B, int C, int H, int W, float *out,
+                                 void *workspace, size_t workspace_bytes,
+                                 int flags, void *stream);
+
+/*
  * Data gradient of the first encoder layer (enc.0: 3x3, stride 2, pad 1, C
  * planar input channels, 1..16, 64 NHWC output channels; csrc/first.hip) --
  * what a learnable representation needs below the predictor:

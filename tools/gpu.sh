@@ -15,7 +15,9 @@
 #                                     the same frames from a device-resident EventSequence, the window kernel alone
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
-#                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50
+#                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
+#                                     forward_alternating: float-atomics forward / learned_fwd_deterministic /
+#                                     fixed voxeliser in alternating blocks of one run
 #                                     (tools/learned_voxel_bench.py)
 #   lossprobe B H W bits...           loss path under the probe build's DVSOF_LOSS_DBG bits
 #   timeline [bench args]             rocprofv3 kernel trace of a short run -> one step per queue

@@ -7,6 +7,10 @@ executor against the eager loop of an identical model, in alternating blocks
 (device time per step and host time to enqueue one).  With DVSOF_LOOPBACK=
 "world:delay_us" in the environment that leg runs under the loopback gradient
 exchange (``--captured-only`` runs nothing else).
+``learned_fwd_deterministic``: the order-independent forward
+(lv.voxelize(..., deterministic=True)) against the float-atomics forward and the
+fixed voxeliser on the same events, in alternating blocks of one run
+(``--forward-only`` runs nothing else).
 One JSON line on stdout.  ``--default-step-only`` measures just the default
 model's eager step: that part also runs on a checkout without the feature."""
 import argparse
@@ -50,6 +54,42 @@ def share(row, nbytes):
     row['bytes'] = nbytes
     row['share_of_8TBs'] = round(nbytes / (row['us'] * 1e-6) / HBM, 4)
     return row
+
+
+def alternating(legs, reps, warmup=5, blocks=5):
+    """legs: [(name, fn)], timed in alternating blocks of ``reps`` calls.
+    -> {name: median / min / max us per call over the blocks}."""
+    for _ in range(warmup):
+        for _, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    out = {name: [] for name, _ in legs}
+    for _ in range(blocks):
+        for name, fn in legs:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            out[name].append(a.elapsed_time(b) * 1e3 / reps)
+    return {name: dict(us=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2))
+            for name, v in out.items()}
+
+
+def forward_legs(B, H, W, C, n, reps):
+    """The three forwards on the same events, one run, alternating blocks."""
+    from dvs_of_training_framework_amd import learned_voxel as lv
+    ev = synthetic.to_torch(synthetic.make_batch(1234, B, H, W, n), 'cuda')['events']
+    t0 = torch.zeros(B, device='cuda')
+    t1 = torch.full((B,), synthetic.WINDOW, device='cuda')
+    R, S = 2, 8
+    theta = lv.initial_kernel(R, S).cuda()
+    return alternating([
+        ('learned_fwd', lambda: lv.voxelize(ev, t0, t1, theta, R, S, B, C, H, W)),
+        ('learned_fwd_deterministic',
+         lambda: lv.voxelize(ev, t0, t1, theta, R, S, B, C, H, W, deterministic=True)),
+        ('voxelize', lambda: voxel.voxelize(ev, t0, t1, B, C, H, W))], reps)
 
 
 def step_time(B, H, W, C, n, learnable, reps):
@@ -140,11 +180,16 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--default-step-only', action='store_true')
     ap.add_argument('--captured-only', action='store_true')
+    ap.add_argument('--forward-only', action='store_true')
     a = ap.parse_args()
     B, H, W, C, n = a.batch, a.size, a.size, a.depth, a.events
     out = dict(shape=dict(B=B, H=H, W=W, C=C, events=B * n))
     if a.captured_only:
         out['step_learnable_captured'] = captured_against_eager(B, H, W, C, n, a.reps)
+        print(json.dumps(out))
+        return
+    if a.forward_only:
+        out['forward_alternating'] = forward_legs(B, H, W, C, n, a.reps)
         print(json.dumps(out))
         return
     out['step_default'] = step_time(B, H, W, C, n, False, a.reps)
@@ -170,6 +215,7 @@ def main():
         out['first_dgrad'] = share(timed(
             lambda: conv.first_dgrad(gz, w, B, C, H, W), a.reps), gz.numel() * 4 + grid_bytes)
         out['step_learnable_captured'] = captured_against_eager(B, H, W, C, n, a.reps)
+        out['forward_alternating'] = forward_legs(B, H, W, C, n, a.reps)
     print(json.dumps(out))
 
 

@@ -153,6 +153,8 @@ def check_representation_args(args, world):
     resident = getattr(args, 'representation_resident', False)
     if resident and not learn:
         raise SystemExit('--representation-resident needs --learnable-representation')
+    if getattr(args, 'representation_deterministic', False) and not learn:
+        raise SystemExit('--representation-deterministic needs --learnable-representation')
     if resident and torch.device(args.device).type != 'cuda':
         raise SystemExit('--representation-resident keeps the gradient of the knots in a '
                          f'device slot: it needs a GPU (--device {args.device})')
