@@ -173,22 +173,41 @@ class DeviceFeeder:
                'augmentation_params': batch.get('augmentation_params')}
         return out, slot
 
+    # ---- position in the stream (docs/CHECKPOINT_SPEC.md) ---------------
+    def _loader_state(self):
+        return self.loader.state() if hasattr(self.loader, 'state') else None
+
+    def state(self):
+        """The loader's state after the last batch HANDED OUT (the feeder has
+        drawn one more by then: that one is drawn again after a resume)."""
+        if getattr(self, '_handed', None) is not None:
+            return self._handed
+        return self._loader_state()
+
+    def restore(self, state):
+        self.loader.restore(state)
+        self._handed = None
+
     def __iter__(self):
         it = iter(self.loader)
         k = 0
         try:
             nxt = self._stage(next(it), self.slots[0])
+            nxt_state = self._loader_state()
         except StopIteration:
             return
         while nxt is not None:
             cur, slot = nxt
+            cur_state = nxt_state
             k += 1
             try:        # batch n+1 is on its way before batch n is handed out
                 nxt = self._stage(next(it), self.slots[k % len(self.slots)])
+                nxt_state = self._loader_state()
             except StopIteration:
                 nxt = None
             main = torch.cuda.current_stream(self.device)
             main.wait_event(slot.ready)
+            self._handed = cur_state
             yield cur
             # the loop is back for the next batch: everything that reads `slot` is enqueued
             if slot.free is None:

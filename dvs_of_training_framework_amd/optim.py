@@ -28,6 +28,7 @@ _lib.register('dvsof_radam_step_dyn', _i, [_vp, _vp, _vp, _i, _vp, _f, _f, _f,
                                            _f, _f, _vp])
 _lib.register('dvsof_grad_centralize', _i, [_vp, _i, _i, _vp])
 _lib.register('dvsof_grad_centralize_multi', _i, [_vp, _i, _vp])
+from . import snapshot as _snapshot  # noqa: E402,F401  (registers dvsof_snapshot_*: the state's way out)
 
 
 class _FusedBase(torch.optim.Optimizer):

@@ -203,6 +203,22 @@ def add_train_arguments(parser):           # utils/options.py:204-302
     parser.add_argument('--synthetic-events', dest='synthetic_events',
                         default=None, type=int,
                         help='events per synthetic sample (default H*W)')
+    parser.add_argument('--validation-sequence', dest='validation_sequence',
+                        default=None, type=Path,
+                        help='validate (before and after training and every '
+                             '--validation_period steps) on ONE recorded sequence, a '
+                             'directory as for --sequence: one pass, central crop, no '
+                             'augmentation')
+    parser.add_argument('--synthetic-validation-batches',
+                        dest='synthetic_validation_batches', default=0, type=int,
+                        help='with --synthetic: validate on this many seeded batches '
+                             '(seeds disjoint from the training batches\')')
+    parser.add_argument('--sync-checkpoints', dest='sync_checkpoints',
+                        action='store_true',
+                        help='write checkpoints on the training thread (state_dict() + '
+                             'torch.save, the reference\'s way) instead of snapshotting '
+                             'the device state in one launch and writing the file from '
+                             'a writer thread (docs/CHECKPOINT_SPEC.md)')
     return parser
 
 

@@ -411,9 +411,9 @@ class SequenceLoader:
                'size': B}
         return augment_batch(raw, is_flip, angle, box, device=s.device)
 
-    def draw_batch(self, idx):
-        """idx int[B] -> a batch with the per-sample parameters drawn (or,
-        without augmentation, fixed) as the reference does."""
+    def draw_params(self, idx):
+        """The host-side draws of one batch, in the order the generator is
+        consumed -> (k, is_flip, angle, box)."""
         from .augment import random_params
         B = len(idx)
         k = [self.draw_k(i) for i in idx]
@@ -423,16 +423,49 @@ class SequenceLoader:
         else:
             is_flip, angle = np.zeros(B, bool), np.zeros(B)
             box = np.tile(central_box(self.seq.shape, self.shape), (B, 1))
-        return self.batch(idx, k, is_flip, angle, box)
+        return k, is_flip, angle, box
+
+    def draw_batch(self, idx):
+        """idx int[B] -> a batch with the per-sample parameters drawn (or,
+        without augmentation, fixed) as the reference does."""
+        return self.batch(idx, *self.draw_params(idx))
+
+    # ---- position in the stream (docs/CHECKPOINT_SPEC.md) ---------------
+    def state(self):
+        """Where the stream stands: the generator's state at the start of the
+        current permutation and the batches drawn from it since.  Plain ints,
+        strings and dicts: loads under ``torch.load(weights_only=True)``."""
+        if getattr(self, '_perm_state', None) is None:
+            return {'rng': self.rng.bit_generator.state, 'drawn': 0}
+        return {'rng': self._perm_state, 'drawn': int(self._drawn)}
+
+    def restore(self, state):
+        """The next iteration continues the stream ``state`` was taken from:
+        the permutation and the draws of the batches already handed out are
+        repeated on the host and discarded, nothing is launched."""
+        self._resume = {'rng': state['rng'], 'drawn': int(state['drawn'])}
+        self._perm_state = None
 
     def __iter__(self):
         B, done = self.batch_size, 0
+        resume, self._resume = getattr(self, '_resume', None), None
+        if resume is not None:
+            self.rng.bit_generator.state = resume['rng']
         while True:
+            self._perm_state, self._drawn = self.rng.bit_generator.state, 0
             order = self.rng.permutation(self.num_samples)
             for b0 in range(0, order.size - B + 1, B):
+                if resume is not None and self._drawn < resume['drawn']:
+                    self.draw_params(order[b0:b0 + B])
+                    self._drawn += 1
+                    continue
                 if self.steps is not None and done >= self.steps:
                     return
-                yield self.draw_batch(order[b0:b0 + B])
+                idx = order[b0:b0 + B]
+                params = self.draw_params(idx)
+                self._drawn += 1        # drawn: state() now belongs to this batch
+                yield self.batch(idx, *params)
                 done += 1
+            resume = None
             if self.steps is None:
                 return

@@ -982,6 +982,37 @@ int dvsof_grad_centralize_multi(const int64_t *rows, int num_rows,
                                 void *stream);
 
 /* ------------------------------------------------------------------ *
+ * Checkpoint snapshot (csrc/snapshot.hip, docs/CHECKPOINT_SPEC.md): one
+ * launch copies the storage of many float32 tensors into one device slab and
+ * counts the values whose exponent field is all ones (NaN, +-Inf).
+ *
+ * Slab: DVSOF_SNAPSHOT_HEADER_BYTES of header, then the tensors at their
+ * offsets.  Header word[parity] (uint32) holds the count of this launch;
+ * word[parity ^ 1] is zeroed by this launch for the next one, which passes
+ * the other parity.  The first launch into a slab needs word[parity] == 0
+ * (a freshly zeroed allocation).  Nothing else of the header and no byte
+ * between or behind the tensors is written.
+ *
+ *   srcs     device uint64[T]: address of tensor t's storage (float32,
+ *            4-byte aligned; dense: counts[t] consecutive floats)
+ *   counts   device int64[T]: elements
+ *   offsets  device int64[T]: first float of tensor t in the slab, counted
+ *            from the slab's start; a multiple of 4 (16 bytes) and at least
+ *            DVSOF_SNAPSHOT_HEADER_BYTES / 4
+ *   items    device int32[2*num_items]: (tensor id, chunk index), chunk =
+ *            dvsof_snapshot_chunk_elems() elements
+ *   slab     16-byte aligned
+ * num_items == 0 enqueues nothing and returns 0.  The tables and the slab
+ * bound are the caller's: the kernel cannot check them.
+ * ------------------------------------------------------------------ */
+#define DVSOF_SNAPSHOT_HEADER_BYTES 16
+int dvsof_snapshot_chunk_elems(void);
+int dvsof_snapshot_header_bytes(void);
+int dvsof_snapshot_pack(const uint64_t *srcs, const int64_t *counts,
+                        const int64_t *offsets, const int32_t *items,
+                        int num_items, void *slab, int parity, void *stream);
+
+/* ------------------------------------------------------------------ *
  * The flow member of a decoder stage in weight space (csrc/flowfold.hip).
  * Stage i convolves cat[x, skip, flow] with flow = Wh x + bh, the previous
  * stage's 1x1 flow head applied to the x member.  For the BACKWARD

@@ -19,6 +19,9 @@
 #                                     forward_alternating: float-atomics forward / learned_fwd_deterministic /
 #                                     fixed voxeliser in alternating blocks of one run
 #                                     (tools/learned_voxel_bench.py)
+#   checkpoint [checkpoint_bench.py args]  training-thread stall of a reference-style checkpoint against the device
+#                                     snapshot + writer thread, the gather launch alone, samples/s with a checkpoint
+#                                     every 100 steps against none (tools/checkpoint_bench.py)
 #   lossprobe B H W bits...           loss path under the probe build's DVSOF_LOSS_DBG bits
 #   timeline [bench args]             rocprofv3 kernel trace of a short run -> one step per queue
 #   feedtrace [wire|compact]          kernel + memory-copy trace of the train loop fed from host memory
@@ -70,6 +73,9 @@ learned)
   # the resident model's replay against its eager loop under the loopback exchange (8 ranks, 50 us)
   timeout -k 10 300 env "${envs[@]}" DVSOF_LOOPBACK=8:50 python tools/learned_voxel_bench.py --captured-only "$@" > $O/learned_loopback.json 2> $O/learned_loopback.err
   echo "learned loopback rc=$?"; cut -c1-2000 $O/learned_loopback.json; tail -3 $O/learned_loopback.err ;;
+checkpoint)
+  timeout -k 10 560 env "${envs[@]}" python tools/checkpoint_bench.py "$@" > $O/checkpoint.jsonl 2> $O/checkpoint.err
+  echo "checkpoint rc=$?"; cut -c1-600 $O/checkpoint.jsonl; tail -3 $O/checkpoint.err ;;
 lossprobe)
   B=$1; H=$2; W=$3; shift 3
   for bits in "$@"; do echo -n "DBG=$bits: "; DVSOF_LOSS_DBG=$bits DVSOF_PROBE_LIB=1 timeout -k 10 120 python tools/loss_probe.py $B $H $W 2>&1 | tail -1; done ;;

@@ -5,10 +5,17 @@
 (RCCL gradient all-reduce overlapped with backward), ``--synthetic`` and
 ``--sequence DIR`` (one recorded sequence kept on the device).
 
-The reference's HDF5 data pipeline, TensorBoard writer, serializer and hooks
-are outside this build's scope: when this file is
-dropped into the reference tree they are imported from there (``utils.*``);
-otherwise ``--synthetic`` supplies batches in the same wire format.
+Checkpoints, resume and validation are the reference's (:142-217) through this
+package's ``serializer.Serializer`` and ``hooks``: a run continues from the
+newest checkpoint of ``--model`` unless ``--do_not_continue``, with its
+optimizer, schedulers and its position in the data stream
+(docs/CHECKPOINT_SPEC.md).
+
+The reference's HDF5 data pipeline and TensorBoard writer are outside this
+build's scope: the pipeline is imported from the
+reference tree (``utils.dataloader``) when this file is dropped into it;
+otherwise ``--synthetic``, ``--sequence`` or ``--preprocessed-dataset-path``
+supply batches in the same wire format.
 """
 import sys
 from argparse import ArgumentParser
@@ -25,8 +32,11 @@ from dvs_of_training_framework_amd.optim import FusedAdamW, FusedRAdam, \
 from dvs_of_training_framework_amd.options import (
     add_train_arguments, add_preprocessed_dataset_arguments,
     validate_train_args)
+from dvs_of_training_framework_amd.hooks import SerializationHook, \
+    ValidationHook
+from dvs_of_training_framework_amd.serializer import Serializer
 from dvs_of_training_framework_amd.timer import EventTimer, FakeTimer
-from dvs_of_training_framework_amd.training import train
+from dvs_of_training_framework_amd.training import make_hook_periodic, train
 
 script_dir = Path(__file__).resolve().parent
 
@@ -112,16 +122,53 @@ class SyntheticLoader:
     """Endless seeded batches in the reference's wire format
     (utils/dataset.py:961-1020), rank-sharded by seed."""
 
-    def __init__(self, args, rank, steps):
+    def __init__(self, args, rank, steps, start=0, seed=1234):
+        """``steps`` batches from batch ``start`` on: batch i is seeded by i,
+        so a resumed run draws what the uninterrupted one would have."""
         self.args, self.rank, self.steps = args, rank, steps
+        self.next, self.seed = int(start), seed
+
+    def __len__(self):
+        return self.steps
+
+    def state(self):
+        return {'next': int(self.next)}
+
+    def restore(self, state):
+        self.next = int(state['next'])
 
     def __iter__(self):
         a = self.args
         seq = a.prefix_length + a.suffix_length + 1
-        for i in range(self.steps):
+        for i in range(self.next, self.next + self.steps):
+            self.next = i + 1
             yield synthetic.to_torch(synthetic.make_batch(
-                1234 + self.rank + 1000 * i, a.mbs, a.height, a.width,
+                self.seed + self.rank + 1000 * i, a.mbs, a.height, a.width,
                 a.synthetic_events, seq_len=seq))
+
+
+class _FixedBatches:
+    """The same ``n`` seeded batches at every pass (validation)."""
+
+    def __init__(self, args, n, seed):
+        self.args, self.n, self.seed = args, n, seed
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        return iter(SyntheticLoader(self.args, 0, self.n, seed=self.seed))
+
+
+# training batches are seeded 1234 + rank + 1000 * i: another residue class
+VALIDATION_SEED = 1234 + 500
+
+
+def preprocessed_position(samples_passed, world, rank, mbs):
+    """Sample the preprocessed loader of ``rank`` continues from: every rank
+    has passed ``samples_passed`` samples, ``_Strided`` then leaves out the
+    other ranks' batches."""
+    return samples_passed * world + rank * mbs
 
 
 class _Strided:
@@ -146,6 +193,18 @@ class _NullLogger:
         pass
 
 
+def make_logger(args, rank):
+    if rank == 0:
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            # (flushed by the serialization hook only, as in the reference)
+            return SummaryWriter(str(args.log_path), max_queue=100000000,
+                                 flush_secs=100000000)
+        except Exception:       # tensorboard is not installed everywhere
+            pass
+    return _NullLogger()
+
+
 def check_representation_args(args, world):
     """More than one process with a learnable representation needs the
     resident gradient slot: that is what joins the gradient exchange."""
@@ -164,6 +223,94 @@ def check_representation_args(args, world):
                          'knots is part of the gradient exchange')
 
 
+def note(text):
+    """One line on stderr (prefix ``run:``; ``capture:`` lines are the loop's)."""
+    print(f'run: {text}', file=sys.stderr)
+
+
+def make_train_loader(args, device, rank, world, steps, samples_passed):
+    """The training loader for ``steps`` micro-batches, ``samples_passed``
+    samples into the run (a loader with ``restore`` is positioned by the
+    caller from its checkpointed state instead)."""
+    if args.synthetic:
+        return SyntheticLoader(args, rank, steps)
+    if getattr(args, 'sequence', None) is not None:
+        # one recorded sequence, resident on the device: batches are a window
+        # table and one gather launch each (sequence.py); ranks draw different
+        # permutations
+        import numpy as np
+        from dvs_of_training_framework_amd.sequence import FrameSequence, \
+            SequenceLoader
+        return SequenceLoader(
+            FrameSequence.from_directory(args.sequence, device), args.shape,
+            args.mbs, augmentation=True, collapse_length=args.cl,
+            seq_length=args.prefix_length + args.suffix_length + 1,
+            rng=np.random.default_rng(1234 + rank), steps=steps)
+    if getattr(args, 'preprocessed_dataset_path', None) is not None:
+        # utils/dataloader.py:89-100: the preprocessed (encoded / quantized)
+        # dataset; --compact-events keeps raw events in their 9 B/event columns
+        # all the way to the device voxeliser.  Ranks read disjoint strides.
+        from dvs_of_training_framework_amd.preprocessed import \
+            PreprocessedDataloader
+        loader = PreprocessedDataloader(
+            path=args.preprocessed_dataset_path, batch_size=args.mbs,
+            is_raw=args.is_raw, cache_dir=getattr(args, 'cache_dir', None),
+            cache_size=getattr(args, 'cache_size', 0),
+            process_only_once=False,
+            compact=getattr(args, 'compact_events', False))
+        loader.set_index(preprocessed_position(samples_passed, world, rank,
+                                               args.mbs))
+        return _Strided(loader, world) if world > 1 else loader
+    try:    # dropped into the reference tree: use its data pipeline
+        from utils.dataloader import get_trainset_params, get_dataloader, \
+            choose_data_path
+        return get_dataloader(get_trainset_params(choose_data_path(args)),
+                              sample_idx=samples_passed)
+    except ImportError as e:
+        raise SystemExit(
+            'no dataset pipeline importable (the reference\'s utils.* and '
+            f'h5py are needed: {e}); pass --synthetic') from e
+
+
+def make_validation_loader(args, device):
+    """None: nothing to validate on (said once on stderr)."""
+    if getattr(args, 'validation_sequence', None) is not None:
+        from dvs_of_training_framework_amd.sequence import FrameSequence, \
+            SequenceLoader
+        return SequenceLoader(
+            FrameSequence.from_directory(args.validation_sequence, device),
+            args.shape, args.mbs, augmentation=False,
+            seq_length=args.prefix_length + args.suffix_length + 1, steps=None)
+    if args.synthetic and getattr(args, 'synthetic_validation_batches', 0) > 0:
+        return _FixedBatches(args, args.synthetic_validation_batches,
+                             VALIDATION_SEED)
+    return None
+
+
+def restore_loader(loader, state, rank, world, global_step, args):
+    """Position ``loader`` from the checkpoint's ``loader_state`` (a list
+    indexed by rank); a checkpoint without one (the reference's) positions by
+    the step count."""
+    if not hasattr(loader, 'restore'):
+        return
+    states = state.get('loader_state')
+    if states is not None and states[rank] is not None:
+        loader.restore(states[rank])
+    elif isinstance(loader, SyntheticLoader):
+        loader.restore({'next': global_step * args.accum_step})
+
+
+def check_resume_world(state, world, path):
+    """A checkpoint holds one loader position per process that wrote it: a run
+    of another size cannot continue its data stream."""
+    written_by = state.get('world_size', 1)
+    if written_by != world:
+        raise SystemExit(
+            f'{path} was written by {written_by} process(es), this run has '
+            f'{world}: the position in the data stream does not carry over; '
+            'pass --do_not_continue to start from step 0')
+
+
 def main(argv=None):
     args = parse_args(sys.argv[1:] if argv is None else argv)
     device = torch.device(args.device)
@@ -178,7 +325,16 @@ def main(argv=None):
     check_representation_args(args, world)
     model = init_model(args, device)
     parallel.broadcast_parameters(model)
-    optimizer, scheduler = construct_train_tools(args, model)
+
+    serializer = Serializer(args.model, args.num_checkpoints,
+                            args.permanent_interval,
+                            async_snapshot=not getattr(args, 'sync_checkpoints',
+                                                       False))
+    known = serializer.list_known_steps()
+    resume = not args.do_not_continue and len(known) > 0
+    last_step = known[-1] if resume else 0
+    optimizer, scheduler = construct_train_tools(args, model,
+                                                 passed_steps=last_step)
     losses = init_losses(args.shape, args.mbs, model, device,
                          sequence_length=args.prefix_length +
                          args.suffix_length + 1, timers=timers)
@@ -187,55 +343,21 @@ def main(argv=None):
         reducer = parallel.GradReducer()
         model.predictor.reducer = reducer
 
-    logger = _NullLogger()
-    if rank == 0:
-        try:
-            from torch.utils.tensorboard import SummaryWriter
-            logger = SummaryWriter(str(args.log_path), max_queue=100000000,
-                                   flush_secs=100000000)
-        except Exception:       # tensorboard is not installed everywhere
-            pass
+    logger = make_logger(args, rank)
 
-    if args.synthetic:
-        loader = SyntheticLoader(args, rank,
-                                 args.training_steps * args.accum_step)
-    elif getattr(args, 'sequence', None) is not None:
-        # one recorded sequence, resident on the device: batches are a window
-        # table and one gather launch each (sequence.py); ranks draw different
-        # permutations
-        import numpy as np
-        from dvs_of_training_framework_amd.sequence import FrameSequence, \
-            SequenceLoader
-        loader = SequenceLoader(
-            FrameSequence.from_directory(args.sequence, device), args.shape,
-            args.mbs, augmentation=True, collapse_length=args.cl,
-            seq_length=args.prefix_length + args.suffix_length + 1,
-            rng=np.random.default_rng(1234 + rank),
-            steps=args.training_steps * args.accum_step)
-    elif getattr(args, 'preprocessed_dataset_path', None) is not None:
-        # utils/dataloader.py:89-100: the preprocessed (encoded / quantized)
-        # dataset; --compact-events keeps raw events in their 9 B/event columns
-        # all the way to the device voxeliser.  Ranks read disjoint strides.
-        from dvs_of_training_framework_amd.preprocessed import \
-            PreprocessedDataloader
-        loader = PreprocessedDataloader(
-            path=args.preprocessed_dataset_path, batch_size=args.mbs,
-            is_raw=args.is_raw, cache_dir=getattr(args, 'cache_dir', None),
-            cache_size=getattr(args, 'cache_size', 0),
-            process_only_once=False,
-            compact=getattr(args, 'compact_events', False))
-        loader.set_index(rank * args.mbs)
-        if world > 1:
-            loader = _Strided(loader, world)
-    else:
-        try:    # dropped into the reference tree: use its data pipeline
-            from utils.dataloader import get_trainset_params, get_dataloader, \
-                choose_data_path
-            loader = get_dataloader(get_trainset_params(choose_data_path(args)))
-        except ImportError as e:
-            raise SystemExit(
-                'no dataset pipeline importable (the reference\'s utils.* and '
-                f'h5py are needed: {e}); pass --synthetic') from e
+    global_step, samples_passed, state = 0, 0, {}
+    if resume:
+        global_step, state = serializer.load_checkpoint(
+            model, last_step, optimizer=optimizer, device=device)
+        check_resume_world(state, world, serializer._id2path(last_step))
+        samples_passed = state.pop('samples_passed', global_step * args.bs)
+        note(f'continuing from step {global_step} ({samples_passed} samples)')
+    remaining = max(args.training_steps - global_step, 0)
+
+    loader = make_train_loader(args, device, rank, world,
+                               remaining * args.accum_step, samples_passed)
+    if resume:
+        restore_loader(loader, state, rank, world, global_step, args)
 
     oib = getattr(args, 'optimizer_in_backward', 'auto')
     if device.type == 'cuda' and hasattr(optimizer, 'fuse_into_backward') and \
@@ -246,19 +368,53 @@ def main(argv=None):
     if getattr(args, 'device_feeder', False) and device.type == 'cuda' and args.is_raw:
         from dvs_of_training_framework_amd.feed import DeviceFeeder
         loader = DeviceFeeder(loader, device)
-    train(model, device, loader, optimizer, args.training_steps,
-          scheduler=scheduler, evaluator=losses, logger=logger,
-          weights=args.loss_weights, is_raw=args.is_raw,
-          accumulation_steps=args.accum_step, timers=timers, hooks={},
-          max_events_per_batch=args.max_events_per_batch, reducer=reducer,
-          capture=getattr(args, 'capture', False))
-    if reducer is not None:
-        reducer.close()
-    if rank == 0:
-        torch.save({'model': model.state_dict(),
-                    'optimizer': optimizer.state_dict(),
-                    'global_step': args.training_steps},
-                   args.model / f'step_{args.training_steps}.pt')
+
+    def extra_state():
+        extra = {'world_size': world}
+        if hasattr(loader, 'state'):
+            extra['loader_state'] = loader.state()
+        return extra
+    hooks = {'serialization': SerializationHook(serializer, model, optimizer,
+                                                logger, extra_state, rank=rank)}
+    periodic = {'serialization': make_hook_periodic(
+        hooks['serialization'], args.checkpointing_interval)}
+    validation_loader = None if args.skip_validation else \
+        make_validation_loader(args, device)
+    if validation_loader is not None:
+        hooks['validation'] = ValidationHook(
+            model, device, validation_loader, logger, losses,
+            args.loss_weights, args.is_raw)
+        periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
+    elif not args.skip_validation:
+        note('no validation data (--validation-sequence, or '
+             '--synthetic-validation-batches with --synthetic): validation is skipped')
+
+    try:
+        if not resume:
+            hooks['serialization'](0, 0)
+        if remaining > 0:
+            if 'validation' in hooks:
+                hooks['validation'](global_step, samples_passed)
+            train(model, device, loader, optimizer, args.training_steps,
+                  scheduler=scheduler, evaluator=losses, logger=logger,
+                  weights=args.loss_weights, is_raw=args.is_raw,
+                  accumulation_steps=args.accum_step, timers=timers,
+                  hooks=periodic, init_step=global_step,
+                  init_samples_passed=samples_passed,
+                  max_events_per_batch=args.max_events_per_batch,
+                  reducer=reducer, capture=getattr(args, 'capture', False))
+            samples = samples_passed + remaining * args.bs
+            if args.training_steps % args.checkpointing_interval != 0:
+                # (otherwise the periodic hook has just written this step)
+                hooks['serialization'](args.training_steps, samples)
+            if 'validation' in hooks:
+                hooks['validation'](args.training_steps, samples)
+        else:
+            note(f'step {global_step} of {args.training_steps} is on disk: nothing to train')
+    finally:
+        if reducer is not None:
+            reducer.close()
+        serializer.close()
 
 
 if __name__ == '__main__':
