@@ -12,6 +12,10 @@ import os
 # runtime initialises, i.e. at the first torch.cuda use -- after this import.
 os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 
+# a DVSOF_* variable nothing reads, or one that chooses the library: say so once, on stderr
+from . import _switches  # noqa: E402
+_switches.report()
+
 
 def __getattr__(name):
     # lazy: importing the package must not need torch.cuda / the HIP library

@@ -5,19 +5,15 @@ raises.  PyTorch is used only for device memory and streams; every entry
 point gets raw device pointers and the current HIP stream.
 """
 import ctypes
-import os
 import re
 from pathlib import Path
 
 import torch
 
+from ._switches import library_path
+
 _PKG = Path(__file__).resolve().parent
-# DVSOF_PROBE_LIB=1: the probe build (`make -C csrc probes`; timing probes of
-# DVSOF_GCONV_DBG / DVSOF_LOSS_DBG compiled in) -- diagnostics tools only
-LIB_PATH = _PKG / ('libdvsof_hip_probes.so' if os.environ.get('DVSOF_PROBE_LIB') == '1'
-                   else 'libdvsof_hip.so')
-if os.environ.get('DVSOF_LIB_PATH'):    # an experiment's variant build (tools/variant.sh)
-    LIB_PATH = Path(os.environ['DVSOF_LIB_PATH']).resolve()
+LIB_PATH = library_path()       # the product build unless DVSOF_LIB_PATH / DVSOF_PROBE_LIB say otherwise
 HEADER_PATH = _PKG.parent / 'include' / 'dvsof.h'
 MAX_SCALES = 8
 

@@ -382,8 +382,8 @@ class CapturedTrainStep:
         self._keep.append(optimizer._dyn)
         if executor:
             pred = model.predictor
-            side = [pred._wgrad_stream(dev)] + list(pred._extra_streams(dev))
-            self.executor = StepExecutor(self.graph, [s for s in side if s is not None])
+            side = pred._wgrad_stream(dev)
+            self.executor = StepExecutor(self.graph, [side] if side is not None else [])
             red = self.reducer
             if self.executor.marks:
                 assert red is not None

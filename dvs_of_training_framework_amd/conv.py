@@ -483,27 +483,3 @@ def act_bwd(dy, actsrc, act, out=None):
         _lib.stream()), 'dvsof_act_bwd')
     return out
 
-
-# ---- timing experiment (DVSOF_STALE_FORMS=1; results are WRONG after the first step): every
-# weight form is made once and reused -- what the step would cost if the forms were free
-import os as _os
-if _os.environ.get('DVSOF_STALE_FORMS') == '1':
-    def _memo(fn, key):
-        cache = {}
-
-        def inner(*a, **k):
-            kk = key(*a, **k)
-            if kk not in cache:
-                cache[kk] = fn(*a, **k)
-            return cache[kk]
-        return inner
-
-    def _dkey(d):
-        return (d.nsrc, tuple(d.src[i].C for i in range(d.nsrc)), d.B, d.H, d.W, d.upsample,
-                d.stride, d.Cout, d.mfma)
-    prepare = _memo(prepare, lambda d, w, dg, phase_weights=None, want16=False:
-                    (_dkey(d), w.data_ptr(), dg, phase_weights is not None and phase_weights.data_ptr(), want16))
-    flow_fold_weights = _memo(flow_fold_weights, lambda w, *a: (w.data_ptr(),) + tuple(
-        x if isinstance(x, int) else x.data_ptr() for x in a))
-    flow_fold_bias = _memo(flow_fold_bias, lambda w, *a: (w.data_ptr(),) + tuple(
-        x if isinstance(x, int) else (x.data_ptr() if x is not None else 0) for x in a))

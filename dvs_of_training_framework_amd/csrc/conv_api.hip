@@ -133,10 +133,6 @@ void fill_wgrad(const dvsof_conv_desc_t *d, const ConvClass &c, WGradParams &P)
     // copies when all of them exist and channel runs are whole 16-byte loads
     P.gout16 = d->mfma == 3 ? (const unsigned short *)d->gout16 : nullptr;
     P.twins = P.gout16 != nullptr && (d->Cout % 8) == 0;
-    {
-        static const bool off = getenv("DVSOF_WGRAD_NO_TWINS") != nullptr;
-        if (off) P.twins = 0;
-    }
     for (int i = 0; i < d->nsrc; ++i)
         if (!P.src[i].flat && (!P.src[i].p16 || (P.src[i].C % 8))) P.twins = 0;
     layer_geometry(P, d, c);
@@ -235,8 +231,7 @@ ConvClass conv_classify(const dvsof_conv_desc_t *d)
     c.wino_mode = d->mfma == 2 ? 2 : 0;
     // ... and its weight gradient too: the tile count is the K dimension of the K-major kernel,
     // which loads whole 16-element groups
-    static const bool no_wino_wgrad = getenv("DVSOF_NO_WINOGRAD_WGRAD") != nullptr;
-    const int wg_tile = (wino && !no_wino_wgrad) ? wino_wgrad_tile(d->B, d->H, d->W, c.wino_mode) : 0;
+    const int wg_tile = wino ? wino_wgrad_tile(d->B, d->H, d->W, c.wino_mode) : 0;
     // sub-pixel layers whose forward (fwd_min.hip) / data gradient (dgrad_min.hip) runs the
     // nine-product minimal algorithm
     bool min9 = false, min9_dgrad = false;

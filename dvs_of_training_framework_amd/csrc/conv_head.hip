@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float *dy,
 // workgroups of the head backward = partial rows of its weight-gradient reduce
 int head_blocks(long long total, int lpp)
 {
-    static const int cap = getenv("DVSOF_HEAD_BLOCKS") ? atoi(getenv("DVSOF_HEAD_BLOCKS")) : 512;
+    constexpr int cap = 512;
     const long long per_block = 4LL * (64 / lpp);
     long long nb = (total + per_block - 1) / per_block;
     return (int)(nb < cap ? (nb < 1 ? 1 : nb) : cap);
@@ -205,6 +205,7 @@ extern "C" {
     default: return DVSOF_EINVAL;                                                              \
     }
 
+constexpr int HEAD_FWD_ITERS = 4;   // pixels per lane group of the forward heads, see dvsof_flow_head_fwd
 static bool head_c_ok(int C) { return C == 16 || C == 32 || C == 64 || C == 128 || C == 256; }
 
 int dvsof_flow_head_fwd(const float *x, const float *w, const float *bias, float *flow, int B,
@@ -214,8 +215,7 @@ int dvsof_flow_head_fwd(const float *x, const float *w, const float *bias, float
     hipStream_t st = as_stream(stream);
     // no partial sums here, so the grid is free: ~4 pixels per lane group keeps enough
     // waves in flight (512 workgroups walked 32 dependent iterations: 22 us for 67 MB)
-    static const int fwd_iters = getenv("DVSOF_HEAD_FWD_ITERS") ? atoi(getenv("DVSOF_HEAD_FWD_ITERS")) : 4;
-    const long long per_block = 4LL * (64 / (C / 4)) * (fwd_iters > 0 ? fwd_iters : 1);
+    const long long per_block = 4LL * (64 / (C / 4)) * HEAD_FWD_ITERS;
     long long nbl = ((long long)B * H * W + per_block - 1) / per_block;
     const int nb = (int)(nbl < 1 ? 1 : nbl > 65535 ? 65535 : nbl);
     HEAD_DISPATCH(head_fwd_kernel, nb, x, w, bias, flow, B, H * W);
@@ -228,7 +228,6 @@ int dvsof_flow_heads_fwd(int n, const float *const *x, const float *const *w, co
                          void *stream)
 {
     if (n < 1 || n > HEADS_MAX || !x || !w || !flow || !H || !W || !C || B < 1) return DVSOF_EINVAL;
-    static const int fwd_iters = getenv("DVSOF_HEAD_FWD_ITERS") ? atoi(getenv("DVSOF_HEAD_FWD_ITERS")) : 4;
     HeadsFwd A = {};
     long long blocks = 0;
     for (int i = 0; i < n; ++i) {
@@ -239,7 +238,7 @@ int dvsof_flow_heads_fwd(int n, const float *const *x, const float *const *w, co
         A.flow[i] = flow[i];
         A.HW[i] = H[i] * W[i];
         A.C[i] = C[i];
-        const long long per_block = 4LL * (64 / (C[i] / 4)) * (fwd_iters > 0 ? fwd_iters : 1);
+        const long long per_block = 4LL * (64 / (C[i] / 4)) * HEAD_FWD_ITERS;
         long long nbl = ((long long)B * H[i] * W[i] + per_block - 1) / per_block;
         nbl = nbl < 1 ? 1 : nbl > 65535 ? 65535 : nbl;
         A.block_begin[i] = (int)blocks;

@@ -77,7 +77,6 @@ WGradPlan wgrad_plan(const WGradParams &P, const FlatWG *flat, int nflat, bool w
 // P.tile_begin = the column tiles, `width` columns each, of the chosen members (vector and / or
 // flat), cols_per_channel columns per channel; returns their number
 int wgrad_enumerate_tiles(WGradParams &P, int cols_per_channel, int width, bool vec, bool flat);
-bool wgrad_xcd_on();    // DVSOF_WGRAD_XCD != 0: XCD-aware workgroup order
 bool wgrad2_eligible(const WGradParams &P);      // what wgrad2_launch requires of its caller
 // wgrad.hip: runs the plan
 int wgrad_launch(WGradParams P, float *dW, float *dbias, float *ws, size_t ws_floats,
@@ -99,7 +98,7 @@ int wgrad_resident_launch(const WGradParams &P0, hipStream_t st)
         DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         attr_set = true;
     }
-    P.xcd = wgrad_xcd_on() ? 1 : 0;
+    P.xcd = 1;      // XCD-aware workgroup order
     hipLaunchKernelGGL(KERNEL, dim3(nt, P.Cout / 32, P.S), dim3(NT), LDS, st, P);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;

@@ -427,11 +427,10 @@ __global__ __launch_bounds__(DM_NT) void dgrad_min_f32_kernel(const GConvParams 
 }  // namespace
 
 // the descriptor's shape beyond fwd_min's test: 64 | every member, 8 | H
-// (DVSOF_NO_DGRAD_MIN=1: the 4x4 stride-2 form on gconv2)
+// (otherwise: the 4x4 stride-2 form on gconv2)
 bool min9_dgrad_shape_ok(const int *C, int Cout, int H)
 {
-    static const bool off = getenv("DVSOF_NO_DGRAD_MIN") != nullptr;
-    return !off && (C[0] & 63) == 0 && (C[1] & 63) == 0 && (H % DM_NR) == 0 && (Cout & 15) == 0;
+    return (C[0] & 63) == 0 && (C[1] & 63) == 0 && (H % DM_NR) == 0 && (Cout & 15) == 0;
 }
 
 int min9_prepare_dgrad(const float *w, float *wq, int Cout, int Ctot, hipStream_t st)
@@ -460,24 +459,18 @@ int dgrad_min_launch(const GConvParams &P, hipStream_t st)
     if (!attr_set) {
         DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)dgrad_min_f32_kernel<1>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, DM_LDS));
-        DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)dgrad_min_f32_kernel<2>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, DM_LDS));
         attr_set = true;
     }
-    // items (pixel block, 64-channel tile) per workgroup.  Two (DVSOF_DGRAD_MIN_IPW=2; needs an even
-    // chunk count: stage = chunk parity) hide the second item's first-chunk latency: alone on the
-    // GPU the finest stage 151 -> 142 us, the others unchanged or worse (230 registers: 121 / 114 /
-    // 108 against 121 / 110 / 107) -- and inside the step, beside the weight-gradient lane, a loss:
-    // 2.538-2.547 against 2.501-2.513 ms.  Default: one.
+    // One item (pixel block, 64-channel tile) per workgroup.  Two (an even chunk count, stage =
+    // chunk parity) hide the second item's first-chunk latency: alone on the GPU the finest stage
+    // 151 -> 142 us, the others unchanged or worse (230 registers: 121 / 114 / 108 against 121 /
+    // 110 / 107) -- and inside the step, beside the weight-gradient lane, a loss: 2.538-2.547
+    // against 2.501-2.513 ms.
     const long long total = (long long)P.B * (P.Ho / DM_NR) * (P.Wo / 16) * (P.N / 64);
-    static const int ipw_env = getenv("DVSOF_DGRAD_MIN_IPW") ? atoi(getenv("DVSOF_DGRAD_MIN_IPW")) : 0;
     const int nchunks = P.Cin_tot / 16;
-    int ipw = ipw_env == 2 ? 2 : 1;
-    if ((nchunks & 1) || (total & 1)) ipw = 1;
     // resident weights (two chunks of K): 256 workgroups (whole channel-tile rows of them), >= 2 items each
-    static const bool no_res = getenv("DVSOF_DGRAD_MIN_RESIDENT") && atoi(getenv("DVSOF_DGRAD_MIN_RESIDENT")) == 0;
     const int nct = P.N / 64;
-    if (!no_res && !ipw_env && nchunks == 2 && 256 % nct == 0 && total >= 2 * 256) {
+    if (nchunks == 2 && 256 % nct == 0 && total >= 2 * 256) {
         static bool attr0 = false;
         if (!attr0) {
             DVSOF_HIP_TRY(hipFuncSetAttribute((const void *)dgrad_min_f32_kernel<0>,
@@ -489,11 +482,8 @@ int dgrad_min_launch(const GConvParams &P, hipStream_t st)
         conv_note_kernel(DVSOF_KERNEL_DGRAD_MIN0, 0);
         return DVSOF_OK;
     }
-    if (ipw == 2)
-        hipLaunchKernelGGL(dgrad_min_f32_kernel<2>, dim3((unsigned)(total / 2)), dim3(DM_NT), DM_LDS, st, P, (int)total);
-    else
-        hipLaunchKernelGGL(dgrad_min_f32_kernel<1>, dim3((unsigned)total), dim3(DM_NT), DM_LDS, st, P, (int)total);
+    hipLaunchKernelGGL(dgrad_min_f32_kernel<1>, dim3((unsigned)total), dim3(DM_NT), DM_LDS, st, P, (int)total);
     DVSOF_LAUNCH_CHECK();
-    conv_note_kernel(ipw == 2 ? DVSOF_KERNEL_DGRAD_MIN2 : DVSOF_KERNEL_DGRAD_MIN1, 0);
+    conv_note_kernel(DVSOF_KERNEL_DGRAD_MIN1, 0);
     return DVSOF_OK;
 }

@@ -763,10 +763,8 @@ int dvsof_exec_calibrate(void *exec, void *stream)
     for (auto e : ev)
         if (e) (void)hipEventDestroy(e);
     if (rc) return rc;
-    // DVSOF_EXEC_PLAN = paths | list | chain: that plan; default: every plan is tried on
-    // the next steps (real steps, timed on the device), the fastest stays
-    static const char *want = getenv("DVSOF_EXEC_PLAN");
-    static const double hop = getenv("DVSOF_EXEC_HOP") ? atof(getenv("DVSOF_EXEC_HOP")) : 8.0;
+    // every plan is tried on the next steps (real steps, timed on the device), the fastest stays
+    constexpr double hop = 8.0;
     x->cands.clear();
     x->trial_next = x->trial_cur = -1;
     if (x->max_lanes < 2) return wire(x);
@@ -774,14 +772,12 @@ int dvsof_exec_calibrate(void *exec, void *stream)
     x->cands.push_back(plan_by_list(x, hop));
     x->cands.push_back(plan_chain(x));
     int fixed = -1;
-    for (size_t i = 0; want && i < x->cands.size(); ++i)
-        if (!strcmp(want, x->cands[i].name)) fixed = (int)i;
     // Under an exchange every rank takes the SAME plan, the capture's own two-stream split
     // ("chain": what the trials picked in every 1-rank and loopback run): timed trials would
     // measure the other ranks' arrival at the collectives as much as this rank's kernels, ranks
     // could settle on different plans, and the trial steps themselves (host waits for a step's
-    // end) are one more place where ranks wait for each other.  DVSOF_EXEC_PLAN overrides.
-    if (fixed < 0 && !want && x->comm)
+    // end) are one more place where ranks wait for each other.
+    if (x->comm)
         for (size_t i = 0; i < x->cands.size(); ++i)
             if (!strcmp("chain", x->cands[i].name)) fixed = (int)i;
     if (fixed >= 0) {
@@ -799,7 +795,7 @@ int dvsof_exec_calibrate(void *exec, void *stream)
 // Steps after calibration: plan k % n on trial k, `rounds` rounds; then the fastest.
 static int next_trial(Exec *x)
 {
-    static const int rounds = getenv("DVSOF_EXEC_TRIALS") ? std::max(1, atoi(getenv("DVSOF_EXEC_TRIALS"))) : 2;
+    constexpr int rounds = 2;
     const int n = (int)x->cands.size();
     if (x->trial_cur >= 0) {    // the step in flight was a trial: its device time
         DVSOF_HIP_TRY(hipEventSynchronize(x->t1));

@@ -336,7 +336,7 @@ inline int ncb_of(int K) { return (K + 1 + 31) / 32; }
 
 inline int wgrad_groups(int ntiles)
 {
-    static const int g = getenv("DVSOF_FIRST_WGRAD_GROUPS") ? atoi(getenv("DVSOF_FIRST_WGRAD_GROUPS")) : 512;
+    constexpr int g = 512;
     return ntiles < g ? ntiles : g;
 }
 
@@ -359,12 +359,11 @@ void fill(FirstP &P, const float *x, int B, int C, int H, int W)
 }  // namespace
 
 // 3x3 / stride 2 / pad 1, one planar source of <= 16 channels, 64 output
-// channels, even frame sides (DVSOF_NO_FIRST_KERNEL=1: the general kernels)
+// channels, even frame sides (otherwise: the general kernels)
 bool first_layer_shape(int nsrc, int planar, int C, int Cout, int H, int W, int ksize, int stride,
                        int pad, int upsample)
 {
-    static const bool off = getenv("DVSOF_NO_FIRST_KERNEL") != nullptr;
-    return !off && nsrc == 1 && planar && C >= 1 && C <= F_MAXC && Cout == F_N && ksize == 3 &&
+    return nsrc == 1 && planar && C >= 1 && C <= F_MAXC && Cout == F_N && ksize == 3 &&
            stride == 2 && pad == 1 && !upsample && !(H & 1) && !(W & 1) && H >= 2 && W >= 2;
 }
 

@@ -370,11 +370,10 @@ __global__ __launch_bounds__(FM_NT) void fwd_min_f32_kernel(const GConvParams P)
 
 // Shape test shared by the weight preparation and the launch (both see the same descriptor):
 // exact f32, two NHWC vector members with multiples of 32 channels, 32 | Cout, 16 | W, 4 | H
-// (DVSOF_NO_FWD_MIN=1: the sixteen-product kernels)
+// (otherwise: the sixteen-product kernels)
 bool min9_shape_ok(int mfma, int nsrc, const int *C, const int *nhwc, int Cout, int H, int W)
 {
-    static const bool off = getenv("DVSOF_NO_FWD_MIN") != nullptr;
-    if (off || mfma != 0 || nsrc != 2) return false;
+    if (mfma != 0 || nsrc != 2) return false;
     for (int s = 0; s < 2; ++s)
         if (!nhwc[s] || (C[s] & 31)) return false;
     return (Cout & 31) == 0 && (W % 16) == 0 && (H % 4) == 0 && H >= 4;
@@ -420,11 +419,9 @@ int fwd_min_launch(const GConvParams &P, hipStream_t st)
         return DVSOF_EINVAL;
     // rows per block: the largest of 16 | 8 | 4 that divides H and leaves >= 256 workgroups
     // (else the smallest that divides)
-    static const int force = getenv("DVSOF_FWD_MIN_NR") ? atoi(getenv("DVSOF_FWD_MIN_NR")) : 0;
     const long long per_row = (long long)P.B * (P.Wv / 16) * (P.N / 32);
     int nr = 4;
     if (P.Hv % 8 == 0 && per_row * (P.Hv / 8) >= 256) nr = 8;
-    if ((force == 4 || force == 8) && P.Hv % force == 0) nr = force;
     const int grid = (int)(per_row * (P.Hv / nr));
     const bool z = P.zout != nullptr;
     if (nr == 8) return z ? fm_launch<8, true>(P, grid, st) : fm_launch<8, false>(P, grid, st);

@@ -518,18 +518,13 @@ __global__ __launch_bounds__(FQ_NT) void fwd_patch_f32_kernel(const GConvParams 
 
 // The finest decoder stage: two vector members of 64 channels, 32 output channels, four
 // sub-pixel phases of 2x2 taps, 16 | width, 2 | height -- in the bf16-twins mode and in exact
-// f32 (DVSOF_NO_FWD_PATCH=1 / DVSOF_NO_FWD_PATCH_F32=1: gconv2)
-static bool fp_f32(const GConvParams &P)
-{
-    static const bool off = getenv("DVSOF_NO_FWD_PATCH_F32") != nullptr;
-    return !off && P.mfma_bf16 == 0;
-}
+// f32 (otherwise: gconv2)
+static bool fp_f32(const GConvParams &P) { return P.mfma_bf16 == 0; }
 
 bool fwd_patch_eligible(const GConvParams &P)
 {
-    static const bool off = getenv("DVSOF_NO_FWD_PATCH") != nullptr;
     const bool f32 = fp_f32(P);
-    if (off || !(f32 || (P.mfma_bf16 == 3 && P.W16)) || !P.W) return false;
+    if (!(f32 || (P.mfma_bf16 == 3 && P.W16)) || !P.W) return false;
     if (P.nph != 4 || P.ks != 2 || P.stride != 1 || P.up != UP_NONE) return false;
     if (P.ph_pad != 1 || P.pad != 1 || P.src_ph_stride != 0 || P.quad || P.ph_exact) return false;
     if (P.nsrc != 2 || P.ndst != 1 || P.N != FP_N || P.Cin_tot != 2 * FP_CM) return false;
@@ -597,16 +592,16 @@ int fwd_patch_launch(const GConvParams &P, hipStream_t st)
         static const int dbg = getenv("DVSOF_FWD_PATCH_DBG") ? atoi(getenv("DVSOF_FWD_PATCH_DBG")) : 0;
         const_cast<GConvParams &>(P).dbg = dbg;
 #endif
-        static const int want = getenv("DVSOF_FWD_PATCH_F32_WGS") ? atoi(getenv("DVSOF_FWD_PATCH_F32_WGS")) : 256;
+        constexpr int want = 256;
         long long bpw = (nblocks + want - 1) / want;
         if (bpw < 2) bpw = 2;
         const int grid = (int)((nblocks + bpw - 1) / bpw);
         return P.zout ? fq_launch<true>(P, (int)nblocks, (int)bpw, grid, st)
                       : fq_launch<false>(P, (int)nblocks, (int)bpw, grid, st);
     }
-    // persistent workgroups: DVSOF_FWD_PATCH_WGS of them (default 512: two per CU), each at
-    // least 4 blocks (the weights are loaded once per workgroup)
-    static const int want = getenv("DVSOF_FWD_PATCH_WGS") ? atoi(getenv("DVSOF_FWD_PATCH_WGS")) : 512;
+    // persistent workgroups: 512 of them (two per CU), each at least 4 blocks (the weights are
+    // loaded once per workgroup)
+    constexpr int want = 512;
     long long bpw = (nblocks + want - 1) / want;
     if (bpw < 4) bpw = 4;
     const int grid = (int)((nblocks + bpw - 1) / bpw);

@@ -456,13 +456,12 @@ int gconv_launch(const GConvParams &P, int tile_hint, hipStream_t st)
         if (!P.src[s].flat && (P.src[s].sc != 1 || (P.src[s].C & 3))) return DVSOF_EINVAL;
     // data-gradient form with trailing narrow planar destinations: peel them off
     {
-        static const bool no_split = getenv("DVSOF_GCONV_NO_SPLIT") != nullptr;
         int ntrail = 0, d = P.ndst;
         while (d > 1 && (P.dst[d - 1].sc != 1 || P.dst[d - 1].C < BK) && ntrail + P.dst[d - 1].C <= FLATN_MAX) {
             ntrail += P.dst[d - 1].C;
             --d;
         }
-        if (!no_split && ntrail > 0 && P.nsrc == 1 && !P.src[0].flat && P.src[0].sc == 1 &&
+        if (ntrail > 0 && P.nsrc == 1 && !P.src[0].flat && P.src[0].sc == 1 &&
             (P.src[0].C & 3) == 0 && P.up == UP_NONE && !P.quad && P.nph == 1 && !P.bias &&
             !P.zout && P.act == ACT_NONE && P.N - ntrail >= 32) {
             GConvParams Q = P;
@@ -489,14 +488,13 @@ int gconv_launch(const GConvParams &P, int tile_hint, hipStream_t st)
     const int tile = tile_hint > 0 ? tile_hint : tile_env > 0 ? tile_env
                                                               : gconv_pick_tile((long long)P.M * P.nph, P.N);
     {   // v2 (LDS-DMA ring, VALU-free main loop) when the shape allows it
-        static const bool force_v1 = getenv("DVSOF_GCONV_V1") != nullptr;
         long long src_bytes = 0;
         for (int s = 0; s < P.nsrc; ++s) {
             const long long b = (long long)P.B * P.src[s].sb * 4;
             src_bytes = b > src_bytes ? b : src_bytes;
         }
         const long long w_bytes = (long long)P.N * P.ks * P.ks * P.Cin_tot * 4 * P.nph;
-        if (!force_v1 && gconv2_eligible(P, src_bytes, w_bytes)) return gconv2_launch(P, tile, st);
+        if (gconv2_eligible(P, src_bytes, w_bytes)) return gconv2_launch(P, tile, st);
     }
     switch (tile) {
     case 1: return launch<2, 2, 2, 2>(P, st);  // 128 x 128

@@ -560,13 +560,11 @@ int launch2x(const GConvParams &P, int nflat, int nvec, hipStream_t st)
     }
     dim3 grid((P.M + BM - 1) / BM, (P.N + BN - 1) / BN, P.nph);
     GConvParams Q = P;
-    {   // XCD-aware tile order (see the kernel): DVSOF_GCONV_XCD = 0 off (default: on)
-        static const int xe = getenv("DVSOF_GCONV_XCD") ? atoi(getenv("DVSOF_GCONV_XCD")) : -1;
+    {   // XCD-aware tile order (see the kernel)
         const unsigned total = grid.x * grid.y * grid.z;
-        const bool want = xe != 0;
         // (not the exact-tap phases: they differ 4x in work and are dispatched heavy first;
         // phase-fastest order put heavy ones into the tail: stride-2 data gradients +20-40 %)
-        Q.xcd = (want && TAG == 0 && !P.ph_exact && (total & 7u) == 0 && total >= 64) ? 1 : 0;
+        Q.xcd = (TAG == 0 && !P.ph_exact && (total & 7u) == 0 && total >= 64) ? 1 : 0;
     }
     hipLaunchKernelGGL((gconv2_kernel<WROWS, WCOLS, TM, TN, KSUB, NS, KSPLIT, BF16, TAG>), grid,
                        dim3(CONV_NT * KSPLIT), LDS, st, Q, nflat, nvec);
@@ -622,8 +620,7 @@ int gconv2_launch(const GConvParams &P0, int tile, hipStream_t st)
     const int unit = P.mfma_bf16 == 3 ? 2 : 1;     // channels per 4-byte unit of a K slice
     // K depth per barrier: 32 when every vector member allows it (small tiles
     // run 1-2 waves per SIMD, where the per-slice sync cost is exposed)
-    static const bool k16 = getenv("DVSOF_GCONV_K16") != nullptr;
-    bool k32 = !k16 && (tile == 2 || tile == 3);
+    bool k32 = tile == 2 || tile == 3;
     for (int s = 0; s < P.nsrc; ++s)
         if (!P.src[s].flat && ((P.src[s].C / unit) % (2 * BK))) k32 = false;
     {   // larger stages cost occupancy: only when the grid is <= 2 workgroups per CU anyway
@@ -636,7 +633,7 @@ int gconv2_launch(const GConvParams &P0, int tile, hipStream_t st)
     // one workgroup per CU (8-wave form): K depth 64 per barrier -- both waves of
     // a SIMD reach the barrier together, so the sync/issue bubble is paid per stage
     bool k64 = false;
-    if (tile == 3 && k32 && !getenv("DVSOF_GCONV_NO_K64")) {
+    if (tile == 3 && k32) {
         const long long blocks = ((P.M + 63) / 64) * ((P.N + 63) / 64) * P.nph;
         k64 = blocks <= 256;
         for (int s = 0; s < P.nsrc; ++s)
@@ -649,7 +646,7 @@ int gconv2_launch(const GConvParams &P0, int tile, hipStream_t st)
         else nvec += taps * (P.src[s].C / unit / (BK * ksub));
     }
     if (dbg & 2) nvec = nvec > 1 ? 1 : nvec;
-    if (nflat > 0 || getenv("DVSOF_NO_PH_EXACT")) P.ph_exact = 0;
+    if (nflat > 0) P.ph_exact = 0;
     // Winograd component GEMMs (winograd.hip): 64 x 64, K depth 16 (measured best of the
     // tiles / depths, tools/wino_sweep.sh), under their own kernel name
     if (P.src_ph_stride != 0 && tile == 3 && !k32 && nflat == 0) {
@@ -662,23 +659,16 @@ int gconv2_launch(const GConvParams &P0, int tile, hipStream_t st)
                        : launch2<2, 2, 2, 1, 1, 4>(P, nflat, nvec, st);  // 128 x 64
     case 3: {
         // few workgroups per CU: 8-wave form (two waves per SIMD from one workgroup)
-        static const bool no8 = getenv("DVSOF_GCONV_NO_KSPLIT") != nullptr;
         const long long blocks = ((P.M + 63) / 64) * ((P.N + 63) / 64) * P.nph;
+        // bf16 twins, ring depth 4: 4 matrix instructions per wave and stage -- the loop is
+        // bound by the latency of the LDS-DMA stream, i.e. by the bytes in flight
+        // ((NS - 1) stages of 32 KiB), not by the matrix pipe as in f32
+        if (k64 && P.mfma_bf16 == 3) return launch2x<2, 2, 1, 1, 4, 4, 2, 3>(P, nflat, nvec, st);
         // ring depth 2 (64 KiB): a deeper ring is no faster stand-alone and its LDS
         // footprint keeps the second stream's workgroups off the CU
-        if (k64 && !no8 && P.mfma_bf16 == 3) {
-            // bf16 twins: 4 matrix instructions per wave and stage -- the loop is bound
-            // by the latency of the LDS-DMA stream, i.e. by the bytes in flight
-            // ((NS - 1) stages of 32 KiB), not by the matrix pipe as in f32
-            static const int ns3 = getenv("DVSOF_GCONV_K64_NS") ? atoi(getenv("DVSOF_GCONV_K64_NS")) : 4;
-            if (ns3 == 4) return launch2x<2, 2, 1, 1, 4, 4, 2, 3>(P, nflat, nvec, st);
-            if (ns3 == 3) return launch2x<2, 2, 1, 1, 4, 3, 2, 3>(P, nflat, nvec, st);
-        }
-        if (k64 && !no8) return launch2<2, 2, 1, 1, 4, 2, 2>(P, nflat, nvec, st);
-        if (k64) { /* 4-wave fallback keeps K32 counting */ return DVSOF_EINVAL; }
+        if (k64) return launch2<2, 2, 1, 1, 4, 2, 2>(P, nflat, nvec, st);
         // (<= 2 workgroups per CU: measured +3 % on the 512-workgroup decoder layers over the 4-wave form)
-        static const long long ks_blocks = getenv("DVSOF_GCONV_KSPLIT_BLOCKS") ? atoll(getenv("DVSOF_GCONV_KSPLIT_BLOCKS")) : 512;
-        if (k32 && !no8 && nflat == 0 && blocks <= ks_blocks)
+        if (k32 && nflat == 0 && blocks <= 512)
             return launch2<2, 2, 1, 1, 2, 4, 2>(P, nflat, nvec, st);
         return k32 ? launch2<2, 2, 1, 1, 2, 4>(P, nflat, nvec, st)
                    : launch2<2, 2, 1, 1, 1, 4>(P, nflat, nvec, st);  // 64 x 64

@@ -812,10 +812,8 @@ bool pyramid_plan(int D, int H, int W, float *const *levels, const int *hs, cons
     };
     if (!fits(TH, TW)) return false;
     // big tiles once the small ones would be more than 8 workgroups per CU
-    // (DVSOF_PYR_BIG=0|1 forces the choice)
-    static const int force = getenv("DVSOF_PYR_BIG") ? atoi(getenv("DVSOF_PYR_BIG")) : -1;
     const long long small = (long long)D * ((ws[K - 1] + TW - 1) / TW) * ((hs[K - 1] + TH - 1) / TH);
-    Q.big = (force == 1 || (force < 0 && small >= 2048)) && fits(2 * TH, 2 * TW) ? 1 : 0;
+    Q.big = small >= 2048 && fits(2 * TH, 2 * TW) ? 1 : 0;
     const int th = Q.big ? 2 * TH : TH, tw = Q.big ? 2 * TW : TW;
     Q.tiles_x = (ws[K - 1] + tw - 1) / tw;
     Q.tiles_per_frame = Q.tiles_x * ((hs[K - 1] + th - 1) / th);
@@ -846,9 +844,8 @@ int pyramid_launch(const float *images, int D, int H, int W, float *const *level
         return DVSOF_EINVAL;
     for (int k = 0; k < K; ++k)
         if (!levels[k] || hs[k] < 1 || ws[k] < 1) return DVSOF_EINVAL;
-    static const bool no_fuse = getenv("DVSOF_LOSS_NO_FUSED_PYRAMID") != nullptr;
     PyrParams Q = {};
-    if (D > 0 && !no_fuse && pyramid_plan(D, H, W, levels, hs, ws, K, images, Q)) {
+    if (D > 0 && pyramid_plan(D, H, W, levels, hs, ws, K, images, Q)) {
         Params dummy = {};
         if (Q.big)
             hipLaunchKernelGGL((loss_pyramid_kernel<2 * TH, 2 * TW>), dim3(Q.nblocks + (P ? nb_count : 0)),

@@ -58,7 +58,6 @@ inline bool v2_plan(int64_t n, int B, int C, int H, int W, VoxV2 &P)
     // tile width 2^lx, 64 <= 2^lx <= 2^lp: the widest one whose column padding
     // (TX * 2^lx - W) stays within an eighth of the frame, else the one with
     // the least padding (640 -> 128, 346 -> 128, 256 -> 256, 512 -> 512)
-    static const int lx_env = getenv("DVSOF_VOX_TILE_LOG2X") ? atoi(getenv("DVSOF_VOX_TILE_LOG2X")) : 0;
     int lx = 6, best_pad = 1 << 30;
     for (int c = 6; c <= lp; ++c) {
         const int wd = 1 << c, padded = (W + wd - 1) / wd * wd;
@@ -70,7 +69,6 @@ inline bool v2_plan(int64_t n, int B, int C, int H, int W, VoxV2 &P)
             lx = c;
         }
     }
-    if (lx_env >= 2 && lx_env <= lp) lx = lx_env;
     P.lx = lx;
     const int vtx = 1 << lx, vty = 1 << (lp - lx);
     P.TX = (W + vtx - 1) / vtx;

@@ -728,8 +728,8 @@ int flat_launch(const FlatWG &F, bool mfma, float *part, float *dW, float *dbias
     const int wb = dbias ? 1 : 0;
     if (dbias && (!mfma || (F.ncol % 32) == 0)) return DVSOF_EINVAL;
     if (mfma) {
-        // 8 waves per workgroup, >= PPW pixel pairs per wave, at most 512 partial sums
-        static const int ppw = getenv("DVSOF_FLAT_PPW") ? atoi(getenv("DVSOF_FLAT_PPW")) : 32;
+        // 8 waves per workgroup, >= ppw pixel pairs per wave, at most 512 partial sums
+        constexpr int ppw = 32;
         const long long npair = ((long long)F.M + 1) / 2;
         long long nw = npair / (ppw * 8);
         nw = nw < 1 ? 1 : nw > 512 ? 512 : nw;

@@ -605,10 +605,10 @@ int launch_w2k(const WGradParams &P, int ntiles, hipStream_t st)
     }
     dim3 grid(ntiles, (P.Cout + BMc - 1) / BMc, P.S * P.nph);
     WGradParams Q = P;
-    // XCD-aware tile order: DVSOF_WGRAD_XCD = 0 off (default: on; measured per launch at batch 8:
-    // f32 -1..-3 %, bf16 operands up to -10 %, bf16 twins unchanged)
+    // XCD-aware tile order (measured per launch at batch 8 against the plain order: f32 -1..-3 %,
+    // bf16 operands up to -10 %, bf16 twins unchanged)
     const unsigned total = grid.x * grid.y * grid.z;
-    Q.xcd = (wgrad_xcd_on() && (total & 7u) == 0 && total >= 64) ? 1 : 0;
+    Q.xcd = ((total & 7u) == 0 && total >= 64) ? 1 : 0;
     hipLaunchKernelGGL(KERNEL, grid, dim3(CONV_NT), LDS, st, Q);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;

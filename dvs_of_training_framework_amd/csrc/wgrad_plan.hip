@@ -8,7 +8,6 @@
 // exact f32 (wgrad_patch.hip), the nine-product form of the latter (wgrad_min.hip), and the flat
 // members' VALU / matrix-core kernels (wgrad.hip).
 #include "conv_host.h"
-#include <stdio.h>
 #include <stdlib.h>
 
 namespace {
@@ -47,13 +46,7 @@ int pick_tile_and_splits(const WGradParams &P, int *S_out)
     // (64x64 is 2.6-3 % faster than 64x128 on the three wide decoder layers one at a time,
     // tools/wgrad_sweep.sh, but beside the data-gradient stream the step then alternates
     // between 2340 and 2470 samples/s from run to run; 64x128 gives a steady 2445)
-    static double eff_of[6] = {0, 0.85, 0.80, 0.70, 0.80, 0.65};
-    static bool eff_init = false;
-    if (!eff_init) {   // tuning: DVSOF_WGRAD_EFF="e1,e2,e3,e4,e5"
-        eff_init = true;
-        if (const char *e = getenv("DVSOF_WGRAD_EFF"))
-            sscanf(e, "%lf,%lf,%lf,%lf,%lf", &eff_of[1], &eff_of[2], &eff_of[3], &eff_of[4], &eff_of[5]);
-    }
+    static const double eff_of[6] = {0, 0.85, 0.80, 0.70, 0.80, 0.65};
     int best = -1, bestS = 1;
     double best_cost = 1e300;
     const long long ksteps = (P.M + BK - 1) / BK;
@@ -105,21 +98,18 @@ bool flat_ncol_ok(int ncol)
 // M = 131072 / 45 columns; a tie at M = 131072 / 18 columns; VALU wins below
 bool flat_uses_mfma(const FlatWG &F)
 {
-    static const bool no_mfma = getenv("DVSOF_WGRAD_FLAT_VALU") != nullptr;
-    static const bool force_mfma = getenv("DVSOF_WGRAD_FLAT_MFMA") != nullptr;
     const int ncb = (F.ncol + 31) / 32;
     const bool big = F.M >= 262144 || (ncb == 2 && F.M >= 65536);
-    return !no_mfma && (big || force_mfma) && (F.Cout % 32) == 0 && ncb <= 2 && F.Wo >= 2;
+    return big && (F.Cout % 32) == 0 && ncb <= 2 && F.Wo >= 2;
 }
 
 // ---- the patch-resident kernels ---------------------------------------------------------------
 // Decoder stages: four sub-pixel phases of 2x2 taps over vector members whose channel counts
-// are multiples of 32, 32 | Cout, 16 | width (DVSOF_NO_WGRAD_PATCH=1: the column-tile kernel).
+// are multiples of 32, 32 | Cout, 16 | width (otherwise: the column-tile kernel).
 // The shape alone: what sizing mode plans for, whether or not the twins are bound yet.
 bool patch_shape_ok(const WGradParams &P)
 {
-    static const bool off = getenv("DVSOF_NO_WGRAD_PATCH") != nullptr;
-    if (off || P.nph != 4 || P.ks != 2 || P.stride != 1 || P.up != UP_NONE) return false;
+    if (P.nph != 4 || P.ks != 2 || P.stride != 1 || P.up != UP_NONE) return false;
     if (P.ph_pad != 1 || P.pad != 1 || P.src_ph_stride != 0) return false;
     if ((P.Cout & 31) || (P.Wo % 16) || (P.Ho & 1) || P.Ho != P.Hv || P.Wo != P.Wv) return false;
     // flat members (the 2-channel flow of a decoder stage) are not this kernel's: their
@@ -133,12 +123,8 @@ bool patch_shape_ok(const WGradParams &P)
     return nvec >= 1;
 }
 
-// exact-f32 operand mode: wgrad_patch_f32_kernel (DVSOF_NO_WGRAD_PATCH_F32=1: wgrad2_kernel)
-bool patch_f32(const WGradParams &P)
-{
-    static const bool off = getenv("DVSOF_NO_WGRAD_PATCH_F32") != nullptr;
-    return !off && !P.twins && P.mfma_bf16 == 0;
-}
+// exact-f32 operand mode: wgrad_patch_f32_kernel
+bool patch_f32(const WGradParams &P) { return !P.twins && P.mfma_bf16 == 0; }
 
 // ... and the call's pointers: the twins bound, or 16-byte loads of the f32 tensors
 bool patch_eligible(const WGradParams &P)
@@ -160,43 +146,38 @@ bool patch_eligible(const WGradParams &P)
 }
 
 // The exact-f32 decoder stages take the nine-product kernel when every vector member has a
-// multiple of 64 channels (DVSOF_NO_WGRAD_MIN=1: the sixteen-product patch kernel)
+// multiple of 64 channels (otherwise: the sixteen-product patch kernel)
 bool min9_ok(const WGradParams &P)
 {
-    static const bool off = getenv("DVSOF_NO_WGRAD_MIN") != nullptr;
-    if (off || !patch_f32(P)) return false;
+    if (!patch_f32(P)) return false;
     for (int s = 0; s < P.nsrc; ++s)
         if (!P.src[s].flat && (P.src[s].C & 63)) return false;
     return true;
 }
 
 // Bound on the K splits: >= 2 stages per split; a slab is a whole phase-form gradient -- at
-// most ~32 MB of partial sums per layer, and no more than DVSOF_WGRAD_PATCH_MAXS (64) slabs
-// per phase (the fold reads them all)
+// most ~32 MB of partial sums per layer, and no more than 64 slabs per phase (the fold reads
+// them all)
 long long patch_max_splits(const WGradParams &P)
 {
     const long long blocks = (long long)P.B * (P.Hv / 2) * (P.Wv / 16);
     long long maxS = blocks / 2 > 0 ? blocks / 2 : 1;
     const long long slab_bytes = 4LL * P.Cout * 4 * P.Cin_tot * 4;
     long long capS = (32LL << 20) / (slab_bytes > 0 ? slab_bytes : 1);
-    static const int max_env = env_int("DVSOF_WGRAD_PATCH_MAXS", 64);
-    if (capS > max_env) capS = max_env;
+    if (capS > 64) capS = 64;
     if (capS < 1) capS = 1;
     return maxS < capS ? maxS : capS;
 }
 
 // 64 input channels per workgroup halve the gradient planes' re-reads
-// (DVSOF_WGRAD_PATCH_CT = 32 | 64 forces one where every vector member allows it)
 int patch_channel_tile(const WGradParams &P)
 {
-    static const int force = env_int("DVSOF_WGRAD_PATCH_CT", 0);
     long long ct = 0;
     for (int s = 0; s < P.nsrc; ++s) {
         if (P.src[s].flat) continue;
         if (P.src[s].C & 63) return 32;
         ct += P.src[s].C / 64;
     }
-    if (force == 32 || force == 64) return force;
     // exact f32: matrix-bound once the planes are read half as often -- as long as one
     // workgroup per CU remains
     if (patch_f32(P)) return (P.Cout / 32) * ct * patch_max_splits(P) >= 256 ? 64 : 32;
@@ -218,15 +199,12 @@ int patch_splits(const WGradParams &P)
     tiles *= P.Cout / 32;
     long long S;
     if (min9) {
-        static const int target = env_int("DVSOF_WGRAD_MIN_WGS", 256);
-        S = (target + tiles - 1) / (tiles > 0 ? tiles : 1);
+        S = (256 + tiles - 1) / (tiles > 0 ? tiles : 1);
         const long long blocks = (long long)P.B * (P.Hv / 2) * (P.Wv / 16);
         if (S > blocks / 2) S = blocks / 2;
         if (S > 128) S = 128;
     } else {
-        static const int target16 = env_int("DVSOF_WGRAD_PATCH_WGS", 512);
-        static const int target32 = env_int("DVSOF_WGRAD_PATCH_F32_WGS", 512);
-        S = ((patch_f32(P) ? target32 : target16) + tiles - 1) / tiles;
+        S = (512 + tiles - 1) / tiles;
         const long long maxS = patch_max_splits(P);
         if (S > maxS) S = maxS;
     }
@@ -262,12 +240,6 @@ void lay_out(WGradPlan &pl, const WGradParams &P, const FlatWG *flat, int nflat,
 }
 
 }  // namespace
-
-bool wgrad_xcd_on()
-{
-    static const bool on = env_int("DVSOF_WGRAD_XCD", -1) != 0;
-    return on;
-}
 
 int wgrad_enumerate_tiles(WGradParams &P, int cols_per_channel, int width, bool vec, bool flat)
 {
@@ -332,11 +304,10 @@ WGradPlan wgrad_plan(const WGradParams &P0, const FlatWG *flat, int nflat, bool 
     int bm;
     tile_dims(pl.tile, bm, pl.bn);
     // ---- kernels ------------------------------------------------------------------------------
-    static const bool force_v1 = getenv("DVSOF_WGRAD_V1") != nullptr;
     // flat members: kernels of their own when every one of them qualifies
-    bool flat_own = nflat > 0 && !force_v1;
+    bool flat_own = nflat > 0;
     for (int i = 0; i < nflat; ++i) flat_own = flat_own && flat_ncol_ok(flat[i].ncol);
-    const bool v2 = !force_v1 && wgrad2_eligible(P);
+    const bool v2 = wgrad2_eligible(P);
     if (!any_vec) pl.vec = WGV_NONE;
     else if (!v2) pl.vec = WGV_V1;
     // (flat members on the v1 tiles would write phase-form columns into the patch kernels' slabs)

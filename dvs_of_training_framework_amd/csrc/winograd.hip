@@ -572,7 +572,7 @@ inline unsigned nblocks(long long n, int nt) { return (unsigned)((n + nt - 1) / 
 }  // namespace
 
 // Output tile side of the forward / data-gradient evaluation: 4 when the image
-// allows it (DVSOF_WINO_F=2 forces the 2x2 form), 0 = direct kernel.
+// allows it, 0 = direct kernel.
 // The tile count is the row dimension of the component GEMMs and the
 // transformed weights are 4x (1.8x) the raw ones: with few tiles the layer is
 // bound by reading them.  Measured, batch 1 at 16x16 (16 | 64 tiles): whole
@@ -582,10 +582,9 @@ inline unsigned nblocks(long long n, int nt) { return (unsigned)((n + nt - 1) / 
 // form: the 4x4 transforms amplify the product error past its 1e-4 test bound.
 int wino_tile(int B, int H, int W, int mfma)
 {
-    static const int f_env = env_int("DVSOF_WINO_F", 0);
     if ((H & 1) || (W & 1)) return 0;
     const long long t4 = (long long)B * (H / 4) * (W / 4), t2 = (long long)B * (H / 2) * (W / 2);
-    if (f_env != 2 && mfma == 0 && (H % 4) == 0 && (W % 4) == 0 && t4 >= 64) return 4;
+    if (mfma == 0 && (H % 4) == 0 && (W % 4) == 0 && t4 >= 64) return 4;
     return t2 >= 128 ? 2 : 0;
 }
 
@@ -601,8 +600,6 @@ int wino_components(int B, int H, int W, int mfma)
 bool wino_eligible_shape(int nsrc, int layout_nhwc, int C, int N, int B, int H, int W, int ksize,
                          int stride, int pad, int upsample, int mfma)
 {
-    static const bool off = getenv("DVSOF_NO_WINOGRAD") != nullptr;
-    if (off) return false;
     if (nsrc != 1 || !layout_nhwc || upsample || ksize != 3 || stride != 1 || pad != 1) return false;
     if (mfma == 1 || mfma == 3) return false;   // bf16-rounded operands: the transforms amplify the rounding
     if ((C % 64) || (N % 64) || C < 256 || N < 256) return false;
@@ -611,11 +608,10 @@ bool wino_eligible_shape(int nsrc, int layout_nhwc, int C, int N, int B, int H, 
 
 // Can the output transform of a Winograd evaluation at this frame also make the consumer's
 // forms (wino_chain_kernel)?  F(4x4) form, whole image per workgroup: <= 64 tiles per image, a
-// multiple of 4 (whole waves), the staged frame within 64 KB of LDS.  DVSOF_NO_WINO_CHAIN=1: off
+// multiple of 4 (whole waves), the staged frame within 64 KB of LDS.
 bool wino_chain_ok(int B, int H, int W, int N, int mfma)
 {
-    static const bool off = getenv("DVSOF_NO_WINO_CHAIN") != nullptr;
-    if (off || wino_tile(B, H, W, mfma) != 4 || (N % WC_CG)) return false;
+    if (wino_tile(B, H, W, mfma) != 4 || (N % WC_CG)) return false;
     const int tiles = (H / 4) * (W / 4);
     return tiles <= 64 && (tiles % 4) == 0 && (size_t)(H + 2) * (W + 2) * WC_CG * 4 <= 64 * 1024;
 }
@@ -659,8 +655,7 @@ static int wino_launch_f(const GConvParams &P, float *scratch, const WinoChain &
     float *V = ch.v_pre ? const_cast<float *>(ch.v_pre) : scratch, *Mb = scratch + (size_t)NG * G.T * C;
 
     // few tiles: one channel per thread (4x the threads; these launches are latency bound)
-    static const int vw_env = env_int("DVSOF_WINO_VW", 0);
-    const bool scalar = vw_env ? vw_env == 1 : (long long)G.T * (C > N ? C : N) / 4 < 256 * 256;
+    const bool scalar = (long long)G.T * (C > N ? C : N) / 4 < 256 * 256;
     if (ch.v_pre) {
     } else if (scalar)
         hipLaunchKernelGGL((wino_input_kernel<F, NT, 1>), dim3(nblocks((long long)G.T * C, NT)), dim3(NT), 0,
@@ -747,16 +742,15 @@ int wino_launch(const GConvParams &P, float *scratch, size_t scratch_floats, con
 // Output tile side: the tile count is the K dimension of the GEMMs, so the 4x4
 // form (4x fewer tiles, 2.25x more components to write and fold) only pays
 // with enough tiles: measured 57 vs 62 us at 128 tiles (batch 8, 16x16, 512
-// channels).  DVSOF_WINO_WGRAD_F overrides.  0: not available.
+// channels).  DVSOF_WINO_WGRAD_F overrides (tools/wino_sweep.sh).  0: not available.
 int wino_wgrad_tile(int B, int H, int W, int mfma)
 {
     static const int f_env = env_int("DVSOF_WINO_WGRAD_F", 0);
-    static const int min_t4 = env_int("DVSOF_WINO_WGRAD_F4_MIN_TILES", 128);
     const bool ok2 = !(H & 1) && !(W & 1) && (B * (H / 2) * (W / 2)) % BK == 0;
     const bool ok4 = mfma == 0 && !(H & 3) && !(W & 3) && (B * (H / 4) * (W / 4)) % BK == 0;
     if (f_env == 2) return ok2 ? 2 : 0;
     if (f_env == 4) return ok4 ? 4 : ok2 ? 2 : 0;
-    if (ok4 && B * (H / 4) * (W / 4) >= min_t4) return 4;
+    if (ok4 && B * (H / 4) * (W / 4) >= 128) return 4;
     return ok2 ? 2 : ok4 ? 4 : 0;
 }
 
@@ -798,8 +792,7 @@ static int wino_wgrad_f(const GSrc &X, const float *V_in, const float *Z_in, con
     float *bias_part = dU + (size_t)NG * S * N * C;
     const float *V = V_in ? V_in : Vws;   // V_in: the forward pass already transformed this input
 
-    static const int vw_env = env_int("DVSOF_WINO_VW", 0);
-    const bool scalar = vw_env ? vw_env == 1 : (long long)G.T * (C > N ? C : N) / 4 < 256 * 256;
+    const bool scalar = (long long)G.T * (C > N ? C : N) / 4 < 256 * 256;
     if (scalar) {
         if (!V_in)
             hipLaunchKernelGGL((wino_input_kernel<F, NT, 1>), dim3(nblocks((long long)G.T * C, NT)), dim3(NT),

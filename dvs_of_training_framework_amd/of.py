@@ -9,10 +9,7 @@ import torch.nn as nn
 
 from .net import Model
 
-import os
-
 script_dir = osp.dirname(osp.realpath(__file__))
-_GRAPH_SYNC = os.environ.get('DVSOF_GRAPH_SYNC') == '1'
 
 
 class OpticalFlow:
@@ -94,8 +91,6 @@ class OpticalFlow:
             if self._use_graph:
                 def static_columns(n):
                     g = self._graph_slot(B, n, _OUT_DTYPES)
-                    if _GRAPH_SYNC and g.get('done') is not None:
-                        g['done'].synchronize()
                     return g['cap'], g['ev']
                 c = seq.collate_frames(starts, stops, box, buffers=static_columns)
                 g = self._graphs[B]
@@ -116,10 +111,7 @@ class OpticalFlow:
         # ordered on one stream; no host synchronisation is needed.  The graph
         # holds kernels only (the voxeliser's control words clean up after
         # themselves, so there is no memset node; its workspace is the one the
-        # eager warm-up call made).  DVSOF_GRAPH_SYNC=1 restores the round-1
-        # behaviour (wait for the previous replay) as a diagnostic.
-        if _GRAPH_SYNC and g.get('done') is not None:
-            g['done'].synchronize()
+        # eager warm-up call made).
         for k, v in ev.items():
             g['ev'][k][:n].copy_(v)
         g['ev']['x'][n:] = -1
@@ -150,9 +142,6 @@ class OpticalFlow:
                          list(learned_voxel._WORKSPACES.values()),
                          dict(self._net._layout_cache))
         g['graph'].replay()
-        if _GRAPH_SYNC:
-            g['done'] = torch.cuda.Event()
-            g['done'].record()
         return g['flow']
 
     def _collate(self, events, start, stop):

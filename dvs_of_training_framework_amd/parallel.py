@@ -82,8 +82,7 @@ def init_distributed(device_type='cuda'):
         backend = 'nccl' if device_type == 'cuda' else 'gloo'
         if device_type == 'cuda':
             torch.cuda.set_device(local)
-            if os.environ.get('DVSOF_NO_STREAM_CLAIM') != '1':
-                claim_streams(torch.device('cuda', local))     # before the communicators' streams
+            claim_streams(torch.device('cuda', local))     # before the communicators' streams
             with _stdout_to_stderr():
                 dist.init_process_group(backend, rank=rank, world_size=world,
                                         device_id=torch.device('cuda', local))
@@ -183,23 +182,14 @@ class GradReducer:
                 'elements': e.value}
 
     def exchange_stream(self, device):
-        """Stream of the collectives.  DVSOF_EXCHANGE_ON_WGRAD_STREAM=1: the
-        backward's second stream (no third stream, the collectives queue up
-        between the weight-gradient kernels) -- a measurement switch."""
-        if os.environ.get('DVSOF_EXCHANGE_ON_WGRAD_STREAM') == '1':
-            from .predictor import _SIDE_STREAMS
-            key = torch.device(device).index
-            key = torch.cuda.current_device() if key is None else key
-            if key in _SIDE_STREAMS:
-                return _SIDE_STREAMS[key]
-        return self._side_stream(device)
+        """Stream of the collectives: a third stream, claimed with the others (claim_streams)."""
+        if self._side is None:
+            self._side = claim_streams(device)[1]
+        return self._side
 
     def update_stream(self, device):
         """Stream of the update lane (dvsof_exec_set_update_stream), claimed with the others;
-        None: the updates stay on the exchange stream (DVSOF_UPDATE_ON_XSTREAM=1, or the streams
-        were not claimed)."""
-        if os.environ.get('DVSOF_UPDATE_ON_XSTREAM') == '1':
-            return None
+        None: the streams were not claimed, the updates stay on the exchange stream."""
         key = torch.device(device).index
         key = torch.cuda.current_device() if key is None else key
         return _UPDATE_STREAMS.get(key)
@@ -233,14 +223,6 @@ class GradReducer:
             _lib.lib().dvsof_comm_destroy(self._comm)
             self._comm = None
 
-    def _side_stream(self, device):
-        if self._side is None:
-            if os.environ.get('DVSOF_NO_STREAM_CLAIM') == '1':
-                self._side = torch.cuda.Stream(device=device)
-            else:
-                self._side = claim_streams(device)[1]
-        return self._side
-
     def active(self):
         """Does bucket_ready exchange anything?"""
         return self.enabled and (self.world > 1 or self.loopback is not None or
@@ -261,25 +243,17 @@ class GradReducer:
             _lib.check(_lib.lib().dvsof_exec_mark(
                 1, self._marked, flat.data_ptr(), flat.numel(), _lib.stream()),
                 'dvsof_exec_mark')
-            if after is not None and os.environ.get('DVSOF_UPDATE_ON_LANE') == '1':
-                # (before round 4's second half: this bucket's update behind a WAIT mark on the
-                # CURRENT stream -- the executor makes that lane wait for the collective there:
-                # 3.18 against 2.65 ms per step under the loopback exchange, the lane stalls)
-                _lib.check(_lib.lib().dvsof_exec_mark(
-                    3, self._marked, flat.data_ptr(), flat.numel(), _lib.stream()),
-                    'dvsof_exec_mark')
-                self._marked += 1
-                after()
-                return
             if after is not None:
                 # optim.fuse_into_backward: this bucket's update is captured ON THE EXCHANGE
                 # STREAM, behind a WAIT mark there (the branch joins the capture again in
                 # wait()).  The executor recognises kernels that follow nothing but WAIT marks
                 # and launches them on the exchange stream behind the collective: the update
                 # overlaps the rest of the backward and no compute lane waits for anything
-                # before the JOIN mark (csrc/exec.hip, XNode.xlane).
+                # before the JOIN mark (csrc/exec.hip, XNode.xlane).  (The update behind a WAIT
+                # mark on the CURRENT stream instead made that lane wait for the collective: 3.18
+                # against 2.65 ms per step under the loopback exchange, as measured then.)
                 cur = torch.cuda.current_stream(flat.device)
-                side = self._side_stream(flat.device)
+                side = self.exchange_stream(flat.device)
                 ev = torch.cuda.Event()
                 ev.record(cur)
                 with torch.cuda.stream(side):
@@ -296,7 +270,7 @@ class GradReducer:
             from . import _lib
             ready = self._ready_event(flat)
             ready.record()
-            side = self._side_stream(flat.device)
+            side = self.exchange_stream(flat.device)
             with torch.cuda.stream(side):
                 side.wait_event(ready)
                 _lib.check(_lib.lib().dvsof_allreduce_bucket(
@@ -310,7 +284,7 @@ class GradReducer:
         elif flat.is_cuda:
             ready = self._ready_event(flat)
             ready.record()
-            side = self._side_stream(flat.device)
+            side = self.exchange_stream(flat.device)
             with torch.cuda.stream(side):
                 side.wait_event(ready)
                 # (one rank: SUM is the same average, and RCCL then launches

@@ -27,7 +27,6 @@ from torch import nn
 from . import conv as C
 
 _SIDE_STREAMS = {}      # device index -> the second backward stream
-_EXTRA_STREAMS = {}     # device index -> further streams (DVSOF_WGRAD_STREAMS > 1)
 
 ENC_CH = (64, 128, 256, 512)
 DEC_CH = (256, 128, 64, 32)
@@ -156,9 +155,8 @@ class _PredictorFn(torch.autograd.Function):
 
         # Decoder stages whose third member is the previous stage's flow run, when
         # training, on cat[x, skip] with that member folded into weight space
-        # (csrc/flowfold.hip; DVSOF_FLOW_FOLD=0: the member as a member)
-        fold_pre = want_grad and os.environ.get('DVSOF_FLOW_FOLD', '1') != '0' and \
-            len(module._extra_streams(dev)) == 0
+        # (csrc/flowfold.hip); in inference the member stays a member
+        fold_pre = want_grad
         if side is not None or fold_pre:
             h16, w16 = H // 16, W // 16
             specs = [(4 + 2 * i + j, [(x0, 512, C.NHWC)], h16, w16, 512,
@@ -198,7 +196,7 @@ class _PredictorFn(torch.autograd.Function):
         # (Measured and not kept: the data-gradient weight forms issued late, beside the
         # decoder's kernels instead of layer by layer beside the encoder / residual layers:
         # 2.522-2.530 ms wherever they run -- the step is bound by total work, and the forms
-        # cost 63 us of it: 2.451 ms with stale forms, DVSOF_STALE_FORMS=1.)
+        # cost 63 us of it: 2.451 ms with the forms of the first step reused, which is wrong.)
 
         def run(srcs, h, w, cout, wgt, bias, stride=1, up=False,
                 residual=None, chained=(False, False)):
@@ -358,10 +356,8 @@ class _PredictorFn(torch.autograd.Function):
             main.wait_event(ctx.dg_ready)
         keep = []
 
-        # DVSOF_WGRAD_STREAMS=n (default 1): weight gradients dealt round-robin
-        # to n side streams (they are independent of each other)
-        sides = [side] + (ctx.module._extra_streams(dev) if side is not None else [])
-        turn = [0]
+        # (One side stream: the weight gradients dealt round-robin to two or three of them
+        # measured no gain.)
 
         # Flow member folded into weight space (csrc/flowfold.hip): a stage's
         # weight gradient leaves its flow columns to dvsof_flow_fold_grads, which
@@ -387,12 +383,10 @@ class _PredictorFn(torch.autograd.Function):
             if side is None:
                 body()
                 return
-            s_ = sides[turn[0] % len(sides)]
-            turn[0] += 1
             ready = torch.cuda.Event()
             ready.record(main)
-            s_.wait_event(ready)
-            with torch.cuda.stream(s_):
+            side.wait_event(ready)
+            with torch.cuda.stream(side):
                 body()
             keep.extend((gz, gz16))
 
@@ -414,14 +408,11 @@ class _PredictorFn(torch.autograd.Function):
         g_skip = [None] * 4  # gradient into e[k] from the decoder
         g_r = g_r16 = None
         head_in_dgrad = False
-        head_part = g_x16 = g_in16 = None
-        fuse_heads = os.environ.get('DVSOF_NO_HEAD_FUSE', '0') == '0'
-        fuse_general = os.environ.get('DVSOF_HEAD_FUSE_GENERAL', '0') == '1'
-        # (the head's weight gradient from per-block partials of the same epilogue instead of
-        # its own pass over the tensor on the other stream, dvsof_grad_dst_t.head_part: measured
-        # 2.58 against 2.53 ms wherever the encoder's weight gradients go -- the shuffles, the
-        # extra barrier and the partial stores sit on the data-gradient chain; DVSOF_HEAD_PARTS=1)
-        head_parts = os.environ.get('DVSOF_HEAD_PARTS', '0') == '1'
+        g_x16 = g_in16 = None
+        # (The head's weight gradient is its own pass over the tensor on the other stream.  From
+        # per-block partials of the data gradient's epilogue instead, dvsof_grad_dst_t.head_part:
+        # measured 2.58 against 2.53 ms wherever the encoder's weight gradients go -- the
+        # shuffles, the extra barrier and the partial stores sit on the data-gradient chain.)
         for i in (3, 2, 1, 0):
             lay = dec_l[i]
             d = lay['desc']
@@ -435,14 +426,9 @@ class _PredictorFn(torch.autograd.Function):
                 # head's own weight / bias gradient is left, off the critical chain
                 gz, gz16 = g_x, g_x16
 
-                if head_part is not None:
-                    # ... of which that epilogue left per-block partial sums
-                    def head_w(part=head_part, gw=grads[pfw], gb=grads[pfb], c=d.Cout):
-                        C.head_reduce(part, c, gw, gb)
-                else:
-                    def head_w(y=y, wf=params[pfw], g=g_f, gw=grads[pfw], gb=grads[pfb],
-                               h=h, w=w, c=d.Cout):
-                        C.head_bwd(y, wf, g, None, None, act, None, gw, gb, B, h, w, c)
+                def head_w(y=y, wf=params[pfw], g=g_f, gw=grads[pfw], gb=grads[pfb],
+                           h=h, w=w, c=d.Cout):
+                    C.head_bwd(y, wf, g, None, None, act, None, gw, gb, B, h, w, c)
             else:
                 gz, gz16 = new(y), tw(y)
                 C.head_bwd(y, params[pfw], g_f, g_x, asrc(lay), act, gz,
@@ -466,11 +452,12 @@ class _PredictorFn(torch.autograd.Function):
                 # path through the flow head, which then sees the loss gradient only
                 g_fprev = gflows[i - 1]
                 wf_prev = params[po_dec + 4 * (i - 1) + 2]
-                # (the general kernels fold a head too, conv_epilogue: bf16s 5 146 against 5 234
-                # samples/s without, bf16 3 941 / 3 912, bf16x3 the same -- their epilogue cannot
-                # start its loads ahead of the K loop's end; DVSOF_HEAD_FUSE_GENERAL=1)
-                if (fuse_heads and C.dgrad_fuses_head(fold['desc'])
-                        and (fuse_general or C.dgrad_head_rows(fold['desc']) > 0)
+                # (only the nine-product kernels, dgrad_head_rows > 0.  The general kernels can
+                # fold a head too, conv_epilogue: bf16s 5 146 against 5 234 samples/s without,
+                # bf16 3 941 / 3 912, bf16x3 the same -- their epilogue cannot start its loads
+                # ahead of the K loop's end)
+                if (C.dgrad_fuses_head(fold['desc'])
+                        and C.dgrad_head_rows(fold['desc']) > 0
                         and wf_prev.data_ptr() % 16 == 0):
                     # ... and the head below goes into this data gradient's epilogue
                     # (dvsof_grad_dst_t.head_w): g_in leaves as dec[i-1]'s dz
@@ -478,11 +465,6 @@ class _PredictorFn(torch.autograd.Function):
                     g_in16 = tw(g_in)       # (twins mode: the data gradient below reads its bf16 copy)
                     dsts[0].update(head_w=wf_prev, head_gflow=g_fprev,
                                    actsrc=asrc(dec_l[i - 1]), p16=g_in16)
-                    head_part = C.dgrad_head_part(fold['desc'], dec_l[i - 1]['desc'].Cout, dev) \
-                        if head_parts else None
-                    if head_part is not None:
-                        dsts[0].update(head_x=dec_l[i - 1]['y'], head_part=head_part)
-                        keep.append(head_part)
                 C.conv_dgrad(fold['desc'], fold['w_dg'], gz, dsts, act,
                              weight16=fold['w_dg16'], gout16=gz16)
             else:
@@ -551,7 +533,7 @@ class _PredictorFn(torch.autograd.Function):
         # bf16 modes and every data-parallel rank 2)
         red_ = getattr(ctx.module, 'reducer', None)
         alone_ = red_ is None or not red_.active()   # (under the exchange marks 2 again: 2.72 vs 2.84 ms)
-        n_side = int(os.environ.get('DVSOF_ENC_SIDE_FROM', '3' if ctx.module.mfma == 0 and alone_ else '2'))
+        n_side = 3 if ctx.module.mfma == 0 and alone_ else 2
         g_grid = None
         for i in (3, 2, 1, 0):
             lay = enc_l[i]
@@ -583,8 +565,7 @@ class _PredictorFn(torch.autograd.Function):
                 C.conv_wgrad(desc, g, gw, gb, g16)
                 finish(unit)
         if side is not None:
-            for s_ in sides:
-                main.wait_stream(s_)
+            main.wait_stream(side)
         del keep
         ctx.L = None
         return (g_grid,) + (None,) * (2 + len(params))
@@ -664,7 +645,7 @@ class Predictor(nn.Module):
         work of the coming forward (weight twins, prepared forms) depends on the
         optimizer's update only, and may start HERE instead of behind the
         voxeliser (78 us of small kernels off the forward's lane at batch 8)."""
-        if os.environ.get('DVSOF_NO_STEP_BEGIN') or self._wgrad_stream(dev) is None:
+        if self._wgrad_stream(dev) is None:
             return
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
@@ -673,15 +654,6 @@ class Predictor(nn.Module):
     def _take_step_begin(self):
         ev, self._step_begin = getattr(self, '_step_begin', None), None
         return ev
-
-    def _extra_streams(self, dev):
-        n = int(os.environ.get('DVSOF_WGRAD_STREAMS', '1')) - 1
-        key = torch.device(dev).index if torch.device(dev).index is not None \
-            else torch.cuda.current_device()
-        have = _EXTRA_STREAMS.setdefault(key, [])
-        while len(have) < n:
-            have.append(torch.cuda.Stream(device=dev))
-        return have[:max(n, 0)]
 
     def _buckets(self, params):
         dev = params[0].device

@@ -810,7 +810,7 @@ enum {
     DVSOF_KERNEL_FWD_PATCH = 9,     /* csrc/fwd_patch.hip (f32 or twins) */
     DVSOF_KERNEL_DGRAD_MIN0 = 10,   /* csrc/dgrad_min.hip <0>: resident weights, persistent */
     DVSOF_KERNEL_DGRAD_MIN1 = 11,   /* <1>: one item per workgroup */
-    DVSOF_KERNEL_DGRAD_MIN2 = 12,   /* <2>: two items per workgroup */
+    DVSOF_KERNEL_DGRAD_MIN2 = 12,   /* <2>: two items per workgroup (a loss inside the step: never reported now) */
     DVSOF_KERNEL_WGRAD_PATCH = 13,  /* csrc/wgrad_patch.hip */
     DVSOF_KERNEL_WGRAD_MIN = 14,    /* csrc/wgrad_min.hip */
     DVSOF_KERNEL_TRANSPOSED = 15,   /* transposed layer (upsample 2): output-parity phases */
@@ -1107,7 +1107,7 @@ int dvsof_comm_create_loopback(void **comm, int world_size, int delay_us);
  *                       dvsof_exec_launch are real steps under each plan in
  *                       turn, timed on the device (the host waits for the
  *                       previous step before each of them); the fastest plan
- *                       stays.  DVSOF_EXEC_PLAN=paths|list|chain fixes one.
+ *                       stays.
  *                       It IS a step: same kernels, same results as
  *                       dvsof_exec_launch -- under every plan
  *   dvsof_exec_plan     name of the plan in effect; settled = 0 while plans
