@@ -24,7 +24,11 @@ batch signature (batch size, frame size, event capacity) and replays it:
     rate and what the step count decides -- Adam's bias corrections; RAdam's
     step size and rectification, Ranger's Lookahead synchronisation (the
     optimizer's ``advance`` refreshes a 4-float row per parameter group before
-    each replay), so LambdaLR keeps working.
+    each replay), so LambdaLR keeps working;
+  * a step guard (``optim.set_guard``: gradient clipping, skip of a step with
+    non-finite gradients) is two more kernel nodes in front of the updates of
+    the roles that close a step, behind the gradient exchange; the updates
+    read its decision from a persistent 32-byte record.
 
 ROLES -- gradient accumulation (utils/options.py:318-325: ``bs // mbs``
 micro-batches per optimizer step, utils/training.py:156-167).  A micro-batch
@@ -367,6 +371,11 @@ class CapturedTrainStep:
             # the recording then finds it large enough and takes its address
             layer.resident.reserve(self.static['events']['x'].numel())
             self._keep.append(layer.resident.tensors())
+        if getattr(optimizer, '_guard', None) is not None:
+            # the step guard (optim.set_guard): its record, its partials workspace -- sized by
+            # the eager step this role's constructor ran over the same parameters; it refuses to
+            # grow inside the recording -- and its concatenated tables
+            self._keep.append(optimizer.guard_tensors())
         optimizer.begin_capture(dev)
         self.graph = torch.cuda.CUDAGraph(keep_graph=True) if executor \
             else torch.cuda.CUDAGraph()

@@ -5,8 +5,15 @@
 keeps torch's state-dict schema (step, exp_avg, exp_avg_sq, max_exp_avg_sq)
 so checkpoints interchange with the reference's (utils/serializer.py:60-110).
 One kernel launch per parameter group updates every tensor of the group.
+
+``set_guard`` puts a step under the STEP GUARD (docs/STEP_GUARD_SPEC.md): the
+global gradient norm and the count of non-finite gradient elements are reduced
+on the device at the head of ``step()``, the update kernels read the decision
+from a 32-byte device record -- clip by a scale, or write nothing at all --
+and the host never waits for it.
 """
 import ctypes
+import struct
 
 import torch
 
@@ -28,6 +35,17 @@ _lib.register('dvsof_radam_step_dyn', _i, [_vp, _vp, _vp, _i, _vp, _f, _f, _f,
                                            _f, _f, _vp])
 _lib.register('dvsof_grad_centralize', _i, [_vp, _i, _i, _vp])
 _lib.register('dvsof_grad_centralize_multi', _i, [_vp, _i, _vp])
+_lib.register('dvsof_grad_guard_record_bytes', _i, [])
+_lib.register('dvsof_grad_guard_partial_bytes', _i, [])
+_lib.register('dvsof_grad_guard', _i, [_vp, _i, _vp, _vp, _i, _vp, ctypes.c_size_t,
+                                       ctypes.c_double, _i, _vp, _vp])
+# the guarded twins: the arguments of the unguarded entry point, the guard record, the stream
+for _name in ('dvsof_adamw_step', 'dvsof_adamw_step_dyn', 'dvsof_radam_step',
+              'dvsof_radam_step_dyn'):
+    _res, _args = _lib._SIGNATURES[_name]
+    _lib.register(_name + '_guarded', _res, _args[:-1] + [_vp, _args[-1]])
+GUARD_FIELDS = ('scale', 'skip', 'norm', 'bad', 'skipped', 'clipped', 'consecutive')
+_GUARD_STRUCT = '<fIdIIII'      # the record of include/dvsof.h, 32 bytes
 from . import snapshot as _snapshot  # noqa: E402,F401  (registers dvsof_snapshot_*: the state's way out)
 
 
@@ -41,6 +59,8 @@ class _FusedBase(torch.optim.Optimizer):
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._tables = {}
+        self._guard = None      # set_guard: (max_norm, skip_nonfinite, record, [partials])
+        self._guard_tables = None
 
     def _init_state(self, p, st):
         for name in self.STATE:
@@ -116,7 +136,7 @@ class _FusedBase(torch.optim.Optimizer):
     def _launch(self, group, tables, step, plist):
         raise NotImplementedError
 
-    def _step_params(self, key, group, plist):
+    def _step_params(self, key, group, plist, tables=None):
         _lib.require_cuda(*plist)
         for p in plist:
             assert _dense(p) and not p.grad.is_sparse
@@ -128,7 +148,9 @@ class _FusedBase(torch.optim.Optimizer):
                 st['step'] = int(st['step']) + 1
             steps.add(st['step'])
         assert len(steps) == 1, 'tensors of one group step together'
-        self._launch(group, self._table(key, plist, group), max(steps.pop(), 1), plist)
+        if tables is None:
+            tables = self._table(key, plist, group)
+        self._launch(group, tables, max(steps.pop(), 1), plist)
 
     # ---- a step captured in a hipGraph (capture.CapturedTrainStep) ---------
     def _dyn_row(self, group, step, out4):
@@ -170,6 +192,117 @@ class _FusedBase(torch.optim.Optimizer):
         """Back to eager steps (the table stays: a graph may still use it)."""
         self._use_dyn = False
 
+    # ---- the step guard (docs/STEP_GUARD_SPEC.md) ---------------------------
+    def set_guard(self, max_norm=None, skip_nonfinite=True):
+        """Clip the global gradient norm of every step to ``max_norm`` (None:
+        no clipping; ``torch.nn.utils.clip_grad_norm_`` semantics over ALL
+        parameter groups) and, with ``skip_nonfinite``, write nothing in a
+        step whose gradients hold a NaN or an Inf.  Decided on the device:
+        ``step()`` enqueues the statistic and updates that obey it, and never
+        waits.  Step counters, bias corrections, RAdam's rectification and the
+        learning-rate schedule therefore advance on a skipped step like on any
+        other; a Lookahead synchronisation that falls on a skipped step is
+        missed and happens at the next multiple of ``k``.
+
+        ``set_guard(None, False)`` removes the guard.  The record (and its
+        counters) is made once and survives a change of the settings; it is
+        not part of ``state_dict()``: counters are per run."""
+        if max_norm is None and not skip_nonfinite:
+            self._guard = None
+            return
+        if hasattr(self, 'fused_active'):
+            raise ValueError('set_guard cannot be combined with fuse_into_backward: a bucket '
+                             'updated during the backward cannot wait for the global gradient '
+                             'norm of the step')
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise ValueError(f'max_norm must be positive (or None), got {max_norm}')
+        max_norm = 0.0 if max_norm is None else float(max_norm)     # 0: the kernels do not clip
+        dev = next(p.device for g in self.param_groups for p in g['params'])
+        if self._guard is None:
+            record = torch.zeros(struct.calcsize(_GUARD_STRUCT) // 8, dtype=torch.int64,
+                                 device=dev)
+            partials = [torch.zeros(0, dtype=torch.int64, device=dev)]
+        else:
+            record, partials = self._guard[2:]
+        self._guard = (max_norm, bool(skip_nonfinite), record, partials)
+
+    def guard_state(self):
+        """The guard record as a dict (GUARD_FIELDS), by ONE 32-byte copy
+        from the device (which waits for the work enqueued so far)."""
+        assert self._guard is not None, 'no guard is set'
+        raw = self._guard[2].cpu().numpy().tobytes()
+        out = dict(zip(GUARD_FIELDS, struct.unpack(_GUARD_STRUCT, raw)))
+        out['skip'] = bool(out['skip'])
+        return out
+
+    def guard_tensors(self):
+        """Device tensors the guard's kernels point at (a captured step keeps
+        them alive); empty without a guard."""
+        if self._guard is None:
+            return []
+        keep = [self._guard[2], self._guard[3][0]]
+        if self._guard_tables is not None:
+            keep += list(self._guard_tables[1:4])
+        return keep
+
+    def _guard_reserve(self, num_chunks):
+        """The partials workspace, grown EAGERLY: a recording takes its
+        address, so it must not grow inside one."""
+        partials = self._guard[3]
+        need = num_chunks * _lib.lib().dvsof_grad_guard_partial_bytes()
+        if partials[0].numel() * 8 < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('the step guard\'s workspace would have to grow inside a '
+                                   'recording: run one eager step over these parameters first')
+            partials[0] = torch.zeros(max(need // 8, 2 * partials[0].numel()),
+                                      dtype=torch.int64, device=partials[0].device)
+        return partials[0]
+
+    def _enqueue_guard(self, work):
+        """The statistic over ALL groups that step now: their tables
+        concatenated (tensor ids offset), one norm, one decision.  Reads the
+        raw gradients: before any centralisation."""
+        tables = [self._table(key, plist, group) for key, group, plist in work]
+        key = [t[0] for t in tables]    # (the tensors themselves: an address may be reused)
+        cached = self._guard_tables
+        if cached is None or len(cached[0]) != len(key) or \
+                any(a is not b for a, b in zip(cached[0], key)):
+            if len(tables) == 1:
+                t_ptrs, t_sizes, t_chunks, n = tables[0][:4]
+            elif tables:
+                chunks, first = [], 0
+                for t in tables:
+                    c = t[2].reshape(-1, 2).clone()
+                    c[:, 0] += first
+                    chunks.append(c)
+                    first += t[1].numel()
+                t_ptrs = torch.cat([t[0] for t in tables])
+                t_sizes = torch.cat([t[1] for t in tables])
+                t_chunks = torch.cat(chunks)
+                n = sum(t[3] for t in tables)
+            else:
+                t_ptrs = t_sizes = t_chunks = None
+                n = 0
+            cached = self._guard_tables = (key, t_ptrs, t_sizes, t_chunks, n)
+        _, t_ptrs, t_sizes, t_chunks, n = cached
+        max_norm, skip_nonfinite, record, _ = self._guard
+        partials = self._guard_reserve(n)
+        _lib.check(_lib.lib().dvsof_grad_guard(
+            t_ptrs.data_ptr() + 8 if n else None, 5,
+            t_sizes.data_ptr() if n else None, t_chunks.data_ptr() if n else None, n,
+            partials.data_ptr() if n else None, partials.numel() * 8, max_norm,
+            1 if skip_nonfinite else 0, record.data_ptr(), _lib.stream()),
+            'dvsof_grad_guard')
+        return tables
+
+    def _guard_args(self, name):
+        """(entry point, its name, trailing arguments) of an update launch:
+        the guarded twin and the record when a guard is set."""
+        if self._guard is None:
+            return getattr(_lib.lib(), name), name, (_lib.stream(),)
+        name += '_guarded'
+        return getattr(_lib.lib(), name), name, (self._guard[2].data_ptr(), _lib.stream())
+
     # ---- update fused into the backward ------------------------------------
     def fuse_into_backward(self, predictor, flush_at=None):
         """Update the gradient buckets of ``predictor`` as soon as their
@@ -184,6 +317,10 @@ class _FusedBase(torch.optim.Optimizer):
         the decoder and residual parameters (82 % of the bytes) when the last
         residual weight gradient is done, beside the encoder's backward, and
         leaves the encoder buckets to ``step()``."""
+        if self._guard is not None:
+            raise ValueError('fuse_into_backward cannot be combined with set_guard: a bucket '
+                             'updated during the backward cannot wait for the global gradient '
+                             'norm of the step')
         self.fused_active = True
         self._flush_at = None if flush_at is None else set(flush_at)
         self._pending = []
@@ -219,12 +356,17 @@ class _FusedBase(torch.optim.Optimizer):
         done = getattr(self, '_done', None)
         if getattr(self, '_pending', None):
             self._pending = []          # never flushed this step: step() takes them
+        work = []
         for gi, group in enumerate(self.param_groups):
             plist = [p for p in group['params'] if p.grad is not None and
                      not (done and id(p) in done)]
-            if not plist:
-                continue
-            self._step_params(gi if not done else (gi, 'rest'), group, plist)
+            if plist:
+                work.append((gi if not done else (gi, 'rest'), group, plist))
+        tables = [None] * len(work)
+        if self._guard is not None:
+            tables = self._enqueue_guard(work)  # one decision for all groups; the updates obey it
+        for (key, group, plist), t in zip(work, tables):
+            self._step_params(key, group, plist, t)
         if done:
             done.clear()
         return loss
@@ -243,18 +385,19 @@ class FusedAdamW(_FusedBase):
         t_ptrs, t_sizes, t_chunks, n = tables[:4]
         b1, b2 = group['betas']
         if getattr(self, '_use_dyn', False):     # captured step: lr and bias corrections from the device table
-            _lib.check(_lib.lib().dvsof_adamw_step_dyn(
+            fn, name, tail = self._guard_args('dvsof_adamw_step_dyn')
+            _lib.check(fn(
                 t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
                 self._dyn_ptr(group), float(b1), float(b2),
                 float(group['eps']), float(group['weight_decay']),
-                1 if group['amsgrad'] else 0, _lib.stream()),
-                'dvsof_adamw_step_dyn')
+                1 if group['amsgrad'] else 0, *tail), name)
             return
-        _lib.check(_lib.lib().dvsof_adamw_step(
+        fn, name, tail = self._guard_args('dvsof_adamw_step')
+        _lib.check(fn(
             t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
             float(group['lr']), float(b1), float(b2), float(group['eps']),
             float(group['weight_decay']), step,
-            1 if group['amsgrad'] else 0, _lib.stream()), 'dvsof_adamw_step')
+            1 if group['amsgrad'] else 0, *tail), name)
 
     def _dyn_row(self, group, step, out4):
         """{lr, lr/bc1, sqrt(bc2), 0}"""
@@ -278,18 +421,19 @@ class _RAdamKind(_FusedBase):
         b1, b2 = group['betas']
         thr, flags, k, alpha = self._consts(group)
         if getattr(self, '_use_dyn', False):     # captured step: lr, step size and the two decisions from the device table
-            _lib.check(_lib.lib().dvsof_radam_step_dyn(
+            fn, name, tail = self._guard_args('dvsof_radam_step_dyn')
+            _lib.check(fn(
                 t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
                 self._dyn_ptr(group), float(b1), float(b2),
                 float(group['eps']), float(group['weight_decay']), alpha,
-                _lib.stream()), 'dvsof_radam_step_dyn')
+                *tail), name)
             return
-        _lib.check(_lib.lib().dvsof_radam_step(
+        fn, name, tail = self._guard_args('dvsof_radam_step')
+        _lib.check(fn(
             t_ptrs.data_ptr(), t_sizes.data_ptr(), t_chunks.data_ptr(), n,
             float(group['lr']), float(b1), float(b2), float(group['eps']),
             float(group['weight_decay']), step, thr, flags,
-            1 if k and step % k == 0 else 0, alpha, _lib.stream()),
-            'dvsof_radam_step')
+            1 if k and step % k == 0 else 0, alpha, *tail), name)
 
     def _dyn_row(self, group, step, out4):
         """{lr, step size (-1: no update), rectified, Lookahead sync now}"""

@@ -172,7 +172,10 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'executor then issues the gradient exchange)')
     parser.add_argument('--optimizer-in-backward', dest='optimizer_in_backward',
                         default='auto', choices=['auto', 'on', 'off'],
-                        help='update a gradient bucket\'s parameters as soon as its '
+                        help='(auto resolves to off, and on is an error, with '
+                             '--clip-grad-norm or --skip-nonfinite-steps: a bucket '
+                             'updated during the backward cannot wait for the global '
+                             'norm)  update a gradient bucket\'s parameters as soon as its '
                              'gradients are final (behind its all-reduce under data '
                              'parallelism) instead of in optimizer.step() '
                              '(optim.fuse_into_backward; same arithmetic).  auto: on '
@@ -182,6 +185,23 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'bandwidth-bound themselves, and under data parallelism '
                              '(the per-bucket waits for the exchange cost more than '
                              'the overlap gives: measured in a 1-rank group)')
+    parser.add_argument('--clip-grad-norm', dest='clip_grad_norm', default=None,
+                        type=float,
+                        help='clip the global gradient norm of every optimizer step to '
+                             'this value (clip_grad_norm_ semantics over all parameter '
+                             'groups; docs/STEP_GUARD_SPEC.md).  With the fused '
+                             'optimizers the norm is reduced and applied on the device, '
+                             'inside the (captured) step; default: off')
+    parser.add_argument('--skip-nonfinite-steps', dest='skip_nonfinite_steps',
+                        action='store_true',
+                        help='an optimizer step whose gradients hold a NaN or an Inf '
+                             'writes nothing: no parameter, no optimizer state (the step '
+                             'count and the schedule advance all the same); default: off')
+    parser.add_argument('--max-skipped-steps', dest='max_skipped_steps', default=32,
+                        type=int,
+                        help='with --skip-nonfinite-steps: end the run once this many '
+                             'optimizer steps IN A ROW were skipped (a policy value, '
+                             'seen at logging steps)')
     parser.add_argument('--device-feeder', dest='device_feeder', action='store_true',
                         help='move batches to the device on a copy stream, one step '
                              'ahead (feed.DeviceFeeder), instead of tensor.to(device) '
@@ -226,6 +246,37 @@ def validate_dataset_args(args):           # utils/options.py:305-309
     args.is_raw = not args.ev_images
     args.shape = (args.height, args.width)
     assert args.prefix_length + args.suffix_length < args.max_sequence_length
+    return args
+
+
+def guard_requested(args):
+    return getattr(args, 'clip_grad_norm', None) is not None or \
+        bool(getattr(args, 'skip_nonfinite_steps', False))
+
+
+def resolve_step_guard(args, parser=None):
+    """--optimizer-in-backward against the step guard: ``auto`` resolves to
+    ``off`` when a guard is requested, an explicit ``on`` is an argparse
+    error (``parser.error``; SystemExit without a parser)."""
+    if not guard_requested(args):
+        return args
+    clip = args.clip_grad_norm
+
+    def fail(message):
+        if parser is not None:
+            parser.error(message)
+        raise SystemExit(message)
+    if clip is not None and not clip > 0:
+        fail(f'--clip-grad-norm must be positive, got {clip}')
+    if getattr(args, 'max_skipped_steps', 32) < 1:
+        fail('--max-skipped-steps must be at least 1')
+    oib = getattr(args, 'optimizer_in_backward', 'auto')
+    if oib == 'on':
+        fail('--optimizer-in-backward on cannot be combined with --clip-grad-norm / '
+             '--skip-nonfinite-steps: a bucket updated during the backward cannot wait '
+             'for the global gradient norm of the step')
+    if oib == 'auto':
+        args.optimizer_in_backward = 'off'
     return args
 
 

@@ -349,3 +349,27 @@ def all_reduce_scalars(t, group=None):
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
         t.div_(dist.get_world_size(group))
     return t
+
+
+def _gather_objects(obj, group=None):
+    out = [None] * dist.get_world_size(group)
+    dist.all_gather_object(out, obj, group=group)
+    return out
+
+
+def check_guard_agreement(record, gather=None, group=None):
+    """Backstop of the step guard under data parallelism
+    (docs/STEP_GUARD_SPEC.md): every rank reduces the same exchanged gradients
+    in the same order, so every rank takes the same decisions; this compares
+    the counters ``(skipped, clipped)`` of the guard record across ranks on
+    the host process group and raises naming both values where they differ.
+    gather: obj -> list of every rank's obj (default: all_gather_object)."""
+    mine = (int(record['skipped']), int(record['clipped']))
+    every = (gather or (lambda o: _gather_objects(o, group)))(mine)
+    for rank, other in enumerate(every):
+        if tuple(other) != tuple(every[0]):
+            raise RuntimeError(
+                'the step guard decided differently on different ranks: (skipped, clipped) = '
+                f'{tuple(every[0])} on rank 0, {tuple(other)} on rank {rank}; the replicas '
+                'have diverged')
+    return mine

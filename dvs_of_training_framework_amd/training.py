@@ -16,7 +16,13 @@ tags are the reference's: ``combined_loss`` (:12-24), ``make_hook_periodic``
                        the data-parallel gradient exchange: buckets are
                        all-reduced on a side stream during backward and joined
                        before ``optimizer.step()``; micro-batches that only
-                       accumulate do not exchange.
+                       accumulate do not exchange;
+  * ``HostGuard``      gradient clipping and the skip of a non-finite step
+                       for an optimizer that has no device-side guard
+                       (``torch.optim`` on the CPU); the fused optimizers
+                       carry their own (optim.set_guard,
+                       docs/STEP_GUARD_SPEC.md).  ``train`` reads either at
+                       logging steps only.
 """
 import torch
 
@@ -243,6 +249,54 @@ class _StepClock:
 CAPTURE_PROTOCOL = ('begin_capture', 'advance', 'end_capture')
 
 
+class HostGuard:
+    """The step guard of docs/STEP_GUARD_SPEC.md for an optimizer without a
+    device-side one: ``torch.nn.utils.clip_grad_norm_`` and a finite check
+    before ``optimizer.step()``, with a host synchronisation per step (fine
+    on the CPU).  ``admit(optimizer)`` -> may the step update?  Counters as in
+    the device record (``state()``)."""
+
+    def __init__(self, max_norm=None, skip_nonfinite=True):
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.record = dict(scale=1.0, skip=False, norm=0.0, bad=0, skipped=0,
+                           clipped=0, consecutive=0)
+
+    def admit(self, optimizer):
+        grads = [p.grad for g in optimizer.param_groups for p in g['params']
+                 if p.grad is not None and p.grad.numel()]
+        r = self.record
+        r['bad'] = int(sum(int((~torch.isfinite(g)).sum()) for g in grads))
+        r['skip'] = bool(r['bad']) and self.skip_nonfinite
+        r['scale'] = 1.0
+        if r['bad']:
+            r['norm'] = float('nan')
+        else:
+            r['norm'] = float(torch.sqrt(sum((g.double() ** 2).sum() for g in grads))) \
+                if grads else 0.0
+            if self.max_norm is not None:
+                r['scale'] = min(1.0, self.max_norm / (r['norm'] + 1e-6))
+                torch.nn.utils.clip_grad_norm_(
+                    [p for g in optimizer.param_groups for p in g['params']],
+                    self.max_norm)
+        r['skipped'] += int(r['skip'])
+        r['clipped'] += int(r['scale'] < 1.0)
+        r['consecutive'] = r['consecutive'] + 1 if r['skip'] else 0
+        return not r['skip']
+
+    def state(self):
+        return dict(self.record)
+
+
+def guard_readout(optimizer, host_guard=None):
+    """The guard record of this run as a dict, or None without a guard: the
+    device record of a fused optimizer (one 32-byte copy, which waits for the
+    device) or the HostGuard's."""
+    if getattr(optimizer, '_guard', None) is not None:
+        return optimizer.guard_state()
+    return host_guard.state() if host_guard is not None else None
+
+
 def capture_refusal(optimizer, is_raw, model=None):
     """Why ``train(capture=True)`` cannot replay its steps (None: it can)."""
     if not all(hasattr(optimizer, m) for m in CAPTURE_PROTOCOL):
@@ -264,7 +318,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           evaluator, weights=[0.5, 1, 1], is_raw=True, accumulation_steps=1,
           timers=None, hooks={}, init_step=0, init_samples_passed=0,
           max_events_per_batch: int = 350000, reducer=None,
-          log_every: int = 1, capture=False):
+          log_every: int = 1, capture=False, guard=None,
+          max_skipped_steps: int = 32, guard_agreement_every: int = 0):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
     batches above ``max_events_per_batch`` events are skipped and not counted,
@@ -285,6 +340,16 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                or a model whose event representation has parameters (unless
                it is resident: net.LearnedVoxelGrid.make_resident) runs the
                eager loop and says so on stderr
+    guard:     HostGuard for an optimizer without a device-side step guard
+               (a fused optimizer carries its own: optim.set_guard).  With
+               either, ``General/gradient norm`` and ``General/skipped steps``
+               are written at logging steps -- the record is read only there,
+               so a step that is not logged never waits for the device -- and
+               the run ends with a RuntimeError once ``max_skipped_steps``
+               steps in a row were skipped
+    guard_agreement_every:  under data parallelism, compare the guard's
+               counters across ranks at logged steps that are multiples of
+               this (the checkpointing interval; 0: never)
     """
     if timers is None:
         on_gpu = torch.device(device).type == 'cuda'
@@ -349,7 +414,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                 if not replayed:        # a captured / replayed step holds the update
                     if reducer is not None:
                         reducer.wait()
-                    optimizer.step()
+                    if guard is None or guard.admit(optimizer):
+                        optimizer.step()
                     optimizer.zero_grad(set_to_none=True)
             scheduler.step()
             with _timed(timers, 'logging'):
@@ -363,6 +429,22 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                     for g, group in enumerate(optimizer.param_groups):
                         logger.add_scalar(f'General/learning rate/{g}',
                                           group['lr'], x)
+                record = guard_readout(optimizer, guard) if wanted else None
+                if record is not None:
+                    if logger is not None:
+                        logger.add_scalar('General/gradient norm', record['norm'], clock.samples)
+                        logger.add_scalar('General/skipped steps', record['skipped'],
+                                          clock.samples)
+                    world = reducer.world if reducer is not None else 1
+                    if world > 1 and guard_agreement_every > 0 and \
+                            clock.step % guard_agreement_every == 0:
+                        from .parallel import check_guard_agreement
+                        check_guard_agreement(record, group=reducer.group)
+                    if record['consecutive'] >= max_skipped_steps:
+                        raise RuntimeError(
+                            f'step {clock.step}: the last {record["consecutive"]} optimizer '
+                            'steps were skipped for non-finite gradients '
+                            f'(--max-skipped-steps {max_skipped_steps})')
                 sums.clear()
             for name, hook in hooks.items():
                 with _timed(timers, name):

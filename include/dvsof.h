@@ -982,6 +982,86 @@ int dvsof_grad_centralize_multi(const int64_t *rows, int num_rows,
                                 void *stream);
 
 /* ------------------------------------------------------------------ *
+ * Step guard (csrc/optim.hip, docs/STEP_GUARD_SPEC.md): global gradient-norm
+ * clipping and the skip of a step with non-finite gradients, decided on the
+ * device by kernels that are part of the (captured) step.
+ *
+ * The guard RECORD is DVSOF_GUARD_RECORD_BYTES of device memory, 8-byte
+ * aligned, zeroed once by the caller and persistent from then on:
+ *
+ *   float    scale        (float)min(1, max_norm / (norm + 1e-6)), the
+ *                         quotient in float64; 1.0f when max_norm <= 0
+ *                         (clipping off) or when bad > 0
+ *   uint32_t skip         1 iff bad > 0 and skip_nonfinite
+ *   double   norm         sqrt(sum of squares); NaN when bad > 0
+ *   uint32_t bad          non-finite gradient elements of this step (saturating)
+ *   uint32_t skipped      steps skipped since the record was zeroed
+ *   uint32_t clipped      steps with scale < 1
+ *   uint32_t consecutive  skipped steps in a row (0 after a step that updated)
+ *
+ * dvsof_grad_guard enqueues two launches in stream order.  PARTIALS: one
+ * workgroup per (tensor, chunk) work item writes {double sum of
+ * (double)g * (double)g over its finite elements, uint32 count of elements
+ * whose exponent field is all ones} -- per thread, then the wave, then the four
+ * waves, in a fixed order, without atomics.  CLOSE: one workgroup sums the
+ * partials in a fixed order in float64 and writes the record.  Nothing inside
+ * a launch waits for another workgroup.
+ *   grads      device uint64: grads[t * ptr_stride] is the gradient pointer of
+ *              tensor t (float32, dense, 4-byte aligned).  With a pointer
+ *              table of dvsof_adamw_step: ptrs + 1 and ptr_stride 5; the
+ *              tables of several parameter groups concatenated (tensor ids of
+ *              `chunks` offset accordingly) give ONE norm and ONE decision
+ *   sizes, chunks, num_chunks   as for dvsof_adamw_step
+ *   partials   device workspace, 8-byte aligned, at least num_chunks *
+ *              dvsof_grad_guard_partial_bytes() (DVSOF_ENOSPACE otherwise;
+ *              nothing is enqueued)
+ *   max_norm   <= 0: no clipping
+ * num_chunks == 0 (no gradient at all): the close alone runs, norm 0.
+ * ------------------------------------------------------------------ */
+#define DVSOF_GUARD_RECORD_BYTES 32
+#define DVSOF_GUARD_PARTIAL_BYTES 16
+int dvsof_grad_guard_record_bytes(void);
+int dvsof_grad_guard_partial_bytes(void);
+int dvsof_grad_guard(const uint64_t *grads, int ptr_stride,
+                     const int64_t *sizes, const int32_t *chunks,
+                     int num_chunks, void *partials, size_t partials_bytes,
+                     double max_norm, int skip_nonfinite, void *guard,
+                     void *stream);
+
+/*
+ * The update entry points above under a guard: every workgroup reads `skip`
+ * and `scale` from the record.  A skipped step returns before any load or
+ * store -- no parameter, moment, max_exp_avg_sq, weight decay, Lookahead slow
+ * buffer or Lookahead synchronisation is written.  Otherwise each gradient is
+ * multiplied by `scale` (one float32 multiply, after the gradient
+ * centralisation of Ranger, which is a launch of its own and is not gated)
+ * and the update is the unguarded one: with scale == 1.0f bit for bit.
+ */
+int dvsof_adamw_step_guarded(const uint64_t *ptrs, const int64_t *sizes,
+                             const int32_t *chunks, int num_chunks, float lr,
+                             float beta1, float beta2, float eps,
+                             float weight_decay, int step, int amsgrad,
+                             const void *guard, void *stream);
+int dvsof_adamw_step_dyn_guarded(const uint64_t *ptrs, const int64_t *sizes,
+                                 const int32_t *chunks, int num_chunks,
+                                 const float *dyn, float beta1, float beta2,
+                                 float eps, float weight_decay, int amsgrad,
+                                 const void *guard, void *stream);
+int dvsof_radam_step_guarded(const uint64_t *ptrs, const int64_t *sizes,
+                             const int32_t *chunks, int num_chunks, float lr,
+                             float beta1, float beta2, float eps,
+                             float weight_decay, int step,
+                             float nsma_threshold, int degenerate_to_sgd,
+                             int lookahead_now, float lookahead_alpha,
+                             const void *guard, void *stream);
+int dvsof_radam_step_dyn_guarded(const uint64_t *ptrs, const int64_t *sizes,
+                                 const int32_t *chunks, int num_chunks,
+                                 const float *dyn, float beta1, float beta2,
+                                 float eps, float weight_decay,
+                                 float lookahead_alpha, const void *guard,
+                                 void *stream);
+
+/* ------------------------------------------------------------------ *
  * Checkpoint snapshot (csrc/snapshot.hip, docs/CHECKPOINT_SPEC.md): one
  * launch copies the storage of many float32 tensors into one device slab and
  * counts the values whose exponent field is all ones (NaN, +-Inf).

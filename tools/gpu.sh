@@ -9,7 +9,9 @@
 #   variants <name> [<name> ...]      `conv` under variant libraries built by tools/variant.sh
 #   hbm [ENV=VAL ...]                 voxeliser / loss call paths at the BASELINE.json sizes
 #   optim [optim_bench.py args]       Ranger / AdamW step, eager loop against executor replay, f32 and bf16s,
-#                                     then the update and centralisation kernels alone (tools/optim_bench.py)
+#                                     then the update and centralisation kernels alone (tools/optim_bench.py);
+#                                     then its --guard leg: step guard off against on in alternating blocks,
+#                                     the statistic kernels alone (docs/STEP_GUARD_SPEC.md)
 #   eval [eval_bench.py args]        testing.evaluate on a synthetic MVSEC-shaped sequence: frames/s at batch 1 and 8,
 #                                     the reference's per-frame structure on the host, the three kernels alone
 #                                     the same frames from a device-resident EventSequence, the window kernel alone
@@ -62,7 +64,10 @@ hbm)
   timeout -k 10 300 env "${envs[@]}" python tools/hbm_bench.py 2>&1 | tee $O/hbm.txt ;;
 optim)
   timeout -k 10 840 env "${envs[@]}" python tools/optim_bench.py "$@" > $O/optim.jsonl 2> $O/optim.err
-  echo "optim rc=$?"; cut -c1-420 $O/optim.jsonl; tail -3 $O/optim.err ;;
+  rc=$?; echo "optim rc=$rc"; cut -c1-420 $O/optim.jsonl; tail -3 $O/optim.err
+  [ $rc -eq 0 ] || exit $rc       # nothing more on the GPU after a failed leg
+  timeout -k 10 560 env "${envs[@]}" python tools/optim_bench.py --guard "$@" > $O/optim_guard.jsonl 2> $O/optim_guard.err
+  echo "optim guard rc=$?"; cut -c1-420 $O/optim_guard.jsonl; tail -3 $O/optim_guard.err ;;
 eval)
   timeout -k 10 560 env "${envs[@]}" python tools/eval_bench.py "$@" > $O/eval.json 2> $O/eval.err
   echo "eval rc=$?"; cut -c1-2600 $O/eval.json; tail -3 $O/eval.err ;;

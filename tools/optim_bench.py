@@ -3,6 +3,7 @@
 against the step executor's replay, and the update kernels alone.
 
     python tools/optim_bench.py [--dtypes f32 bf16s] [--legs eager replay] [--fused]
+    python tools/optim_bench.py --guard         # the step guard's cost alone
 
 GPU only (no device: it fails).  B = 8, 256x256x5, 65 536 events per sample,
 two resident batches.  Per dtype and optimizer the two legs -- every kernel
@@ -18,7 +19,15 @@ repetitions): the RAdam/Ranger update kernel over the predictor's parameters
 on a step that does not synchronise the Lookahead slow weights (28 B per
 parameter: p, g, m, v read, p, m, v written) and on one that does (36 B), with
 the share of 8 TB/s those bytes over that time are; and the gradient
-centralisation, one launch per tensor against the multi-tensor launch."""
+centralisation, one launch per tensor against the multi-tensor launch.
+
+``--guard`` (docs/STEP_GUARD_SPEC.md) measures the step guard instead: f32,
+AdamW and Ranger, eager and executor replay, blocks of a guard-off and a
+guard-on leg alternating within one run (``set_guard(1e9)``: nothing clips,
+nothing skips, so both legs do the same arithmetic; no update inside the
+backward in either, which a guard excludes); then the two statistic kernels
+alone (HIP events; 4 B per parameter read).  On a commit without ``set_guard``
+the guard-off legs alone are measured."""
 import argparse
 import json
 import sys
@@ -42,7 +51,7 @@ class Leg:
     """A model, an optimizer and two resident batches, stepped eagerly or as
     replays of captured steps bound to the batches."""
 
-    def __init__(self, optimizer, dtype, replay, fused):
+    def __init__(self, optimizer, dtype, replay, fused, guard=False):
         from dvs_of_training_framework_amd import optim, synthetic
         from dvs_of_training_framework_amd.loss import init_losses
         from dvs_of_training_framework_amd.net import Model
@@ -56,6 +65,8 @@ class Leg:
             self.opt = optim.FusedAdamW(params, lr=1e-3, weight_decay=1e-4, amsgrad=True)
         if fused:
             self.opt.fuse_into_backward(self.model.predictor)
+        if guard:
+            self.opt.set_guard(1e9, True)       # never binds: the cost of deciding, nothing else
         self.sched = torch.optim.lr_scheduler.LambdaLR(self.opt, lambda s: 2 ** (-s / 100000))
         self.losses = init_losses((H, W), B, self.model, 'cuda', sequence_length=1)
         self.batches = [synthetic.to_torch(synthetic.make_batch(1234 + 1000 * i, B, H, W, None), 'cuda')
@@ -136,6 +147,67 @@ def steps(a, optimizer, dtype):
         leg.close()
 
 
+def guard_steps(a, optimizer):
+    """Guard off against guard on, per launch mode, in alternating blocks."""
+    from dvs_of_training_framework_amd import optim
+    cls = optim.FusedRanger if optimizer == 'ranger' else optim.FusedAdamW
+    has_guard = hasattr(cls, 'set_guard')
+    for mode in a.legs:
+        replay = mode == 'replay'
+        legs = {'guard off': Leg(optimizer, 'f32', replay, False)}
+        if has_guard:
+            legs['guard on'] = Leg(optimizer, 'f32', replay, False, guard=True)
+        else:
+            say(what='guard', optimizer=optimizer, mode=mode, leg='guard on', ms_per_step=None,
+                note=f'not measured: {cls.__name__} has no set_guard on this commit')
+        for leg in legs.values():
+            leg.settle(a.warmup)
+        blocks = {name: [] for name in legs}
+        for _ in range(a.blocks):
+            for name, leg in legs.items():
+                blocks[name].append(leg.block(a.block_steps))
+        for name, ms in blocks.items():
+            mean = sum(ms) / len(ms)
+            say(what='guard', optimizer=optimizer, mode=mode, leg=name, dtype='f32',
+                ms_per_step=round(mean, 4), samples_per_s=round(B / mean * 1e3, 1),
+                timed_steps=a.blocks * a.block_steps, block_ms=[round(v, 4) for v in ms],
+                spread_ms=round(max(ms) - min(ms), 4))
+        if has_guard:
+            state = legs['guard on'].opt.guard_state()
+            say(what='guard record', optimizer=optimizer, mode=mode,
+                **{k: state[k] for k in ('norm', 'scale', 'bad', 'skipped', 'clipped')})
+        for leg in legs.values():
+            leg.close()
+
+
+def guard_alone(a):
+    """The two statistic kernels (partials, close) over the predictor's
+    gradients: HIP events, bytes from the parameter shapes."""
+    from dvs_of_training_framework_amd import optim
+    from dvs_of_training_framework_amd.net import Model
+    if not hasattr(optim.FusedAdamW, 'set_guard'):
+        say(what='guard statistic alone', event_ms_median=None,
+            note='not measured: no set_guard on this commit')
+        return
+    torch.manual_seed(1)
+    model = Model('cuda', event_representation_depth=BINS)
+    plist = list(model.predictor.parameters())
+    for p in plist:
+        p.grad = torch.randn_like(p) * 1e-3
+    opt = optim.FusedAdamW(plist, lr=1e-4, amsgrad=True)
+    opt.set_guard(1e9, True)
+    opt.step()                                  # state, tables, workspace
+    torch.cuda.synchronize()
+    work = [(0, opt.param_groups[0], plist)]
+    n_params = sum(p.numel() for p in plist)
+    med, best = event_ms(lambda: opt._enqueue_guard(work), a.reps)
+    say(what='guard statistic alone', launches=2, tensors=len(plist), parameters=n_params,
+        work_items=opt._guard_tables[4], bytes=4 * n_params, bytes_per_parameter=4,
+        event_ms_median=round(med, 4), event_ms_min=round(best, 4),
+        gb_per_s=round(4 * n_params / med / 1e6, 1),
+        share_of_8tb_per_s=round(4 * n_params / (med * 1e-3) / HBM_PEAK, 4))
+
+
 def event_ms(fn, reps):
     """Median HIP-event time of fn() over reps."""
     out = []
@@ -212,11 +284,19 @@ def main():
     p.add_argument('--reps', type=int, default=31, help='repetitions of the update-alone timings')
     p.add_argument('--fused', action='store_true',
                    help='optim.fuse_into_backward in both legs (bench.py does so for f32)')
+    p.add_argument('--guard', action='store_true',
+                   help='measure the step guard (guard off against guard on, the statistic '
+                        'kernels alone) instead of the legs above')
     a = p.parse_args()
     if not torch.cuda.is_available():
         sys.exit('optim_bench: no GPU; nothing is measured without one')
     say(what='config', device=torch.cuda.get_device_name(0), B=B, H=H, W=W, bins=BINS,
         events_per_sample=H * W, blocks=a.blocks, block_steps=a.block_steps, warmup=a.warmup)
+    if a.guard:
+        for optimizer in a.optimizers:
+            guard_steps(a, optimizer)
+        guard_alone(a)
+        return
     for dtype in a.dtypes:
         for optimizer in a.optimizers:
             steps(a, optimizer, dtype)

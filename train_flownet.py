@@ -30,13 +30,14 @@ from dvs_of_training_framework_amd.model import init_model
 from dvs_of_training_framework_amd.optim import FusedAdamW, FusedRAdam, \
     FusedRanger
 from dvs_of_training_framework_amd.options import (
-    add_train_arguments, add_preprocessed_dataset_arguments,
-    validate_train_args)
+    add_train_arguments, add_preprocessed_dataset_arguments, guard_requested,
+    resolve_step_guard, validate_train_args)
 from dvs_of_training_framework_amd.hooks import SerializationHook, \
     ValidationHook
 from dvs_of_training_framework_amd.serializer import Serializer
 from dvs_of_training_framework_amd.timer import EventTimer, FakeTimer
-from dvs_of_training_framework_amd.training import make_hook_periodic, train
+from dvs_of_training_framework_amd.training import HostGuard, \
+    make_hook_periodic, train
 
 script_dir = Path(__file__).resolve().parent
 
@@ -46,6 +47,7 @@ def parse_args(argv):
     parser = add_train_arguments(parser)
     parser = add_preprocessed_dataset_arguments(parser)
     args = parser.parse_args(argv)
+    args = resolve_step_guard(args, parser)
     args = validate_train_args(args)
     args.model.mkdir(exist_ok=True, parents=True)
     args.log_path = args.model / 'log'
@@ -359,6 +361,16 @@ def main(argv=None):
     if resume:
         restore_loader(loader, state, rank, world, global_step, args)
 
+    # the step guard (docs/STEP_GUARD_SPEC.md): on the device for the fused optimizers, a host
+    # check in front of optimizer.step() for the others
+    host_guard = None
+    if guard_requested(args):
+        skip = bool(getattr(args, 'skip_nonfinite_steps', False))
+        if hasattr(optimizer, 'set_guard'):
+            optimizer.set_guard(args.clip_grad_norm, skip)
+        else:
+            host_guard = HostGuard(args.clip_grad_norm, skip)
+
     oib = getattr(args, 'optimizer_in_backward', 'auto')
     if device.type == 'cuda' and hasattr(optimizer, 'fuse_into_backward') and \
             hasattr(model, 'predictor') and \
@@ -402,7 +414,10 @@ def main(argv=None):
                   hooks=periodic, init_step=global_step,
                   init_samples_passed=samples_passed,
                   max_events_per_batch=args.max_events_per_batch,
-                  reducer=reducer, capture=getattr(args, 'capture', False))
+                  reducer=reducer, capture=getattr(args, 'capture', False),
+                  guard=host_guard,
+                  max_skipped_steps=getattr(args, 'max_skipped_steps', 32),
+                  guard_agreement_every=args.checkpointing_interval)
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
