@@ -268,7 +268,10 @@ __device__ __forceinline__ void radam_elem(float &p, float g, float &m, float &v
 {
     v = v * a.beta2 + (1.f - a.beta2) * g * g;
     m = m * a.beta1 + (1.f - a.beta1) * g;
-    if (a.weight_decay != 0.f) p = p - a.weight_decay * a.lr * p;
+    // decay only where an update is taken: RAdam without degenerate-to-SGD leaves p alone
+    // while the variance is not tractable (step_size -1); Ranger's step size is never -1
+    if (a.weight_decay != 0.f && (a.rectified || a.step_size > 0.f))
+        p = p - a.weight_decay * a.lr * p;
     if (a.rectified) p = p - a.step_size * a.lr * (m / (sqrtf(v) + a.eps));
     else if (a.step_size > 0.f) p = p - a.step_size * a.lr * m;
     if (a.lookahead) {

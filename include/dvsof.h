@@ -940,6 +940,11 @@ int dvsof_adamw_step_dyn(const uint64_t *ptrs, const int64_t *sizes,
  *   degenerate_to_sgd  bit 0: take an un-rectified momentum step while the
  *                      variance is not tractable (both upstream defaults);
  *                      bit 1: RAdam's ">= threshold" rule instead of Ranger's ">"
+ *                      Weight decay (p -= weight_decay * lr * p, before the
+ *                      update) is applied only on a step that takes an update:
+ *                      rectified, or un-rectified with bit 0.  Without bit 0
+ *                      the un-rectified steps advance the moments and leave p
+ *                      bit for bit (docs/OPTIM_SPEC.md).
  *   lookahead_now      1 on every k-th step of Ranger, else 0
  *   lookahead_alpha    slow-weight step (0 = no slow buffer: plain RAdam)
  */
