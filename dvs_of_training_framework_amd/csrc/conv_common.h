@@ -160,13 +160,16 @@ __device__ __forceinline__ float act_bwd(float s, int act)
 {
     if (act == ACT_RELU) return s > 0.f ? 1.f : 0.f;
     if (act == ACT_MISH) {
-        // th + s (1 - th^2) sigmoid(s);  1 - th = 2 / (t + 2) without cancellation
+        // th + s (1 - th^2) sigmoid(s);  1 - th = 2 / (t + 2) without cancellation.  The
+        // product takes the s that n was made from (clamped at 20, where the term is
+        // ~1.7e-16): with the unclamped s it grows back into the result from s ~ 1e9 on.
+        // (A select, not fminf: a NaN pre-activation stays a NaN gradient.)
         float n;
         const float t = mish_t(s, n);
         const float r = __builtin_amdgcn_rcpf(t + 2.f);
         const float th = t * r;
         const float sg = n * __builtin_amdgcn_rcpf(1.f + n);
-        return th + s * ((2.f * r) * (1.f + th)) * sg;
+        return th + (s > 20.f ? 20.f : s) * ((2.f * r) * (1.f + th)) * sg;
     }
     return 1.f;
 }

@@ -280,7 +280,8 @@ int dvsof_flow_fold_grads(float *dW, const float *w, int Cout, int Ctot, int cx_
                           int H, int W, float *dwh, float *dbh, void *ws, size_t ws_bytes, void *stream)
 {
     if (!dW || !w || !wh || !bh || !db_conv || !g || !dwh || !dbh || !ws || Cout < 1 || Ctot < 3 || Cx < 1 ||
-        B < 1 || H < 1 || W < 1 || cf_off + 2 > Ctot || cx_off + Cx > Ctot)
+        B < 1 || H < 1 || W < 1 || cx_off < 0 || cf_off < 0 || cf_off + 2 > Ctot || cx_off + Cx > Ctot ||
+        (cx_off < cf_off + 2 && cf_off < cx_off + Cx))
         return DVSOF_EINVAL;
     if (ws_bytes < dvsof_flow_fold_workspace_bytes(B, Cout)) return DVSOF_ENOSPACE;
     hipStream_t st = as_stream(stream);

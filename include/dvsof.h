@@ -1115,6 +1115,9 @@ int dvsof_snapshot_pack(const uint64_t *srcs, const int64_t *counts,
  * cx_off / cf_off: first column of the x member / of the flow pair in a
  * weight row; 3x3 taps; the flow is the member convolved at the x member's
  * resolution (both up-sampled together).  ws: dvsof_flow_fold_workspace_bytes.
+ * Both entries refuse, with DVSOF_EINVAL and before any launch: a negative
+ * offset, an x range [cx_off, cx_off + Cx) or a flow pair [cf_off, cf_off + 2)
+ * that leaves the row or that overlap each other, Ctot < 3.
  * ------------------------------------------------------------------ */
 int dvsof_flow_fold_weights(const float *w, int Cout, int Ctot, int cx_off,
                             int Cx, int cf_off, const float *wh, float *w_eff,
