@@ -12,6 +12,10 @@ The architecture is the canonical EV-FlowNet (Zhu et al., RSS 2018):
   dec.i   3x3 conv + act on the 2x nearest-upsampled concat[x, skip, flow]
           -> 256, 128, 64, 32;  dec.i.flow = 1x1 conv -> 2 (linear head)
 
+``LAYERS`` is the one description of these 12 conv layers (members, frames,
+parameters, gradient units); modules, parameter order, FLOPs, the forward's
+loop and the backward's lookups all read it.
+
 Forward and backward are ONE autograd node with an explicit schedule: the
 backward pass is ~45 launches of the gather-conv / wgrad / head kernels with
 the gradient sums and activation derivatives folded into kernel epilogues
@@ -20,6 +24,7 @@ the gradient sums and activation derivatives folded into kernel epilogues
 import contextlib
 import math
 import os
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -31,6 +36,63 @@ _SIDE_STREAMS = {}      # device index -> the second backward stream
 ENC_CH = (64, 128, 256, 512)
 DEC_CH = (256, 128, 64, 32)
 NUM_RES = 2
+
+VOXELS = -1             # Layer.inputs: the network's input
+
+
+class Layer(NamedTuple):
+    """One conv layer of the network: everything about it that is no tensor."""
+    unit: tuple         # gradient unit key: ('enc', i) | ('res', i, 1 | 2) | ('dec', i)
+    srcs: tuple         # source members (channels, layout); channels None: the input's
+    inputs: tuple       # per member VOXELS | the layer whose output it is | ('flow', layer)
+    cout: int
+    stride: int
+    up: bool            # 2x nearest upsampling of the concatenated members
+    shift: int          # its frame is (H >> shift, W >> shift)
+    params: tuple       # indices in param_list(): w, b and, with a flow head, flow w, flow b
+    residual: object    # the layer whose output is added ahead of the activation, or None
+    chained: tuple      # (its producer, its consumer) is a Winograd layer of the same frame
+
+    @property
+    def name(self):
+        return '.'.join(map(str, self.unit))
+
+
+def _layer_table():
+    """The 12 conv layers in forward order; parameters numbered as they come."""
+    table = []
+
+    def add(unit, srcs, inputs, cout, shift, stride=1, up=False, residual=None,
+            chained=(False, False), head=False):
+        first = table[-1].params[-1] + 1 if table else 0
+        table.append(Layer(unit, tuple(srcs), tuple(inputs), cout, stride, up, shift,
+                           tuple(range(first, first + (4 if head else 2))), residual, chained))
+        return len(table) - 1
+    c, lay, x, deep = None, C.NCHW, VOXELS, len(ENC_CH)
+    for i, cout in enumerate(ENC_CH):
+        x = add(('enc', i), [(c, lay)], [x], cout, i, stride=2)
+        c, lay = cout, C.NHWC
+    skips = list(range(deep))
+    for i in range(NUM_RES):
+        t = add(('res', i, 1), [(c, lay)], [x], c, deep, chained=(i > 0, True))
+        x = add(('res', i, 2), [(c, lay)], [t], c, deep, residual=x,
+                chained=(True, i + 1 < NUM_RES))
+    for i, cout in enumerate(DEC_CH):
+        skip = skips.pop()
+        srcs, inputs = [(c, lay), (ENC_CH[skip], lay)], [x, skip]
+        if i > 0:       # the flow of the stage below
+            srcs.append((2, C.NCHW))
+            inputs.append(('flow', x))
+        x = add(('dec', i), srcs, inputs, cout, deep - i, up=True, head=True)
+        c = cout
+    return tuple(table)
+
+
+LAYERS = _layer_table()
+# layer indices by part of the network (the backward walks them in reverse)
+_ENC = tuple(i for i, l in enumerate(LAYERS) if l.unit[0] == 'enc')
+_RES = tuple((l.inputs[0], i) for i, l in enumerate(LAYERS) if l.residual is not None)
+_DEC = tuple(i for i, l in enumerate(LAYERS) if l.unit[0] == 'dec')
 
 
 def activation_id(activation):
@@ -86,32 +148,60 @@ def _phys(w):
     return w
 
 
-class _PredictorFn(torch.autograd.Function):
+class _NoTensor:
+    """Source member of a descriptor made before the layer's inputs exist: conv.prepare and
+    the planning queries read the shape fields only, and want an address that is not NULL."""
     @staticmethod
-    def forward(ctx, x0, module, want_grad, *params):
-        # params: enc(w,b)x4, res(w1,b1,w2,b2)x2, dec(w,b,fw,fb)x4
-        dev = x0.device
-        act = module.act
-        B, Cin, H, W = x0.shape
-        mish = act == C.ACT_MISH
-        twins = module.mfma == C.MFMA_BF16_TWINS
-        p = list(params)
-        enc = [(p[2 * i], p[2 * i + 1]) for i in range(4)]
-        o = 8
-        res = [(p[o + 4 * i], p[o + 4 * i + 1], p[o + 4 * i + 2],
-                p[o + 4 * i + 3]) for i in range(NUM_RES)]
-        o += 4 * NUM_RES
-        dec = [(p[o + 4 * i], p[o + 4 * i + 1], p[o + 4 * i + 2],
-                p[o + 4 * i + 3]) for i in range(4)]
-        L = []          # per conv layer: dict(desc, y, z, srcs)
-        # data-gradient forms of the weights are only needed by the backward:
-        # they are made on the second stream while the forward runs.  That
-        # stream first waits for everything enqueued so far (the optimizer's
-        # update of the weights; the previous backward's readers of the
-        # buffers it is about to reuse).
-        main = torch.cuda.current_stream(dev)
-        side = module._wgrad_stream(dev) if want_grad else None
+    def data_ptr():
+        return 4096
+
+
+class _Fold(NamedTuple):
+    """Decoder stage run on cat[x, skip], its flow member folded into weight space
+    (csrc/flowfold.hip): what forward and backward share."""
+    desc: object        # the two-member descriptor forward and data gradient run on
+    w: object           # the stage's raw weight
+    cx: int             # channels of x = column where the skip member starts
+    cf_off: int         # column where the flow member starts
+    ctot: int
+    head: tuple         # param_list() indices of (w, b) of the head below, whose flow it is
+    keep: tuple         # forms made on the second stream and read on the main one
+
+
+class _Done(NamedTuple):
+    """A layer as the forward leaves it for the backward."""
+    desc: object
+    y: object
+    z: object
+    srcs: list
+    w_dg: object
+    w_dg16: object
+    fold: object
+
+
+class _Plan:
+    """The weight forms of one step: which stream makes each, and where the main stream
+    first waits for them."""
+    # Training with the second stream, that stream makes, in this order: the bf16 twins of
+    # the raw weights, every prepared FORWARD form (Winograd-domain weights of the residual
+    # layers, sub-pixel phase kernels of the decoder: not needed before the encoder has
+    # run), then layer by layer beside the forward the data-gradient forms, which only the
+    # backward needs.  The main stream waits once for the twins and once for the forward
+    # forms, each at the first layer that takes one.  A forward form that was not made ahead
+    # is made on the main stream where it is used, and the second stream waits for it.
+    # Without the second stream (DVSOF_WGRAD_STREAM=0, inference) everything is made on the
+    # main stream: folded decoder stages at the top, the rest where it is used.
+
+    def __init__(self, module, dims, params, want_grad, dev):
+        self.dims, self.act, self.mfma = dims, module.act, module.mfma
+        self.params, self.want_grad = params, want_grad
+        self.twins = twins = module.mfma == C.MFMA_BF16_TWINS
+        self.main = torch.cuda.current_stream(dev)
+        self.side = side = module._wgrad_stream(dev) if want_grad else None
         begin = module._take_step_begin()
+        # The second stream first waits for everything enqueued so far (the optimizer's
+        # update of the weights; the previous backward's readers of the buffers it is about
+        # to reuse) ...
         if side is not None:
             # ... or, when the caller marked the start of the step (mark_step_begin, ahead
             # of the voxeliser), only for what preceded THAT: nothing made here reads the
@@ -119,199 +209,163 @@ class _PredictorFn(torch.autograd.Function):
             if begin is not None:
                 side.wait_event(begin)
             else:
-                side.wait_stream(main)
-
+                side.wait_stream(self.main)
+        self.pending = {}       # 'raw16' | 'fwd' -> event the main stream has yet to wait for
         # bf16-twins mode: the twins of the weights that are used as they are
         # (stride-2 encoder layers, direct residual layers) in ONE launch; the
         # twins of prepared forms come from the kernels that make the forms
-        raw16, raw16_ready = {}, None
+        self.raw16 = {}         # layer -> twin of its raw weight
         if twins:
-            raws = [e_[0] for e_ in enc] + [r_[j] for r_ in res for j in (0, 2)]
-            # on the second stream when there is one (16 us off the forward's lane): the
-            # first layer does not read them, the main stream waits before the second
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                raw16 = {id(w_): t_ for w_, t_ in
-                         zip(raws, C.to_bf16_many([_phys(w_) for w_ in raws]))}
-                if side is not None:
-                    raw16_ready = torch.cuda.Event()
-                    raw16_ready.record(side)
-
-        # Prepared FORWARD forms (Winograd-domain weights of the residual
-        # layers, sub-pixel phase kernels of the decoder) are not needed
-        # before the encoder has run: when training they are made on the
-        # second stream too, ahead of the data-gradient forms, and the main
-        # stream waits for them once, at the first residual layer.
-        pre, pre_ready = {}, None
-
-        def _fold_pre(srcs2, hh, ww, cout_, wgt_, bias_, head):
-            cx, cs = srcs2[0][1], srcs2[1][1]
-            ctot = cx + cs + 2
-            w_eff = C.flow_fold_weights(_phys(wgt_), cout_, ctot, 0, cx, cx + cs, head[0])
-            b_eff, b_cls = C.flow_fold_bias(_phys(wgt_), cout_, ctot, cx + cs, head[1], bias_)
-            d2 = C.make_desc(list(srcs2), B, hh, ww, cout_, 3, 1, 1, True, act, module.mfma)
-            w_f, _, w_f16, _ = _prep(d2, w_eff, False, want16=twins)
-            return dict(w_eff=w_eff, w_fwd=w_f, w_fwd16=w_f16, bias=b_eff, bias_cls=b_cls,
-                        cx=cx, cf_off=cx + cs, ctot=ctot, head=head)
-
-        # Decoder stages whose third member is the previous stage's flow run, when
-        # training, on cat[x, skip] with that member folded into weight space
-        # (csrc/flowfold.hip); in inference the member stays a member
-        fold_pre = want_grad
-        if side is not None or fold_pre:
-            h16, w16 = H // 16, W // 16
-            specs = [(4 + 2 * i + j, [(x0, 512, C.NHWC)], h16, w16, 512,
-                      res[i][2 * j], False)
-                     for i in range(NUM_RES) for j in range(2)]
-            cx_, hh, ww = 512, h16, w16
-            for i in range(4):
-                srcs_ = [(x0, cx_, C.NHWC), (x0, ENC_CH[3 - i], C.NHWC)]
-                if i > 0:
-                    srcs_.append((x0, 2, C.NCHW))
-                specs.append((4 + 2 * NUM_RES + i, srcs_, hh, ww, DEC_CH[i],
-                              dec[i][0], True))
-                cx_, hh, ww = DEC_CH[i], 2 * hh, 2 * ww
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                for li, srcs_, hh, ww, cout_, wgt_, up_ in specs:
-                    if fold_pre and len(srcs_) == 3:
-                        # decoder stage with a flow member: forward AND backward run
-                        # on cat[x, skip] with the head folded into the weights
-                        i_ = li - (4 + 2 * NUM_RES)
-                        pre[li] = _fold_pre(srcs_[:2], hh, ww, cout_, wgt_, dec[i_][1],
-                                            (dec[i_ - 1][2], dec[i_ - 1][3]))
-                        continue
-                    if side is None:
-                        continue        # the other forms are made where they are used
-                    d_ = C.make_desc(srcs_, B, hh, ww, cout_, 3, 1, 1, up_, act,
-                                     module.mfma)
-                    w_f, _, w_f16, _ = _prep(d_, _phys(wgt_), False,
-                                                 want16=twins)
-                    if w_f is not wgt_:
-                        pre[li] = (w_f, w_f16)
-            if side is not None:
-                pre_ready = torch.cuda.Event()
-                pre_ready.record(side)
-        waited, waited16 = [False], [False]
-
-        chain = {'v': None}     # Winograd form a layer made for its consumer
+            raws = [li for li, l in enumerate(LAYERS) if not l.up]
+            # on the second stream when there is one (16 us off the forward's lane)
+            with self._on_side():
+                self.raw16 = dict(zip(raws, C.to_bf16_many(
+                    [_phys(params[LAYERS[li].params[0]]) for li in raws])))
+                self._record('raw16')
+        self.fwd, self.folds = {}, {}       # layer -> (w_fwd, w_fwd16) | folded forms
+        if want_grad:
+            with self._on_side():
+                for li, l in enumerate(LAYERS):
+                    if len(l.srcs) == 3:
+                        # decoder stage with a flow member: when training, forward AND
+                        # backward run on cat[x, skip] with the head folded into the
+                        # weights; in inference the member stays a member
+                        self.folds[li] = self._fold_forms(l)
+                    elif side is not None and l.stride == 1:    # (the encoder's: where used)
+                        w = params[l.params[0]]
+                        w_f, _, w_f16, _ = _prep(self.desc(l)[1], _phys(w), False, want16=twins)
+                        if w_f is not w:
+                            self.fwd[li] = (w_f, w_f16)
+                self._record('fwd')
         # (Measured and not kept: the data-gradient weight forms issued late, beside the
         # decoder's kernels instead of layer by layer beside the encoder / residual layers:
         # 2.522-2.530 ms wherever they run -- the step is bound by total work, and the forms
         # cost 63 us of it: 2.451 ms with the forms of the first step reused, which is wrong.)
 
-        def run(srcs, h, w, cout, wgt, bias, stride=1, up=False,
-                residual=None, chained=(False, False)):
-            """-> (y, y16): the layer's output and, in the bf16-twins mode,
-            its bf16 copy (written by the same kernel).  chained = (its
-            producer / its consumer is a Winograd layer of the same frame:
-            the transformed input travels from output transform to GEMM,
-            dvsof_conv_desc_t.winograd_next)."""
-            d = C.make_desc(srcs, B, h, w, cout, 3, stride, 1, up, act,
-                            module.mfma)
-            # prepared weights: sub-pixel phase kernels for the decoder,
-            # Winograd forms for the residual layers, and (when training) the
-            # data-gradient form, made once per step
-            first = len(L) == 0       # voxel input needs no data gradient
-            need_dg = want_grad and not first
-            w_fwd16 = w_dg16 = w_dg = fold = None
-            fpre = pre.get(len(L)) if isinstance(pre.get(len(L)), dict) else None
-            if fpre is not None:
-                # flow member folded (forward and backward): two vector members
-                if side is not None and not waited[0]:
-                    main.wait_event(pre_ready)
-                    waited[0] = True
-                d2 = C.make_desc(list(srcs[:2]), B, h, w, cout, 3, 1, 1, True, act,
-                                 module.mfma)
-                with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                    _, wd, _, wd16 = _prep(d2, fpre['w_eff'], True,
-                                           phase_weights=fpre['w_fwd'], want16=twins)
-                fold = dict(desc=d2, w_dg=wd, w_dg16=wd16, keep=(fpre,), cx=fpre['cx'],
-                            cf_off=fpre['cf_off'], ctot=fpre['ctot'], head=fpre['head'])
-                y, z = C.conv_fwd(d2, fpre['w_fwd'], fpre['bias'], dev, residual, mish,
-                                  keep_input_transform=want_grad,
-                                  weight16=fpre['w_fwd16'], bias_cls=fpre['bias_cls'])
-                L.append(dict(desc=d, y=y, z=z, srcs=srcs, w=wgt, w_dg=None,
-                              w_dg16=None, fold=fold))
-                return y, d2._y16
-            if side is not None and need_dg:
-                if isinstance(pre.get(len(L)), tuple):    # made on the second stream
-                    w_fwd, w_fwd16 = pre[len(L)]
-                    if not waited[0]:
-                        main.wait_event(pre_ready)
-                        waited[0] = True
-                else:
-                    w_fwd, _ = C.prepare(d, _phys(wgt), False)
-                    if w_fwd is not wgt:      # prepared form made on main
-                        ev = torch.cuda.Event()
-                        ev.record(main)
-                        side.wait_event(ev)
-                with torch.cuda.stream(side):
-                    _, w_dg, _, w_dg16 = _prep(d, _phys(wgt), True,
-                                               phase_weights=w_fwd,
-                                               want16=twins)
-            else:
-                w_fwd, w_dg, w_fwd16, w_dg16 = _prep(
-                    d, _phys(wgt), need_dg, want16=twins)
-            if twins and w_fwd16 is None:
-                if raw16_ready is not None and not waited16[0]:
-                    main.wait_event(raw16_ready)
-                    waited16[0] = True
-                w_fwd16 = raw16.get(id(wgt))
-                if w_fwd16 is None or w_fwd is not wgt:
-                    w_fwd16 = C.to_bf16(w_fwd)
-            v_pre = chain['v'] if chained[0] else None
-            chain['v'] = C.winograd_form(d, cout, dev) \
-                if chained[1] and C.winograd_chain(d, 0) else None
-            y, z = C.conv_fwd(d, w_fwd, bias, dev, residual, mish,
-                              keep_input_transform=want_grad,
-                              weight16=w_fwd16, wino_pre=v_pre,
-                              wino_next=chain['v'])
-            L.append(dict(desc=d, y=y, z=z, srcs=srcs, w=wgt, w_dg=w_dg,
-                          w_dg16=w_dg16, fold=fold))
-            return y, d._y16
+    def _on_side(self):
+        return torch.cuda.stream(self.side) if self.side is not None \
+            else contextlib.nullcontext()
 
-        # encoder (activations travel as (f32 tensor, bf16 twin or None))
-        e, h, w = [], H, W
-        cur, ccur, lay = (x0, None), Cin, C.NCHW
-        for i in range(4):
-            cur = run([(cur[0], ccur, lay, cur[1])], h, w, ENC_CH[i], *enc[i],
-                      stride=2)
-            h, w, ccur, lay = h // 2, w // 2, ENC_CH[i], C.NHWC
-            e.append(cur)
-        # residual blocks
-        r = e[3]
-        for i in range(NUM_RES):
-            t = run([(t_[0], 512, C.NHWC, t_[1]) for t_ in (r,)], h, w, 512,
-                    res[i][0], res[i][1], chained=(i > 0, True))
-            r = run([(t[0], 512, C.NHWC, t[1])], h, w, 512, res[i][2],
-                    res[i][3], residual=r[0], chained=(True, i + 1 < NUM_RES))
-        # decoder
-        flows, xx, cx, f, heads = [], r, 512, None, []
-        for i in range(4):
-            sk = e[3 - i]
-            srcs = [(xx[0], cx, C.NHWC, xx[1]),
-                    (sk[0], ENC_CH[3 - i], C.NHWC, sk[1])]
-            if f is not None:
-                srcs.append((f, 2, C.NCHW))
-            xx = run(srcs, h, w, DEC_CH[i], dec[i][0], dec[i][1], up=True)
-            x = xx[0]
-            h, w, cx = 2 * h, 2 * w, DEC_CH[i]
-            if fold_pre:
-                # folded: no later stage reads this flow -- all four heads run in
-                # one launch after the last stage (the tensor is only named here)
-                f = torch.empty(B, 2, h, w, dtype=torch.float32, device=dev)
-                heads.append((x, dec[i][2], dec[i][3], h, w, cx))
+    def _record(self, what):
+        if self.side is not None:
+            self.pending[what] = torch.cuda.Event()
+            self.pending[what].record(self.side)
+
+    def _await(self, what):
+        ev = self.pending.pop(what, None)
+        if ev is not None:
+            self.main.wait_event(ev)
+
+    def desc(self, l, members=()):
+        """-> (srcs, descriptor) of table layer ``l`` on ``members``, its first sources as
+        (tensor, bf16 twin or None); none: shapes only."""
+        B, Cin, H, W = self.dims
+        members = members or ((_NoTensor, None),) * len(l.srcs)
+        srcs = [(t, c or Cin, lay, t16) for (c, lay), (t, t16) in zip(l.srcs, members)]
+        return srcs, C.make_desc(srcs, B, H >> l.shift, W >> l.shift, l.cout, 3, l.stride,
+                                 1, l.up, self.act, self.mfma)
+
+    def _fold_forms(self, l):
+        (cx, _), (cs, _) = l.srcs[:2]
+        ctot = cx + cs + 2
+        w, bias = (self.params[i] for i in l.params[:2])
+        head = LAYERS[l.inputs[2][1]].params[2:]
+        wh, bh = (self.params[i] for i in head)
+        w_eff = C.flow_fold_weights(_phys(w), l.cout, ctot, 0, cx, cx + cs, wh)
+        b_eff, b_cls = C.flow_fold_bias(_phys(w), l.cout, ctot, cx + cs, bh, bias)
+        d2 = self.desc(l, ((_NoTensor, None),) * 2)[1]
+        w_f, _, w_f16, _ = _prep(d2, w_eff, False, want16=self.twins)
+        return _Fold(None, w, cx, cx + cs, ctot, head, (w_eff, w_f, w_f16, b_eff, b_cls))
+
+    def layer(self, li, l, d, members):
+        """-> (descriptor to run on, forward form, its twin, bias, bias table, data-gradient
+        form, its twin, _Fold or None) of layer ``li`` = ``l`` described by ``d``."""
+        twins, side = self.twins, self.side
+        w, bias = (self.params[i] for i in l.params[:2])
+        fold = self.folds.get(li)
+        if fold is not None:
+            self._await('fwd')
+            w_eff, w_f, w_f16, b_eff, b_cls = fold.keep
+            d2 = self.desc(l, members[:2])[1]
+            with self._on_side():
+                _, w_dg, _, w_dg16 = _prep(d2, w_eff, True, phase_weights=w_f, want16=twins)
+            return d2, w_f, w_f16, b_eff, b_cls, w_dg, w_dg16, fold._replace(desc=d2)
+        # the voxel input needs no data gradient
+        need_dg = self.want_grad and l.inputs[0] != VOXELS
+        if side is not None and need_dg:
+            if li in self.fwd:          # made ahead on the second stream
+                w_fwd, w_fwd16 = self.fwd[li]
+                self._await('fwd')
             else:
-                f = C.head_fwd(x, dec[i][2], dec[i][3], B, h, w, cx)
-            flows.append(f)
+                w_fwd, w_fwd16 = C.prepare(d, _phys(w), False)[0], None
+                if w_fwd is not w:      # prepared form made on main
+                    ev = torch.cuda.Event()
+                    ev.record(self.main)
+                    side.wait_event(ev)
+            with torch.cuda.stream(side):
+                _, w_dg, _, w_dg16 = _prep(d, _phys(w), True, phase_weights=w_fwd,
+                                           want16=twins)
+        else:
+            w_fwd, w_dg, w_fwd16, w_dg16 = _prep(d, _phys(w), need_dg, want16=twins)
+        if twins and w_fwd16 is None:
+            self._await('raw16')
+            w_fwd16 = self.raw16.get(li)
+            if w_fwd16 is None or w_fwd is not w:
+                w_fwd16 = C.to_bf16(w_fwd)
+        return d, w_fwd, w_fwd16, bias, None, w_dg, w_dg16, None
+
+    def close(self):
+        """-> the event after the last data-gradient form (None: all on the main stream)."""
+        self._record('dg')
+        return self.pending.pop('dg', None)
+
+
+class _PredictorFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, module, want_grad, *params):
+        dev, act = x0.device, module.act
+        B, Cin, H, W = dims = tuple(x0.shape)
+        mish = act == C.ACT_MISH
+        plan = _Plan(module, dims, params, want_grad, dev)
+        L = []                          # per conv layer: _Done
+        # what the layers read: activations travel as (f32 tensor, bf16 twin or None)
+        outs = {VOXELS: (x0, None)}
+        flows, heads = [], []
+        chain = None    # Winograd form a layer made for its consumer: the transformed input
+        # travels from output transform to GEMM (dvsof_conv_desc_t.winograd_next)
+        for li, l in enumerate(LAYERS):
+            members = [outs[k] for k in l.inputs]
+            srcs, d = plan.desc(l, members)
+            d_run, w_fwd, w_fwd16, bias, bias_cls, w_dg, w_dg16, fold = \
+                plan.layer(li, l, d, members)
+            v_pre = chain if l.chained[0] else None
+            chain = C.winograd_form(d, l.cout, dev) \
+                if l.chained[1] and C.winograd_chain(d, 0) else None
+            y, z = C.conv_fwd(d_run, w_fwd, bias, dev,
+                              None if l.residual is None else outs[l.residual][0], mish,
+                              keep_input_transform=want_grad, weight16=w_fwd16,
+                              bias_cls=bias_cls, wino_pre=v_pre, wino_next=chain)
+            L.append(_Done(d, y, z, srcs, w_dg, w_dg16, fold))
+            # in the bf16-twins mode the same kernel wrote the output's bf16 copy
+            outs[li] = (y, d_run._y16)
+            if len(l.params) == 4:
+                h, w = C.out_size(d)
+                head = (y, params[l.params[2]], params[l.params[3]], h, w, l.cout)
+                if want_grad:
+                    # folded: no later stage reads this flow -- all four heads run in
+                    # one launch after the last stage (the tensor is only named here)
+                    flow = torch.empty(B, 2, h, w, dtype=torch.float32, device=dev)
+                    heads.append(head)
+                else:
+                    flow = C.head_fwd(*head[:3], B, h, w, l.cout)
+                outs['flow', li] = (flow, None)
+                flows.append(flow)
         if heads:
             C.heads_fwd(heads, B, out=flows)
         if want_grad:
-            ctx.dg_ready = None
-            if side is not None:
-                ctx.dg_ready = torch.cuda.Event()
-                ctx.dg_ready.record(side)
-            ctx.L, ctx.act, ctx.dims = L, act, (B, Cin, H, W)
-            ctx.raw16 = raw16       # made on the second stream, read on this one: alive until backward
+            ctx.dg_ready = plan.close()
+            ctx.L, ctx.act, ctx.dims = L, act, dims
+            ctx.raw16 = plan.raw16  # made on the second stream, read on this one: alive until backward
             ctx.params = params
             ctx.module = module
             # a learnable event representation (net.LearnedVoxelGrid) below the
@@ -327,12 +381,10 @@ class _PredictorFn(torch.autograd.Function):
         mish = act == C.ACT_MISH
         grads, finish = ctx.module._grad_targets(params)
         gflows = [g.contiguous() for g in gflows]
+        gflow = dict(zip(_DEC, gflows))         # by decoder layer
 
         def asrc(layer):        # what act' is evaluated on
-            return layer['z'] if mish else layer['y']
-
-        def wt(layer):
-            return layer['w_dg']
+            return layer.z if mish else layer.y
 
         def new(t):
             return torch.empty_like(t)
@@ -341,9 +393,6 @@ class _PredictorFn(torch.autograd.Function):
 
         def tw(t):          # bf16 twin of a gradient a later data gradient reads
             return C.twin(t) if twins else None
-
-        enc_l, res_l, dec_l = L[0:4], L[4:4 + 2 * NUM_RES], L[4 + 2 * NUM_RES:]
-        po_res, po_dec = 8, 8 + 4 * NUM_RES
 
         # The data-gradient chain is the critical path; every weight gradient
         # only needs its layer's output gradient.  They run on a second HIP
@@ -366,8 +415,10 @@ class _PredictorFn(torch.autograd.Function):
         # weight gradient, ahead of it on the same stream.
         pending = []
 
-        def wgrad(desc, gz, gw, gb, unit, gz16=None, fold=None, first=None,
-                  wino_gout=None):
+        def wgrad(li, gz, gz16=None, fold=None, first=None, wino_gout=None):
+            desc, unit = L[li].desc, LAYERS[li].unit
+            gw, gb = (grads[i] for i in LAYERS[li].params[:2])
+
             def body():
                 if first is not None:
                     first()
@@ -392,20 +443,19 @@ class _PredictorFn(torch.autograd.Function):
 
         def fold_job(desc, gz, gw, gb, unit, fold):
             ho, wo = C.out_size(desc)
-            wh, bh = fold['head']
-            i_h = fold['head_idx']
+            (wh, gwh), (bh, gbh) = ((params[i], grads[i]) for i in fold.head)
 
             def job():
-                C.flow_fold_grads(gw, _phys(fold['w']), desc.Cout, fold['ctot'], 0,
-                                  fold['cx'], fold['cf_off'], wh, bh, gb, gz, B, ho,
-                                  wo, grads[i_h], grads[i_h + 1])
+                C.flow_fold_grads(gw, _phys(fold.w), desc.Cout, fold.ctot, 0,
+                                  fold.cx, fold.cf_off, wh, bh, gb, gz, B, ho,
+                                  wo, gwh, gbh)
                 finish(unit)
             return job
 
         # ---- decoder, fine to coarse
-        g_x = None          # gradient w.r.t. dec[i].y from the finer stage
-        g_f = gflows[3]     # total gradient of the flow of this stage
-        g_skip = [None] * 4  # gradient into e[k] from the decoder
+        g_x = None          # gradient w.r.t. this stage's y from the finer stage
+        g_f = gflows[-1]    # total gradient of the flow of this stage
+        g_skip = {}         # encoder layer -> gradient into its output from the decoder
         g_r = g_r16 = None
         head_in_dgrad = False
         g_x16 = g_in16 = None
@@ -413,12 +463,12 @@ class _PredictorFn(torch.autograd.Function):
         # per-block partials of the data gradient's epilogue instead, dvsof_grad_dst_t.head_part:
         # measured 2.58 against 2.53 ms wherever the encoder's weight gradients go -- the
         # shuffles, the extra barrier and the partial stores sit on the data-gradient chain.)
-        for i in (3, 2, 1, 0):
-            lay = dec_l[i]
-            d = lay['desc']
+        for li in reversed(_DEC):
+            lay, (below, skip) = L[li], LAYERS[li].inputs[:2]
+            d = lay.desc
             h, w = C.out_size(d)
-            y = lay['y']
-            pw, pb, pfw, pfb = (po_dec + 4 * i + j for j in range(4))
+            y = lay.y
+            pfw, pfb = LAYERS[li].params[2:]
             head_w = None
             if head_in_dgrad:
                 # the finer stage's data gradient already wrote d/d(pre-activation)
@@ -433,53 +483,49 @@ class _PredictorFn(torch.autograd.Function):
                 gz, gz16 = new(y), tw(y)
                 C.head_bwd(y, params[pfw], g_f, g_x, asrc(lay), act, gz,
                            grads[pfw], grads[pfb], B, h, w, d.Cout, gx16=gz16)
-            fold = lay.get('fold')
-            if fold is not None:
-                fold = dict(fold, w=params[pw], head_idx=po_dec + 4 * (i - 1) + 2)
-            wgrad(d, gz, grads[pw], grads[pb], ('dec', i), gz16, fold, first=head_w)
-            srcs = lay['srcs']
+            fold = lay.fold
+            wgrad(li, gz, gz16, fold, first=head_w)
+            srcs = lay.srcs
             g_in = new(srcs[0][0])
             g_e = new(srcs[1][0])
             dsts = [dict(p=g_in), dict(p=g_e)]
             head_in_dgrad = False
-            if i == 0:
+            lowest = below not in _DEC
+            if lowest:
                 # x = r (last residual output): single consumer -> its dz,
                 # which the residual chain's data gradients read next
-                dsts[0]['actsrc'] = asrc(res_l[-1])
+                dsts[0]['actsrc'] = asrc(L[below])
                 g_r16 = dsts[0]['p16'] = tw(g_in)
             if fold is not None:
                 # cat[x, skip] with the folded weights: g_in already holds the
                 # path through the flow head, which then sees the loss gradient only
-                g_fprev = gflows[i - 1]
-                wf_prev = params[po_dec + 4 * (i - 1) + 2]
+                g_fprev = gflow[below]
+                wf_prev = params[fold.head[0]]
                 # (only the nine-product kernels, dgrad_head_rows > 0.  The general kernels can
                 # fold a head too, conv_epilogue: bf16s 5 146 against 5 234 samples/s without,
                 # bf16 3 941 / 3 912, bf16x3 the same -- their epilogue cannot start its loads
                 # ahead of the K loop's end)
-                if (C.dgrad_fuses_head(fold['desc'])
-                        and C.dgrad_head_rows(fold['desc']) > 0
+                if (C.dgrad_fuses_head(fold.desc)
+                        and C.dgrad_head_rows(fold.desc) > 0
                         and wf_prev.data_ptr() % 16 == 0):
                     # ... and the head below goes into this data gradient's epilogue
-                    # (dvsof_grad_dst_t.head_w): g_in leaves as dec[i-1]'s dz
+                    # (dvsof_grad_dst_t.head_w): g_in leaves as the stage below's dz
                     head_in_dgrad = True
                     g_in16 = tw(g_in)       # (twins mode: the data gradient below reads its bf16 copy)
                     dsts[0].update(head_w=wf_prev, head_gflow=g_fprev,
-                                   actsrc=asrc(dec_l[i - 1]), p16=g_in16)
-                C.conv_dgrad(fold['desc'], fold['w_dg'], gz, dsts, act,
-                             weight16=fold['w_dg16'], gout16=gz16)
-            else:
-                if len(srcs) == 3:
-                    g_fprev = new(srcs[2][0])
-                    dsts.append(dict(p=g_fprev, addend=gflows[i - 1]))
-                C.conv_dgrad(d, wt(lay), gz, dsts, act, weight16=lay['w_dg16'],
-                             gout16=gz16)
+                                   actsrc=asrc(L[below]), p16=g_in16)
+            elif len(srcs) == 3:
+                g_fprev = new(srcs[2][0])
+                dsts.append(dict(p=g_fprev, addend=gflow[below]))
+            C.conv_dgrad(d if fold is None else fold.desc, lay.w_dg, gz, dsts, act,
+                         weight16=lay.w_dg16, gout16=gz16)
             keep.append(gz16)
-            g_skip[3 - i] = g_e
-            if i > 0:
+            g_skip[skip] = g_e
+            if lowest:
+                g_r = g_in
+            else:
                 g_x, g_f = g_in, g_fprev
                 g_x16 = g_in16 if head_in_dgrad else None
-            else:
-                g_r = g_in
         # ---- residual blocks (g_r is already d/d pre-activation)
         gs, gs16 = g_r, g_r16
         # Winograd forms along the chain (dvsof_conv_desc_t.winograd_next /
@@ -497,28 +543,26 @@ class _PredictorFn(torch.autograd.Function):
                 if C.winograd_tile(consumer, 2) == 4 else None
             keep.extend((v, z))
             return v, z
-        for i in reversed(range(NUM_RES)):
-            l1, l2 = res_l[2 * i], res_l[2 * i + 1]
-            pw1, pb1, pw2, pb2 = (po_res + 4 * i + j for j in range(4))
-            wgrad(l2['desc'], gs, grads[pw2], grads[pb2], ('res', i, 2), gs16,
-                  wino_gout=z_pre)
-            g_t, g_t16 = new(l1['y']), tw(l1['y'])
-            v_n, z_n = forms(l2['desc'], l1['desc'])
-            C.conv_dgrad(l2['desc'], wt(l2), gs,
+        for li1, li2 in reversed(_RES):
+            l1, l2 = L[li1], L[li2]
+            wgrad(li2, gs, gs16, wino_gout=z_pre)
+            g_t, g_t16 = new(l1.y), tw(l1.y)
+            v_n, z_n = forms(l2.desc, l1.desc)
+            C.conv_dgrad(l2.desc, l2.w_dg, gs,
                          [dict(p=g_t, actsrc=asrc(l1), p16=g_t16)], act,
-                         weight16=l2['w_dg16'], gout16=gs16, wino_pre=v_pre,
+                         weight16=l2.w_dg16, gout16=gs16, wino_pre=v_pre,
                          wino_next=v_n, wino_next_gout=z_n)
             v_pre, z_pre = v_n, z_n
-            wgrad(l1['desc'], g_t, grads[pw1], grads[pb1], ('res', i, 1), g_t16,
-                  wino_gout=z_pre)
-            below = res_l[2 * i - 1] if i > 0 else enc_l[3]
-            g_prev, g_prev16 = new(below['y']), tw(below['y'])
+            wgrad(li1, g_t, g_t16, wino_gout=z_pre)
+            li0 = LAYERS[li1].inputs[0]     # another block's output, or the encoder's
+            below = L[li0]
+            g_prev, g_prev16 = new(below.y), tw(below.y)
             dst = dict(p=g_prev, addend=gs, actsrc=asrc(below), p16=g_prev16)
-            if i == 0:
-                dst['addend2'] = g_skip[3]      # dec.0's skip into e4
-            v_n, z_n = forms(l1['desc'], below['desc']) if i > 0 else (None, None)
-            C.conv_dgrad(l1['desc'], wt(l1), g_t, [dst], act,
-                         weight16=l1['w_dg16'], gout16=g_t16, wino_pre=v_pre,
+            if li0 in _ENC:
+                dst['addend2'] = g_skip[li0]    # the coarsest decoder stage's skip
+            v_n, z_n = forms(l1.desc, below.desc) if li0 not in _ENC else (None, None)
+            C.conv_dgrad(l1.desc, l1.w_dg, g_t, [dst], act,
+                         weight16=l1.w_dg16, gout16=g_t16, wino_pre=v_pre,
                          wino_next=v_n, wino_next_gout=z_n)
             v_pre, z_pre = v_n, z_n
             keep.extend((gs16, g_t16))
@@ -535,35 +579,34 @@ class _PredictorFn(torch.autograd.Function):
         alone_ = red_ is None or not red_.active()   # (under the exchange marks 2 again: 2.72 vs 2.84 ms)
         n_side = 3 if ctx.module.mfma == 0 and alone_ else 2
         g_grid = None
-        for i in (3, 2, 1, 0):
-            lay = enc_l[i]
-            if i == 0 and ctx.grid_grad:
+        for li in reversed(_ENC):
+            lay, li0 = L[li], LAYERS[li].inputs[0]
+            if li0 == VOXELS and ctx.grid_grad:
                 # gz is d/d(pre-activation) of enc.0 (the layer above applied act'), the
                 # tensor the weight gradient below reads.  Ahead of that weight gradient:
                 # its bucket may be updated as soon as it closes (optim.fuse_into_backward)
-                g_grid = C.first_dgrad(gz, _phys(params[0]), B, Cin, H, W)
-            item = (lay['desc'], gz, grads[2 * i], grads[2 * i + 1], ('enc', i),
-                    gz16)
-            if i >= n_side:
-                wgrad(*item)            # second stream (it is about to run dry)
+                g_grid = C.first_dgrad(gz, _phys(params[LAYERS[li].params[0]]), B, Cin, H, W)
+            if LAYERS[li].unit[1] >= n_side:
+                wgrad(li, gz, gz16)     # second stream (it is about to run dry)
             else:
-                deferred.append(item)   # main stream, after the last data gradient
-            if i == 0:
+                deferred.append((li, gz, gz16))     # main stream, after the last data gradient
+            if li0 == VOXELS:
                 break
-            below = enc_l[i - 1]
-            g_prev, g_prev16 = new(below['y']), tw(below['y'])
-            C.conv_dgrad(lay['desc'], wt(lay), gz,
-                         [dict(p=g_prev, addend=g_skip[i - 1],
+            below = L[li0]
+            g_prev, g_prev16 = new(below.y), tw(below.y)
+            C.conv_dgrad(lay.desc, lay.w_dg, gz,
+                         [dict(p=g_prev, addend=g_skip[li0],
                                actsrc=asrc(below), p16=g_prev16)], act,
-                         weight16=lay['w_dg16'], gout16=gz16)
+                         weight16=lay.w_dg16, gout16=gz16)
             keep.append(gz16)
             gz, gz16 = g_prev, g_prev16
-        for desc, g, gw, gb, unit, g16 in deferred:
+        for li, g, g16 in deferred:
             if side is None:
-                wgrad(desc, g, gw, gb, unit, g16)
+                wgrad(li, g, g16)
             else:
-                C.conv_wgrad(desc, g, gw, gb, g16)
-                finish(unit)
+                gw, gb = (grads[i] for i in LAYERS[li].params[:2])
+                C.conv_wgrad(L[li].desc, g, gw, gb, g16)
+                finish(LAYERS[li].unit)
         if side is not None:
             main.wait_stream(side)
         del keep
@@ -593,30 +636,25 @@ class Predictor(nn.Module):
         self.compute_dtype = compute_dtype
         self.mfma = modes[compute_dtype]
         self.reducer = None      # parallel.GradReducer for data parallelism
-        chans = (in_channels,) + ENC_CH
-        self.enc = nn.ModuleList(
-            _Named(conv=ConvParams(chans[i], chans[i + 1], 3))
-            for i in range(4))
-        self.res = nn.ModuleList(
-            _Named(conv1=ConvParams(512, 512, 3), conv2=ConvParams(512, 512, 3))
-            for _ in range(NUM_RES))
-        dec_in = (512 + 512, 256 + 256 + 2, 128 + 128 + 2, 64 + 64 + 2)
-        self.dec = nn.ModuleList(
-            _Named(conv=ConvParams(dec_in[i], DEC_CH[i], 3),
-                   flow=ConvParams(DEC_CH[i], 2, 1))
-            for i in range(4))
+        # enc.i.conv, res.i.conv1 / conv2, dec.i.conv / flow, created in table order
+        groups = {'enc': {}, 'res': {}, 'dec': {}}
+        self._convs = []        # the ConvParams in param_list() order
+        for l in LAYERS:
+            kind, i, *j = l.unit
+            convs = {'conv%d' % j[0] if j else 'conv':
+                     ConvParams(sum(c or in_channels for c, _ in l.srcs), l.cout, 3)}
+            if len(l.params) == 4:
+                convs['flow'] = ConvParams(l.cout, 2, 1)
+            groups[kind].setdefault(i, {}).update(convs)
+            self._convs += convs.values()
+        for kind, group in groups.items():
+            setattr(self, kind, nn.ModuleList(_Named(**convs) for convs in group.values()))
 
     # Gradient buckets in the order the backward completes them (fine decoder
     # stages first, encoder last): persistent flat buffers that the wgrad
     # kernels write into, that ``p.grad`` views, that the DP reducer
     # all-reduces and that the fused optimizer reads.
-    UNIT_PARAMS = {
-        **{('dec', i): tuple(8 + 4 * NUM_RES + 4 * i + j for j in range(4))
-           for i in range(4)},
-        **{('res', i, 2): (8 + 4 * i + 2, 8 + 4 * i + 3) for i in range(NUM_RES)},
-        **{('res', i, 1): (8 + 4 * i, 8 + 4 * i + 1) for i in range(NUM_RES)},
-        **{('enc', i): (2 * i, 2 * i + 1) for i in range(4)},
-    }
+    UNIT_PARAMS = {l.unit: l.params for l in LAYERS}
     BUCKETS = (
         (('dec', 3), ('dec', 2), ('dec', 1)),
         (('dec', 0),),
@@ -669,7 +707,12 @@ class Predictor(nn.Module):
                         off += params[i].numel()
                 self._bucket_flat.append(
                     torch.empty(off, dtype=torch.float32, device=dev))
-            self._bucket_views = None
+            # every parameter's slice of its bucket, shaped and strided as the parameter
+            self._bucket_views = []
+            for i, p in enumerate(params):
+                b, off = self._bucket_slot[i]
+                self._bucket_views.append(self._bucket_flat[b][off:off + p.numel()]
+                                          .as_strided(p.shape, p.stride()))
         return self._bucket_flat, self._bucket_slot
 
     def attach_bucket_grads(self):
@@ -679,11 +722,7 @@ class Predictor(nn.Module):
         Python's view of what the replay did: the next eager micro-batch of
         the same optimizer step then accumulates into the buckets."""
         params = self.param_list()
-        flats, slot = self._buckets(params)
-        if getattr(self, '_bucket_views', None) is None:
-            self._bucket_views = [
-                flats[slot[i][0]][slot[i][1]:slot[i][1] + p.numel()]
-                .as_strided(p.shape, p.stride()) for i, p in enumerate(params)]
+        self._buckets(params)
         for p, v in zip(params, self._bucket_views):
             if p.grad is None:
                 p.grad = v
@@ -694,18 +733,11 @@ class Predictor(nn.Module):
         A parameter without .grad gets a view of its bucket as .grad; one that
         already has a gradient (micro-batch accumulation,
         reference utils/training.py:156-167) is accumulated into."""
-        flats, slot = self._buckets(params)
-        views, targets, accumulate = [], [], []
-        for i, p in enumerate(params):
-            b, off = slot[i]
-            v = flats[b][off:off + p.numel()].as_strided(p.shape, p.stride())
-            views.append(v)
-            if p.grad is None:
-                targets.append(v)
-                accumulate.append(False)
-            else:
-                targets.append(torch.empty_like(p))
-                accumulate.append(True)
+        flats, _ = self._buckets(params)
+        views = self._bucket_views
+        accumulate = [p.grad is not None for p in params]
+        targets = [torch.empty_like(p) if acc else v
+                   for p, v, acc in zip(params, views, accumulate)]
         remaining = [len(units) for units in self.BUCKETS]
         unit_bucket = {u: b for b, units in enumerate(self.BUCKETS)
                        for u in units}
@@ -755,14 +787,7 @@ class Predictor(nn.Module):
         return targets, finish
 
     def param_list(self):
-        out = []
-        for m in self.enc:
-            out += [m.conv.weight, m.conv.bias]
-        for m in self.res:
-            out += [m.conv1.weight, m.conv1.bias, m.conv2.weight, m.conv2.bias]
-        for m in self.dec:
-            out += [m.conv.weight, m.conv.bias, m.flow.weight, m.flow.bias]
-        return out
+        return [t for m in self._convs for t in (m.weight, m.bias)]
 
     def forward(self, voxels):
         """voxels: float32 [B,C,H,W] (NCHW dense), H and W multiples of 16.
@@ -779,14 +804,10 @@ class Predictor(nn.Module):
 
     def flops_per_sample(self, H, W):
         """Algorithmic forward FLOPs (2*MACs), SURVEY.md section 8d formula."""
-        total, h, w, c = 0, H, W, self.in_channels
-        for co in ENC_CH:
-            h, w = h // 2, w // 2
-            total += 2 * h * w * co * c * 9
-            c = co
-        total += 2 * NUM_RES * 2 * h * w * 512 * 512 * 9
-        cin = (1024, 514, 258, 130)
-        for i, co in enumerate(DEC_CH):
-            h, w = 2 * h, 2 * w
-            total += 2 * h * w * co * cin[i] * 9 + 2 * h * w * 2 * co
+        total = 0
+        for l in LAYERS:
+            scale = 2 if l.up else 1
+            pixels = ((H >> l.shift) * scale // l.stride) * ((W >> l.shift) * scale // l.stride)
+            cin = sum(c or self.in_channels for c, _ in l.srcs)
+            total += 2 * pixels * l.cout * (9 * cin + (2 if len(l.params) == 4 else 0))
         return total

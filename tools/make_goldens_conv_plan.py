@@ -22,8 +22,6 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 NHWC, NCHW = 0, 1
-ENC_CH = (64, 128, 256, 512)
-DEC_CH = (256, 128, 64, 32)
 
 # one value per name, in this order, for every descriptor
 QUERIES = ('tile_id0', 'tile_id1', 'tile_id2', 'generation0', 'generation1', 'generation2',
@@ -39,20 +37,15 @@ def desc(B, H, W, src, Cout, k=3, stride=1, pad=1, up=0, mfma=0, nsrc=None):
 
 
 def predictor_layers(B, H, W, mfma, bins=5):
-    """Every conv layer of the predictor (predictor.py): encoder, residual blocks, decoder
+    """Every conv layer of the predictor (predictor.LAYERS): encoder, residual blocks, decoder
     stages as cat[x, skip, flow] and, as trained, with the flow member folded away."""
-    out, h, w, c, lay = [], H, W, bins, NCHW
-    for cout in ENC_CH:
-        out.append(desc(B, h, w, [(c, lay)], cout, stride=2, mfma=mfma))
-        h, w, c, lay = h // 2, w // 2, cout, NHWC
-    out += [desc(B, h, w, [(512, NHWC)], 512, mfma=mfma)] * 4
-    cx = 512
-    for i, cout in enumerate(DEC_CH):
-        src = [(cx, NHWC), (ENC_CH[3 - i], NHWC)]
-        if i > 0:
-            out.append(desc(B, h, w, src + [(2, NCHW)], cout, up=1, mfma=mfma))
-        out.append(desc(B, h, w, src, cout, up=1, mfma=mfma))
-        h, w, cx = 2 * h, 2 * w, cout
+    from dvs_of_training_framework_amd.predictor import LAYERS
+    out = []
+    for l in LAYERS:
+        src = [(c or bins, lay) for c, lay in l.srcs]
+        for members in (src, src[:2]) if len(src) == 3 else (src,):
+            out.append(desc(B, H >> l.shift, W >> l.shift, members, l.cout, stride=l.stride,
+                            up=l.up, mfma=mfma))
     return out
 
 
