@@ -70,6 +70,11 @@ _SIGNATURES = {
                               _sz, _vp]),
     'dvsof_count_image_batched': (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i,
                                        _i, _vp, _vp]),
+    'dvsof_flow_render_chunk_rows': (_i, [_i, _i]),
+    'dvsof_flow_render_workspace_bytes': (_sz, [_i]),
+    'dvsof_flow_render_stats': (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
+    'dvsof_flow_render': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _sz,
+                               _vp, _vp]),
     'dvsof_event_windows': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _i64, _i64, _vp]),

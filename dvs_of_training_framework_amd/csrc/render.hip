@@ -1,0 +1,312 @@
+// Predicted flow as a colour image on the device (docs/RENDER_SPEC.md).
+//
+// Replaces (reference paths): flow2img utils/visualization.py:5-18 (norm,
+// arctan2, cv2.normalize, cv2.cvtColor: four passes over host copies of every
+// pyramid level of every sample) and the canvas assembly of visualize.py:
+// put_image / visualize_prediction / visualize_predictions / join_images
+// (:37-127).
+//
+// Two launches over one host-built item table, whatever the batch and the
+// number of levels: per-item min / max / non-finite count, then one workgroup
+// per item that reduces the few partials of its image and writes BGR bytes
+// straight into the mosaic.  Both are HBM-bound and small.  The arithmetic is
+// pinned operation by operation by the spec; this file relies on
+// -ffp-contract=off.
+#include "common.h"
+
+static_assert(sizeof(dvsof_render_item_t) == 64, "items are 64 bytes (visualization.py packs them as such)");
+static_assert(sizeof(dvsof_render_stats_t) == 16, "stats rows are 16 bytes (visualization.py reads them as such)");
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int kMaxChunks = DVSOF_RENDER_MAX_CHUNKS;
+constexpr int kMaxSide = 32767;
+constexpr int kChunkPixels = 2048;  // 8 per thread: enough to hide the launch of a workgroup
+
+__device__ __forceinline__ bool finite2(float a, float b)
+{
+    return __builtin_isfinite(a) && __builtin_isfinite(b);
+}
+
+// ---------------------------------------------------------------------------
+// Launch 1.  mag >= +0 for finite components (never NaN, +inf on overflow), so
+// fminf / fmaxf select the same bits in any order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void flow_render_stats_kernel(
+    const dvsof_render_item_t *__restrict__ items, dvsof_render_stats_t *__restrict__ part)
+{
+    const dvsof_render_item_t it = items[blockIdx.x];
+    const size_t plane = (size_t)it.h * it.w;
+    const float *fx = (const float *)it.src + (size_t)it.row0 * it.w, *fy = fx + plane;
+    const int n = it.rows * it.w;  // <= 32767^2 < 2^31
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    int bad = 0;
+    for (int p = threadIdx.x; p < n; p += NT) {
+        const float x = fx[p], y = fy[p];
+        if (finite2(x, y)) {
+            const float mag = sqrtf(x * x + y * y);
+            lo = fminf(lo, mag);
+            hi = fmaxf(hi, mag);
+        } else {
+            ++bad;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = fminf(lo, __shfl_down(lo, off, kWave));
+        hi = fmaxf(hi, __shfl_down(hi, off, kWave));
+        bad += __shfl_down(bad, off, kWave);
+    }
+    __shared__ float sh_lo[NT / kWave], sh_hi[NT / kWave];
+    __shared__ int sh_bad[NT / kWave];
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        sh_lo[threadIdx.x / kWave] = lo;
+        sh_hi[threadIdx.x / kWave] = hi;
+        sh_bad[threadIdx.x / kWave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < NT / kWave; ++k) {
+            lo = fminf(lo, sh_lo[k]);
+            hi = fmaxf(hi, sh_hi[k]);
+            bad += sh_bad[k];
+        }
+        part[(size_t)it.image * kMaxChunks + it.chunk] = dvsof_render_stats_t{lo, hi, bad, 0};
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Launch 2.  Three bytes per pixel: a row segment of the destination starts
+// at an arbitrary byte, so a row is cut into a head of (address & 3) pixels,
+// after which 3 * head more bytes make the address a multiple of 4, groups of
+// 4 pixels = three aligned dwords, and a tail of fewer than 4 pixels.  Head
+// and tail go out as bytes.  Consecutive threads take consecutive groups: a
+// wave's dword stores cover 768 contiguous bytes.
+// ---------------------------------------------------------------------------
+struct Bgr {
+    uint32_t b, g, r;
+};
+
+// OpenCV's float HSV -> BGR for 8-bit input, hue range 180, S = 255
+__device__ __forceinline__ Bgr hsv2bgr(int h, int V)
+{
+    const int sector = (h / 30) % 6;
+    const float f = (float)(h % 30) / 30.0f;
+    const float v = (float)V / 255.0f;
+    const float tab[4] = {v, 0.f, v * (1.f - f), v * f};
+    // {b, g, r} indices into tab, two bits each
+    constexpr uint32_t kSector[6] = {1 | 3 << 2 | 0 << 4, 1 | 0 << 2 | 2 << 4, 3 | 0 << 2 | 1 << 4,
+                                     0 | 2 << 2 | 1 << 4, 0 | 1 << 2 | 3 << 4, 2 | 1 << 2 | 0 << 4};
+    const uint32_t s = kSector[sector];
+    auto pick = [&](uint32_t k) -> float { return k == 0 ? tab[0] : (k == 1 ? tab[1] : (k == 2 ? tab[2] : tab[3])); };
+    Bgr c;
+    c.b = (uint32_t)rintf(pick(s & 3) * 255.0f);
+    c.g = (uint32_t)rintf(pick((s >> 2) & 3) * 255.0f);
+    c.r = (uint32_t)rintf(pick((s >> 4) & 3) * 255.0f);
+    return c;
+}
+
+struct FlowColour {
+    const float *fx, *fy;  // the image's planes
+    float lo, scale, clamp;  // clamp > 0: caller-given scale
+    __device__ __forceinline__ Bgr operator()(size_t p) const
+    {
+        const float x = fx[p], y = fy[p];
+        if (!finite2(x, y)) return Bgr{0u, 0u, 0u};
+        float mag = sqrtf(x * x + y * y);
+        if (clamp > 0.f) mag = fminf(mag, clamp);
+        const int V = (int)truncf(fminf((mag - lo) * scale, 255.0f));
+        const float a = (atan2f(y, x) + 3.14159265358979323846f) * (float)(180.0 / 3.14159265358979323846 / 2.0);
+        return hsv2bgr((int)truncf(a), V);
+    }
+};
+struct GreyColour {
+    const uint8_t *src;
+    __device__ __forceinline__ Bgr operator()(size_t p) const
+    {
+        const uint32_t g = src[p];
+        return Bgr{g, g, g};
+    }
+};
+struct NoColour {
+    __device__ __forceinline__ Bgr operator()(size_t) const { return Bgr{0u, 0u, 0u}; }
+};
+
+template <typename Colour>
+__device__ __forceinline__ void emit_rows(const dvsof_render_item_t &it, uint8_t *__restrict__ canvas,
+                                          const Colour &colour)
+{
+    const int units = (it.w + 3) / 4 + 1;  // per row: the head, then groups (the last one may be the tail)
+    const int total = it.rows * units;     // < 2^15 * 2^13
+    for (int k = threadIdx.x; k < total; k += NT) {
+        const int r = it.row0 + k / units, u = k % units;
+        uint8_t *row = canvas + it.dst_offset + (int64_t)(it.y0 + r) * it.dst_stride + 3 * (int64_t)it.x0;
+        const int head = min((int)((uintptr_t)row & 3), it.w);
+        const int p0 = u == 0 ? 0 : head + 4 * (u - 1);
+        const int p1 = u == 0 ? head : min(p0 + 4, it.w);
+        if (p0 >= p1) continue;
+        const size_t src = (size_t)r * it.w;
+        if (p1 - p0 == 4) {  // u >= 1: row + 3 * p0 is a multiple of 4
+            const Bgr c0 = colour(src + p0), c1 = colour(src + p0 + 1), c2 = colour(src + p0 + 2),
+                      c3 = colour(src + p0 + 3);
+            uint32_t *q = (uint32_t *)(row + 3 * (size_t)p0);
+            q[0] = c0.b | c0.g << 8 | c0.r << 16 | c1.b << 24;
+            q[1] = c1.g | c1.r << 8 | c2.b << 16 | c2.g << 24;
+            q[2] = c2.r | c3.b << 8 | c3.g << 16 | c3.r << 24;
+        } else {
+            for (int p = p0; p < p1; ++p) {
+                const Bgr c = colour(src + p);
+                row[3 * (size_t)p + 0] = (uint8_t)c.b;
+                row[3 * (size_t)p + 1] = (uint8_t)c.g;
+                row[3 * (size_t)p + 2] = (uint8_t)c.r;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT) void flow_render_kernel(
+    const dvsof_render_item_t *__restrict__ items, const dvsof_render_stats_t *__restrict__ part,
+    const float *__restrict__ max_magnitude, uint8_t *__restrict__ canvas,
+    dvsof_render_stats_t *__restrict__ stats)
+{
+    const dvsof_render_item_t it = items[blockIdx.x];
+    if (it.kind == DVSOF_RENDER_FILL) {
+        emit_rows(it, canvas, NoColour{});
+        return;
+    }
+    if (it.kind == DVSOF_RENDER_FRAME) {
+        emit_rows(it, canvas, GreyColour{(const uint8_t *)it.src});
+        return;
+    }
+    // the partials of this image: at most 64 uniform loads, the same in every lane
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    int bad = 0;
+    const dvsof_render_stats_t *mine = part + (size_t)it.image * kMaxChunks;
+    for (int c = 0; c < it.chunks; ++c) {
+        lo = fminf(lo, mine[c].lo);
+        hi = fmaxf(hi, mine[c].hi);
+        bad += mine[c].nonfinite;
+    }
+    if (it.chunk == 0 && threadIdx.x == 0) stats[it.image] = dvsof_render_stats_t{lo, hi, bad, 0};
+    const float m = max_magnitude ? max_magnitude[it.image] : 0.f;
+    FlowColour colour;
+    colour.fx = (const float *)it.src;
+    colour.fy = colour.fx + (size_t)it.h * it.w;
+    colour.clamp = m > 0.f ? m : 0.f;
+    if (m > 0.f) {
+        lo = 0.f;
+        hi = m;
+    }
+    colour.lo = lo;
+    colour.scale = hi - lo > 0.f ? 255.0f / (hi - lo) : 0.f;
+    emit_rows(it, canvas, colour);
+}
+
+int chunk_rows(int h, int w)
+{
+    if (h < 1 || w < 1 || h > kMaxSide || w > kMaxSide) return 0;
+    const int by_pixels = (kChunkPixels + w - 1) / w, by_count = (h + kMaxChunks - 1) / kMaxChunks;
+    return by_pixels > by_count ? by_pixels : by_count;
+}
+
+// The source side of the table: n_flow flow items, the chunks of an image
+// together, in order, tiling its rows; every image exactly once.
+bool bad_flow_items(const dvsof_render_item_t *items, int n_flow, int n_images)
+{
+    if (n_flow < 0 || n_images < 0 || n_images > n_flow) return true;
+    if (n_flow == 0) return false;
+    if (!items) return true;
+    uint64_t *seen = new uint64_t[((size_t)n_images + 63) / 64]();
+    bool bad = false;
+    int images = 0;
+    for (int i = 0; i < n_flow && !bad; ++i) {
+        const dvsof_render_item_t &it = items[i];
+        bad = it.kind != DVSOF_RENDER_FLOW || !it.src || it.h < 1 || it.w < 1 || it.h > kMaxSide ||
+              it.w > kMaxSide || it.rows < 1 || it.row0 < 0 || it.row0 > it.h - it.rows || it.image < 0 ||
+              it.image >= n_images || it.chunks < 1 || it.chunks > kMaxChunks || it.chunk < 0 ||
+              it.chunk >= it.chunks;
+        if (bad) break;
+        if (it.chunk == 0) {
+            uint64_t &word = seen[it.image / 64];
+            bad = it.row0 != 0 || (word >> (it.image % 64) & 1u);
+            word |= (uint64_t)1 << (it.image % 64);
+            ++images;
+        } else if (i == 0) {
+            bad = true;
+        } else {
+            const dvsof_render_item_t &prev = items[i - 1];
+            bad = prev.image != it.image || prev.chunk + 1 != it.chunk || prev.chunks != it.chunks ||
+                  prev.src != it.src || prev.h != it.h || prev.w != it.w || prev.row0 + prev.rows != it.row0;
+        }
+        if (!bad && it.chunk == it.chunks - 1) bad = it.row0 + it.rows != it.h;
+        if (!bad && it.chunk != it.chunks - 1) bad = i + 1 >= n_flow;  // the image's last chunk is missing
+    }
+    delete[] seen;
+    return bad || images != n_images;
+}
+
+// The destination side: every item inside its row and inside the canvas.
+bool bad_destinations(const dvsof_render_item_t *items, int n_items, int n_flow, size_t canvas_bytes)
+{
+    for (int i = 0; i < n_items; ++i) {
+        const dvsof_render_item_t &it = items[i];
+        if ((it.kind == DVSOF_RENDER_FLOW) != (i < n_flow)) return true;
+        if (it.kind != DVSOF_RENDER_FLOW && it.kind != DVSOF_RENDER_FRAME && it.kind != DVSOF_RENDER_FILL) return true;
+        if (it.kind == DVSOF_RENDER_FRAME && !it.src) return true;
+        if (it.h < 1 || it.w < 1 || it.h > kMaxSide || it.w > kMaxSide || it.rows < 1 || it.row0 < 0 ||
+            it.row0 > it.h - it.rows)
+            return true;
+        if (it.x0 < 0 || it.y0 < 0 || it.dst_offset < 0 || it.dst_stride < 3 * ((int64_t)it.x0 + it.w)) return true;
+        // the last byte of the item's last row (all terms < 2^63: stride is checked below)
+        if (it.dst_stride > (int64_t)1 << 40 || (uint64_t)it.dst_offset > canvas_bytes) return true;
+        const uint64_t end = (uint64_t)it.dst_offset + (uint64_t)((int64_t)it.y0 + it.h - 1) * (uint64_t)it.dst_stride +
+                             3u * ((uint64_t)it.x0 + it.w);
+        if (end > canvas_bytes) return true;
+    }
+    return false;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dvsof_flow_render_chunk_rows(int h, int w) { return chunk_rows(h, w); }
+
+size_t dvsof_flow_render_workspace_bytes(int n_images)
+{
+    if (n_images < 1) return 0;
+    return sizeof(dvsof_render_stats_t) * (size_t)n_images * kMaxChunks;
+}
+
+int dvsof_flow_render_stats(const dvsof_render_item_t *items, const dvsof_render_item_t *items_dev, int n_flow,
+                            int n_images, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (bad_flow_items(items, n_flow, n_images)) return DVSOF_EINVAL;
+    if (n_flow == 0) return DVSOF_OK;
+    if (!items_dev) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < dvsof_flow_render_workspace_bytes(n_images)) return DVSOF_ENOSPACE;
+    hipLaunchKernelGGL(flow_render_stats_kernel, dim3((unsigned)n_flow), dim3(NT), 0, as_stream(stream), items_dev,
+                       (dvsof_render_stats_t *)workspace);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int dvsof_flow_render(const dvsof_render_item_t *items, const dvsof_render_item_t *items_dev, int n_items, int n_flow,
+                      int n_images, const float *max_magnitude, const void *workspace, size_t workspace_bytes,
+                      uint8_t *canvas, size_t canvas_bytes, dvsof_render_stats_t *stats, void *stream)
+{
+    if (n_items < 0 || n_flow > n_items || bad_flow_items(items, n_flow, n_images)) return DVSOF_EINVAL;
+    if (n_items == 0) return DVSOF_OK;
+    if (!items || !items_dev || !canvas || (n_flow > 0 && !stats)) return DVSOF_EINVAL;
+    if (bad_destinations(items, n_items, n_flow, canvas_bytes)) return DVSOF_EINVAL;
+    if (n_flow > 0 && (!workspace || workspace_bytes < dvsof_flow_render_workspace_bytes(n_images)))
+        return DVSOF_ENOSPACE;
+    hipLaunchKernelGGL(flow_render_kernel, dim3((unsigned)n_items), dim3(NT), 0, as_stream(stream), items_dev,
+                       (const dvsof_render_stats_t *)workspace, max_magnitude, canvas, stats);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+}  // extern "C"

@@ -233,6 +233,15 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         dest='synthetic_validation_batches', default=0, type=int,
                         help='with --synthetic: validate on this many seeded batches '
                              '(seeds disjoint from the training batches\')')
+    parser.add_argument('--visualization-period', dest='visualization_period',
+                        default=0, type=int,
+                        help='every this many optimizer steps render the first '
+                             '--visualization-samples samples of the validation data '
+                             '(frames on top, the predicted flow pyramid below; '
+                             'docs/RENDER_SPEC.md) into <model>/visualization/step_N/ and, '
+                             'where the logger takes images, into the log; 0: off')
+    parser.add_argument('--visualization-samples', dest='visualization_samples',
+                        default=4, type=int)
     parser.add_argument('--sync-checkpoints', dest='sync_checkpoints',
                         action='store_true',
                         help='write checkpoints on the training thread (state_dict() + '

@@ -386,6 +386,97 @@ int dvsof_count_image_batched(const int64_t *x, const int64_t *y,
                               void *stream);
 
 /* ------------------------------------------------------------------ *
+ * Rendering (csrc/render.hip, docs/RENDER_SPEC.md): predicted flow as a
+ * colour image on the device.  Replaces flow2img, utils/visualization.py:5-18
+ * (four numpy passes and two cv2 calls per sample on the host) and the
+ * put_image / join_images layout of visualize.py:37-127.  Two launches per
+ * call whatever the number of images: per-chunk min / max, then colouring.
+ * ------------------------------------------------------------------ */
+
+#define DVSOF_RENDER_FLOW 0   /* src: float32 [2,h,w], x plane then y plane */
+#define DVSOF_RENDER_FRAME 1  /* src: uint8 [h,w] grey, replicated to B, G, R */
+#define DVSOF_RENDER_FILL 2   /* no src: the rectangle is set to 0 */
+#define DVSOF_RENDER_MAX_CHUNKS 64
+
+/*
+ * One workgroup's work: rows [row0, row0 + rows) of an h x w source, written
+ * as BGR bytes at pixel (x0, y0 + row0) of a destination whose first byte is
+ * canvas + dst_offset and whose rows are dst_stride bytes apart.  64 bytes.
+ * The table is built on the host (visualization.py) and must be readable at
+ * BOTH addresses the entry points take: `items` by the host (it is validated
+ * there), `items_dev` by the kernels (the caller's one upload of the same
+ * bytes).
+ * Flow items come first in the table.  The chunks of one image stand together
+ * in ascending order, chunk 0 first, and tile its rows exactly; an image has
+ * at most DVSOF_RENDER_MAX_CHUNKS of them (dvsof_flow_render_chunk_rows keeps
+ * to that).  Every image 0 .. n_images-1 occurs exactly once.  Items must not
+ * overlap in the destination (not checked: the table is the caller's layout).
+ */
+typedef struct {
+    const void *src;
+    int64_t dst_offset; /* bytes from `canvas` to the destination's pixel (0,0) */
+    int64_t dst_stride; /* bytes per destination row, >= 3 * (x0 + w) */
+    int32_t kind;       /* DVSOF_RENDER_* */
+    int32_t image;      /* flow: row of stats / max_magnitude; else ignored */
+    int32_t h, w;       /* the source (flow, frame) or the rectangle (fill) */
+    int32_t x0, y0;     /* where its pixel (0,0) lands in the destination */
+    int32_t row0, rows; /* the rows of the source this item covers */
+    int32_t chunk, chunks; /* flow: this item's place among the image's items */
+} dvsof_render_item_t;
+
+/* per image, 16 bytes: over the pixels whose two components are finite
+ * (lo = +inf, hi = -inf when there is none) */
+typedef struct {
+    float lo, hi;       /* min / max of sqrtf(fx*fx + fy*fy) */
+    int32_t nonfinite;  /* pixels with a NaN or an infinite component */
+    int32_t reserved;
+} dvsof_render_stats_t;
+
+/* Rows per item for an h x w source: about 2048 pixels, and at most
+ * DVSOF_RENDER_MAX_CHUNKS items per image.  0 for h or w outside [1, 32767]. */
+int dvsof_flow_render_chunk_rows(int h, int w);
+/* Scratch for the per-chunk partials of n_images flow images. */
+size_t dvsof_flow_render_workspace_bytes(int n_images);
+
+/*
+ * Launch 1: one workgroup per flow item (the first n_flow entries of the
+ * table) writes {lo, hi, nonfinite} of its rows into `workspace`.  Min and
+ * max are exact in any order and the count is an integer: same input, same
+ * bits.  n_flow == 0: nothing to do.
+ */
+int dvsof_flow_render_stats(const dvsof_render_item_t *items,
+                            const dvsof_render_item_t *items_dev, int n_flow,
+                            int n_images, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/*
+ * Launch 2: one workgroup per item of the whole table.  A flow item reduces
+ * the partials of its image (chunk 0 also stores them to stats[image]), then
+ * colours its pixels (docs/RENDER_SPEC.md section 2):
+ *   V = trunc(min((mag - lo) * (hi - lo > 0 ? 255 / (hi - lo) : 0), 255))
+ *   hue = trunc((atan2f(fy, fx) + pi) * 180 / pi / 2), S = 255, HSV -> BGR by
+ *   OpenCV's float formula, a pixel with a non-finite component black.
+ *   max_magnitude  float32[n_images] or NULL.  m > 0: lo = 0, hi = m, mag
+ *                  clamped to m (one colour scale for several images);
+ *                  m <= 0 or NULL: the image's own min / max.
+ *   canvas         the byte range every destination lies in
+ *   stats          dvsof_render_stats_t[n_images]: always the image's OWN
+ *                  min / max; the caller may copy it back once
+ * Stream order after dvsof_flow_render_stats is the only synchronisation.  No
+ * memset: what no flow or frame item covers is the caller's to cover with
+ * fill items.  DVSOF_EINVAL, before any launch: null pointers, sizes outside
+ * [1, 32767], a malformed table (see dvsof_render_item_t), an item reaching
+ * outside its destination row or outside the canvas; DVSOF_ENOSPACE: the
+ * workspace is missing or too small.
+ */
+int dvsof_flow_render(const dvsof_render_item_t *items,
+                      const dvsof_render_item_t *items_dev, int n_items,
+                      int n_flow, int n_images, const float *max_magnitude,
+                      const void *workspace, size_t workspace_bytes,
+                      uint8_t *canvas, size_t canvas_bytes,
+                      dvsof_render_stats_t *stats, void *stream);
+
+/* ------------------------------------------------------------------ *
  * Device-resident event sequence -> wire-format batch
  * (docs/SEQUENCE_SPEC.md)
  * ------------------------------------------------------------------ */

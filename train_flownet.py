@@ -3,7 +3,9 @@
 (train_flownet.py:31-217): model plugin -> optimizer + LambdaLR ->
 ``init_losses`` -> ``train``.  Additions: one process per GPU under torchrun
 (RCCL gradient all-reduce overlapped with backward), ``--synthetic`` and
-``--sequence DIR`` (one recorded sequence kept on the device).
+``--sequence DIR`` (one recorded sequence kept on the device),
+``--visualization-period N`` (pictures of the predicted flow on the
+validation data every N steps; docs/RENDER_SPEC.md).
 
 Checkpoints, resume and validation are the reference's (:142-217) through this
 package's ``serializer.Serializer`` and ``hooks``: a run continues from the
@@ -33,7 +35,7 @@ from dvs_of_training_framework_amd.options import (
     add_train_arguments, add_preprocessed_dataset_arguments, guard_requested,
     resolve_step_guard, validate_train_args)
 from dvs_of_training_framework_amd.hooks import SerializationHook, \
-    ValidationHook
+    ValidationHook, VisualizationHook
 from dvs_of_training_framework_amd.serializer import Serializer
 from dvs_of_training_framework_amd.timer import EventTimer, FakeTimer
 from dvs_of_training_framework_amd.training import HostGuard, \
@@ -289,6 +291,23 @@ def make_validation_loader(args, device):
     return None
 
 
+def add_visualization(args, hooks, periodic, model, device, logger, losses, rank):
+    """--visualization-period N > 0: a ``VisualizationHook`` on its own pass
+    over the validation data every N optimizer steps.  0 constructs nothing."""
+    if getattr(args, 'visualization_period', 0) <= 0:
+        return
+    loader = make_validation_loader(args, device)
+    if loader is None:
+        raise SystemExit('--visualization-period needs validation data '
+                         '(--validation-sequence, or --synthetic-validation-batches '
+                         'with --synthetic)')
+    hooks['visualization'] = VisualizationHook(
+        model, device, loader, logger, losses, args.loss_weights, args.is_raw, args,
+        args.model / 'visualization', samples=args.visualization_samples, rank=rank)
+    periodic['visualization'] = make_hook_periodic(hooks['visualization'],
+                                                   args.visualization_period)
+
+
 def restore_loader(loader, state, rank, world, global_step, args):
     """Position ``loader`` from the checkpoint's ``loader_state`` (a list
     indexed by rank); a checkpoint without one (the reference's) positions by
@@ -400,6 +419,7 @@ def main(argv=None):
     elif not args.skip_validation:
         note('no validation data (--validation-sequence, or '
              '--synthetic-validation-batches with --synthetic): validation is skipped')
+    add_visualization(args, hooks, periodic, model, device, logger, losses, rank)
 
     try:
         if not resume:
