@@ -70,6 +70,14 @@ _SIGNATURES = {
                               _sz, _vp]),
     'dvsof_count_image_batched': (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i,
                                        _i, _vp, _vp]),
+    'dvsof_count_image_polarity_batched': (_i, [_vp, _vp, _vp, _i64, _vp, _i,
+                                                _i, _i, _i, _i, _vp, _vp]),
+    'dvsof_eval_panels_workspace_bytes': (_sz, [_i]),
+    'dvsof_eval_panels_stats': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp,
+                                     _sz, _vp]),
+    'dvsof_eval_panels': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f,
+                               _f, _i, _vp, _sz, _vp, _sz, _i64, _i64, _vp,
+                               _vp]),
     'dvsof_flow_render_chunk_rows': (_i, [_i, _i]),
     'dvsof_flow_render_workspace_bytes': (_sz, [_i]),
     'dvsof_flow_render_stats': (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),

@@ -1,5 +1,6 @@
 // Evaluation on the device: ground-truth flow propagation, masked endpoint
-// error and the batched event mask (docs/EVAL_SPEC.md).
+// error and the batched event mask (docs/EVAL_SPEC.md), the latter also by
+// polarity for the evaluation pictures (docs/EVAL_PANELS_SPEC.md section 1).
 //
 // Replaces (reference paths): estimate_corresponding_gt_flow / prop_flow
 // utils/eval.py:53-184 (a dozen cv2.remap calls over full-resolution maps per
@@ -210,6 +211,29 @@ __global__ __launch_bounds__(NT) void count_image_batched_kernel(
     }
 }
 
+// The same with the polarity: plane 0 of a frame counts p > 0, plane 1 the rest.
+__global__ __launch_bounds__(NT) void count_image_polarity_batched_kernel(
+    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const int64_t *__restrict__ pol,
+    int64_t n, const int64_t *__restrict__ begin, int F, int y0, int x0, int h, int w,
+    uint32_t *__restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * NT;
+    const int64_t first = begin[0], last = begin[F];
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
+        if (e < first || e >= last) continue;
+        int lo = 0, hi = F;  // begin[lo] <= e < begin[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (begin[mid] <= e) lo = mid; else hi = mid;
+        }
+        const int64_t xi = x[e] - x0, yi = y[e] - y0;
+        if (xi >= 0 && xi < w && yi >= 0 && yi < h) {
+            const size_t plane = (size_t)lo * 2 + (pol[e] > 0 ? 0 : 1);
+            atomicAdd(&out[(plane * h + (size_t)yi) * w + (size_t)xi], 1u);
+        }
+    }
+}
+
 bool bad_window(int H, int W, int y0, int x0, int h, int w)
 {
     return H < 1 || W < 1 || H > kMaxSide || W > kMaxSide || y0 < 0 || x0 < 0 || h < 1 || w < 1 ||
@@ -286,6 +310,25 @@ int dvsof_count_image_batched(const int64_t *x, const int64_t *y, int64_t n_even
     hipLaunchKernelGGL(count_image_batched_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)),
                        dim3(NT), 0, as_stream(stream), x, y, n_events, frame_event_begin, F, y0, x0, h,
                        w, out);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int dvsof_count_image_polarity_batched(const int64_t *x, const int64_t *y, const int64_t *p,
+                                       int64_t n_events, const int64_t *frame_event_begin, int F,
+                                       int y0, int x0, int h, int w, uint32_t *out, void *stream)
+{
+    if (F < 0 || n_events < 0) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (!out || !frame_event_begin || y0 < 0 || x0 < 0 || h < 1 || w < 1 || h > kMaxSide || w > kMaxSide)
+        return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !p)) return DVSOF_EINVAL;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(out, 0u, sizeof(uint32_t) * (size_t)F * 2 * h * w, as_stream(stream)));
+    if (n_events == 0) return DVSOF_OK;
+    const int64_t blocks = (n_events + NT - 1) / NT;
+    hipLaunchKernelGGL(count_image_polarity_batched_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)),
+                       dim3(NT), 0, as_stream(stream), x, y, p, n_events, frame_event_begin, F, y0, x0,
+                       h, w, out);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }

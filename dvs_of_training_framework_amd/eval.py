@@ -190,6 +190,30 @@ def count_image_batched(x, y, frame_event_begin, shape, box=None):
     return out
 
 
+def count_image_polarity_batched(x, y, p, frame_event_begin, shape, box=None):
+    """``count_image_batched`` by polarity: p is the int64 wire polarity
+    column.  -> int32 device tensor [F,2,h,w] holding the uint32 counts, plane
+    0 the events with p > 0, plane 1 those with p <= 0; the planes add up to
+    ``count_image_batched`` of the same columns."""
+    _lib.require_cuda(x, y, p)
+    x, y, p = x.contiguous(), y.contiguous(), p.contiguous()
+    assert x.dtype == y.dtype == p.dtype == torch.long \
+        and x.numel() == y.numel() == p.numel()
+    begin = torch.as_tensor(frame_event_begin, dtype=torch.long) \
+        .to(x.device).contiguous()
+    F = begin.numel() - 1
+    h, w = int(shape[0]), int(shape[1])
+    y0, x0 = (0, 0) if box is None else (int(box[0]), int(box[1]))
+    if box is not None:
+        assert (int(box[2]), int(box[3])) == (h, w), (box, shape)
+    out = torch.empty(max(F, 0), 2, h, w, dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().dvsof_count_image_polarity_batched(
+        x.data_ptr(), y.data_ptr(), p.data_ptr(), x.numel(), begin.data_ptr(),
+        F, y0, x0, h, w, out.data_ptr(), _lib.stream()),
+        'dvsof_count_image_polarity_batched')
+    return out
+
+
 def _upload_maps(a, device):
     a = np.asarray(a)
     if a.dtype not in (np.float32, np.float64):

@@ -1,12 +1,14 @@
 """The two hooks of the reference's training script (utils/hooks/):
 ``SerializationHook`` checkpoints, ``ValidationHook`` runs a validation pass;
-``VisualizationHook`` (an addition) draws what the model predicts.
+``VisualizationHook`` (an addition) draws what the model predicts and
+``EvaluationHook`` (another) measures it against ground truth.
 ``training.train`` calls ``hook(step, samples_passed)`` after an optimizer
 step and times each under its dictionary name."""
 from contextlib import contextmanager
 from copy import deepcopy
 from pathlib import Path
 
+import numpy as np
 import torch
 import yaml
 
@@ -92,6 +94,132 @@ class ValidationHook:
         with model_left_as_found(self.model):
             validate(self.model, self.device, self.loader, samples, self.logger,
                      self.losses, weights=self.weights, is_raw=self.is_raw)
+
+
+def evaluation_frames(image_ts, gt_timestamps, last_event_time, step=1):
+    """The frames an evaluation runs over (test.py:85-100 of the reference
+    with the grid's start and stop unset) -> (frames [(start, stop)], the index
+    of every frame's closing image).  The range begins at the first image (not
+    before the first ground-truth timestamp) and stops at min(last event time,
+    gt timestamps[-2]); a frame spans ``step`` images:
+    zip(image_ts[b : e - step], image_ts[b + step : e])."""
+    image_ts = np.asarray(image_ts, np.float64).reshape(-1)
+    gt_timestamps = np.asarray(gt_timestamps, np.float64).reshape(-1)
+    step = int(step)
+    if step < 1:
+        raise ValueError(f'a frame spans at least one image, not {step}')
+    start = max(image_ts[0], gt_timestamps[0])
+    stop = min(float(last_event_time), gt_timestamps[-2])
+    b, e = (int(i) for i in np.searchsorted(image_ts, [start, stop]))
+    n = max(e - step - b, 0)
+    frames = list(zip(image_ts[b:b + n].tolist(), image_ts[b + step:b + step + n].tolist()))
+    return frames, list(range(b + step, b + step + n))
+
+
+def picture_indices(n_frames, pictures):
+    """Which frames are drawn: ``(k * F) // pictures``, k = 0 .. pictures - 1
+    (at most one picture per frame)."""
+    pictures = max(min(int(pictures), int(n_frames)), 0)
+    return [(k * n_frames) // pictures for k in range(pictures)]
+
+
+class _Crop:
+    """A box crop as ``testing.fold_box`` reads it (utils/data.py:24-42)."""
+
+    def __init__(self, box):
+        self.box = [int(b) for b in box]
+
+
+class EvaluationHook:
+    """Endpoint error of the live weights against ground truth
+    (``testing.evaluate_frames`` on a device-resident ``FrameSequence``, events
+    and ground truth cropped centrally to ``shape``), and for ``pictures``
+    frames the four panels of ``visualization.eval_panels``.  Logs
+    ``Evaluation/mean AEE`` and ``Evaluation/mean %AEE`` (x 100, as the
+    reference's test.py does), writes ``<directory>/step_<N>/<k>.png`` + ``.yml``
+    and hands the pictures to ``logger.add_image`` where there is one.  Only
+    rank 0 evaluates, and nothing in here is a collective.  The model is left
+    as it was found.
+
+    gt: dict with 'timestamps', 'x_flow_dist', 'y_flow_dist' on the clock of
+    the sequence's image timestamps."""
+
+    def __init__(self, model, sequence, gt, logger, shape, directory, frame_step=1,
+                 pictures=4, is_car=False, rank=0, batch_size=8):
+        self.model, self.sequence, self.gt, self.logger = model, sequence, gt, logger
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.directory, self.rank = Path(directory), rank
+        self.is_car, self.batch_size = bool(is_car), int(batch_size)
+        self.frames = self.closing = self.chosen = ()
+        if rank != 0:
+            return
+        if getattr(model, 'prefix_length', 0) or getattr(model, 'suffix_length', 0):
+            raise ValueError('the evaluation runs the model on one window per frame: '
+                             'prefix_length = suffix_length = 0')
+        from .sequence import central_box
+        self.crop = _Crop(central_box(sequence.shape, self.shape))
+        last = sequence.t[-1] if len(sequence) else -np.inf
+        self.frames, self.closing = evaluation_frames(sequence.image_ts, gt['timestamps'],
+                                                      last, frame_step)
+        if not self.frames:
+            raise ValueError('no frame of the validation sequence lies inside the ground truth')
+        self.chosen = picture_indices(len(self.frames), pictures)
+
+    def evaluate(self):
+        """-> (result rows of every frame, [(frame, picture, its statistics)])
+        with the model as it stands; pictures and statistics on the device."""
+        from . import testing, visualization as vis
+        from .of import OpticalFlow
+        of = OpticalFlow.from_model(self.model, self.shape)
+        y0, x0, h, w = self.crop.box
+        drawn = []
+
+        def observer(first, pred, gt_u, gt_v, max_row, count2):
+            mine = [i for i in self.chosen if first <= i < first + pred.shape[0]]
+            if not mine:
+                return
+            local = torch.tensor([i - first for i in mine], device=pred.device)
+            closing = torch.tensor([self.closing[i] for i in mine], device=pred.device)
+            grey = self.sequence.images[closing, y0:y0 + h, x0:x0 + w]
+            image, stats = vis.eval_panels(pred[local], gt_u[local], gt_v[local], count2()[local],
+                                           grey, max_row, return_stats=True)
+            drawn.append((mine, image, stats))
+        rows = testing.evaluate_frames(of, self.sequence, self.frames, self.gt, self.crop, None,
+                                       self.crop, self.is_car, self.batch_size, observer=observer)
+        return rows, drawn
+
+    def __call__(self, steps, samples):
+        if self.rank != 0:
+            return
+        from . import eval as dev_eval, testing, visualization as vis
+        with model_left_as_found(self.model) as m:
+            m.eval()
+            with torch.no_grad():
+                rows, drawn = self.evaluate()
+        mean_aee, mean_percent = testing.summarize(rows)
+        self.logger.add_scalar('Evaluation/mean AEE', float(mean_aee[-1]), samples)
+        self.logger.add_scalar('Evaluation/mean %AEE', float(mean_percent[-1]) * 100, samples)
+        aee, percent = dev_eval.derive(rows)
+        out = self.directory / f'step_{steps}'
+        k = 0
+        for mine, images, stats in drawn:
+            images, stats = vis._host(images), vis.read_panel_stats(stats)
+            for i, image, s in zip(mine, images, stats):
+                statistics = {
+                    'frame': i, 'start': float(self.frames[i][0]), 'stop': float(self.frames[i][1]),
+                    'AEE': float(aee[i]), 'n_points': int(rows['n_points'][i]),
+                    'share_under_3px': float(percent[i]),
+                    'prediction': {'lo': float(s['pred_lo']), 'hi': float(s['pred_hi']),
+                                   'nonfinite': int(s['pred_nonfinite'])},
+                    'ground_truth': {'lo': float(s['gt_lo']), 'hi': float(s['gt_hi']),
+                                     'nonfinite': int(s['gt_nonfinite'])},
+                    'm': float(vis.panel_scale(s))}
+                if hasattr(self.logger, 'add_image'):
+                    self.logger.add_image(f'Evaluation/{k}', image, samples, dataformats='HWC')
+                out.mkdir(parents=True, exist_ok=True)
+                write_png(out / f'{k:04d}.png', image)
+                (out / f'{k:04d}.yml').write_text(yaml.dump(statistics))
+                k += 1
 
 
 class VisualizationHook:

@@ -34,6 +34,19 @@ class OpticalFlow:
         self._net.eval()
         self.imsize = imsize
 
+    @classmethod
+    def from_model(cls, net, imsize):
+        """Wrap a live ``Model`` (one that is being trained, say): no weight
+        is loaded or copied, and the model's mode is the caller's business
+        (``hooks.model_left_as_found``).  No graph: the weights move between
+        calls."""
+        self = cls.__new__(cls)
+        self._use_graph, self._graphs = False, {}
+        self._device = next(net.parameters()).device
+        self._net = net
+        self.imsize = imsize
+        return self
+
     def load_state_dict(self, state_dict):
         self._net.load_state_dict(state_dict)
         self._net.to(device=self._device)

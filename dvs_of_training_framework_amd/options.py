@@ -242,6 +242,30 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'where the logger takes images, into the log; 0: off')
     parser.add_argument('--visualization-samples', dest='visualization_samples',
                         default=4, type=int)
+    parser.add_argument('--validation-ground-truth', dest='validation_ground_truth',
+                        default=None, type=Path,
+                        help='ground-truth flow of --validation-sequence: an MVSEC '
+                             '*_gt_flow_dist.npz (timestamps, x_flow_dist, y_flow_dist) on '
+                             'the clock of the sequence\'s image timestamps')
+    parser.add_argument('--evaluation-period', dest='evaluation_period', default=0,
+                        type=int,
+                        help='every this many optimizer steps measure the endpoint error '
+                             'of the live weights on --validation-sequence against '
+                             '--validation-ground-truth (central crop to --height x '
+                             '--width), log Evaluation/mean AEE and Evaluation/mean %%AEE '
+                             'and draw --evaluation-pictures frames (events | prediction '
+                             '| ground truth | endpoint error; docs/EVAL_PANELS_SPEC.md) '
+                             'into <model>/evaluation/step_N/; 0: off')
+    parser.add_argument('--evaluation-frame-step', dest='evaluation_frame_step',
+                        default=1, type=int,
+                        help='images a frame of the evaluation spans (the step of the '
+                             'reference\'s test grid)')
+    parser.add_argument('--evaluation-pictures', dest='evaluation_pictures', default=4,
+                        type=int)
+    parser.add_argument('--evaluation-is-car', dest='evaluation_is_car',
+                        action='store_true',
+                        help='outdoor driving sequence: rows from 190 on (the hood) are '
+                             'not counted')
     parser.add_argument('--sync-checkpoints', dest='sync_checkpoints',
                         action='store_true',
                         help='write checkpoints on the training thread (state_dict() + '

@@ -126,11 +126,18 @@ _check_in_frame = dev_eval.check_in_frame
 
 def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
                     pred_postproc_fun=None, gt_proc_fun=None, is_car=False,
-                    batch_size=8, fold=True):
+                    batch_size=8, fold=True, *, observer=None):
     """The per-frame results behind ``evaluate``: a numpy structured array
     (eval.RESULT_DTYPE: sum_ee, n_points, n_below, pred_max, pred_min), one
     row per frame.  fold=False applies box crops on the host like any other
     callable (same results; for tests).
+
+    observer: called once per batch as ``observer(first, pred, gt_u, gt_v,
+    max_row, count2)`` with the index of the batch's first frame, the device
+    tensors the error kernel reads and a zero-argument callable that returns
+    the polarity count image [F,2,h,w] of the batch
+    (``eval.count_image_polarity_batched`` of the columns the count image was
+    made of; launched only when called).  None: nothing more is launched.
 
     events: the columns [x, y, t, p], or a ``sequence.EventSequence`` holding
     them on the device: a batch of frames is then one window-kernel launch in
@@ -229,9 +236,16 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
             count = dev_eval.count_image_batched(
                 collated.events['x'], collated.events['y'], collated.win_out,
                 (h, w), (0, 0, h, w))
-            res = dev_eval.flow_error(gt_u, gt_v, pred, count,
-                                      min(dev_eval.CAR_ROWS, h) if is_car else h)
+            max_row = min(dev_eval.CAR_ROWS, h) if is_car else h
+            res = dev_eval.flow_error(gt_u, gt_v, pred, count, max_row)
             out.append(dev_eval.read_results(res))
+            if observer is not None:
+                ev = collated.events
+                observer(b0, pred, gt_u, gt_v, max_row,
+                         lambda ev=ev, begin=collated.win_out, h=h, w=w:
+                         dev_eval.count_image_polarity_batched(
+                             ev['x'], ev['y'], ev['polarity'], begin, (h, w),
+                             (0, 0, h, w)))
             continue
         if ev_box is not None and ev_box[2:] == (h, w):
             cols, box = raw, ev_box         # the kernel drops and shifts
@@ -249,10 +263,28 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
         xy = torch.from_numpy(xy).to(device)
         count = dev_eval.count_image_batched(xy[0], xy[1], begin, (h, w), box)
 
-        res = dev_eval.flow_error(gt_u, gt_v, pred, count,
-                                  min(dev_eval.CAR_ROWS, h) if is_car else h)
+        max_row = min(dev_eval.CAR_ROWS, h) if is_car else h
+        res = dev_eval.flow_error(gt_u, gt_v, pred, count, max_row)
         out.append(dev_eval.read_results(res))      # the batch's one copy back
+        if observer is not None:
+            def count2(cols=cols, xy=xy, begin=begin, h=h, w=w, box=box):
+                pol = np.concatenate([np.asarray(e[3]).astype(np.int64)
+                                      for e in cols] + [np.zeros(0, np.int64)])
+                return dev_eval.count_image_polarity_batched(
+                    xy[0], xy[1], torch.from_numpy(pol).to(device), begin,
+                    (h, w), box)
+            observer(b0, pred, gt_u, gt_v, max_row, count2)
     return np.concatenate(out)
+
+
+def summarize(rows):
+    """Per-frame result rows -> (running mean AEE, running mean share under
+    3 px) float64 [F]: sums in frame order, so that a NaN (a frame without a
+    counted pixel) spoils the mean from there on, as it does in the
+    reference.  The last entries are what ``evaluate`` returns."""
+    aee, percent = dev_eval.derive(rows)
+    count = np.arange(1, len(rows) + 1)
+    return np.cumsum(aee) / count, np.cumsum(percent) / count
 
 
 def evaluate(of, events, frames, gt, event_preproc_fun=None,
@@ -276,12 +308,9 @@ def evaluate(of, events, frames, gt, event_preproc_fun=None,
                            pred_postproc_fun, gt_proc_fun, is_car, batch_size)
     if len(rows) == 0:
         raise ValueError('evaluate needs at least one frame')
-    aee, percent = dev_eval.derive(rows)
-    # running sums in frame order, so that a NaN (a frame without a counted
-    # pixel) spoils the mean from there on, as it does in the reference
-    count = np.arange(1, len(rows) + 1)
-    mean_aee, mean_percent = np.cumsum(aee) / count, np.cumsum(percent) / count
+    mean_aee, mean_percent = summarize(rows)
     if log:
+        count = np.arange(1, len(rows) + 1)
         mean_max = np.cumsum(rows['pred_max'], dtype=np.float64) / count
         mean_min = np.cumsum(rows['pred_min'], dtype=np.float64) / count
         for k in range(99, len(rows), 100):

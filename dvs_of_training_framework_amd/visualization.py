@@ -8,7 +8,10 @@ is visualize.py:130-140 of the reference without its text band.  A mosaic is
 laid out once on the host (``Canvas``) and drawn by two kernel launches, or,
 for sources that are not on a GPU, by the numpy float32 restatement of the
 spec that lives here too (``flow2img_numpy``): it is what a CPU-only user
-gets and what the tests pin the kernels against.
+gets and what the tests pin the kernels against.  ``eval_panels`` (HIP,
+csrc/eval_panels.hip; docs/EVAL_PANELS_SPEC.md) draws a prediction against its
+ground truth: events, both flows on one scale, the endpoint error;
+``eval_panels_numpy`` is its restatement.
 """
 import struct
 import zlib
@@ -410,6 +413,169 @@ def visualize(args, batch, loss, parts, weights, prediction):
     ``process_minibatch(..., return_prediction=True)`` returns.  ``weights`` is
     kept for the reference's signature: it only fed the text band."""
     return sample_picture(args, batch, loss, parts, prediction, 0)
+
+
+# ------------------------------------------------------ evaluation panels
+# dvsof_eval_panel_stats_t
+PANEL_STATS_DTYPE = np.dtype([('pred_lo', '<f4'), ('pred_hi', '<f4'), ('pred_nonfinite', '<i4'),
+                              ('gt_lo', '<f4'), ('gt_hi', '<f4'), ('gt_nonfinite', '<i4'),
+                              ('n_counted', '<i4'), ('n_below', '<i4')])
+assert PANEL_STATS_DTYPE.itemsize == 32
+UNCOUNTED = 64                  # grey of a pixel the metric does not count
+PANELS = ('events', 'prediction', 'ground truth', 'endpoint error')
+
+
+def counted_numpy(gt_u, gt_v, count2=None, max_row=None):
+    """The pixels ``eval.flow_error`` counts (EVAL_SPEC section 3) -> bool
+    [..,h,w]: row < max_row, an event of either polarity (count2 [..,2,h,w];
+    None: dense), no infinite ground-truth component, its float32 norm > 0."""
+    gu, gv = np.asarray(gt_u, _F), np.asarray(gt_v, _F)
+    h = gu.shape[-2]
+    rows = np.arange(h)[:, None] < (h if max_row is None else int(max_row))
+    with np.errstate(all='ignore'):
+        moving = np.sqrt(gu * gu + gv * gv) > 0
+    ok = rows & ~np.isinf(gu) & ~np.isinf(gv) & moving
+    if count2 is not None:
+        c = np.asarray(count2).astype(np.int64) & 0xFFFFFFFF    # the uint32 counts
+        ok = ok & (c[..., 0, :, :] + c[..., 1, :, :] > 0)
+    return ok
+
+
+def endpoint_error_numpy(pred, gt_u, gt_v):
+    """EE of ``dvsof_flow_error``: sqrtf(du * du + dv * dv) with du = gt_u -
+    pred_u, every operation rounded to float32.  pred [..,2,h,w]."""
+    pred = np.asarray(pred, _F)
+    with np.errstate(all='ignore'):
+        du = np.asarray(gt_u, _F) - pred[..., 0, :, :]
+        dv = np.asarray(gt_v, _F) - pred[..., 1, :, :]
+        return np.sqrt(du * du + dv * dv)
+
+
+def panel_scale(stats, flow_scale=0.0):
+    """The ``max_magnitude`` both flow panels of a frame are drawn with:
+    ``flow_scale`` when > 0, else the ground truth's ``hi`` when it is finite
+    and > 0, else the prediction's ``hi``.  stats: one PANEL_STATS_DTYPE row."""
+    if _F(flow_scale) > 0:
+        return _F(flow_scale)
+    hi = _F(stats['gt_hi'])
+    return hi if np.isfinite(hi) and hi > 0 else _F(stats['pred_hi'])
+
+
+def heat_numpy(ee, counted, err_max=6.0):
+    """The error panel -> uint8 [..,3] BGR: black -> red -> yellow -> white
+    over 0 .. err_max, a NaN at the maximum, an uncounted pixel (64, 64, 64)."""
+    with np.errstate(all='ignore'):
+        t = np.trunc(np.fmin(np.asarray(ee, _F) * (_F(255) / _F(err_max)), _F(255)))
+    t3 = 3 * np.where(counted, t, 0).astype(np.int64)
+    bgr = np.stack([np.clip(t3 - 510, 0, 255), np.clip(t3 - 255, 0, 255),
+                    np.minimum(t3, 255)], -1).astype(np.uint8)
+    bgr[~np.asarray(counted, bool)] = UNCOUNTED
+    return bgr
+
+
+def events_numpy(shape, count2=None, frames=None, gain=85):
+    """The events panel -> uint8 shape + (3,) BGR: ON events red, OFF events
+    blue, ``gain`` per event, over the grey frame (black without one)."""
+    out = np.zeros(tuple(shape) + (3,), np.uint8)
+    if frames is not None:
+        out[:] = np.asarray(frames, np.uint8)[..., None]
+    if count2 is not None:
+        c = np.asarray(count2).astype(np.int64) & 0xFFFFFFFF
+        on, off = c[..., 0, :, :], c[..., 1, :, :]
+        hit = on + off > 0
+        colour = np.stack([np.minimum(255, np.minimum(off, 255) * int(gain)), np.zeros_like(on),
+                           np.minimum(255, np.minimum(on, 255) * int(gain))], -1)
+        out[hit] = colour[hit].astype(np.uint8)
+    return out
+
+
+def eval_panels_numpy(pred, gt_u, gt_v, count2=None, frames=None, max_row=None, flow_scale=0.0,
+                      err_max=6.0, gain=85, return_stats=False):
+    """docs/EVAL_PANELS_SPEC.md in numpy float32: what ``eval_panels`` runs
+    without a GPU and what the kernels are pinned to.  pred [F,2,h,w], gt_u,
+    gt_v [F,h,w], count2 [F,2,h,w] or None, frames uint8 [F,h,w] or None ->
+    uint8 [F,h,4w,3] BGR (events | prediction | ground truth | endpoint
+    error) and, with return_stats, a PANEL_STATS_DTYPE array [F]."""
+    pred, gu, gv = np.asarray(pred, _F), np.asarray(gt_u, _F), np.asarray(gt_v, _F)
+    F, two, h, w = pred.shape
+    assert two == 2 and gu.shape == gv.shape == (F, h, w), (pred.shape, gu.shape, gv.shape)
+    counted = counted_numpy(gu, gv, count2, max_row)
+    ee = endpoint_error_numpy(pred, gu, gv)
+    image = np.empty((F, h, 4 * w, 3), np.uint8)
+    stats = np.zeros(F, PANEL_STATS_DTYPE)
+    image[:, :, :w] = events_numpy((F, h, w), count2, frames, gain)
+    image[:, :, 3 * w:] = heat_numpy(ee, counted, err_max)
+    for f in range(F):
+        s = stats[f]
+        _, _, s['pred_lo'], s['pred_hi'], s['pred_nonfinite'] = flow_stats_numpy(pred[f, 0], pred[f, 1])
+        _, _, s['gt_lo'], s['gt_hi'], s['gt_nonfinite'] = flow_stats_numpy(gu[f], gv[f])
+        s['n_counted'] = counted[f].sum()
+        with np.errstate(invalid='ignore'):
+            s['n_below'] = (ee[f][counted[f]] < _F(3)).sum()
+        m = panel_scale(s, flow_scale)
+        image[f, :, w:2 * w] = flow2img_numpy(pred[f, 0], pred[f, 1], m)
+        image[f, :, 2 * w:3 * w] = flow2img_numpy(gu[f], gv[f], m)
+    return (image, stats) if return_stats else image
+
+
+def eval_panels(pred, gt_u, gt_v, count2=None, frames=None, max_row=None, flow_scale=0.0,
+                err_max=6.0, gain=85, out=None, return_stats=False):
+    """Per frame one picture of four panels, events | prediction | ground
+    truth | endpoint error, the two flows on one colour scale: two launches
+    for any F on the device, ``eval_panels_numpy`` for host arrays.
+
+    pred float32 [F,2,h,w]; gt_u, gt_v float32 [F,h,w]; count2 [F,2,h,w]
+    (``eval.count_image_polarity_batched``) or None (dense); frames uint8
+    [F,h,w] or None; max_row: rows the metric counts (default h).  out: a
+    device uint8 [F,h,4w,3] to draw into, contiguous or a strided view whose
+    pixels are 3 and whose columns 1 byte apart.  -> uint8 [F,h,4w,3] BGR and,
+    with return_stats, the statistics (device uint8 [F,32]: ``read_panel_stats``)."""
+    if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
+        assert out is None, 'out= is for device rendering'
+        return eval_panels_numpy(_host(pred), _host(gt_u), _host(gt_v),
+                                 None if count2 is None else _host(count2),
+                                 None if frames is None else _host(frames), max_row, flow_scale,
+                                 err_max, gain, return_stats)
+    _lib.require_cuda(gt_u, gt_v, count2, frames)
+    pred, gt_u, gt_v = pred.contiguous(), gt_u.contiguous(), gt_v.contiguous()
+    F, two, h, w = pred.shape
+    assert two == 2 and tuple(gt_u.shape) == tuple(gt_v.shape) == (F, h, w) \
+        and pred.dtype == gt_u.dtype == gt_v.dtype == torch.float32, \
+        (pred.shape, gt_u.shape, gt_v.shape)
+    if count2 is not None:
+        count2 = count2.contiguous()
+        assert tuple(count2.shape) == (F, 2, h, w) and count2.element_size() == 4
+    if frames is not None:
+        frames = frames.contiguous()
+        assert tuple(frames.shape) == (F, h, w) and frames.dtype == torch.uint8
+    dev = pred.device
+    if out is None:
+        out = torch.empty(F, h, 4 * w, 3, dtype=torch.uint8, device=dev)
+    assert tuple(out.shape) == (F, h, 4 * w, 3) and out.dtype == torch.uint8 \
+        and out.device == dev and out.stride(3) == 1 and out.stride(2) == 3, \
+        (tuple(out.shape), out.stride(), out.dtype, out.device)
+    lib = _lib.lib()
+    stats = torch.empty(max(F, 1), PANEL_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    nbytes = lib.dvsof_eval_panels_workspace_bytes(F)
+    ws = torch.empty(max(nbytes, 32), dtype=torch.uint8, device=dev)
+    max_row = h if max_row is None else int(max_row)
+    _lib.check(lib.dvsof_eval_panels_stats(
+        pred.data_ptr(), gt_u.data_ptr(), gt_v.data_ptr(), _lib.ptr(count2), F, h, w, max_row,
+        ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_eval_panels_stats')
+    _lib.check(lib.dvsof_eval_panels(
+        pred.data_ptr(), gt_u.data_ptr(), gt_v.data_ptr(), _lib.ptr(count2), _lib.ptr(frames),
+        F, h, w, max_row, float(flow_scale), float(err_max), int(gain), ws.data_ptr(), nbytes,
+        out.data_ptr(), out.untyped_storage().nbytes() - out.storage_offset(),
+        out.stride(0), out.stride(1), stats.data_ptr(), _lib.stream()), 'dvsof_eval_panels')
+    return (out, stats[:F]) if return_stats else out
+
+
+def read_panel_stats(stats):
+    """Statistics of ``eval_panels`` -> numpy structured array
+    (PANEL_STATS_DTYPE): the one device-to-host copy."""
+    if isinstance(stats, torch.Tensor):
+        return stats.cpu().numpy().view(PANEL_STATS_DTYPE).reshape(-1)
+    return np.asarray(stats, PANEL_STATS_DTYPE).reshape(-1)
 
 
 # ------------------------------------------------------------------ files

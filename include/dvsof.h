@@ -385,6 +385,18 @@ int dvsof_count_image_batched(const int64_t *x, const int64_t *y,
                               int x0, int h, int w, uint32_t *out,
                               void *stream);
 
+/*
+ * dvsof_count_image_batched by polarity: p is the int64 wire polarity column,
+ * out uint32[F,2,h,w] (zeroed by the call); plane 0 of a frame counts its
+ * events with p > 0, plane 1 those with p <= 0.  The two planes add up to
+ * what dvsof_count_image_batched writes for the same columns, exactly.
+ */
+int dvsof_count_image_polarity_batched(const int64_t *x, const int64_t *y,
+                                       const int64_t *p, int64_t n_events,
+                                       const int64_t *frame_event_begin,
+                                       int F, int y0, int x0, int h, int w,
+                                       uint32_t *out, void *stream);
+
 /* ------------------------------------------------------------------ *
  * Rendering (csrc/render.hip, docs/RENDER_SPEC.md): predicted flow as a
  * colour image on the device.  Replaces flow2img, utils/visualization.py:5-18
@@ -475,6 +487,69 @@ int dvsof_flow_render(const dvsof_render_item_t *items,
                       const void *workspace, size_t workspace_bytes,
                       uint8_t *canvas, size_t canvas_bytes,
                       dvsof_render_stats_t *stats, void *stream);
+
+/* ------------------------------------------------------------------ *
+ * Evaluation panels (csrc/eval_panels.hip, docs/EVAL_PANELS_SPEC.md): per
+ * frame one picture of h x 4w BGR bytes, the panels events | prediction |
+ * ground truth | endpoint error side by side, prediction and ground truth
+ * on one colour scale.  Two launches for any number of frames.
+ * ------------------------------------------------------------------ */
+
+/* per frame, 32 bytes: the prediction's and the ground truth's
+ * dvsof_render_stats_t values, then the pixels dvsof_flow_error counts */
+typedef struct {
+    float pred_lo, pred_hi;
+    int32_t pred_nonfinite;
+    float gt_lo, gt_hi;
+    int32_t gt_nonfinite;
+    int32_t n_counted;  /* dvsof_eval_result_t.n_points */
+    int32_t n_below;    /* ... with an endpoint error < 3 */
+} dvsof_eval_panel_stats_t;
+
+/* Scratch for the per-chunk partials of F frames (64 slots of 32 bytes each). */
+size_t dvsof_eval_panels_workspace_bytes(int F);
+
+/*
+ * Launch 1: one workgroup per (frame, chunk of dvsof_flow_render_chunk_rows
+ * rows) writes the partial statistics of its rows into `workspace`.
+ *   pred         float32[F,2,h,w]
+ *   gt_u, gt_v   float32[F,h,w]
+ *   count2       uint32[F,2,h,w] (dvsof_count_image_polarity_batched) or NULL
+ *   max_row      rows >= max_row are not counted, 0 <= max_row <= h
+ * Integers and min / max only: same input, same bits.
+ */
+int dvsof_eval_panels_stats(const float *pred, const float *gt_u,
+                            const float *gt_v, const uint32_t *count2, int F,
+                            int h, int w, int max_row, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/*
+ * Launch 2: one workgroup per (frame, panel, chunk) reduces the partials of
+ * its frame and colours its rows (docs/EVAL_PANELS_SPEC.md).  Picture f has
+ * its pixel (0,0) at canvas + f * frame_stride, rows row_stride bytes apart,
+ * panel k at x0 = k * w.
+ *   frames       uint8[F,h,w] grey under the events, or NULL (black)
+ *   flow_scale   > 0: max_magnitude of both flow panels; <= 0: the ground
+ *                truth's hi when finite and > 0, else the prediction's
+ *   err_max      > 0: the endpoint error drawn at full scale
+ *   gain         1..255: colour per event
+ *   stats        dvsof_eval_panel_stats_t[F]; the caller may copy it back once
+ * Stream order after dvsof_eval_panels_stats is the only synchronisation.
+ * Every byte of every picture is written exactly once, nothing else is.
+ * DVSOF_EINVAL before any launch: null pointers, F < 0, h or w outside
+ * [1, 32767], max_row outside [0, h], row_stride < 12 w, pictures that overlap
+ * (F > 1 and frame_stride < h * row_stride) or reach past canvas_bytes,
+ * err_max not > 0 or not finite, gain outside 1..255; DVSOF_ENOSPACE: the
+ * workspace is missing or too small.  F == 0: nothing to do.
+ */
+int dvsof_eval_panels(const float *pred, const float *gt_u, const float *gt_v,
+                      const uint32_t *count2, const uint8_t *frames, int F,
+                      int h, int w, int max_row, float flow_scale,
+                      float err_max, int gain, const void *workspace,
+                      size_t workspace_bytes, uint8_t *canvas,
+                      size_t canvas_bytes, int64_t frame_stride,
+                      int64_t row_stride, dvsof_eval_panel_stats_t *stats,
+                      void *stream);
 
 /* ------------------------------------------------------------------ *
  * Device-resident event sequence -> wire-format batch

@@ -169,13 +169,142 @@ def host_reference_structure(of, events, frames, gt, box):
     return aee_sum / len(frames)
 
 
+def panels_alone(F=8, side=CROP, per_frame=30000, seed=0):
+    """--hook, first part: the polarity count and the panel launch pair alone at
+    F frames of side x side (HIP events around the C ABI calls; bytes from the
+    shapes), against visualization.eval_panels_numpy on the host."""
+    from dvs_of_training_framework_amd import visualization as vis
+    dev, lib, stream = 'cuda', _lib.lib(), _lib.stream()
+    rng = np.random.default_rng(seed)
+    gt = rng.normal(0, 4, (F, 2, side, side)).astype(np.float32)
+    gt[:, :, rng.random((side, side)) < 0.05] = 0.0
+    pred = (gt + rng.normal(0, 2, gt.shape)).astype(np.float32)
+    frames = rng.integers(0, 256, (F, side, side)).astype(np.uint8)
+    n = F * per_frame
+    cols = [torch.from_numpy(rng.integers(0, side, n)).to(dev) for _ in range(2)]
+    pol = torch.from_numpy(rng.choice([-1, 1], n)).to(dev)
+    begin = torch.arange(F + 1, device=dev) * per_frame
+    count2 = torch.empty(F, 2, side, side, dtype=torch.int32, device=dev)
+    out = {}
+
+    def run_count():
+        rc = lib.dvsof_count_image_polarity_batched(
+            cols[0].data_ptr(), cols[1].data_ptr(), pol.data_ptr(), n, begin.data_ptr(), F, 0, 0,
+            side, side, count2.data_ptr(), stream)
+        assert rc == 0, rc
+    us = timed(run_count)
+    nbytes = n * 24 + F * 2 * side * side * 4 + n * 4      # columns in, zero fill, one atomic per event
+    out['count_image_polarity'] = dict(us=round(us, 2), events=n, bytes=nbytes,
+                                       GBps=round(nbytes / us / 1e3, 1))
+    t = [torch.from_numpy(a).to(dev) for a in (pred, gt[:, 0].copy(), gt[:, 1].copy(), frames)]
+    need = lib.dvsof_eval_panels_workspace_bytes(F)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    canvas = torch.empty(F, side, 4 * side, 3, dtype=torch.uint8, device=dev)
+    stats = torch.empty(F, 32, dtype=torch.uint8, device=dev)
+
+    def run_stats():
+        rc = lib.dvsof_eval_panels_stats(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(),
+                                         count2.data_ptr(), F, side, side, side, ws.data_ptr(), need, stream)
+        assert rc == 0, rc
+
+    def run_colour():
+        rc = lib.dvsof_eval_panels(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), count2.data_ptr(),
+                                   t[3].data_ptr(), F, side, side, side, 0.0, 6.0, 85, ws.data_ptr(), need,
+                                   canvas.data_ptr(), canvas.numel(), side * 12 * side, 12 * side,
+                                   stats.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def run_pair():
+        run_stats()
+        run_colour()
+    px = F * side * side
+    for name, fn, nbytes in (('stats', run_stats, px * 24), ('colour', run_colour, px * (24 + 16 + 9 + 12)),
+                             ('pair', run_pair, px * (48 + 16 + 9 + 12))):
+        us = timed(fn)
+        out[name] = dict(us=round(us, 2), bytes=nbytes, GBps=round(nbytes / us / 1e3, 1))
+    host = [a.cpu().numpy() for a in (*t[:3], count2, t[3])]
+    want = vis.eval_panels_numpy(*host)
+    assert np.array_equal(canvas.cpu().numpy()[:, :, [0, 3 * side]], want[:, :, [0, 3 * side]])
+    times = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        vis.eval_panels_numpy(*host)
+        times.append(round((time.perf_counter() - t0) * 1e3, 1))
+    out['numpy_ms'] = times
+    return out
+
+
+def hook_leg(n_frames, per_frame):
+    """--hook, second part: one EvaluationHook call over the synthetic sequence
+    against the step time of the same run (eager steps of the same model at
+    batch 8, 256 x 256, between which the hook runs)."""
+    from dvs_of_training_framework_amd import hooks, synthetic
+    from dvs_of_training_framework_amd.loss import init_losses
+    from dvs_of_training_framework_amd.net import Model
+    from dvs_of_training_framework_amd.optim import FusedAdamW
+    from dvs_of_training_framework_amd.sequence import FrameSequence
+    from dvs_of_training_framework_amd.timer import FakeTimer
+    from dvs_of_training_framework_amd.training import process_minibatch
+    import tempfile
+    dev = torch.device('cuda:0')
+    events, frames, gt = sequence(n_frames, 1, per_frame)
+    image_ts = np.array([a for a, _ in frames] + [frames[-1][1]])
+    images = np.random.default_rng(1).integers(0, 256, (len(image_ts), H, W)).astype(np.uint8)
+    keep = events[2] <= image_ts[-1]
+    seq = FrameSequence([c[keep] for c in events], images, image_ts, device=dev)
+    torch.manual_seed(0)
+    model = Model(dev, event_representation_depth=5).train()
+    opt = FusedAdamW(model.predictor.parameters(), lr=1e-4)
+    B = 8
+    losses = init_losses((CROP, CROP), B, model, dev, sequence_length=1)
+    batches = [synthetic.to_torch(synthetic.make_batch(s, B, CROP, CROP, per_frame), dev) for s in range(4)]
+
+    class Log:
+        def add_scalar(self, tag, value, x):
+            setattr(self, 'aee' if tag.endswith('mean AEE') else 'share', value)
+
+    def steps(k):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(k):
+            loss = process_minibatch(model, batches[i % 4], FakeTimer(), dev, True, losses, [0.5, 1, 1])[0]
+            loss.backward()
+            opt.step()
+            opt.zero_grad()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / k
+    out = dict(frames=None, step_ms=[], hook_ms=[])
+    with tempfile.TemporaryDirectory() as tmp:
+        hook = hooks.EvaluationHook(model, seq, gt, Log(), (CROP, CROP), tmp, pictures=4)
+        out['frames'] = len(hook.frames)
+        steps(10)
+        hook(0, 0)                      # warm-up: every shape of the call
+        for k in range(3):              # alternating: steps, a hook call, steps, ...
+            out['step_ms'].append(round(steps(50), 3))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            hook(k + 1, 0)
+            torch.cuda.synchronize()
+            out['hook_ms'].append(round((time.perf_counter() - t0) * 1e3, 1))
+        out['mean_aee'] = hook.logger.aee
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=200)
     ap.add_argument('--events', type=int, default=30000)
     ap.add_argument('--steps', type=int, nargs='+', default=[1, 4])
     ap.add_argument('--host-frames', type=int, default=40)
+    ap.add_argument('--hook', action='store_true',
+                    help='the evaluation hook instead (profiles/evaluation_hook/README.md): the '
+                         'polarity count and the panel launches alone at F = 8, then one hook '
+                         'call over --frames frames against the step time of the same run')
     args = ap.parse_args()
+    if args.hook:
+        print(json.dumps(dict(panels_F8=panels_alone(per_frame=args.events),
+                              hook=hook_leg(args.frames, args.events))))
+        return
     box = [(H - CROP) // 2, (W - CROP) // 2, CROP, CROP]
     of = OpticalFlow((CROP, CROP), model=None, event_representation_depth=5)
     crops = dict(event_preproc_fun=ec.EventCrop(box), gt_proc_fun=ec.ImageCrop(box))

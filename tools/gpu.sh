@@ -15,6 +15,9 @@
 #   eval [eval_bench.py args]        testing.evaluate on a synthetic MVSEC-shaped sequence: frames/s at batch 1 and 8,
 #                                     the reference's per-frame structure on the host, the three kernels alone
 #                                     the same frames from a device-resident EventSequence, the window kernel alone
+#   evalhook [eval_bench.py args]    the evaluation hook (tools/eval_bench.py --hook): polarity count and the panel
+#                                     launch pair alone at F = 8, 256x256, against the numpy restatement on the host;
+#                                     one hook call over 200 frames against the step time of the same run
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -71,6 +74,9 @@ optim)
 eval)
   timeout -k 10 560 env "${envs[@]}" python tools/eval_bench.py "$@" > $O/eval.json 2> $O/eval.err
   echo "eval rc=$?"; cut -c1-2600 $O/eval.json; tail -3 $O/eval.err ;;
+evalhook)
+  timeout -k 10 560 env "${envs[@]}" python tools/eval_bench.py --hook "$@" > $O/eval_hook.json 2> $O/eval_hook.err
+  echo "evalhook rc=$?"; cut -c1-2600 $O/eval_hook.json; tail -3 $O/eval_hook.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

@@ -34,8 +34,8 @@ from dvs_of_training_framework_amd.optim import FusedAdamW, FusedRAdam, \
 from dvs_of_training_framework_amd.options import (
     add_train_arguments, add_preprocessed_dataset_arguments, guard_requested,
     resolve_step_guard, validate_train_args)
-from dvs_of_training_framework_amd.hooks import SerializationHook, \
-    ValidationHook, VisualizationHook
+from dvs_of_training_framework_amd.hooks import EvaluationHook, \
+    SerializationHook, ValidationHook, VisualizationHook
 from dvs_of_training_framework_amd.serializer import Serializer
 from dvs_of_training_framework_amd.timer import EventTimer, FakeTimer
 from dvs_of_training_framework_amd.training import HostGuard, \
@@ -308,6 +308,32 @@ def add_visualization(args, hooks, periodic, model, device, logger, losses, rank
                                                    args.visualization_period)
 
 
+def add_evaluation(args, hooks, periodic, model, device, logger, rank):
+    """--evaluation-period N > 0: an ``EvaluationHook`` every N optimizer steps
+    (endpoint error against ground truth, and pictures).  0 constructs
+    nothing.  Rank 0 alone holds the sequence and the ground truth."""
+    if getattr(args, 'evaluation_period', 0) <= 0:
+        return
+    missing = [flag for flag, value in
+               (('--validation-sequence', getattr(args, 'validation_sequence', None)),
+                ('--validation-ground-truth', getattr(args, 'validation_ground_truth', None)))
+               if value is None]
+    if missing:
+        raise SystemExit('--evaluation-period needs ' + ' and '.join(missing))
+    sequence = gt = None
+    if rank == 0:
+        import numpy as np
+        from dvs_of_training_framework_amd.sequence import FrameSequence
+        sequence = FrameSequence.from_directory(args.validation_sequence, device)
+        with np.load(str(args.validation_ground_truth)) as data:
+            gt = {k: data[k] for k in ('timestamps', 'x_flow_dist', 'y_flow_dist')}
+    hooks['evaluation'] = EvaluationHook(
+        model, sequence, gt, logger, args.shape, args.model / 'evaluation',
+        frame_step=args.evaluation_frame_step, pictures=args.evaluation_pictures,
+        is_car=args.evaluation_is_car, rank=rank)
+    periodic['evaluation'] = make_hook_periodic(hooks['evaluation'], args.evaluation_period)
+
+
 def restore_loader(loader, state, rank, world, global_step, args):
     """Position ``loader`` from the checkpoint's ``loader_state`` (a list
     indexed by rank); a checkpoint without one (the reference's) positions by
@@ -420,6 +446,7 @@ def main(argv=None):
         note('no validation data (--validation-sequence, or '
              '--synthetic-validation-batches with --synthetic): validation is skipped')
     add_visualization(args, hooks, periodic, model, device, logger, losses, rank)
+    add_evaluation(args, hooks, periodic, model, device, logger, rank)
 
     try:
         if not resume:
