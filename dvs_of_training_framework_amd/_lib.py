@@ -78,6 +78,11 @@ _SIGNATURES = {
     'dvsof_eval_panels': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f,
                                _f, _i, _vp, _sz, _vp, _sz, _i64, _i64, _vp,
                                _vp]),
+    'dvsof_iwe_splat': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i,
+                             _vp, _vp]),
+    'dvsof_iwe_stats_workspace_bytes': (_sz, [_i, _i, _i]),
+    'dvsof_iwe_stats': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'dvsof_iwe_render': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'dvsof_flow_render_chunk_rows': (_i, [_i, _i]),
     'dvsof_flow_render_workspace_bytes': (_sz, [_i]),
     'dvsof_flow_render_stats': (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),

@@ -7,6 +7,11 @@ out, the work done by the kernels.  The batched device functions underneath
 (``propagate``, ``flow_error``, ``count_image_batched``) are what
 ``testing.evaluate`` drives; ``plan_gt_steps`` is the host-side part of the
 propagation (which maps, which scale factors) and needs no GPU.
+
+Without ground truth: ``iwe_splat``, ``iwe_stats``, ``iwe_render`` and
+``derive_fwl`` (csrc/iwe.hip, docs/IWE_SPEC.md), the image of warped events
+and its flow warp loss, driven by ``testing.flow_warp_loss``; for host arrays
+they run the numpy float32 restatement ``iwe_*_host`` the kernels are pinned to.
 """
 import numpy as np
 import torch
@@ -260,3 +265,205 @@ def estimate_corresponding_gt_flow(x_flow_in, y_flow_in, gt_timestamps,
         dt = np.result_type(np.asarray(x_flow_in[lo]).dtype, np.float64)
         return u.astype(dt), v.astype(dt)
     return u, v
+
+
+# ---------------------------------------------------------------------------
+# Image of warped events and flow warp loss (csrc/iwe.hip, docs/IWE_SPEC.md)
+# ---------------------------------------------------------------------------
+# dvsof_iwe_result_t
+IWE_RESULT_DTYPE = np.dtype([('sum_sq', '<f8'), ('sum_q', '<i8'), ('max_q', '<i8'),
+                             ('count_sum', '<i8'), ('count_sq', '<i8'),
+                             ('count_max', '<i8')])
+assert IWE_RESULT_DTYPE.itemsize == 48
+IWE_ONE = 1 << 32       # the fixed-point unit of q
+_F = np.float32
+
+
+def _on_device(t):
+    return isinstance(t, torch.Tensor) and t.is_cuda
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _counts(count):
+    """A count image as the kernels read it: the uint32 bits, as int64."""
+    c = np.ascontiguousarray(_np(count))
+    assert c.dtype.itemsize == 4, c.dtype
+    return c.view(np.uint32).astype(np.int64)
+
+
+def iwe_splat_host(x, y, t, frame_event_begin, frame_ts, flow):
+    """IWE_SPEC section 2 in numpy float32: what ``iwe_splat`` runs without a
+    GPU and what the kernel is pinned to, byte for byte.  x, y int64 [n], t
+    float32 [n], frame_event_begin int64 [F+1], frame_ts float32 [2F], flow
+    float32 [F,2,h,w] -> q int64 [F,h,w]."""
+    x, y = np.asarray(x, np.int64).reshape(-1), np.asarray(y, np.int64).reshape(-1)
+    t = np.asarray(t, _F).reshape(-1)
+    begin = np.asarray(frame_event_begin, np.int64).reshape(-1)
+    ts = np.asarray(frame_ts, _F).reshape(-1)
+    flow = np.asarray(flow, _F)
+    F, _, h, w = flow.shape
+    assert begin.size == F + 1 and ts.size == 2 * F and x.size == y.size == t.size
+    q = np.zeros((F, h, w), np.int64)
+    if F == 0 or x.size == 0:
+        return q
+    e = np.arange(x.size, dtype=np.int64)
+    keep = (e >= begin[0]) & (e < begin[F]) & (x >= 0) & (x < w) & (y >= 0) & (y < h)
+    e = e[keep]
+    f = np.searchsorted(begin[:F], e, side='right') - 1     # the last f with begin[f] <= e
+    x, y, t = x[keep], y[keep], t[keep]
+    t0 = ts[2 * f]
+    d = ts[2 * f + 1] - t0
+    with np.errstate(all='ignore'):
+        tau = np.where(d > 0, np.fmin(np.fmax((t - t0) / d, _F(0)), _F(1)), _F(0)).astype(_F)
+        u, v = flow[f, 0, y, x], flow[f, 1, y, x]
+        xw = x.astype(_F) - tau * u
+        yw = y.astype(_F) - tau * v
+        inside = (xw > _F(-1)) & (xw < _F(w)) & (yw > _F(-1)) & (yw < _F(h))
+    f, xw, yw = f[inside], xw[inside], yw[inside]
+    flx, fly = np.floor(xw), np.floor(yw)
+    fx, fy = xw - flx, yw - fly
+    cx, cy = flx.astype(np.int64), fly.astype(np.int64)
+    for j, wy in enumerate((_F(1) - fy, fy)):
+        for i, wx in enumerate((_F(1) - fx, fx)):
+            xx, yy = cx + i, cy + j
+            Q = ((wy * wx).astype(_F) * _F(IWE_ONE)).astype(np.int64)    # truncates
+            ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h) & (Q > 0)
+            np.add.at(q, (f[ok], yy[ok], xx[ok]), Q[ok])
+    return q
+
+
+def iwe_stats_host(q, count):
+    """IWE_SPEC section 3 on the host -> structured array [F]
+    (IWE_RESULT_DTYPE).  The integer fields are exact; sum_sq is a float64 sum
+    of the kernel's terms in numpy's order, not the kernel's."""
+    q = np.asarray(_np(q), np.int64)
+    c = _counts(count)
+    F = q.shape[0]
+    assert q.ndim == 3 and c.shape == q.shape, (q.shape, c.shape)
+    res = np.zeros(F, IWE_RESULT_DTYPE)
+    qf, cf = q.reshape(F, -1), c.reshape(F, -1)
+    image = qf.astype(np.float64) * 2.0 ** -32
+    res['sum_sq'] = (image * image).sum(1)
+    res['sum_q'], res['max_q'] = qf.sum(1), qf.max(1, initial=0)
+    res['count_sum'], res['count_sq'] = cf.sum(1), (cf * cf).sum(1)
+    res['count_max'] = cf.max(1, initial=0)
+    return res
+
+
+def _grey_host(value, m):
+    """g = m > 0 ? min(255, (int)(value / m * 255.f + 0.5f)) : 0, float32."""
+    if not m > 0:
+        return np.zeros(value.shape, np.uint8)
+    g = (value / _F(m) * _F(255) + _F(0.5)).astype(np.int64)
+    return np.minimum(g, 255).astype(np.uint8)
+
+
+def iwe_render_host(q, count, results):
+    """IWE_SPEC section 4 in numpy float32 -> uint8 [F,h,2w,3]: the count image
+    on the left, the image of warped events on the right, each grey on its own
+    scale."""
+    q = np.asarray(_np(q), np.int64)
+    c = _counts(count)
+    res = read_iwe_results(results)
+    F, h, w = q.shape
+    canvas = np.empty((F, h, 2 * w, 3), np.uint8)
+    for f in range(F):
+        canvas[f, :, :w] = _grey_host(c[f].astype(_F), _F(res['count_max'][f]))[..., None]
+        image = (q[f].astype(np.float64) * 2.0 ** -32).astype(_F)
+        m = _F(np.float64(res['max_q'][f]) * 2.0 ** -32)
+        canvas[f, :, w:] = _grey_host(image, m)[..., None]
+    return canvas
+
+
+def iwe_splat(events, win_out, frame_ts, flow):
+    """The image of warped events of a batch of frames.  events: the collated
+    wire columns ('x', 'y' int64, 'timestamp' float32;
+    ``EventSequence.collate_frames``), win_out int64 [F+1] the first slot of
+    every frame, frame_ts float32 [2F] start and stop of every frame on the
+    clock of the timestamps, flow float32 [F,2,h,w] -> int64 [F,h,w] in units
+    of 2^-32, on the device; ``iwe_splat_host`` (a numpy array) for host
+    input."""
+    x, y, t = events['x'], events['y'], events['timestamp']
+    if not _on_device(flow):
+        return iwe_splat_host(_np(x), _np(y), _np(t), _np(win_out), _np(frame_ts), _np(flow))
+    _lib.require_cuda(x, y, t, frame_ts)
+    x, y, t = x.contiguous(), y.contiguous(), t.contiguous()
+    flow, frame_ts = flow.contiguous(), frame_ts.contiguous()
+    assert x.dtype == y.dtype == torch.long and t.dtype == flow.dtype == frame_ts.dtype == torch.float32
+    assert x.numel() == y.numel() == t.numel()
+    begin = torch.as_tensor(win_out, dtype=torch.long).to(flow.device).contiguous()
+    F, two, h, w = flow.shape
+    assert two == 2 and begin.numel() == F + 1 and frame_ts.numel() == 2 * F, \
+        (flow.shape, begin.shape, frame_ts.shape)
+    q = torch.empty(F, h, w, dtype=torch.long, device=flow.device)
+    _lib.check(_lib.lib().dvsof_iwe_splat(
+        x.data_ptr(), y.data_ptr(), t.data_ptr(), x.numel(), begin.data_ptr(),
+        frame_ts.data_ptr(), flow.data_ptr(), F, h, w, q.data_ptr(), _lib.stream()),
+        'dvsof_iwe_splat')
+    return q
+
+
+def iwe_stats(q, count):
+    """q int64 [F,h,w] (``iwe_splat``), count uint32/int32 [F,h,w]
+    (``count_image_batched`` of the same columns) -> device uint8 [F,48], one
+    dvsof_iwe_result_t per frame (``read_iwe_results`` copies it to the host);
+    for host input the rows of ``iwe_stats_host`` as a numpy uint8 [F,48]."""
+    if not _on_device(q):
+        return iwe_stats_host(q, count).view(np.uint8).reshape(-1, IWE_RESULT_DTYPE.itemsize)
+    _lib.require_cuda(count)
+    q, count = q.contiguous(), count.contiguous()
+    F, h, w = q.shape
+    assert q.dtype == torch.long and tuple(count.shape) == (F, h, w) and count.element_size() == 4
+    lib = _lib.lib()
+    out = torch.empty(F, IWE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=q.device)
+    nbytes = lib.dvsof_iwe_stats_workspace_bytes(F, h, w)
+    ws = torch.empty(max(nbytes, 48), dtype=torch.uint8, device=q.device)
+    _lib.check(lib.dvsof_iwe_stats(q.data_ptr(), count.data_ptr(), F, h, w, out.data_ptr(),
+                                   ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_iwe_stats')
+    return out
+
+
+def iwe_render(q, count, results):
+    """Per frame the count image beside the image of warped events, grey, each
+    on its own scale -> uint8 [F,h,2w,3] on the device; ``iwe_render_host`` for
+    host input.  results: the rows of ``iwe_stats`` (device uint8 [F,48])."""
+    if not _on_device(q):
+        return iwe_render_host(q, count, results)
+    _lib.require_cuda(count, results)
+    q, count, results = q.contiguous(), count.contiguous(), results.contiguous()
+    F, h, w = q.shape
+    assert q.dtype == torch.long and tuple(count.shape) == (F, h, w) and count.element_size() == 4
+    assert results.dtype == torch.uint8 and results.numel() == F * IWE_RESULT_DTYPE.itemsize
+    canvas = torch.empty(F, h, 2 * w, 3, dtype=torch.uint8, device=q.device)
+    _lib.check(_lib.lib().dvsof_iwe_render(q.data_ptr(), count.data_ptr(), results.data_ptr(),
+                                           F, h, w, canvas.data_ptr(), _lib.stream()),
+               'dvsof_iwe_render')
+    return canvas
+
+
+def read_iwe_results(results):
+    """Rows of ``iwe_stats`` -> numpy structured array [F] (IWE_RESULT_DTYPE):
+    the one device-to-host copy of a batch."""
+    a = _np(results)
+    if a.dtype == IWE_RESULT_DTYPE:
+        return a.reshape(-1)
+    return np.ascontiguousarray(a).view(IWE_RESULT_DTYPE).reshape(-1)
+
+
+def derive_fwl(res, n_pixels):
+    """-> (FWL, kept mass) float64 arrays of per-frame rows: FWL = variance of
+    the image of warped events / variance of the count image (NaN where the
+    latter is 0: no events, or the same count everywhere), kept mass = the
+    share of the events' weight that landed inside the image."""
+    n = float(n_pixels)
+    sum_i = res['sum_q'].astype(np.float64) * 2.0 ** -32
+    count_sum = res['count_sum'].astype(np.float64)
+    var_iwe = res['sum_sq'] / n - (sum_i / n) ** 2
+    var_cnt = res['count_sq'].astype(np.float64) / n - (count_sum / n) ** 2
+    with np.errstate(invalid='ignore', divide='ignore'):
+        fwl = np.where(var_cnt == 0, np.nan, var_iwe / var_cnt)
+        kept = res['sum_q'].astype(np.float64) / (count_sum * 2.0 ** 32)
+    return fwl, kept

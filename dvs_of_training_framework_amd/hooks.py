@@ -1,7 +1,8 @@
 """The two hooks of the reference's training script (utils/hooks/):
 ``SerializationHook`` checkpoints, ``ValidationHook`` runs a validation pass;
-``VisualizationHook`` (an addition) draws what the model predicts and
-``EvaluationHook`` (another) measures it against ground truth.
+``VisualizationHook`` (an addition) draws what the model predicts,
+``EvaluationHook`` (another) measures it against ground truth and
+``SharpnessHook`` without any (the flow warp loss of the warped events).
 ``training.train`` calls ``hook(step, samples_passed)`` after an optimizer
 step and times each under its dictionary name."""
 from contextlib import contextmanager
@@ -216,6 +217,104 @@ class EvaluationHook:
                     'm': float(vis.panel_scale(s))}
                 if hasattr(self.logger, 'add_image'):
                     self.logger.add_image(f'Evaluation/{k}', image, samples, dataformats='HWC')
+                out.mkdir(parents=True, exist_ok=True)
+                write_png(out / f'{k:04d}.png', image)
+                (out / f'{k:04d}.yml').write_text(yaml.dump(statistics))
+                k += 1
+
+
+def sharpness_frames(image_ts, last_event_time, step=1):
+    """The frames a label-free validation runs over: ``evaluation_frames``
+    without the ground-truth bounds.  The range begins at the first image and
+    stops at the last event; a frame spans ``step`` images:
+    zip(image_ts[b : e - step], image_ts[b + step : e])."""
+    image_ts = np.asarray(image_ts, np.float64).reshape(-1)
+    step = int(step)
+    if step < 1:
+        raise ValueError(f'a frame spans at least one image, not {step}')
+    b, e = (int(i) for i in np.searchsorted(image_ts, [image_ts[0], float(last_event_time)]))
+    n = max(e - step - b, 0)
+    return list(zip(image_ts[b:b + n].tolist(), image_ts[b + step:b + step + n].tolist()))
+
+
+class SharpnessHook:
+    """Flow warp loss of the live weights, no ground truth needed
+    (``testing.flow_warp_loss`` on a device-resident ``FrameSequence``, the
+    events cropped centrally to ``shape``; docs/IWE_SPEC.md).  Logs
+    ``Sharpness/mean FWL`` (the mean over the frames whose count image has a
+    variance; NaN if none has), ``Sharpness/mean kept mass`` and
+    ``Sharpness/frames without events``, draws ``pictures`` frames (count image
+    | image of warped events) into ``<directory>/step_<N>/<k>.png`` + ``.yml``
+    and hands them to ``logger.add_image`` where there is one.  Only rank 0
+    evaluates, and nothing in here is a collective.  The model is left as it
+    was found."""
+
+    def __init__(self, model, sequence, logger, shape, directory, frame_step=1, pictures=4,
+                 rank=0, batch_size=8):
+        self.model, self.sequence, self.logger = model, sequence, logger
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.directory, self.rank = Path(directory), rank
+        self.batch_size = int(batch_size)
+        self.frames = self.chosen = ()
+        if rank != 0:
+            return
+        if getattr(model, 'prefix_length', 0) or getattr(model, 'suffix_length', 0):
+            raise ValueError('the sharpness hook runs the model on one window per frame: '
+                             'prefix_length = suffix_length = 0')
+        from .sequence import central_box
+        self.box = tuple(central_box(sequence.shape, self.shape))
+        last = sequence.t[-1] if len(sequence) else -np.inf
+        self.frames = sharpness_frames(sequence.image_ts, last, frame_step)
+        if not self.frames:
+            raise ValueError('no frame of the validation sequence holds events')
+        self.chosen = picture_indices(len(self.frames), pictures)
+
+    def evaluate(self):
+        """-> (result rows of every frame, [(frames, their pictures)]) with the
+        model as it stands; pictures on the device."""
+        from . import eval as dev_eval, testing
+        from .of import OpticalFlow
+        of = OpticalFlow.from_model(self.model, self.shape)
+        drawn = []
+
+        def observer(first, q, count, results):
+            mine = [i for i in self.chosen if first <= i < first + q.shape[0]]
+            if not mine:
+                return
+            local = torch.tensor([i - first for i in mine], device=q.device)
+            drawn.append((mine, dev_eval.iwe_render(q[local], count[local], results[local])))
+        rows = testing.flow_warp_loss(of, self.sequence, self.frames, self.box, self.batch_size,
+                                      observer=observer)
+        return rows, drawn
+
+    def __call__(self, steps, samples):
+        if self.rank != 0:
+            return
+        from . import eval as dev_eval, visualization as vis
+        with model_left_as_found(self.model) as m:
+            m.eval()
+            with torch.no_grad():
+                rows, drawn = self.evaluate()
+        fwl, kept = dev_eval.derive_fwl(rows, self.shape[0] * self.shape[1])
+        valid = ~np.isnan(fwl)
+        has_events = rows['count_sum'] > 0
+        self.logger.add_scalar('Sharpness/mean FWL',
+                               float(fwl[valid].mean()) if valid.any() else float('nan'), samples)
+        self.logger.add_scalar('Sharpness/mean kept mass',
+                               float(kept[has_events].mean()) if has_events.any() else float('nan'),
+                               samples)
+        self.logger.add_scalar('Sharpness/frames without events', int((~has_events).sum()), samples)
+        out = self.directory / f'step_{steps}'
+        k = 0
+        for mine, images in drawn:
+            for i, image in zip(mine, vis._host(images)):
+                statistics = {
+                    'frame': i, 'start': float(self.frames[i][0]), 'stop': float(self.frames[i][1]),
+                    'FWL': float(fwl[i]), 'kept_mass': float(kept[i]),
+                    'count_max': int(rows['count_max'][i]),
+                    'iwe_max': float(rows['max_q'][i]) * 2.0 ** -32}
+                if hasattr(self.logger, 'add_image'):
+                    self.logger.add_image(f'Sharpness/{k}', image, samples, dataformats='HWC')
                 out.mkdir(parents=True, exist_ok=True)
                 write_png(out / f'{k:04d}.png', image)
                 (out / f'{k:04d}.yml').write_text(yaml.dump(statistics))

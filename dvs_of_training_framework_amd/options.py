@@ -266,6 +266,22 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         action='store_true',
                         help='outdoor driving sequence: rows from 190 on (the hood) are '
                              'not counted')
+    parser.add_argument('--sharpness-period', dest='sharpness_period', default=0,
+                        type=int,
+                        help='every this many optimizer steps measure, without ground truth, '
+                             'whether the flow of the live weights sharpens the events of '
+                             '--validation-sequence (central crop to --height x --width): '
+                             'log Sharpness/mean FWL (flow warp loss: variance of the image '
+                             'of warped events over that of the count image, > 1 is '
+                             'sharper), Sharpness/mean kept mass and Sharpness/frames '
+                             'without events, and draw --sharpness-pictures frames (count '
+                             'image | image of warped events; docs/IWE_SPEC.md) into '
+                             '<model>/sharpness/step_N/; 0: off')
+    parser.add_argument('--sharpness-frame-step', dest='sharpness_frame_step',
+                        default=1, type=int,
+                        help='images a frame of the sharpness measurement spans')
+    parser.add_argument('--sharpness-pictures', dest='sharpness_pictures', default=4,
+                        type=int)
     parser.add_argument('--sync-checkpoints', dest='sync_checkpoints',
                         action='store_true',
                         help='write checkpoints on the training thread (state_dict() + '

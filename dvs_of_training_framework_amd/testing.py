@@ -277,6 +277,53 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
     return np.concatenate(out)
 
 
+def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None):
+    """Label-free quality of ``of`` on a device-resident
+    ``sequence.EventSequence``: per frame the statistics of the image of warped
+    events and of the count image (docs/IWE_SPEC.md) as a numpy structured
+    array (eval.IWE_RESULT_DTYPE); ``eval.derive_fwl`` makes the flow warp loss
+    of them.  Per batch of frames: one ``of.flow_sequence``, one count image of
+    the collated columns, one splat, one statistics call and one copy back of
+    48 bytes per frame.
+
+    frames: [(start, stop)]; box: None or a (y0, x0, h, w) inside the frame,
+    the crop the events get (``of`` predicts at that size);
+    observer(first, q, count, results): called once per batch with the index
+    of its first frame and the device tensors."""
+    from .sequence import EventSequence, check_box
+    if not isinstance(sequence, EventSequence):
+        raise TypeError('flow_warp_loss takes a sequence.EventSequence (the events stay on '
+                        f'the device), not {type(sequence).__name__}')
+    if not hasattr(of, 'flow_sequence'):
+        raise TypeError('flow_warp_loss needs an `of` with flow_sequence (OpticalFlow)')
+    if box is not None:
+        box = check_box(box, sequence.shape)
+    frames = np.array(frames, dtype=np.float64)
+    if frames.size == 0:
+        return np.zeros(0, dev_eval.IWE_RESULT_DTYPE)
+    frames = frames.reshape(-1, 2)
+    batch_size = max(int(batch_size), 1)
+    out = []
+    for b0 in range(0, len(frames), batch_size):
+        fr = frames[b0:b0 + batch_size]
+        pred, collated = of.flow_sequence(sequence, list(fr[:, 0]), list(fr[:, 1]), box=box,
+                                          return_events=True)
+        pred = pred.to(torch.float32).contiguous()
+        h, w = pred.shape[-2:]
+        eh, ew = box[2:] if box is not None else sequence.shape
+        if (eh, ew) != (h, w):
+            raise ValueError(f'the flow is {(h, w)}, the events cover {(eh, ew)}')
+        ev = collated.events
+        count = dev_eval.count_image_batched(ev['x'], ev['y'], collated.win_out, (h, w),
+                                             (0, 0, h, w))
+        q = dev_eval.iwe_splat(ev, collated.win_out, collated.timestamps, pred)
+        res = dev_eval.iwe_stats(q, count)
+        out.append(dev_eval.read_iwe_results(res))      # the batch's one copy back
+        if observer is not None:
+            observer(b0, q, count, res)
+    return np.concatenate(out)
+
+
 def summarize(rows):
     """Per-frame result rows -> (running mean AEE, running mean share under
     3 px) float64 [F]: sums in frame order, so that a NaN (a frame without a

@@ -552,6 +552,61 @@ int dvsof_eval_panels(const float *pred, const float *gt_u, const float *gt_v,
                       void *stream);
 
 /* ------------------------------------------------------------------ *
+ * Image of warped events and flow warp loss (csrc/iwe.hip,
+ * docs/IWE_SPEC.md): label-free validation.  Every event of a frame is moved
+ * along the predicted flow to the start of its window and splatted
+ * bilinearly; FWL = variance of that image / variance of the count image.
+ * ------------------------------------------------------------------ */
+
+typedef struct {            /* 48 bytes, one per frame */
+    double  sum_sq;         /* sum over pixels of I*I, I = (double)Q * 2^-32; fixed order */
+    int64_t sum_q;          /* sum over pixels of Q (exact) */
+    int64_t max_q;          /* max over pixels of Q */
+    int64_t count_sum;      /* sum over pixels of c (exact) */
+    int64_t count_sq;       /* sum over pixels of c*c (exact) */
+    int64_t count_max;
+} dvsof_iwe_result_t;
+
+/*
+ * Events [begin[f], begin[f+1]) of the wire columns x, y, t (n_events entries)
+ * belong to frame f; events outside [begin[0], begin[F]) and events with x or
+ * y outside the image (the -1 slots of cropped and padded events) are skipped.
+ *   frame_ts   float32[2F]: start and stop of every frame on the clock of t
+ *   flow       float32[F,2,h,w], read at the event's own pixel
+ *   q          int64[F,h,w], zeroed by the call: bilinear weights in units of
+ *              2^-32, summed by integer atomics (exact in any order)
+ * tau = clamp((t - start) / (stop - start), 0, 1), 0 for stop <= start; the
+ * event lands at (x - tau u, y - tau v); corners outside the image and events
+ * whose warped position is not inside (-1, w) x (-1, h) are dropped.
+ * DVSOF_EINVAL before any launch: F < 0 or > 65535, n_events < 0, h or w
+ * outside [1, 32767], null pointers.  F == 0: nothing to do.
+ */
+int dvsof_iwe_splat(const int64_t *x, const int64_t *y, const float *t, int64_t n_events,
+                    const int64_t *frame_event_begin, const float *frame_ts /* [2F]: start, stop */,
+                    const float *flow /* [F,2,h,w] */, int F, int h, int w,
+                    int64_t *q /* [F,h,w] */, void *stream);
+
+/*
+ * One dvsof_iwe_result_t per frame from q and the count image of the same
+ * events (dvsof_count_image_batched).  Two launches: per-block partials in
+ * `workspace`, then one closing wave per frame; the order is fixed and there
+ * are no floating-point atomics: same input, same bits.  DVSOF_EINVAL as
+ * above; DVSOF_ENOSPACE: the workspace is missing or too small.
+ */
+size_t dvsof_iwe_stats_workspace_bytes(int F, int h, int w);
+int dvsof_iwe_stats(const int64_t *q, const uint32_t *count /* [F,h,w] */, int F, int h, int w,
+                    dvsof_iwe_result_t *result, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Per frame two grey panels side by side, the count image on the left and the
+ * image of warped events on the right, each scaled to its own maximum
+ * (count_max, max_q of `result`).  One launch; every byte of the canvas is
+ * written exactly once.
+ */
+int dvsof_iwe_render(const int64_t *q, const uint32_t *count, const dvsof_iwe_result_t *result,
+                     int F, int h, int w, uint8_t *canvas /* [F,h,2w,3] */, void *stream);
+
+/* ------------------------------------------------------------------ *
  * Device-resident event sequence -> wire-format batch
  * (docs/SEQUENCE_SPEC.md)
  * ------------------------------------------------------------------ */

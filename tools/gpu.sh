@@ -18,6 +18,9 @@
 #   evalhook [eval_bench.py args]    the evaluation hook (tools/eval_bench.py --hook): polarity count and the panel
 #                                     launch pair alone at F = 8, 256x256, against the numpy restatement on the host;
 #                                     one hook call over 200 frames against the step time of the same run
+#   iwe [iwe_bench.py args]          label-free validation (tools/iwe_bench.py): splat, statistics and render alone at
+#                                     F = 8, 256x256, 30 000 and 120 000 events per frame, the splat's atomic bytes/s;
+#                                     testing.flow_warp_loss against the same frames' inference alone
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -77,6 +80,9 @@ eval)
 evalhook)
   timeout -k 10 560 env "${envs[@]}" python tools/eval_bench.py --hook "$@" > $O/eval_hook.json 2> $O/eval_hook.err
   echo "evalhook rc=$?"; cut -c1-2600 $O/eval_hook.json; tail -3 $O/eval_hook.err ;;
+iwe)
+  timeout -k 10 560 env "${envs[@]}" python tools/iwe_bench.py "$@" > $O/iwe.json 2> $O/iwe.err
+  echo "iwe rc=$?"; cut -c1-2600 $O/iwe.json; tail -3 $O/iwe.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

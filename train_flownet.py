@@ -35,7 +35,7 @@ from dvs_of_training_framework_amd.options import (
     add_train_arguments, add_preprocessed_dataset_arguments, guard_requested,
     resolve_step_guard, validate_train_args)
 from dvs_of_training_framework_amd.hooks import EvaluationHook, \
-    SerializationHook, ValidationHook, VisualizationHook
+    SerializationHook, SharpnessHook, ValidationHook, VisualizationHook
 from dvs_of_training_framework_amd.serializer import Serializer
 from dvs_of_training_framework_amd.timer import EventTimer, FakeTimer
 from dvs_of_training_framework_amd.training import HostGuard, \
@@ -334,6 +334,27 @@ def add_evaluation(args, hooks, periodic, model, device, logger, rank):
     periodic['evaluation'] = make_hook_periodic(hooks['evaluation'], args.evaluation_period)
 
 
+def add_sharpness(args, hooks, periodic, model, device, logger, rank):
+    """--sharpness-period N > 0: a ``SharpnessHook`` every N optimizer steps
+    (flow warp loss of the validation sequence's own events, and pictures; no
+    ground truth).  0 constructs nothing.  Rank 0 alone holds the sequence,
+    and shares the one an ``EvaluationHook`` has already uploaded."""
+    if getattr(args, 'sharpness_period', 0) <= 0:
+        return
+    if getattr(args, 'validation_sequence', None) is None:
+        raise SystemExit('--sharpness-period needs --validation-sequence')
+    sequence = None
+    if rank == 0:
+        sequence = getattr(hooks.get('evaluation'), 'sequence', None)
+        if sequence is None:
+            from dvs_of_training_framework_amd.sequence import FrameSequence
+            sequence = FrameSequence.from_directory(args.validation_sequence, device)
+    hooks['sharpness'] = SharpnessHook(
+        model, sequence, logger, args.shape, args.model / 'sharpness',
+        frame_step=args.sharpness_frame_step, pictures=args.sharpness_pictures, rank=rank)
+    periodic['sharpness'] = make_hook_periodic(hooks['sharpness'], args.sharpness_period)
+
+
 def restore_loader(loader, state, rank, world, global_step, args):
     """Position ``loader`` from the checkpoint's ``loader_state`` (a list
     indexed by rank); a checkpoint without one (the reference's) positions by
@@ -447,6 +468,7 @@ def main(argv=None):
              '--synthetic-validation-batches with --synthetic): validation is skipped')
     add_visualization(args, hooks, periodic, model, device, logger, losses, rank)
     add_evaluation(args, hooks, periodic, model, device, logger, rank)
+    add_sharpness(args, hooks, periodic, model, device, logger, rank)
 
     try:
         if not resume:
