@@ -31,9 +31,12 @@ class Logger:
 @pytest.fixture(scope='module')
 def case():
     from dvs_of_training_framework_amd.sequence import FrameSequence
-    # 3000 events per frame: every batch stays at the event count from which the voxeliser is
-    # the tiled, order-independent kernel, so the same weights give the same bits
-    c = ec.make_eval_case(per_frame=3000)
+    # 4000 events per frame of time-uniform events: the six frames the hook takes differ in
+    # length and hold 4655, 1126, 5432, 6037, 1183 and 3628 of them, so every batch of 3, 4 or 8
+    # frames stays at the 4096 events from which the voxeliser is the tiled, order-independent
+    # kernel, and the same weights give the same bits.  (With 3000 the closing batch of a batch
+    # size of 4 held 3580 and ran the float-atomics kernel: tests/test_gpu_network_repeat.py.)
+    c = ec.make_eval_case(per_frame=4000)
     image_ts = np.append(c['frames'][:, 0], c['frames'][-1, 1])
     images = np.random.default_rng(4).integers(0, 256, (len(image_ts),) + ec.EVAL_SHAPE).astype(np.uint8)
     seq = FrameSequence([col for col in c['events']], images, image_ts, device=DEV)
@@ -92,11 +95,10 @@ def test_hook_logs_what_evaluate_returns_and_draws_what_eval_panels_draws(case, 
     assert np.isfinite(want[0]) and 0 < want[1] < 1
 
     # an observer changes no result row, and sees what the metric saw
-    # (the network's last bits depend on the batch it runs in: 3 shows the call per batch, the
-    # hook's own 8 is what its pictures and statistics are compared at.  Not 4: the closing
-    # batch of two frames of 32 x 64 does not repeat its own bits from one call to the next,
-    # observer or not)
-    for batch_size, firsts in ((3, [0, 3]), (hook.batch_size, [0])):
+    # (the network's last bits depend on the batch it runs in: 3 and 4 show the call per batch --
+    # 4 closes with a batch of two frames --, the hook's own 8 is what its pictures and
+    # statistics are compared at)
+    for batch_size, firsts in ((3, [0, 3]), (4, [0, 4]), (hook.batch_size, [0])):
         seen = []
         plain = testing.evaluate_frames(of, seq, hook.frames, gt, **CROPS, batch_size=batch_size)
         rows = testing.evaluate_frames(

@@ -227,9 +227,14 @@ def exact_sequence():
 
 def test_flow_warp_loss_in_batches_of_one_and_of_eight(exact_sequence):
     """With the network itself the rows of two batch sizes differ: its last bits depend on the
-    batch it runs in (at batch 1 it does not even repeat its own; measured on the MI355X with
-    the model of the test above, all 7 frames differ in sum_q).  What flow_warp_loss adds to
-    that must not depend on the batch: a predictor that answers per frame, exact times."""
+    batch it runs in (measured on the MI355X with the model of the test above, all 7 frames
+    differ in sum_q between batches of one and of eight).  At batch 1 most frames do not even
+    repeat their own bits, and that is the voxeliser, not the network: five of the seven frames
+    hold fewer than 4096 events (3503, 856, 4048, 4539, 877, 2703, 4176), so their calls run the
+    thread-per-event kernel with float atomics, the documented order-dependent path
+    (docs/VOXEL_SPEC.md; tests/test_gpu_network_repeat.py pins that every call of 4096 events
+    or more repeats).  What flow_warp_loss adds to that must not depend on the batch: a
+    predictor that answers per frame, exact times."""
     sequence = exact_sequence
     frames = ec.EVAL_FRAMES
     rng = np.random.default_rng(3)

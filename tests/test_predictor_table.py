@@ -63,6 +63,37 @@ def test_table_names_units_and_params():
     assert {l.unit: l.params for l in LAYERS} == UNIT_PARAMS
 
 
+@pytest.mark.parametrize('bins', [3, 5])
+def test_small_network_layer_cases_are_the_table_at_every_small_frame(bins):
+    """tests/network_cases.layer_cases (what test_gpu_network_layers.py runs) against the table
+    read here directly: every layer once, each decoder stage with a flow member a second time
+    without it, frames H >> shift, nothing else."""
+    from dvs_of_training_framework_amd import conv as C
+    from tests import network_cases as nc
+    assert nc.SMALL_FRAMES == ((1, 32, 64), (2, 32, 64), (3, 32, 64), (2, 64, 64), (2, 32, 48))
+    for B, H, W in nc.SMALL_FRAMES:
+        want = []
+        for li, l in enumerate(LAYERS):
+            src = [(c or bins, 'nchw' if lay == C.NCHW else 'nhwc') for c, lay in l.srcs]
+            for members, tag in ((src, ''), (src[:2], '/folded')) if len(src) == 3 else ((src, ''),):
+                want.append(dict(B=B, H=H >> l.shift, W=W >> l.shift, src=members, Cout=l.cout,
+                                 stride=l.stride, up=l.up, residual=l.residual is not None,
+                                 act='relu', name=l.name + tag, layer=li))
+        got = nc.layer_cases(B, H, W, bins)
+        # the residual blocks' first layers are one shape: kept once
+        uniq = []
+        for c in want:
+            if not any(nc._key(c) == nc._key(u) for u in uniq):
+                uniq.append(c)
+        assert got == uniq
+        assert len(got) == 13 and [c['name'] for c in got if c['name'].startswith('dec')] == [
+            'dec.0', 'dec.1', 'dec.1/folded', 'dec.2', 'dec.2/folded', 'dec.3', 'dec.3/folded']
+        assert min(min(c['H'], c['W']) for c in got) == min(H, W) >> 4
+        assert got[0]['src'] == [(bins, 'nchw')]
+    ids = [nc.case_id(c) for c in nc.all_layer_cases()]
+    assert len(set(ids)) == len(ids)
+
+
 @pytest.mark.parametrize('cin,frame,flops', [(5, (256, 256), 26213351424),
                                              (5, (96, 160), 6143754240),
                                              (10, (256, 256), 26307723264),
