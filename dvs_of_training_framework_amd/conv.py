@@ -8,75 +8,17 @@ import torch
 
 from . import _lib
 
-_vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+_vp = ctypes.c_void_p
+_C = _lib.CONSTANTS
 
-ACT_NONE, ACT_RELU, ACT_MISH = 0, 1, 2
-NHWC, NCHW = 0, 1
+ACT_NONE, ACT_RELU, ACT_MISH = _C['DVSOF_ACT_NONE'], _C['DVSOF_ACT_RELU'], _C['DVSOF_ACT_MISH']
+NHWC, NCHW = _C['DVSOF_NHWC'], _C['DVSOF_NCHW']
+WGRAD_SKIP_FLAT = _C['DVSOF_CONV_WGRAD_SKIP_FLAT']
 
-
-class Src(ctypes.Structure):
-    """dvsof_src_t"""
-    _fields_ = [('p', _vp), ('C', _i), ('layout', _i), ('p16', _vp)]
-
-
-class ConvDesc(ctypes.Structure):
-    """dvsof_conv_desc_t"""
-    _fields_ = [('src', Src * 3), ('nsrc', _i), ('B', _i), ('H', _i),
-                ('W', _i), ('upsample', _i), ('ksize', _i), ('stride', _i),
-                ('pad', _i), ('Cout', _i), ('act', _i), ('mfma', _i),
-                ('scratch', _vp), ('scratch_bytes', _sz),
-                ('winograd_input', _vp), ('y16', _vp), ('w16', _vp),
-                ('gout16', _vp), ('flags', _i), ('bias_cls', _vp),
-                ('winograd_pre', _vp), ('winograd_next', _vp),
-                ('winograd_next_gout', _vp), ('winograd_gout', _vp)]
-
-
-class GradDst(ctypes.Structure):
-    """dvsof_grad_dst_t"""
-    _fields_ = [('p', _vp), ('addend', _vp), ('addend2', _vp),
-                ('actsrc', _vp), ('p16', _vp), ('head_w', _vp),
-                ('head_gflow', _vp), ('head_x', _vp), ('head_part', _vp)]
-
-
-_P = ctypes.POINTER
-_lib.register('dvsof_conv2d_fwd', _i, [_P(ConvDesc), _vp, _vp, _vp, _vp, _vp,
-                                       _vp])
-_lib.register('dvsof_conv2d_dgrad', _i, [_P(ConvDesc), _vp, _vp, _P(GradDst),
-                                         _i, _vp])
-_lib.register('dvsof_conv2d_wgrad_workspace_bytes', _sz, [_P(ConvDesc)])
-_lib.register('dvsof_conv2d_dgrad_fuses_head', _i, [_P(ConvDesc)])
-_lib.register('dvsof_conv2d_dgrad_head_rows', _i, [_P(ConvDesc)])
-_lib.register('dvsof_flow_head_reduce', _i, [_vp, _i, _i, _vp, _vp, _vp])
-_lib.register('dvsof_conv2d_wgrad', _i, [_P(ConvDesc), _vp, _vp, _vp, _vp,
-                                         _sz, _vp])
-_lib.register('dvsof_weight_flip_transpose', _i, [_vp, _vp, _i, _i, _i, _vp])
-_lib.register('dvsof_flow_head_fwd', _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i,
-                                          _vp])
-_lib.register('dvsof_flow_head_bwd_workspace_bytes', _sz, [_i, _i, _i, _i])
-_lib.register('dvsof_flow_head_bwd', _i, [_vp, _vp, _vp, _vp, _vp, _i, _vp,
-                                          _vp, _vp, _i, _i, _i, _i, _vp, _sz,
-                                          _vp, _vp])
-_lib.register('dvsof_to_bf16', _i, [_vp, _vp, _sz, _vp])
-_lib.register('dvsof_act_bwd', _i, [_vp, _vp, _i, _vp, _sz, _vp])
-_lib.register('dvsof_conv2d_tile_id', _i, [_P(ConvDesc), _i])
-_lib.register('dvsof_conv2d_kernel_generation', _i, [_P(ConvDesc), _i])
-_lib.register('dvsof_conv2d_last_patch', _i, [_i])
-_lib.register('dvsof_conv2d_last_kernel', _i, [_i])
-_lib.register('dvsof_conv2d_fwd_weight_elems', _sz, [_P(ConvDesc)])
-_lib.register('dvsof_conv2d_dgrad_weight_elems', _sz, [_P(ConvDesc)])
-_lib.register('dvsof_conv2d_prepare', _i, [_P(ConvDesc), _vp, _vp, _vp, _vp])
-_lib.register('dvsof_conv2d_prepare16', _i, [_P(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.register('dvsof_to_bf16_many', _i, [_P(_vp), _P(_vp), _P(ctypes.c_size_t), _i, _vp])
-_lib.register('dvsof_conv2d_scratch_bytes', _sz, [_P(ConvDesc)])
-_lib.register('dvsof_flow_fold_weights', _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp])
-_lib.register('dvsof_flow_fold_workspace_bytes', _sz, [_i, _i])
-_lib.register('dvsof_flow_fold_bias', _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
-_lib.register('dvsof_flow_fold_grads', _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp,
-                                            _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp])
-WGRAD_SKIP_FLAT = 1
-_lib.register('dvsof_conv2d_winograd_tile', _i, [_P(ConvDesc), _i])
-_lib.register('dvsof_conv2d_winograd_chain', _i, [_P(ConvDesc), _i])
-
+# ctypes Structures laid out by the header
+Src = _lib.STRUCTS['dvsof_src_t']
+ConvDesc = _lib.STRUCTS['dvsof_conv_desc_t']
+GradDst = _lib.STRUCTS['dvsof_grad_dst_t']
 
 MFMA_F32, MFMA_BF16, MFMA_BF16X3, MFMA_BF16_TWINS = 0, 1, 2, 3
 
@@ -115,13 +57,12 @@ def to_bf16_many(tensors):
 
 UP_NONE, UP_NEAREST, UP_ZERO = 0, 1, 2     # dvsof_conv_desc_t.upsample
 
-# kernel families (include/dvsof.h DVSOF_KERNEL_*), as dvsof_conv2d_last_kernel reports them
-(K_NONE, K_GENERAL_V1, K_GENERAL_V2, K_FLAT_VALU, K_FIRST, K_WINO2, K_WINO4, K_FWD_MIN4,
- K_FWD_MIN8, K_FWD_PATCH, K_DGRAD_MIN0, K_DGRAD_MIN1, K_DGRAD_MIN2, K_WGRAD_PATCH, K_WGRAD_MIN,
- K_TRANSPOSED, K_STRIDE2_PHASED) = range(17)
-KERNEL_NAMES = ('none', 'general_v1', 'general_v2', 'flat_valu', 'first', 'wino2', 'wino4',
-                'fwd_min4', 'fwd_min8', 'fwd_patch', 'dgrad_min0', 'dgrad_min1', 'dgrad_min2',
-                'wgrad_patch', 'wgrad_min', 'transposed', 'stride2_phased')
+# kernel families (include/dvsof.h DVSOF_KERNEL_*), as dvsof_conv2d_last_kernel reports them:
+# K_NONE, K_GENERAL_V1, ... and their lower-cased names in value order
+_KERNELS = sorted((v, k[len('DVSOF_KERNEL_'):]) for k, v in _C.items() if k.startswith('DVSOF_KERNEL_'))
+assert [v for v, _ in _KERNELS] == list(range(len(_KERNELS)))
+globals().update(('K_' + name, v) for v, name in _KERNELS)
+KERNEL_NAMES = tuple(name.lower() for _, name in _KERNELS)
 
 
 def last_kernel(kind):
@@ -415,10 +356,6 @@ def head_fwd(x, w, bias, B, H, W, C):
     return flow
 
 
-_lib.register('dvsof_flow_heads_fwd', _i, [_i, _P(_vp), _P(_vp), _P(_vp), _P(_vp), _i,
-                                           _P(_i), _P(_i), _P(_i), _vp])
-
-
 def heads_fwd(items, B, out=None):
     """items: [(x NHWC, w, bias, H, W, C)] (at most 4) -> [flow NCHW] from ONE
     launch (dvsof_flow_heads_fwd); ``out``: preallocated flow tensors."""
@@ -427,7 +364,7 @@ def heads_fwd(items, B, out=None):
         torch.empty(B, 2, H, W, dtype=torch.float32, device=x.device)
         for x, _, _, H, W, _ in items]
     arr = lambda ts: (_vp * n)(*[_lib.ptr(t) for t in ts])        # noqa: E731
-    ints = lambda k: (_i * n)(*[it[k] for it in items])             # noqa: E731
+    ints = lambda k: (ctypes.c_int * n)(*[it[k] for it in items])   # noqa: E731
     _lib.check(_lib.lib().dvsof_flow_heads_fwd(
         n, arr([it[0] for it in items]), arr([it[1] for it in items]),
         arr([it[2] for it in items]), arr(flows), B, ints(3), ints(4), ints(5),

@@ -17,15 +17,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._abi import dtype_of
 
-F32, F64 = 0, 1         # DVSOF_EVAL_F32 / DVSOF_EVAL_F64
+F32, F64 = _lib.CONSTANTS['DVSOF_EVAL_F32'], _lib.CONSTANTS['DVSOF_EVAL_F64']
 DIRECT, PROPAGATE = 1, 0
 CAR_ROWS = 190          # utils/eval.py:18-19: the hood of the car is below
 
-# dvsof_eval_result_t
-RESULT_DTYPE = np.dtype([('sum_ee', '<f8'), ('n_points', '<i8'),
-                         ('n_below', '<i8'), ('pred_max', '<f4'),
-                         ('pred_min', '<f4')])
+RESULT_DTYPE = dtype_of('dvsof_eval_result_t')   # sum_ee, n_points, n_below, pred_max, pred_min
 assert RESULT_DTYPE.itemsize == 32
 
 
@@ -270,10 +268,8 @@ def estimate_corresponding_gt_flow(x_flow_in, y_flow_in, gt_timestamps,
 # ---------------------------------------------------------------------------
 # Image of warped events and flow warp loss (csrc/iwe.hip, docs/IWE_SPEC.md)
 # ---------------------------------------------------------------------------
-# dvsof_iwe_result_t
-IWE_RESULT_DTYPE = np.dtype([('sum_sq', '<f8'), ('sum_q', '<i8'), ('max_q', '<i8'),
-                             ('count_sum', '<i8'), ('count_sq', '<i8'),
-                             ('count_max', '<i8')])
+# sum_sq, sum_q, max_q, count_sum, count_sq, count_max
+IWE_RESULT_DTYPE = dtype_of('dvsof_iwe_result_t')
 assert IWE_RESULT_DTYPE.itemsize == 48
 IWE_ONE = 1 << 32       # the fixed-point unit of q
 _F = np.float32

@@ -19,34 +19,9 @@ import torch
 
 from . import _lib
 
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_lib.register('dvsof_adamw_chunk_elems', _i, [])
-_lib.register('dvsof_adamw_step', _i, [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f,
-                                       _i, _i, _vp])
-_lib.register('dvsof_adamw_dynamic', None, [_f, _f, _f, _i, ctypes.POINTER(_f)])
-_lib.register('dvsof_adamw_set_dynamic', _i, [_vp, ctypes.POINTER(_f), _i, _vp])
-_lib.register('dvsof_adamw_step_dyn', _i, [_vp, _vp, _vp, _i, _vp, _f, _f, _f,
-                                           _f, _i, _vp])
-_lib.register('dvsof_radam_step', _i, [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f,
-                                       _i, _f, _i, _i, _f, _vp])
-_lib.register('dvsof_radam_dynamic', None, [_f, _f, _f, _i, _f, _i, _i,
-                                            ctypes.POINTER(_f)])
-_lib.register('dvsof_radam_step_dyn', _i, [_vp, _vp, _vp, _i, _vp, _f, _f, _f,
-                                           _f, _f, _vp])
-_lib.register('dvsof_grad_centralize', _i, [_vp, _i, _i, _vp])
-_lib.register('dvsof_grad_centralize_multi', _i, [_vp, _i, _vp])
-_lib.register('dvsof_grad_guard_record_bytes', _i, [])
-_lib.register('dvsof_grad_guard_partial_bytes', _i, [])
-_lib.register('dvsof_grad_guard', _i, [_vp, _i, _vp, _vp, _i, _vp, ctypes.c_size_t,
-                                       ctypes.c_double, _i, _vp, _vp])
-# the guarded twins: the arguments of the unguarded entry point, the guard record, the stream
-for _name in ('dvsof_adamw_step', 'dvsof_adamw_step_dyn', 'dvsof_radam_step',
-              'dvsof_radam_step_dyn'):
-    _res, _args = _lib._SIGNATURES[_name]
-    _lib.register(_name + '_guarded', _res, _args[:-1] + [_vp, _args[-1]])
 GUARD_FIELDS = ('scale', 'skip', 'norm', 'bad', 'skipped', 'clipped', 'consecutive')
-_GUARD_STRUCT = '<fIdIIII'      # the record of include/dvsof.h, 32 bytes
-from . import snapshot as _snapshot  # noqa: E402,F401  (registers dvsof_snapshot_*: the state's way out)
+_GUARD_STRUCT = '<fIdIIII'      # the record of include/dvsof.h
+assert struct.calcsize(_GUARD_STRUCT) == _lib.CONSTANTS['DVSOF_GUARD_RECORD_BYTES']
 
 
 class _FusedBase(torch.optim.Optimizer):

@@ -204,13 +204,14 @@ class GradReducer:
                        'dvsof_comm_create_loopback')
             return comm
         rank = dist.get_rank(self.group) if dist.is_initialized() else 0
-        ident = ctypes.create_string_buffer(128)
+        id_bytes = _lib.CONSTANTS['DVSOF_COMM_ID_BYTES']
+        ident = ctypes.create_string_buffer(id_bytes)
         if rank == 0:
             _lib.check(lib.dvsof_comm_unique_id(ident), 'dvsof_comm_unique_id')
         if self.world > 1:
             box = [ident.raw]
             dist.broadcast_object_list(box, src=0, group=self.group)
-            ident = ctypes.create_string_buffer(box[0], 128)
+            ident = ctypes.create_string_buffer(box[0], id_bytes)
         with _stdout_to_stderr():        # RCCL's banner, as in init_distributed
             _lib.check(lib.dvsof_comm_create(ctypes.byref(comm), self.world, rank,
                                              ident), 'dvsof_comm_create')
@@ -241,7 +242,8 @@ class GradReducer:
             # goes; the step executor issues it on every replay (csrc/exec.hip)
             from . import _lib
             _lib.check(_lib.lib().dvsof_exec_mark(
-                1, self._marked, flat.data_ptr(), flat.numel(), _lib.stream()),
+                _lib.CONSTANTS['DVSOF_MARK_BUCKET'], self._marked, flat.data_ptr(), flat.numel(),
+                _lib.stream()),
                 'dvsof_exec_mark')
             if after is not None:
                 # optim.fuse_into_backward: this bucket's update is captured ON THE EXCHANGE
@@ -259,7 +261,8 @@ class GradReducer:
                 with torch.cuda.stream(side):
                     side.wait_event(ev)
                     _lib.check(_lib.lib().dvsof_exec_mark(
-                        3, self._marked, flat.data_ptr(), flat.numel(), _lib.stream()),
+                        _lib.CONSTANTS['DVSOF_MARK_WAIT'], self._marked, flat.data_ptr(),
+                        flat.numel(), _lib.stream()),
                         'dvsof_exec_mark')
                     after()
                 self._capture_branch = side
@@ -316,8 +319,8 @@ class GradReducer:
             branch, self._capture_branch = getattr(self, '_capture_branch', None), None
             if branch is not None:      # the updates captured on the exchange stream join here
                 torch.cuda.current_stream().wait_stream(branch)
-            _lib.check(_lib.lib().dvsof_exec_mark(2, 0, None, 0, _lib.stream()),
-                       'dvsof_exec_mark')
+            _lib.check(_lib.lib().dvsof_exec_mark(_lib.CONSTANTS['DVSOF_MARK_JOIN'], 0, None, 0,
+                                                  _lib.stream()), 'dvsof_exec_mark')
             self._marked = 0
             return
         for item in self.pending:

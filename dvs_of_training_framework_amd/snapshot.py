@@ -8,18 +8,12 @@ thread) waits on the ticket's event and rebuilds the tensors on the host.
 PyTorch is plumbing here: memory, streams, events.
 """
 import copy
-import ctypes
 
 import torch
 
 from . import _lib
 
-_vp, _i = ctypes.c_void_p, ctypes.c_int
-_lib.register('dvsof_snapshot_chunk_elems', _i, [])
-_lib.register('dvsof_snapshot_header_bytes', _i, [])
-_lib.register('dvsof_snapshot_pack', _i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp])
-
-HEADER_FLOATS = 4       # DVSOF_SNAPSHOT_HEADER_BYTES / 4
+HEADER_FLOATS = _lib.CONSTANTS['DVSOF_SNAPSHOT_HEADER_BYTES'] // 4
 ALIGN_FLOATS = 4        # destination offsets are multiples of 16 bytes
 
 

@@ -20,18 +20,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._abi import dtype_of
 
-FLOW, FRAME, FILL = 0, 1, 2     # DVSOF_RENDER_*
-MAX_CHUNKS = 64                 # DVSOF_RENDER_MAX_CHUNKS
+FLOW, FRAME, FILL = (_lib.CONSTANTS['DVSOF_RENDER_' + k] for k in ('FLOW', 'FRAME', 'FILL'))
+MAX_CHUNKS = _lib.CONSTANTS['DVSOF_RENDER_MAX_CHUNKS']
 CHUNK_PIXELS = 2048
 
-# dvsof_render_item_t / dvsof_render_stats_t
-ITEM_DTYPE = np.dtype([('src', '<u8'), ('dst_offset', '<i8'), ('dst_stride', '<i8'),
-                       ('kind', '<i4'), ('image', '<i4'), ('h', '<i4'), ('w', '<i4'),
-                       ('x0', '<i4'), ('y0', '<i4'), ('row0', '<i4'), ('rows', '<i4'),
-                       ('chunk', '<i4'), ('chunks', '<i4')])
-STATS_DTYPE = np.dtype([('lo', '<f4'), ('hi', '<f4'), ('nonfinite', '<i4'),
-                        ('reserved', '<i4')])
+# src, dst_offset, dst_stride, kind, image, h, w, x0, y0, row0, rows, chunk, chunks
+ITEM_DTYPE = dtype_of('dvsof_render_item_t')
+STATS_DTYPE = dtype_of('dvsof_render_stats_t')       # lo, hi, nonfinite, reserved
 assert ITEM_DTYPE.itemsize == 64 and STATS_DTYPE.itemsize == 16
 
 _F = np.float32
@@ -416,10 +413,8 @@ def visualize(args, batch, loss, parts, weights, prediction):
 
 
 # ------------------------------------------------------ evaluation panels
-# dvsof_eval_panel_stats_t
-PANEL_STATS_DTYPE = np.dtype([('pred_lo', '<f4'), ('pred_hi', '<f4'), ('pred_nonfinite', '<i4'),
-                              ('gt_lo', '<f4'), ('gt_hi', '<f4'), ('gt_nonfinite', '<i4'),
-                              ('n_counted', '<i4'), ('n_below', '<i4')])
+# pred_lo, pred_hi, pred_nonfinite, gt_lo, gt_hi, gt_nonfinite, n_counted, n_below
+PANEL_STATS_DTYPE = dtype_of('dvsof_eval_panel_stats_t')
 assert PANEL_STATS_DTYPE.itemsize == 32
 UNCOUNTED = 64                  # grey of a pixel the metric does not count
 PANELS = ('events', 'prediction', 'ground truth', 'endpoint error')

@@ -30,7 +30,7 @@ def get_count_image(events, imsize, device='cuda'):
     return out.cpu().numpy().astype(np.uint32).astype(np.uint64)
 
 
-WS_CLEAN = 1       # DVSOF_VOX_WS_CLEAN
+WS_CLEAN = _lib.CONSTANTS['DVSOF_VOX_WS_CLEAN']
 _WORKSPACES = {}
 _WS_ROUND = 1 << 16
 
