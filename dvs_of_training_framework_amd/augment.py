@@ -35,7 +35,10 @@ def augment_batch(batch, is_flip, angle, box, device='cuda'):
     device.  is_flip bool[B], angle (degrees) float[B], box int[B,4] =
     (y0, x0, h, w), same (h, w) for every sample.  -> new batch dict (device
     tensors): cropped float32 'images' [D,1,h,w], events with mapped x / y,
-    'augmentation_params' updated with box / angle / is_flip."""
+    'augmentation_params' updated with box / angle / is_flip.
+    'sample_idx' values must lie in [0, B): a host tensor is checked
+    (ValueError), a device tensor is the caller's precondition.  The exact
+    contract: docs/AUGMENT_SPEC.md."""
     dev = torch.device(device)
     is_flip = np.asarray(is_flip, bool).reshape(-1)
     angle = np.asarray(angle, np.float64).reshape(-1)
@@ -51,6 +54,14 @@ def augment_batch(batch, is_flip, angle, box, device='cuda'):
         (box[:, 0] + h <= H).all() and (box[:, 1] + w <= W).all(), \
         'crop box outside the frame'
     D = images.numel() // (H * W)
+    # the frames kernel indexes box / cos_sin / flip with sample_idx[d]
+    # unchecked (docs/AUGMENT_SPEC.md section 7): a host table is checked here, where it
+    # costs no sync; a device table is the caller's precondition
+    sidx = batch['sample_idx']
+    assert sidx.numel() == D
+    if not sidx.is_cuda and D and (int(sidx.min()) < 0 or int(sidx.max()) >= B):
+        raise ValueError(f'sample_idx outside [0, {B}): '
+                         f'min {int(sidx.min())}, max {int(sidx.max())}')
     src = images.to(dev).reshape(D, H, W).contiguous()
     if src.dtype not in (torch.uint8, torch.float32):
         src = src.float()
@@ -59,8 +70,7 @@ def augment_batch(batch, is_flip, angle, box, device='cuda'):
     cs = torch.from_numpy(np.stack([np.cos(rad), np.sin(rad)], 1)).to(dev)
     flip_d = torch.from_numpy(is_flip.astype(np.uint8)).to(dev)
     box_d = torch.from_numpy(box.astype(np.int32)).to(dev)
-    frame_sample = batch['sample_idx'].to(dev, torch.int32).contiguous()
-    assert frame_sample.numel() == D
+    frame_sample = sidx.to(dev, torch.int32).contiguous()
     lib, st = _lib.lib(), _lib.stream()
     out = torch.empty(D, 1, h, w, dtype=torch.float32, device=dev)
     _lib.check(lib.dvsof_augment_frames(

@@ -11,6 +11,12 @@
 // pixel; an event there moves to the SMALLEST such pixel (atomicMin while the
 // LUT is built) -- the native map's rule is unknown (source absent).
 //
+// The exact contract (operation order, ties, LUT rule, dropped events, argument
+// rules) is docs/AUGMENT_SPEC.md; tests/test_gpu_augment_exact.py pins every
+// pixel, entry and event of it.  frame_sample[d] must lie in [0, B): the frames
+// kernel is not told B and indexes flip / cs / box with it unchecked (spec
+// section 7; augment.augment_batch checks a host-resident table).
+//
 // HBM-bound, trivially parallel: one thread per output pixel / event.
 #include "common.h"
 

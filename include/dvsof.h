@@ -290,7 +290,9 @@ int dvsof_augment_lut(const double *cos_sin, int B, int H, int W, int32_t *lut,
                       void *stream);
 
 /* dst f32[D,h,w] = crop(rotate(flip(src[D,H,W]))); src is u8 or f32;
- * frame_sample i32[D] = sample of every frame.  utils/dataset.py:755-757,
+ * frame_sample i32[D] = sample of every frame, each in [0, B): the call does
+ * not know B and reads flip / cos_sin / box there unchecked
+ * (docs/AUGMENT_SPEC.md section 7).  utils/dataset.py:755-757,
  * utils/data.py:203-206 (rimages), utils/data.py:45-75 (crop). */
 int dvsof_augment_frames(const void *src, int src_is_u8, int D, int H, int W,
                          const int32_t *frame_sample, const uint8_t *flip,

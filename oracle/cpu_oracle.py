@@ -209,6 +209,15 @@ def voxelize(events, t0, t1, B, C, H, W):
 # rotated pixels read the same source pixel (events there go to the SMALLEST
 # such pixel index -- this file's rule); bijective cases (multiples of 90
 # degrees) are pinned by tests/dataset/test_dataset.py:76-170.
+# BLAS CAVEAT: the reference forms the rotated coordinates as a matrix product
+# (mat.dot, utils/data.py:189); rotation_sources writes the same sum
+# elementwise, c*x + (-s)*y + W/2, two rounded products and two rounded sums.
+# Which products a BLAS fuses is its own business, so the reference itself may
+# select another pixel where the unrounded coordinate lies within a few ulp of
+# k + 0.5 (e.g. 9 x 9, 7 x 9, 17 x 31 at +-45 degrees); at 260 x 346 and the
+# angles tested there the two agree everywhere.  The exact contract and what
+# is asserted about the difference: docs/AUGMENT_SPEC.md section 7,
+# tests/test_augment_oracle.py.
 # ---------------------------------------------------------------------------
 def rotation_sources(angle, H, W):
     """-> src_y, src_x int64[H,W] (source pixel of every rotated pixel) and the
