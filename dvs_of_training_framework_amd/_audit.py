@@ -199,7 +199,7 @@ def audit_exchange(step):
            'foreign': [], 'update_ranges': 0}
     names = {}
     # With the optimizer inside the backward (optim.fuse_into_backward) a bucket's UPDATE runs on
-    # a lane of its own behind the collective (csrc/exec.hip, XNode.xlane): the kernels of the
+    # a lane of its own behind the collective (csrc/exec_sched.h, Sched::update): the kernels of the
     # window then also run beside IT, and must not touch the bucket's parameters or optimizer
     # state either.  bucket pointer -> [(lo, hi)] of those tensors
     update_ranges = {}

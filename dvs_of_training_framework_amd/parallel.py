@@ -251,7 +251,7 @@ class GradReducer:
                 # wait()).  The executor recognises kernels that follow nothing but WAIT marks
                 # and launches them on the exchange stream behind the collective: the update
                 # overlaps the rest of the backward and no compute lane waits for anything
-                # before the JOIN mark (csrc/exec.hip, XNode.xlane).  (The update behind a WAIT
+                # before the JOIN mark (csrc/exec_sched.h, Sched::update).  (The update behind a WAIT
                 # mark on the CURRENT stream instead made that lane wait for the collective: 3.18
                 # against 2.65 ms per step under the loopback exchange, as measured then.)
                 cur = torch.cuda.current_stream(flat.device)
