@@ -28,6 +28,9 @@ from pathlib import Path
 import numpy as np
 
 HEADER_PATH = Path(__file__).resolve().parent.parent / 'include' / 'dvsof.h'
+# Extension headers, read after dvsof.h with its struct types known: their entry points are
+# tables of their own (EXTENSION_FUNCTIONS), beside the recorded one of dvsof.h (FUNCTIONS)
+EXTENSION_PATHS = (HEADER_PATH.with_name('dvsof_contrast.h'),)
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -52,10 +55,14 @@ def _struct_pointer(struct):
 
 class Abi:
     """functions {name: (restype, argtypes)}, structs {name: Structure class},
-    constants {name: int} of one header text."""
+    constants {name: int} of one header text.  ``base``: the Abi of a header this
+    one includes, whose struct types it may name; ``name`` goes into the errors."""
 
-    def __init__(self, text):
+    def __init__(self, text, base=None, name='dvsof.h'):
         self.functions, self.structs, self.constants, self._pointers = {}, {}, {}, {}
+        self._name = name
+        if base is not None:
+            self.structs, self._pointers = dict(base.structs), dict(base._pointers)
         self._text = text = self._preprocess(text)
         depth = start = 0
         for m in re.finditer(r'[{};]', text):       # statements end at a ';' outside braces
@@ -68,7 +75,7 @@ class Abi:
 
     def _fail(self, pos, why):
         pos += len(self._text[pos:]) - len(self._text[pos:].lstrip())
-        raise AbiError(f'dvsof.h line {self._text.count(chr(10), 0, pos) + 1}: {why}')
+        raise AbiError(f'{self._name} line {self._text.count(chr(10), 0, pos) + 1}: {why}')
 
     def _preprocess(self, text):
         """Comments and preprocessor lines -> blanks (line numbers stay);
@@ -164,3 +171,11 @@ def dtype_of(struct):
 
 _header = Abi(HEADER_PATH.read_text())
 FUNCTIONS, STRUCTS, CONSTANTS = _header.functions, _header.structs, _header.constants
+EXTENSION_FUNCTIONS = {}
+for _path in EXTENSION_PATHS:
+    _ext = Abi(_path.read_text(), base=_header, name=_path.name)
+    _clash = set(_ext.functions) & (set(FUNCTIONS) | set(EXTENSION_FUNCTIONS))
+    if _clash or _ext.constants or set(_ext.structs) != set(STRUCTS):
+        raise AbiError(f'{_path.name}: an extension header declares new functions only '
+                       f'({sorted(_clash) or "constants or structs found"})')
+    EXTENSION_FUNCTIONS.update(_ext.functions)

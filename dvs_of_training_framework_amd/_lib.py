@@ -3,7 +3,9 @@
 Signatures, struct layouts and constants are not written down here: _abi.py
 reads them from the header when the package is imported.  To add an entry
 point, declare it in include/dvsof.h and update
-tests/golden/abi_signatures.json, the recorded table a review sees change.
+tests/golden/abi_signatures.json, the recorded table a review sees change;
+or, leaving that table as it is, in an extension header (_abi.EXTENSION_PATHS:
+include/dvsof_contrast.h, recorded in tests/golden/abi_signatures_contrast.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -26,6 +28,8 @@ LossScale = STRUCTS['dvsof_loss_scale_t']
 
 # {name: (restype, argtypes)} of every entry point, derived from the header
 _SIGNATURES = _abi.FUNCTIONS
+# the same of the extension headers (include/dvsof_contrast.h)
+_EXTENSION_SIGNATURES = _abi.EXTENSION_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -36,6 +40,15 @@ def declared_symbols():
     text = HEADER_PATH.read_text()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     return sorted(set(re.findall(r'\b(dvsof_[a-z0-9_]+)\s*\(', text)))
+
+
+def declared_extension_symbols():
+    """Names of all entry points the extension headers declare."""
+    found = set()
+    for path in _abi.EXTENSION_PATHS:
+        text = re.sub(r'/\*.*?\*/', '', path.read_text(), flags=re.S)
+        found |= set(re.findall(r'\b(dvsof_[a-z0-9_]+)\s*\(', text))
+    return sorted(found)
 
 
 def lib():
@@ -51,7 +64,7 @@ def lib():
         st = LIB_PATH.stat()
         global LOADED_STAT      # the file these code objects came from (_audit.py)
         LOADED_STAT = (st.st_ino, st.st_size, st.st_mtime_ns)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

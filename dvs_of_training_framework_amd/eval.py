@@ -349,6 +349,43 @@ def iwe_stats_host(q, count):
     return res
 
 
+def _wave_tree(a):
+    """Lane 0 of the kernels' shuffle tree over the last axis (64 lanes)."""
+    a = a.copy()
+    off = 32
+    while off:
+        a[..., :off] = a[..., :off] + a[..., off:2 * off]
+        off >>= 1
+    return a[..., 0]
+
+
+def iwe_sum_sq_kernel_order(q):
+    """``sum_sq`` of IWE_SPEC section 3 with the kernels' own order of float64
+    additions (thread: strided pixels ascending; wave: shuffle tree; block:
+    waves 0..3; frame: partials ascending per lane, shuffle tree): the bits
+    ``dvsof_iwe_stats`` stores.  q int64 [F,h,w] -> float64 [F]."""
+    q = np.asarray(_np(q), np.int64)
+    F, h, w = q.shape
+    n = h * w
+    nb = min(max((n + 1023) // 1024, 1), 128)       # stat_blocks of csrc/iwe.hip
+    per = nb * 256
+    rounds = (n + per - 1) // per
+    image = q.reshape(F, n).astype(np.float64) * 2.0 ** -32
+    sq = np.zeros((F, rounds * per))
+    sq[:, :n] = image * image
+    sq = sq.reshape(F, rounds, nb, 256)
+    thread = np.zeros((F, nb, 256))
+    for k in range(rounds):
+        thread = thread + sq[:, k]
+    waves = _wave_tree(thread.reshape(F, nb, 4, 64))
+    part = waves[..., 0]
+    for k in range(1, 4):
+        part = part + waves[..., k]
+    lanes = np.zeros((F, 128))
+    lanes[:, :nb] = part
+    return _wave_tree(lanes[:, :64] + lanes[:, 64:])
+
+
 def _grey_host(value, m):
     """g = m > 0 ? min(255, (int)(value / m * 255.f + 0.5f)) : 0, float32."""
     if not m > 0:

@@ -85,16 +85,18 @@ class ValidationHook:
     """A validation pass (training.validate) that leaves the model as it found
     it (``model_left_as_found``)."""
 
-    def __init__(self, model, device, loader, logger, losses, weights, is_raw):
+    def __init__(self, model, device, loader, logger, losses, weights, is_raw,
+                 contrast_weight=0.0):
         self.model, self.device, self.loader = model, device, loader
         self.logger, self.losses = logger, losses
         self.weights = deepcopy(weights)
         self.is_raw = is_raw
+        self.extra = {'contrast_weight': contrast_weight} if contrast_weight else {}
 
     def __call__(self, steps, samples):
         with model_left_as_found(self.model):
             validate(self.model, self.device, self.loader, samples, self.logger,
-                     self.losses, weights=self.weights, is_raw=self.is_raw)
+                     self.losses, weights=self.weights, is_raw=self.is_raw, **self.extra)
 
 
 def evaluation_frames(image_ts, gt_timestamps, last_event_time, step=1):

@@ -14,6 +14,7 @@ Differences that are deliberate (MI355X-first):
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -162,6 +163,173 @@ class _FusedLoss(torch.autograd.Function):
         return (None,) * 6 + tuple(torch._foreach_mul(list(ctx.grads), g_loss))
 
 
+# ---------------------------------------------------------------------------
+# Contrast-maximisation term (csrc/contrast.hip, docs/CONTRAST_SPEC.md)
+# ---------------------------------------------------------------------------
+_F32 = np.float32
+CONTRAST_UNIT_BITS = 40
+
+
+def _contrast_pairs(x, y, t, sample_index, frame_ts, frame_sample, flow):
+    """The (event, frame) pairs that take part, frame by frame, and their warp
+    (steps 1-6 of IWE_SPEC section 2 in numpy float32).  -> dict of per-pair
+    arrays: f, x, y, tau, inside (the inside test), cx, cy, wx [2], wy [2]
+    (the last four only meaningful where ``inside``)."""
+    x, y = np.asarray(x, np.int64).reshape(-1), np.asarray(y, np.int64).reshape(-1)
+    t = np.asarray(t, _F32).reshape(-1)
+    s = np.asarray(sample_index, np.int64).reshape(-1)
+    ts = np.asarray(frame_ts, _F32).reshape(-1)
+    fs = np.asarray(frame_sample, np.int64).reshape(-1)
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    assert ts.size == 2 * F and fs.size == F and x.size == y.size == t.size == s.size
+    inb = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+    sel = [np.flatnonzero(inb & (s == fs[f]) & (ts[2 * f] <= t) & (t <= ts[2 * f + 1]))
+           for f in range(F)]
+    e = np.concatenate(sel) if F else np.zeros(0, np.int64)
+    f = np.concatenate([np.full(k.size, i, np.int64) for i, k in enumerate(sel)]) if F \
+        else np.zeros(0, np.int64)
+    x, y, t = x[e], y[e], t[e]
+    t0 = ts[2 * f]
+    d = ts[2 * f + 1] - t0
+    with np.errstate(all='ignore'):
+        tau = np.where(d > 0, np.fmin(np.fmax((t - t0) / d, _F32(0)), _F32(1)), _F32(0)).astype(_F32)
+        xw = x.astype(_F32) - tau * flow[f, 0, y, x]
+        yw = y.astype(_F32) - tau * flow[f, 1, y, x]
+        inside = (xw > _F32(-1)) & (xw < _F32(w)) & (yw > _F32(-1)) & (yw < _F32(h))
+        xw, yw = np.where(inside, xw, _F32(0)), np.where(inside, yw, _F32(0))
+    flx, fly = np.floor(xw), np.floor(yw)
+    fx, fy = xw - flx, yw - fly
+    return dict(f=f, x=x, y=y, tau=tau, inside=inside, cx=flx.astype(np.int64), cy=fly.astype(np.int64),
+                wx=(_F32(1) - fx, fx), wy=(_F32(1) - fy, fy))
+
+
+def contrast_fwd_host(x, y, t, sample_index, frame_ts, frame_sample, flow):
+    """CONTRAST_SPEC sections 2-4 on the host: what ``dvsof_contrast_fwd`` is
+    pinned to, byte for byte.  x, y, sample_index int64 [n], t float32 [n],
+    frame_ts float32 [2F] (or [F,2]), frame_sample int64 [F], flow float32
+    [F,2,h,w] -> dict: q int64 [F,h,w], count uint32 [F,h,w], result (rows of
+    eval.IWE_RESULT_DTYPE, sum_sq in the kernels' order), term float32, and
+    the per-frame float64 records mean, coef, unit, frame_term."""
+    from . import eval as ev
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    p = _contrast_pairs(x, y, t, sample_index, frame_ts, frame_sample, flow)
+    q = np.zeros((F, h, w), np.int64)
+    count = np.zeros((F, h, w), np.uint32)
+    np.add.at(count, (p['f'], p['y'], p['x']), 1)
+    k = p['inside']
+    f, cx, cy = p['f'][k], p['cx'][k], p['cy'][k]
+    for j in range(2):
+        for i in range(2):
+            xx, yy = cx + i, cy + j
+            Q = ((p['wy'][j][k] * p['wx'][i][k]).astype(_F32) * _F32(ev.IWE_ONE)).astype(np.int64)
+            ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h) & (Q > 0)
+            np.add.at(q, (f[ok], yy[ok], xx[ok]), Q[ok])
+    res = ev.iwe_stats_host(q, count)
+    res['sum_sq'] = ev.iwe_sum_sq_kernel_order(q)
+    # the closing wave, in float64
+    N = np.float64(h) * np.float64(w)
+    mean = res['sum_q'].astype(np.float64) * 2.0 ** -32 / N
+    var_i = res['sum_sq'] / N - mean * mean
+    cmean = res['count_sum'].astype(np.float64) / N
+    var_c = res['count_sq'].astype(np.float64) / N - cmean * cmean
+    live = var_c > 0
+    with np.errstate(all='ignore'):
+        coef = np.where(live, -2.0 / (N * var_c), 0.0)
+        frame_term = np.where(live, 1.0 - var_i / var_c, 0.0)
+    gmax = np.abs(coef) * np.fmax(res['max_q'].astype(np.float64) * 2.0 ** -32 - mean, mean)
+    e = np.where(gmax > 0, np.frexp(gmax)[1], 0)
+    unit = np.ldexp(1.0, CONTRAST_UNIT_BITS - e)
+    total = np.float64(0)
+    for v in frame_term:                # in frame order
+        total = total + v
+    with np.errstate(all='ignore'):
+        term = _F32(total / np.float64(F))
+    return dict(q=q, count=count, result=res, term=term, mean=mean, coef=coef, unit=unit,
+                frame_term=frame_term)
+
+
+def contrast_bwd_host(x, y, t, sample_index, frame_ts, frame_sample, flow, fwd, seed=1.0, weight=1.0):
+    """CONTRAST_SPEC section 5 on the host: what ``dvsof_contrast_bwd`` is
+    pinned to.  fwd: the dict of ``contrast_fwd_host`` for the same input.
+    -> (grad_flow float32 [F,2,h,w] = seed * weight * d term / d flow,
+    sums int64 [F,2,h,w], the fixed-point sums in units of 1/unit[f])."""
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    p = _contrast_pairs(x, y, t, sample_index, frame_ts, frame_sample, flow)
+    k = p['inside'] & (fwd['coef'][p['f']] != 0)
+    f, cx, cy, px, py = p['f'][k], p['cx'][k], p['cy'][k], p['x'][k], p['y'][k]
+    coef, mean, unit = fwd['coef'][f], fwd['mean'][f], fwd['unit'][f]
+    G = [[None, None], [None, None]]
+    for j in range(2):
+        for i in range(2):
+            xx, yy = cx + i, cy + j
+            ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+            Q = fwd['q'][f, np.where(ok, yy, 0), np.where(ok, xx, 0)]
+            G[j][i] = np.where(ok, coef * (Q.astype(np.float64) * 2.0 ** -32 - mean), 0.0)
+    wx = [a[k].astype(np.float64) for a in p['wx']]
+    wy = [a[k].astype(np.float64) for a in p['wy']]
+    gx = wy[0] * (G[0][1] - G[0][0]) + wy[1] * (G[1][1] - G[1][0])
+    gy = wx[0] * (G[1][0] - G[0][0]) + wx[1] * (G[1][1] - G[0][1])
+    mt = -p['tau'][k].astype(np.float64)
+    sums = np.zeros((F, 2, h, w), np.int64)
+    np.add.at(sums, (f, 0, py, px), np.trunc(mt * gx * unit).astype(np.int64))
+    np.add.at(sums, (f, 1, py, px), np.trunc(mt * gy * unit).astype(np.int64))
+    value = sums.astype(np.float64) / fwd['unit'].reshape(F, 1, 1, 1) / np.float64(max(F, 1))
+    sw = _F32(seed) * _F32(weight)
+    return sw * value.astype(_F32), sums
+
+
+class _Contrast(torch.autograd.Function):
+    """(weight * term, term) of the finest flow; the gradient of the first
+    enters the flow (dvsof_contrast_fwd / dvsof_contrast_bwd).  The weight is
+    applied inside the backward's closing kernel."""
+
+    @staticmethod
+    def forward(ctx, flow, x, y, t, sample_index, frame_ts, frame_sample, weight):
+        from .eval import IWE_RESULT_DTYPE
+        dev = flow.device
+        flow = flow.detach().contiguous().float()
+        F, _, h, w = flow.shape
+        lib = _lib.lib()
+        q = torch.empty(F, h, w, dtype=torch.long, device=dev)
+        count = torch.empty(F, h, w, dtype=torch.int32, device=dev)
+        result = torch.empty(F, IWE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        term = torch.zeros((), dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+        nbytes = lib.dvsof_contrast_workspace_bytes(F, h, w)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
+        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
+        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
+        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flow.shape, frame_ts.shape)
+        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
+        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
+        _lib.check(lib.dvsof_contrast_fwd(
+            *[c.data_ptr() for c in cols], cols[0].numel(), tables[0].data_ptr(), tables[1].data_ptr(),
+            flow.data_ptr(), F, h, w, q.data_ptr(), count.data_ptr(), result.data_ptr(),
+            term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_contrast_fwd')
+        ctx.held = (cols, tables, flow, q, ws, nbytes)
+        ctx.weight = float(weight)
+        ctx.mark_non_differentiable(term)
+        ctx.set_materialize_grads(False)
+        return term * ctx.weight, term
+
+    @staticmethod
+    def backward(ctx, g_value, _g_term):
+        if g_value is None:
+            return (None,) * 8
+        cols, tables, flow, q, ws, nbytes = ctx.held
+        F, _, h, w = flow.shape
+        grad = torch.empty_like(flow)
+        seed = g_value.contiguous().float()
+        _lib.check(_lib.lib().dvsof_contrast_bwd(
+            *[c.data_ptr() for c in cols], cols[0].numel(), tables[0].data_ptr(), tables[1].data_ptr(),
+            flow.data_ptr(), F, h, w, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(),
+            ctx.weight, grad.data_ptr(), _lib.stream()), 'dvsof_contrast_bwd')
+        return (grad,) + (None,) * 7
+
+
 class Loss:
     """Single-scale evaluator (reference utils/loss.py:38-171)."""
 
@@ -278,6 +446,24 @@ class Losses:
         img, frames = self._level_buffers(images)
         return _FusedLoss.apply(frames, img, start, stop, tuple(weights),
                                 loss_scale, *flows)
+
+    def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None):
+        """The contrast-maximisation term of the finest flow ``flows[-1]``
+        (docs/CONTRAST_SPEC.md): the mean over the predictions of
+        1 - var(image of warped events) / var(count image), negative where the
+        flow sharpens the events of its own window.  events: the wire columns
+        on the device.  -> the 0-dim term, differentiable with respect to
+        ``flows[-1]``; with a ``weight`` -> (weight * term, term), the first
+        differentiable (the weight is applied inside the backward kernel), the
+        second detached for logging.  Nothing waits for the device."""
+        flow = flows[-1]
+        assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
+            f'flow of size {tuple(flow.shape)} given to the contrast term of scale {self.shapes[-1]}'
+        cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
+        _lib.require_cuda(flow, flow_ts, flow_sample_idx, *cols)
+        value, term = _Contrast.apply(flow, *cols, flow_ts, flow_sample_idx,
+                                      1.0 if weight is None else float(weight))
+        return value if weight is None else (value, term)
 
 
 def init_losses(shape, batch_size, model, device, sequence_length,

@@ -282,6 +282,16 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         help='images a frame of the sharpness measurement spans')
     parser.add_argument('--sharpness-pictures', dest='sharpness_pictures', default=4,
                         type=int)
+    parser.add_argument('--contrast-weight', dest='contrast_weight', default=0.0,
+                        type=float,
+                        help='add this times the contrast-maximisation term to the '
+                             'training loss: per prediction 1 - variance of the image of '
+                             'the events warped along the finest flow / variance of their '
+                             'count image, negative where the flow sharpens the events '
+                             '(docs/CONTRAST_SPEC.md); logged as Train/contrast and '
+                             'Validation/contrast.  Needs the raw events in their wire '
+                             'columns on the device (not --ev_images, not '
+                             '--compact-events); such a run is not captured.  0: off')
     parser.add_argument('--sync-checkpoints', dest='sync_checkpoints',
                         action='store_true',
                         help='write checkpoints on the training thread (state_dict() + '
@@ -339,6 +349,21 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
+    return validate_contrast_args(args)
+
+
+def validate_contrast_args(args):
+    """--contrast-weight against what it cannot be combined with."""
+    weight = getattr(args, 'contrast_weight', 0.0)
+    if weight < 0 or weight != weight:
+        raise SystemExit(f'--contrast-weight must not be negative, got {weight}')
+    if weight > 0 and getattr(args, 'ev_images', False):
+        raise SystemExit('--contrast-weight cannot be combined with --ev_images: the term is '
+                         'computed from the raw events on the device, and a batch of '
+                         'preprocessed event images carries none')
+    if weight > 0 and getattr(args, 'compact_events', False):
+        raise SystemExit('--contrast-weight cannot be combined with --compact-events: the term '
+                         'reads the int64 / float32 wire columns, not the 9 B/event encoded ones')
     return args
 
 

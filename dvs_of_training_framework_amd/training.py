@@ -46,24 +46,50 @@ class _Terms(tuple):
         return self
 
 
+class _TermsAndContrast(tuple):
+    """The terms structure as it is, carrying the contrast-maximisation term
+    of the micro-batch beside it (``contrast``: a 0-dim device tensor)."""
+    def __new__(cls, terms, contrast):
+        self = super().__new__(cls, terms)
+        self.packed = getattr(terms, 'packed', None)
+        self.contrast = contrast
+        return self
+
+
 def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   timestamps, sample_idx, features, weights=[0.5, 1, 1],
-                  frame_indices=None):
+                  frame_indices=None, contrast_weight=0.0, events=None):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
     that has ``fused`` and flows that need gradients the value and the flow
-    gradients come out of one sweep (loss.Losses.fused)."""
+    gradients come out of one sweep (loss.Losses.fused).
+
+    contrast_weight > 0: plus contrast_weight * the contrast-maximisation term
+    of the finest flow over ``events``, the wire columns on the device
+    (loss.Losses.contrast, docs/CONTRAST_SPEC.md); the term rides on the
+    returned terms as ``.contrast``.  At 0 nothing of that is constructed and
+    ``events`` is not looked at."""
     extra = {} if frame_indices is None else {'frame_indices': frame_indices}
     call = (flows, flow_ts, flow_sample_idx, images, timestamps, sample_idx)
     trainable = torch.is_grad_enabled() and \
         any(f.requires_grad for f in flows)
     if trainable and hasattr(evaluator, 'fused'):
         loss, packed = evaluator.fused(*call, weights=weights, **extra)
-        return loss, _Terms(packed)
-    terms = evaluator(*call, **extra)
-    loss = 0
-    for weight, per_scale in zip(weights, terms):
-        loss = loss + weight * mean(per_scale)
-    return loss, terms
+        terms = _Terms(packed)
+    else:
+        terms = evaluator(*call, **extra)
+        loss = 0
+        for weight, per_scale in zip(weights, terms):
+            loss = loss + weight * mean(per_scale)
+    if not contrast_weight:
+        return loss, terms
+    if contrast_weight < 0:
+        raise ValueError(f'contrast_weight must not be negative, got {contrast_weight}')
+    if events is None:
+        raise ValueError('contrast_weight > 0 needs the raw events of the batch on the device '
+                         '(is_raw=True); preprocessed voxel grids carry none')
+    value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events,
+                                     weight=contrast_weight)
+    return loss + value, _TermsAndContrast(terms, term)
 
 
 class TermReadback:
@@ -79,6 +105,14 @@ class TermReadback:
         self.n_terms = len(terms)
         self.n_scales = len(terms[0]) if self.n_terms else 0
         self._table = None
+        self._contrast = getattr(terms, 'contrast', None)
+
+    def contrast(self):
+        """The contrast-maximisation term as a host float (one small copy),
+        None when the loss has none."""
+        if isinstance(self._contrast, torch.Tensor):
+            self._contrast = float(self._contrast)
+        return self._contrast
 
     def host(self):
         if self._table is None:
@@ -134,8 +168,14 @@ def _to_device(batch, device, is_raw):
 
 
 def process_minibatch(model, batch, timers, device, is_raw, evaluator,
-                      weights, return_prediction=False):
-    """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs])."""
+                      weights, return_prediction=False, contrast_weight=0.0):
+    """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs]).
+    contrast_weight > 0 (raw events only): see ``combined_loss``."""
+    contrast = {}
+    if contrast_weight:
+        if not is_raw:
+            raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
+        contrast = {'contrast_weight': contrast_weight}
     with _timed(timers, 'batch2gpu'):
         timestamps, sample_idx, images, payload = _to_device(batch, device,
                                                              is_raw)
@@ -151,7 +191,8 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
         loss, terms = combined_loss(
             evaluator, flows, flow_ts, flow_sample_idx, images, timestamps,
             sample_idx, features, weights=weights,
-            frame_indices=getattr(model, 'last_frame_indices', None))
+            frame_indices=getattr(model, 'last_frame_indices', None),
+            **(dict(contrast, events=payload) if contrast else {}))
         terms = TermReadback(terms)
     if not return_prediction:
         return loss, terms, tags
@@ -184,6 +225,7 @@ class ScaleSums:
     def clear(self):
         self.per_term = None        # [term][scale]
         self.loss = 0.0
+        self.contrast = None        # sum of the contrast-maximisation term, if the loss has one
         self.tags = None
 
     def add(self, loss, readback, tags):
@@ -194,6 +236,9 @@ class ScaleSums:
             self.per_term = [[a + b for a, b in zip(acc, new)]
                              for acc, new in zip(self.per_term, rows)]
         self.loss += loss.item()
+        extra = readback.contrast() if hasattr(readback, 'contrast') else None
+        if extra is not None:
+            self.contrast = (self.contrast or 0.0) + extra
         self.tags = list(tags)
 
     def write(self, logger, x, divisor, families):
@@ -297,8 +342,11 @@ def guard_readout(optimizer, host_guard=None):
     return host_guard.state() if host_guard is not None else None
 
 
-def capture_refusal(optimizer, is_raw, model=None):
+def capture_refusal(optimizer, is_raw, model=None, contrast_weight=0.0):
     """Why ``train(capture=True)`` cannot replay its steps (None: it can)."""
+    if contrast_weight:
+        return (f'--contrast-weight {contrast_weight}: the captured step does not carry the '
+                'contrast-maximisation term (dvsof_contrast_fwd / dvsof_contrast_bwd)')
     if not all(hasattr(optimizer, m) for m in CAPTURE_PROTOCOL):
         return (f'optimizer {type(optimizer).__name__} has no begin_capture / advance / '
                 'end_capture (optim.FusedAdamW, FusedRAdam and FusedRanger do)')
@@ -319,7 +367,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           timers=None, hooks={}, init_step=0, init_samples_passed=0,
           max_events_per_batch: int = 350000, reducer=None,
           log_every: int = 1, capture=False, guard=None,
-          max_skipped_steps: int = 32, guard_agreement_every: int = 0):
+          max_skipped_steps: int = 32, guard_agreement_every: int = 0,
+          contrast_weight: float = 0.0):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
     batches above ``max_events_per_batch`` events are skipped and not counted,
@@ -350,6 +399,10 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     guard_agreement_every:  under data parallelism, compare the guard's
                counters across ranks at logged steps that are multiples of
                this (the checkpointing interval; 0: never)
+    contrast_weight:  > 0 adds this times the contrast-maximisation term of
+               the finest flow to the loss (docs/CONTRAST_SPEC.md; raw events
+               only), logged as ``Train/contrast``; such a run is not
+               captured.  0: the step launches what it launches without it
     """
     if timers is None:
         on_gpu = torch.device(device).type == 'cuda'
@@ -358,7 +411,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                        init_samples_passed)
     sums = ScaleSums()
     captured = None
-    refused = capture_refusal(optimizer, is_raw, model) if capture else None
+    refused = capture_refusal(optimizer, is_raw, model, contrast_weight) if capture else None
     if refused:
         import sys
         print(f'capture: not used, the loop runs eagerly: {refused}', file=sys.stderr)
@@ -396,7 +449,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
             replayed = True
         if not replayed:
             loss, terms, tags = process_minibatch(
-                model, batch, timers, device, is_raw, evaluator, weights)
+                model, batch, timers, device, is_raw, evaluator, weights,
+                **({'contrast_weight': contrast_weight} if contrast_weight else {}))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass
@@ -426,6 +480,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                     x = clock.samples
                     sums.write(logger, x, accumulation_steps, _TRAIN_FAMILIES)
                     logger.add_scalar('General/Train loss', sums.loss, x)
+                    if sums.contrast is not None:
+                        logger.add_scalar('Train/contrast',
+                                          sums.contrast / accumulation_steps, x)
                     for g, group in enumerate(optimizer.param_groups):
                         logger.add_scalar(f'General/learning rate/{g}',
                                           group['lr'], x)
@@ -459,17 +516,23 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
 
 
 def validate(model, device, loader, samples_passed, logger, evaluator,
-             weights=[0.5, 1, 1], is_raw=True):
+             weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
-    no_grad), written against ``samples_passed``."""
+    no_grad), written against ``samples_passed``; with contrast_weight > 0
+    the loss holds the contrast-maximisation term, written as
+    ``Validation/contrast``."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
     with torch.no_grad():
         for batch in loader:
             loss, terms, tags = process_minibatch(
-                model, batch, quiet, device, is_raw, evaluator, weights)
+                model, batch, quiet, device, is_raw, evaluator, weights,
+                **({'contrast_weight': contrast_weight} if contrast_weight else {}))
             sums.add(loss, terms, tags)
     logger.add_scalar('General/Validation loss', sums.loss / n_batches,
                       samples_passed)
     sums.write(logger, samples_passed, n_batches, _VALID_FAMILIES)
+    if sums.contrast is not None:
+        logger.add_scalar('Validation/contrast', sums.contrast / n_batches,
+                          samples_passed)

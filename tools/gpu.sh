@@ -21,6 +21,9 @@
 #   iwe [iwe_bench.py args]          label-free validation (tools/iwe_bench.py): splat, statistics and render alone at
 #                                     F = 8, 256x256, 30 000 and 120 000 events per frame, the splat's atomic bytes/s;
 #                                     testing.flow_warp_loss against the same frames' inference alone
+#   contrast [contrast_bench.py args] contrast-maximisation term (tools/contrast_bench.py): dvsof_contrast_fwd and
+#                                     dvsof_contrast_bwd alone at batch 8, 256x256, 65 536 events per sample; the eager
+#                                     training step with --contrast-weight 0 against 0.25 in alternating blocks
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -83,6 +86,9 @@ evalhook)
 iwe)
   timeout -k 10 560 env "${envs[@]}" python tools/iwe_bench.py "$@" > $O/iwe.json 2> $O/iwe.err
   echo "iwe rc=$?"; cut -c1-2600 $O/iwe.json; tail -3 $O/iwe.err ;;
+contrast)
+  timeout -k 10 420 env "${envs[@]}" python tools/contrast_bench.py "$@" > $O/contrast.json 2> $O/contrast.err
+  echo "contrast rc=$?"; cut -c1-2600 $O/contrast.json; tail -3 $O/contrast.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

@@ -461,7 +461,9 @@ def main(argv=None):
     if validation_loader is not None:
         hooks['validation'] = ValidationHook(
             model, device, validation_loader, logger, losses,
-            args.loss_weights, args.is_raw)
+            args.loss_weights, args.is_raw,
+            **({'contrast_weight': args.contrast_weight}
+               if getattr(args, 'contrast_weight', 0.0) else {}))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
     elif not args.skip_validation:
         note('no validation data (--validation-sequence, or '
@@ -486,7 +488,8 @@ def main(argv=None):
                   reducer=reducer, capture=getattr(args, 'capture', False),
                   guard=host_guard,
                   max_skipped_steps=getattr(args, 'max_skipped_steps', 32),
-                  guard_agreement_every=args.checkpointing_interval)
+                  guard_agreement_every=args.checkpointing_interval,
+                  contrast_weight=getattr(args, 'contrast_weight', 0.0))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
