@@ -6,24 +6,21 @@
 //
 // Replaces nothing of the reference: its loss reads the grey frames only.
 //
-// Forward: the splat of iwe.hip with the frame found by sample and time
-// window instead of by position in the columns, the statistics of
-// dvsof_iwe_stats, one closing wave.  Backward: the scatter into the flow
-// gradient collides on almost every active pixel, so it is summed in 64-bit
-// fixed point with a per-frame power-of-two unit and integer atomics (the sums
-// have no order), and one thread per element converts once.  No floating-point
-// atomics anywhere.  This file relies on -ffp-contract=off.
-#include "common.h"
+// Forward: the warp and splat of frame_common.h, which are iwe.hip's, with the
+// frame found by sample and time window instead of by position in the
+// columns, the statistics of dvsof_iwe_stats, one closing wave.  Backward: the
+// scatter into the flow gradient collides on almost every active pixel, so it
+// is summed in 64-bit fixed point with a per-frame power-of-two unit and
+// integer atomics (the sums have no order), and one thread per element
+// converts once.  No floating-point atomics anywhere.  This file relies on
+// -ffp-contract=off.
+#include "frame_common.h"
 #include "../../include/dvsof_contrast.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int kMaxSide = 32767;    // as iwe.hip
-constexpr int kMaxFrames = 65535;  // as dvsof_iwe_stats
-constexpr int kMaxBlocks = 2048;
-constexpr float kOne = 4294967296.f;  // 2^32: the fixed-point unit of q
-constexpr int kUnitBits = 40;         // |one event's addend| < 2^(kUnitBits + 1) units
+constexpr int NT = kFrameNT;
+constexpr int kUnitBits = 40;  // |one event's addend| < 2^(kUnitBits + 1) units
 
 // one per frame, in the workspace behind the fixed-point sums
 struct FrameRec {
@@ -33,35 +30,6 @@ struct FrameRec {
     double term;  // 1 - var(I_f)/var(c_f); 0 where var(c_f) is not positive
 };
 static_assert(sizeof(FrameRec) == 32, "the workspace holds 32 bytes per frame");
-
-struct Warp {
-    int cx, cy;  // the corner floor(xw), floor(yw)
-    float wx[2], wy[2];
-    float tau;
-};
-
-// Steps 1-6 of IWE_SPEC section 2 for an event that takes part in a frame;
-// false: dropped by the inside test.  The forward and the backward both call
-// this, so they see the same bits.
-__device__ __forceinline__ bool warp_event(float te, float t0, float t1, const float *__restrict__ fl,
-                                           size_t plane, int64_t xi, int64_t yi, int h, int w, Warp &o)
-{
-    const float d = t1 - t0;
-    o.tau = d > 0.f ? fminf(fmaxf((te - t0) / d, 0.f), 1.f) : 0.f;
-    const float u = fl[0], v = fl[plane];
-    const float xw = (float)xi - o.tau * u, yw = (float)yi - o.tau * v;
-    // in float, before any conversion: false for a NaN, an infinity, 1e30
-    if (!(xw > -1.f && xw < (float)w && yw > -1.f && yw < (float)h)) return false;
-    const float flx = floorf(xw), fly = floorf(yw);  // in [-1, side - 1]
-    const float fx = xw - flx, fy = yw - fly;
-    o.wx[0] = 1.f - fx;
-    o.wx[1] = fx;
-    o.wy[0] = 1.f - fy;
-    o.wy[1] = fy;
-    o.cx = (int)flx;
-    o.cy = (int)fly;
-    return true;
-}
 
 // ---------------------------------------------------------------------------
 // Forward.  One thread per event; an event takes part in every frame of its
@@ -88,17 +56,7 @@ __global__ __launch_bounds__(NT) void contrast_splat_kernel(
             atomicAdd(count + (size_t)f * plane + pix, 1u);
             Warp p;
             if (!warp_event(te, t0, t1, flow + (size_t)f * 2 * plane + pix, plane, xi, yi, h, w, p)) continue;
-            unsigned long long *img = q + (size_t)f * plane;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int xx = p.cx + i, yy = p.cy + j;
-                    if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
-                    const int64_t Q = (int64_t)(p.wy[j] * p.wx[i] * kOne);  // truncates; 0 <= Q <= 2^32
-                    if (Q > 0) atomicAdd(img + (size_t)yy * w + (size_t)xx, (unsigned long long)Q);
-                }
-            }
+            splat_corners(p, h, w, q + (size_t)f * plane);
         }
     }
 }
@@ -201,15 +159,7 @@ __global__ __launch_bounds__(NT) void contrast_bwd_close_kernel(long long *__res
     }
 }
 
-bool bad_sizes(int F, int h, int w) { return F > kMaxFrames || h < 1 || w < 1 || h > kMaxSide || w > kMaxSide; }
-
 size_t sums_bytes(int F, int h, int w) { return sizeof(int64_t) * 2 * (size_t)F * h * w; }
-
-unsigned event_blocks(int64_t n)
-{
-    const int64_t blocks = (n + NT - 1) / NT;
-    return (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
-}
 
 }  // namespace
 
@@ -217,7 +167,7 @@ extern "C" {
 
 size_t dvsof_contrast_workspace_bytes(int F, int h, int w)
 {
-    if (F < 1 || bad_sizes(F, h, w)) return 0;
+    if (F < 1 || bad_frame_sizes(F, h, w)) return 0;
     return sums_bytes(F, h, w) + sizeof(FrameRec) * (size_t)F + dvsof_iwe_stats_workspace_bytes(F, h, w);
 }
 
@@ -228,7 +178,7 @@ int dvsof_contrast_fwd(const int64_t *x, const int64_t *y, const float *t, const
 {
     if (F < 0 || n_events < 0) return DVSOF_EINVAL;
     if (F == 0) return DVSOF_OK;
-    if (bad_sizes(F, h, w) || !q || !count || !result || !term || !frame_ts || !frame_sample || !flow)
+    if (bad_frame_sizes(F, h, w) || !q || !count || !result || !term || !frame_ts || !frame_sample || !flow)
         return DVSOF_EINVAL;
     if (n_events > 0 && (!x || !y || !t || !sample_index)) return DVSOF_EINVAL;
     if (!workspace || workspace_bytes < dvsof_contrast_workspace_bytes(F, h, w)) return DVSOF_ENOSPACE;
@@ -260,7 +210,7 @@ int dvsof_contrast_bwd(const int64_t *x, const int64_t *y, const float *t, const
 {
     if (F < 0 || n_events < 0) return DVSOF_EINVAL;
     if (F == 0) return DVSOF_OK;
-    if (bad_sizes(F, h, w) || !q || !seed || !grad_flow || !frame_ts || !frame_sample || !flow)
+    if (bad_frame_sizes(F, h, w) || !q || !seed || !grad_flow || !frame_ts || !frame_sample || !flow)
         return DVSOF_EINVAL;
     if (n_events > 0 && (!x || !y || !t || !sample_index)) return DVSOF_EINVAL;
     if (!workspace || workspace_bytes < dvsof_contrast_workspace_bytes(F, h, w)) return DVSOF_ENOSPACE;
@@ -274,9 +224,8 @@ int dvsof_contrast_bwd(const int64_t *x, const int64_t *y, const float *t, const
         DVSOF_LAUNCH_CHECK();
     }
     const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
-    const size_t blocks = (total + NT - 1) / NT;
-    hipLaunchKernelGGL(contrast_bwd_close_kernel, dim3((unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks)),
-                       dim3(NT), 0, st, (long long *)ws, rec, seed, weight, F, per_frame, grad_flow);
+    hipLaunchKernelGGL(contrast_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
+                       (long long *)ws, rec, seed, weight, F, per_frame, grad_flow);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }

@@ -4,7 +4,7 @@
 //
 // Replaces nothing the reference draws: its test.py reports two numbers per
 // sequence.  The counted-pixel predicate and the endpoint error are those of
-// flow_error_partial_kernel (eval.hip), the flow colours those of
+// dvsof_flow_error (frame_common.h), the flow colours those of
 // flow_render_kernel (render.hip, through render_common.h).
 //
 // Two launches whatever the number of frames: per (frame, chunk) partial
@@ -20,32 +20,23 @@ namespace {
 
 constexpr int NT = kRenderNT;
 constexpr int kMaxChunks = kRenderMaxChunks;
-constexpr int kMaxSide = kRenderMaxSide;
-constexpr int kMaxFrames = 65535;  // as dvsof_flow_error
 constexpr int kPanels = 4;
 
-struct PanelAcc {
-    float plo, phi, glo, ghi;
-    int pbad, gbad, counted, below;
+// The stats row is the accumulator.  mag >= +0 for finite components (never NaN), so fminf / fmaxf
+// select the same bits in any order.
+struct PanelSum {
+    using Row = dvsof_eval_panel_stats_t;
+    static __device__ __forceinline__ Row zero()
+    {
+        return Row{__builtin_inff(), -__builtin_inff(), 0, __builtin_inff(), -__builtin_inff(), 0, 0, 0};
+    }
+    static __device__ __forceinline__ Row add(const Row &a, const Row &b)
+    {
+        return Row{fminf(a.pred_lo, b.pred_lo), fmaxf(a.pred_hi, b.pred_hi), a.pred_nonfinite + b.pred_nonfinite,
+                   fminf(a.gt_lo, b.gt_lo), fmaxf(a.gt_hi, b.gt_hi), a.gt_nonfinite + b.gt_nonfinite,
+                   a.n_counted + b.n_counted, a.n_below + b.n_below};
+    }
 };
-__device__ __forceinline__ PanelAcc panel_zero()
-{
-    return PanelAcc{__builtin_inff(), -__builtin_inff(), __builtin_inff(), -__builtin_inff(), 0, 0, 0, 0};
-}
-// mag >= +0 for finite components (never NaN), so fminf / fmaxf select the same bits in any order
-__device__ __forceinline__ PanelAcc panel_add(const PanelAcc &a, const PanelAcc &b)
-{
-    return PanelAcc{fminf(a.plo, b.plo), fmaxf(a.phi, b.phi), fminf(a.glo, b.glo), fmaxf(a.ghi, b.ghi),
-                    a.pbad + b.pbad, a.gbad + b.gbad, a.counted + b.counted, a.below + b.below};
-}
-__device__ __forceinline__ PanelAcc panel_load(const dvsof_eval_panel_stats_t &s)
-{
-    return PanelAcc{s.pred_lo, s.pred_hi, s.gt_lo, s.gt_hi, s.pred_nonfinite, s.gt_nonfinite, s.n_counted, s.n_below};
-}
-__device__ __forceinline__ dvsof_eval_panel_stats_t panel_store(const PanelAcc &a)
-{
-    return dvsof_eval_panel_stats_t{a.plo, a.phi, a.pbad, a.glo, a.ghi, a.gbad, a.counted, a.below};
-}
 
 // What one frame's panels read.  counted = max_row * w: rows below max_row are the first
 // max_row * w pixels of a plane.
@@ -53,14 +44,13 @@ struct Frame {
     const float *pu, *pv, *gu, *gv;
     const uint32_t *on, *off;  // NULL: dense
     int counted;
-    // the predicate of flow_error_partial_kernel, and its endpoint error
+    // whether dvsof_flow_error counts pixel p, and its endpoint error
     __device__ __forceinline__ bool counts(int p, float *ee) const
     {
         if (p >= counted || (on && (on[p] | off[p]) == 0u)) return false;
         const float tu = gu[p], tv = gv[p];
-        if (isinf(tu) || isinf(tv) || !(sqrtf(tu * tu + tv * tv) > 0.f)) return false;
-        const float du = tu - pu[p], dv = tv - pv[p];
-        *ee = sqrtf(du * du + dv * dv);
+        if (!gt_counts(tu, tv)) return false;
+        *ee = endpoint_error(tu, tv, pu[p], pv[p]);
         return true;
     }
 };
@@ -90,51 +80,32 @@ __global__ __launch_bounds__(NT) void eval_panels_stats_kernel(
     const int f = blockIdx.x / chunks, c = blockIdx.x % chunks;
     const Frame fr = frame_of(pred, gt_u, gt_v, count2, f, h, w, max_row);
     const int row0 = c * step, rows = min(step, h - row0);
-    const int p0 = row0 * w, p1 = p0 + rows * w;  // <= 32767^2 < 2^31
-    PanelAcc a = panel_zero();
+    const int p0 = row0 * w, p1 = p0 + rows * w;  // <= kMaxSide^2 < 2^31
+    dvsof_eval_panel_stats_t a = PanelSum::zero();
     for (int p = p0 + threadIdx.x; p < p1; p += NT) {
         const float qu = fr.pu[p], qv = fr.pv[p], tu = fr.gu[p], tv = fr.gv[p];
         if (finite2(qu, qv)) {
             const float mag = sqrtf(qu * qu + qv * qv);
-            a.plo = fminf(a.plo, mag);
-            a.phi = fmaxf(a.phi, mag);
+            a.pred_lo = fminf(a.pred_lo, mag);
+            a.pred_hi = fmaxf(a.pred_hi, mag);
         } else {
-            ++a.pbad;
+            ++a.pred_nonfinite;
         }
         if (finite2(tu, tv)) {
             const float mag = sqrtf(tu * tu + tv * tv);
-            a.glo = fminf(a.glo, mag);
-            a.ghi = fmaxf(a.ghi, mag);
+            a.gt_lo = fminf(a.gt_lo, mag);
+            a.gt_hi = fmaxf(a.gt_hi, mag);
         } else {
-            ++a.gbad;
+            ++a.gt_nonfinite;
         }
         float ee;
         if (fr.counts(p, &ee)) {
-            a.counted += 1;
-            a.below += ee < 3.f ? 1 : 0;
+            a.n_counted += 1;
+            a.n_below += ee < 3.f ? 1 : 0;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        PanelAcc b;
-        b.plo = __shfl_down(a.plo, off, kWave);
-        b.phi = __shfl_down(a.phi, off, kWave);
-        b.glo = __shfl_down(a.glo, off, kWave);
-        b.ghi = __shfl_down(a.ghi, off, kWave);
-        b.pbad = __shfl_down(a.pbad, off, kWave);
-        b.gbad = __shfl_down(a.gbad, off, kWave);
-        b.counted = __shfl_down(a.counted, off, kWave);
-        b.below = __shfl_down(a.below, off, kWave);
-        a = panel_add(a, b);
-    }
-    __shared__ PanelAcc sh[NT / kWave];
-    if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < NT / kWave; ++k) a = panel_add(a, sh[k]);
-        part[(size_t)f * kMaxChunks + c] = panel_store(a);
-    }
+    a = block_tree<PanelSum>(a);
+    if (threadIdx.x == 0) part[(size_t)f * kMaxChunks + c] = a;
 }
 
 // ---------------------------------------------------------------------------
@@ -195,28 +166,27 @@ __global__ __launch_bounds__(NT) void eval_panels_kernel(
         return;
     }
     // the partials of this frame: at most 64 uniform loads, the same in every lane
-    PanelAcc a = panel_zero();
+    dvsof_eval_panel_stats_t a = PanelSum::zero();
     const dvsof_eval_panel_stats_t *mine = part + (size_t)f * kMaxChunks;
-    for (int k = 0; k < chunks; ++k) a = panel_add(a, panel_load(mine[k]));
-    if (panel == 1 && c == 0 && threadIdx.x == 0) stats[f] = panel_store(a);
-    const float m = flow_scale > 0.f ? flow_scale : (__builtin_isfinite(a.ghi) && a.ghi > 0.f ? a.ghi : a.phi);
+    for (int k = 0; k < chunks; ++k) a = PanelSum::add(a, mine[k]);
+    if (panel == 1 && c == 0 && threadIdx.x == 0) stats[f] = a;
+    const float m = flow_scale > 0.f ? flow_scale : (__builtin_isfinite(a.gt_hi) && a.gt_hi > 0.f ? a.gt_hi : a.pred_hi);
     FlowColour colour;
     if (panel == 1) {
         colour.fx = fr.pu;
         colour.fy = fr.pv;
-        colour.set_scale(a.plo, a.phi, m);
+        colour.set_scale(a.pred_lo, a.pred_hi, m);
     } else {
         colour.fx = fr.gu;
         colour.fy = fr.gv;
-        colour.set_scale(a.glo, a.ghi, m);
+        colour.set_scale(a.gt_lo, a.gt_hi, m);
     }
     emit_rows(it, canvas, colour);
 }
 
 bool bad_sources(const float *pred, const float *gt_u, const float *gt_v, int F, int h, int w, int max_row)
 {
-    return !pred || !gt_u || !gt_v || F > kMaxFrames || h < 1 || w < 1 || h > kMaxSide || w > kMaxSide ||
-           max_row < 0 || max_row > h;
+    return !pred || !gt_u || !gt_v || bad_frame_sizes(F, h, w) || max_row < 0 || max_row > h;
 }
 
 }  // namespace

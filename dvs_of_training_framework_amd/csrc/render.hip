@@ -21,54 +21,43 @@ namespace {
 
 constexpr int NT = kRenderNT;
 constexpr int kMaxChunks = kRenderMaxChunks;
-constexpr int kMaxSide = kRenderMaxSide;
 
 // ---------------------------------------------------------------------------
 // Launch 1.  mag >= +0 for finite components (never NaN, +inf on overflow), so
 // fminf / fmaxf select the same bits in any order.
 // ---------------------------------------------------------------------------
+struct MagnitudeRange {
+    struct Row {
+        float lo, hi;
+        int bad;
+    };
+    static __device__ __forceinline__ Row zero() { return Row{__builtin_inff(), -__builtin_inff(), 0}; }
+    static __device__ __forceinline__ Row add(const Row &a, const Row &b)
+    {
+        return Row{fminf(a.lo, b.lo), fmaxf(a.hi, b.hi), a.bad + b.bad};
+    }
+};
+
 __global__ __launch_bounds__(NT) void flow_render_stats_kernel(
     const dvsof_render_item_t *__restrict__ items, dvsof_render_stats_t *__restrict__ part)
 {
     const dvsof_render_item_t it = items[blockIdx.x];
     const size_t plane = (size_t)it.h * it.w;
     const float *fx = (const float *)it.src + (size_t)it.row0 * it.w, *fy = fx + plane;
-    const int n = it.rows * it.w;  // <= 32767^2 < 2^31
-    float lo = __builtin_inff(), hi = -__builtin_inff();
-    int bad = 0;
+    const int n = it.rows * it.w;  // <= kMaxSide^2 < 2^31
+    MagnitudeRange::Row a = MagnitudeRange::zero();
     for (int p = threadIdx.x; p < n; p += NT) {
         const float x = fx[p], y = fy[p];
         if (finite2(x, y)) {
             const float mag = sqrtf(x * x + y * y);
-            lo = fminf(lo, mag);
-            hi = fmaxf(hi, mag);
+            a.lo = fminf(a.lo, mag);
+            a.hi = fmaxf(a.hi, mag);
         } else {
-            ++bad;
+            ++a.bad;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off, kWave));
-        hi = fmaxf(hi, __shfl_down(hi, off, kWave));
-        bad += __shfl_down(bad, off, kWave);
-    }
-    __shared__ float sh_lo[NT / kWave], sh_hi[NT / kWave];
-    __shared__ int sh_bad[NT / kWave];
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        sh_lo[threadIdx.x / kWave] = lo;
-        sh_hi[threadIdx.x / kWave] = hi;
-        sh_bad[threadIdx.x / kWave] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < NT / kWave; ++k) {
-            lo = fminf(lo, sh_lo[k]);
-            hi = fmaxf(hi, sh_hi[k]);
-            bad += sh_bad[k];
-        }
-        part[(size_t)it.image * kMaxChunks + it.chunk] = dvsof_render_stats_t{lo, hi, bad, 0};
-    }
+    a = block_tree<MagnitudeRange>(a);
+    if (threadIdx.x == 0) part[(size_t)it.image * kMaxChunks + it.chunk] = dvsof_render_stats_t{a.lo, a.hi, a.bad, 0};
 }
 
 // ---------------------------------------------------------------------------

@@ -3,13 +3,13 @@
 // with its head / aligned-dword-triple / tail stores (section 3).  Everything
 // here relies on -ffp-contract=off.
 #pragma once
-#include "common.h"
+#include "frame_common.h"
 
 namespace {
 
-constexpr int kRenderNT = 256;
+constexpr int kRenderNT = kFrameNT;
 constexpr int kRenderMaxChunks = DVSOF_RENDER_MAX_CHUNKS;
-constexpr int kRenderMaxSide = 32767;
+constexpr int kRenderMaxSide = kMaxSide;
 constexpr int kRenderChunkPixels = 2048;  // 8 per thread: enough to hide the launch of a workgroup
 
 __device__ __forceinline__ bool finite2(float a, float b)
@@ -118,7 +118,7 @@ __device__ __forceinline__ void emit_rows(const dvsof_render_item_t &it, uint8_t
     }
 }
 
-// dvsof_flow_render_chunk_rows; 0 for sides outside [1, 32767]
+// dvsof_flow_render_chunk_rows; 0 for sides outside [1, kMaxSide]
 inline int chunk_rows(int h, int w)
 {
     if (h < 1 || w < 1 || h > kRenderMaxSide || w > kRenderMaxSide) return 0;

@@ -359,24 +359,28 @@ def _wave_tree(a):
     return a[..., 0]
 
 
-def iwe_sum_sq_kernel_order(q):
-    """``sum_sq`` of IWE_SPEC section 3 with the kernels' own order of float64
-    additions (thread: strided pixels ascending; wave: shuffle tree; block:
-    waves 0..3; frame: partials ascending per lane, shuffle tree): the bits
-    ``dvsof_iwe_stats`` stores.  q int64 [F,h,w] -> float64 [F]."""
-    q = np.asarray(_np(q), np.int64)
-    F, h, w = q.shape
-    n = h * w
-    nb = min(max((n + 1023) // 1024, 1), 128)       # stat_blocks of csrc/iwe.hip
+def partial_blocks(n):
+    """Partials per frame of n pixels: partial_blocks of csrc/frame_common.h."""
+    return min(max((n + 1023) // 1024, 1), 128)
+
+
+def kernel_order_sum(terms, nb):
+    """The per-frame float64 sum of csrc/frame_common.h with the kernels' own
+    order of additions (thread: strided pixels ascending; wave: shuffle tree;
+    block: waves 0..3; frame: partials ascending per lane, shuffle tree): the
+    bits ``dvsof_flow_error`` and ``dvsof_iwe_stats`` store.  terms float64
+    [F,n], a pixel that adds nothing as +0; nb partials -> float64 [F]."""
+    terms = np.asarray(terms, np.float64)
+    F, n = terms.shape
+    assert 1 <= nb <= 128
     per = nb * 256
     rounds = (n + per - 1) // per
-    image = q.reshape(F, n).astype(np.float64) * 2.0 ** -32
-    sq = np.zeros((F, rounds * per))
-    sq[:, :n] = image * image
-    sq = sq.reshape(F, rounds, nb, 256)
+    padded = np.zeros((F, rounds * per))
+    padded[:, :n] = terms
+    padded = padded.reshape(F, rounds, nb, 256)
     thread = np.zeros((F, nb, 256))
     for k in range(rounds):
-        thread = thread + sq[:, k]
+        thread = thread + padded[:, k]
     waves = _wave_tree(thread.reshape(F, nb, 4, 64))
     part = waves[..., 0]
     for k in range(1, 4):
@@ -384,6 +388,16 @@ def iwe_sum_sq_kernel_order(q):
     lanes = np.zeros((F, 128))
     lanes[:, :nb] = part
     return _wave_tree(lanes[:, :64] + lanes[:, 64:])
+
+
+def iwe_sum_sq_kernel_order(q):
+    """``sum_sq`` of IWE_SPEC section 3 in the kernels' order
+    (``kernel_order_sum``): the bits ``dvsof_iwe_stats`` stores.
+    q int64 [F,h,w] -> float64 [F]."""
+    q = np.asarray(_np(q), np.int64)
+    F, h, w = q.shape
+    image = q.reshape(F, h * w).astype(np.float64) * 2.0 ** -32
+    return kernel_order_sum(image * image, partial_blocks(h * w))
 
 
 def _grey_host(value, m):

@@ -160,6 +160,115 @@ def test_flow_error_batch_equals_single_frames(golden):
     assert res['n_points'][1] == 0 and res['n_points'][0] > 0
 
 
+_F = np.float32
+# (F, h, w, max_row): the smallest shapes that reach each stage of the reduction
+ORDER_CASES = [
+    (1, 1, 1, 1),           # a single pixel
+    (1, 5, 7, 5),           # one block, one partly filled wave
+    (1, 37, 70, 37),        # 3 partials
+    (1, 260, 346, 260),     # 88 partials: closing lanes with two partials next to lanes with one
+    (1, 400, 400, 400),     # the cap of 128 partials and several rounds per thread
+    (3, 37, 70, 37),        # one batch with an empty middle frame
+    (1, 37, 70, 29),        # max_row < h
+]
+_order_cases = {}
+
+
+def draw_order_inputs(F, h, w, seed):
+    """gt [F,2,h,w], pred [F,2,h,w], count [F,h,w]: infinities, zero vectors and
+    empty pixels, and per pixel a scale 2^-40 .. 2^6 on both the vector and the
+    error, so that the endpoint errors spread over 46 binades."""
+    rng = np.random.default_rng([F, h, w, seed])
+    scale = np.exp2(rng.uniform(-40, 6, (F, 1, h, w)))
+    gt = (rng.uniform(0.5, 2, (F, 2, h, w)) * rng.choice([-1.0, 1.0], (F, 2, h, w)) * scale).astype(_F)
+    angle = rng.uniform(0, 2 * np.pi, (F, 1, h, w))
+    pred = (gt + np.concatenate([np.cos(angle), np.sin(angle)], 1) * rng.uniform(0.5, 2, (F, 1, h, w)) * scale)
+    pred = pred.astype(_F)
+    drop = rng.random((F, h, w))
+    gt[:, 0][drop < 0.05] = np.inf
+    gt[:, 1][(drop >= 0.05) & (drop < 0.1)] = -np.inf
+    zero = (drop >= 0.1) & (drop < 0.15)
+    gt[:, 0][zero], gt[:, 1][zero] = 0, 0                   # zero vectors
+    count = (rng.random((F, h, w)) < 0.6) * rng.integers(1, 9, (F, h, w))
+    if h * w == 1:
+        gt[0, :, 0, 0], count[:] = (1.5, -2.25), 1          # the single pixel counts
+    if F == 3:
+        gt[1], count[1] = 0, 0                              # the empty frame: no vector, no event
+    return gt, pred, count.astype(np.int32)
+
+
+def restate_rows(gt, pred, count, max_row):
+    """-> (rows, terms): the rows EVAL_SPEC asks for, every step of the endpoint
+    error in numpy float32 (one rounding each), the sum by ``kernel_order_sum``
+    of the float64 terms [F,n] (0 where a pixel does not count)."""
+    F, _, h, w = gt.shape
+    tu, tv, qu, qv = gt[:, 0], gt[:, 1], pred[:, 0], pred[:, 1]
+    with np.errstate(invalid='ignore'):
+        m = ~np.isinf(tu) & ~np.isinf(tv) & (np.sqrt(tu * tu + tv * tv) > 0)
+        m[:, max_row:] = False
+        if count is not None:
+            m &= count > 0
+        du, dv = tu - qu, tv - qv
+        ee = np.sqrt(du * du + dv * dv)
+    assert ee.dtype == _F
+    terms = np.where(m, ee, _F(0)).astype(np.float64).reshape(F, h * w)
+    rows = np.zeros(F, dev_eval.RESULT_DTYPE)
+    rows['sum_ee'] = dev_eval.kernel_order_sum(terms, dev_eval.partial_blocks(h * w))
+    rows['n_points'] = m.reshape(F, -1).sum(1)
+    rows['n_below'] = (m & (ee < _F(3))).reshape(F, -1).sum(1)
+    rows['pred_max'], rows['pred_min'] = pred.reshape(F, -1).max(1), pred.reshape(F, -1).min(1)
+    return rows, terms
+
+
+def sees_the_order(terms, nb, restated):
+    """Another order of the same terms gives other bytes: numpy's sum, or the
+    kernels' order with the blocks of every round reversed."""
+    F, n = terms.shape
+    per = nb * 256
+    padded = np.zeros((F, -(-n // per) * per))
+    padded[:, :n] = terms
+    swapped = padded.reshape(F, -1, nb, 256)[:, :, ::-1].reshape(F, -1)
+    return terms.sum(1).tobytes() != restated.tobytes() or \
+        dev_eval.kernel_order_sum(swapped, nb).tobytes() != restated.tobytes()
+
+
+def order_case(F, h, w, max_row):
+    """-> (gt, pred, count, {dense: rows}), computed once.  A case of more than
+    one block that could not see a change of the order is drawn again."""
+    key = (F, h, w, max_row)
+    if key not in _order_cases:
+        nb = dev_eval.partial_blocks(h * w)
+        for seed in range(16):
+            gt, pred, count = draw_order_inputs(F, h, w, seed)
+            both = {dense: restate_rows(gt, pred, None if dense else count, max_row) for dense in (True, False)}
+            if nb == 1 or all(sees_the_order(terms, nb, rows['sum_ee']) for rows, terms in both.values()):
+                break
+        else:
+            raise AssertionError(f'{key}: no draw sees the order of the additions')
+        _order_cases[key] = (gt, pred, count, {dense: rows for dense, (rows, _) in both.items()})
+    return _order_cases[key]
+
+
+@pytest.mark.parametrize('dense', [True, False], ids=['dense', 'count'])
+@pytest.mark.parametrize('case', ORDER_CASES, ids=lambda c: 'F%d_%dx%d_rows%d' % c)
+def test_sum_ee_is_the_fixed_order_sum_byte_for_byte(case, dense):
+    """EVAL_SPEC "reduction order": sum_ee is ``kernel_order_sum`` of the
+    float32 endpoint errors, to the byte; the other fields are exact."""
+    F, h, w, max_row = case
+    gt, pred, count, rows = order_case(*case)
+    want = rows[dense]
+    assert dev_eval.partial_blocks(h * w) == {1: 1, 35: 1, 2590: 3, 89960: 88, 160000: 128}[h * w]
+    res = dev_eval.read_results(dev_eval.flow_error(
+        dev(gt[:, 0]), dev(gt[:, 1]), dev(pred), None if dense else dev(count), max_row))
+    print(case, 'dense' if dense else 'count', 'sum_ee', res['sum_ee'], 'restated', want['sum_ee'],
+          'n', res['n_points'])
+    for k in ('n_points', 'n_below', 'pred_max', 'pred_min'):
+        assert np.array_equal(res[k], want[k]), k
+    assert res['sum_ee'].tobytes() == want['sum_ee'].tobytes()
+    if F == 3:
+        assert res['n_points'][1] == 0 and res['sum_ee'][1] == 0.0 and (res['n_points'][[0, 2]] > 0).all()
+
+
 def test_reference_shaped_flow_error_dense(golden):
     gt, pred, count = error_inputs(golden, '260x346')
     aee, pct, n = dev_eval.flow_error_dense(gt, pred, count.astype(np.uint64), is_car=True)

@@ -92,6 +92,7 @@ def test_statistics(name):
         print(name, f, 'sum_sq', res['sum_sq'][f], 'error', abs(res['sum_sq'][f] - exact),
               'bound', n * 2.0 ** -53 * exact)
         assert abs(res['sum_sq'][f] - exact) <= n * 2.0 ** -53 * exact
+    assert res['sum_sq'].tobytes() == dev_eval.iwe_sum_sq_kernel_order(q).tobytes()     # the kernels' order
     assert torch.equal(dev_eval.iwe_stats(qd, cd), rows)        # a second run: the same bits
 
 
