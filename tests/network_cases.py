@@ -176,7 +176,7 @@ def first_difference(a, b):
     """-> None when a and b hold the same bits, else (flat index, a there, b there, count)."""
     a, b = a.detach().contiguous(), b.detach().contiguous()
     assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
-    ia = a.view(torch.int32 if a.element_size() == 4 else torch.int16).flatten()
+    ia = a.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]).flatten()
     ib = b.view(ia.dtype).flatten()
     ne = ia != ib
     n = int(ne.sum())

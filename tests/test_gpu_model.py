@@ -402,7 +402,8 @@ def test_mish_predictor_full_size_vs_float64_and_determinism():
 def test_bf16_operand_mode_tracks_the_f32_predictor():
     """compute_dtype='bf16' (operands rounded in registers, f32 accumulate and
     storage) against the exact-f32 predictor with the same weights: flows and
-    parameter gradients agree to bf16 accuracy."""
+    parameter gradients agree to bf16 accuracy.  These bounds are about rounding only: the
+    wiring of this mode is pinned exactly by tests/test_gpu_network_exact.py."""
     from dvs_of_training_framework_amd.predictor import Predictor
     torch.manual_seed(11)
     a = Predictor(5).cuda()
@@ -426,7 +427,8 @@ def test_bf16_operand_mode_tracks_the_f32_predictor():
 
 def test_bf16x3_mode_is_f32_accurate():
     """compute_dtype='bf16x3' (hi/lo split operands, three bf16 products) stays
-    inside the north star's 1e-3 relative parity budget with a wide margin."""
+    inside the north star's 1e-3 relative parity budget with a wide margin.  The bound is about
+    rounding only: the wiring of this mode is pinned exactly by tests/test_gpu_network_exact.py."""
     from dvs_of_training_framework_amd.predictor import Predictor
     torch.manual_seed(12)
     a = Predictor(5).cuda()
@@ -449,7 +451,9 @@ def test_bf16_twins_mode_matches_the_bf16_operand_mode():
     operands rounded in registers).  The forward of a layer is the SAME
     arithmetic in both -- bf16(x) * bf16(w) accumulated in f32 -- so flows agree
     to accumulation order; the data gradients differ by one bf16 rounding of
-    the stored gradient per layer.  Mish exercises the z twin-less path too."""
+    the stored gradient per layer.  Mish exercises the z twin-less path too.  The bounds are
+    about rounding only: the wiring of this mode (which twin is made, and when) is pinned
+    exactly by tests/test_gpu_network_exact.py."""
     from dvs_of_training_framework_amd.options import Mish
     from dvs_of_training_framework_amd.predictor import Predictor
     for act in (torch.nn.ReLU(), Mish()):
