@@ -31,6 +31,9 @@ HEADER_PATH = Path(__file__).resolve().parent.parent / 'include' / 'dvsof.h'
 # Extension headers, read after dvsof.h with its struct types known: their entry points are
 # tables of their own (EXTENSION_FUNCTIONS), beside the recorded one of dvsof.h (FUNCTIONS)
 EXTENSION_PATHS = (HEADER_PATH.with_name('dvsof_contrast.h'),)
+# A later extension with a table of its own again (CONTRAST_MULTI_FUNCTIONS): the table of
+# dvsof_contrast.h is recorded as exactly its three names and stays that
+CONTRAST_MULTI_PATH = HEADER_PATH.with_name('dvsof_contrast_multi.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -172,10 +175,18 @@ def dtype_of(struct):
 _header = Abi(HEADER_PATH.read_text())
 FUNCTIONS, STRUCTS, CONSTANTS = _header.functions, _header.structs, _header.constants
 EXTENSION_FUNCTIONS = {}
+
+
+def _read_extension(path, taken):
+    """The functions of one extension header; ``taken``: the names it must not repeat."""
+    ext = Abi(path.read_text(), base=_header, name=path.name)
+    clash = set(ext.functions) & set(taken)
+    if clash or ext.constants or set(ext.structs) != set(STRUCTS):
+        raise AbiError(f'{path.name}: an extension header declares new functions only '
+                       f'({sorted(clash) or "constants or structs found"})')
+    return ext.functions
+
+
 for _path in EXTENSION_PATHS:
-    _ext = Abi(_path.read_text(), base=_header, name=_path.name)
-    _clash = set(_ext.functions) & (set(FUNCTIONS) | set(EXTENSION_FUNCTIONS))
-    if _clash or _ext.constants or set(_ext.structs) != set(STRUCTS):
-        raise AbiError(f'{_path.name}: an extension header declares new functions only '
-                       f'({sorted(_clash) or "constants or structs found"})')
-    EXTENSION_FUNCTIONS.update(_ext.functions)
+    EXTENSION_FUNCTIONS.update(_read_extension(_path, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS)))
+CONTRAST_MULTI_FUNCTIONS = _read_extension(CONTRAST_MULTI_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS))

@@ -5,7 +5,9 @@ reads them from the header when the package is imported.  To add an entry
 point, declare it in include/dvsof.h and update
 tests/golden/abi_signatures.json, the recorded table a review sees change;
 or, leaving that table as it is, in an extension header (_abi.EXTENSION_PATHS:
-include/dvsof_contrast.h, recorded in tests/golden/abi_signatures_contrast.json).
+include/dvsof_contrast.h, recorded in tests/golden/abi_signatures_contrast.json;
+_abi.CONTRAST_MULTI_PATH: include/dvsof_contrast_multi.h, recorded in
+tests/golden/abi_signatures_contrast_multi.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -30,6 +32,8 @@ LossScale = STRUCTS['dvsof_loss_scale_t']
 _SIGNATURES = _abi.FUNCTIONS
 # the same of the extension headers (include/dvsof_contrast.h)
 _EXTENSION_SIGNATURES = _abi.EXTENSION_FUNCTIONS
+# and of include/dvsof_contrast_multi.h, a table of its own
+_CONTRAST_MULTI_SIGNATURES = _abi.CONTRAST_MULTI_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -42,13 +46,22 @@ def declared_symbols():
     return sorted(set(re.findall(r'\b(dvsof_[a-z0-9_]+)\s*\(', text)))
 
 
-def declared_extension_symbols():
-    """Names of all entry points the extension headers declare."""
+def _declared_in(paths):
     found = set()
-    for path in _abi.EXTENSION_PATHS:
+    for path in paths:
         text = re.sub(r'/\*.*?\*/', '', path.read_text(), flags=re.S)
         found |= set(re.findall(r'\b(dvsof_[a-z0-9_]+)\s*\(', text))
     return sorted(found)
+
+
+def declared_extension_symbols():
+    """Names of all entry points the extension headers declare."""
+    return _declared_in(_abi.EXTENSION_PATHS)
+
+
+def declared_contrast_multi_symbols():
+    """Names of all entry points include/dvsof_contrast_multi.h declares."""
+    return _declared_in((_abi.CONTRAST_MULTI_PATH,))
 
 
 def lib():
@@ -64,7 +77,7 @@ def lib():
         st = LIB_PATH.stat()
         global LOADED_STAT      # the file these code objects came from (_audit.py)
         LOADED_STAT = (st.st_ino, st.st_size, st.st_mtime_ns)
-        for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -281,6 +281,180 @@ def contrast_bwd_host(x, y, t, sample_index, frame_ts, frame_sample, flow, fwd, 
     return sw * value.astype(_F32), sums
 
 
+# Several reference times, ON and OFF events apart (csrc/contrast_multi.hip,
+# CONTRAST_SPEC sections 11-15)
+CONTRAST_REFERENCES = {'start': 0.0, 'middle': 0.5, 'end': 1.0}     # name -> rho, in the order of the mask's bits
+CONTRAST_SHARED_BITS = 2
+
+
+def contrast_reference_mask(references):
+    """('end', 'start') -> 5: bit 0 start, bit 1 middle, bit 2 end.  Names in
+    any order; an empty list, an unknown name and a duplicate are refused.  An
+    int in [1, 7] is taken as the mask it is."""
+    if isinstance(references, (int, np.integer)):
+        if not 1 <= references <= 7:
+            raise ValueError(f'reference mask {references} is outside [1, 7]')
+        return int(references)
+    if isinstance(references, str):
+        references = references.split(',')
+    names = list(CONTRAST_REFERENCES)
+    mask = 0
+    for name in references:
+        if name not in names:
+            raise ValueError(f'unknown reference time "{name}": one of {", ".join(names)}')
+        if mask >> names.index(name) & 1:
+            raise ValueError(f'reference time "{name}" is given twice')
+        mask |= 1 << names.index(name)
+    if not mask:
+        raise ValueError('no reference time given')
+    return mask
+
+
+def _contrast_rhos(mask):
+    return [_F32(rho) for b, rho in enumerate(CONTRAST_REFERENCES.values()) if mask >> b & 1]
+
+
+def _contrast_multi_pairs(x, y, t, p, sample_index, frame_ts, frame_sample, flow, polarity):
+    """The (event, frame) pairs that take part, frame by frame: dict of
+    per-pair arrays f, c (the channel), x, y, tau, u, v (the flow at the
+    event's own pixel).  With ``polarity`` an event with p == 0 takes no part;
+    without it p is not read."""
+    x, y = np.asarray(x, np.int64).reshape(-1), np.asarray(y, np.int64).reshape(-1)
+    t = np.asarray(t, _F32).reshape(-1)
+    s = np.asarray(sample_index, np.int64).reshape(-1)
+    ts = np.asarray(frame_ts, _F32).reshape(-1)
+    fs = np.asarray(frame_sample, np.int64).reshape(-1)
+    F, _, h, w = flow.shape
+    assert ts.size == 2 * F and fs.size == F and x.size == y.size == t.size == s.size
+    inb = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+    chan = np.zeros(x.size, np.int64)
+    if polarity:
+        p = np.asarray(p, np.int64).reshape(-1)
+        assert p.size == x.size
+        inb &= p != 0
+        chan = (p < 0).astype(np.int64)
+    sel = [np.flatnonzero(inb & (s == fs[f]) & (ts[2 * f] <= t) & (t <= ts[2 * f + 1]))
+           for f in range(F)]
+    e = np.concatenate(sel) if F else np.zeros(0, np.int64)
+    f = np.concatenate([np.full(k.size, i, np.int64) for i, k in enumerate(sel)]) if F \
+        else np.zeros(0, np.int64)
+    x, y, t = x[e], y[e], t[e]
+    t0 = ts[2 * f]
+    d = ts[2 * f + 1] - t0
+    with np.errstate(all='ignore'):
+        tau = np.where(d > 0, np.fmin(np.fmax((t - t0) / d, _F32(0)), _F32(1)), _F32(0)).astype(_F32)
+    return dict(f=f, c=chan[e], x=x, y=y, tau=tau, u=flow[f, 0, y, x], v=flow[f, 1, y, x])
+
+
+def _contrast_warp_to(p, rho, h, w):
+    """``warp_event_to`` of csrc/frame_common.h for the pairs p and one
+    reference: sig = tau - rho in float32, then steps 2-6 of IWE_SPEC section
+    2 with sig in place of tau -> dict sig, inside, cx, cy, wx [2], wy [2]."""
+    with np.errstate(all='ignore'):
+        sig = (p['tau'] - _F32(rho)).astype(_F32)
+        xw = p['x'].astype(_F32) - sig * p['u']
+        yw = p['y'].astype(_F32) - sig * p['v']
+        inside = (xw > _F32(-1)) & (xw < _F32(w)) & (yw > _F32(-1)) & (yw < _F32(h))
+        xw, yw = np.where(inside, xw, _F32(0)), np.where(inside, yw, _F32(0))
+    flx, fly = np.floor(xw), np.floor(yw)
+    fx, fy = xw - flx, yw - fly
+    return dict(sig=sig, inside=inside, cx=flx.astype(np.int64), cy=fly.astype(np.int64),
+                wx=(_F32(1) - fx, fx), wy=(_F32(1) - fy, fy))
+
+
+def contrast_multi_fwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flow, references=('start',),
+                            polarity=False):
+    """CONTRAST_SPEC sections 11-13 on the host: what
+    ``dvsof_contrast_multi_fwd`` is pinned to, byte for byte.  The arguments of
+    ``contrast_fwd_host`` and the column p int64 [n] (None without
+    ``polarity``); references: names or a mask.  With M = F R C images,
+    m = (f R + r) C + c -> dict: q int64 [M,h,w], count uint32 [M,h,w], result
+    (M rows), term float32, the per-image float64 records mean, coef, gmax,
+    image_term [M], the per-frame unit [F], and mask, R, C."""
+    from . import eval as ev
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    mask = contrast_reference_mask(references)
+    rhos, C = _contrast_rhos(mask), 2 if polarity else 1
+    R = len(rhos)
+    M = F * R * C
+    pr = _contrast_multi_pairs(x, y, t, p, sample_index, frame_ts, frame_sample, flow, polarity)
+    q = np.zeros((M, h, w), np.int64)
+    count = np.zeros((M, h, w), np.uint32)
+    for r, rho in enumerate(rhos):
+        m = (pr['f'] * R + r) * C + pr['c']
+        np.add.at(count, (m, pr['y'], pr['x']), 1)
+        wp = _contrast_warp_to(pr, rho, h, w)
+        k = wp['inside']
+        mk, cx, cy = m[k], wp['cx'][k], wp['cy'][k]
+        for j in range(2):
+            for i in range(2):
+                xx, yy = cx + i, cy + j
+                Q = ((wp['wy'][j][k] * wp['wx'][i][k]).astype(_F32) * _F32(ev.IWE_ONE)).astype(np.int64)
+                ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h) & (Q > 0)
+                np.add.at(q, (mk[ok], yy[ok], xx[ok]), Q[ok])
+    res = ev.iwe_stats_host(q, count)
+    res['sum_sq'] = ev.iwe_sum_sq_kernel_order(q)
+    # the closing wave, in float64
+    N = np.float64(h) * np.float64(w)
+    mean = res['sum_q'].astype(np.float64) * 2.0 ** -32 / N
+    var_i = res['sum_sq'] / N - mean * mean
+    cmean = res['count_sum'].astype(np.float64) / N
+    var_c = res['count_sq'].astype(np.float64) / N - cmean * cmean
+    live = var_c > 0
+    with np.errstate(all='ignore'):
+        coef = np.where(live, -2.0 / (N * var_c), 0.0)
+        image_term = np.where(live, 1.0 - var_i / var_c, 0.0)
+    gmax = np.abs(coef) * np.fmax(res['max_q'].astype(np.float64) * 2.0 ** -32 - mean, mean)
+    frame_gmax = gmax.reshape(F, R * C).max(1) if F else np.zeros(0)
+    e = np.where(frame_gmax > 0, np.frexp(frame_gmax)[1], 0)
+    unit = np.ldexp(1.0, CONTRAST_UNIT_BITS - (CONTRAST_SHARED_BITS if R > 1 else 0) - e)
+    total = np.float64(0)
+    for v in image_term:                # in image order
+        total = total + v
+    with np.errstate(all='ignore'):
+        term = _F32(total / np.float64(M))
+    return dict(q=q, count=count, result=res, term=term, mean=mean, coef=coef, gmax=gmax,
+                image_term=image_term, unit=unit, mask=mask, R=R, C=C)
+
+
+def contrast_multi_bwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flow, fwd, seed=1.0, weight=1.0):
+    """CONTRAST_SPEC section 14 on the host: what ``dvsof_contrast_multi_bwd``
+    is pinned to.  fwd: the dict of ``contrast_multi_fwd_host`` for the same
+    input; references and polarity are read from it.  -> (grad_flow float32
+    [F,2,h,w] = seed * weight * d term / d flow, sums int64 [F,2,h,w], the
+    fixed-point sums of all images of a frame in units of 1/unit[f])."""
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    R, C = fwd['R'], fwd['C']
+    M = F * R * C
+    pr = _contrast_multi_pairs(x, y, t, p, sample_index, frame_ts, frame_sample, flow, C == 2)
+    sums = np.zeros((F, 2, h, w), np.int64)
+    for r, rho in enumerate(_contrast_rhos(fwd['mask'])):
+        m = (pr['f'] * R + r) * C + pr['c']
+        wp = _contrast_warp_to(pr, rho, h, w)
+        k = wp['inside'] & (fwd['coef'][m] != 0)
+        m, f, cx, cy, px, py = m[k], pr['f'][k], wp['cx'][k], wp['cy'][k], pr['x'][k], pr['y'][k]
+        coef, mean, unit = fwd['coef'][m], fwd['mean'][m], fwd['unit'][f]
+        G = [[None, None], [None, None]]
+        for j in range(2):
+            for i in range(2):
+                xx, yy = cx + i, cy + j
+                ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+                Q = fwd['q'][m, np.where(ok, yy, 0), np.where(ok, xx, 0)]
+                G[j][i] = np.where(ok, coef * (Q.astype(np.float64) * 2.0 ** -32 - mean), 0.0)
+        wx = [a[k].astype(np.float64) for a in wp['wx']]
+        wy = [a[k].astype(np.float64) for a in wp['wy']]
+        gx = wy[0] * (G[0][1] - G[0][0]) + wy[1] * (G[1][1] - G[1][0])
+        gy = wx[0] * (G[1][0] - G[0][0]) + wx[1] * (G[1][1] - G[0][1])
+        ms = -wp['sig'][k].astype(np.float64)
+        np.add.at(sums, (f, 0, py, px), np.trunc(ms * gx * unit).astype(np.int64))
+        np.add.at(sums, (f, 1, py, px), np.trunc(ms * gy * unit).astype(np.int64))
+    value = sums.astype(np.float64) / fwd['unit'].reshape(F, 1, 1, 1) / np.float64(max(M, 1))
+    sw = _F32(seed) * _F32(weight)
+    return sw * value.astype(_F32), sums
+
+
 class _Contrast(torch.autograd.Function):
     """(weight * term, term) of the finest flow; the gradient of the first
     enters the flow (dvsof_contrast_fwd / dvsof_contrast_bwd).  The weight is
@@ -328,6 +502,57 @@ class _Contrast(torch.autograd.Function):
             flow.data_ptr(), F, h, w, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(),
             ctx.weight, grad.data_ptr(), _lib.stream()), 'dvsof_contrast_bwd')
         return (grad,) + (None,) * 7
+
+
+class _ContrastMulti(torch.autograd.Function):
+    """``_Contrast`` with several reference times and the polarities apart
+    (dvsof_contrast_multi_fwd / dvsof_contrast_multi_bwd)."""
+
+    @staticmethod
+    def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity):
+        from .eval import IWE_RESULT_DTYPE
+        dev = flow.device
+        flow = flow.detach().contiguous().float()
+        F, _, h, w = flow.shape
+        lib = _lib.lib()
+        M = F * bin(mask).count('1') * (2 if polarity else 1)
+        q = torch.empty(M, h, w, dtype=torch.long, device=dev)
+        count = torch.empty(M, h, w, dtype=torch.int32, device=dev)
+        result = torch.empty(M, IWE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        term = torch.zeros((), dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+        nbytes = lib.dvsof_contrast_multi_workspace_bytes(F, mask, int(polarity), h, w)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
+        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
+        pol = p.contiguous() if polarity else None
+        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
+        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flow.shape, frame_ts.shape)
+        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
+        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
+        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
+        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
+                                                        tables[0].data_ptr(), tables[1].data_ptr(),
+                                                        flow.data_ptr(), F, h, w, mask, int(polarity)])
+        _lib.check(lib.dvsof_contrast_multi_fwd(
+            *ctx.args, q.data_ptr(), count.data_ptr(), result.data_ptr(), term.data_ptr(), ws.data_ptr(),
+            nbytes, _lib.stream()), 'dvsof_contrast_multi_fwd')
+        ctx.held = (cols, pol, tables, flow, q, ws, nbytes)
+        ctx.weight = float(weight)
+        ctx.mark_non_differentiable(term)
+        ctx.set_materialize_grads(False)
+        return term * ctx.weight, term
+
+    @staticmethod
+    def backward(ctx, g_value, _g_term):
+        if g_value is None:
+            return (None,) * 11
+        flow, q, ws, nbytes = ctx.held[3:]
+        grad = torch.empty_like(flow)
+        seed = g_value.contiguous().float()
+        _lib.check(_lib.lib().dvsof_contrast_multi_bwd(
+            *ctx.args, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(),
+            _lib.stream()), 'dvsof_contrast_multi_bwd')
+        return (grad,) + (None,) * 10
 
 
 class Loss:
@@ -447,7 +672,8 @@ class Losses:
         return _FusedLoss.apply(frames, img, start, stop, tuple(weights),
                                 loss_scale, *flows)
 
-    def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None):
+    def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None,
+                 references=('start',), polarity=False):
         """The contrast-maximisation term of the finest flow ``flows[-1]``
         (docs/CONTRAST_SPEC.md): the mean over the predictions of
         1 - var(image of warped events) / var(count image), negative where the
@@ -455,14 +681,28 @@ class Losses:
         on the device.  -> the 0-dim term, differentiable with respect to
         ``flows[-1]``; with a ``weight`` -> (weight * term, term), the first
         differentiable (the weight is applied inside the backward kernel), the
-        second detached for logging.  Nothing waits for the device."""
+        second detached for logging.  Nothing waits for the device.
+
+        references: names among 'start', 'middle', 'end', the times of the
+        window the events are warped to, one image each; polarity: ON and OFF
+        events in images of their own (``events['polarity']``; an event of
+        polarity 0 takes no part).  The term is the mean over all images
+        (CONTRAST_SPEC sections 11-15).  The defaults are the term as it was,
+        by the calls it was."""
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the contrast term of scale {self.shapes[-1]}'
         cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
         _lib.require_cuda(flow, flow_ts, flow_sample_idx, *cols)
-        value, term = _Contrast.apply(flow, *cols, flow_ts, flow_sample_idx,
-                                      1.0 if weight is None else float(weight))
+        mask = contrast_reference_mask(references)
+        weight_ = 1.0 if weight is None else float(weight)
+        if mask == 1 and not polarity:
+            value, term = _Contrast.apply(flow, *cols, flow_ts, flow_sample_idx, weight_)
+        else:
+            pol = events['polarity'] if polarity else None
+            _lib.require_cuda(pol)
+            value, term = _ContrastMulti.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx,
+                                               weight_, mask, bool(polarity))
         return value if weight is None else (value, term)
 
 

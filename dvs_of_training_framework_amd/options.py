@@ -292,6 +292,17 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'Validation/contrast.  Needs the raw events in their wire '
                              'columns on the device (not --ev_images, not '
                              '--compact-events); such a run is not captured.  0: off')
+    parser.add_argument('--contrast-references', dest='contrast_references',
+                        default='start', type=str,
+                        help='comma-separated reference times of the contrast term, among '
+                             'start, middle, end (any order, none twice): the events are '
+                             'warped to each of these times of their window and the term is '
+                             'the mean over the images (Zhu et al. 2019: start,end; Shiba et '
+                             'al. 2022: start,middle,end).  Needs --contrast-weight')
+    parser.add_argument('--contrast-polarity', dest='contrast_polarity',
+                        action='store_true',
+                        help='accumulate ON and OFF events in images of their own in the '
+                             'contrast term.  Needs --contrast-weight')
     parser.add_argument('--sync-checkpoints', dest='sync_checkpoints',
                         action='store_true',
                         help='write checkpoints on the training thread (state_dict() + '
@@ -352,11 +363,35 @@ def validate_train_args(args):             # utils/options.py:318-325
     return validate_contrast_args(args)
 
 
+CONTRAST_REFERENCE_NAMES = ('start', 'middle', 'end')
+
+
+def parse_contrast_references(text):
+    """'end,start' -> ('start', 'end'): the names in the order of the window."""
+    names = [n.strip() for n in text.split(',')] if isinstance(text, str) else list(text)
+    for n in names:
+        if n not in CONTRAST_REFERENCE_NAMES:
+            raise SystemExit(f'--contrast-references: unknown reference time "{n}", '
+                             f'one of {", ".join(CONTRAST_REFERENCE_NAMES)}')
+        if names.count(n) > 1:
+            raise SystemExit(f'--contrast-references: "{n}" is given twice')
+    return tuple(n for n in CONTRAST_REFERENCE_NAMES if n in names)
+
+
 def validate_contrast_args(args):
-    """--contrast-weight against what it cannot be combined with."""
+    """--contrast-weight against what it cannot be combined with, and the
+    term's options against a run without the term.  ``args.contrast_references``
+    becomes a tuple of names."""
     weight = getattr(args, 'contrast_weight', 0.0)
     if weight < 0 or weight != weight:
         raise SystemExit(f'--contrast-weight must not be negative, got {weight}')
+    args.contrast_references = parse_contrast_references(getattr(args, 'contrast_references', 'start'))
+    args.contrast_polarity = bool(getattr(args, 'contrast_polarity', False))
+    if not weight > 0:
+        if args.contrast_references != ('start',):
+            raise SystemExit('--contrast-references needs a positive --contrast-weight')
+        if args.contrast_polarity:
+            raise SystemExit('--contrast-polarity needs a positive --contrast-weight')
     if weight > 0 and getattr(args, 'ev_images', False):
         raise SystemExit('--contrast-weight cannot be combined with --ev_images: the term is '
                          'computed from the raw events on the device, and a batch of '

@@ -56,9 +56,30 @@ class _TermsAndContrast(tuple):
         return self
 
 
+def _contrast_options(references, polarity):
+    """The keywords of ``Losses.contrast`` that differ from its defaults, so
+    that a run without them makes the call it always made."""
+    out = {}
+    if tuple(references) != ('start',):
+        out['references'] = tuple(references)
+    if polarity:
+        out['polarity'] = True
+    return out
+
+
+def _contrast_keywords(weight, references, polarity):
+    """What a call down the chain gets: nothing at weight 0, and the options
+    only where they differ from the defaults."""
+    if not weight:
+        return {}
+    return dict({'contrast_weight': weight},
+                **{'contrast_' + k: v for k, v in _contrast_options(references, polarity).items()})
+
+
 def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   timestamps, sample_idx, features, weights=[0.5, 1, 1],
-                  frame_indices=None, contrast_weight=0.0, events=None):
+                  frame_indices=None, contrast_weight=0.0, events=None,
+                  contrast_references=('start',), contrast_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
     that has ``fused`` and flows that need gradients the value and the flow
     gradients come out of one sweep (loss.Losses.fused).
@@ -67,7 +88,9 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     of the finest flow over ``events``, the wire columns on the device
     (loss.Losses.contrast, docs/CONTRAST_SPEC.md); the term rides on the
     returned terms as ``.contrast``.  At 0 nothing of that is constructed and
-    ``events`` is not looked at."""
+    ``events`` is not looked at.  contrast_references, contrast_polarity: the
+    reference times of the term and whether ON and OFF events are kept apart
+    (``Losses.contrast``); the defaults are the term of one image per frame."""
     extra = {} if frame_indices is None else {'frame_indices': frame_indices}
     call = (flows, flow_ts, flow_sample_idx, images, timestamps, sample_idx)
     trainable = torch.is_grad_enabled() and \
@@ -88,7 +111,8 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         raise ValueError('contrast_weight > 0 needs the raw events of the batch on the device '
                          '(is_raw=True); preprocessed voxel grids carry none')
     value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events,
-                                     weight=contrast_weight)
+                                     weight=contrast_weight, **_contrast_options(
+                                         contrast_references, contrast_polarity))
     return loss + value, _TermsAndContrast(terms, term)
 
 
@@ -168,14 +192,14 @@ def _to_device(batch, device, is_raw):
 
 
 def process_minibatch(model, batch, timers, device, is_raw, evaluator,
-                      weights, return_prediction=False, contrast_weight=0.0):
+                      weights, return_prediction=False, contrast_weight=0.0,
+                      contrast_references=('start',), contrast_polarity=False):
     """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs]).
-    contrast_weight > 0 (raw events only): see ``combined_loss``."""
-    contrast = {}
-    if contrast_weight:
-        if not is_raw:
-            raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
-        contrast = {'contrast_weight': contrast_weight}
+    contrast_weight > 0 (raw events only), contrast_references,
+    contrast_polarity: see ``combined_loss``."""
+    contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity)
+    if contrast and not is_raw:
+        raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
     with _timed(timers, 'batch2gpu'):
         timestamps, sample_idx, images, payload = _to_device(batch, device,
                                                              is_raw)
@@ -368,7 +392,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           max_events_per_batch: int = 350000, reducer=None,
           log_every: int = 1, capture=False, guard=None,
           max_skipped_steps: int = 32, guard_agreement_every: int = 0,
-          contrast_weight: float = 0.0):
+          contrast_weight: float = 0.0, contrast_references=('start',),
+          contrast_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
     batches above ``max_events_per_batch`` events are skipped and not counted,
@@ -403,6 +428,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                the finest flow to the loss (docs/CONTRAST_SPEC.md; raw events
                only), logged as ``Train/contrast``; such a run is not
                captured.  0: the step launches what it launches without it
+    contrast_references, contrast_polarity:  the reference times of that term
+               ('start', 'middle', 'end') and whether ON and OFF events are
+               accumulated apart (``loss.Losses.contrast``)
     """
     if timers is None:
         on_gpu = torch.device(device).type == 'cuda'
@@ -450,7 +478,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
         if not replayed:
             loss, terms, tags = process_minibatch(
                 model, batch, timers, device, is_raw, evaluator, weights,
-                **({'contrast_weight': contrast_weight} if contrast_weight else {}))
+                **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass
@@ -516,11 +544,12 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
 
 
 def validate(model, device, loader, samples_passed, logger, evaluator,
-             weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0):
+             weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
+             contrast_references=('start',), contrast_polarity=False):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
-    the loss holds the contrast-maximisation term, written as
-    ``Validation/contrast``."""
+    the loss holds the contrast-maximisation term (of those reference times
+    and polarity setting), written as ``Validation/contrast``."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -528,7 +557,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
         for batch in loader:
             loss, terms, tags = process_minibatch(
                 model, batch, quiet, device, is_raw, evaluator, weights,
-                **({'contrast_weight': contrast_weight} if contrast_weight else {}))
+                **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity))
             sums.add(loss, terms, tags)
     logger.add_scalar('General/Validation loss', sums.loss / n_batches,
                       samples_passed)

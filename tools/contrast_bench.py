@@ -13,6 +13,10 @@ per sample.
   step    the eager training step (Ranger, f32, process_minibatch +
           unit_backward + step) with contrast_weight 0 against --weight, in
           alternating blocks of one run; the median block of each.
+  --multi only this: the existing calls, dvsof_contrast_multi_fwd / _bwd at
+          mask = start without polarity and at all three references with
+          polarity, in alternating blocks of one run
+          (profiles/contrast_multi/README.md).
 """
 import argparse
 import json
@@ -100,6 +104,71 @@ def calls_alone(rounds=7, reps=40, seed=0):
     return out
 
 
+def calls_multi(rounds=9, reps=40, seed=0):
+    """dvsof_contrast_fwd / _bwd (the existing calls), dvsof_contrast_multi_fwd
+    / _bwd at mask = start without polarity (the same work by the new kernels)
+    and at all three references with polarity (six images per frame), the six
+    taking turns block by block within one run."""
+    dev, lib, stream = 'cuda', _lib.lib(), _lib.stream()
+    batch = synthetic.make_batch(seed, B, H, W, EVENTS)
+    ev = batch['events']
+    rng = np.random.default_rng(seed)
+    c = dict(x=ev['x'], y=ev['y'], t=ev['timestamp'], p=ev['polarity'], s=ev['sample_index'],
+             ts=np.tile(np.array([0, synthetic.WINDOW], np.float32), B), fs=np.arange(B, dtype=np.int64),
+             flow=rng.normal(0, 3, (B, 2, H, W)).astype(np.float32))
+    d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in c.items()}
+    n, F = d['x'].numel(), B
+    grad = torch.empty(F, 2, H, W, device=dev)
+    seed_t = torch.ones((), device=dev)
+    tables = [d[k].data_ptr() for k in ('ts', 'fs', 'flow')]
+
+    def check(rc):
+        assert rc == 0, rc
+
+    def buffers(M, need):
+        return dict(q=torch.empty(M, H, W, dtype=torch.long, device=dev),
+                    count=torch.empty(M, H, W, dtype=torch.int32, device=dev),
+                    rows=torch.empty(M, 48, dtype=torch.uint8, device=dev), term=torch.empty((), device=dev),
+                    ws=torch.empty(need // 8, dtype=torch.long, device=dev), need=need)
+
+    def outs(b):
+        return [b[k].data_ptr() for k in ('q', 'count', 'rows', 'term', 'ws')] + [b['need'], stream]
+
+    old = buffers(F, lib.dvsof_contrast_workspace_bytes(F, H, W))
+    cols = [d[k].data_ptr() for k in ('x', 'y', 't', 's')] + [n] + tables + [F, H, W]
+    calls = {
+        'parent_fwd': lambda: check(lib.dvsof_contrast_fwd(*cols, *outs(old))),
+        'parent_bwd': lambda: check(lib.dvsof_contrast_bwd(*cols, old['q'].data_ptr(), old['ws'].data_ptr(),
+                                                           old['need'], seed_t.data_ptr(), 0.25, grad.data_ptr(),
+                                                           stream))}
+    held = {}
+    for tag, mask, pol in (('start', 1, 0), ('all_polarity', 7, 1)):
+        M = F * bin(mask).count('1') * (1 + pol)
+        b = held[tag] = buffers(M, lib.dvsof_contrast_multi_workspace_bytes(F, mask, pol, H, W))
+        head = [d[k].data_ptr() for k in ('x', 'y', 't', 'p', 's')] + [n] + tables + [F, H, W, mask, pol]
+        calls[tag + '_fwd'] = lambda head=head, b=b: check(lib.dvsof_contrast_multi_fwd(*head, *outs(b)))
+        calls[tag + '_bwd'] = lambda head=head, b=b: check(lib.dvsof_contrast_multi_bwd(
+            *head, b['q'].data_ptr(), b['ws'].data_ptr(), b['need'], seed_t.data_ptr(), 0.25, grad.data_ptr(), stream))
+    grads = {}
+    for k, fn in calls.items():
+        for _ in range(3):
+            fn()
+        grads[k] = grad.clone()
+    torch.cuda.synchronize()
+    # mask = start without polarity is the existing term, bit for bit
+    assert torch.equal(old['q'], held['start']['q']) and torch.equal(old['term'], held['start']['term'])
+    assert torch.equal(grads['parent_bwd'], grads['start_bwd'])
+    blocks = {k: [] for k in calls}
+    for _ in range(rounds):
+        for k, fn in calls.items():
+            blocks[k].append(block_us(fn, reps))
+    out = dict(events=n, rounds=rounds, reps=reps, terms={k: float(b['term']) for k, b in held.items()})
+    for k, v in blocks.items():
+        out[k] = dict(us=round(statistics.median(v), 2), min_us=round(min(v), 2), max_us=round(max(v), 2),
+                      blocks=[round(u, 2) for u in v])
+    return out
+
+
 class Leg:
     def __init__(self, weight):
         torch.manual_seed(1234)
@@ -147,7 +216,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--weight', type=float, default=0.25)
     ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--multi', action='store_true',
+                    help='only the leg of the entry points with several references and the polarities '
+                         'apart against the existing ones (profiles/contrast_multi/README.md)')
     args = ap.parse_args()
+    if args.multi:
+        print(json.dumps(dict(shape=dict(B=B, H=H, W=W, events_per_sample=EVENTS), multi=calls_multi())))
+        return
     print(json.dumps(dict(shape=dict(B=B, H=H, W=W, bins=BINS, events_per_sample=EVENTS),
                           calls=calls_alone(args.rounds), step=step_off_against_on(args.weight, args.rounds))))
 

@@ -24,6 +24,9 @@
 #   contrast [contrast_bench.py args] contrast-maximisation term (tools/contrast_bench.py): dvsof_contrast_fwd and
 #                                     dvsof_contrast_bwd alone at batch 8, 256x256, 65 536 events per sample; the eager
 #                                     training step with --contrast-weight 0 against 0.25 in alternating blocks
+#   contrast-multi [contrast_bench.py args]  its --multi leg: dvsof_contrast_fwd / _bwd, dvsof_contrast_multi_fwd /
+#                                     _bwd at mask = start without polarity and at all three references with
+#                                     polarity, in alternating blocks of one run (profiles/contrast_multi/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -89,6 +92,9 @@ iwe)
 contrast)
   timeout -k 10 420 env "${envs[@]}" python tools/contrast_bench.py "$@" > $O/contrast.json 2> $O/contrast.err
   echo "contrast rc=$?"; cut -c1-2600 $O/contrast.json; tail -3 $O/contrast.err ;;
+contrast-multi)
+  timeout -k 10 420 env "${envs[@]}" python tools/contrast_bench.py --multi "$@" > $O/contrast_multi.json 2> $O/contrast_multi.err
+  echo "contrast-multi rc=$?"; cut -c1-2600 $O/contrast_multi.json; tail -3 $O/contrast_multi.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

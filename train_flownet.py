@@ -462,7 +462,9 @@ def main(argv=None):
         hooks['validation'] = ValidationHook(
             model, device, validation_loader, logger, losses,
             args.loss_weights, args.is_raw,
-            **({'contrast_weight': args.contrast_weight}
+            **({'contrast_weight': args.contrast_weight,
+                'contrast_references': getattr(args, 'contrast_references', ('start',)),
+                'contrast_polarity': getattr(args, 'contrast_polarity', False)}
                if getattr(args, 'contrast_weight', 0.0) else {}))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
     elif not args.skip_validation:
@@ -489,7 +491,9 @@ def main(argv=None):
                   guard=host_guard,
                   max_skipped_steps=getattr(args, 'max_skipped_steps', 32),
                   guard_agreement_every=args.checkpointing_interval,
-                  contrast_weight=getattr(args, 'contrast_weight', 0.0))
+                  contrast_weight=getattr(args, 'contrast_weight', 0.0),
+                  contrast_references=getattr(args, 'contrast_references', ('start',)),
+                  contrast_polarity=getattr(args, 'contrast_polarity', False))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
