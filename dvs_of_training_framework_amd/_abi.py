@@ -34,6 +34,8 @@ EXTENSION_PATHS = (HEADER_PATH.with_name('dvsof_contrast.h'),)
 # A later extension with a table of its own again (CONTRAST_MULTI_FUNCTIONS): the table of
 # dvsof_contrast.h is recorded as exactly its three names and stays that
 CONTRAST_MULTI_PATH = HEADER_PATH.with_name('dvsof_contrast_multi.h')
+# And one more (IWE_MULTI_FUNCTIONS): the validation side of the same options
+IWE_MULTI_PATH = HEADER_PATH.with_name('dvsof_iwe_multi.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -190,3 +192,5 @@ def _read_extension(path, taken):
 for _path in EXTENSION_PATHS:
     EXTENSION_FUNCTIONS.update(_read_extension(_path, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS)))
 CONTRAST_MULTI_FUNCTIONS = _read_extension(CONTRAST_MULTI_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS))
+IWE_MULTI_FUNCTIONS = _read_extension(IWE_MULTI_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS)
+                                     | set(CONTRAST_MULTI_FUNCTIONS))

@@ -7,7 +7,8 @@ tests/golden/abi_signatures.json, the recorded table a review sees change;
 or, leaving that table as it is, in an extension header (_abi.EXTENSION_PATHS:
 include/dvsof_contrast.h, recorded in tests/golden/abi_signatures_contrast.json;
 _abi.CONTRAST_MULTI_PATH: include/dvsof_contrast_multi.h, recorded in
-tests/golden/abi_signatures_contrast_multi.json).
+tests/golden/abi_signatures_contrast_multi.json; _abi.IWE_MULTI_PATH:
+include/dvsof_iwe_multi.h, recorded in tests/golden/abi_signatures_iwe_multi.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -34,6 +35,8 @@ _SIGNATURES = _abi.FUNCTIONS
 _EXTENSION_SIGNATURES = _abi.EXTENSION_FUNCTIONS
 # and of include/dvsof_contrast_multi.h, a table of its own
 _CONTRAST_MULTI_SIGNATURES = _abi.CONTRAST_MULTI_FUNCTIONS
+# and of include/dvsof_iwe_multi.h, likewise
+_IWE_MULTI_SIGNATURES = _abi.IWE_MULTI_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -64,6 +67,11 @@ def declared_contrast_multi_symbols():
     return _declared_in((_abi.CONTRAST_MULTI_PATH,))
 
 
+def declared_iwe_multi_symbols():
+    """Names of all entry points include/dvsof_iwe_multi.h declares."""
+    return _declared_in((_abi.IWE_MULTI_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -77,7 +85,8 @@ def lib():
         st = LIB_PATH.stat()
         global LOADED_STAT      # the file these code objects came from (_audit.py)
         LOADED_STAT = (st.st_ino, st.st_size, st.st_mtime_ns)
-        for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES,
+                                  **_IWE_MULTI_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -331,6 +331,75 @@ def iwe_splat_host(x, y, t, frame_event_begin, frame_ts, flow):
     return q
 
 
+IWE_REFERENCES = (('start', 0.0), ('middle', 0.5), ('end', 1.0))    # in the order of the mask's bits
+IWE_CHANNELS = ('ON', 'OFF')
+
+
+def iwe_image_names(mask, polarity):
+    """[(reference name, channel name or None)] of the R C images of a frame, in image order."""
+    refs = [name for b, (name, _) in enumerate(IWE_REFERENCES) if mask >> b & 1]
+    return [(r, c) for r in refs for c in (IWE_CHANNELS if polarity else (None,))]
+
+
+def iwe_splat_multi_host(x, y, t, p, frame_event_begin, frame_ts, flow, references=('start',), polarity=False):
+    """IWE_SPEC sections 8-9 in numpy float32: what ``iwe_splat_multi`` runs
+    without a GPU and what ``dvsof_iwe_splat_multi`` is pinned to, byte for
+    byte.  The arguments of ``iwe_splat_host`` and the column p int64 [n]
+    (not read without ``polarity``; may be None); references: names or a mask.
+    With M = F R C images, m = (f R + r) C + c -> (q int64 [M,h,w], count
+    uint32 [M,h,w])."""
+    from .loss import contrast_reference_mask
+    mask = contrast_reference_mask(references)
+    rhos = [_F(rho) for b, (_, rho) in enumerate(IWE_REFERENCES) if mask >> b & 1]
+    R, C = len(rhos), 2 if polarity else 1
+    x, y = np.asarray(x, np.int64).reshape(-1), np.asarray(y, np.int64).reshape(-1)
+    t = np.asarray(t, _F).reshape(-1)
+    begin = np.asarray(frame_event_begin, np.int64).reshape(-1)
+    ts = np.asarray(frame_ts, _F).reshape(-1)
+    flow = np.asarray(flow, _F)
+    F, _, h, w = flow.shape
+    assert begin.size == F + 1 and ts.size == 2 * F and x.size == y.size == t.size
+    q = np.zeros((F * R * C, h, w), np.int64)
+    count = np.zeros((F * R * C, h, w), np.uint32)
+    if F == 0 or x.size == 0:
+        return q, count
+    e = np.arange(x.size, dtype=np.int64)
+    keep = (e >= begin[0]) & (e < begin[F]) & (x >= 0) & (x < w) & (y >= 0) & (y < h)
+    chan = np.zeros(x.size, np.int64)
+    if polarity:
+        p = np.asarray(p, np.int64).reshape(-1)
+        assert p.size == x.size
+        keep &= p != 0
+        chan = (p < 0).astype(np.int64)
+    e = e[keep]
+    f = np.searchsorted(begin[:F], e, side='right') - 1     # the last f with begin[f] <= e
+    x, y, t, chan = x[keep], y[keep], t[keep], chan[keep]
+    t0 = ts[2 * f]
+    d = ts[2 * f + 1] - t0
+    with np.errstate(all='ignore'):
+        tau = np.where(d > 0, np.fmin(np.fmax((t - t0) / d, _F(0)), _F(1)), _F(0)).astype(_F)
+    u, v = flow[f, 0, y, x], flow[f, 1, y, x]
+    for r, rho in enumerate(rhos):
+        m = (f * R + r) * C + chan
+        np.add.at(count, (m, y, x), 1)
+        with np.errstate(all='ignore'):
+            sig = (tau - rho).astype(_F)
+            xw = x.astype(_F) - sig * u
+            yw = y.astype(_F) - sig * v
+            inside = (xw > _F(-1)) & (xw < _F(w)) & (yw > _F(-1)) & (yw < _F(h))
+        mi, xi, yi = m[inside], xw[inside], yw[inside]
+        flx, fly = np.floor(xi), np.floor(yi)
+        fx, fy = xi - flx, yi - fly
+        cx, cy = flx.astype(np.int64), fly.astype(np.int64)
+        for j, wy in enumerate((_F(1) - fy, fy)):
+            for i, wx in enumerate((_F(1) - fx, fx)):
+                xx, yy = cx + i, cy + j
+                Q = ((wy * wx).astype(_F) * _F(IWE_ONE)).astype(np.int64)    # truncates
+                ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h) & (Q > 0)
+                np.add.at(q, (mi[ok], yy[ok], xx[ok]), Q[ok])
+    return q, count
+
+
 def iwe_stats_host(q, count):
     """IWE_SPEC section 3 on the host -> structured array [F]
     (IWE_RESULT_DTYPE).  The integer fields are exact; sum_sq is a float64 sum
@@ -451,6 +520,51 @@ def iwe_splat(events, win_out, frame_ts, flow):
         frame_ts.data_ptr(), flow.data_ptr(), F, h, w, q.data_ptr(), _lib.stream()),
         'dvsof_iwe_splat')
     return q
+
+
+def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), polarity=False):
+    """``iwe_splat`` at several reference times of the window and with ON and
+    OFF events apart (csrc/iwe_multi.hip, IWE_SPEC sections 8-13).  events,
+    win_out, frame_ts, flow as ``iwe_splat`` takes them, and the column
+    'polarity' int64 with ``polarity``; references: names among start, middle,
+    end, or a mask (``loss.contrast_reference_mask``).  With M = F R C images,
+    m = (f R + r) C + c -> (q int64 [M,h,w] in units of 2^-32, count int32
+    [M,h,w] holding the uint32 counts of the image's channel) on the device;
+    ``iwe_splat_multi_host`` (numpy arrays, count uint32) for host input.
+    ``iwe_stats`` and ``iwe_render`` take them as M frames."""
+    from .loss import contrast_reference_mask
+    mask, polarity = contrast_reference_mask(references), bool(polarity)
+    x, y, t = events['x'], events['y'], events['timestamp']
+    if polarity and events.get('polarity') is None:
+        raise ValueError('polarity=True needs the events\' polarity column')
+    p = events['polarity'] if polarity else None
+    if not _on_device(flow):
+        return iwe_splat_multi_host(_np(x), _np(y), _np(t), None if p is None else _np(p), _np(win_out),
+                                    _np(frame_ts), _np(flow), mask, polarity)
+    _lib.require_cuda(x, y, t, p, frame_ts)
+    x, y, t = x.contiguous(), y.contiguous(), t.contiguous()
+    flow, frame_ts = flow.contiguous(), frame_ts.contiguous()
+    assert x.dtype == y.dtype == torch.long and t.dtype == flow.dtype == frame_ts.dtype == torch.float32
+    assert x.numel() == y.numel() == t.numel()
+    if p is not None:
+        p = p.contiguous()
+        assert p.dtype == torch.long and p.numel() == x.numel()
+    begin = torch.as_tensor(win_out, dtype=torch.long).to(flow.device).contiguous()
+    F, two, h, w = flow.shape
+    assert two == 2 and begin.numel() == F + 1 and frame_ts.numel() == 2 * F, \
+        (flow.shape, begin.shape, frame_ts.shape)
+    lib = _lib.lib()
+    M = lib.dvsof_iwe_multi_images(F, mask, int(polarity))
+    if F > 0 and M == 0:
+        raise ValueError(f'{F} frames at {bin(mask).count("1")} reference times'
+                         f'{" and two polarities" if polarity else ""} are more than 65535 images')
+    q = torch.empty(M, h, w, dtype=torch.long, device=flow.device)
+    count = torch.empty(M, h, w, dtype=torch.int32, device=flow.device)
+    _lib.check(lib.dvsof_iwe_splat_multi(
+        x.data_ptr(), y.data_ptr(), t.data_ptr(), _lib.ptr(p), x.numel(), begin.data_ptr(),
+        frame_ts.data_ptr(), flow.data_ptr(), F, h, w, mask, int(polarity), q.data_ptr(), count.data_ptr(),
+        _lib.stream()), 'dvsof_iwe_splat_multi')
+    return q, count
 
 
 def iwe_stats(q, count):

@@ -250,11 +250,26 @@ class SharpnessHook:
     | image of warped events) into ``<directory>/step_<N>/<k>.png`` + ``.yml``
     and hands them to ``logger.add_image`` where there is one.  Only rank 0
     evaluates, and nothing in here is a collective.  The model is left as it
-    was found."""
+    was found.
+
+    references, polarity: the reference times the events are warped to (names
+    among start, middle, end, or a mask) and whether ON and OFF events get
+    images of their own (docs/IWE_SPEC.md sections 8-13): a frame then has
+    R C images.  The three scalars keep their tags: the mean FWL is taken over
+    all images that have one, the mean kept mass over the images with events,
+    and a frame is without events when every image of it is empty.  With
+    anything but the defaults the hook also logs ``Sharpness/mean FWL/<reference>``
+    for every chosen reference and, with ``polarity``, ``Sharpness/mean FWL/ON``
+    and ``/OFF``; a drawn frame is one picture of its images below one another
+    in image order, and its ``.yml`` lists the statistics per image."""
 
     def __init__(self, model, sequence, logger, shape, directory, frame_step=1, pictures=4,
-                 rank=0, batch_size=8):
+                 rank=0, batch_size=8, references=('start',), polarity=False):
+        from .eval import iwe_image_names
+        from .loss import contrast_reference_mask
         self.model, self.sequence, self.logger = model, sequence, logger
+        self.reference_mask, self.polarity = contrast_reference_mask(references), bool(polarity)
+        self.image_names = iwe_image_names(self.reference_mask, self.polarity)
         self.shape = (int(shape[0]), int(shape[1]))
         self.directory, self.rank = Path(directory), rank
         self.batch_size = int(batch_size)
@@ -273,21 +288,25 @@ class SharpnessHook:
         self.chosen = picture_indices(len(self.frames), pictures)
 
     def evaluate(self):
-        """-> (result rows of every frame, [(frames, their pictures)]) with the
+        """-> (result rows of every image, [(frames, their pictures)]) with the
         model as it stands; pictures on the device."""
         from . import eval as dev_eval, testing
         from .of import OpticalFlow
         of = OpticalFlow.from_model(self.model, self.shape)
         drawn = []
+        per = len(self.image_names)
 
         def observer(first, q, count, results):
-            mine = [i for i in self.chosen if first <= i < first + q.shape[0]]
+            mine = [i for i in self.chosen if first <= i < first + q.shape[0] // per]
             if not mine:
                 return
-            local = torch.tensor([i - first for i in mine], device=q.device)
-            drawn.append((mine, dev_eval.iwe_render(q[local], count[local], results[local])))
+            local = torch.tensor([(i - first) * per + k for i in mine for k in range(per)], device=q.device)
+            canvas = dev_eval.iwe_render(q[local], count[local], results[local])
+            # the images of a frame are contiguous: below one another, one picture
+            drawn.append((mine, canvas.view(len(mine), per * canvas.shape[1], *canvas.shape[2:])))
         rows = testing.flow_warp_loss(of, self.sequence, self.frames, self.box, self.batch_size,
-                                      observer=observer)
+                                      observer=observer, references=self.reference_mask,
+                                      polarity=self.polarity)
         return rows, drawn
 
     def __call__(self, steps, samples):
@@ -301,21 +320,38 @@ class SharpnessHook:
         fwl, kept = dev_eval.derive_fwl(rows, self.shape[0] * self.shape[1])
         valid = ~np.isnan(fwl)
         has_events = rows['count_sum'] > 0
-        self.logger.add_scalar('Sharpness/mean FWL',
-                               float(fwl[valid].mean()) if valid.any() else float('nan'), samples)
+        names, per = self.image_names, len(self.image_names)
+
+        def mean_fwl(pick):
+            return float(fwl[valid & pick].mean()) if (valid & pick).any() else float('nan')
+        self.logger.add_scalar('Sharpness/mean FWL', mean_fwl(True), samples)
         self.logger.add_scalar('Sharpness/mean kept mass',
                                float(kept[has_events].mean()) if has_events.any() else float('nan'),
                                samples)
-        self.logger.add_scalar('Sharpness/frames without events', int((~has_events).sum()), samples)
+        self.logger.add_scalar('Sharpness/frames without events',
+                               int((~has_events).reshape(-1, per).all(1).sum()), samples)
+        multi = self.reference_mask != 1 or self.polarity
+        if multi:
+            kind = np.arange(len(rows)) % per       # the image's place in its frame
+            groups = list(dict.fromkeys(r for r, _ in names)) + (['ON', 'OFF'] if self.polarity else [])
+            for group in groups:
+                pick = np.isin(kind, [k for k, (r, c) in enumerate(names) if group in (r, c)])
+                self.logger.add_scalar(f'Sharpness/mean FWL/{group}', mean_fwl(pick), samples)
+
+        def image_statistics(m):
+            return {'FWL': float(fwl[m]), 'kept_mass': float(kept[m]), 'count_max': int(rows['count_max'][m]),
+                    'iwe_max': float(rows['max_q'][m]) * 2.0 ** -32}
         out = self.directory / f'step_{steps}'
         k = 0
         for mine, images in drawn:
             for i, image in zip(mine, vis._host(images)):
-                statistics = {
-                    'frame': i, 'start': float(self.frames[i][0]), 'stop': float(self.frames[i][1]),
-                    'FWL': float(fwl[i]), 'kept_mass': float(kept[i]),
-                    'count_max': int(rows['count_max'][i]),
-                    'iwe_max': float(rows['max_q'][i]) * 2.0 ** -32}
+                statistics = {'frame': i, 'start': float(self.frames[i][0]), 'stop': float(self.frames[i][1])}
+                if multi:
+                    statistics['images'] = [
+                        {'reference': r, **({'channel': c} if c else {}), **image_statistics(i * per + j)}
+                        for j, (r, c) in enumerate(names)]
+                else:
+                    statistics.update(image_statistics(i))
                 if hasattr(self.logger, 'add_image'):
                     self.logger.add_image(f'Sharpness/{k}', image, samples, dataformats='HWC')
                 out.mkdir(parents=True, exist_ok=True)

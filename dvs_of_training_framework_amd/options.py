@@ -282,6 +282,20 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         help='images a frame of the sharpness measurement spans')
     parser.add_argument('--sharpness-pictures', dest='sharpness_pictures', default=4,
                         type=int)
+    parser.add_argument('--sharpness-references', dest='sharpness_references',
+                        default='start', type=str,
+                        help='comma-separated reference times of the sharpness measurement, '
+                             'among start, middle, end (any order, none twice): the events '
+                             'are warped to each of these times of their frame, every image '
+                             'has a flow warp loss of its own, Sharpness/mean FWL is their '
+                             'mean and Sharpness/mean FWL/<reference> the mean per reference '
+                             '(a collapsing flow is rewarded at the start and not at the '
+                             'end; docs/IWE_SPEC.md section 8).  Needs --sharpness-period')
+    parser.add_argument('--sharpness-polarity', dest='sharpness_polarity',
+                        action='store_true',
+                        help='accumulate ON and OFF events in images of their own in the '
+                             'sharpness measurement, and log Sharpness/mean FWL/ON and /OFF.  '
+                             'Needs --sharpness-period')
     parser.add_argument('--contrast-weight', dest='contrast_weight', default=0.0,
                         type=float,
                         help='add this times the contrast-maximisation term to the '
@@ -360,21 +374,21 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_contrast_args(args)
+    return validate_sharpness_args(validate_contrast_args(args))
 
 
 CONTRAST_REFERENCE_NAMES = ('start', 'middle', 'end')
 
 
-def parse_contrast_references(text):
+def parse_contrast_references(text, option='--contrast-references'):
     """'end,start' -> ('start', 'end'): the names in the order of the window."""
     names = [n.strip() for n in text.split(',')] if isinstance(text, str) else list(text)
     for n in names:
         if n not in CONTRAST_REFERENCE_NAMES:
-            raise SystemExit(f'--contrast-references: unknown reference time "{n}", '
+            raise SystemExit(f'{option}: unknown reference time "{n}", '
                              f'one of {", ".join(CONTRAST_REFERENCE_NAMES)}')
         if names.count(n) > 1:
-            raise SystemExit(f'--contrast-references: "{n}" is given twice')
+            raise SystemExit(f'{option}: "{n}" is given twice')
     return tuple(n for n in CONTRAST_REFERENCE_NAMES if n in names)
 
 
@@ -399,6 +413,20 @@ def validate_contrast_args(args):
     if weight > 0 and getattr(args, 'compact_events', False):
         raise SystemExit('--contrast-weight cannot be combined with --compact-events: the term '
                          'reads the int64 / float32 wire columns, not the 9 B/event encoded ones')
+    return args
+
+
+def validate_sharpness_args(args):
+    """The options of the sharpness measurement against a run without it.
+    ``args.sharpness_references`` becomes a tuple of names."""
+    args.sharpness_references = parse_contrast_references(getattr(args, 'sharpness_references', 'start'),
+                                                          '--sharpness-references')
+    args.sharpness_polarity = bool(getattr(args, 'sharpness_polarity', False))
+    if not getattr(args, 'sharpness_period', 0) > 0:
+        if args.sharpness_references != ('start',):
+            raise SystemExit('--sharpness-references needs a positive --sharpness-period')
+        if args.sharpness_polarity:
+            raise SystemExit('--sharpness-polarity needs a positive --sharpness-period')
     return args
 
 

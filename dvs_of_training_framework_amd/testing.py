@@ -277,7 +277,8 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
     return np.concatenate(out)
 
 
-def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None):
+def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None, references=('start',),
+                   polarity=False):
     """Label-free quality of ``of`` on a device-resident
     ``sequence.EventSequence``: per frame the statistics of the image of warped
     events and of the count image (docs/IWE_SPEC.md) as a numpy structured
@@ -289,8 +290,19 @@ def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None):
     frames: [(start, stop)]; box: None or a (y0, x0, h, w) inside the frame,
     the crop the events get (``of`` predicts at that size);
     observer(first, q, count, results): called once per batch with the index
-    of its first frame and the device tensors."""
+    of its first frame and the device tensors.
+
+    references, polarity: the reference times the events are warped to (names
+    among start, middle, end, or a mask) and whether ON and OFF events get
+    images of their own (IWE_SPEC sections 8-13).  With anything but the
+    defaults a batch makes one ``eval.iwe_splat_multi`` call in place of the
+    count image and the splat, and every frame has R C rows, in image order
+    m = (f R + r) C + c (``eval.iwe_image_names``); the observer gets the
+    tensors of the batch's images."""
+    from .loss import contrast_reference_mask
     from .sequence import EventSequence, check_box
+    mask, polarity = contrast_reference_mask(references), bool(polarity)
+    multi = mask != 1 or polarity
     if not isinstance(sequence, EventSequence):
         raise TypeError('flow_warp_loss takes a sequence.EventSequence (the events stay on '
                         f'the device), not {type(sequence).__name__}')
@@ -314,9 +326,12 @@ def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None):
         if (eh, ew) != (h, w):
             raise ValueError(f'the flow is {(h, w)}, the events cover {(eh, ew)}')
         ev = collated.events
-        count = dev_eval.count_image_batched(ev['x'], ev['y'], collated.win_out, (h, w),
-                                             (0, 0, h, w))
-        q = dev_eval.iwe_splat(ev, collated.win_out, collated.timestamps, pred)
+        if multi:
+            q, count = dev_eval.iwe_splat_multi(ev, collated.win_out, collated.timestamps, pred, mask, polarity)
+        else:
+            count = dev_eval.count_image_batched(ev['x'], ev['y'], collated.win_out, (h, w),
+                                                 (0, 0, h, w))
+            q = dev_eval.iwe_splat(ev, collated.win_out, collated.timestamps, pred)
         res = dev_eval.iwe_stats(q, count)
         out.append(dev_eval.read_iwe_results(res))      # the batch's one copy back
         if observer is not None:

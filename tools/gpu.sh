@@ -20,7 +20,9 @@
 #                                     one hook call over 200 frames against the step time of the same run
 #   iwe [iwe_bench.py args]          label-free validation (tools/iwe_bench.py): splat, statistics and render alone at
 #                                     F = 8, 256x256, 30 000 and 120 000 events per frame, the splat's atomic bytes/s;
-#                                     testing.flow_warp_loss against the same frames' inference alone
+#                                     testing.flow_warp_loss against the same frames' inference alone;
+#                                     dvsof_iwe_splat_multi at masks 1, 5, 7 without and with polarity and, at mask 1
+#                                     without, against count image + splat; --references / --polarity: the metric there
 #   contrast [contrast_bench.py args] contrast-maximisation term (tools/contrast_bench.py): dvsof_contrast_fwd and
 #                                     dvsof_contrast_bwd alone at batch 8, 256x256, 65 536 events per sample; the eager
 #                                     training step with --contrast-weight 0 against 0.25 in alternating blocks

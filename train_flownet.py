@@ -337,7 +337,8 @@ def add_evaluation(args, hooks, periodic, model, device, logger, rank):
 def add_sharpness(args, hooks, periodic, model, device, logger, rank):
     """--sharpness-period N > 0: a ``SharpnessHook`` every N optimizer steps
     (flow warp loss of the validation sequence's own events, and pictures; no
-    ground truth).  0 constructs nothing.  Rank 0 alone holds the sequence,
+    ground truth) at --sharpness-references, with --sharpness-polarity.  0
+    constructs nothing.  Rank 0 alone holds the sequence,
     and shares the one an ``EvaluationHook`` has already uploaded."""
     if getattr(args, 'sharpness_period', 0) <= 0:
         return
@@ -351,7 +352,9 @@ def add_sharpness(args, hooks, periodic, model, device, logger, rank):
             sequence = FrameSequence.from_directory(args.validation_sequence, device)
     hooks['sharpness'] = SharpnessHook(
         model, sequence, logger, args.shape, args.model / 'sharpness',
-        frame_step=args.sharpness_frame_step, pictures=args.sharpness_pictures, rank=rank)
+        frame_step=args.sharpness_frame_step, pictures=args.sharpness_pictures, rank=rank,
+        references=getattr(args, 'sharpness_references', ('start',)),
+        polarity=getattr(args, 'sharpness_polarity', False))
     periodic['sharpness'] = make_hook_periodic(hooks['sharpness'], args.sharpness_period)
 
 
