@@ -36,6 +36,8 @@ EXTENSION_PATHS = (HEADER_PATH.with_name('dvsof_contrast.h'),)
 CONTRAST_MULTI_PATH = HEADER_PATH.with_name('dvsof_contrast_multi.h')
 # And one more (IWE_MULTI_FUNCTIONS): the validation side of the same options
 IWE_MULTI_PATH = HEADER_PATH.with_name('dvsof_iwe_multi.h')
+# And the loss of a run without frames (LOSS_FRAMELESS_FUNCTIONS)
+LOSS_FRAMELESS_PATH = HEADER_PATH.with_name('dvsof_loss_frameless.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -194,3 +196,5 @@ for _path in EXTENSION_PATHS:
 CONTRAST_MULTI_FUNCTIONS = _read_extension(CONTRAST_MULTI_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS))
 IWE_MULTI_FUNCTIONS = _read_extension(IWE_MULTI_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS)
                                      | set(CONTRAST_MULTI_FUNCTIONS))
+LOSS_FRAMELESS_FUNCTIONS = _read_extension(LOSS_FRAMELESS_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS)
+                                          | set(CONTRAST_MULTI_FUNCTIONS) | set(IWE_MULTI_FUNCTIONS))

@@ -8,7 +8,9 @@ or, leaving that table as it is, in an extension header (_abi.EXTENSION_PATHS:
 include/dvsof_contrast.h, recorded in tests/golden/abi_signatures_contrast.json;
 _abi.CONTRAST_MULTI_PATH: include/dvsof_contrast_multi.h, recorded in
 tests/golden/abi_signatures_contrast_multi.json; _abi.IWE_MULTI_PATH:
-include/dvsof_iwe_multi.h, recorded in tests/golden/abi_signatures_iwe_multi.json).
+include/dvsof_iwe_multi.h, recorded in tests/golden/abi_signatures_iwe_multi.json;
+_abi.LOSS_FRAMELESS_PATH: include/dvsof_loss_frameless.h, recorded in
+tests/golden/abi_signatures_loss_frameless.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -37,6 +39,8 @@ _EXTENSION_SIGNATURES = _abi.EXTENSION_FUNCTIONS
 _CONTRAST_MULTI_SIGNATURES = _abi.CONTRAST_MULTI_FUNCTIONS
 # and of include/dvsof_iwe_multi.h, likewise
 _IWE_MULTI_SIGNATURES = _abi.IWE_MULTI_FUNCTIONS
+# and of include/dvsof_loss_frameless.h, likewise
+_LOSS_FRAMELESS_SIGNATURES = _abi.LOSS_FRAMELESS_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -72,6 +76,11 @@ def declared_iwe_multi_symbols():
     return _declared_in((_abi.IWE_MULTI_PATH,))
 
 
+def declared_loss_frameless_symbols():
+    """Names of all entry points include/dvsof_loss_frameless.h declares."""
+    return _declared_in((_abi.LOSS_FRAMELESS_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -86,7 +95,7 @@ def lib():
         global LOADED_STAT      # the file these code objects came from (_audit.py)
         LOADED_STAT = (st.st_ino, st.st_size, st.st_mtime_ns)
         for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES,
-                                  **_IWE_MULTI_SIGNATURES}.items():
+                                  **_IWE_MULTI_SIGNATURES, **_LOSS_FRAMELESS_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -103,3 +103,60 @@ def augment_batch(batch, is_flip, angle, box, device='cuda'):
                is_flip=torch.from_numpy(is_flip))
     result['augmentation_params'] = aug
     return result
+
+
+def augment_events_batch(batch, is_flip, angle, box, in_shape, device='cuda'):
+    """``augment_batch`` for a frameless batch (``'images': None``;
+    docs/FRAMELESS_SPEC.md): the events are flipped, rotated and cropped by
+    the same two kernels with the same tables (dvsof_augment_lut,
+    dvsof_augment_events), so their columns are those ``augment_batch`` gives
+    for the same parameters; the frames kernel is not launched.  in_shape:
+    (H, W) of the sensor, which ``augment_batch`` reads off the images.
+    -> new batch dict with ``'images': None`` and ``'shape': (h, w)`` of the
+    crop."""
+    dev = torch.device(device)
+    is_flip = np.asarray(is_flip, bool).reshape(-1)
+    angle = np.asarray(angle, np.float64).reshape(-1)
+    box = np.asarray(box, np.int64).reshape(-1, 4)
+    B = is_flip.size
+    assert angle.size == B and box.shape[0] == B
+    h, w = int(box[0, 2]), int(box[0, 3])
+    assert (box[:, 2] == h).all() and (box[:, 3] == w).all(), \
+        'one crop shape per batch'
+    assert batch.get('images') is None, 'a batch with frames goes through augment_batch'
+    H, W = int(in_shape[0]), int(in_shape[1])
+    assert (box[:, 0] >= 0).all() and (box[:, 1] >= 0).all() and \
+        (box[:, 0] + h <= H).all() and (box[:, 1] + w <= W).all(), \
+        'crop box outside the frame'
+    rad = angle * np.pi / 180                       # utils/data.py:181-186
+    cs = torch.from_numpy(np.stack([np.cos(rad), np.sin(rad)], 1)).to(dev)
+    flip_d = torch.from_numpy(is_flip.astype(np.uint8)).to(dev)
+    box_d = torch.from_numpy(box.astype(np.int32)).to(dev)
+    lib, st = _lib.lib(), _lib.stream()
+    ev = {k: v.to(dev) for k, v in batch['events'].items()
+          if isinstance(v, torch.Tensor)}
+    _lib.require_cuda(ev['x'])
+    n = ev['x'].numel()
+    lut = None
+    if bool((angle != 0).any()):
+        lut = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+        _lib.check(lib.dvsof_augment_lut(cs.data_ptr(), B, H, W,
+                                         lut.data_ptr(), st),
+                   'dvsof_augment_lut')
+    x = ev['x'].to(torch.long).contiguous()
+    y = ev['y'].to(torch.long).contiguous()
+    s = ev['sample_index'].to(torch.long).contiguous()
+    xo, yo = torch.empty_like(x), torch.empty_like(y)
+    _lib.check(lib.dvsof_augment_events(
+        x.data_ptr(), y.data_ptr(), s.data_ptr(), n, flip_d.data_ptr(),
+        _lib.ptr(lut), box_d.data_ptr(), B, H, W, xo.data_ptr(),
+        yo.data_ptr(), st), 'dvsof_augment_events')
+    ev['x'], ev['y'] = xo, yo
+    result = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v)
+              for k, v in batch.items() if k not in ('events', 'images', 'shape')}
+    result['events'], result['images'], result['shape'] = ev, None, (h, w)
+    aug = dict(batch.get('augmentation_params') or {})
+    aug.update(box=torch.from_numpy(box), angle=torch.from_numpy(angle),
+               is_flip=torch.from_numpy(is_flip))
+    result['augmentation_params'] = aug
+    return result

@@ -10,7 +10,10 @@ Differences that are deliberate (MI355X-first):
     and ONE backward launch (csrc/loss.hip) instead of ~15 ATen ops per scale;
   * frames are not gathered (``images[start_indices]``): kernels index the
     pyramid level through the start/stop index vectors;
-  * ``Losses.fused`` is a training fast path (forward + gradient in one sweep).
+  * ``Losses.fused`` is a training fast path (forward + gradient in one sweep);
+  * ``Losses.frameless`` is the loss of a batch without frames: smoothness and
+    out-of-border alone, no pyramid and no frame read (csrc/loss_frameless.hip,
+    docs/FRAMELESS_SPEC.md).
 """
 import ctypes
 
@@ -161,6 +164,49 @@ class _FusedLoss(torch.autograd.Function):
             return (None,) * 6 + tuple(ctx.grads)      # seed is exactly 1.0
         # one multi-tensor launch for all scales
         return (None,) * 6 + tuple(torch._foreach_mul(list(ctx.grads), g_loss))
+
+
+class _FramelessLoss(torch.autograd.Function):
+    """loss = (w_s sum_k smooth_k + w_o sum_k border_k) / K * scale with the
+    flow gradients produced in the same sweep (dvsof_loss_frameless,
+    docs/FRAMELESS_SPEC.md): no frame is read, the photometric row of the
+    terms is +0."""
+
+    @staticmethod
+    def forward(ctx, weights, scale, *flows):
+        K, N = len(flows), flows[0].shape[0]
+        dev = flows[0].device
+        flows = tuple(f.detach().contiguous().float() for f in flows)
+        grads = tuple(torch.empty_like(f) for f in flows)
+        arr = (_lib.LossScale * K)()
+        for k, (f, g) in enumerate(zip(flows, grads)):
+            arr[k].frames, arr[k].flow, arr[k].grad_flow = None, f.data_ptr(), g.data_ptr()
+            arr[k].h, arr[k].w = f.shape[-2], f.shape[-1]
+        lib = _lib.lib()
+        nbytes = lib.dvsof_loss_frameless_workspace_bytes(arr, K, N)
+        if nbytes == 0:
+            raise RuntimeError('dvsof_loss_frameless_workspace_bytes: invalid scales')
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        terms = torch.empty(3, K, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        oob = torch.empty(K * N, dtype=torch.int32, device=dev)
+        w = (ctypes.c_float * 2)(*[float(x) for x in weights])
+        _lib.check(lib.dvsof_loss_frameless(
+            arr, K, N, w, float(scale), terms.data_ptr(), loss.data_ptr(), oob.data_ptr(),
+            ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_loss_frameless')
+        ctx.grads = grads
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_terms):
+        if g_loss is None:
+            return (None,) * (2 + len(ctx.grads))
+        one = _UNIT.get(g_loss.device)
+        if one is not None and g_loss.data_ptr() == one.data_ptr():
+            return (None,) * 2 + tuple(ctx.grads)      # seed is exactly 1.0
+        return (None,) * 2 + tuple(torch._foreach_mul(list(ctx.grads), g_loss))
 
 
 # ---------------------------------------------------------------------------
@@ -671,6 +717,18 @@ class Losses:
         img, frames = self._level_buffers(images)
         return _FusedLoss.apply(frames, img, start, stop, tuple(weights),
                                 loss_scale, *flows)
+
+    def frameless(self, flows, weights=(0.5, 1), loss_scale=1.0):
+        """The loss of a batch that has no frames (docs/FRAMELESS_SPEC.md):
+        weights = (smoothness, out-of-border) -> (loss, terms[3,K]) with
+        loss = (w_s sum_k smooth_k + w_o sum_k border_k) / K * loss_scale; the
+        photometric row of the terms is 0.  Out-of-border count, terms and flow
+        gradients: 3 launches, no pyramid, no frame read."""
+        _lib.require_cuda(*flows)
+        self._check_flows(flows)
+        weights = tuple(weights)
+        assert len(weights) == 2, 'weights = (smoothness, out-of-border)'
+        return _FramelessLoss.apply(weights, loss_scale, *flows)
 
     def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None,
                  references=('start',), polarity=False):

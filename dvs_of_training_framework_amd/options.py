@@ -317,6 +317,26 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         action='store_true',
                         help='accumulate ON and OFF events in images of their own in the '
                              'contrast term.  Needs --contrast-weight')
+    parser.add_argument('--recording', dest='recording', default=None, type=Path,
+                        help='train from ONE event-only recording kept on the device: a '
+                             '.npz or .hdf5 file with the arrays x, y, t, p (sorted by t) and '
+                             'shape = (H, W); no frames are needed or read '
+                             '(docs/FRAMELESS_SPEC.md).  Windows are cut by --window-duration '
+                             'or --window-events, batches by sequence.EventWindowLoader (the '
+                             'rules of --sequence), and the loss is smoothness + out-of-border '
+                             '+ the contrast-maximisation term: needs --contrast-weight > 0')
+    parser.add_argument('--validation-recording', dest='validation_recording', default=None,
+                        type=Path,
+                        help='validate on ONE event-only recording, a file as for --recording '
+                             '(one pass, central crop, no augmentation; the windows of '
+                             '--window-duration / --window-events); --sharpness-period takes '
+                             'it in place of --validation-sequence')
+    parser.add_argument('--window-duration', dest='window_duration', default=None, type=float,
+                        help='with --recording / --validation-recording: windows of this many '
+                             'seconds from the first event on')
+    parser.add_argument('--window-events', dest='window_events', default=None, type=int,
+                        help='with --recording / --validation-recording: windows of this many '
+                             'events (exactly one of --window-duration and --window-events)')
     parser.add_argument('--sync-checkpoints', dest='sync_checkpoints',
                         action='store_true',
                         help='write checkpoints on the training thread (state_dict() + '
@@ -374,7 +394,7 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_sharpness_args(validate_contrast_args(args))
+    return validate_frameless_args(validate_sharpness_args(validate_contrast_args(args)))
 
 
 CONTRAST_REFERENCE_NAMES = ('start', 'middle', 'end')
@@ -428,6 +448,67 @@ def validate_sharpness_args(args):
         if args.sharpness_polarity:
             raise SystemExit('--sharpness-polarity needs a positive --sharpness-period')
     return args
+
+
+def validate_frameless_args(args):
+    """--recording / --validation-recording (docs/FRAMELESS_SPEC.md) against
+    what they need and what they cannot be combined with.  Without them
+    nothing is looked at but the two window flags, which need one of them."""
+    recording = getattr(args, 'recording', None)
+    validation = getattr(args, 'validation_recording', None)
+    duration = getattr(args, 'window_duration', None)
+    events = getattr(args, 'window_events', None)
+    if recording is None and validation is None:
+        for flag, value in (('--window-duration', duration), ('--window-events', events)):
+            if value is not None:
+                raise SystemExit(f'{flag} needs --recording or --validation-recording')
+        return args
+    which = '--recording' if recording is not None else '--validation-recording'
+    if (duration is None) == (events is None):
+        raise SystemExit(f'{which} needs exactly one of --window-duration and --window-events')
+    if duration is not None and not (duration > 0 and duration != float('inf')):
+        raise SystemExit(f'--window-duration must be positive and finite, got {duration}')
+    if events is not None and events < 1:
+        raise SystemExit(f'--window-events must be at least 1, got {events}')
+    weight = getattr(args, 'contrast_weight', 0.0)
+    if recording is not None:
+        if not weight > 0:
+            raise SystemExit('--recording needs --contrast-weight > 0: without frames the '
+                             'contrast-maximisation term is the only data term')
+        for flag, value in (('--sequence', getattr(args, 'sequence', None) is not None),
+                            ('--synthetic', getattr(args, 'synthetic', False)),
+                            ('--preprocessed-dataset-path',
+                             getattr(args, 'preprocessed_dataset_path', None) is not None),
+                            ('--ev_images', getattr(args, 'ev_images', False)),
+                            ('--compact-events', getattr(args, 'compact_events', False)),
+                            ('--device-feeder', getattr(args, 'device_feeder', False))):
+            if value:
+                raise SystemExit(f'--recording cannot be combined with {flag}: the batches are '
+                                 'cut from the event-only recording on the device')
+    if validation is not None:
+        if getattr(args, 'validation_sequence', None) is not None:
+            raise SystemExit('--validation-recording cannot be combined with '
+                             '--validation-sequence: one validation source')
+        if not weight > 0 and not getattr(args, 'skip_validation', False):
+            raise SystemExit('--validation-recording needs --contrast-weight > 0 (or '
+                             '--skip-validation): a frameless validation loss has no other '
+                             'data term')
+        if getattr(args, 'visualization_period', 0) > 0:
+            raise SystemExit('--visualization-period cannot be combined with '
+                             '--validation-recording: its pictures show grey images, and a '
+                             'frameless recording has none')
+        if getattr(args, 'evaluation_period', 0) > 0:
+            raise SystemExit('--evaluation-period cannot be combined with '
+                             '--validation-recording: the evaluation hook needs '
+                             '--validation-sequence (grey images under its pictures)')
+    return args
+
+
+def window_kwargs(args):
+    """The window arguments of ``sequence.WindowedEvents.from_file``."""
+    if getattr(args, 'window_duration', None) is not None:
+        return {'duration': args.window_duration}
+    return {'events_per_window': args.window_events}
 
 
 def options2dataset_kwargs(parameters):    # utils/options.py:332-338

@@ -469,3 +469,176 @@ class SequenceLoader:
             resume = None
             if self.steps is None:
                 return
+
+
+# ---------------------------------------------------------------------------
+# Recordings without frames (docs/FRAMELESS_SPEC.md)
+# ---------------------------------------------------------------------------
+RECORDING_KEYS = ('x', 'y', 't', 'p', 'shape')
+
+
+class WindowedEvents(EventSequence):
+    """An ``EventSequence`` plus n + 1 ascending window boundaries (float64):
+    a recording that has no frames, cut into n samples.  Sample i is the
+    interval image_ts[i] .. image_ts[i+1] with the events
+    [frame_event_begin[i], frame_event_begin[i+1]) -- the names and the
+    meaning ``FrameSequence`` gives them, so that what needs only those
+    (``hooks.sharpness_frames``, ``testing.flow_warp_loss``) takes either.
+    There are no ``images``.
+
+    frame_event_begin None: ``np.searchsorted(t, boundaries, side='right')``,
+    ``FrameSequence``'s rule: a window holds the events with
+    start < t <= stop."""
+
+    def __init__(self, events, shape, boundaries, frame_event_begin=None,
+                 device='cuda'):
+        super().__init__(events, shape, device)
+        ts = np.ascontiguousarray(boundaries, dtype=np.float64).reshape(-1)
+        if ts.size < 2:
+            raise ValueError('a windowed recording needs at least two window '
+                             f'boundaries (one window), got {ts.size}')
+        if not np.isfinite(ts).all() or (np.diff(ts) < 0).any():
+            raise ValueError('window boundaries are not sorted (or not finite)')
+        if frame_event_begin is None:
+            feb = np.searchsorted(self.t, ts, side='right')
+        else:
+            feb = np.asarray(frame_event_begin)
+        feb = np.ascontiguousarray(feb, dtype=np.int64).reshape(-1)
+        if feb.size != ts.size or (np.diff(feb) < 0).any() or \
+                feb[0] < 0 or feb[-1] > self.n_events:
+            raise ValueError('frame_event_begin: n+1 ascending event indices '
+                             f'within 0..{self.n_events}')
+        self.image_ts = ts
+        self.frame_event_begin = feb
+
+    @property
+    def n_samples(self):
+        return self.image_ts.size - 1
+
+    @classmethod
+    def cut(cls, events, shape, boundaries=None, duration=None,
+            events_per_window=None, device='cuda'):
+        """Exactly one of
+          boundaries         the n + 1 window boundaries themselves;
+          duration           seconds: boundaries t[0] + i * duration (float64),
+                             the last one the last that is not beyond the last
+                             event;
+          events_per_window  N: boundary i is the time of event i * N and
+                             frame_event_begin[i] = i * N, given explicitly
+                             (ties in t cannot move an event to its neighbour);
+                             the events from the last boundary on belong to no
+                             window.
+        In the two time modes frame_event_begin is searchsorted(side='right')."""
+        given = [v is not None for v in (boundaries, duration, events_per_window)]
+        if sum(given) != 1:
+            raise ValueError('exactly one of boundaries, duration and '
+                             'events_per_window cuts a recording')
+        if boundaries is not None:
+            return cls(events, shape, boundaries, None, device)
+        t = np.ascontiguousarray(np.asarray(events[2]).reshape(-1), dtype=np.float64)
+        if duration is not None:
+            duration = float(duration)
+            if not (duration > 0 and np.isfinite(duration)):
+                raise ValueError(f'the window duration is positive and finite, not {duration}')
+            ts = np.zeros(0)
+            if t.size and np.isfinite(t[0]) and np.isfinite(t[-1]) and t[-1] >= t[0]:
+                m = int(np.floor((t[-1] - t[0]) / duration))
+                ts = t[0] + np.arange(m + 2, dtype=np.float64) * duration
+                ts = ts[ts <= t[-1]]
+            return cls(events, shape, ts, None, device)
+        N = int(events_per_window)
+        if N < 1:
+            raise ValueError(f'a window holds at least one event, not {events_per_window}')
+        begin = np.arange(0, t.size, N, dtype=np.int64)
+        return cls(events, shape, t[begin], begin, device)
+
+    @classmethod
+    def from_file(cls, path, duration=None, events_per_window=None,
+                  boundaries=None, device='cuda'):
+        """A recording in ONE file: ``.npz`` with the arrays x, y, t, p
+        (one entry per event, sorted by t) and shape = (H, W) of the sensor,
+        or ``.hdf5`` / ``.h5`` with datasets of the same names (read through
+        ``hdf5io``).  A file that lacks one of them is refused, with the name
+        in the message.  The window arguments are ``cut``'s."""
+        from pathlib import Path
+        path = Path(path)
+        suffix = path.suffix.lower()
+
+        def missing(have):
+            lacks = [k for k in RECORDING_KEYS if k not in have]
+            if lacks:
+                raise ValueError(f'{path}: a recording holds the arrays '
+                                 f'{", ".join(RECORDING_KEYS)}; missing: {", ".join(lacks)}')
+        if suffix == '.npz':
+            with np.load(str(path)) as data:
+                missing(data.files)
+                arrays = {k: np.asarray(data[k]) for k in RECORDING_KEYS}
+        elif suffix in ('.hdf5', '.h5'):
+            from . import hdf5io
+            with hdf5io.File(path, 'r') as f:
+                missing(list(f.keys()))
+                arrays = {k: np.array(f[k][...]) for k in RECORDING_KEYS}
+        else:
+            raise ValueError(f'{path}: a recording is a .npz or a .hdf5 file')
+        shape = np.asarray(arrays['shape']).reshape(-1)
+        if shape.size != 2:
+            raise ValueError(f'{path}: shape holds (H, W), not {shape.tolist()}')
+        return cls.cut([arrays[k] for k in ('x', 'y', 't', 'p')],
+                       (int(shape[0]), int(shape[1])), boundaries=boundaries,
+                       duration=duration, events_per_window=events_per_window,
+                       device=device)
+
+
+class EventWindowLoader(SequenceLoader):
+    """Frameless training batches in the wire format from a
+    ``WindowedEvents``: ``SequenceLoader`` without its images.  The rules are
+    that class's own code -- ``draw_k``, the window table of ``plan``, the order
+    in which ``draw_params`` consumes the generator, ``state`` / ``restore``,
+    the permutation and the dropped incomplete batch of ``__iter__`` -- so a
+    recording cut at a ``FrameSequence``'s image timestamps gives that
+    loader's events, timestamps and sample_idx.  What is not here: no
+    ``image_index`` in the plan, no ``index_select`` of resident images, no
+    frames kernel.  A batch carries ``'images': None`` and ``'shape': (h, w)``
+    of the crop (docs/FRAMELESS_SPEC.md)."""
+
+    def __init__(self, seq, shape, batch_size, augmentation=False,
+                 collapse_length=6, seq_length=1, angle=30, rng=None,
+                 steps=None):
+        assert isinstance(seq, WindowedEvents)
+        assert seq_length >= 1 and collapse_length >= 1 and batch_size >= 1
+        self.seq, self.shape = seq, (int(shape[0]), int(shape[1]))
+        self.batch_size, self.augmentation = int(batch_size), bool(augmentation)
+        self.collapse_length, self.seq_length = int(collapse_length), int(seq_length)
+        self.angle, self.steps = angle, steps
+        self.rng = np.random.default_rng() if rng is None else rng
+        check_box(central_box(seq.shape, self.shape), seq.shape)
+        if self.num_samples < self.batch_size:
+            raise ValueError(f'{self.num_samples} windows do not fill a batch '
+                             f'of {self.batch_size}')
+
+    def plan(self, idx, k):
+        """``SequenceLoader.plan`` without ``image_index``: the window table,
+        and timestamps float32 and sample_idx int64 of the B * (seq_length + 1)
+        boundaries."""
+        pl = super().plan(idx, k)
+        del pl['image_index']
+        return pl
+
+    def batch(self, idx, k, is_flip, angle, box):
+        """One frameless batch from explicit per-sample parameters (those of
+        ``SequenceLoader.batch``)."""
+        from .augment import augment_events_batch
+        s = self.seq
+        pl = self.plan(idx, k)
+        B = np.asarray(idx).size
+        cols, _, (ts, sidx), _ = s.windows(
+            pl['win_begin'], pl['win_end'], pl['win_origin'], pl['win_sample'],
+            pl['win_element'], extra=(pl['timestamps'], pl['sample_idx']))
+        raw = {'events': cols, 'timestamps': ts, 'sample_idx': sidx,
+               'images': None, 'shape': s.shape,
+               'augmentation_params': {
+                   'idx': torch.from_numpy(np.asarray(idx, np.int64).reshape(-1).copy()),
+                   'sequence_length': torch.full((B,), self.seq_length, dtype=torch.long),
+                   'collapse_length': torch.from_numpy(np.asarray(k, np.int64).reshape(-1).copy())},
+               'size': B}
+        return augment_events_batch(raw, is_flip, angle, box, s.shape, device=s.device)

@@ -90,12 +90,31 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     returned terms as ``.contrast``.  At 0 nothing of that is constructed and
     ``events`` is not looked at.  contrast_references, contrast_polarity: the
     reference times of the term and whether ON and OFF events are kept apart
-    (``Losses.contrast``); the defaults are the term of one image per frame."""
+    (``Losses.contrast``); the defaults are the term of one image per frame.
+
+    images=None with an evaluator that has ``frameless`` (loss.Losses): a
+    frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
+    and out-of-border with the weights (weights[0], weights[2]) and a
+    photometric row of zeros; ``timestamps``
+    and ``sample_idx`` are not looked at; the contrast term is added as above
+    and has to be there (ValueError at contrast_weight 0: smoothness alone has
+    no data term)."""
     extra = {} if frame_indices is None else {'frame_indices': frame_indices}
     call = (flows, flow_ts, flow_sample_idx, images, timestamps, sample_idx)
     trainable = torch.is_grad_enabled() and \
         any(f.requires_grad for f in flows)
-    if trainable and hasattr(evaluator, 'fused'):
+    if images is None and hasattr(evaluator, 'frameless'):
+        # a frameless batch (docs/FRAMELESS_SPEC.md): smoothness and
+        # out-of-border alone, no frame is read; the contrast term below is
+        # the data term.  (An evaluator without ``frameless`` is handed the
+        # None as before: what it makes of it is its own business.)
+        if not contrast_weight:
+            raise ValueError('images=None needs contrast_weight > 0: without frames the '
+                             'contrast-maximisation term is the only data term, smoothness '
+                             'alone has none')
+        loss, packed = evaluator.frameless(flows, weights=(weights[0], weights[2]))
+        terms = _Terms(packed)
+    elif trainable and hasattr(evaluator, 'fused'):
         loss, packed = evaluator.fused(*call, weights=weights, **extra)
         terms = _Terms(packed)
     else:
@@ -181,8 +200,9 @@ def predictions2tag(predictions):
 def _to_device(batch, device, is_raw):
     def put(t):
         return t.to(device, non_blocking=True)
-    frames = tuple(put(batch[k]) for k in ('timestamps', 'sample_idx',
-                                           'images'))
+    frames = tuple(put(batch[k]) for k in ('timestamps', 'sample_idx'))
+    # (a frameless batch carries 'images': None and its size as 'shape')
+    frames += (None if batch['images'] is None else put(batch['images']),)
     if not is_raw:
         return frames + (put(batch['data']),)
     events = batch['events']
@@ -196,7 +216,9 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       contrast_references=('start',), contrast_polarity=False):
     """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs]).
     contrast_weight > 0 (raw events only), contrast_references,
-    contrast_polarity: see ``combined_loss``."""
+    contrast_polarity: see ``combined_loss``.  A frameless batch
+    (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
+    the frame size from ``'shape'`` and the loss that reads no frame."""
     contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity)
     if contrast and not is_raw:
         raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
@@ -207,8 +229,9 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
         hints = {}
         if hasattr(model, 'last_frame_indices') and 'size' in batch:
             hints['batch_size'] = int(batch['size'])    # B without a device sync
+        shape = tuple(batch['shape']) if images is None else images.size()[-2:]
         flows, flow_ts, flow_sample_idx, features = model(
-            payload, timestamps, sample_idx, images.size()[-2:], raw=is_raw,
+            payload, timestamps, sample_idx, shape, raw=is_raw,
             intermediate=True, **hints)
         tags = predictions2tag(flows)
     with _timed(timers, 'loss'):
@@ -431,6 +454,10 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     contrast_references, contrast_polarity:  the reference times of that term
                ('start', 'middle', 'end') and whether ON and OFF events are
                accumulated apart (``loss.Losses.contrast``)
+
+    A loader of frameless batches (sequence.EventWindowLoader: is_raw=True,
+    ``'images': None``) needs contrast_weight > 0; the photometric rows are
+    then logged as 0 (docs/FRAMELESS_SPEC.md).
     """
     if timers is None:
         on_gpu = torch.device(device).type == 'cuda'

@@ -29,6 +29,11 @@
 #   contrast-multi [contrast_bench.py args]  its --multi leg: dvsof_contrast_fwd / _bwd, dvsof_contrast_multi_fwd /
 #                                     _bwd at mask = start without polarity and at all three references with
 #                                     polarity, in alternating blocks of one run (profiles/contrast_multi/README.md)
+#   frameless [frameless_bench.py args]  the loss that reads no frame (tools/frameless_bench.py): dvsof_loss_frameless
+#                                     against dvsof_loss_fused_pyramid on zero frames with photometric weight 0 at
+#                                     batch 8, 256x256, four scales, and one eager Ranger step of a frameless batch
+#                                     against the framed one with zero images, in alternating blocks of one run
+#                                     (profiles/frameless/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -97,6 +102,9 @@ contrast)
 contrast-multi)
   timeout -k 10 420 env "${envs[@]}" python tools/contrast_bench.py --multi "$@" > $O/contrast_multi.json 2> $O/contrast_multi.err
   echo "contrast-multi rc=$?"; cut -c1-2600 $O/contrast_multi.json; tail -3 $O/contrast_multi.err ;;
+frameless)
+  timeout -k 10 420 env "${envs[@]}" python tools/frameless_bench.py "$@" > $O/frameless.json 2> $O/frameless.err
+  echo "frameless rc=$?"; cut -c1-2600 $O/frameless.json; tail -3 $O/frameless.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

@@ -4,6 +4,8 @@
 ``init_losses`` -> ``train``.  Additions: one process per GPU under torchrun
 (RCCL gradient all-reduce overlapped with backward), ``--synthetic`` and
 ``--sequence DIR`` (one recorded sequence kept on the device),
+``--recording FILE`` (one event-only recording, no frames at all;
+docs/FRAMELESS_SPEC.md),
 ``--visualization-period N`` (pictures of the predicted flow on the
 validation data every N steps; docs/RENDER_SPEC.md).
 
@@ -16,8 +18,8 @@ optimizer, schedulers and its position in the data stream
 The reference's HDF5 data pipeline and TensorBoard writer are outside this
 build's scope: the pipeline is imported from the
 reference tree (``utils.dataloader``) when this file is dropped into it;
-otherwise ``--synthetic``, ``--sequence`` or ``--preprocessed-dataset-path``
-supply batches in the same wire format.
+otherwise ``--synthetic``, ``--sequence``, ``--recording`` or
+``--preprocessed-dataset-path`` supply batches in the same wire format.
 """
 import sys
 from argparse import ArgumentParser
@@ -33,7 +35,7 @@ from dvs_of_training_framework_amd.optim import FusedAdamW, FusedRAdam, \
     FusedRanger
 from dvs_of_training_framework_amd.options import (
     add_train_arguments, add_preprocessed_dataset_arguments, guard_requested,
-    resolve_step_guard, validate_train_args)
+    resolve_step_guard, validate_train_args, window_kwargs)
 from dvs_of_training_framework_amd.hooks import EvaluationHook, \
     SerializationHook, SharpnessHook, ValidationHook, VisualizationHook
 from dvs_of_training_framework_amd.serializer import Serializer
@@ -250,6 +252,17 @@ def make_train_loader(args, device, rank, world, steps, samples_passed):
             args.mbs, augmentation=True, collapse_length=args.cl,
             seq_length=args.prefix_length + args.suffix_length + 1,
             rng=np.random.default_rng(1234 + rank), steps=steps)
+    if getattr(args, 'recording', None) is not None:
+        # one event-only recording, resident on the device: windows cut from
+        # the event stream, frameless batches (sequence.EventWindowLoader)
+        import numpy as np
+        from dvs_of_training_framework_amd.sequence import EventWindowLoader, \
+            WindowedEvents
+        return EventWindowLoader(
+            WindowedEvents.from_file(args.recording, device=device, **window_kwargs(args)),
+            args.shape, args.mbs, augmentation=True, collapse_length=args.cl,
+            seq_length=args.prefix_length + args.suffix_length + 1,
+            rng=np.random.default_rng(1234 + rank), steps=steps)
     if getattr(args, 'preprocessed_dataset_path', None) is not None:
         # utils/dataloader.py:89-100: the preprocessed (encoded / quantized)
         # dataset; --compact-events keeps raw events in their 9 B/event columns
@@ -283,6 +296,14 @@ def make_validation_loader(args, device):
             SequenceLoader
         return SequenceLoader(
             FrameSequence.from_directory(args.validation_sequence, device),
+            args.shape, args.mbs, augmentation=False,
+            seq_length=args.prefix_length + args.suffix_length + 1, steps=None)
+    if getattr(args, 'validation_recording', None) is not None:
+        from dvs_of_training_framework_amd.sequence import EventWindowLoader, \
+            WindowedEvents
+        return EventWindowLoader(
+            WindowedEvents.from_file(args.validation_recording, device=device,
+                                     **window_kwargs(args)),
             args.shape, args.mbs, augmentation=False,
             seq_length=args.prefix_length + args.suffix_length + 1, steps=None)
     if args.synthetic and getattr(args, 'synthetic_validation_batches', 0) > 0:
@@ -339,14 +360,21 @@ def add_sharpness(args, hooks, periodic, model, device, logger, rank):
     (flow warp loss of the validation sequence's own events, and pictures; no
     ground truth) at --sharpness-references, with --sharpness-polarity.  0
     constructs nothing.  Rank 0 alone holds the sequence,
-    and shares the one an ``EvaluationHook`` has already uploaded."""
+    and shares the one an ``EvaluationHook`` has already uploaded.  With
+    --validation-recording the sequence is a ``WindowedEvents``: the hook needs
+    the window boundaries and the events only."""
     if getattr(args, 'sharpness_period', 0) <= 0:
         return
-    if getattr(args, 'validation_sequence', None) is None:
-        raise SystemExit('--sharpness-period needs --validation-sequence')
+    recording = getattr(args, 'validation_recording', None)
+    if getattr(args, 'validation_sequence', None) is None and recording is None:
+        raise SystemExit('--sharpness-period needs --validation-sequence or '
+                         '--validation-recording')
     sequence = None
     if rank == 0:
         sequence = getattr(hooks.get('evaluation'), 'sequence', None)
+        if sequence is None and recording is not None:
+            from dvs_of_training_framework_amd.sequence import WindowedEvents
+            sequence = WindowedEvents.from_file(recording, device=device, **window_kwargs(args))
         if sequence is None:
             from dvs_of_training_framework_amd.sequence import FrameSequence
             sequence = FrameSequence.from_directory(args.validation_sequence, device)
@@ -471,7 +499,7 @@ def main(argv=None):
                if getattr(args, 'contrast_weight', 0.0) else {}))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
     elif not args.skip_validation:
-        note('no validation data (--validation-sequence, or '
+        note('no validation data (--validation-sequence, --validation-recording, or '
              '--synthetic-validation-batches with --synthetic): validation is skipped')
     add_visualization(args, hooks, periodic, model, device, logger, losses, rank)
     add_evaluation(args, hooks, periodic, model, device, logger, rank)
