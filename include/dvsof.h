@@ -802,8 +802,10 @@ typedef struct {
                  loop.  Producers write the twin of their output next to the
                  f32 tensor (y16, dst[i].p16, dvsof_flow_head_bwd's gx16); the
                  weight gradient, the heads and the loss keep reading f32.
-                 Needs every NHWC source channel count % 32 == 0, else the
-                 call runs as mode 1.
+                 Needs every NHWC operand of the call in whole 64-byte runs of
+                 bf16 -- forward: every NHWC source channel count % 32 == 0;
+                 data gradient: Cout % 32 == 0 -- else the call runs as
+                 mode 1.
                  Rounding contract (tests/test_gpu_conv_exact.py emulates it
                  in float64): every product a*b of a pass is
                    modes 1, 3: RNE_bf16(a) * RNE_bf16(b)
@@ -811,12 +813,19 @@ typedef struct {
                                hi = RNE_bf16(a), lo = RNE_bf16(a - hi)
                  of the f32 operands, accumulated in f32:
                    forward:  input (every member, planar ones included)
-                             x the forward weight form -- of an up-sampling
-                             layer the sub-pixel phase sums of taps, made in
-                             f32 and then rounded;
+                             x the forward weight form -- of a sub-pixel
+                             layer (up-sampling, 3x3 / pad 1) the phase sums
+                             of taps, made in f32 and then rounded; any other
+                             up-sampling layer rounds the raw taps;
                    data gradient: gout x the data-gradient form (the same
-                             values); the gradient of a planar (NCHW) member
-                             is exact f32 in every mode;
+                             values); the gradient of a narrow planar (NCHW)
+                             member (trailing, <= 4 channels in all, beside
+                             >= 32 other channels) of a stride-1 layer that
+                             is plain or sub-pixel is exact f32 in every mode:
+                             it runs beside the matrix-core launch.  In the
+                             quad-summed form (other up-sampling layers) and
+                             in a stride-2 layer it stays in the matrix-core
+                             problem and rounds like the rest;
                    weight gradient: gout x input on the (up-sampled) frame,
                              the raw taps' sums; the columns of a planar
                              member are exact f32; the bias gradient sums the

@@ -1,5 +1,5 @@
 """Tables and helpers shared by the conv tests (test_gpu_conv.py, test_gpu_conv_exact.py,
-test_conv_emulation.py): the layer cases with the kernel family each operand mode runs, the
+test_gpu_conv_geometry.py, test_conv_emulation.py): the layer cases with the kernel family each operand mode runs, the
 descriptor builder, and the float64 references."""
 import torch
 import torch.nn.functional as F
@@ -241,6 +241,116 @@ WGRAD_TWIN_CASES = [
 
 
 # ---------------------------------------------------------------------------
+# Every accepted geometry off the 3x3 / pad-1 forms (tests/test_gpu_conv_geometry.py): ksize
+# 1 | 3 | 5, stride 1 | 2, pad 0 .. ksize-1, 2x nearest up-sampling in front of any of them.
+# All of these run the general family; `path` is derived from the dispatch:
+#   forward (gconv_launch):  v2 when every vector member (NHWC, 4 | C, C >= 16) has 16 | C,
+#                            else v1; no vector member: v1
+#   data gradient:           the same test on gout, i.e. on Cout; its form by conv_classify:
+#                            DG_PLAIN, DG_ZERO2 (stride 2), DG_QUAD (up-sampling)
+#   weight gradient (wgrad_plan): v2 when 16 | Wo and the layer does not up-sample, else
+#                            the v1 tiles; a flat-only layer takes flat_valu when its
+#                            ksize^2 C columns are 18, 27, 45, 81 or 108, else the v1 tiles
+# A family written 'general_v2:1' reports operand mode 1 in that call: mode 3 falls back to
+# mode 1 on v2 when a vector operand is no multiple of 32 channels (gconv2_launch).
+# Each case is the smallest frame at which its path can still go wrong.
+# ---------------------------------------------------------------------------
+_V221 = ('general_v2 general_v2 general_v1',) * 4
+_V222 = ('general_v2 general_v2 general_v2',) * 4
+_ONE = [(32, 'nhwc')]
+GEOMETRY = [
+    # ---- plain layers: FWD_GENERAL, DG_PLAIN (pad' = ksize - 1 - pad), WG_GENERAL
+    # 1x1 / pad 0; Cout = 48: the mode-3 data gradient reads 48 channels of gout, no whole
+    # 64-byte slices of bf16
+    dict(B=2, H=5, W=7, src=_ONE, Cout=48, k=1, pad=0,
+         path=_V221[:3] + ('general_v2 general_v2:1 general_v1',)),
+    # ... on the v1 tiles with a flat member of 3 columns and Cout % 4 != 0 (gout is a flat
+    # operand of the data gradient)
+    dict(B=2, H=5, W=7, src=[(20, 'nhwc'), (3, 'nchw')], Cout=10, k=1, pad=0,
+         path=('general_v1 general_v1 general_v1',) * 3),
+    dict(B=2, H=6, W=9, src=_ONE, Cout=32, pad=0, path=_V221),
+    # the output (6 x 7) is larger than the input: corner outputs see one input pixel
+    dict(B=2, H=4, W=5, src=_ONE, Cout=32, pad=2, path=_V221),
+    # 5x5 at every pad but 2 (CASES holds that one); 24 channels of gout: v1 data gradient
+    dict(B=1, H=7, W=9, src=[(16, 'nhwc'), (2, 'nchw')], Cout=24, k=5, pad=0,
+         path=('general_v2 general_v1 general_v1',) * 3),
+    dict(B=1, H=7, W=9, src=[(16, 'nhwc'), (2, 'nchw')], Cout=24, k=5, pad=1,
+         path=('general_v2 general_v1 general_v1',) * 3),
+    dict(B=1, H=7, W=9, src=[(16, 'nhwc'), (2, 'nchw')], Cout=24, k=5, pad=3,
+         path=('general_v2 general_v1 general_v1',) * 3),
+    dict(B=1, H=7, W=9, src=[(16, 'nhwc'), (2, 'nchw')], Cout=24, k=5, pad=4,
+         path=('general_v2 general_v1 general_v1',) * 3),
+    # one-pixel frames
+    dict(B=3, H=1, W=1, src=_ONE, Cout=32, k=1, pad=0, path=_V221),
+    dict(B=3, H=1, W=1, src=_ONE, Cout=32, path=_V221),
+    dict(B=3, H=1, W=1, src=_ONE, Cout=32, k=5, pad=4, path=_V221),     # 5 x 5 output
+    # ---- stride 2 off the phased form: DG_ZERO2 (zero-inserted gout)
+    dict(B=2, H=9, W=11, src=_ONE, Cout=32, stride=2, path=_V221),      # odd frame
+    dict(B=2, H=9, W=11, src=[(24, 'nhwc'), (2, 'nchw')], Cout=32, stride=2,   # v1 forward, planar destination
+         path=('general_v1 general_v2 general_v1',) * 3),
+    dict(B=2, H=8, W=10, src=_ONE, Cout=32, stride=2, pad=0, path=_V221),      # row 7, column 9 unread
+    dict(B=2, H=8, W=8, src=_ONE, Cout=32, stride=2, pad=2, path=_V221),
+    dict(B=2, H=6, W=7, src=_ONE, Cout=32, k=1, stride=2, pad=0, path=_V221),  # odd positions unread
+    dict(B=1, H=9, W=12, src=_ONE, Cout=32, k=5, stride=2, pad=2, path=_V221),
+    dict(B=1, H=8, W=12, src=_ONE, Cout=32, k=5, stride=2, pad=0, path=_V221),  # row 7, column 11 unread
+    # ---- up-sampling off the sub-pixel form: general forward, DG_QUAD, general weight gradient
+    dict(B=1, H=4, W=8, src=[(32, 'nhwc'), (32, 'nhwc')], Cout=32, up=True, pad=0, path=_V221),
+    dict(B=1, H=4, W=8, src=[(32, 'nhwc'), (32, 'nhwc')], Cout=32, up=True, pad=2, path=_V221),
+    # a planar destination in the quad epilogue (mode 3 falls back to mode 1 on the
+    # 16-channel member: test_mode3_falls_back_on_a_narrow_member)
+    dict(B=2, H=5, W=6, src=[(32, 'nhwc'), (16, 'nhwc'), (2, 'nchw')], Cout=32, up=True, k=5, pad=2,
+         path=_V221[:3]),
+    dict(B=1, H=5, W=6, src=[(20, 'nhwc')], Cout=24, up=True, k=5, pad=2,      # the quad rows on v1
+         path=('general_v1 general_v1 general_v1',) * 3),
+    dict(B=2, H=3, W=5, src=_ONE, Cout=32, up=True, k=1, pad=0, path=_V221),
+    # the nine-product gate's shape with only `pad` changed
+    dict(B=1, H=8, W=16, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, pad=0, path=_V221),
+    # ---- one field away from a special kernel
+    # not `first` (planar 5 -> 64, stride 2): pad 0, 5x5 / pad 2 (125 flat columns: on the v1
+    # tiles), 3x3 / pad 1 on an odd frame
+    dict(B=1, H=8, W=8, src=[(5, 'nchw')], Cout=64, stride=2, pad=0,
+         path=('general_v1 general_v2 flat_valu',) * 4),
+    dict(B=1, H=8, W=8, src=[(5, 'nchw')], Cout=64, stride=2, k=5, pad=2,
+         path=('general_v1 general_v2 general_v1',) * 4),
+    dict(B=1, H=9, W=8, src=[(5, 'nchw')], Cout=64, stride=2,
+         path=('general_v1 general_v2 flat_valu',) * 4),
+    # not Winograd (B2 16x16 256 -> 256 is at its gate with pad 1)
+    dict(B=2, H=16, W=16, src=[(256, 'nhwc')], Cout=256, pad=0, path=_V221, no_wino=True),
+    dict(B=2, H=16, W=16, src=[(256, 'nhwc')], Cout=256, pad=2, path=_V221, no_wino=True),
+    # not fwd_patch
+    dict(B=1, H=2, W=16, src=[(64, 'nhwc'), (64, 'nhwc')], Cout=32, up=True, pad=2, path=_V221),
+    # ---- added to the issue's list because the dispatch needs them
+    # DG_ZERO2 through the v1 VECTOR loader: v1 reads gout as a vector operand only when
+    # 4 | Cout, Cout >= 16 and 16 does not divide Cout (32 channels of gout go to v2)
+    dict(B=2, H=9, W=11, src=_ONE, Cout=24, stride=2,
+         path=('general_v2 general_v1 general_v1',) * 4),
+    # the v2 weight gradient needs rows of whole 16-pixel groups (16 | Wo), which no frame
+    # above has: 3x3 / pad 0 on 5 x 18 and 5x5 / pad 3 on 4 x 14 (Wo = 16; the latter is also
+    # the 5x5 DG_PLAIN data gradient on v2 with pad' = 1)
+    dict(B=1, H=5, W=18, src=_ONE, Cout=32, pad=0, path=_V222),
+    dict(B=1, H=4, W=14, src=_ONE, Cout=32, k=5, pad=3, path=_V222),
+]
+for _c in GEOMETRY:     # every case carries its geometry in full
+    _c.update(k=_c.get('k', 3), stride=_c.get('stride', 1), pad=_c.get('pad', 1), up=_c.get('up', False))
+
+
+def geometry_id(case):
+    o = layer_geometry(case)
+    return 'B%dH%dW%d_%s_%d_k%ds%dp%d%s' % (
+        case['B'], case['H'], case['W'], '+'.join('%d%s' % (c, 'p' if lay == 'nchw' else '') for c, lay in case['src']),
+        case['Cout'], o['k'], o['stride'], o['pad'], 'up' if o['up'] else '')
+
+
+def split_path(case, mode):
+    """-> [(family, reported operand mode)] x 3 of `case` in a call of operand mode `mode`."""
+    out = []
+    for kind, tok in enumerate(case['path'][mode].split()):
+        fam, _, m = tok.partition(':')
+        out.append((fam, int(m) if m else effective_mode(kind, fam, mode)))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # Integer-grid data: every product and every partial sum is an integer (or a
 # dyadic fraction) far below 2^24, so f32 arithmetic in any order, the bf16
 # operand modes (integers of at most 8 bits are exact bf16, lo = 0 in the
@@ -280,8 +390,9 @@ def assert_exact_premise(K, amax, bmax, family, up=False, extra=0.0):
 # float64.  An operand is rounded from its f32 value:
 #   modes 1, 3: a * b -> RNE(a) * RNE(b)
 #   mode 2:     a * b -> hi(a) hi(b) + hi(a) lo(b) + lo(a) hi(b),  hi = RNE(a), lo = RNE(a - hi)
-# where the weight operand of an up-sampling layer is its sub-pixel phase form (sums of
-# taps made in f32, then rounded).  Bias, residual, addends and the epilogue stay f32.
+# where the weight operand of a sub-pixel layer (up-sampling, 3x3 / pad 1) is its phase
+# form (sums of taps made in f32, then rounded); any other up-sampling layer rounds the raw
+# taps.  Bias, residual, addends and the epilogue stay f32.
 # ---------------------------------------------------------------------------
 # relative L2 error a bf16 pass may have against its emulation, per mode: f32 summation
 # order only (4x the worst of the first run on an MI355X, test_gpu_conv_exact.py)
@@ -329,11 +440,19 @@ def phase_forms(w):
     return torch.stack([torch.stack([fold(fold(w, 2, a), 3, b) for b in (0, 1)]) for a in (0, 1)])
 
 
+def is_subpixel(o):
+    """The layer runs as sub-pixel phases: 2x nearest up-sampling in front of 3x3 / pad 1
+    (csrc/conv_api.hip, conv_classify).  Every other up-sampling layer gathers the raw taps
+    from the up-sampled frame."""
+    return bool(o['up']) and o.get('k', 3) == 3 and o.get('pad', 1) == 1 and o.get('stride', 1) == 1
+
+
 def lin_fwd(x, wf, o):
     """The layer's bilinear part on NCHW x with the forward weight form wf (raw OIHW, or
-    phase_forms for an up-sampling layer)."""
-    if not o['up']:
-        return F.conv2d(x, wf, stride=o['stride'], padding=o['pad'])
+    phase_forms for a sub-pixel layer)."""
+    if not is_subpixel(o):
+        xv = F.interpolate(x, scale_factor=2, mode='nearest') if o['up'] else x
+        return F.conv2d(xv, wf, stride=o['stride'], padding=o['pad'])
     B, _, H, W = x.shape
     xp = F.pad(x, (1, 1, 1, 1))
     out = x.new_zeros(B, wf.shape[2], 2 * H, 2 * W)
@@ -344,7 +463,7 @@ def lin_fwd(x, wf, o):
 
 
 def fwd_form(w, o):
-    return phase_forms(w) if o['up'] else w
+    return phase_forms(w) if is_subpixel(o) else w
 
 
 def emulate_fwd(x, w, o, rounding):

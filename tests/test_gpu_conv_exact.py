@@ -17,7 +17,7 @@ import torch.nn.functional as F
 from tests.conv_cases import (CASES, F32_ONLY, GRID, TWIN_LAYERS, WGRAD_TWIN_CASES,
                               assert_exact_premise, EMU_TAU, EMU_TAU_DB, contract_errors, dyadic_weights,
                               effective_mode, emulate_dgrad, emulate_fwd, emulate_wgrad,
-                              int_grid, layer_geometry, reference64, rel_l2, rne_bf16,
+                              int_grid, is_subpixel, layer_geometry, reference64, rel_l2, rne_bf16,
                               run_layer, twins_apply)
 
 pytestmark = pytest.mark.gpu
@@ -76,11 +76,17 @@ def pass_bounds(case, fams):
     ctot = sum(c for c, _ in case['src'])
     ho, wo = out_hw(case)
     k2 = o['k'] ** 2
-    return (assert_exact_premise(ctot * k2, GRID['x'], GRID['w'], fams[0], o['up'],
+    # a sub-pixel layer (up-sampling, 3x3 / pad 1) multiplies phase forms, sums of up to four
+    # taps, and its weight gradient reduces over the B H W low-resolution pixels.  Any other
+    # up-sampling layer reads the raw taps from the up-sampled frame: growth 1, a weight
+    # gradient over the B Ho Wo output pixels -- and a data gradient that sums the 2x2 quad
+    # of up-sampled pixels (growth 4, like the sub-pixel 4x4 form)
+    sub = is_subpixel(o)
+    return (assert_exact_premise(ctot * k2, GRID['x'], GRID['w'], fams[0], sub,
                                  extra=2 * GRID['b']),
             assert_exact_premise(Cout * k2, GRID['g'], GRID['w'], fams[1], o['up'], extra=2 * GRID['b']),
-            assert_exact_premise(B * H * W if o['up'] else B * ho * wo, GRID['g'], GRID['x'], fams[2],
-                                 o['up']))
+            assert_exact_premise(B * H * W if sub else B * ho * wo, GRID['g'], GRID['x'], fams[2],
+                                 sub))
 
 
 def within_ulps(got, want, absref, ulps):
@@ -378,17 +384,25 @@ def emu_data(case, seed):
     B, H, W, Cout = case['B'], case['H'], case['W'], case['Cout']
     ctot = sum(c for c, _ in case['src'])
     ho, wo = out_hw(case)
+    k = case.get('k', 3)
     xs = [torch.randn(B, c, H, W, generator=g).double() for c, _ in case['src']]
-    w = dyadic_weights(g, (Cout, ctot, 3, 3))
+    w = dyadic_weights(g, (Cout, ctot, k, k))
     b = torch.randn(Cout, generator=g).float().double()
     gz = torch.randn(B, Cout, ho, wo, generator=g).float().double()
     return xs, w, b, gz
 
 
 def emu_measure(ei, mode):
-    """-> (families, {pass: (rounding, rel, elem, {alternative: rel distance})})"""
-    case = EMU_LAYERS[ei]
-    xs, w, b, gz = emu_data(case, 500 + ei)
+    return emu_measure_case(EMU_LAYERS[ei], 500 + ei, mode)
+
+
+def emu_measure_case(case, seed, mode, planar_dx_exact=True):
+    """-> (families, {pass: (rounding, rel, elem, {alternative: rel distance})})
+    planar_dx_exact: the planar members' data gradient runs beside the matrix-core launch in
+    exact f32 (csrc/gconv.hip peels narrow trailing planar destinations off a plain or
+    sub-pixel data gradient); False where it stays in the matrix-core problem and rounds
+    like every other column (quad rows, zero-inserted gout)."""
+    xs, w, b, gz = emu_data(case, seed)
     out = run_layer(case, mode, xs, w, b, None, gz)
     o = layer_geometry(case)
     x = torch.cat(xs, 1).cuda()
@@ -405,6 +419,8 @@ def emu_measure(ei, mode):
 
     def one(name, kind, fn, absval, got, per_member=False):
         r = emu_rounding(mode, out['fam'][kind], kind)
+        if name == 'dx' and not planar_dx_exact:
+            per_member = False
 
         def emu(rr):
             t = fn(rr)

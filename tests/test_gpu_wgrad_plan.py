@@ -1,8 +1,8 @@
 """The weight gradient's workspace invariant (csrc/wgrad_plan.hip): the size that
 dvsof_conv2d_wgrad_workspace_bytes answers from the shape alone covers the plan of every
 call of that shape -- with or without a bias gradient, in mode 3 with the bf16 twins bound or
-not.  For every layer of tests/conv_cases.py (its last five are there for the plan outcomes
-the others miss) the call runs in a workspace of exactly that many bytes, placed inside a
+not.  For every layer of tests/conv_cases.py (the last five of CASES are there for the plan
+outcomes the others miss; GEOMETRY adds the layers off the 3x3 / pad-1 forms) the call runs in a workspace of exactly that many bytes, placed inside a
 larger tensor whose remainder holds a sentinel: it returns DVSOF_OK, leaves the sentinel
 alone and writes, bit for bit, the dW and dbias of the same call in a generous workspace."""
 import ctypes
@@ -10,7 +10,7 @@ import ctypes
 import pytest
 import torch
 
-from tests.conv_cases import CASES, TWIN_LAYERS, WGRAD_TWIN_CASES, layer_geometry, twins_apply
+from tests.conv_cases import CASES, GEOMETRY, TWIN_LAYERS, WGRAD_TWIN_CASES, layer_geometry, twins_apply
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +23,7 @@ def _key(c):
             c.get('pad', 1), c.get('up', False))
 
 
-LAYERS = list({_key(c): c for c in CASES + [c for c, _, _ in TWIN_LAYERS] + WGRAD_TWIN_CASES}.values())
+LAYERS = list({_key(c): c for c in CASES + [c for c, _, _ in TWIN_LAYERS] + WGRAD_TWIN_CASES + GEOMETRY}.values())
 PARAMS = [(li, m) for li in range(len(LAYERS)) for m in range(4) if m != 3 or twins_apply(LAYERS[li])]
 
 

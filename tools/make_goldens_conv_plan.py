@@ -76,6 +76,10 @@ def descriptors():
         out.append(desc(1, 7, 16, [(32, NHWC), (32, NHWC)], 32, up=1, mfma=mfma))
         out.append(desc(1, 8, 8, [(16, NHWC)], 32, stride=2, mfma=mfma))
         out.append(desc(1, 9, 8, [(16, NHWC)], 32, stride=2, mfma=mfma))
+        # every accepted geometry off the 3x3 / pad-1 forms (tests/test_gpu_conv_geometry.py).
+        # The grid follows the case tables it is run beside: with a tests/conv_cases.py from
+        # before that list (and the golden file recorded with it) it is the grid of that time
+        out += [case_desc(c, mfma) for c in getattr(conv_cases, 'GEOMETRY', [])]
     # rejected descriptors
     ok = dict(B=1, H=8, W=8, src=[(16, NHWC)], Cout=16)
     out.append(desc(**ok, k=2))
