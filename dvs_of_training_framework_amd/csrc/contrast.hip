@@ -1,44 +1,56 @@
 // Contrast-maximisation term of the training loss and its gradient with
-// respect to the flow (docs/CONTRAST_SPEC.md): per frame the image of warped
-// events I_f of csrc/iwe.hip and the count image c_f of the same events,
-// term = mean_f (1 - var(I_f)/var(c_f)) (Gallego et al., CVPR 2018; the
-// normalisation is the flow warp loss of Stoffregen et al., ECCV 2020).
+// respect to the flow (docs/CONTRAST_SPEC.md): per image the warped events I_m
+// and the count image c_m of the same events,
+// term = mean_m (1 - var(I_m)/var(c_m)) (Gallego et al., CVPR 2018; the
+// normalisation is the flow warp loss of Stoffregen et al., ECCV 2020).  A
+// frame has one image, of all its events carried to the start of its window,
+// or one per reference time and polarity channel (sections 11-15; Zhu et al.,
+// CVPR 2019 warp to both ends of the window and keep the polarities apart,
+// Shiba et al., ECCV 2022 add the middle): m = (f R + r) C + c of
+// event_images.h, which iwe.hip shares.
 //
 // Replaces nothing of the reference: its loss reads the grey frames only.
 //
-// Forward: the warp and splat of frame_common.h, which are iwe.hip's, with the
-// frame found by sample and time window instead of by position in the
-// columns, the statistics of dvsof_iwe_stats, one closing wave.  Backward: the
-// scatter into the flow gradient collides on almost every active pixel, so it
-// is summed in 64-bit fixed point with a per-frame power-of-two unit and
-// integer atomics (the sums have no order), and one thread per element
-// converts once.  No floating-point atomics anywhere.  This file relies on
-// -ffp-contract=off.
-#include "frame_common.h"
+// Forward: one thread per event finds its frames by sample and time window,
+// reads the flow at its pixel once per frame and splats into the R images of
+// its channel (splat_event of event_images.h; the count image is repeated per
+// reference by R atomics in the same thread, not by a copy launch);
+// dvsof_iwe_stats on M frames; one closing wave.  Backward: the scatter into
+// the flow gradient collides on almost every active pixel, so the R C images
+// of a frame add into the same 64-bit fixed-point sums, with one power-of-two
+// unit per frame taken from the largest |G| over the frame's images; a thread
+// adds its R addends in registers (integers: no order) and issues one integer
+// atomic per component, and one thread per element converts once.  No
+// floating-point atomics anywhere.  This file relies on -ffp-contract=off.
+#include "event_images.h"
 #include "../../include/dvsof_contrast.h"
+#include "../../include/dvsof_contrast_multi.h"
 
 namespace {
 
 constexpr int NT = kFrameNT;
-constexpr int kUnitBits = 40;  // |one event's addend| < 2^(kUnitBits + 1) units
+constexpr int kUnitBits = 40;   // R = 1: |one event's addend| < 2^(kUnitBits + 1) units
+constexpr int kSharedBits = 2;  // R > 1: up to three addends of a pixel's event share a sum
 
-// one per frame, in the workspace behind the fixed-point sums
-struct FrameRec {
-    double mean;  // of I_f
-    double coef;  // -2 / (N var(c_f)); 0 where var(c_f) is not positive
-    double unit;  // 2^k: the flow gradient of the frame is summed in units of 1/unit
-    double term;  // 1 - var(I_f)/var(c_f); 0 where var(c_f) is not positive
+// one per image, in the workspace behind the fixed-point sums
+struct ImageRec {
+    double mean;  // of I_m
+    double coef;  // -2 / (N var(c_m)); 0 where var(c_m) is not positive
+    double gmax;  // |coef (I_m - mean)| <= gmax on every pixel
+    double term;  // 1 - var(I_m)/var(c_m); 0 where var(c_m) is not positive
 };
-static_assert(sizeof(FrameRec) == 32, "the workspace holds 32 bytes per frame");
+static_assert(sizeof(ImageRec) == 32, "the workspace holds 32 bytes per image");
 
 // ---------------------------------------------------------------------------
 // Forward.  One thread per event; an event takes part in every frame of its
-// sample whose window holds its time (both ends included).
+// sample whose window holds its time (both ends included), in the channel of
+// the sign of p.
 // ---------------------------------------------------------------------------
+template <int R, bool POL>
 __global__ __launch_bounds__(NT) void contrast_splat_kernel(
     const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w,
+    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
     unsigned long long *__restrict__ q, uint32_t *__restrict__ count)
 {
     const int64_t stride = (int64_t)gridDim.x * NT;
@@ -46,6 +58,8 @@ __global__ __launch_bounds__(NT) void contrast_splat_kernel(
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
         const int64_t xi = x[e], yi = y[e];
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // the -1 slots of cropped and padded events
+        int c;
+        if (!event_channel<POL>(pol, e, c)) continue;
         const float te = t[e];
         const int64_t s = sample[e];
         const size_t pix = (size_t)yi * w + (size_t)xi;
@@ -53,61 +67,82 @@ __global__ __launch_bounds__(NT) void contrast_splat_kernel(
             if (frame_sample[f] != s) continue;
             const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
             if (!(t0 <= te && te <= t1)) continue;  // a test, not a clamp; false for a NaN
-            atomicAdd(count + (size_t)f * plane + pix, 1u);
-            Warp p;
-            if (!warp_event(te, t0, t1, flow + (size_t)f * 2 * plane + pix, plane, xi, yi, h, w, p)) continue;
-            splat_corners(p, h, w, q + (size_t)f * plane);
+            const float tau = event_tau(te, t0, t1);
+            const float *fl = flow + (size_t)f * 2 * plane + pix;
+            const float u = fl[0], v = fl[plane];
+            splat_event<R, POL, true>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, count);
         }
     }
 }
 
-// One wave: the record of every frame (lane k takes frames k, k + 64, ...),
-// then lane 0 adds the frames' terms in frame order.
-__global__ __launch_bounds__(kWave) void contrast_close_kernel(const dvsof_iwe_result_t *__restrict__ result,
-                                                               int F, int h, int w, FrameRec *rec, float *term)
+// 2^k: the flow gradient of a frame is summed in units of 1/unit; |G_m| <= gmax < 2^e for every image of the frame
+__device__ __forceinline__ double unit_of(double gmax, int unit_bits)
+{
+    int e = 0;
+    if (gmax > 0.0) (void)frexp(gmax, &e);
+    return ldexp(1.0, unit_bits - e);
+}
+
+// One wave: the record of every image (lane k takes images k, k + 64, ...);
+// after a barrier the unit of every frame (lane k takes frames k, k + 64, ...;
+// a maximum has no order) and, in lane 0, the images' terms in image order.
+// A frame of one image has its unit from the gmax its lane holds.
+__global__ __launch_bounds__(kWave) void contrast_close_kernel(const dvsof_iwe_result_t *__restrict__ result, int F,
+                                                               int RC, int h, int w, int unit_bits, ImageRec *rec,
+                                                               double *unit, float *term)
 {
     const double N = (double)h * (double)w;
-    for (int f = threadIdx.x; f < F; f += kWave) {
-        const dvsof_iwe_result_t r = result[f];
+    const int M = F * RC;
+    for (int m = threadIdx.x; m < M; m += kWave) {
+        const dvsof_iwe_result_t r = result[m];
         const double mean = (double)r.sum_q * 0x1p-32 / N;
         const double var_i = r.sum_sq / N - mean * mean;
         const double cmean = (double)r.count_sum / N;
         const double var_c = (double)r.count_sq / N - cmean * cmean;
-        FrameRec o;
+        ImageRec o;
         o.mean = mean;
         o.coef = var_c > 0.0 ? -2.0 / (N * var_c) : 0.0;
         o.term = var_c > 0.0 ? 1.0 - var_i / var_c : 0.0;
-        // |G| = |coef (I - mean)| <= gmax < 2^e
-        const double gmax = fabs(o.coef) * fmax((double)r.max_q * 0x1p-32 - mean, mean);
-        int e = 0;
-        if (gmax > 0.0) (void)frexp(gmax, &e);
-        o.unit = ldexp(1.0, kUnitBits - e);
-        rec[f] = o;
+        o.gmax = fabs(o.coef) * fmax((double)r.max_q * 0x1p-32 - mean, mean);
+        rec[m] = o;
+        if (RC == 1) unit[m] = unit_of(o.gmax, unit_bits);
     }
     __syncthreads();
+    if (RC > 1) {
+        for (int f = threadIdx.x; f < F; f += kWave) {
+            double gmax = 0.0;
+            for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[f * RC + k].gmax);
+            unit[f] = unit_of(gmax, unit_bits);
+        }
+    }
     if (threadIdx.x == 0) {
         double s = 0.0;
-        for (int f = 0; f < F; ++f) s += rec[f].term;
-        *term = (float)(s / (double)F);
+        for (int m = 0; m < M; ++m) s += rec[m].term;
+        *term = (float)(s / (double)M);
     }
 }
 
 // ---------------------------------------------------------------------------
-// Backward.  One thread per event: G = coef (I - mean) at the four corners
-// (0 outside the image), the derivative of the bilinear weights, -tau of it to
-// the event's own pixel of the flow, in float64, truncated to the frame's unit.
+// Backward.  One thread per event and frame: for every reference G = coef (I -
+// mean) at the four corners of the image of its channel (0 outside the image),
+// the derivative of the bilinear weights, -sig of it to the event's own pixel
+// of the flow, in float64, truncated to the frame's unit.
 // ---------------------------------------------------------------------------
+template <int R, bool POL>
 __global__ __launch_bounds__(NT) void contrast_bwd_events_kernel(
     const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w,
-    const int64_t *__restrict__ q, const FrameRec *__restrict__ rec, unsigned long long *__restrict__ acc)
+    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
+    const int64_t *__restrict__ q, const ImageRec *__restrict__ rec, const double *__restrict__ unit,
+    unsigned long long *__restrict__ acc)
 {
     const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
         const int64_t xi = x[e], yi = y[e];
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
+        int c;
+        if (!event_channel<POL>(pol, e, c)) continue;
         const float te = t[e];
         const int64_t s = sample[e];
         const size_t pix = (size_t)yi * w + (size_t)xi;
@@ -115,29 +150,40 @@ __global__ __launch_bounds__(NT) void contrast_bwd_events_kernel(
             if (frame_sample[f] != s) continue;
             const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
             if (!(t0 <= te && te <= t1)) continue;
-            const FrameRec r = rec[f];
-            if (r.coef == 0.0) continue;  // var(c_f) = 0: every addend would be 0
-            Warp p;
-            if (!warp_event(te, t0, t1, flow + (size_t)f * 2 * plane + pix, plane, xi, yi, h, w, p)) continue;
-            const int64_t *img = q + (size_t)f * plane;
-            double G[2][2];
+            const float tau = event_tau(te, t0, t1);
+            const float *fl = flow + (size_t)f * 2 * plane + pix;
+            const float u = fl[0], v = fl[plane];
+            const double un = unit[f];
+            // R = 1: |ms g| < 2^(e+1) (1 + 2^-22), so |a| < 2^41 (1 + 2^-22); R > 1: at most three addends
+            // below 2^39 (1 + 2^-22) each; the product with the unit is exact
+            long long su = 0, sv = 0;
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
+            for (int r = 0; r < R; ++r) {
+                const size_t m = image_of<R, POL>(f, r, c);
+                const ImageRec a = rec[m];
+                if (a.coef == 0.0) continue;  // var(c_m) = 0: every addend would be 0
+                Warp p;
+                if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
+                const int64_t *img = q + m * plane;
+                double G[2][2];
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int xx = p.cx + i, yy = p.cy + j;
-                    const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
-                    G[j][i] = in ? r.coef * ((double)img[(size_t)yy * w + (size_t)xx] * 0x1p-32 - r.mean) : 0.0;
+                for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int xx = p.cx + i, yy = p.cy + j;
+                        const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
+                        G[j][i] = in ? a.coef * ((double)img[(size_t)yy * w + (size_t)xx] * 0x1p-32 - a.mean) : 0.0;
+                    }
                 }
+                const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
+                const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
+                const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
+                su += (long long)(ms * gx * un);
+                sv += (long long)(ms * gy * un);
             }
-            const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
-            const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
-            const double mt = -(double)p.tau;
-            // |mt g| < 2^(e+1) (1 + 2^-22), so |a| < 2^41 (1 + 2^-22); the product with the unit is exact
-            const long long au = (long long)(mt * gx * r.unit), av = (long long)(mt * gy * r.unit);
             unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
-            if (au != 0) atomicAdd(dst, (unsigned long long)au);
-            if (av != 0) atomicAdd(dst + plane, (unsigned long long)av);
+            if (su != 0) atomicAdd(dst, (unsigned long long)su);
+            if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
         }
     }
 }
@@ -145,30 +191,126 @@ __global__ __launch_bounds__(NT) void contrast_bwd_events_kernel(
 // One thread per element of grad_flow: convert, clear the sum for the next
 // backward of the same forward, store.
 __global__ __launch_bounds__(NT) void contrast_bwd_close_kernel(long long *__restrict__ acc,
-                                                                const FrameRec *__restrict__ rec,
+                                                                const double *__restrict__ unit,
                                                                 const float *__restrict__ seed, float weight, int F,
-                                                                size_t per_frame, float *__restrict__ grad)
+                                                                int M, size_t per_frame, float *__restrict__ grad)
 {
     const size_t total = (size_t)F * per_frame, stride = (size_t)gridDim.x * NT;
     const float sw = seed[0] * weight;
     for (size_t k = (size_t)blockIdx.x * NT + threadIdx.x; k < total; k += stride) {
         const long long a = acc[k];
         acc[k] = 0;
-        const double value = (double)a / rec[k / per_frame].unit / (double)F;  // the first division is exact
+        const double value = (double)a / unit[k / per_frame] / (double)M;  // the first division is exact
         grad[k] = sw * (float)value;
     }
 }
 
 size_t sums_bytes(int F, int h, int w) { return sizeof(int64_t) * 2 * (size_t)F * h * w; }
 
+// the workspace: the sums, M records, F units, the statistics' partials
+struct Workspace {
+    unsigned long long *sums;
+    ImageRec *rec;
+    double *unit;
+    void *stats;
+    size_t stats_bytes;
+};
+
+Workspace carve(void *workspace, int F, int h, int w, const Plan &pl)
+{
+    char *ws = (char *)workspace;
+    Workspace o;
+    o.sums = (unsigned long long *)ws;
+    o.rec = (ImageRec *)(ws + sums_bytes(F, h, w));
+    o.unit = (double *)(o.rec + pl.M);
+    o.stats = o.unit + F;
+    o.stats_bytes = dvsof_iwe_stats_workspace_bytes(pl.M, h, w);
+    return o;
+}
+
 }  // namespace
 
 extern "C" {
 
+size_t dvsof_contrast_multi_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
+{
+    Plan pl;
+    if (F < 1 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return 0;
+    return sums_bytes(F, h, w) + sizeof(ImageRec) * (size_t)pl.M + sizeof(double) * (size_t)F +
+           dvsof_iwe_stats_workspace_bytes(pl.M, h, w);
+}
+
+int dvsof_contrast_multi_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                             const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                             const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                             int reference_mask, int polarity, int64_t *q, uint32_t *count,
+                             dvsof_iwe_result_t *result, float *term, void *workspace, size_t workspace_bytes,
+                             void *stream)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !q || !count || !result || !term || !frame_ts || !frame_sample || !flow)
+        return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < dvsof_contrast_multi_workspace_bytes(F, reference_mask, polarity, h, w))
+        return DVSOF_ENOSPACE;
+    hipStream_t st = as_stream(stream);
+    const size_t pixels = (size_t)pl.M * h * w;
+    const Workspace ws = carve(workspace, F, h, w, pl);
+    DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
+    DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
+    DVSOF_HIP_TRY((hipError_t)fill_u32(ws.sums, 0u, sums_bytes(F, h, w), st));
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t, p,
+                                sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
+                                (unsigned long long *)q, count);
+        DVSOF_LAUNCH_CHECK();
+    }
+    const int rc = dvsof_iwe_stats(q, count, pl.M, h, w, result, ws.stats, ws.stats_bytes, stream);
+    if (rc != DVSOF_OK) return rc;
+    hipLaunchKernelGGL(contrast_close_kernel, dim3(1), dim3(kWave), 0, st, result, F, pl.R * pl.C, h, w,
+                       pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, ws.rec, ws.unit, term);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int dvsof_contrast_multi_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                             const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                             const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                             int reference_mask, int polarity, const int64_t *q, void *workspace,
+                             size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
+                             void *stream)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !q || !seed || !grad_flow || !frame_ts || !frame_sample || !flow)
+        return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < dvsof_contrast_multi_workspace_bytes(F, reference_mask, polarity, h, w))
+        return DVSOF_ENOSPACE;
+    hipStream_t st = as_stream(stream);
+    const Workspace ws = carve(workspace, F, h, w, pl);
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(contrast_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y,
+                                t, p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, q,
+                                (const ImageRec *)ws.rec, (const double *)ws.unit, ws.sums);
+        DVSOF_LAUNCH_CHECK();
+    }
+    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
+    hipLaunchKernelGGL(contrast_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
+                       (long long *)ws.sums, (const double *)ws.unit, seed, weight, F, pl.M, per_frame, grad_flow);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+// The term as it was before the references and the polarities: one image per frame, of all its
+// events carried to the start of the window.  The refusals are those of the general calls at
+// these options, code for code and in the same order (F > 65535 is refused by the plan).
 size_t dvsof_contrast_workspace_bytes(int F, int h, int w)
 {
-    if (F < 1 || bad_frame_sizes(F, h, w)) return 0;
-    return sums_bytes(F, h, w) + sizeof(FrameRec) * (size_t)F + dvsof_iwe_stats_workspace_bytes(F, h, w);
+    return dvsof_contrast_multi_workspace_bytes(F, 1, 0, h, w);
 }
 
 int dvsof_contrast_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *sample_index,
@@ -176,31 +318,8 @@ int dvsof_contrast_fwd(const int64_t *x, const int64_t *y, const float *t, const
                        int F, int h, int w, int64_t *q, uint32_t *count, dvsof_iwe_result_t *result, float *term,
                        void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (F < 0 || n_events < 0) return DVSOF_EINVAL;
-    if (F == 0) return DVSOF_OK;
-    if (bad_frame_sizes(F, h, w) || !q || !count || !result || !term || !frame_ts || !frame_sample || !flow)
-        return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || !sample_index)) return DVSOF_EINVAL;
-    if (!workspace || workspace_bytes < dvsof_contrast_workspace_bytes(F, h, w)) return DVSOF_ENOSPACE;
-    hipStream_t st = as_stream(stream);
-    const size_t pixels = (size_t)F * h * w;
-    char *ws = (char *)workspace;
-    FrameRec *rec = (FrameRec *)(ws + sums_bytes(F, h, w));
-    DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
-    DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
-    DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, sums_bytes(F, h, w), st));
-    if (n_events > 0) {
-        hipLaunchKernelGGL(contrast_splat_kernel, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
-                           sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, (unsigned long long *)q,
-                           count);
-        DVSOF_LAUNCH_CHECK();
-    }
-    const int rc = dvsof_iwe_stats(q, count, F, h, w, result, rec + F, dvsof_iwe_stats_workspace_bytes(F, h, w),
-                                   stream);
-    if (rc != DVSOF_OK) return rc;
-    hipLaunchKernelGGL(contrast_close_kernel, dim3(1), dim3(kWave), 0, st, result, F, h, w, rec, term);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return dvsof_contrast_multi_fwd(x, y, t, nullptr, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w,
+                                    1, 0, q, count, result, term, workspace, workspace_bytes, stream);
 }
 
 int dvsof_contrast_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *sample_index,
@@ -208,26 +327,8 @@ int dvsof_contrast_bwd(const int64_t *x, const int64_t *y, const float *t, const
                        int F, int h, int w, const int64_t *q, void *workspace, size_t workspace_bytes,
                        const float *seed, float weight, float *grad_flow, void *stream)
 {
-    if (F < 0 || n_events < 0) return DVSOF_EINVAL;
-    if (F == 0) return DVSOF_OK;
-    if (bad_frame_sizes(F, h, w) || !q || !seed || !grad_flow || !frame_ts || !frame_sample || !flow)
-        return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || !sample_index)) return DVSOF_EINVAL;
-    if (!workspace || workspace_bytes < dvsof_contrast_workspace_bytes(F, h, w)) return DVSOF_ENOSPACE;
-    hipStream_t st = as_stream(stream);
-    char *ws = (char *)workspace;
-    const FrameRec *rec = (const FrameRec *)(ws + sums_bytes(F, h, w));
-    if (n_events > 0) {
-        hipLaunchKernelGGL(contrast_bwd_events_kernel, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
-                           sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, q, rec,
-                           (unsigned long long *)ws);
-        DVSOF_LAUNCH_CHECK();
-    }
-    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
-    hipLaunchKernelGGL(contrast_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
-                       (long long *)ws, rec, seed, weight, F, per_frame, grad_flow);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return dvsof_contrast_multi_bwd(x, y, t, nullptr, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w,
+                                    1, 0, q, workspace, workspace_bytes, seed, weight, grad_flow, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Device helpers shared by the per-frame evaluation kernels (eval.hip,
-// iwe.hip, eval_panels.hip, render.hip, contrast.hip, contrast_multi.hip), so
-// that what the specs call the same arithmetic is the same code:
+// iwe.hip, eval_panels.hip, render.hip, contrast.hip; iwe.hip and contrast.hip
+// reach the warp and the splat through event_images.h), so that what the specs
+// call the same arithmetic is the same code:
 //   - the fixed-order reduction of docs/EVAL_SPEC.md section 3 and
 //     docs/IWE_SPEC.md section 3: thread (strided pixels, ascending) -> wave
 //     (shuffle tree) -> block (waves 0..3) -> frame (partials ascending per
@@ -149,28 +150,6 @@ struct Warp {
     float tau;
 };
 
-// Steps 1-6 for an event that takes part in a frame; false: dropped by the
-// inside test.  Every splat and the backward call this, so they see the same bits.
-__device__ __forceinline__ bool warp_event(float te, float t0, float t1, const float *__restrict__ fl,
-                                           size_t plane, int64_t xi, int64_t yi, int h, int w, Warp &o)
-{
-    const float d = t1 - t0;
-    o.tau = d > 0.f ? fminf(fmaxf((te - t0) / d, 0.f), 1.f) : 0.f;
-    const float u = fl[0], v = fl[plane];
-    const float xw = (float)xi - o.tau * u, yw = (float)yi - o.tau * v;
-    // in float, before any conversion: false for a NaN, an infinity, 1e30
-    if (!(xw > -1.f && xw < (float)w && yw > -1.f && yw < (float)h)) return false;
-    const float flx = floorf(xw), fly = floorf(yw);  // in [-1, side - 1]
-    const float fx = xw - flx, fy = yw - fly;
-    o.wx[0] = 1.f - fx;
-    o.wx[1] = fx;
-    o.wy[0] = 1.f - fy;
-    o.wy[1] = fy;
-    o.cx = (int)flx;
-    o.cy = (int)fly;
-    return true;
-}
-
 // Step 1 alone: the time of an event within its window, in [0, 1]
 __device__ __forceinline__ float event_tau(float te, float t0, float t1)
 {
@@ -178,19 +157,21 @@ __device__ __forceinline__ float event_tau(float te, float t0, float t1)
     return d > 0.f ? fminf(fmaxf((te - t0) / d, 0.f), 1.f) : 0.f;
 }
 
-// warp_event's sibling for a reference time rho in [0, 1] of the window
-// (docs/CONTRAST_SPEC.md section 11): the event is carried over sig = tau - rho
-// instead of tau, everything else is steps 2-6 operation by operation.  o.tau
-// holds sig.  At rho = 0 sig has the bits of tau and the result those of
-// warp_event.  u, v: the flow at the event's own pixel, read by the caller once
-// for all references.
+// Steps 2-6 for an event that takes part in a frame, carried to the reference
+// time rho in [0, 1] of the window (docs/CONTRAST_SPEC.md section 11) over
+// sig = tau - rho; rho = 0 is the start of the window of IWE_SPEC section 2,
+// where sig has the bits of tau (tau - 0.f, -0 included).  o.tau holds sig.
+// u, v: the flow at the event's own pixel, read by the caller once for all
+// references.  false: dropped by the inside test.  Every splat and the backward
+// call this, so they see the same bits.
 __device__ __forceinline__ bool warp_event_to(float tau, float rho, float u, float v, int64_t xi, int64_t yi,
                                               int h, int w, Warp &o)
 {
     o.tau = tau - rho;
     const float xw = (float)xi - o.tau * u, yw = (float)yi - o.tau * v;
+    // in float, before any conversion: false for a NaN, an infinity, 1e30
     if (!(xw > -1.f && xw < (float)w && yw > -1.f && yw < (float)h)) return false;
-    const float flx = floorf(xw), fly = floorf(yw);
+    const float flx = floorf(xw), fly = floorf(yw);  // in [-1, side - 1]
     const float fx = xw - flx, fy = yw - fly;
     o.wx[0] = 1.f - fx;
     o.wx[1] = fx;

@@ -13,8 +13,16 @@
 // path; no tiled LDS pass (a validation batch is a few hundred thousand
 // events).  The frame search, the warp, the splat and the fixed-order
 // reduction of the statistics are those of frame_common.h.
+//
+// The same kernel splats at several reference times of the window and with ON
+// and OFF events accumulated apart (docs/IWE_SPEC.md sections 8-13; the images
+// are those of event_images.h, which contrast.hip shares): it then writes the
+// count image of every channel too, repeated per reference, so that
+// dvsof_iwe_stats and dvsof_iwe_render take the M images as M frames.
 // This file relies on -ffp-contract=off.
 #include "render_common.h"
+#include "event_images.h"
+#include "../../include/dvsof_iwe_multi.h"
 
 static_assert(sizeof(dvsof_iwe_result_t) == 48, "result rows are 48 bytes (eval.py reads them as such)");
 
@@ -24,21 +32,28 @@ constexpr int NT = kFrameNT;
 constexpr int kPanels = 2;
 
 // ---------------------------------------------------------------------------
-// Splat.  One thread per event of a frame.
+// Splat.  One thread per event of a frame: it reads the flow at its pixel once
+// and issues, per reference, one 32-bit count atomic (COUNT) and up to four
+// 64-bit integer atomics (splat_event of event_images.h).
 // ---------------------------------------------------------------------------
+template <int R, bool POL, bool COUNT = true>
 __global__ __launch_bounds__(NT) void iwe_splat_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t, int64_t n,
-    const int64_t *__restrict__ begin, const float *__restrict__ ts, const float *__restrict__ flow, int F,
-    int h, int w, unsigned long long *__restrict__ q)
+    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
+    const int64_t *__restrict__ pol, int64_t n, const int64_t *__restrict__ begin, const float *__restrict__ ts,
+    const float *__restrict__ flow, int F, int h, int w, Refs refs, unsigned long long *__restrict__ q,
+    uint32_t *__restrict__ count)
 {
     const size_t plane = (size_t)h * w;
     for_each_frame_event(n, begin, F, [=](int64_t e, int f) {
         const int64_t xi = x[e], yi = y[e];
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) return;  // the -1 slots of cropped and padded events
-        Warp p;
-        if (warp_event(t[e], ts[2 * f], ts[2 * f + 1], flow + (size_t)f * 2 * plane + (size_t)yi * w + (size_t)xi,
-                       plane, xi, yi, h, w, p))
-            splat_corners(p, h, w, q + (size_t)f * plane);
+        int c;
+        if (!event_channel<POL>(pol, e, c)) return;
+        const size_t pix = (size_t)yi * w + (size_t)xi;
+        const float tau = event_tau(t[e], ts[2 * f], ts[2 * f + 1]);
+        const float *fl = flow + (size_t)f * 2 * plane + pix;
+        const float u = fl[0], v = fl[plane];
+        splat_event<R, POL, COUNT>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, count);
     });
 }
 
@@ -140,9 +155,39 @@ int dvsof_iwe_splat(const int64_t *x, const int64_t *y, const float *t, int64_t 
     if (n_events > 0 && (!x || !y || !t)) return DVSOF_EINVAL;
     DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * (size_t)F * h * w, as_stream(stream)));
     if (n_events == 0) return DVSOF_OK;
-    hipLaunchKernelGGL(iwe_splat_kernel, dim3(event_blocks(n_events)), dim3(NT), 0,
-                       as_stream(stream), x, y, t, n_events, frame_event_begin, frame_ts, flow, F, h, w,
-                       (unsigned long long *)q);
+    Plan pl;
+    (void)plan_of(F, 1, 0, pl);  // the start of the window, the polarities together; no count image
+    hipLaunchKernelGGL((iwe_splat_kernel<1, false, false>), dim3(event_blocks(n_events)), dim3(NT), 0,
+                       as_stream(stream), x, y, t, (const int64_t *)nullptr, n_events, frame_event_begin, frame_ts,
+                       flow, F, h, w, pl.refs, (unsigned long long *)q, (uint32_t *)nullptr);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int dvsof_iwe_multi_images(int F, int reference_mask, int polarity)
+{
+    Plan pl;
+    return plan_of(F, reference_mask, polarity, pl) ? pl.M : 0;
+}
+
+int dvsof_iwe_splat_multi(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                          int64_t n_events, const int64_t *frame_event_begin, const float *frame_ts,
+                          const float *flow, int F, int h, int w, int reference_mask, int polarity, int64_t *q,
+                          uint32_t *count, void *stream)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !q || !count || !frame_event_begin || !frame_ts || !flow) return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !t || (polarity && !p))) return DVSOF_EINVAL;
+    hipStream_t st = as_stream(stream);
+    const size_t pixels = (size_t)pl.M * h * w;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
+    DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
+    if (n_events == 0) return DVSOF_OK;
+    DVSOF_REFS_POL_DISPATCH(iwe_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t, p,
+                            n_events, frame_event_begin, frame_ts, flow, F, h, w, pl.refs,
+                            (unsigned long long *)q, count);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }

@@ -524,7 +524,7 @@ def iwe_splat(events, win_out, frame_ts, flow):
 
 def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), polarity=False):
     """``iwe_splat`` at several reference times of the window and with ON and
-    OFF events apart (csrc/iwe_multi.hip, IWE_SPEC sections 8-13).  events,
+    OFF events apart (csrc/iwe.hip, IWE_SPEC sections 8-13).  events,
     win_out, frame_ts, flow as ``iwe_splat`` takes them, and the column
     'polarity' int64 with ``polarity``; references: names among start, middle,
     end, or a mask (``loss.contrast_reference_mask``).  With M = F R C images,

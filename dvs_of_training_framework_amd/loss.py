@@ -327,7 +327,7 @@ def contrast_bwd_host(x, y, t, sample_index, frame_ts, frame_sample, flow, fwd, 
     return sw * value.astype(_F32), sums
 
 
-# Several reference times, ON and OFF events apart (csrc/contrast_multi.hip,
+# Several reference times, ON and OFF events apart (csrc/contrast.hip,
 # CONTRAST_SPEC sections 11-15)
 CONTRAST_REFERENCES = {'start': 0.0, 'middle': 0.5, 'end': 1.0}     # name -> rho, in the order of the mask's bits
 CONTRAST_SHARED_BITS = 2
@@ -503,56 +503,9 @@ def contrast_multi_bwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, fl
 
 class _Contrast(torch.autograd.Function):
     """(weight * term, term) of the finest flow; the gradient of the first
-    enters the flow (dvsof_contrast_fwd / dvsof_contrast_bwd).  The weight is
-    applied inside the backward's closing kernel."""
-
-    @staticmethod
-    def forward(ctx, flow, x, y, t, sample_index, frame_ts, frame_sample, weight):
-        from .eval import IWE_RESULT_DTYPE
-        dev = flow.device
-        flow = flow.detach().contiguous().float()
-        F, _, h, w = flow.shape
-        lib = _lib.lib()
-        q = torch.empty(F, h, w, dtype=torch.long, device=dev)
-        count = torch.empty(F, h, w, dtype=torch.int32, device=dev)
-        result = torch.empty(F, IWE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        term = torch.zeros((), dtype=torch.float32, device=dev) if F == 0 else \
-            torch.empty((), dtype=torch.float32, device=dev)
-        nbytes = lib.dvsof_contrast_workspace_bytes(F, h, w)
-        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
-        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
-        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
-        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flow.shape, frame_ts.shape)
-        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
-        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
-        _lib.check(lib.dvsof_contrast_fwd(
-            *[c.data_ptr() for c in cols], cols[0].numel(), tables[0].data_ptr(), tables[1].data_ptr(),
-            flow.data_ptr(), F, h, w, q.data_ptr(), count.data_ptr(), result.data_ptr(),
-            term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_contrast_fwd')
-        ctx.held = (cols, tables, flow, q, ws, nbytes)
-        ctx.weight = float(weight)
-        ctx.mark_non_differentiable(term)
-        ctx.set_materialize_grads(False)
-        return term * ctx.weight, term
-
-    @staticmethod
-    def backward(ctx, g_value, _g_term):
-        if g_value is None:
-            return (None,) * 8
-        cols, tables, flow, q, ws, nbytes = ctx.held
-        F, _, h, w = flow.shape
-        grad = torch.empty_like(flow)
-        seed = g_value.contiguous().float()
-        _lib.check(_lib.lib().dvsof_contrast_bwd(
-            *[c.data_ptr() for c in cols], cols[0].numel(), tables[0].data_ptr(), tables[1].data_ptr(),
-            flow.data_ptr(), F, h, w, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(),
-            ctx.weight, grad.data_ptr(), _lib.stream()), 'dvsof_contrast_bwd')
-        return (grad,) + (None,) * 7
-
-
-class _ContrastMulti(torch.autograd.Function):
-    """``_Contrast`` with several reference times and the polarities apart
-    (dvsof_contrast_multi_fwd / dvsof_contrast_multi_bwd)."""
+    enters the flow (dvsof_contrast_multi_fwd / dvsof_contrast_multi_bwd, with
+    the reference times of ``mask`` and the polarities apart or not).  The
+    weight is applied inside the backward's closing kernel."""
 
     @staticmethod
     def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity):
@@ -745,8 +698,8 @@ class Losses:
         window the events are warped to, one image each; polarity: ON and OFF
         events in images of their own (``events['polarity']``; an event of
         polarity 0 takes no part).  The term is the mean over all images
-        (CONTRAST_SPEC sections 11-15).  The defaults are the term as it was,
-        by the calls it was."""
+        (CONTRAST_SPEC sections 11-15).  The defaults are the term as it was:
+        the same kernels, through the general entry point."""
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the contrast term of scale {self.shapes[-1]}'
@@ -754,13 +707,10 @@ class Losses:
         _lib.require_cuda(flow, flow_ts, flow_sample_idx, *cols)
         mask = contrast_reference_mask(references)
         weight_ = 1.0 if weight is None else float(weight)
-        if mask == 1 and not polarity:
-            value, term = _Contrast.apply(flow, *cols, flow_ts, flow_sample_idx, weight_)
-        else:
-            pol = events['polarity'] if polarity else None
-            _lib.require_cuda(pol)
-            value, term = _ContrastMulti.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx,
-                                               weight_, mask, bool(polarity))
+        pol = events['polarity'] if polarity else None
+        _lib.require_cuda(pol)
+        value, term = _Contrast.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
+                                      bool(polarity))
         return value if weight is None else (value, term)
 
 

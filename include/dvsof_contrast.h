@@ -21,8 +21,11 @@ extern "C" {
 
 /*
  * Bytes of the workspace both calls share: the fixed-point gradient sums
- * int64[F,2,h,w], one 32-byte record {mean, coef, unit, term} per frame and
- * the partials of dvsof_iwe_stats.  0 for sizes the calls refuse.
+ * int64[F,2,h,w], one 32-byte record {mean, coef, gmax, term} per frame, one
+ * float64 unit per frame and the partials of dvsof_iwe_stats: what
+ * dvsof_contrast_multi_workspace_bytes(F, 1, 0, h, w) of dvsof_contrast_multi.h
+ * returns, whose kernels these calls run (8 F bytes more than while the unit
+ * was the record's third field).  0 for sizes the calls refuse.
  */
 size_t dvsof_contrast_workspace_bytes(int F, int h, int w);
 

@@ -2,7 +2,7 @@
  * dvsof_contrast_multi.h -- extension of the C ABI of libdvsof_hip.so (dvsof.h,
  * whose conventions hold here): the contrast-maximisation term of
  * dvsof_contrast.h with several reference times and with ON and OFF events
- * accumulated apart (csrc/contrast_multi.hip, docs/CONTRAST_SPEC.md sections
+ * accumulated apart (csrc/contrast.hip, docs/CONTRAST_SPEC.md sections
  * 11-15; Zhu et al., CVPR 2019; Shiba et al., ECCV 2022).
  *
  *   reference_mask  bit 0: the window's start (rho = 0), bit 1: its middle

@@ -2,7 +2,7 @@
  * dvsof_iwe_multi.h -- extension of the C ABI of libdvsof_hip.so (dvsof.h,
  * whose conventions hold here): the image of warped events of dvsof_iwe_splat
  * at several reference times of the window and with ON and OFF events
- * accumulated apart (csrc/iwe_multi.hip, docs/IWE_SPEC.md sections 8-13).  The
+ * accumulated apart (csrc/iwe.hip, docs/IWE_SPEC.md sections 8-13).  The
  * options and the images are those of dvsof_contrast_multi.h, so that the
  * validation metric and the training term look at the same image:
  *

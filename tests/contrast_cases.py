@@ -312,6 +312,12 @@ def degenerate_case():
     return _finish(dict(c, ts=ts, fs=fs, t=t, s=np.zeros_like(c['s'])))
 
 
+def many_frames_case():
+    """More frames than the closing wave has lanes: 130 frames of 2x3, eight
+    events each on average; a lane of the wave takes frames k, k + 64, k + 128."""
+    return device_case((2, 3), 130, 1040)
+
+
 DEVICE_SHAPES = ((1, 1), (2, 3), (5, 7), (16, 16), (33, 31))
 DEVICE_COUNTS = (0, 1, 255, 256, 257, 4097)
 
@@ -319,7 +325,7 @@ DEVICE_COUNTS = (0, 1, 255, 256, 257, 4097)
 def device_cases():
     """name -> case: F in {1, 3} x the shapes at 257 events, every event count
     at 5x7 and 33x31, two frames large enough for several partial blocks in the
-    statistics, and the two special cases."""
+    statistics, the two special cases, and 130 frames."""
     out = {}
     for F in (1, 3):
         for shape in DEVICE_SHAPES:
@@ -333,6 +339,7 @@ def device_cases():
     out['400x400_F1_n4097'] = device_case((400, 400), 1, 4097)
     out['one_pixel_4097'] = one_pixel_case()
     out['degenerate_windows'] = degenerate_case()
+    out['2x3_F130_n1040'] = many_frames_case()
     return out
 
 

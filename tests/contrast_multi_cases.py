@@ -281,7 +281,8 @@ def device_matrix():
     """name -> (case, mask, polarity): the shapes x F in {1, 3} at 257 events
     for every mask and both polarity settings; every event count at 5x7 and
     33x31, the one-pixel and degenerate-window cases and 40x40 F=3 (M = 18,
-    two partial blocks per image) at mask 7 with polarity."""
+    two partial blocks per image) at mask 7 with polarity; 130 frames, more
+    than the closing wave has lanes, with one image a frame and with six."""
     out = {}
     for F in (1, 3):
         for shape in DEVICE_SHAPES:
@@ -294,6 +295,9 @@ def device_matrix():
     out['one_pixel_4097_m7_p1'] = (with_polarity(cc.one_pixel_case()), 7, True)
     out['degenerate_windows_m7_p1'] = (with_polarity(cc.degenerate_case()), 7, True)
     out['40x40_F3_n4097_m7_p1'] = (with_polarity(cc.device_case((40, 40), 3, 4097)), 7, True)
+    many = with_polarity(cc.many_frames_case())
+    out['2x3_F130_n1040_m1_p0'] = (many, 1, False)
+    out['2x3_F130_n1040_m7_p1'] = (many, 7, True)
     return out
 
 

@@ -1,8 +1,8 @@
 """CPU checks of the extension header include/dvsof_contrast.h: the library
 exports what it declares, the derived binding equals a recorded table
 (tests/golden/abi_signatures_contrast.json) and signatures written out by
-hand, a C compiler accepts the header, and the table of include/dvsof.h is
-left as it was."""
+hand, a C compiler accepts the header, the table of include/dvsof.h is left as it
+was, and the workspace is that of the general entry points at their defaults."""
 import ctypes
 import json
 import os
@@ -71,3 +71,15 @@ def test_an_extension_header_may_only_add_functions():
     assert list(ext.functions) == ['dvsof_x'] and ext.structs.keys() == base.structs.keys()
     with pytest.raises(_abi.AbiError, match=r'x\.h line 2:'):
         _abi.Abi('\nint dvsof_x(widget_t *w);', base=base, name='x.h')
+
+
+def test_the_workspace_is_that_of_the_general_entry_points_at_the_start_without_polarity():
+    """Host code only.  The refused sizes are those tests/test_gpu_contrast.py lists."""
+    lib = _lib.lib()
+    for F, h, w in ((1, 5, 7), (3, 33, 31), (3, 2, 3), (65535, 1, 1)):
+        need = lib.dvsof_contrast_workspace_bytes(F, h, w)
+        assert need == lib.dvsof_contrast_multi_workspace_bytes(F, 1, 0, h, w)
+        assert need == 16 * F * h * w + 32 * F + 8 * F + lib.dvsof_iwe_stats_workspace_bytes(F, h, w) > 0
+    for F, h, w in ((0, 4, 4), (-1, 4, 4), (65536, 4, 4), (1, 0, 4), (1, 4, 32768)):
+        assert lib.dvsof_contrast_workspace_bytes(F, h, w) == 0, (F, h, w)
+        assert lib.dvsof_contrast_multi_workspace_bytes(F, 1, 0, h, w) == 0, (F, h, w)

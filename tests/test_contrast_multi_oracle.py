@@ -1,7 +1,7 @@
 """The contrast term with several reference times and the polarities apart,
 without a GPU (docs/CONTRAST_SPEC.md sections 11-15): the numpy restatement
 loss.contrast_multi_fwd_host / contrast_multi_bwd_host, which the kernels of
-csrc/contrast_multi.hip are pinned to byte for byte
+csrc/contrast.hip are pinned to byte for byte
 (tests/test_gpu_contrast_multi.py), against the existing restatement where
 the two must agree, against the float64 definition within the derived bounds,
 the exact identities (dyadic cases, the mirrored window, the polarities), the

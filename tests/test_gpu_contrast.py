@@ -1,7 +1,7 @@
 """csrc/contrast.hip on the device against the numpy restatement of
 docs/CONTRAST_SPEC.md (loss.contrast_fwd_host / contrast_bwd_host), byte for
-byte: the images, the counts, the statistics rows, the term and the flow
-gradient on every case of tests/contrast_cases.py and on a permuted copy of
+byte: the images, the counts, the statistics rows, the frames' records and
+units in the workspace, the term and the flow gradient on every case of tests/contrast_cases.py and on a permuted copy of
 each; the argument rules; and the term through autograd in a training step."""
 import numpy as np
 import pytest
@@ -27,7 +27,9 @@ CASE_IDS = list(cases())
 
 def device_run(c, seed=1.0, weight=1.0, fills=(0xAA, 0x55)):
     """dvsof_contrast_fwd, then dvsof_contrast_bwd once per fill pattern of the
-    gradient buffer -> (q, count, rows, term, [grad per fill]) as numpy."""
+    gradient buffer -> (q, count, rows, term, [grad per fill], rec [F,4] =
+    {mean, coef, gmax, term} and unit [F] as the forward left them in the
+    workspace behind the sums) as numpy."""
     lib = _lib.lib()
     h, w = c['shape']
     F = len(c['fs'])
@@ -44,6 +46,7 @@ def device_run(c, seed=1.0, weight=1.0, fills=(0xAA, 0x55)):
     tables = [d[k].data_ptr() for k in ('ts', 'fs', 'flow')]
     assert lib.dvsof_contrast_fwd(*cols, n, *tables, F, h, w, q.data_ptr(), count.data_ptr(), rows.data_ptr(),
                                   term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()) == 0
+    after_fwd = ws.cpu().numpy()
     seed_t = torch.tensor(seed, dtype=torch.float32, device=DEV)
     grads = []
     for fill in fills:
@@ -54,20 +57,25 @@ def device_run(c, seed=1.0, weight=1.0, fills=(0xAA, 0x55)):
                                       seed_t.data_ptr(), weight, grad.data_ptr(), _lib.stream()) == 0
         grads.append(grad.cpu().numpy())
     torch.cuda.synchronize()
+    n_sums = 2 * F * h * w
     return (q.cpu().numpy(), count.cpu().numpy().view(np.uint32), dev_eval.read_iwe_results(rows),
-            term.cpu().numpy(), grads)
+            term.cpu().numpy(), grads, after_fwd[n_sums:n_sums + 4 * F].view(np.float64).reshape(F, 4),
+            after_fwd[n_sums + 4 * F:n_sums + 5 * F].view(np.float64))
 
 
 def same_as_restatement(c, seed, weight):
     fwd = L.contrast_fwd_host(*cc.args_of(c))
     want, _ = L.contrast_bwd_host(*cc.args_of(c), fwd, seed=seed, weight=weight)
-    q, count, rows, term, grads = device_run(c, seed, weight)
+    q, count, rows, term, grads, rec, unit = device_run(c, seed, weight)
     assert np.array_equal(q, fwd['q']), 'q'
     assert np.array_equal(count, fwd['count']), 'count'
     for k in ('sum_q', 'max_q', 'count_sum', 'count_sq', 'count_max'):
         assert np.array_equal(rows[k], fwd['result'][k]), k
     assert rows['sum_sq'].tobytes() == fwd['result']['sum_sq'].tobytes(), 'sum_sq'
     assert term.tobytes() == fwd['term'].tobytes(), (term, fwd['term'])
+    for i, k in ((0, 'mean'), (1, 'coef'), (3, 'frame_term')):
+        assert rec[:, i].tobytes() == fwd[k].tobytes(), k
+    assert unit.tobytes() == fwd['unit'].tobytes(), 'unit'  # a frame of one image: from the gmax its lane holds
     for g in grads:                                     # every element written, from either pattern
         assert g.tobytes() == want.tobytes(), int((g.view(np.uint32) != want.view(np.uint32)).sum())
     return fwd, want
@@ -102,6 +110,15 @@ def test_the_cases_reach_what_they_are_there_for():
     # d == 0: tau = 0 and every event stays where it is, unless its flow is not finite (0 * inf)
     finite = np.isfinite(cases()['degenerate_windows']['flow'][0]).all(0)
     assert np.array_equal(deg['q'][0][finite], deg['count'][0][finite].astype(np.int64) << 32)
+    # var(c) = 0 in the frames without events: no coefficient, and the unit of gmax = 0
+    assert deg['coef'][0] != 0 and not deg['coef'][1:].any() and (deg['unit'][1:] == 2.0 ** 40).all()
+    # more frames than lanes: frames of every round of the closing wave have contrast and a gradient
+    many = cases()['2x3_F130_n1040']
+    fwd = L.contrast_fwd_host(*cc.args_of(many))
+    grad, _ = L.contrast_bwd_host(*cc.args_of(many), fwd)
+    assert len(many['fs']) == 130 and many['x'].size == 1040
+    for lo, hi in ((0, 64), (64, 128), (128, 130)):
+        assert fwd['coef'][lo:hi].any() and grad[lo:hi].any(), (lo, hi)
 
 
 def test_seed_and_weight_reach_the_closing_kernel():
@@ -191,7 +208,7 @@ def test_the_term_reaches_the_finest_flow_by_one_add(training_runs):
              flow=on['flow'])
     c = {k: v.cpu().numpy() for k, v in c.items()}
     c['shape'] = (H, W)
-    q, count, rows, term, (grad,) = device_run(c, 1.0, WEIGHT, fills=(0xAA,))
+    q, count, rows, term, (grad,), _, _ = device_run(c, 1.0, WEIGHT, fills=(0xAA,))
     assert count.sum() == 2 * EVENTS and np.abs(grad).max() > 0
     want = plain['flow_grad'].cpu().numpy() + grad              # one float32 add per element
     assert want.dtype == np.float32 and on['flow_grad'].cpu().numpy().tobytes() == want.tobytes()

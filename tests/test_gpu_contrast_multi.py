@@ -1,5 +1,5 @@
-"""csrc/contrast_multi.hip on the device against the numpy restatement of
-docs/CONTRAST_SPEC.md sections 11-14 (loss.contrast_multi_fwd_host /
+"""csrc/contrast.hip with its options on the device against the numpy
+restatement of docs/CONTRAST_SPEC.md sections 11-14 (loss.contrast_multi_fwd_host /
 contrast_multi_bwd_host), byte for byte: the images, the counts, the
 statistics rows, the image records and frame units in the workspace, the term
 and the flow gradient on every case of tests/contrast_multi_cases.py and on a

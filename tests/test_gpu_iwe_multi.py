@@ -1,5 +1,5 @@
-"""csrc/iwe_multi.hip on the device against the numpy float32 restatement
-(eval.iwe_splat_multi_host, docs/IWE_SPEC.md sections 8-13), byte for byte: on
+"""csrc/iwe.hip with its options on the device against the numpy float32
+restatement (eval.iwe_splat_multi_host, docs/IWE_SPEC.md sections 8-13), byte for byte: on
 every case of tests/iwe_cases.py with a polarity column, at five masks and both
 polarity settings, in any order of the events, in a batch or frame by frame,
 from filled buffers, beyond one pass of the capped grid; against the entry

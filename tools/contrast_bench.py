@@ -13,10 +13,11 @@ per sample.
   step    the eager training step (Ranger, f32, process_minibatch +
           unit_backward + step) with contrast_weight 0 against --weight, in
           alternating blocks of one run; the median block of each.
-  --multi only this: the existing calls, dvsof_contrast_multi_fwd / _bwd at
-          mask = start without polarity and at all three references with
+  --multi only this: dvsof_contrast_fwd / _bwd, dvsof_contrast_multi_fwd /
+          _bwd at mask = start without polarity (the same kernels through
+          the general entry point) and at all three references with
           polarity, in alternating blocks of one run
-          (profiles/contrast_multi/README.md).
+          (profiles/contrast_multi/README.md, profiles/event_images/README.md).
 """
 import argparse
 import json
@@ -105,10 +106,11 @@ def calls_alone(rounds=7, reps=40, seed=0):
 
 
 def calls_multi(rounds=9, reps=40, seed=0):
-    """dvsof_contrast_fwd / _bwd (the existing calls), dvsof_contrast_multi_fwd
-    / _bwd at mask = start without polarity (the same work by the new kernels)
-    and at all three references with polarity (six images per frame), the six
-    taking turns block by block within one run."""
+    """dvsof_contrast_fwd / _bwd (the entry points without options),
+    dvsof_contrast_multi_fwd / _bwd at mask = start without polarity (the same
+    kernels through the general entry point) and at all three references with
+    polarity (six images per frame), the six taking turns block by block
+    within one run."""
     dev, lib, stream = 'cuda', _lib.lib(), _lib.stream()
     batch = synthetic.make_batch(seed, B, H, W, EVENTS)
     ev = batch['events']
@@ -137,8 +139,8 @@ def calls_multi(rounds=9, reps=40, seed=0):
     old = buffers(F, lib.dvsof_contrast_workspace_bytes(F, H, W))
     cols = [d[k].data_ptr() for k in ('x', 'y', 't', 's')] + [n] + tables + [F, H, W]
     calls = {
-        'parent_fwd': lambda: check(lib.dvsof_contrast_fwd(*cols, *outs(old))),
-        'parent_bwd': lambda: check(lib.dvsof_contrast_bwd(*cols, old['q'].data_ptr(), old['ws'].data_ptr(),
+        'default_fwd': lambda: check(lib.dvsof_contrast_fwd(*cols, *outs(old))),
+        'default_bwd': lambda: check(lib.dvsof_contrast_bwd(*cols, old['q'].data_ptr(), old['ws'].data_ptr(),
                                                            old['need'], seed_t.data_ptr(), 0.25, grad.data_ptr(),
                                                            stream))}
     held = {}
@@ -155,9 +157,9 @@ def calls_multi(rounds=9, reps=40, seed=0):
             fn()
         grads[k] = grad.clone()
     torch.cuda.synchronize()
-    # mask = start without polarity is the existing term, bit for bit
+    # mask = start without polarity is the term of the entry points without options, bit for bit
     assert torch.equal(old['q'], held['start']['q']) and torch.equal(old['term'], held['start']['term'])
-    assert torch.equal(grads['parent_bwd'], grads['start_bwd'])
+    assert torch.equal(grads['default_bwd'], grads['start_bwd'])
     blocks = {k: [] for k in calls}
     for _ in range(rounds):
         for k, fn in calls.items():
@@ -218,7 +220,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--multi', action='store_true',
                     help='only the leg of the entry points with several references and the polarities '
-                         'apart against the existing ones (profiles/contrast_multi/README.md)')
+                         'apart beside those without options (profiles/contrast_multi/README.md)')
     args = ap.parse_args()
     if args.multi:
         print(json.dumps(dict(shape=dict(B=B, H=H, W=W, events_per_sample=EVENTS), multi=calls_multi())))

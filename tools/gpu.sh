@@ -27,8 +27,9 @@
 #                                     dvsof_contrast_bwd alone at batch 8, 256x256, 65 536 events per sample; the eager
 #                                     training step with --contrast-weight 0 against 0.25 in alternating blocks
 #   contrast-multi [contrast_bench.py args]  its --multi leg: dvsof_contrast_fwd / _bwd, dvsof_contrast_multi_fwd /
-#                                     _bwd at mask = start without polarity and at all three references with
-#                                     polarity, in alternating blocks of one run (profiles/contrast_multi/README.md)
+#                                     _bwd at mask = start without polarity (the same kernels of csrc/contrast.hip
+#                                     through the general entry point) and at all three references with polarity, in
+#                                     alternating blocks of one run (profiles/contrast_multi/README.md)
 #   frameless [frameless_bench.py args]  the loss that reads no frame (tools/frameless_bench.py): dvsof_loss_frameless
 #                                     against dvsof_loss_fused_pyramid on zero frames with photometric weight 0 at
 #                                     batch 8, 256x256, four scales, and one eager Ranger step of a frameless batch
