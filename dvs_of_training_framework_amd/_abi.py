@@ -38,6 +38,9 @@ CONTRAST_MULTI_PATH = HEADER_PATH.with_name('dvsof_contrast_multi.h')
 IWE_MULTI_PATH = HEADER_PATH.with_name('dvsof_iwe_multi.h')
 # And the loss of a run without frames (LOSS_FRAMELESS_FUNCTIONS)
 LOSS_FRAMELESS_PATH = HEADER_PATH.with_name('dvsof_loss_frameless.h')
+# And the contrast term on every flow scale (CONTRAST_PYRAMID_FUNCTIONS), the one extension with
+# structs of its own (CONTRAST_PYRAMID_STRUCTS: the level table, passed by value)
+CONTRAST_PYRAMID_PATH = HEADER_PATH.with_name('dvsof_contrast_pyramid.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -198,3 +201,19 @@ IWE_MULTI_FUNCTIONS = _read_extension(IWE_MULTI_PATH, set(FUNCTIONS) | set(EXTEN
                                      | set(CONTRAST_MULTI_FUNCTIONS))
 LOSS_FRAMELESS_FUNCTIONS = _read_extension(LOSS_FRAMELESS_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS)
                                           | set(CONTRAST_MULTI_FUNCTIONS) | set(IWE_MULTI_FUNCTIONS))
+
+
+def _read_struct_extension(path, taken):
+    """An extension header that also declares structs of its own (a table passed by value):
+    -> (functions, {name: Structure} of the new structs).  STRUCTS stays that of dvsof.h."""
+    ext = Abi(path.read_text(), base=_header, name=path.name)
+    clash = set(ext.functions) & set(taken)
+    if clash or ext.constants or not set(STRUCTS) <= set(ext.structs):
+        raise AbiError(f'{path.name}: an extension header declares new functions and structs only '
+                       f'({sorted(clash) or "constants found"})')
+    return ext.functions, {k: v for k, v in ext.structs.items() if k not in STRUCTS}
+
+
+CONTRAST_PYRAMID_FUNCTIONS, CONTRAST_PYRAMID_STRUCTS = _read_struct_extension(
+    CONTRAST_PYRAMID_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
+    | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS))

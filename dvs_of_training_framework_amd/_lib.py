@@ -10,7 +10,9 @@ _abi.CONTRAST_MULTI_PATH: include/dvsof_contrast_multi.h, recorded in
 tests/golden/abi_signatures_contrast_multi.json; _abi.IWE_MULTI_PATH:
 include/dvsof_iwe_multi.h, recorded in tests/golden/abi_signatures_iwe_multi.json;
 _abi.LOSS_FRAMELESS_PATH: include/dvsof_loss_frameless.h, recorded in
-tests/golden/abi_signatures_loss_frameless.json).
+tests/golden/abi_signatures_loss_frameless.json; _abi.CONTRAST_PYRAMID_PATH:
+include/dvsof_contrast_pyramid.h, recorded in
+tests/golden/abi_signatures_contrast_pyramid.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -41,6 +43,10 @@ _CONTRAST_MULTI_SIGNATURES = _abi.CONTRAST_MULTI_FUNCTIONS
 _IWE_MULTI_SIGNATURES = _abi.IWE_MULTI_FUNCTIONS
 # and of include/dvsof_loss_frameless.h, likewise
 _LOSS_FRAMELESS_SIGNATURES = _abi.LOSS_FRAMELESS_FUNCTIONS
+# and of include/dvsof_contrast_pyramid.h, with the level table it passes by value
+_CONTRAST_PYRAMID_SIGNATURES = _abi.CONTRAST_PYRAMID_FUNCTIONS
+ContrastLevel = _abi.CONTRAST_PYRAMID_STRUCTS['dvsof_contrast_level_t']
+ContrastLevels = _abi.CONTRAST_PYRAMID_STRUCTS['dvsof_contrast_levels_t']
 
 _lib = None
 LOADED_STAT = None
@@ -81,6 +87,11 @@ def declared_loss_frameless_symbols():
     return _declared_in((_abi.LOSS_FRAMELESS_PATH,))
 
 
+def declared_contrast_pyramid_symbols():
+    """Names of all entry points include/dvsof_contrast_pyramid.h declares."""
+    return _declared_in((_abi.CONTRAST_PYRAMID_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -95,7 +106,8 @@ def lib():
         global LOADED_STAT      # the file these code objects came from (_audit.py)
         LOADED_STAT = (st.st_ino, st.st_size, st.st_mtime_ns)
         for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES,
-                                  **_IWE_MULTI_SIGNATURES, **_LOSS_FRAMELESS_SIGNATURES}.items():
+                                  **_IWE_MULTI_SIGNATURES, **_LOSS_FRAMELESS_SIGNATURES,
+                                  **_CONTRAST_PYRAMID_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

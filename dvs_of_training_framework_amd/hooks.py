@@ -86,13 +86,16 @@ class ValidationHook:
     it (``model_left_as_found``)."""
 
     def __init__(self, model, device, loader, logger, losses, weights, is_raw,
-                 contrast_weight=0.0, contrast_references=('start',), contrast_polarity=False):
+                 contrast_weight=0.0, contrast_references=('start',), contrast_polarity=False,
+                 contrast_scales='finest'):
         self.model, self.device, self.loader = model, device, loader
         self.logger, self.losses = logger, losses
         self.weights = deepcopy(weights)
         self.is_raw = is_raw
         self.extra = {'contrast_weight': contrast_weight, 'contrast_references': tuple(contrast_references),
                       'contrast_polarity': bool(contrast_polarity)} if contrast_weight else {}
+        if contrast_weight and contrast_scales != 'finest':
+            self.extra['contrast_scales'] = contrast_scales
 
     def __call__(self, steps, samples):
         with model_left_as_found(self.model):

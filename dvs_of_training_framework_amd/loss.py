@@ -554,6 +554,170 @@ class _Contrast(torch.autograd.Function):
         return (grad,) + (None,) * 10
 
 
+# The term on every flow scale (csrc/contrast.hip, CONTRAST_SPEC sections 19-23)
+CONTRAST_SCALES = ('finest', 'all')
+CONTRAST_MAX_LEVELS = 8
+CONTRAST_MAX_SHIFT = 15
+
+
+def contrast_level_shift(shape, level_shape):
+    """The shift s of a level of shape ``level_shape`` under the frame
+    ``shape`` the event coordinates live in: the smallest s in [0, 15] with
+    h_k == ceil(h / 2^s) and w_k == ceil(w / 2^s), the chain of stride-2
+    halvings.  An event at x < w sits at level column x >> s < w_k.  A level
+    with no such s is refused."""
+    (h, w), (hk, wk) = (int(v) for v in shape), (int(v) for v in level_shape)
+    for s in range(CONTRAST_MAX_SHIFT + 1):
+        if hk == -(-h // 2 ** s) and wk == -(-w // 2 ** s):
+            return s
+    raise ValueError(f'a level of shape {(hk, wk)} is no halving of the frame {(h, w)}: '
+                     f'no shift s in [0, {CONTRAST_MAX_SHIFT}] gives ceil(h / 2^s), ceil(w / 2^s)')
+
+
+def contrast_level_columns(x, y, shape, shift):
+    """The columns x, y quantised to a level's grid: x >> shift, y >> shift
+    for an event inside the full-resolution frame, -1 for one outside it (the
+    inside test is made before the shift)."""
+    x, y = np.asarray(x, np.int64).reshape(-1), np.asarray(y, np.int64).reshape(-1)
+    h, w = shape
+    inside = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+    return np.where(inside, x >> shift, -1), np.where(inside, y >> shift, -1)
+
+
+def contrast_level_weights(weight, K):
+    """One float32 weight per level: float32(weight) / float32(K), one
+    division (the reference's mean over scales)."""
+    return [_F32(weight) / _F32(K)] * K
+
+
+def contrast_pyramid_fwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flows, shape, weights=None,
+                              references=('start',), polarity=False):
+    """CONTRAST_SPEC sections 19-21 on the host: what
+    ``dvsof_contrast_pyramid_fwd`` is pinned to, byte for byte.  flows: one
+    float32 [F,2,h_k,w_k] per level; shape: the frame (h, w) of the event
+    coordinates; weights: one per level (default ``contrast_level_weights(1,
+    K)``).  Per level ``contrast_multi_fwd_host`` on the quantised columns,
+    then the combination -> dict: levels (the K dicts of that function),
+    shifts, weights float32 [K], terms float32 [K] (unweighted), terms64,
+    value float32."""
+    K = len(flows)
+    if not 1 <= K <= CONTRAST_MAX_LEVELS:
+        raise ValueError(f'{K} levels: the level table holds 1 to {CONTRAST_MAX_LEVELS}')
+    flows = [np.asarray(f, _F32) for f in flows]
+    shifts = [contrast_level_shift(shape, f.shape[-2:]) for f in flows]
+    weights = np.asarray(contrast_level_weights(1.0, K) if weights is None else weights, _F32)
+    assert weights.shape == (K,)
+    levels = []
+    for flow, s in zip(flows, shifts):
+        xs, ys = contrast_level_columns(x, y, shape, s)
+        levels.append(contrast_multi_fwd_host(xs, ys, t, p, sample_index, frame_ts, frame_sample, flow,
+                                              references, polarity))
+    terms64 = np.zeros(K, np.float64)
+    total = np.float64(0)
+    with np.errstate(all='ignore'):
+        for k, lev in enumerate(levels):        # in level order
+            s = np.float64(0)
+            for v in lev['image_term']:         # in image order
+                s = s + v
+            terms64[k] = s / np.float64(len(lev['image_term']))
+            total = total + np.float64(weights[k]) * terms64[k]
+        return dict(levels=levels, shifts=shifts, weights=weights, terms=terms64.astype(_F32), terms64=terms64,
+                    value=_F32(total), shape=tuple(int(v) for v in shape))
+
+
+def contrast_pyramid_bwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flows, fwd, seed=1.0):
+    """CONTRAST_SPEC section 22 on the host: what ``dvsof_contrast_pyramid_bwd``
+    is pinned to.  fwd: the dict of ``contrast_pyramid_fwd_host`` for the same
+    input.  -> one (grad_flow_k float32 [F,2,h_k,w_k] = seed * weight_k *
+    d term_k / d flow_k, sums int64 [F,2,h_k,w_k]) per level."""
+    out = []
+    for flow, s, lev, weight in zip(flows, fwd['shifts'], fwd['levels'], fwd['weights']):
+        xs, ys = contrast_level_columns(x, y, fwd['shape'], s)
+        out.append(contrast_multi_bwd_host(xs, ys, t, p, sample_index, frame_ts, frame_sample, flow, lev,
+                                           seed=seed, weight=weight))
+    return out
+
+
+def contrast_level_table(shape, level_shapes, F, M, weights, flows=None, grads=None):
+    """The by-value level table of include/dvsof_contrast_pyramid.h with the
+    packed offsets: shapes, shifts (``contrast_level_shift``: ValueError for a
+    level that is no halving), weights and, where given, the addresses of the
+    flows and of the gradient buffers."""
+    K = len(level_shapes)
+    if not 1 <= K <= CONTRAST_MAX_LEVELS:
+        raise ValueError(f'{K} levels: the level table holds 1 to {CONTRAST_MAX_LEVELS}')
+    table = _lib.ContrastLevels()
+    table.K = K
+    pixels = 0
+    for k, (hk, wk) in enumerate(level_shapes):
+        lev = table.level[k]
+        lev.h, lev.w, lev.shift = int(hk), int(wk), contrast_level_shift(shape, (hk, wk))
+        lev.weight = float(weights[k])
+        lev.image_offset, lev.row_offset, lev.sums_offset = M * pixels, k * M, 2 * F * pixels
+        lev.flow = flows[k] if flows is not None else None
+        lev.grad_flow = grads[k] if grads is not None else None
+        pixels += int(hk) * int(wk)
+    return table
+
+
+class _ContrastPyramid(torch.autograd.Function):
+    """(sum_k weight_k term_k, terms [K]) of all flows; the gradient of the
+    first enters every flow (dvsof_contrast_pyramid_fwd /
+    dvsof_contrast_pyramid_bwd: one splat and one backward for all levels).
+    The weights are applied inside the kernels."""
+
+    @staticmethod
+    def forward(ctx, x, y, t, p, sample_index, frame_ts, frame_sample, shape, weights, mask, polarity, *flows):
+        from .eval import IWE_RESULT_DTYPE
+        dev = flows[0].device
+        flows = tuple(f.detach().contiguous().float() for f in flows)
+        K, F = len(flows), flows[0].shape[0]
+        assert all(f.shape[0] == F and f.shape[1] == 2 for f in flows)
+        lib = _lib.lib()
+        M = F * bin(mask).count('1') * (2 if polarity else 1)
+        shapes = [tuple(f.shape[-2:]) for f in flows]
+        table = contrast_level_table(shape, shapes, F, M, weights, [f.data_ptr() for f in flows])
+        terms = torch.zeros(K, dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty(K, dtype=torch.float32, device=dev)
+        value = torch.zeros((), dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+        result = torch.empty(K * M, IWE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        h, w = (int(v) for v in shape)
+        nbytes = lib.dvsof_contrast_pyramid_workspace_bytes(F, mask, int(polarity), h, w, table)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
+        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
+        pol = p.contiguous() if polarity else None
+        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
+        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flows[0].shape, frame_ts.shape)
+        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
+        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
+        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
+        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
+                                                        tables[0].data_ptr(), tables[1].data_ptr(),
+                                                        F, h, w, mask, int(polarity)])
+        _lib.check(lib.dvsof_contrast_pyramid_fwd(
+            *ctx.args, table, result.data_ptr(), terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes,
+            _lib.stream()), 'dvsof_contrast_pyramid_fwd')
+        ctx.held = (cols, pol, tables, flows, ws, nbytes, table)
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)
+        return value, terms
+
+    @staticmethod
+    def backward(ctx, g_value, _g_terms):
+        flows, ws, nbytes, table = ctx.held[3:]
+        if g_value is None:
+            return (None,) * (11 + len(flows))
+        grads = tuple(torch.empty_like(f) for f in flows)
+        for k, g in enumerate(grads):
+            table.level[k].grad_flow = g.data_ptr()
+        seed = g_value.contiguous().float()
+        _lib.check(_lib.lib().dvsof_contrast_pyramid_bwd(
+            *ctx.args, table, ws.data_ptr(), nbytes, seed.data_ptr(), _lib.stream()),
+            'dvsof_contrast_pyramid_bwd')
+        return (None,) * 11 + grads
+
+
 class Loss:
     """Single-scale evaluator (reference utils/loss.py:38-171)."""
 
@@ -684,7 +848,7 @@ class Losses:
         return _FramelessLoss.apply(weights, loss_scale, *flows)
 
     def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None,
-                 references=('start',), polarity=False):
+                 references=('start',), polarity=False, scales='finest'):
         """The contrast-maximisation term of the finest flow ``flows[-1]``
         (docs/CONTRAST_SPEC.md): the mean over the predictions of
         1 - var(image of warped events) / var(count image), negative where the
@@ -699,7 +863,20 @@ class Losses:
         events in images of their own (``events['polarity']``; an event of
         polarity 0 takes no part).  The term is the mean over all images
         (CONTRAST_SPEC sections 11-15).  The defaults are the term as it was:
-        the same kernels, through the general entry point."""
+        the same kernels, through the general entry point.
+
+        scales='all': the term of every flow on the events quantised to that
+        flow's grid (CONTRAST_SPEC sections 19-23), one splat and one backward
+        for all levels; each level weighs float32(weight) / float32(K), the
+        mean over the scales.  -> the 0-dim weighted sum, differentiable with
+        respect to every flow (without a ``weight``: the mean of the levels'
+        terms); with a ``weight`` -> (that, terms [K]), the levels' unweighted
+        terms detached for logging.  'finest', the default, is the call above
+        and constructs nothing else."""
+        if scales != 'finest':
+            if scales not in CONTRAST_SCALES:
+                raise ValueError(f'unknown contrast scales "{scales}": one of {", ".join(CONTRAST_SCALES)}')
+            return self._contrast_all(flows, flow_ts, flow_sample_idx, events, weight, references, polarity)
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the contrast term of scale {self.shapes[-1]}'
@@ -712,6 +889,20 @@ class Losses:
         value, term = _Contrast.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
                                       bool(polarity))
         return value if weight is None else (value, term)
+
+    def _contrast_all(self, flows, flow_ts, flow_sample_idx, events, weight, references, polarity):
+        self._check_flows(flows)
+        cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
+        _lib.require_cuda(flow_ts, flow_sample_idx, *flows, *cols)
+        mask = contrast_reference_mask(references)
+        for shape in self.shapes:                       # a level that is no halving is refused here
+            contrast_level_shift(self.shapes[-1], shape)
+        weights = contrast_level_weights(1.0 if weight is None else weight, len(flows))
+        pol = events['polarity'] if polarity else None
+        _lib.require_cuda(pol)
+        value, terms = _ContrastPyramid.apply(*cols[:3], pol, cols[3], flow_ts, flow_sample_idx,
+                                              self.shapes[-1], weights, mask, bool(polarity), *flows)
+        return value if weight is None else (value, terms)
 
 
 def init_losses(shape, batch_size, model, device, sequence_length,

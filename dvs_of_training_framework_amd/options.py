@@ -3,6 +3,7 @@ reference (utils/options.py:10-347) so existing launch scripts keep working;
 ``--world-size`` / ``--synthetic*`` are additions for the MI355X build.
 The reference module itself cannot be imported here (it imports the absent
 ``mish`` submodule at :7)."""
+import argparse
 import os
 from pathlib import Path
 
@@ -317,6 +318,14 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         action='store_true',
                         help='accumulate ON and OFF events in images of their own in the '
                              'contrast term.  Needs --contrast-weight')
+    parser.add_argument('--contrast-scales', dest='contrast_scales',
+                        default=argparse.SUPPRESS, choices=('finest', 'all'),
+                        help='the flow scales the contrast term is taken on: finest (the '
+                             'default) supervises the finest flow alone; all takes the term of '
+                             'every flow head on the events quantised to that head\'s grid, each '
+                             'level weighing --contrast-weight / K, and logs Train/contrast/<tag> '
+                             'per level beside the mean (docs/CONTRAST_SPEC.md sections 19-23).  '
+                             'Needs --contrast-weight')
     parser.add_argument('--recording', dest='recording', default=None, type=Path,
                         help='train from ONE event-only recording kept on the device: a '
                              '.npz or .hdf5 file with the arrays x, y, t, p (sorted by t) and '
@@ -426,6 +435,8 @@ def validate_contrast_args(args):
             raise SystemExit('--contrast-references needs a positive --contrast-weight')
         if args.contrast_polarity:
             raise SystemExit('--contrast-polarity needs a positive --contrast-weight')
+        if getattr(args, 'contrast_scales', 'finest') != 'finest':     # absent unless given
+            raise SystemExit('--contrast-scales needs a positive --contrast-weight')
     if weight > 0 and getattr(args, 'ev_images', False):
         raise SystemExit('--contrast-weight cannot be combined with --ev_images: the term is '
                          'computed from the raw events on the device, and a batch of '

@@ -56,10 +56,12 @@ class _TermsAndContrast(tuple):
         return self
 
 
-def _contrast_options(references, polarity):
+def _contrast_options(references, polarity, scales='finest'):
     """The keywords of ``Losses.contrast`` that differ from its defaults, so
     that a run without them makes the call it always made."""
     out = {}
+    if scales != 'finest':
+        out['scales'] = scales
     if tuple(references) != ('start',):
         out['references'] = tuple(references)
     if polarity:
@@ -67,19 +69,20 @@ def _contrast_options(references, polarity):
     return out
 
 
-def _contrast_keywords(weight, references, polarity):
+def _contrast_keywords(weight, references, polarity, scales='finest'):
     """What a call down the chain gets: nothing at weight 0, and the options
     only where they differ from the defaults."""
     if not weight:
         return {}
     return dict({'contrast_weight': weight},
-                **{'contrast_' + k: v for k, v in _contrast_options(references, polarity).items()})
+                **{'contrast_' + k: v for k, v in _contrast_options(references, polarity, scales).items()})
 
 
 def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   timestamps, sample_idx, features, weights=[0.5, 1, 1],
                   frame_indices=None, contrast_weight=0.0, events=None,
-                  contrast_references=('start',), contrast_polarity=False):
+                  contrast_references=('start',), contrast_polarity=False,
+                  contrast_scales='finest'):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
     that has ``fused`` and flows that need gradients the value and the flow
     gradients come out of one sweep (loss.Losses.fused).
@@ -91,6 +94,10 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     ``events`` is not looked at.  contrast_references, contrast_polarity: the
     reference times of the term and whether ON and OFF events are kept apart
     (``Losses.contrast``); the defaults are the term of one image per frame.
+    contrast_scales='all': the term of every flow, each level weighing
+    contrast_weight / K (CONTRAST_SPEC sections 19-23); ``.contrast`` is then
+    the [K] tensor of the levels' terms.  'finest', the default, is the call
+    as it was.
 
     images=None with an evaluator that has ``frameless`` (loss.Losses): a
     frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
@@ -131,7 +138,7 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                          '(is_raw=True); preprocessed voxel grids carry none')
     value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events,
                                      weight=contrast_weight, **_contrast_options(
-                                         contrast_references, contrast_polarity))
+                                         contrast_references, contrast_polarity, contrast_scales))
     return loss + value, _TermsAndContrast(terms, term)
 
 
@@ -149,13 +156,25 @@ class TermReadback:
         self.n_scales = len(terms[0]) if self.n_terms else 0
         self._table = None
         self._contrast = getattr(terms, 'contrast', None)
+        self._contrast_levels = None
 
     def contrast(self):
         """The contrast-maximisation term as a host float (one small copy),
-        None when the loss has none."""
+        None when the loss has none; with the term on every scale the mean of
+        the levels' terms."""
         if isinstance(self._contrast, torch.Tensor):
-            self._contrast = float(self._contrast)
+            if self._contrast.dim() == 1:
+                self._contrast_levels = self._contrast.tolist()
+                self._contrast = sum(self._contrast_levels) / len(self._contrast_levels)
+            else:
+                self._contrast = float(self._contrast)
         return self._contrast
+
+    def contrast_levels(self):
+        """The levels' terms as host floats, coarsest first; None unless the
+        term is taken on every scale."""
+        self.contrast()
+        return self._contrast_levels
 
     def host(self):
         if self._table is None:
@@ -213,13 +232,14 @@ def _to_device(batch, device, is_raw):
 
 def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       weights, return_prediction=False, contrast_weight=0.0,
-                      contrast_references=('start',), contrast_polarity=False):
+                      contrast_references=('start',), contrast_polarity=False,
+                      contrast_scales='finest'):
     """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs]).
     contrast_weight > 0 (raw events only), contrast_references,
-    contrast_polarity: see ``combined_loss``.  A frameless batch
+    contrast_polarity, contrast_scales: see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
     the frame size from ``'shape'`` and the loss that reads no frame."""
-    contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity)
+    contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales)
     if contrast and not is_raw:
         raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
     with _timed(timers, 'batch2gpu'):
@@ -273,6 +293,7 @@ class ScaleSums:
         self.per_term = None        # [term][scale]
         self.loss = 0.0
         self.contrast = None        # sum of the contrast-maximisation term, if the loss has one
+        self.contrast_levels = None  # and per level, if it is taken on every scale
         self.tags = None
 
     def add(self, loss, readback, tags):
@@ -286,6 +307,9 @@ class ScaleSums:
         extra = readback.contrast() if hasattr(readback, 'contrast') else None
         if extra is not None:
             self.contrast = (self.contrast or 0.0) + extra
+            levels = readback.contrast_levels() if hasattr(readback, 'contrast_levels') else None
+            if levels is not None:
+                self.contrast_levels = [a + b for a, b in zip(self.contrast_levels or [0.0] * len(levels), levels)]
         self.tags = list(tags)
 
     def write(self, logger, x, divisor, families):
@@ -416,7 +440,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           log_every: int = 1, capture=False, guard=None,
           max_skipped_steps: int = 32, guard_agreement_every: int = 0,
           contrast_weight: float = 0.0, contrast_references=('start',),
-          contrast_polarity: bool = False):
+          contrast_polarity: bool = False, contrast_scales: str = 'finest'):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
     batches above ``max_events_per_batch`` events are skipped and not counted,
@@ -454,6 +478,10 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     contrast_references, contrast_polarity:  the reference times of that term
                ('start', 'middle', 'end') and whether ON and OFF events are
                accumulated apart (``loss.Losses.contrast``)
+    contrast_scales:  'all' takes that term on every flow scale, each level
+               weighing contrast_weight / K; ``Train/contrast`` is then the
+               mean of the levels' terms and ``Train/contrast/<tag>`` each
+               level's.  'finest' (the default): the finest flow alone
 
     A loader of frameless batches (sequence.EventWindowLoader: is_raw=True,
     ``'images': None``) needs contrast_weight > 0; the photometric rows are
@@ -505,7 +533,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
         if not replayed:
             loss, terms, tags = process_minibatch(
                 model, batch, timers, device, is_raw, evaluator, weights,
-                **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity))
+                **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
+                                     contrast_scales))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass
@@ -538,6 +567,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                     if sums.contrast is not None:
                         logger.add_scalar('Train/contrast',
                                           sums.contrast / accumulation_steps, x)
+                        for tag, level in zip(sums.tags, sums.contrast_levels or ()):
+                            logger.add_scalar(f'Train/contrast/{tag}',
+                                              level / accumulation_steps, x)
                     for g, group in enumerate(optimizer.param_groups):
                         logger.add_scalar(f'General/learning rate/{g}',
                                           group['lr'], x)
@@ -572,11 +604,13 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
 
 def validate(model, device, loader, samples_passed, logger, evaluator,
              weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
-             contrast_references=('start',), contrast_polarity=False):
+             contrast_references=('start',), contrast_polarity=False,
+             contrast_scales='finest'):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
     the loss holds the contrast-maximisation term (of those reference times
-    and polarity setting), written as ``Validation/contrast``."""
+    and polarity setting), written as ``Validation/contrast``; with
+    contrast_scales='all' that is the mean of the levels' terms."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -584,7 +618,8 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
         for batch in loader:
             loss, terms, tags = process_minibatch(
                 model, batch, quiet, device, is_raw, evaluator, weights,
-                **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity))
+                **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
+                                     contrast_scales))
             sums.add(loss, terms, tags)
     logger.add_scalar('General/Validation loss', sums.loss / n_batches,
                       samples_passed)

@@ -30,6 +30,11 @@
 #                                     _bwd at mask = start without polarity (the same kernels of csrc/contrast.hip
 #                                     through the general entry point) and at all three references with polarity, in
 #                                     alternating blocks of one run (profiles/contrast_multi/README.md)
+#   contrast_pyramid [contrast_pyramid_bench.py args]  the term on every flow scale (tools/contrast_pyramid_bench.py):
+#                                     dvsof_contrast_pyramid_fwd / _bwd against four calls of dvsof_contrast_multi_fwd /
+#                                     _bwd on shifted columns at batch 8, 256x256, four levels, what a level costs alone,
+#                                     and one eager Ranger step of a frameless batch with --contrast-scales all against
+#                                     finest, in alternating blocks of one run (profiles/contrast_pyramid/README.md)
 #   frameless [frameless_bench.py args]  the loss that reads no frame (tools/frameless_bench.py): dvsof_loss_frameless
 #                                     against dvsof_loss_fused_pyramid on zero frames with photometric weight 0 at
 #                                     batch 8, 256x256, four scales, and one eager Ranger step of a frameless batch
@@ -103,6 +108,9 @@ contrast)
 contrast-multi)
   timeout -k 10 420 env "${envs[@]}" python tools/contrast_bench.py --multi "$@" > $O/contrast_multi.json 2> $O/contrast_multi.err
   echo "contrast-multi rc=$?"; cut -c1-2600 $O/contrast_multi.json; tail -3 $O/contrast_multi.err ;;
+contrast_pyramid)
+  timeout -k 10 540 env "${envs[@]}" python tools/contrast_pyramid_bench.py "$@" > $O/contrast_pyramid.json 2> $O/contrast_pyramid.err
+  echo "contrast_pyramid rc=$?"; cut -c1-3600 $O/contrast_pyramid.json; tail -3 $O/contrast_pyramid.err ;;
 frameless)
   timeout -k 10 420 env "${envs[@]}" python tools/frameless_bench.py "$@" > $O/frameless.json 2> $O/frameless.err
   echo "frameless rc=$?"; cut -c1-2600 $O/frameless.json; tail -3 $O/frameless.err ;;

@@ -495,7 +495,8 @@ def main(argv=None):
             args.loss_weights, args.is_raw,
             **({'contrast_weight': args.contrast_weight,
                 'contrast_references': getattr(args, 'contrast_references', ('start',)),
-                'contrast_polarity': getattr(args, 'contrast_polarity', False)}
+                'contrast_polarity': getattr(args, 'contrast_polarity', False),
+                'contrast_scales': getattr(args, 'contrast_scales', 'finest')}
                if getattr(args, 'contrast_weight', 0.0) else {}))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
     elif not args.skip_validation:
@@ -524,7 +525,8 @@ def main(argv=None):
                   guard_agreement_every=args.checkpointing_interval,
                   contrast_weight=getattr(args, 'contrast_weight', 0.0),
                   contrast_references=getattr(args, 'contrast_references', ('start',)),
-                  contrast_polarity=getattr(args, 'contrast_polarity', False))
+                  contrast_polarity=getattr(args, 'contrast_polarity', False),
+                  contrast_scales=getattr(args, 'contrast_scales', 'finest'))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
