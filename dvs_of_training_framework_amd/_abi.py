@@ -41,6 +41,8 @@ LOSS_FRAMELESS_PATH = HEADER_PATH.with_name('dvsof_loss_frameless.h')
 # And the contrast term on every flow scale (CONTRAST_PYRAMID_FUNCTIONS), the one extension with
 # structs of its own (CONTRAST_PYRAMID_STRUCTS: the level table, passed by value)
 CONTRAST_PYRAMID_PATH = HEADER_PATH.with_name('dvsof_contrast_pyramid.h')
+# And the average-timestamp term (AVG_TIMESTAMP_FUNCTIONS), functions only
+AVG_TIMESTAMP_PATH = HEADER_PATH.with_name('dvsof_avg_timestamp.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -217,3 +219,6 @@ def _read_struct_extension(path, taken):
 CONTRAST_PYRAMID_FUNCTIONS, CONTRAST_PYRAMID_STRUCTS = _read_struct_extension(
     CONTRAST_PYRAMID_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
     | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS))
+AVG_TIMESTAMP_FUNCTIONS = _read_extension(
+    AVG_TIMESTAMP_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
+    | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS))

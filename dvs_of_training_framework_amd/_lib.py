@@ -12,7 +12,9 @@ include/dvsof_iwe_multi.h, recorded in tests/golden/abi_signatures_iwe_multi.jso
 _abi.LOSS_FRAMELESS_PATH: include/dvsof_loss_frameless.h, recorded in
 tests/golden/abi_signatures_loss_frameless.json; _abi.CONTRAST_PYRAMID_PATH:
 include/dvsof_contrast_pyramid.h, recorded in
-tests/golden/abi_signatures_contrast_pyramid.json).
+tests/golden/abi_signatures_contrast_pyramid.json; _abi.AVG_TIMESTAMP_PATH:
+include/dvsof_avg_timestamp.h, recorded in
+tests/golden/abi_signatures_avg_timestamp.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -47,6 +49,8 @@ _LOSS_FRAMELESS_SIGNATURES = _abi.LOSS_FRAMELESS_FUNCTIONS
 _CONTRAST_PYRAMID_SIGNATURES = _abi.CONTRAST_PYRAMID_FUNCTIONS
 ContrastLevel = _abi.CONTRAST_PYRAMID_STRUCTS['dvsof_contrast_level_t']
 ContrastLevels = _abi.CONTRAST_PYRAMID_STRUCTS['dvsof_contrast_levels_t']
+# and of include/dvsof_avg_timestamp.h, functions only
+_AVG_TIMESTAMP_SIGNATURES = _abi.AVG_TIMESTAMP_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -92,6 +96,11 @@ def declared_contrast_pyramid_symbols():
     return _declared_in((_abi.CONTRAST_PYRAMID_PATH,))
 
 
+def declared_avg_timestamp_symbols():
+    """Names of all entry points include/dvsof_avg_timestamp.h declares."""
+    return _declared_in((_abi.AVG_TIMESTAMP_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -107,7 +116,7 @@ def lib():
         LOADED_STAT = (st.st_ino, st.st_size, st.st_mtime_ns)
         for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES,
                                   **_IWE_MULTI_SIGNATURES, **_LOSS_FRAMELESS_SIGNATURES,
-                                  **_CONTRAST_PYRAMID_SIGNATURES}.items():
+                                  **_CONTRAST_PYRAMID_SIGNATURES, **_AVG_TIMESTAMP_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

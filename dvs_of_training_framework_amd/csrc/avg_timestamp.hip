@@ -1,0 +1,396 @@
+// Average-timestamp term of a training from events alone and its gradient
+// with respect to the flow (docs/AVG_TIMESTAMP_SPEC.md): beside its bilinear
+// weight every warped event splats its distance in time from the reference,
+// a = |tau - rho|; per pixel T = A / (I + eps) is the average distance of the
+// events that landed there, and per image
+// value_m = (sum T^2 / n) / (sum T0^2 / n0), T0 the same at zero flow
+// (Zhu et al., CVPR 2019; Hagenaars et al., NeurIPS 2021, who normalise by the
+// pixels that hold events).  A flow that brings the events of one edge together
+// lowers it; piling unrelated events onto a pixel averages their distances and
+// earns nothing, which is what the contrast term of contrast.hip rewards.
+//
+// Replaces nothing of the reference: its loss reads the grey frames only.
+//
+// The images, the events that take part in them and the warp are those of
+// event_images.h and frame_common.h, so q and count are the bytes of
+// dvsof_contrast_multi_fwd.  Forward: one fill of the whole zeroed region; one
+// thread per event, which reads the flow at its pixel once per frame and issues
+// per reference one 32-bit and up to nine 64-bit integer atomics; the
+// fixed-order reduction of frame_common.h over the pixels of every image; one
+// closing wave.  Backward: contrast.hip's shape, G(p) = 2 k T D (a - T) at the
+// four corners, the R C images of a frame in one set of fixed-point sums with a
+// power-of-two unit per frame, one integer atomic per component, one thread per
+// element converts and clears.  No floating-point atomics, kernels only.  This
+// file relies on -ffp-contract=off.
+#include "event_images.h"
+#include "../../include/dvsof_avg_timestamp.h"
+
+namespace {
+
+constexpr int NT = kFrameNT;
+constexpr int kUnitBits = 40;    // R = 1: |one event's addend| < 2^(kUnitBits + 1) units
+constexpr int kSharedBits = 2;   // R > 1: up to three addends of a pixel's event share a sum
+constexpr double kEps = 0x1p-10;  // T = A / (I + kEps): 1 / (I + kEps) <= 1024
+
+// one per image, in the workspace behind the zeroed region
+struct ImageRec {
+    double S, S0;     // sum_p T^2, sum_p T0^2
+    double n, n0;     // pixels with q > 0, with count > 0
+    double peak;      // max_p 2 T D
+    double value;     // (S / n) / (S0 / n0); 0 without events, 1 when they all left
+    double k2;        // 2 n0 / (n S0); 0 where the image has no gradient
+    double gmax;      // |G| <= gmax on every pixel, for every event
+};
+static_assert(sizeof(ImageRec) == 64, "the workspace holds 64 bytes per image");
+
+// the accumulator of the statistics
+struct StatRow {
+    double S, S0, peak;
+    uint32_t n, n0;  // at most h w < 2^30
+};
+static_assert(sizeof(StatRow) == 32, "the workspace holds 32 bytes per statistics row");
+
+// ---------------------------------------------------------------------------
+// Forward.  The event loop and the frame rule of contrast_splat_kernel; per
+// reference the count and the distance at the event's own pixel, and at the
+// corners inside the image the weight and the weight times the distance.
+// ---------------------------------------------------------------------------
+template <int R, bool POL>
+__global__ __launch_bounds__(NT) void avgts_splat_kernel(
+    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
+    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
+    unsigned long long *__restrict__ q, unsigned long long *__restrict__ s, unsigned long long *__restrict__ base,
+    uint32_t *__restrict__ count)
+{
+    const int64_t stride = (int64_t)gridDim.x * NT;
+    const size_t plane = (size_t)h * w;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
+        const int64_t xi = x[e], yi = y[e];
+        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // the -1 slots of cropped and padded events
+        int c;
+        if (!event_channel<POL>(pol, e, c)) continue;
+        const float te = t[e];
+        const int64_t smp = sample[e];
+        const size_t pix = (size_t)yi * w + (size_t)xi;
+        for (int f = 0; f < F; ++f) {
+            if (frame_sample[f] != smp) continue;
+            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
+            if (!(t0 <= te && te <= t1)) continue;  // a test, not a clamp; false for a NaN
+            const float tau = event_tau(te, t0, t1);
+            const float *fl = flow + (size_t)f * 2 * plane + pix;
+            const float u = fl[0], v = fl[plane];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const size_t m = image_of<R, POL>(f, r, c);
+                Warp p;
+                const bool inside = warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p);
+                const float a = fabsf(p.tau);  // p.tau holds sig, set before the inside test; 0 <= a <= 1
+                atomicAdd(count + m * plane + pix, 1u);
+                const int64_t B = (int64_t)(a * kOne);  // exact; 0 <= B <= 2^32
+                if (B > 0) atomicAdd(base + m * plane + pix, (unsigned long long)B);
+                if (!inside) continue;
+                unsigned long long *qm = q + m * plane, *sm = s + m * plane;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int xx = p.cx + i, yy = p.cy + j;
+                        if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
+                        const float wgt = p.wy[j] * p.wx[i];
+                        const int64_t Q = (int64_t)(wgt * kOne);         // the addend of splat_corners
+                        const int64_t QA = (int64_t)((wgt * a) * kOne);  // one float32 product, then exact; QA <= Q
+                        const size_t at = (size_t)yy * w + (size_t)xx;
+                        if (Q > 0) atomicAdd(qm + at, (unsigned long long)Q);
+                        if (QA > 0) atomicAdd(sm + at, (unsigned long long)QA);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Statistics, by the fixed-order reduction of frame_common.h.
+// ---------------------------------------------------------------------------
+struct AvgSum {
+    using Row = StatRow;
+    static __device__ __forceinline__ Row zero() { return Row{0.0, 0.0, 0.0, 0u, 0u}; }
+    static __device__ __forceinline__ Row add(const Row &a, const Row &b)
+    {
+        return Row{a.S + b.S, a.S0 + b.S0, a.peak > b.peak ? a.peak : b.peak, a.n + b.n, a.n0 + b.n0};
+    }
+};
+
+__global__ __launch_bounds__(NT) void avgts_stats_partial_kernel(
+    const int64_t *__restrict__ q, const int64_t *__restrict__ s, const int64_t *__restrict__ base,
+    const uint32_t *__restrict__ count, int h, int w, int nb, StatRow *__restrict__ part)
+{
+    const int m = blockIdx.y;
+    const int n = h * w;
+    const int64_t *qm = q + (size_t)m * n, *sm = s + (size_t)m * n, *bm = base + (size_t)m * n;
+    const uint32_t *cm = count + (size_t)m * n;
+    frame_partial<AvgSum>(n, nb, part, [=](StatRow &a, int p) {
+        const int64_t Q = qm[p];
+        const uint32_t c = cm[p];
+        const double den = (double)Q * 0x1p-32 + kEps;
+        const double T = (double)sm[p] * 0x1p-32 / den;
+        const double D = 1.0 / den;
+        const double T0 = (double)bm[p] * 0x1p-32 / ((double)c + kEps);
+        const double pk = 2.0 * T * D;
+        a.S += T * T;
+        a.S0 += T0 * T0;
+        a.peak = a.peak > pk ? a.peak : pk;
+        a.n += Q > 0;
+        a.n0 += c > 0;
+    });
+}
+
+// 2^k: the flow gradient of a frame is summed in units of 1/unit; |G_m| <= gmax < 2^e for every image of the frame
+__device__ __forceinline__ double unit_of(double gmax, int unit_bits)
+{
+    int e = 0;
+    if (gmax > 0.0) (void)frexp(gmax, &e);
+    return ldexp(1.0, unit_bits - e);
+}
+
+// One wave: the record of every image (lane k takes images k, k + 64, ...);
+// after a barrier the unit of every frame (lane k takes frames k, k + 64, ...;
+// a maximum has no order) and, in lane 0, the images' values in image order.
+__global__ __launch_bounds__(kWave) void avgts_close_kernel(const StatRow *__restrict__ rows, int F, int RC,
+                                                            int unit_bits, ImageRec *rec, double *unit, float *term)
+{
+    const int M = F * RC;
+    for (int m = threadIdx.x; m < M; m += kWave) {
+        const StatRow r = rows[m];
+        ImageRec o;
+        o.S = r.S;
+        o.S0 = r.S0;
+        o.n = (double)r.n;
+        o.n0 = (double)r.n0;
+        o.peak = r.peak;
+        const bool live = r.S0 > 0.0, stayed = r.n > 0;
+        o.value = !live ? 0.0 : (stayed ? (o.S / o.n) / (o.S0 / o.n0) : 1.0);
+        o.k2 = live && stayed ? 2.0 * (o.n0 / (o.n * o.S0)) : 0.0;
+        o.gmax = 0.5 * o.k2 * o.peak;
+        rec[m] = o;
+    }
+    __syncthreads();
+    for (int f = threadIdx.x; f < F; f += kWave) {
+        double gmax = 0.0;
+        for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[f * RC + k].gmax);
+        unit[f] = unit_of(gmax, unit_bits);
+    }
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int m = 0; m < M; ++m) sum += rec[m].value;
+        *term = (float)(sum / (double)M);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Backward.  One thread per event and frame: for every reference
+// G = 2 k T D (a - T) at the four corners of the image of its channel (0
+// outside the image), the derivative of the bilinear weights, -sig of it to
+// the event's own pixel of the flow, in float64, truncated to the frame's unit.
+// ---------------------------------------------------------------------------
+template <int R, bool POL>
+__global__ __launch_bounds__(NT) void avgts_bwd_events_kernel(
+    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
+    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
+    const int64_t *__restrict__ q, const int64_t *__restrict__ s, const ImageRec *__restrict__ rec,
+    const double *__restrict__ unit, unsigned long long *__restrict__ acc)
+{
+    const int64_t stride = (int64_t)gridDim.x * NT;
+    const size_t plane = (size_t)h * w;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
+        const int64_t xi = x[e], yi = y[e];
+        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
+        int c;
+        if (!event_channel<POL>(pol, e, c)) continue;
+        const float te = t[e];
+        const int64_t smp = sample[e];
+        const size_t pix = (size_t)yi * w + (size_t)xi;
+        for (int f = 0; f < F; ++f) {
+            if (frame_sample[f] != smp) continue;
+            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
+            if (!(t0 <= te && te <= t1)) continue;
+            const float tau = event_tau(te, t0, t1);
+            const float *fl = flow + (size_t)f * 2 * plane + pix;
+            const float u = fl[0], v = fl[plane];
+            const double un = unit[f];
+            // |a - T| <= 1 and 2 k T D <= gmax < 2^e: the bounds of contrast_bwd_events_kernel
+            long long su = 0, sv = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const size_t m = image_of<R, POL>(f, r, c);
+                const double k2 = rec[m].k2;
+                if (k2 == 0.0) continue;  // no events, or they all left: every addend would be 0
+                Warp p;
+                if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
+                const double a = (double)fabsf(p.tau);
+                const int64_t *qm = q + m * plane, *sm = s + m * plane;
+                double G[2][2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int xx = p.cx + i, yy = p.cy + j;
+                        const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
+                        double g = 0.0;
+                        if (in) {
+                            const size_t at = (size_t)yy * w + (size_t)xx;
+                            const double den = (double)qm[at] * 0x1p-32 + kEps;
+                            const double T = (double)sm[at] * 0x1p-32 / den;
+                            const double D = 1.0 / den;
+                            g = k2 * T * D * (a - T);
+                        }
+                        G[j][i] = g;
+                    }
+                }
+                const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
+                const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
+                const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
+                su += (long long)(ms * gx * un);
+                sv += (long long)(ms * gy * un);
+            }
+            unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
+            if (su != 0) atomicAdd(dst, (unsigned long long)su);
+            if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
+        }
+    }
+}
+
+// One thread per element of grad_flow: convert, clear the sum for the next
+// backward of the same forward, store.
+__global__ __launch_bounds__(NT) void avgts_bwd_close_kernel(long long *__restrict__ acc,
+                                                             const double *__restrict__ unit,
+                                                             const float *__restrict__ seed, float weight, int F,
+                                                             int M, size_t per_frame, float *__restrict__ grad)
+{
+    const size_t total = (size_t)F * per_frame, stride = (size_t)gridDim.x * NT;
+    const float sw = seed[0] * weight;
+    for (size_t k = (size_t)blockIdx.x * NT + threadIdx.x; k < total; k += stride) {
+        const long long a = acc[k];
+        acc[k] = 0;
+        const double value = (double)a / unit[k / per_frame] / (double)M;  // the first division is exact
+        grad[k] = sw * (float)value;
+    }
+}
+
+// the workspace as byte offsets, in the order of the header
+struct Layout {
+    size_t s, base, sums, count, zeroed_bytes, rec, unit, rows, part, bytes;
+    int nb;
+};
+
+Layout layout_of(int F, int h, int w, const Plan &pl)
+{
+    const size_t P = (size_t)pl.M * h * w, S = 2 * (size_t)F * h * w;
+    Layout o;
+    o.nb = partial_blocks(h, w);
+    o.s = sizeof(int64_t) * P;
+    o.base = o.s + sizeof(int64_t) * P;
+    o.sums = o.base + sizeof(int64_t) * P;
+    o.count = o.sums + sizeof(int64_t) * S;
+    o.zeroed_bytes = o.count + sizeof(uint32_t) * P;
+    o.rec = (o.zeroed_bytes + 7) / 8 * 8;
+    o.unit = o.rec + sizeof(ImageRec) * (size_t)pl.M;
+    o.rows = o.unit + sizeof(double) * (size_t)F;
+    o.part = o.rows + sizeof(StatRow) * (size_t)pl.M;
+    o.bytes = o.part + sizeof(StatRow) * (size_t)pl.M * o.nb;
+    return o;
+}
+
+// The refusals both calls share, in the order of dvsof_contrast_multi_fwd; outputs: the call's
+// own pointers are all there.  DVSOF_OK with F == 0: nothing to do.
+int check_call(const int64_t *x, const int64_t *y, const float *t, const int64_t *p, const int64_t *sample_index,
+               int64_t n_events, const float *frame_ts, const int64_t *frame_sample, const float *flow, int F, int h,
+               int w, int reference_mask, int polarity, bool outputs, const void *workspace, size_t workspace_bytes,
+               Plan &pl)
+{
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !outputs || !frame_ts || !frame_sample || !flow) return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < layout_of(F, h, w, pl).bytes) return DVSOF_ENOSPACE;
+    return DVSOF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dvsof_avg_timestamp_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
+{
+    Plan pl;
+    if (F < 1 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return 0;
+    return layout_of(F, h, w, pl).bytes;
+}
+
+int dvsof_avg_timestamp_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                            const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                            const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                            int reference_mask, int polarity, float *term, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    Plan pl;
+    const int rc = check_call(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w,
+                              reference_mask, polarity, term != nullptr, workspace, workspace_bytes, pl);
+    if (rc != DVSOF_OK || F == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const Layout lay = layout_of(F, h, w, pl);
+    char *ws = (char *)workspace;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, lay.zeroed_bytes, st));
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t, p,
+                                sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
+                                (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
+                                (unsigned long long *)(ws + lay.base), (uint32_t *)(ws + lay.count));
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(avgts_stats_partial_kernel, dim3((unsigned)lay.nb, (unsigned)pl.M), dim3(NT), 0, st,
+                       (const int64_t *)ws, (const int64_t *)(ws + lay.s), (const int64_t *)(ws + lay.base),
+                       (const uint32_t *)(ws + lay.count), h, w, lay.nb, (StatRow *)(ws + lay.part));
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(frame_final_kernel<AvgSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
+                       (const StatRow *)(ws + lay.part), lay.nb, (StatRow *)(ws + lay.rows));
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(avgts_close_kernel, dim3(1), dim3(kWave), 0, st, (const StatRow *)(ws + lay.rows), F,
+                       pl.R * pl.C, pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, (ImageRec *)(ws + lay.rec),
+                       (double *)(ws + lay.unit), term);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int dvsof_avg_timestamp_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                            const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                            const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                            int reference_mask, int polarity, void *workspace, size_t workspace_bytes,
+                            const float *seed, float weight, float *grad_flow, void *stream)
+{
+    Plan pl;
+    const int rc = check_call(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w,
+                              reference_mask, polarity, seed && grad_flow, workspace, workspace_bytes, pl);
+    if (rc != DVSOF_OK || F == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const Layout lay = layout_of(F, h, w, pl);
+    char *ws = (char *)workspace;
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(avgts_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
+                                p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
+                                (const int64_t *)ws, (const int64_t *)(ws + lay.s),
+                                (const ImageRec *)(ws + lay.rec), (const double *)(ws + lay.unit),
+                                (unsigned long long *)(ws + lay.sums));
+        DVSOF_LAUNCH_CHECK();
+    }
+    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
+    hipLaunchKernelGGL(avgts_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
+                       (long long *)(ws + lay.sums), (const double *)(ws + lay.unit), seed, weight, F, pl.M,
+                       per_frame, grad_flow);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+}  // extern "C"

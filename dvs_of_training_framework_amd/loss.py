@@ -13,7 +13,10 @@ Differences that are deliberate (MI355X-first):
   * ``Losses.fused`` is a training fast path (forward + gradient in one sweep);
   * ``Losses.frameless`` is the loss of a batch without frames: smoothness and
     out-of-border alone, no pyramid and no frame read (csrc/loss_frameless.hip,
-    docs/FRAMELESS_SPEC.md).
+    docs/FRAMELESS_SPEC.md);
+  * ``Losses.contrast`` and ``Losses.avg_timestamp`` are training terms from the
+    events alone, on the finest flow (csrc/contrast.hip, csrc/avg_timestamp.hip;
+    docs/CONTRAST_SPEC.md, docs/AVG_TIMESTAMP_SPEC.md).
 """
 import ctypes
 
@@ -718,6 +721,189 @@ class _ContrastPyramid(torch.autograd.Function):
         return (None,) * 11 + grads
 
 
+# ---------------------------------------------------------------------------
+# Average-timestamp term (csrc/avg_timestamp.hip, docs/AVG_TIMESTAMP_SPEC.md)
+# ---------------------------------------------------------------------------
+AVG_TIMESTAMP_EPS = 2.0 ** -10
+AVG_TIMESTAMP_REC_DTYPE = np.dtype([(k, '<f8') for k in ('S', 'S0', 'n', 'n0', 'peak', 'value', 'k2', 'gmax')])
+AVG_TIMESTAMP_ROW_DTYPE = np.dtype([('S', '<f8'), ('S0', '<f8'), ('peak', '<f8'), ('n', '<u4'), ('n0', '<u4')])
+
+
+def avg_timestamp_layout(F, M, h, w):
+    """The byte offsets of include/dvsof_avg_timestamp.h -> dict: q, s, base,
+    sums, count, zeroed_bytes, rec, unit, rows, part, bytes, nb."""
+    from . import eval as ev
+    P, S, nb = M * h * w, 2 * F * h * w, ev.partial_blocks(h * w)
+    o = dict(q=0, s=8 * P, base=16 * P, sums=24 * P, count=24 * P + 8 * S, nb=nb)
+    o['zeroed_bytes'] = o['count'] + 4 * P
+    o['rec'] = (o['zeroed_bytes'] + 7) // 8 * 8
+    o['unit'] = o['rec'] + 64 * M
+    o['rows'] = o['unit'] + 8 * F
+    o['part'] = o['rows'] + 32 * M
+    o['bytes'] = o['part'] + 32 * M * nb
+    return o
+
+
+def _avg_timestamp_pixels(q, s):
+    """T = A / (I + eps) and D = 1 / (I + eps) in float64, as both kernels form them."""
+    den = q.astype(np.float64) * 2.0 ** -32 + AVG_TIMESTAMP_EPS
+    return s.astype(np.float64) * 2.0 ** -32 / den, 1.0 / den
+
+
+def avg_timestamp_fwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flow, references=('start', 'end'),
+                           polarity=False):
+    """AVG_TIMESTAMP_SPEC sections 2-5 on the host: what
+    ``dvsof_avg_timestamp_fwd`` is pinned to, byte for byte.  The arguments of
+    ``contrast_multi_fwd_host``.  With M = F R C images, m = (f R + r) C + c ->
+    dict: q, s, base int64 [M,h,w], count uint32 [M,h,w], rows (M statistics
+    rows, AVG_TIMESTAMP_ROW_DTYPE, the sums in the kernels' order), rec (M
+    records, AVG_TIMESTAMP_REC_DTYPE), image_value float64 [M], unit float64
+    [F], term float32, and mask, R, C."""
+    from . import eval as ev
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    mask = contrast_reference_mask(references)
+    rhos, C = _contrast_rhos(mask), 2 if polarity else 1
+    R = len(rhos)
+    M = F * R * C
+    pr = _contrast_multi_pairs(x, y, t, p, sample_index, frame_ts, frame_sample, flow, polarity)
+    q, s, base = (np.zeros((M, h, w), np.int64) for _ in range(3))
+    count = np.zeros((M, h, w), np.uint32)
+    one = _F32(ev.IWE_ONE)
+    for r, rho in enumerate(rhos):
+        m = (pr['f'] * R + r) * C + pr['c']
+        wp = _contrast_warp_to(pr, rho, h, w)
+        a = np.abs(wp['sig'])
+        np.add.at(count, (m, pr['y'], pr['x']), 1)
+        np.add.at(base, (m, pr['y'], pr['x']), (a * one).astype(np.int64))
+        k = wp['inside']
+        mk, cx, cy, ak = m[k], wp['cx'][k], wp['cy'][k], a[k]
+        for j in range(2):
+            for i in range(2):
+                xx, yy = cx + i, cy + j
+                wgt = (wp['wy'][j][k] * wp['wx'][i][k]).astype(_F32)
+                Q = (wgt * one).astype(np.int64)
+                QA = ((wgt * ak).astype(_F32) * one).astype(np.int64)
+                ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+                np.add.at(q, (mk[ok], yy[ok], xx[ok]), Q[ok])
+                np.add.at(s, (mk[ok], yy[ok], xx[ok]), QA[ok])
+    # the statistics, in float64 and in the kernels' order
+    N, nb = h * w, ev.partial_blocks(h * w)
+    T, D = _avg_timestamp_pixels(q.reshape(M, N), s.reshape(M, N))
+    T0 = base.reshape(M, N).astype(np.float64) * 2.0 ** -32 / (count.reshape(M, N).astype(np.float64)
+                                                              + AVG_TIMESTAMP_EPS)
+    rows = np.zeros(M, AVG_TIMESTAMP_ROW_DTYPE)
+    if M:
+        rows['S'], rows['S0'] = ev.kernel_order_sum(T * T, nb), ev.kernel_order_sum(T0 * T0, nb)
+        rows['peak'] = (2.0 * T * D).max(1)
+        rows['n'], rows['n0'] = (q.reshape(M, N) > 0).sum(1), (count.reshape(M, N) > 0).sum(1)
+    # the closing wave
+    rec = np.zeros(M, AVG_TIMESTAMP_REC_DTYPE)
+    for k_ in ('S', 'S0', 'n', 'n0', 'peak'):
+        rec[k_] = rows[k_]
+    live, stayed = rec['S0'] > 0, rec['n'] > 0
+    with np.errstate(all='ignore'):
+        rec['value'] = np.where(live, np.where(stayed, (rec['S'] / rec['n']) / (rec['S0'] / rec['n0']), 1.0), 0.0)
+        rec['k2'] = np.where(live & stayed, 2.0 * (rec['n0'] / (rec['n'] * rec['S0'])), 0.0)
+    rec['gmax'] = 0.5 * rec['k2'] * rec['peak']
+    frame_gmax = rec['gmax'].reshape(F, R * C).max(1) if F else np.zeros(0)
+    e = np.where(frame_gmax > 0, np.frexp(frame_gmax)[1], 0)
+    unit = np.ldexp(1.0, CONTRAST_UNIT_BITS - (CONTRAST_SHARED_BITS if R > 1 else 0) - e)
+    total = np.float64(0)
+    for v in rec['value']:              # in image order
+        total = total + v
+    with np.errstate(all='ignore'):
+        term = _F32(total / np.float64(M))
+    return dict(q=q, s=s, base=base, count=count, rows=rows, rec=rec, image_value=rec['value'].copy(), unit=unit,
+                term=term, mask=mask, R=R, C=C)
+
+
+def avg_timestamp_bwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flow, fwd, seed=1.0, weight=1.0):
+    """AVG_TIMESTAMP_SPEC section 6 on the host: what ``dvsof_avg_timestamp_bwd``
+    is pinned to.  fwd: the dict of ``avg_timestamp_fwd_host`` for the same
+    input; references and polarity are read from it.  -> (grad_flow float32
+    [F,2,h,w] = seed * weight * d term / d flow, sums int64 [F,2,h,w], the
+    fixed-point sums of all images of a frame in units of 1/unit[f])."""
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    R, C = fwd['R'], fwd['C']
+    M = F * R * C
+    pr = _contrast_multi_pairs(x, y, t, p, sample_index, frame_ts, frame_sample, flow, C == 2)
+    T, D = _avg_timestamp_pixels(fwd['q'], fwd['s'])
+    sums = np.zeros((F, 2, h, w), np.int64)
+    for r, rho in enumerate(_contrast_rhos(fwd['mask'])):
+        m = (pr['f'] * R + r) * C + pr['c']
+        wp = _contrast_warp_to(pr, rho, h, w)
+        k = wp['inside'] & (fwd['rec']['k2'][m] != 0)
+        m, f, cx, cy, px, py = m[k], pr['f'][k], wp['cx'][k], wp['cy'][k], pr['x'][k], pr['y'][k]
+        k2, unit = fwd['rec']['k2'][m], fwd['unit'][f]
+        a = np.abs(wp['sig'][k]).astype(np.float64)
+        G = [[None, None], [None, None]]
+        for j in range(2):
+            for i in range(2):
+                xx, yy = cx + i, cy + j
+                ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+                at = (m, np.where(ok, yy, 0), np.where(ok, xx, 0))
+                G[j][i] = np.where(ok, k2 * T[at] * D[at] * (a - T[at]), 0.0)
+        wx = [v[k].astype(np.float64) for v in wp['wx']]
+        wy = [v[k].astype(np.float64) for v in wp['wy']]
+        gx = wy[0] * (G[0][1] - G[0][0]) + wy[1] * (G[1][1] - G[1][0])
+        gy = wx[0] * (G[1][0] - G[0][0]) + wx[1] * (G[1][1] - G[0][1])
+        ms = -wp['sig'][k].astype(np.float64)
+        np.add.at(sums, (f, 0, py, px), np.trunc(ms * gx * unit).astype(np.int64))
+        np.add.at(sums, (f, 1, py, px), np.trunc(ms * gy * unit).astype(np.int64))
+    value = sums.astype(np.float64) / fwd['unit'].reshape(F, 1, 1, 1) / np.float64(max(M, 1))
+    sw = _F32(seed) * _F32(weight)
+    return sw * value.astype(_F32), sums
+
+
+class _AvgTimestamp(torch.autograd.Function):
+    """(weight * term, term) of the finest flow; the gradient of the first
+    enters the flow (dvsof_avg_timestamp_fwd / dvsof_avg_timestamp_bwd).  The
+    images live in the workspace; the weight is applied inside the backward's
+    closing kernel."""
+
+    @staticmethod
+    def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity):
+        dev = flow.device
+        flow = flow.detach().contiguous().float()
+        F, _, h, w = flow.shape
+        lib = _lib.lib()
+        term = torch.zeros((), dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+        nbytes = lib.dvsof_avg_timestamp_workspace_bytes(F, mask, int(polarity), h, w)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
+        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
+        pol = p.contiguous() if polarity else None
+        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
+        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flow.shape, frame_ts.shape)
+        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
+        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
+        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
+        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
+                                                        tables[0].data_ptr(), tables[1].data_ptr(),
+                                                        flow.data_ptr(), F, h, w, mask, int(polarity)])
+        _lib.check(lib.dvsof_avg_timestamp_fwd(*ctx.args, term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
+                   'dvsof_avg_timestamp_fwd')
+        ctx.held = (cols, pol, tables, flow, ws, nbytes)
+        ctx.weight = float(weight)
+        ctx.mark_non_differentiable(term)
+        ctx.set_materialize_grads(False)
+        return term * ctx.weight, term
+
+    @staticmethod
+    def backward(ctx, g_value, _g_term):
+        if g_value is None:
+            return (None,) * 11
+        flow, ws, nbytes = ctx.held[3:]
+        grad = torch.empty_like(flow)
+        seed = g_value.contiguous().float()
+        _lib.check(_lib.lib().dvsof_avg_timestamp_bwd(
+            *ctx.args, ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(), _lib.stream()),
+            'dvsof_avg_timestamp_bwd')
+        return (grad,) + (None,) * 10
+
+
 class Loss:
     """Single-scale evaluator (reference utils/loss.py:38-171)."""
 
@@ -888,6 +1074,35 @@ class Losses:
         _lib.require_cuda(pol)
         value, term = _Contrast.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
                                       bool(polarity))
+        return value if weight is None else (value, term)
+
+    def avg_timestamp(self, flows, flow_ts, flow_sample_idx, events, weight=None,
+                      references=('start', 'end'), polarity=False):
+        """The average-timestamp term of the finest flow ``flows[-1]``
+        (docs/AVG_TIMESTAMP_SPEC.md): per image the mean over the pixels that
+        hold events of the squared average distance in time between the events
+        warped onto a pixel and the reference time, over the same at zero
+        flow; the mean over all images.  1 at zero flow, below 1 where the flow
+        brings events of the same edge together.  The arguments and what is
+        returned are those of ``contrast``: the 0-dim term, differentiable with
+        respect to ``flows[-1]``; with a ``weight`` -> (weight * term, term),
+        the second detached for logging.  Nothing waits for the device.
+
+        references: names among 'start', 'middle', 'end'; the default warps
+        to both ends of the window (Zhu et al., CVPR 2019): at one end alone
+        the events that need no warp carry no distance.  polarity: ON and OFF
+        events in images of their own."""
+        flow = flows[-1]
+        assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
+            f'flow of size {tuple(flow.shape)} given to the average-timestamp term of scale {self.shapes[-1]}'
+        cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
+        _lib.require_cuda(flow, flow_ts, flow_sample_idx, *cols)
+        mask = contrast_reference_mask(references)
+        weight_ = 1.0 if weight is None else float(weight)
+        pol = events['polarity'] if polarity else None
+        _lib.require_cuda(pol)
+        value, term = _AvgTimestamp.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
+                                          bool(polarity))
         return value if weight is None else (value, term)
 
     def _contrast_all(self, flows, flow_ts, flow_sample_idx, events, weight, references, polarity):

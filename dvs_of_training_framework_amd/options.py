@@ -326,6 +326,27 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'level weighing --contrast-weight / K, and logs Train/contrast/<tag> '
                              'per level beside the mean (docs/CONTRAST_SPEC.md sections 19-23).  '
                              'Needs --contrast-weight')
+    parser.add_argument('--avg-timestamp-weight', dest='avg_timestamp_weight',
+                        default=argparse.SUPPRESS, type=float,
+                        help='add this times the average-timestamp term to the training '
+                             'loss: per prediction the mean squared per-pixel average of the '
+                             'distance in time between the events warped along the finest '
+                             'flow and the reference time, over the same at zero flow: 1 at '
+                             'zero flow, below 1 where the flow aligns the events of an edge '
+                             '(docs/AVG_TIMESTAMP_SPEC.md; Zhu et al. 2019); logged as '
+                             'Train/avg timestamp and Validation/avg timestamp.  With or '
+                             'without --contrast-weight.  Needs the raw events in their wire '
+                             'columns on the device (not --ev_images, not --compact-events); '
+                             'such a run is not captured.  Absent or 0: off')
+    parser.add_argument('--avg-timestamp-references', dest='avg_timestamp_references',
+                        default=argparse.SUPPRESS, type=str,
+                        help='comma-separated reference times of the average-timestamp term, '
+                             'among start, middle, end (any order, none twice; default '
+                             'start,end).  Needs --avg-timestamp-weight')
+    parser.add_argument('--avg-timestamp-polarity', dest='avg_timestamp_polarity',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='accumulate ON and OFF events in images of their own in the '
+                             'average-timestamp term.  Needs --avg-timestamp-weight')
     parser.add_argument('--recording', dest='recording', default=None, type=Path,
                         help='train from ONE event-only recording kept on the device: a '
                              '.npz or .hdf5 file with the arrays x, y, t, p (sorted by t) and '
@@ -403,7 +424,8 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_frameless_args(validate_sharpness_args(validate_contrast_args(args)))
+    return validate_frameless_args(validate_sharpness_args(validate_avg_timestamp_args(
+        validate_contrast_args(args))))
 
 
 CONTRAST_REFERENCE_NAMES = ('start', 'middle', 'end')
@@ -445,6 +467,46 @@ def validate_contrast_args(args):
         raise SystemExit('--contrast-weight cannot be combined with --compact-events: the term '
                          'reads the int64 / float32 wire columns, not the 9 B/event encoded ones')
     return args
+
+
+AVG_TIMESTAMP_REFERENCES = ('start', 'end')
+
+
+def validate_avg_timestamp_args(args):
+    """--avg-timestamp-weight against what it cannot be combined with, and the
+    term's options against a run without the term.  The three options are
+    absent from ``args`` unless given (read them with ``getattr``); a given
+    ``args.avg_timestamp_references`` becomes a tuple of names."""
+    weight = getattr(args, 'avg_timestamp_weight', 0.0)
+    if weight < 0 or weight != weight:
+        raise SystemExit(f'--avg-timestamp-weight must not be negative, got {weight}')
+    if hasattr(args, 'avg_timestamp_references'):
+        args.avg_timestamp_references = parse_contrast_references(args.avg_timestamp_references,
+                                                                  '--avg-timestamp-references')
+    if not weight > 0:
+        if hasattr(args, 'avg_timestamp_references'):
+            raise SystemExit('--avg-timestamp-references needs a positive --avg-timestamp-weight')
+        if getattr(args, 'avg_timestamp_polarity', False):
+            raise SystemExit('--avg-timestamp-polarity needs a positive --avg-timestamp-weight')
+    if weight > 0 and getattr(args, 'ev_images', False):
+        raise SystemExit('--avg-timestamp-weight cannot be combined with --ev_images: the term is '
+                         'computed from the raw events on the device, and a batch of '
+                         'preprocessed event images carries none')
+    if weight > 0 and getattr(args, 'compact_events', False):
+        raise SystemExit('--avg-timestamp-weight cannot be combined with --compact-events: the term '
+                         'reads the int64 / float32 wire columns, not the 9 B/event encoded ones')
+    return args
+
+
+def avg_timestamp_keywords(args):
+    """The keywords of training.train / validate / hooks.ValidationHook for
+    the average-timestamp term: none unless --avg-timestamp-weight is positive."""
+    weight = getattr(args, 'avg_timestamp_weight', 0.0)
+    if not weight:
+        return {}
+    return {'avg_timestamp_weight': weight,
+            'avg_timestamp_references': tuple(getattr(args, 'avg_timestamp_references', AVG_TIMESTAMP_REFERENCES)),
+            'avg_timestamp_polarity': bool(getattr(args, 'avg_timestamp_polarity', False))}
 
 
 def validate_sharpness_args(args):

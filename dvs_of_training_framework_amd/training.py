@@ -48,11 +48,14 @@ class _Terms(tuple):
 
 class _TermsAndContrast(tuple):
     """The terms structure as it is, carrying the contrast-maximisation term
-    of the micro-batch beside it (``contrast``: a 0-dim device tensor)."""
-    def __new__(cls, terms, contrast):
+    of the micro-batch beside it (``contrast``: a 0-dim device tensor) and,
+    where the loss has one, the average-timestamp term (``avg_timestamp``,
+    likewise; either is None where the loss has none)."""
+    def __new__(cls, terms, contrast, avg_timestamp=None):
         self = super().__new__(cls, terms)
         self.packed = getattr(terms, 'packed', None)
         self.contrast = contrast
+        self.avg_timestamp = avg_timestamp
         return self
 
 
@@ -78,11 +81,35 @@ def _contrast_keywords(weight, references, polarity, scales='finest'):
                 **{'contrast_' + k: v for k, v in _contrast_options(references, polarity, scales).items()})
 
 
+AVG_TIMESTAMP_REFERENCES = ('start', 'end')
+
+
+def _avg_timestamp_options(references, polarity):
+    """The keywords of ``Losses.avg_timestamp`` that differ from its defaults."""
+    out = {}
+    if tuple(references) != AVG_TIMESTAMP_REFERENCES:
+        out['references'] = tuple(references)
+    if polarity:
+        out['polarity'] = True
+    return out
+
+
+def _avg_timestamp_keywords(weight, references, polarity):
+    """What a call down the chain gets: nothing at weight 0, and the options
+    only where they differ from the defaults."""
+    if not weight:
+        return {}
+    return dict({'avg_timestamp_weight': weight},
+                **{'avg_timestamp_' + k: v for k, v in _avg_timestamp_options(references, polarity).items()})
+
+
 def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   timestamps, sample_idx, features, weights=[0.5, 1, 1],
                   frame_indices=None, contrast_weight=0.0, events=None,
                   contrast_references=('start',), contrast_polarity=False,
-                  contrast_scales='finest'):
+                  contrast_scales='finest', avg_timestamp_weight=0.0,
+                  avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+                  avg_timestamp_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
     that has ``fused`` and flows that need gradients the value and the flow
     gradients come out of one sweep (loss.Losses.fused).
@@ -98,6 +125,12 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     contrast_weight / K (CONTRAST_SPEC sections 19-23); ``.contrast`` is then
     the [K] tensor of the levels' terms.  'finest', the default, is the call
     as it was.
+
+    avg_timestamp_weight > 0: plus avg_timestamp_weight * the average-timestamp
+    term of the finest flow over ``events`` (loss.Losses.avg_timestamp,
+    docs/AVG_TIMESTAMP_SPEC.md), beside the contrast term or without it; the
+    term rides on the returned terms as ``.avg_timestamp``.  At 0 nothing of
+    that is constructed and ``events`` is not looked at.
 
     images=None with an evaluator that has ``frameless`` (loss.Losses): a
     frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
@@ -129,17 +162,30 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         loss = 0
         for weight, per_scale in zip(weights, terms):
             loss = loss + weight * mean(per_scale)
-    if not contrast_weight:
+    if not contrast_weight and not avg_timestamp_weight:
         return loss, terms
-    if contrast_weight < 0:
-        raise ValueError(f'contrast_weight must not be negative, got {contrast_weight}')
-    if events is None:
-        raise ValueError('contrast_weight > 0 needs the raw events of the batch on the device '
-                         '(is_raw=True); preprocessed voxel grids carry none')
-    value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events,
-                                     weight=contrast_weight, **_contrast_options(
-                                         contrast_references, contrast_polarity, contrast_scales))
-    return loss + value, _TermsAndContrast(terms, term)
+    term = avg_term = None
+    if contrast_weight:
+        if contrast_weight < 0:
+            raise ValueError(f'contrast_weight must not be negative, got {contrast_weight}')
+        if events is None:
+            raise ValueError('contrast_weight > 0 needs the raw events of the batch on the device '
+                             '(is_raw=True); preprocessed voxel grids carry none')
+        value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events,
+                                         weight=contrast_weight, **_contrast_options(
+                                             contrast_references, contrast_polarity, contrast_scales))
+        loss = loss + value
+    if avg_timestamp_weight:
+        if avg_timestamp_weight < 0:
+            raise ValueError(f'avg_timestamp_weight must not be negative, got {avg_timestamp_weight}')
+        if events is None:
+            raise ValueError('avg_timestamp_weight > 0 needs the raw events of the batch on the device '
+                             '(is_raw=True); preprocessed voxel grids carry none')
+        value, avg_term = evaluator.avg_timestamp(flows, flow_ts, flow_sample_idx, events,
+                                                  weight=avg_timestamp_weight, **_avg_timestamp_options(
+                                                      avg_timestamp_references, avg_timestamp_polarity))
+        loss = loss + value
+    return loss, _TermsAndContrast(terms, term, avg_term)
 
 
 class TermReadback:
@@ -157,6 +203,14 @@ class TermReadback:
         self._table = None
         self._contrast = getattr(terms, 'contrast', None)
         self._contrast_levels = None
+        self._avg_timestamp = getattr(terms, 'avg_timestamp', None)
+
+    def avg_timestamp(self):
+        """The average-timestamp term as a host float (one small copy), None
+        when the loss has none."""
+        if isinstance(self._avg_timestamp, torch.Tensor):
+            self._avg_timestamp = float(self._avg_timestamp)
+        return self._avg_timestamp
 
     def contrast(self):
         """The contrast-maximisation term as a host float (one small copy),
@@ -233,15 +287,23 @@ def _to_device(batch, device, is_raw):
 def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       weights, return_prediction=False, contrast_weight=0.0,
                       contrast_references=('start',), contrast_polarity=False,
-                      contrast_scales='finest'):
+                      contrast_scales='finest', avg_timestamp_weight=0.0,
+                      avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+                      avg_timestamp_polarity=False):
     """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs]).
     contrast_weight > 0 (raw events only), contrast_references,
-    contrast_polarity, contrast_scales: see ``combined_loss``.  A frameless batch
+    contrast_polarity, contrast_scales, and avg_timestamp_weight > 0 (raw
+    events only) with its references and polarity: see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
     the frame size from ``'shape'`` and the loss that reads no frame."""
     contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales)
     if contrast and not is_raw:
         raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
+    avg = _avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references, avg_timestamp_polarity)
+    if avg and not is_raw:
+        raise ValueError('avg_timestamp_weight > 0 needs raw events (is_raw=True)')
+    if avg:
+        contrast = dict(contrast, **avg)
     with _timed(timers, 'batch2gpu'):
         timestamps, sample_idx, images, payload = _to_device(batch, device,
                                                              is_raw)
@@ -294,6 +356,7 @@ class ScaleSums:
         self.loss = 0.0
         self.contrast = None        # sum of the contrast-maximisation term, if the loss has one
         self.contrast_levels = None  # and per level, if it is taken on every scale
+        self.avg_timestamp = None   # sum of the average-timestamp term, if the loss has one
         self.tags = None
 
     def add(self, loss, readback, tags):
@@ -310,6 +373,9 @@ class ScaleSums:
             levels = readback.contrast_levels() if hasattr(readback, 'contrast_levels') else None
             if levels is not None:
                 self.contrast_levels = [a + b for a, b in zip(self.contrast_levels or [0.0] * len(levels), levels)]
+        extra = readback.avg_timestamp() if hasattr(readback, 'avg_timestamp') else None
+        if extra is not None:
+            self.avg_timestamp = (self.avg_timestamp or 0.0) + extra
         self.tags = list(tags)
 
     def write(self, logger, x, divisor, families):
@@ -433,6 +499,16 @@ def capture_refusal(optimizer, is_raw, model=None, contrast_weight=0.0):
     return None
 
 
+def avg_timestamp_capture_refusal(avg_timestamp_weight=0.0):
+    """Why ``train(capture=True)`` cannot replay a step that holds the
+    average-timestamp term (None: there is none); asked before
+    ``capture_refusal``."""
+    if avg_timestamp_weight:
+        return (f'--avg-timestamp-weight {avg_timestamp_weight}: the captured step does not carry the '
+                'average-timestamp term (dvsof_avg_timestamp_fwd / dvsof_avg_timestamp_bwd)')
+    return None
+
+
 def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           evaluator, weights=[0.5, 1, 1], is_raw=True, accumulation_steps=1,
           timers=None, hooks={}, init_step=0, init_samples_passed=0,
@@ -440,7 +516,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           log_every: int = 1, capture=False, guard=None,
           max_skipped_steps: int = 32, guard_agreement_every: int = 0,
           contrast_weight: float = 0.0, contrast_references=('start',),
-          contrast_polarity: bool = False, contrast_scales: str = 'finest'):
+          contrast_polarity: bool = False, contrast_scales: str = 'finest',
+          avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+          avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
     batches above ``max_events_per_batch`` events are skipped and not counted,
@@ -482,6 +560,14 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                weighing contrast_weight / K; ``Train/contrast`` is then the
                mean of the levels' terms and ``Train/contrast/<tag>`` each
                level's.  'finest' (the default): the finest flow alone
+    avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
+               the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
+               events only), logged as ``Train/avg timestamp``, beside the
+               contrast term or without it; such a run is not captured.  0:
+               the step launches what it launches without it
+    avg_timestamp_references, avg_timestamp_polarity:  the reference times of
+               that term (default: both ends of the window) and whether ON
+               and OFF events are accumulated apart
 
     A loader of frameless batches (sequence.EventWindowLoader: is_raw=True,
     ``'images': None``) needs contrast_weight > 0; the photometric rows are
@@ -494,7 +580,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                        init_samples_passed)
     sums = ScaleSums()
     captured = None
-    refused = capture_refusal(optimizer, is_raw, model, contrast_weight) if capture else None
+    refused = (avg_timestamp_capture_refusal(avg_timestamp_weight)
+               or capture_refusal(optimizer, is_raw, model, contrast_weight)) if capture else None
     if refused:
         import sys
         print(f'capture: not used, the loop runs eagerly: {refused}', file=sys.stderr)
@@ -534,7 +621,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
             loss, terms, tags = process_minibatch(
                 model, batch, timers, device, is_raw, evaluator, weights,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
-                                     contrast_scales))
+                                     contrast_scales),
+                **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
+                                          avg_timestamp_polarity))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass
@@ -570,6 +659,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                         for tag, level in zip(sums.tags, sums.contrast_levels or ()):
                             logger.add_scalar(f'Train/contrast/{tag}',
                                               level / accumulation_steps, x)
+                    if sums.avg_timestamp is not None:
+                        logger.add_scalar('Train/avg timestamp',
+                                          sums.avg_timestamp / accumulation_steps, x)
                     for g, group in enumerate(optimizer.param_groups):
                         logger.add_scalar(f'General/learning rate/{g}',
                                           group['lr'], x)
@@ -605,12 +697,15 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
 def validate(model, device, loader, samples_passed, logger, evaluator,
              weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
              contrast_references=('start',), contrast_polarity=False,
-             contrast_scales='finest'):
+             contrast_scales='finest', avg_timestamp_weight=0.0,
+             avg_timestamp_references=AVG_TIMESTAMP_REFERENCES, avg_timestamp_polarity=False):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
     the loss holds the contrast-maximisation term (of those reference times
     and polarity setting), written as ``Validation/contrast``; with
-    contrast_scales='all' that is the mean of the levels' terms."""
+    contrast_scales='all' that is the mean of the levels' terms; with
+    avg_timestamp_weight > 0 it holds the average-timestamp term as well,
+    written as ``Validation/avg timestamp``."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -619,11 +714,16 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
             loss, terms, tags = process_minibatch(
                 model, batch, quiet, device, is_raw, evaluator, weights,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
-                                     contrast_scales))
+                                     contrast_scales),
+                **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
+                                          avg_timestamp_polarity))
             sums.add(loss, terms, tags)
     logger.add_scalar('General/Validation loss', sums.loss / n_batches,
                       samples_passed)
     sums.write(logger, samples_passed, n_batches, _VALID_FAMILIES)
     if sums.contrast is not None:
         logger.add_scalar('Validation/contrast', sums.contrast / n_batches,
+                          samples_passed)
+    if sums.avg_timestamp is not None:
+        logger.add_scalar('Validation/avg timestamp', sums.avg_timestamp / n_batches,
                           samples_passed)

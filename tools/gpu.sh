@@ -40,6 +40,11 @@
 #                                     batch 8, 256x256, four scales, and one eager Ranger step of a frameless batch
 #                                     against the framed one with zero images, in alternating blocks of one run
 #                                     (profiles/frameless/README.md)
+#   avgts [avg_timestamp_bench.py args]  the average-timestamp term (tools/avg_timestamp_bench.py): dvsof_avg_timestamp_fwd /
+#                                     _bwd against dvsof_contrast_multi_fwd / _bwd at start,end and at start,middle,end
+#                                     with polarity, batch 8, 256x256, 65 536 events per sample, and one eager Ranger
+#                                     step with and without --avg-timestamp-weight, in alternating blocks of one run
+#                                     (profiles/avg_timestamp/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -114,6 +119,9 @@ contrast_pyramid)
 frameless)
   timeout -k 10 420 env "${envs[@]}" python tools/frameless_bench.py "$@" > $O/frameless.json 2> $O/frameless.err
   echo "frameless rc=$?"; cut -c1-2600 $O/frameless.json; tail -3 $O/frameless.err ;;
+avgts)
+  timeout -k 10 540 env "${envs[@]}" python tools/avg_timestamp_bench.py "$@" > $O/avgts.json 2> $O/avgts.err
+  echo "avgts rc=$?"; cut -c1-3600 $O/avgts.json; tail -3 $O/avgts.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

@@ -34,8 +34,8 @@ from dvs_of_training_framework_amd.model import init_model
 from dvs_of_training_framework_amd.optim import FusedAdamW, FusedRAdam, \
     FusedRanger
 from dvs_of_training_framework_amd.options import (
-    add_train_arguments, add_preprocessed_dataset_arguments, guard_requested,
-    resolve_step_guard, validate_train_args, window_kwargs)
+    add_train_arguments, add_preprocessed_dataset_arguments, avg_timestamp_keywords,
+    guard_requested, resolve_step_guard, validate_train_args, window_kwargs)
 from dvs_of_training_framework_amd.hooks import EvaluationHook, \
     SerializationHook, SharpnessHook, ValidationHook, VisualizationHook
 from dvs_of_training_framework_amd.serializer import Serializer
@@ -497,7 +497,8 @@ def main(argv=None):
                 'contrast_references': getattr(args, 'contrast_references', ('start',)),
                 'contrast_polarity': getattr(args, 'contrast_polarity', False),
                 'contrast_scales': getattr(args, 'contrast_scales', 'finest')}
-               if getattr(args, 'contrast_weight', 0.0) else {}))
+               if getattr(args, 'contrast_weight', 0.0) else {}),
+            **avg_timestamp_keywords(args))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
     elif not args.skip_validation:
         note('no validation data (--validation-sequence, --validation-recording, or '
@@ -526,7 +527,8 @@ def main(argv=None):
                   contrast_weight=getattr(args, 'contrast_weight', 0.0),
                   contrast_references=getattr(args, 'contrast_references', ('start',)),
                   contrast_polarity=getattr(args, 'contrast_polarity', False),
-                  contrast_scales=getattr(args, 'contrast_scales', 'finest'))
+                  contrast_scales=getattr(args, 'contrast_scales', 'finest'),
+                  **avg_timestamp_keywords(args))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
