@@ -105,6 +105,8 @@ def held_ranges(step):
     """[(lo, hi)] address ranges of the storages the step keeps alive."""
     from . import loss as loss_mod
     roots = [step._keep, step.static, step.loss, getattr(step._terms, 'packed', None),
+             # (the events-only terms of a step that carries them: static outputs too)
+             getattr(step._terms, 'contrast', None), getattr(step._terms, 'avg_timestamp', None),
              list(step.model.parameters()), list(step.model.buffers()),
              [v for st in step.optimizer.state.values() for v in st.values()],
              [p.grad for p in step.model.parameters()],

@@ -28,7 +28,17 @@ batch signature (batch size, frame size, event capacity) and replays it:
   * a step guard (``optim.set_guard``: gradient clipping, skip of a step with
     non-finite gradients) is two more kernel nodes in front of the updates of
     the roles that close a step, behind the gradient exchange; the updates
-    read its decision from a persistent 32-byte record.
+    read its decision from a persistent 32-byte record;
+  * the events-only terms -- the contrast-maximisation term with its scales,
+    reference times and polarities, the average-timestamp term -- are in the
+    step when ``loss_options`` names them (``training.train(capture=True,
+    capture_event_terms=True)``, opt-in): their kernels zero their workspace
+    with a fill kernel, sum in 64-bit integer atomics and leave a padded
+    event slot at the first test of the splat, so they add kernel nodes only,
+    and their values are static outputs beside the loss and the term table;
+  * a frameless batch (``'images': None``, ``'shape': (h, w)``;
+    docs/FRAMELESS_SPEC.md) is a signature of its own: no image buffer, the
+    frame size rides in the static batch.
 
 ROLES -- gradient accumulation (utils/options.py:318-325: ``bs // mbs``
 micro-batches per optimizer step, utils/training.py:156-167).  A micro-batch
@@ -211,7 +221,8 @@ def _event_layout(events):
 class CapturedTrainStep:
     def __init__(self, model, evaluator, optimizer, weights, device,
                  example_batch, event_capacity=None, executor=True, bind=False,
-                 reducer=None, role='full', accumulation_steps=1, share=None):
+                 reducer=None, role='full', accumulation_steps=1, share=None,
+                 loss_options=None):
         """example_batch: a batch of the signature to capture (wire-format or
         compact events; its tensors may live on the host).  The constructor
         runs ONE eager, validated micro-batch on it in the given role (host-
@@ -229,7 +240,15 @@ class CapturedTrainStep:
                   the step (needs executor=True)
         role, accumulation_steps:  see the module docstring
         share:    another CapturedTrainStep of the same signature whose input
-                  buffers this one reads (the roles of one loop)"""
+                  buffers this one reads (the roles of one loop)
+        loss_options:  the keywords ``training.train`` hands ``process_minibatch``
+                  for the events-only terms (``_contrast_keywords`` merged with
+                  ``_avg_timestamp_keywords``: a default option is absent); None or
+                  {}: the call without them
+
+        A frameless example batch (``'images': None``, ``'shape': (h, w)``;
+        docs/FRAMELESS_SPEC.md) gives a step without an image buffer: its
+        signature holds ('frameless', h, w) in place of the image shape."""
         assert all(hasattr(optimizer, m) for m in CAPTURE_PROTOCOL), \
             'the captured step needs an optimizer with begin_capture / advance / ' \
             'end_capture (optim.FusedAdamW, FusedRAdam, FusedRanger: what changes per ' \
@@ -242,6 +261,7 @@ class CapturedTrainStep:
         self.weights, self.device = list(weights), torch.device(device)
         self.reducer, self.role, self.accum = reducer, role, int(accumulation_steps)
         self.closes = role in ('full', 'last')
+        self.loss_options = dict(loss_options or {})
         exchanging = reducer is not None and self.closes and self._would_exchange()
         assert executor or not exchanging, \
             'the gradient exchange of a captured step is issued by the step executor'
@@ -263,7 +283,7 @@ class CapturedTrainStep:
             assert not bind and share.fits(example_batch)
             self.capacity, self.static = share.capacity, share.static
         elif bind:
-            assert all(t.is_cuda for t in (ev['x'], example_batch['images'])), \
+            assert all(t.is_cuda for t in (ev['x'], example_batch['images']) if t is not None), \
                 'bind=True needs a device-resident batch'
             self.capacity = n
             self.static = {'events': {k: ev[k] for k in self.keys},
@@ -271,6 +291,8 @@ class CapturedTrainStep:
                            'sample_idx': example_batch['sample_idx'],
                            'images': example_batch['images'],
                            'size': int(example_batch['size'])}
+            if example_batch['images'] is None:
+                self.static['shape'] = tuple(int(v) for v in example_batch['shape'])
         else:
             self.capacity = event_capacity or _pow2_at_least(n)
             assert n <= self.capacity
@@ -280,9 +302,12 @@ class CapturedTrainStep:
                            for k in self.keys},
                 'timestamps': torch.zeros_like(example_batch['timestamps'], device=dev),
                 'sample_idx': torch.zeros_like(example_batch['sample_idx'], device=dev),
-                'images': torch.zeros_like(example_batch['images'], device=dev),
+                'images': None if example_batch['images'] is None else
+                torch.zeros_like(example_batch['images'], device=dev),
                 'size': int(example_batch['size']),
             }
+            if example_batch['images'] is None:
+                self.static['shape'] = tuple(int(v) for v in example_batch['shape'])
         self.signature = self._signature(example_batch)
         if not bind:
             self._load(example_batch)
@@ -294,7 +319,7 @@ class CapturedTrainStep:
             # (inside the capture they would become graph-owned ATen launches)
             model.strict = False
             model._select(self.static['timestamps'], self.static['sample_idx'],
-                          self.static['size'])
+                          self.static['size'])      # (a frameless batch has the same two tables)
         self.tags = list(tags)
         self.first_loss, self.first_terms = loss.detach().clone(), terms
         terms.host()
@@ -328,7 +353,7 @@ class CapturedTrainStep:
             red.enabled = self.closes
         loss, terms, tags = process_minibatch(
             self.model, batch, timers, self.device, True, self.evaluator,
-            self.weights)
+            self.weights, **self.loss_options)
         if self.accum == 1:
             unit_backward(loss)
         else:
@@ -387,7 +412,10 @@ class CapturedTrainStep:
         with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
             loss, terms, _ = self._body(self.static, FakeTimer())
         self.loss = loss.detach()
-        self._terms = terms._terms      # _Terms: .packed is the [3,K] tensor
+        # _Terms: .packed is the [3,K] tensor; with an events-only term a _TermsAndContrast,
+        # whose .contrast (0-dim, or [K] on every scale) and .avg_timestamp are static outputs
+        # of the graph like .packed: held here, read after a replay through TermReadback
+        self._terms = terms._terms
         self._keep.append(optimizer._dyn)
         if executor:
             pred = model.predictor
@@ -413,8 +441,10 @@ class CapturedTrainStep:
     # ------------------------------------------------------------ the batch
     @staticmethod
     def _signature(batch):
-        return (int(batch['size']), tuple(batch['images'].shape),
-                tuple(batch['timestamps'].shape),
+        images = batch['images']
+        frame = ('frameless',) + tuple(int(v) for v in batch['shape']) if images is None \
+            else tuple(images.shape)
+        return (int(batch['size']), frame, tuple(batch['timestamps'].shape),
                 voxel.is_compact(batch['events']))
 
     def same_signature(self, batch):
@@ -439,7 +469,8 @@ class CapturedTrainStep:
             if 'sample_index' in st:
                 st['sample_index'][n:] = 0
         for k in ('timestamps', 'sample_idx', 'images'):
-            self.static[k].copy_(batch[k], non_blocking=True)
+            if self.static[k] is not None:      # (a frameless step has no image buffer)
+                self.static[k].copy_(batch[k], non_blocking=True)
 
     def __call__(self, batch=None):
         """-> (loss, terms): 0-dim tensor and a TermReadback, both reading the
@@ -493,8 +524,9 @@ class CapturedLoop:
 
     def __init__(self, model, evaluator, optimizer, weights, device,
                  accumulation_steps=1, reducer=None, executor=True,
-                 event_capacity=None):
+                 event_capacity=None, loss_options=None):
         self.args = (model, evaluator, optimizer, weights, device)
+        self.loss_options = dict(loss_options or {})    # of the events-only terms, for every step
         self.accum, self.reducer, self.executor = accumulation_steps, reducer, executor
         self.event_capacity = event_capacity
         self.steps = {}         # role -> step over this loop's own input buffers
@@ -530,7 +562,8 @@ class CapturedLoop:
             try:
                 step = self.bound[key] = CapturedTrainStep(
                     *self.args, batch, executor=self.executor, bind=True,
-                    reducer=self.reducer, role=role, accumulation_steps=self.accum)
+                    reducer=self.reducer, role=role, accumulation_steps=self.accum,
+                    loss_options=self.loss_options)
             except CaptureFailed as e:
                 return self._failed(e, role)
             return step.first_loss, step.first_terms, step.tags
@@ -559,7 +592,7 @@ class CapturedLoop:
                 step = self.steps[role] = CapturedTrainStep(
                     *self.args, batch, event_capacity=cap, executor=self.executor,
                     reducer=self.reducer, role=role, accumulation_steps=self.accum,
-                    share=lead)
+                    share=lead, loss_options=self.loss_options)
             except CaptureFailed as e:
                 return self._failed(e, role)
             return step.first_loss, step.first_terms, step.tags
@@ -576,7 +609,7 @@ class CapturedLoop:
             (v for k, v in self.bound.items() if k[0] == role), None)
         if proto is not None:
             return proto.eager_step(batch, timers)
-        body = _EagerBody(*self.args, self.reducer, role, self.accum)
+        body = _EagerBody(*self.args, self.reducer, role, self.accum, self.loss_options)
         opt = self.args[2]
         was = getattr(opt, '_use_dyn', False)
         if was:
@@ -596,9 +629,10 @@ class _EagerBody(CapturedTrainStep):
     """The body of a role without a recording (CapturedLoop fall-back)."""
 
     def __init__(self, model, evaluator, optimizer, weights, device, reducer,
-                 role, accumulation_steps):     # noqa: super().__init__ records
+                 role, accumulation_steps, loss_options=None):  # noqa: super().__init__ records
         self.model, self.evaluator, self.optimizer = model, evaluator, optimizer
         self.weights, self.device = list(weights), torch.device(device)
         self.reducer, self.role, self.accum = reducer, role, int(accumulation_steps)
         self.closes = role in ('full', 'last')
+        self.loss_options = dict(loss_options or {})
         self.executor = None

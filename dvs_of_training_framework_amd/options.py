@@ -170,7 +170,9 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'once a batch signature has been seen (capture.CapturedLoop '
                              '/ the step executor; ADAM; with or without gradient '
                              'accumulation, with or without data parallelism -- the '
-                             'executor then issues the gradient exchange)')
+                             'executor then issues the gradient exchange; a run with '
+                             '--contrast-weight or --avg-timestamp-weight is replayed '
+                             'with --capture-event-terms, and runs eagerly without it)')
     parser.add_argument('--optimizer-in-backward', dest='optimizer_in_backward',
                         default='auto', choices=['auto', 'on', 'off'],
                         help='(auto resolves to off, and on is an error, with '
@@ -306,7 +308,8 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              '(docs/CONTRAST_SPEC.md); logged as Train/contrast and '
                              'Validation/contrast.  Needs the raw events in their wire '
                              'columns on the device (not --ev_images, not '
-                             '--compact-events); such a run is not captured.  0: off')
+                             '--compact-events); --capture replays such a run only with '
+                             '--capture-event-terms.  0: off')
     parser.add_argument('--contrast-references', dest='contrast_references',
                         default='start', type=str,
                         help='comma-separated reference times of the contrast term, among '
@@ -337,7 +340,8 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'Train/avg timestamp and Validation/avg timestamp.  With or '
                              'without --contrast-weight.  Needs the raw events in their wire '
                              'columns on the device (not --ev_images, not --compact-events); '
-                             'such a run is not captured.  Absent or 0: off')
+                             '--capture replays such a run only with --capture-event-terms.  Absent or 0: '
+                             'off')
     parser.add_argument('--avg-timestamp-references', dest='avg_timestamp_references',
                         default=argparse.SUPPRESS, type=str,
                         help='comma-separated reference times of the average-timestamp term, '
@@ -347,6 +351,13 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         default=argparse.SUPPRESS, action='store_true',
                         help='accumulate ON and OFF events in images of their own in the '
                              'average-timestamp term.  Needs --avg-timestamp-weight')
+    parser.add_argument('--capture-event-terms', dest='capture_event_terms',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='with --capture and a positive --contrast-weight or '
+                             '--avg-timestamp-weight: the captured step carries those terms, '
+                             'with all their options, and the frameless batches of --recording, '
+                             'instead of running the loop eagerly for them; bit-identical to '
+                             'the eager step.  Opt-in: without it --capture decides as before')
     parser.add_argument('--recording', dest='recording', default=None, type=Path,
                         help='train from ONE event-only recording kept on the device: a '
                              '.npz or .hdf5 file with the arrays x, y, t, p (sorted by t) and '
@@ -424,8 +435,23 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_frameless_args(validate_sharpness_args(validate_avg_timestamp_args(
-        validate_contrast_args(args))))
+    return validate_capture_event_terms_args(validate_frameless_args(validate_sharpness_args(
+        validate_avg_timestamp_args(validate_contrast_args(args)))))
+
+
+def validate_capture_event_terms_args(args):
+    """--capture-event-terms (absent from ``args`` unless given) against what
+    it needs: --capture, and a term to carry."""
+    if not getattr(args, 'capture_event_terms', False):
+        return args
+    if not getattr(args, 'capture', False):
+        raise SystemExit('--capture-event-terms needs --capture: it says what the captured step '
+                         'carries')
+    if not (getattr(args, 'contrast_weight', 0.0) > 0 or getattr(args, 'avg_timestamp_weight', 0.0) > 0):
+        raise SystemExit('--capture-event-terms needs a positive --contrast-weight or '
+                         '--avg-timestamp-weight: without either there is no events-only term to '
+                         'capture')
+    return args
 
 
 CONTRAST_REFERENCE_NAMES = ('start', 'middle', 'end')

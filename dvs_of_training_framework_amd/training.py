@@ -509,6 +509,27 @@ def avg_timestamp_capture_refusal(avg_timestamp_weight=0.0):
     return None
 
 
+EVENT_TERM_METHODS = ('contrast', 'avg_timestamp', 'frameless')
+
+
+def event_terms_capture_refusal(evaluator, is_raw, needs=EVENT_TERM_METHODS[:2]):
+    """Why ``train(capture=True, capture_event_terms=True)`` cannot replay a
+    step that holds an events-only term (None: it can), beyond what
+    ``capture_refusal(optimizer, is_raw, model)`` says.  needs: the evaluator's
+    methods the run will call, among ``EVENT_TERM_METHODS`` (``train`` names
+    those of the terms whose weight is positive; 'frameless' for a caller that
+    knows its batches carry no frames)."""
+    if not is_raw:
+        return ('is_raw=False batches (preprocessed voxel grids) carry no events: the '
+                'events-only terms cannot be computed, let alone captured')
+    missing = [m for m in needs if not callable(getattr(evaluator, m, None))]
+    if missing:
+        return (f'evaluator {type(evaluator).__name__} has no {" / ".join(missing)} '
+                '(loss.Losses has contrast, avg_timestamp and frameless): the captured step '
+                'records the evaluator\'s own kernels')
+    return None
+
+
 def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           evaluator, weights=[0.5, 1, 1], is_raw=True, accumulation_steps=1,
           timers=None, hooks={}, init_step=0, init_samples_passed=0,
@@ -517,6 +538,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           max_skipped_steps: int = 32, guard_agreement_every: int = 0,
           contrast_weight: float = 0.0, contrast_references=('start',),
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
+          capture_event_terms: bool = False,
           avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
@@ -551,8 +573,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                this (the checkpointing interval; 0: never)
     contrast_weight:  > 0 adds this times the contrast-maximisation term of
                the finest flow to the loss (docs/CONTRAST_SPEC.md; raw events
-               only), logged as ``Train/contrast``; such a run is not
-               captured.  0: the step launches what it launches without it
+               only), logged as ``Train/contrast``; such a run is
+               captured with ``capture_event_terms`` only.  0: the step
+               launches what it launches without it
     contrast_references, contrast_polarity:  the reference times of that term
                ('start', 'middle', 'end') and whether ON and OFF events are
                accumulated apart (``loss.Losses.contrast``)
@@ -563,11 +586,24 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
                the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
                events only), logged as ``Train/avg timestamp``, beside the
-               contrast term or without it; such a run is not captured.  0:
+               contrast term or without it; such a run is captured with
+               ``capture_event_terms`` only.  0:
                the step launches what it launches without it
     avg_timestamp_references, avg_timestamp_polarity:  the reference times of
                that term (default: both ends of the window) and whether ON
                and OFF events are accumulated apart
+    capture_event_terms:  with ``capture`` and a positive contrast_weight or
+               avg_timestamp_weight: the captured step carries those terms
+               (their keywords travel as ``CapturedLoop(loss_options=...)``)
+               and frameless batches, instead of refusing for the weights;
+               ``Train/contrast``, ``Train/contrast/<tag>`` and ``Train/avg
+               timestamp`` are then logged from replays.  What
+               ``capture_refusal(optimizer, is_raw, model)`` and
+               ``event_terms_capture_refusal`` name still runs the eager loop
+               and says so.  False (the default): every decision, line on
+               stderr and launch as without the keyword.  (Pass it by name: it
+               stands in front of the avg_timestamp keywords, whose place at
+               the end is held by a test)
 
     A loader of frameless batches (sequence.EventWindowLoader: is_raw=True,
     ``'images': None``) needs contrast_weight > 0; the photometric rows are
@@ -580,15 +616,28 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                        init_samples_passed)
     sums = ScaleSums()
     captured = None
-    refused = (avg_timestamp_capture_refusal(avg_timestamp_weight)
-               or capture_refusal(optimizer, is_raw, model, contrast_weight)) if capture else None
+    # the opt-in: the captured step carries the events-only terms that are asked for
+    event_terms = {}
+    if capture and capture_event_terms:
+        event_terms = dict(
+            _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales),
+            **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
+                                      avg_timestamp_polarity))
+    if event_terms:
+        refused = capture_refusal(optimizer, is_raw, model) or event_terms_capture_refusal(
+            evaluator, is_raw, [m for m, w in zip(EVENT_TERM_METHODS, (contrast_weight, avg_timestamp_weight))
+                                if w])
+    else:
+        refused = (avg_timestamp_capture_refusal(avg_timestamp_weight)
+                   or capture_refusal(optimizer, is_raw, model, contrast_weight)) if capture else None
     if refused:
         import sys
         print(f'capture: not used, the loop runs eagerly: {refused}', file=sys.stderr)
     elif capture:
         from .capture import CapturedLoop
         captured = CapturedLoop(model, evaluator, optimizer, weights, device,
-                                accumulation_steps, reducer)
+                                accumulation_steps, reducer,
+                                **({'loss_options': event_terms} if event_terms else {}))
     model.train()
     optimizer.zero_grad(set_to_none=True)
 

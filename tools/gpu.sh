@@ -45,6 +45,11 @@
 #                                     with polarity, batch 8, 256x256, 65 536 events per sample, and one eager Ranger
 #                                     step with and without --avg-timestamp-weight, in alternating blocks of one run
 #                                     (profiles/avg_timestamp/README.md)
+#   eventcapture [event_terms_capture_bench.py args]  the captured step with the events-only terms
+#                                     (--capture-event-terms; tools/event_terms_capture_bench.py): framed + contrast,
+#                                     frameless + contrast on every scale, the same + average timestamp, f32 and bf16s,
+#                                     eager loop against executor replay in alternating blocks of one run after a
+#                                     bitwise comparison of the two (profiles/event_terms_capture/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -122,6 +127,9 @@ frameless)
 avgts)
   timeout -k 10 540 env "${envs[@]}" python tools/avg_timestamp_bench.py "$@" > $O/avgts.json 2> $O/avgts.err
   echo "avgts rc=$?"; cut -c1-3600 $O/avgts.json; tail -3 $O/avgts.err ;;
+eventcapture)
+  timeout -k 10 560 env "${envs[@]}" python tools/event_terms_capture_bench.py "$@" > $O/eventcapture.jsonl 2> $O/eventcapture.err
+  echo "eventcapture rc=$?"; cut -c1-900 $O/eventcapture.jsonl; tail -3 $O/eventcapture.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

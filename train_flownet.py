@@ -528,7 +528,9 @@ def main(argv=None):
                   contrast_references=getattr(args, 'contrast_references', ('start',)),
                   contrast_polarity=getattr(args, 'contrast_polarity', False),
                   contrast_scales=getattr(args, 'contrast_scales', 'finest'),
-                  **avg_timestamp_keywords(args))
+                  **avg_timestamp_keywords(args),
+                  **({'capture_event_terms': True}
+                     if getattr(args, 'capture_event_terms', False) else {}))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
