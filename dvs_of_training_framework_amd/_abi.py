@@ -43,6 +43,9 @@ LOSS_FRAMELESS_PATH = HEADER_PATH.with_name('dvsof_loss_frameless.h')
 CONTRAST_PYRAMID_PATH = HEADER_PATH.with_name('dvsof_contrast_pyramid.h')
 # And the average-timestamp term (AVG_TIMESTAMP_FUNCTIONS), functions only
 AVG_TIMESTAMP_PATH = HEADER_PATH.with_name('dvsof_avg_timestamp.h')
+# And that term on every flow scale (AVG_TIMESTAMP_PYRAMID_FUNCTIONS): functions only, which take
+# the level table of dvsof_contrast_pyramid.h
+AVG_TIMESTAMP_PYRAMID_PATH = HEADER_PATH.with_name('dvsof_avg_timestamp_pyramid.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -186,11 +189,13 @@ FUNCTIONS, STRUCTS, CONSTANTS = _header.functions, _header.structs, _header.cons
 EXTENSION_FUNCTIONS = {}
 
 
-def _read_extension(path, taken):
-    """The functions of one extension header; ``taken``: the names it must not repeat."""
-    ext = Abi(path.read_text(), base=_header, name=path.name)
+def _read_extension(path, taken, base=None):
+    """The functions of one extension header; ``taken``: the names it must not repeat;
+    ``base``: the Abi of the header it includes, whose struct types it may name (dvsof.h)."""
+    base = _header if base is None else base
+    ext = Abi(path.read_text(), base=base, name=path.name)
     clash = set(ext.functions) & set(taken)
-    if clash or ext.constants or set(ext.structs) != set(STRUCTS):
+    if clash or ext.constants or set(ext.structs) != set(base.structs):
         raise AbiError(f'{path.name}: an extension header declares new functions only '
                        f'({sorted(clash) or "constants or structs found"})')
     return ext.functions
@@ -213,12 +218,18 @@ def _read_struct_extension(path, taken):
     if clash or ext.constants or not set(STRUCTS) <= set(ext.structs):
         raise AbiError(f'{path.name}: an extension header declares new functions and structs only '
                        f'({sorted(clash) or "constants found"})')
+    _struct_headers[path] = ext
     return ext.functions, {k: v for k, v in ext.structs.items() if k not in STRUCTS}
 
 
+_struct_headers = {}    # {path: Abi} of the extension headers with structs, for those that include them
 CONTRAST_PYRAMID_FUNCTIONS, CONTRAST_PYRAMID_STRUCTS = _read_struct_extension(
     CONTRAST_PYRAMID_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
     | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS))
 AVG_TIMESTAMP_FUNCTIONS = _read_extension(
     AVG_TIMESTAMP_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
     | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS))
+AVG_TIMESTAMP_PYRAMID_FUNCTIONS = _read_extension(
+    AVG_TIMESTAMP_PYRAMID_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
+    | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS)
+    | set(AVG_TIMESTAMP_FUNCTIONS), base=_struct_headers[CONTRAST_PYRAMID_PATH])

@@ -105,7 +105,9 @@ def held_ranges(step):
     """[(lo, hi)] address ranges of the storages the step keeps alive."""
     from . import loss as loss_mod
     roots = [step._keep, step.static, step.loss, getattr(step._terms, 'packed', None),
-             # (the events-only terms of a step that carries them: static outputs too)
+             # (the events-only terms of a step that carries them: static outputs too, 0-dim or the
+             # [K] of every scale; their workspaces come from the graph's pool, and the level flows
+             # and gradients of a by-value level table are read word by word below)
              getattr(step._terms, 'contrast', None), getattr(step._terms, 'avg_timestamp', None),
              list(step.model.parameters()), list(step.model.buffers()),
              [v for st in step.optimizer.state.values() for v in st.values()],

@@ -14,7 +14,9 @@ tests/golden/abi_signatures_loss_frameless.json; _abi.CONTRAST_PYRAMID_PATH:
 include/dvsof_contrast_pyramid.h, recorded in
 tests/golden/abi_signatures_contrast_pyramid.json; _abi.AVG_TIMESTAMP_PATH:
 include/dvsof_avg_timestamp.h, recorded in
-tests/golden/abi_signatures_avg_timestamp.json).
+tests/golden/abi_signatures_avg_timestamp.json; _abi.AVG_TIMESTAMP_PYRAMID_PATH:
+include/dvsof_avg_timestamp_pyramid.h, recorded in
+tests/golden/abi_signatures_avg_timestamp_pyramid.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -51,6 +53,8 @@ ContrastLevel = _abi.CONTRAST_PYRAMID_STRUCTS['dvsof_contrast_level_t']
 ContrastLevels = _abi.CONTRAST_PYRAMID_STRUCTS['dvsof_contrast_levels_t']
 # and of include/dvsof_avg_timestamp.h, functions only
 _AVG_TIMESTAMP_SIGNATURES = _abi.AVG_TIMESTAMP_FUNCTIONS
+# and of include/dvsof_avg_timestamp_pyramid.h, which takes the level table above
+_AVG_TIMESTAMP_PYRAMID_SIGNATURES = _abi.AVG_TIMESTAMP_PYRAMID_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -101,6 +105,11 @@ def declared_avg_timestamp_symbols():
     return _declared_in((_abi.AVG_TIMESTAMP_PATH,))
 
 
+def declared_avg_timestamp_pyramid_symbols():
+    """Names of all entry points include/dvsof_avg_timestamp_pyramid.h declares."""
+    return _declared_in((_abi.AVG_TIMESTAMP_PYRAMID_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -116,7 +125,8 @@ def lib():
         LOADED_STAT = (st.st_ino, st.st_size, st.st_mtime_ns)
         for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES,
                                   **_IWE_MULTI_SIGNATURES, **_LOSS_FRAMELESS_SIGNATURES,
-                                  **_CONTRAST_PYRAMID_SIGNATURES, **_AVG_TIMESTAMP_SIGNATURES}.items():
+                                  **_CONTRAST_PYRAMID_SIGNATURES, **_AVG_TIMESTAMP_SIGNATURES,
+                                  **_AVG_TIMESTAMP_PYRAMID_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

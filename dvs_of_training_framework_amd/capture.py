@@ -413,7 +413,7 @@ class CapturedTrainStep:
             loss, terms, _ = self._body(self.static, FakeTimer())
         self.loss = loss.detach()
         # _Terms: .packed is the [3,K] tensor; with an events-only term a _TermsAndContrast,
-        # whose .contrast (0-dim, or [K] on every scale) and .avg_timestamp are static outputs
+        # whose .contrast and .avg_timestamp (0-dim, or [K] on every scale) are static outputs
         # of the graph like .packed: held here, read after a replay through TermReadback
         self._terms = terms._terms
         self._keep.append(optimizer._dyn)

@@ -87,8 +87,8 @@ class ValidationHook:
 
     def __init__(self, model, device, loader, logger, losses, weights, is_raw,
                  contrast_weight=0.0, contrast_references=('start',), contrast_polarity=False,
-                 contrast_scales='finest', avg_timestamp_weight=0.0, avg_timestamp_references=('start', 'end'),
-                 avg_timestamp_polarity=False):
+                 contrast_scales='finest', avg_timestamp_scales='finest', avg_timestamp_weight=0.0,
+                 avg_timestamp_references=('start', 'end'), avg_timestamp_polarity=False):
         self.model, self.device, self.loader = model, device, loader
         self.logger, self.losses = logger, losses
         self.weights = deepcopy(weights)
@@ -101,6 +101,8 @@ class ValidationHook:
             self.extra.update(avg_timestamp_weight=avg_timestamp_weight,
                               avg_timestamp_references=tuple(avg_timestamp_references),
                               avg_timestamp_polarity=bool(avg_timestamp_polarity))
+            if avg_timestamp_scales != 'finest':
+                self.extra['avg_timestamp_scales'] = avg_timestamp_scales
 
     def __call__(self, steps, samples):
         with model_left_as_found(self.model):

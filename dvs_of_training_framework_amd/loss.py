@@ -15,8 +15,10 @@ Differences that are deliberate (MI355X-first):
     out-of-border alone, no pyramid and no frame read (csrc/loss_frameless.hip,
     docs/FRAMELESS_SPEC.md);
   * ``Losses.contrast`` and ``Losses.avg_timestamp`` are training terms from the
-    events alone, on the finest flow (csrc/contrast.hip, csrc/avg_timestamp.hip;
-    docs/CONTRAST_SPEC.md, docs/AVG_TIMESTAMP_SPEC.md).
+    events alone, on the finest flow or, with ``scales='all'``
+    (``Losses.avg_timestamp_scales`` for the second), on every flow
+    (csrc/contrast.hip, csrc/avg_timestamp.hip; docs/CONTRAST_SPEC.md,
+    docs/AVG_TIMESTAMP_SPEC.md).
 """
 import ctypes
 
@@ -904,6 +906,134 @@ class _AvgTimestamp(torch.autograd.Function):
         return (grad,) + (None,) * 10
 
 
+# The term on every flow scale (csrc/avg_timestamp.hip, AVG_TIMESTAMP_SPEC sections 11-15)
+AVG_TIMESTAMP_SCALES = ('finest', 'all')
+
+
+def avg_timestamp_pyramid_layout(F, M, level_shapes):
+    """The byte offsets of include/dvsof_avg_timestamp_pyramid.h for levels of
+    the shapes ``level_shapes`` -> dict: q, s, base, sums, count,
+    zeroed_bytes, rec, unit, rows, part, bytes, nb (the largest level's),
+    pixels (sum_k h_k w_k)."""
+    from . import eval as ev
+    K = len(level_shapes)
+    pixels = sum(int(h) * int(w) for h, w in level_shapes)
+    P, S = M * pixels, 2 * F * pixels
+    nb = max(ev.partial_blocks(int(h) * int(w)) for h, w in level_shapes)
+    o = dict(q=0, s=8 * P, base=16 * P, sums=24 * P, count=24 * P + 8 * S, nb=nb, pixels=pixels)
+    o['zeroed_bytes'] = o['count'] + 4 * P
+    o['rec'] = (o['zeroed_bytes'] + 7) // 8 * 8
+    o['unit'] = o['rec'] + 64 * K * M
+    o['rows'] = o['unit'] + 8 * K * F
+    o['part'] = o['rows'] + 32 * K * M
+    o['bytes'] = o['part'] + 32 * M * nb
+    return o
+
+
+def avg_timestamp_pyramid_fwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flows, shape, weights=None,
+                                   references=('start', 'end'), polarity=False):
+    """AVG_TIMESTAMP_SPEC sections 11-13 on the host: what
+    ``dvsof_avg_timestamp_pyramid_fwd`` is pinned to, byte for byte.  The
+    arguments of ``contrast_pyramid_fwd_host``.  Per level
+    ``avg_timestamp_fwd_host`` on the quantised columns, then the combination
+    -> dict: levels (the K dicts of that function), shifts, weights float32
+    [K], terms float32 [K] (unweighted), terms64, value float32."""
+    K = len(flows)
+    if not 1 <= K <= CONTRAST_MAX_LEVELS:
+        raise ValueError(f'{K} levels: the level table holds 1 to {CONTRAST_MAX_LEVELS}')
+    flows = [np.asarray(f, _F32) for f in flows]
+    shifts = [contrast_level_shift(shape, f.shape[-2:]) for f in flows]
+    weights = np.asarray(contrast_level_weights(1.0, K) if weights is None else weights, _F32)
+    assert weights.shape == (K,)
+    levels = []
+    for flow, s in zip(flows, shifts):
+        xs, ys = contrast_level_columns(x, y, shape, s)
+        levels.append(avg_timestamp_fwd_host(xs, ys, t, p, sample_index, frame_ts, frame_sample, flow,
+                                             references, polarity))
+    terms64 = np.zeros(K, np.float64)
+    total = np.float64(0)
+    with np.errstate(all='ignore'):
+        for k, lev in enumerate(levels):        # in level order
+            s = np.float64(0)
+            for v in lev['image_value']:        # in image order
+                s = s + v
+            terms64[k] = s / np.float64(len(lev['image_value']))
+            total = total + np.float64(weights[k]) * terms64[k]
+        return dict(levels=levels, shifts=shifts, weights=weights, terms=terms64.astype(_F32), terms64=terms64,
+                    value=_F32(total), shape=tuple(int(v) for v in shape))
+
+
+def avg_timestamp_pyramid_bwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flows, fwd, seed=1.0):
+    """AVG_TIMESTAMP_SPEC section 14 on the host: what
+    ``dvsof_avg_timestamp_pyramid_bwd`` is pinned to.  fwd: the dict of
+    ``avg_timestamp_pyramid_fwd_host`` for the same input.  -> one
+    (grad_flow_k float32 [F,2,h_k,w_k] = seed * weight_k * d term_k / d flow_k,
+    sums int64 [F,2,h_k,w_k]) per level."""
+    out = []
+    for flow, s, lev, weight in zip(flows, fwd['shifts'], fwd['levels'], fwd['weights']):
+        xs, ys = contrast_level_columns(x, y, fwd['shape'], s)
+        out.append(avg_timestamp_bwd_host(xs, ys, t, p, sample_index, frame_ts, frame_sample, flow, lev,
+                                          seed=seed, weight=weight))
+    return out
+
+
+class _AvgTimestampPyramid(torch.autograd.Function):
+    """(sum_k weight_k term_k, terms [K]) of all flows; the gradient of the
+    first enters every flow (dvsof_avg_timestamp_pyramid_fwd /
+    dvsof_avg_timestamp_pyramid_bwd: one splat and one backward for all
+    levels).  The images live in the workspace; the weights are applied inside
+    the kernels."""
+
+    @staticmethod
+    def forward(ctx, x, y, t, p, sample_index, frame_ts, frame_sample, shape, weights, mask, polarity, *flows):
+        dev = flows[0].device
+        flows = tuple(f.detach().contiguous().float() for f in flows)
+        K, F = len(flows), flows[0].shape[0]
+        assert all(f.shape[0] == F and f.shape[1] == 2 for f in flows)
+        lib = _lib.lib()
+        M = F * bin(mask).count('1') * (2 if polarity else 1)
+        shapes = [tuple(f.shape[-2:]) for f in flows]
+        table = contrast_level_table(shape, shapes, F, M, weights, [f.data_ptr() for f in flows])
+        terms = torch.zeros(K, dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty(K, dtype=torch.float32, device=dev)
+        value = torch.zeros((), dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+        h, w = (int(v) for v in shape)
+        nbytes = lib.dvsof_avg_timestamp_pyramid_workspace_bytes(F, mask, int(polarity), h, w, table)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
+        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
+        pol = p.contiguous() if polarity else None
+        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
+        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flows[0].shape, frame_ts.shape)
+        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
+        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
+        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
+        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
+                                                        tables[0].data_ptr(), tables[1].data_ptr(),
+                                                        F, h, w, mask, int(polarity)])
+        _lib.check(lib.dvsof_avg_timestamp_pyramid_fwd(
+            *ctx.args, table, terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
+            'dvsof_avg_timestamp_pyramid_fwd')
+        ctx.held = (cols, pol, tables, flows, ws, nbytes, table)
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)
+        return value, terms
+
+    @staticmethod
+    def backward(ctx, g_value, _g_terms):
+        flows, ws, nbytes, table = ctx.held[3:]
+        if g_value is None:
+            return (None,) * (11 + len(flows))
+        grads = tuple(torch.empty_like(f) for f in flows)
+        for k, g in enumerate(grads):
+            table.level[k].grad_flow = g.data_ptr()
+        seed = g_value.contiguous().float()
+        _lib.check(_lib.lib().dvsof_avg_timestamp_pyramid_bwd(
+            *ctx.args, table, ws.data_ptr(), nbytes, seed.data_ptr(), _lib.stream()),
+            'dvsof_avg_timestamp_pyramid_bwd')
+        return (None,) * 11 + grads
+
+
 class Loss:
     """Single-scale evaluator (reference utils/loss.py:38-171)."""
 
@@ -1091,7 +1221,8 @@ class Losses:
         references: names among 'start', 'middle', 'end'; the default warps
         to both ends of the window (Zhu et al., CVPR 2019): at one end alone
         the events that need no warp carry no distance.  polarity: ON and OFF
-        events in images of their own."""
+        events in images of their own.  The term on every flow scale is
+        ``avg_timestamp_scales``."""
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the average-timestamp term of scale {self.shapes[-1]}'
@@ -1105,7 +1236,32 @@ class Losses:
                                           bool(polarity))
         return value if weight is None else (value, term)
 
+    def avg_timestamp_scales(self, flows, flow_ts, flow_sample_idx, events, weight=None,
+                             references=('start', 'end'), polarity=False, scales='finest'):
+        """``avg_timestamp`` with the choice of the flow scales (a method of
+        its own: the signature of ``avg_timestamp`` is held as it is).
+        scales='all': the term of every flow on the events quantised to that
+        flow's grid (AVG_TIMESTAMP_SPEC sections 11-15), one splat and one
+        backward for all levels; each level weighs float32(weight) /
+        float32(K), the mean over the scales.  -> the 0-dim weighted sum,
+        differentiable with respect to every flow (without a ``weight``: the
+        mean of the levels' terms); with a ``weight`` -> (that, terms [K]),
+        the levels' unweighted terms detached for logging.  A level that is no
+        halving of the finest is refused (``contrast_level_shift``).
+        'finest', the default, is ``avg_timestamp`` and constructs nothing
+        else; any other name raises ValueError."""
+        if scales == 'finest':
+            return self.avg_timestamp(flows, flow_ts, flow_sample_idx, events, weight, references, polarity)
+        if scales not in AVG_TIMESTAMP_SCALES:
+            raise ValueError(f'unknown avg-timestamp scales "{scales}": one of {", ".join(AVG_TIMESTAMP_SCALES)}')
+        return self._event_term_all(_AvgTimestampPyramid, flows, flow_ts, flow_sample_idx, events, weight,
+                                    references, polarity)
+
     def _contrast_all(self, flows, flow_ts, flow_sample_idx, events, weight, references, polarity):
+        return self._event_term_all(_ContrastPyramid, flows, flow_ts, flow_sample_idx, events, weight,
+                                    references, polarity)
+
+    def _event_term_all(self, function, flows, flow_ts, flow_sample_idx, events, weight, references, polarity):
         self._check_flows(flows)
         cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
         _lib.require_cuda(flow_ts, flow_sample_idx, *flows, *cols)
@@ -1115,8 +1271,8 @@ class Losses:
         weights = contrast_level_weights(1.0 if weight is None else weight, len(flows))
         pol = events['polarity'] if polarity else None
         _lib.require_cuda(pol)
-        value, terms = _ContrastPyramid.apply(*cols[:3], pol, cols[3], flow_ts, flow_sample_idx,
-                                              self.shapes[-1], weights, mask, bool(polarity), *flows)
+        value, terms = function.apply(*cols[:3], pol, cols[3], flow_ts, flow_sample_idx,
+                                      self.shapes[-1], weights, mask, bool(polarity), *flows)
         return value if weight is None else (value, terms)
 
 

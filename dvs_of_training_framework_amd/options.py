@@ -351,6 +351,15 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         default=argparse.SUPPRESS, action='store_true',
                         help='accumulate ON and OFF events in images of their own in the '
                              'average-timestamp term.  Needs --avg-timestamp-weight')
+    parser.add_argument('--avg-timestamp-scales', dest='avg_timestamp_scales',
+                        default=argparse.SUPPRESS, choices=('finest', 'all'),
+                        help='the flow scales the average-timestamp term is taken on: finest '
+                             '(the default) supervises the finest flow alone; all takes the term '
+                             'of every flow head on the events quantised to that head\'s grid, '
+                             'each level weighing --avg-timestamp-weight / K, and logs Train/avg '
+                             'timestamp/<tag> per level beside the mean '
+                             '(docs/AVG_TIMESTAMP_SPEC.md sections 11-15).  Needs '
+                             '--avg-timestamp-weight')
     parser.add_argument('--capture-event-terms', dest='capture_event_terms',
                         default=argparse.SUPPRESS, action='store_true',
                         help='with --capture and a positive --contrast-weight or '
@@ -500,7 +509,7 @@ AVG_TIMESTAMP_REFERENCES = ('start', 'end')
 
 def validate_avg_timestamp_args(args):
     """--avg-timestamp-weight against what it cannot be combined with, and the
-    term's options against a run without the term.  The three options are
+    term's options against a run without the term.  The options are
     absent from ``args`` unless given (read them with ``getattr``); a given
     ``args.avg_timestamp_references`` becomes a tuple of names."""
     weight = getattr(args, 'avg_timestamp_weight', 0.0)
@@ -514,6 +523,8 @@ def validate_avg_timestamp_args(args):
             raise SystemExit('--avg-timestamp-references needs a positive --avg-timestamp-weight')
         if getattr(args, 'avg_timestamp_polarity', False):
             raise SystemExit('--avg-timestamp-polarity needs a positive --avg-timestamp-weight')
+        if getattr(args, 'avg_timestamp_scales', 'finest') != 'finest':     # absent unless given
+            raise SystemExit('--avg-timestamp-scales needs a positive --avg-timestamp-weight')
     if weight > 0 and getattr(args, 'ev_images', False):
         raise SystemExit('--avg-timestamp-weight cannot be combined with --ev_images: the term is '
                          'computed from the raw events on the device, and a batch of '
@@ -530,9 +541,12 @@ def avg_timestamp_keywords(args):
     weight = getattr(args, 'avg_timestamp_weight', 0.0)
     if not weight:
         return {}
-    return {'avg_timestamp_weight': weight,
-            'avg_timestamp_references': tuple(getattr(args, 'avg_timestamp_references', AVG_TIMESTAMP_REFERENCES)),
-            'avg_timestamp_polarity': bool(getattr(args, 'avg_timestamp_polarity', False))}
+    out = {'avg_timestamp_weight': weight,
+           'avg_timestamp_references': tuple(getattr(args, 'avg_timestamp_references', AVG_TIMESTAMP_REFERENCES)),
+           'avg_timestamp_polarity': bool(getattr(args, 'avg_timestamp_polarity', False))}
+    if getattr(args, 'avg_timestamp_scales', 'finest') != 'finest':     # only where it differs from the default
+        out['avg_timestamp_scales'] = args.avg_timestamp_scales
+    return out
 
 
 def validate_sharpness_args(args):

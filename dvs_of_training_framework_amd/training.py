@@ -50,7 +50,8 @@ class _TermsAndContrast(tuple):
     """The terms structure as it is, carrying the contrast-maximisation term
     of the micro-batch beside it (``contrast``: a 0-dim device tensor) and,
     where the loss has one, the average-timestamp term (``avg_timestamp``,
-    likewise; either is None where the loss has none)."""
+    likewise; either is None where the loss has none, and the [K] tensor of
+    the levels' terms where it is taken on every scale)."""
     def __new__(cls, terms, contrast, avg_timestamp=None):
         self = super().__new__(cls, terms)
         self.packed = getattr(terms, 'packed', None)
@@ -84,9 +85,12 @@ def _contrast_keywords(weight, references, polarity, scales='finest'):
 AVG_TIMESTAMP_REFERENCES = ('start', 'end')
 
 
-def _avg_timestamp_options(references, polarity):
-    """The keywords of ``Losses.avg_timestamp`` that differ from its defaults."""
+def _avg_timestamp_options(references, polarity, scales='finest'):
+    """The keywords of ``Losses.avg_timestamp`` that differ from its defaults;
+    with 'scales' among them the call goes to ``Losses.avg_timestamp_scales``."""
     out = {}
+    if scales != 'finest':
+        out['scales'] = scales
     if tuple(references) != AVG_TIMESTAMP_REFERENCES:
         out['references'] = tuple(references)
     if polarity:
@@ -94,20 +98,22 @@ def _avg_timestamp_options(references, polarity):
     return out
 
 
-def _avg_timestamp_keywords(weight, references, polarity):
+def _avg_timestamp_keywords(weight, references, polarity, scales='finest'):
     """What a call down the chain gets: nothing at weight 0, and the options
     only where they differ from the defaults."""
     if not weight:
         return {}
     return dict({'avg_timestamp_weight': weight},
-                **{'avg_timestamp_' + k: v for k, v in _avg_timestamp_options(references, polarity).items()})
+                **{'avg_timestamp_' + k: v
+                   for k, v in _avg_timestamp_options(references, polarity, scales).items()})
 
 
 def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   timestamps, sample_idx, features, weights=[0.5, 1, 1],
                   frame_indices=None, contrast_weight=0.0, events=None,
                   contrast_references=('start',), contrast_polarity=False,
-                  contrast_scales='finest', avg_timestamp_weight=0.0,
+                  contrast_scales='finest', avg_timestamp_scales='finest',
+                  avg_timestamp_weight=0.0,
                   avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                   avg_timestamp_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
@@ -131,6 +137,10 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     docs/AVG_TIMESTAMP_SPEC.md), beside the contrast term or without it; the
     term rides on the returned terms as ``.avg_timestamp``.  At 0 nothing of
     that is constructed and ``events`` is not looked at.
+    avg_timestamp_scales='all': the term of every flow, each level weighing
+    avg_timestamp_weight / K (loss.Losses.avg_timestamp_scales,
+    AVG_TIMESTAMP_SPEC sections 11-15); ``.avg_timestamp`` is then the [K]
+    tensor of the levels' terms.  'finest', the default, is the call as it was.
 
     images=None with an evaluator that has ``frameless`` (loss.Losses): a
     frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
@@ -181,9 +191,9 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         if events is None:
             raise ValueError('avg_timestamp_weight > 0 needs the raw events of the batch on the device '
                              '(is_raw=True); preprocessed voxel grids carry none')
-        value, avg_term = evaluator.avg_timestamp(flows, flow_ts, flow_sample_idx, events,
-                                                  weight=avg_timestamp_weight, **_avg_timestamp_options(
-                                                      avg_timestamp_references, avg_timestamp_polarity))
+        options = _avg_timestamp_options(avg_timestamp_references, avg_timestamp_polarity, avg_timestamp_scales)
+        method = evaluator.avg_timestamp_scales if 'scales' in options else evaluator.avg_timestamp
+        value, avg_term = method(flows, flow_ts, flow_sample_idx, events, weight=avg_timestamp_weight, **options)
         loss = loss + value
     return loss, _TermsAndContrast(terms, term, avg_term)
 
@@ -204,13 +214,25 @@ class TermReadback:
         self._contrast = getattr(terms, 'contrast', None)
         self._contrast_levels = None
         self._avg_timestamp = getattr(terms, 'avg_timestamp', None)
+        self._avg_timestamp_levels = None
 
     def avg_timestamp(self):
         """The average-timestamp term as a host float (one small copy), None
-        when the loss has none."""
+        when the loss has none; with the term on every scale the mean of the
+        levels' terms."""
         if isinstance(self._avg_timestamp, torch.Tensor):
-            self._avg_timestamp = float(self._avg_timestamp)
+            if self._avg_timestamp.dim() == 1:
+                self._avg_timestamp_levels = self._avg_timestamp.tolist()
+                self._avg_timestamp = sum(self._avg_timestamp_levels) / len(self._avg_timestamp_levels)
+            else:
+                self._avg_timestamp = float(self._avg_timestamp)
         return self._avg_timestamp
+
+    def avg_timestamp_levels(self):
+        """The levels' average-timestamp terms as host floats, coarsest first;
+        None unless the term is taken on every scale."""
+        self.avg_timestamp()
+        return self._avg_timestamp_levels
 
     def contrast(self):
         """The contrast-maximisation term as a host float (one small copy),
@@ -287,19 +309,21 @@ def _to_device(batch, device, is_raw):
 def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       weights, return_prediction=False, contrast_weight=0.0,
                       contrast_references=('start',), contrast_polarity=False,
-                      contrast_scales='finest', avg_timestamp_weight=0.0,
+                      contrast_scales='finest', avg_timestamp_scales='finest',
+                      avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
     """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs]).
     contrast_weight > 0 (raw events only), contrast_references,
     contrast_polarity, contrast_scales, and avg_timestamp_weight > 0 (raw
-    events only) with its references and polarity: see ``combined_loss``.  A frameless batch
+    events only) with its references, polarity and scales: see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
     the frame size from ``'shape'`` and the loss that reads no frame."""
     contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales)
     if contrast and not is_raw:
         raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
-    avg = _avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references, avg_timestamp_polarity)
+    avg = _avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references, avg_timestamp_polarity,
+                                  avg_timestamp_scales)
     if avg and not is_raw:
         raise ValueError('avg_timestamp_weight > 0 needs raw events (is_raw=True)')
     if avg:
@@ -357,6 +381,7 @@ class ScaleSums:
         self.contrast = None        # sum of the contrast-maximisation term, if the loss has one
         self.contrast_levels = None  # and per level, if it is taken on every scale
         self.avg_timestamp = None   # sum of the average-timestamp term, if the loss has one
+        self.avg_timestamp_levels = None    # and per level, if it is taken on every scale
         self.tags = None
 
     def add(self, loss, readback, tags):
@@ -376,6 +401,10 @@ class ScaleSums:
         extra = readback.avg_timestamp() if hasattr(readback, 'avg_timestamp') else None
         if extra is not None:
             self.avg_timestamp = (self.avg_timestamp or 0.0) + extra
+            levels = readback.avg_timestamp_levels() if hasattr(readback, 'avg_timestamp_levels') else None
+            if levels is not None:
+                self.avg_timestamp_levels = [a + b for a, b in
+                                             zip(self.avg_timestamp_levels or [0.0] * len(levels), levels)]
         self.tags = list(tags)
 
     def write(self, logger, x, divisor, families):
@@ -538,7 +567,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           max_skipped_steps: int = 32, guard_agreement_every: int = 0,
           contrast_weight: float = 0.0, contrast_references=('start',),
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
-          capture_event_terms: bool = False,
+          capture_event_terms: bool = False, avg_timestamp_scales: str = 'finest',
           avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
@@ -592,6 +621,12 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     avg_timestamp_references, avg_timestamp_polarity:  the reference times of
                that term (default: both ends of the window) and whether ON
                and OFF events are accumulated apart
+    avg_timestamp_scales:  'all' takes that term on every flow scale, each
+               level weighing avg_timestamp_weight / K; ``Train/avg
+               timestamp`` is then the mean of the levels' terms and
+               ``Train/avg timestamp/<tag>`` each level's.  'finest' (the
+               default): the finest flow alone.  (By name, like
+               ``capture_event_terms`` beside which it stands)
     capture_event_terms:  with ``capture`` and a positive contrast_weight or
                avg_timestamp_weight: the captured step carries those terms
                (their keywords travel as ``CapturedLoop(loss_options=...)``)
@@ -622,11 +657,12 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
         event_terms = dict(
             _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales),
             **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
-                                      avg_timestamp_polarity))
+                                      avg_timestamp_polarity, avg_timestamp_scales))
     if event_terms:
+        avg_method = 'avg_timestamp' if avg_timestamp_scales == 'finest' else 'avg_timestamp_scales'
         refused = capture_refusal(optimizer, is_raw, model) or event_terms_capture_refusal(
-            evaluator, is_raw, [m for m, w in zip(EVENT_TERM_METHODS, (contrast_weight, avg_timestamp_weight))
-                                if w])
+            evaluator, is_raw, [m for m, w in zip((EVENT_TERM_METHODS[0], avg_method),
+                                                  (contrast_weight, avg_timestamp_weight)) if w])
     else:
         refused = (avg_timestamp_capture_refusal(avg_timestamp_weight)
                    or capture_refusal(optimizer, is_raw, model, contrast_weight)) if capture else None
@@ -672,7 +708,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
                                      contrast_scales),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
-                                          avg_timestamp_polarity))
+                                          avg_timestamp_polarity, avg_timestamp_scales))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass
@@ -711,6 +747,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                     if sums.avg_timestamp is not None:
                         logger.add_scalar('Train/avg timestamp',
                                           sums.avg_timestamp / accumulation_steps, x)
+                        for tag, level in zip(sums.tags, sums.avg_timestamp_levels or ()):
+                            logger.add_scalar(f'Train/avg timestamp/{tag}',
+                                              level / accumulation_steps, x)
                     for g, group in enumerate(optimizer.param_groups):
                         logger.add_scalar(f'General/learning rate/{g}',
                                           group['lr'], x)
@@ -746,7 +785,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
 def validate(model, device, loader, samples_passed, logger, evaluator,
              weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
              contrast_references=('start',), contrast_polarity=False,
-             contrast_scales='finest', avg_timestamp_weight=0.0,
+             contrast_scales='finest', avg_timestamp_scales='finest', avg_timestamp_weight=0.0,
              avg_timestamp_references=AVG_TIMESTAMP_REFERENCES, avg_timestamp_polarity=False):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
@@ -754,7 +793,9 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
     and polarity setting), written as ``Validation/contrast``; with
     contrast_scales='all' that is the mean of the levels' terms; with
     avg_timestamp_weight > 0 it holds the average-timestamp term as well,
-    written as ``Validation/avg timestamp``."""
+    written as ``Validation/avg timestamp``; with avg_timestamp_scales='all'
+    that is the mean of the levels' terms, each written as ``Validation/avg
+    timestamp/<tag>`` beside it."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -765,7 +806,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
                                      contrast_scales),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
-                                          avg_timestamp_polarity))
+                                          avg_timestamp_polarity, avg_timestamp_scales))
             sums.add(loss, terms, tags)
     logger.add_scalar('General/Validation loss', sums.loss / n_batches,
                       samples_passed)
@@ -776,3 +817,5 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
     if sums.avg_timestamp is not None:
         logger.add_scalar('Validation/avg timestamp', sums.avg_timestamp / n_batches,
                           samples_passed)
+        for tag, level in zip(sums.tags, sums.avg_timestamp_levels or ()):
+            logger.add_scalar(f'Validation/avg timestamp/{tag}', level / n_batches, samples_passed)

@@ -15,6 +15,19 @@ events per sample.
           unit_backward + step) of a framed batch without the term against
           --weight times it, in alternating blocks of one run; ms per step,
           the median block of each and every block.
+
+--scales all: the term on every flow scale (AVG_TIMESTAMP_SPEC sections 11-15;
+profiles/avg_timestamp_pyramid/README.md), the four levels 32, 64, 128, 256 of
+the network, at start,end without and with polarity:
+  pyramid dvsof_avg_timestamp_pyramid_fwd / _bwd against four calls of
+          dvsof_avg_timestamp_fwd / _bwd on columns shifted beforehand (the
+          one-level entry points of the same library), compared bit for bit
+          before anything is timed, then in alternating blocks of one run: the
+          median block of each, the spread of the block means, the host time
+          to issue a call, and the launches of either form counted from a
+          capture of one forward and one backward.
+  step    one eager Ranger step of a frameless batch (contrast term on the
+          finest flow) with --avg-timestamp-scales finest against all.
 """
 import argparse
 import json
@@ -170,12 +183,193 @@ def step_with_and_without(weight, rounds=7, steps=30, warmup=15):
                 added_share=round((on - off) / off, 4))
 
 
+SHAPES = ((32, 32), (64, 64), (128, 128), (256, 256))      # the network's order: coarsest first
+PYRAMID_OPTIONS = (('default', 5, 0), ('polarity', 5, 1))
+
+
+def block_us_host(fn, reps):
+    """-> (device us per call between two HIP events, host us per call spent issuing it)."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    host = time.perf_counter() - t0
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps, host * 1e6 / reps
+
+
+def ok(rc):
+    assert rc == 0, rc
+
+
+class Pyramid:
+    """The buffers and the two calls of one level table."""
+
+    def __init__(self, d, flows, mask, pol, weights):
+        self.lib, F = _lib.lib(), B
+        self.M = M = F * bin(mask).count('1') * (1 + pol)
+        self.grads = [torch.empty_like(f) for f in flows]
+        self.table = L.contrast_level_table((H, W), SHAPES, F, M, weights, [f.data_ptr() for f in flows],
+                                            [g.data_ptr() for g in self.grads])
+        self.need = self.lib.dvsof_avg_timestamp_pyramid_workspace_bytes(F, mask, pol, H, W, self.table)
+        assert self.need == L.avg_timestamp_pyramid_layout(F, M, SHAPES)['bytes']
+        self.ws = torch.empty(self.need // 8, dtype=torch.long, device='cuda')
+        self.terms, self.value = torch.empty(len(SHAPES), device='cuda'), torch.empty((), device='cuda')
+        self.seed = torch.ones((), device='cuda')
+        self.head = [d[k].data_ptr() for k in ('x', 'y', 't', 'p', 's')] + [d['x'].numel()] + \
+            [d['ts'].data_ptr(), d['fs'].data_ptr(), F, H, W, mask, pol]
+
+    def fwd(self):
+        ok(self.lib.dvsof_avg_timestamp_pyramid_fwd(*self.head, self.table, self.terms.data_ptr(),
+                                                    self.value.data_ptr(), self.ws.data_ptr(), self.need,
+                                                    _lib.stream()))
+
+    def bwd(self):
+        ok(self.lib.dvsof_avg_timestamp_pyramid_bwd(*self.head, self.table, self.ws.data_ptr(), self.need,
+                                                    self.seed.data_ptr(), _lib.stream()))
+
+    def images(self):
+        """q, s, base of all levels: the head of the workspace."""
+        return self.ws[:3 * self.M * sum(h * w for h, w in SHAPES)]
+
+
+class FourCalls:
+    """dvsof_avg_timestamp_fwd / _bwd once per level on columns shifted beforehand."""
+
+    def __init__(self, d, flows, mask, pol, weights):
+        self.lib, F = _lib.lib(), B
+        self.M = M = F * bin(mask).count('1') * (1 + pol)
+        self.levels = []
+        self.seed = torch.ones((), device='cuda')
+        inside = (d['x'] >= 0) & (d['x'] < W) & (d['y'] >= 0) & (d['y'] < H)
+        for flow, (h, w), weight in zip(flows, SHAPES, weights):
+            s_ = L.contrast_level_shift((H, W), (h, w))
+            x = torch.where(inside, d['x'] >> s_, torch.full_like(d['x'], -1)).contiguous()
+            y = torch.where(inside, d['y'] >> s_, torch.full_like(d['y'], -1)).contiguous()
+            need = self.lib.dvsof_avg_timestamp_workspace_bytes(F, mask, pol, h, w)
+            lev = dict(x=x, y=y, term=torch.empty((), device='cuda'), need=need, pixels=M * h * w,
+                       ws=torch.empty(need // 8, dtype=torch.long, device='cuda'), grad=torch.empty_like(flow),
+                       weight=float(weight))
+            lev['head'] = [x.data_ptr(), y.data_ptr(), d['t'].data_ptr(), d['p'].data_ptr(), d['s'].data_ptr(),
+                           x.numel(), d['ts'].data_ptr(), d['fs'].data_ptr(), flow.data_ptr(), F, h, w, mask, pol]
+            self.levels.append(lev)
+
+    def fwd(self):
+        for v in self.levels:
+            ok(self.lib.dvsof_avg_timestamp_fwd(*v['head'], v['term'].data_ptr(), v['ws'].data_ptr(), v['need'],
+                                                _lib.stream()))
+
+    def bwd(self):
+        for v in self.levels:
+            ok(self.lib.dvsof_avg_timestamp_bwd(*v['head'], v['ws'].data_ptr(), v['need'], self.seed.data_ptr(),
+                                                v['weight'], v['grad'].data_ptr(), _lib.stream()))
+
+    def images(self):
+        """q of all levels, then s, then base: the order of the pyramid's workspace."""
+        return torch.cat([v['ws'][i * v['pixels']:(i + 1) * v['pixels']] for i in range(3) for v in self.levels])
+
+
+def launches_of(fn):
+    """The kernel nodes of a capture of ``fn``, read through the step executor."""
+    from dvs_of_training_framework_amd.capture import StepExecutor
+    graph = torch.cuda.CUDAGraph(keep_graph=True)
+    with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+        fn()
+    x = StepExecutor(graph, [])
+    names = [n[3] for n in x.nodes() if n[3] not in ('(empty)', '?')]
+    x.close()
+    return len(names)
+
+
+def pyramid_calls(rounds, reps, seed=0):
+    ev = synthetic.make_batch(seed, B, H, W, EVENTS)['events']
+    rng = np.random.default_rng(seed)
+    c = dict(x=ev['x'], y=ev['y'], t=ev['timestamp'], p=ev['polarity'], s=ev['sample_index'],
+             ts=np.tile(np.array([0, synthetic.WINDOW], np.float32), B), fs=np.arange(B, dtype=np.int64))
+    d = {k: torch.from_numpy(np.ascontiguousarray(v)).to('cuda') for k, v in c.items()}
+    # sigma 3 pixels at full size, halved with every level
+    flows = [torch.from_numpy(rng.normal(0, 3.0 * h / H, (B, 2, h, w)).astype(np.float32)).to('cuda')
+             for h, w in SHAPES]
+    weights = L.contrast_level_weights(0.5, len(SHAPES))
+    out = dict(events=int(d['x'].numel()), rounds=rounds, reps=reps)
+    for tag, mask, pol in PYRAMID_OPTIONS:
+        one, four = Pyramid(d, flows, mask, pol, weights), FourCalls(d, flows, mask, pol, weights)
+        forms = {'pyramid_fwd': one.fwd, 'four_fwd': four.fwd, 'pyramid_bwd': one.bwd, 'four_bwd': four.bwd}
+        for fn in forms.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        # the same bits from both forms, before anything is timed
+        assert torch.equal(one.images(), four.images())
+        assert torch.equal(one.terms, torch.stack([v['term'] for v in four.levels]))
+        for g, v in zip(one.grads, four.levels):
+            assert torch.equal(g, v['grad']) and bool(g.any())
+        launches = {k: launches_of(fn) for k, fn in forms.items()}
+        torch.cuda.synchronize()
+        blocks = {k: [] for k in forms}
+        for _ in range(rounds):
+            for k, fn in forms.items():
+                blocks[k].append(block_us_host(fn, reps))
+        med = {k: statistics.median(u for u, _ in v) for k, v in blocks.items()}
+        leg = {k: dict(us=round(med[k], 2), min_us=round(min(u for u, _ in blocks[k]), 2),
+                       max_us=round(max(u for u, _ in blocks[k]), 2),
+                       host_us=round(statistics.median(h_ for _, h_ in blocks[k]), 2),
+                       launches=launches[k], blocks=[round(u, 2) for u, _ in blocks[k]]) for k in forms}
+        leg['fwd_ratio_to_four_calls'] = round(med['pyramid_fwd'] / med['four_fwd'], 4)
+        leg['bwd_ratio_to_four_calls'] = round(med['pyramid_bwd'] / med['four_bwd'], 4)
+        leg['host_us_fwd_plus_bwd'] = dict(
+            pyramid=round(leg['pyramid_fwd']['host_us'] + leg['pyramid_bwd']['host_us'], 2),
+            four=round(leg['four_fwd']['host_us'] + leg['four_bwd']['host_us'], 2))
+        leg['terms'] = [float(v) for v in one.terms]
+        leg['workspace_bytes'] = one.need
+        out[tag] = leg
+    return out
+
+
+class FramelessLeg(Leg):
+    """A frameless batch: the contrast term on the finest flow (a frameless run needs it) and the
+    average-timestamp term at the scales asked for."""
+
+    def __init__(self, weight, scales):
+        super().__init__(weight)
+        self.batches = [dict(b, images=None, shape=(H, W)) for b in self.batches]
+        self.extra = {'contrast_weight': 0.25, 'avg_timestamp_weight': weight}
+        if scales != 'finest':
+            self.extra['avg_timestamp_scales'] = scales
+
+
+def step_finest_against_all(weight, rounds, steps=30, warmup=15):
+    legs = {'finest': FramelessLeg(weight, 'finest'), 'all': FramelessLeg(weight, 'all')}
+    for leg in legs.values():
+        leg.block(warmup)
+    ms = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, leg in legs.items():
+            ms[k].append(round(leg.block(steps), 4))
+    finest, every = statistics.median(ms['finest']), statistics.median(ms['all'])
+    return dict(weight=weight, finest_ms=ms['finest'], all_ms=ms['all'], finest_median_ms=finest,
+                all_median_ms=every, added_ms=round(every - finest, 4), added_share=round((every - finest) / finest, 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--weight', type=float, default=0.5)
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--calls-only', action='store_true')
+    ap.add_argument('--scales', choices=('finest', 'all'), default='finest',
+                    help='all: the legs of the term on every flow scale instead of the one-level ones')
+    ap.add_argument('--reps', type=int, default=20, help='calls per block of the --scales all leg')
     args = ap.parse_args()
+    if args.scales == 'all':
+        out = dict(shape=dict(B=B, H=H, W=W, bins=BINS, events_per_sample=EVENTS, levels=[list(s_) for s_ in SHAPES]),
+                   calls=pyramid_calls(args.rounds, args.reps))
+        if not args.calls_only:
+            out['step'] = step_finest_against_all(args.weight, args.rounds)
+        print(json.dumps(out))
+        return
     out = dict(shape=dict(B=B, H=H, W=W, bins=BINS, events_per_sample=EVENTS), calls=calls_alone())
     if not args.calls_only:
         out['step'] = step_with_and_without(args.weight, args.rounds)

@@ -45,6 +45,12 @@
 #                                     with polarity, batch 8, 256x256, 65 536 events per sample, and one eager Ranger
 #                                     step with and without --avg-timestamp-weight, in alternating blocks of one run
 #                                     (profiles/avg_timestamp/README.md)
+#   avgts_pyramid [avg_timestamp_bench.py args]  that term on every flow scale (its --scales all legs):
+#                                     dvsof_avg_timestamp_pyramid_fwd / _bwd against four calls of dvsof_avg_timestamp_fwd /
+#                                     _bwd on shifted columns at batch 8, 256x256, four levels, start,end with and without
+#                                     polarity, the launches of either counted from a capture, and one eager Ranger step
+#                                     of a frameless batch with --avg-timestamp-scales all against finest, in alternating
+#                                     blocks of one run (profiles/avg_timestamp_pyramid/README.md)
 #   eventcapture [event_terms_capture_bench.py args]  the captured step with the events-only terms
 #                                     (--capture-event-terms; tools/event_terms_capture_bench.py): framed + contrast,
 #                                     frameless + contrast on every scale, the same + average timestamp, f32 and bf16s,
@@ -127,6 +133,9 @@ frameless)
 avgts)
   timeout -k 10 540 env "${envs[@]}" python tools/avg_timestamp_bench.py "$@" > $O/avgts.json 2> $O/avgts.err
   echo "avgts rc=$?"; cut -c1-3600 $O/avgts.json; tail -3 $O/avgts.err ;;
+avgts_pyramid)
+  timeout -k 10 540 env "${envs[@]}" python tools/avg_timestamp_bench.py --scales all "$@" > $O/avgts_pyramid.json 2> $O/avgts_pyramid.err
+  echo "avgts_pyramid rc=$?"; cut -c1-4800 $O/avgts_pyramid.json; tail -3 $O/avgts_pyramid.err ;;
 eventcapture)
   timeout -k 10 560 env "${envs[@]}" python tools/event_terms_capture_bench.py "$@" > $O/eventcapture.jsonl 2> $O/eventcapture.err
   echo "eventcapture rc=$?"; cut -c1-900 $O/eventcapture.jsonl; tail -3 $O/eventcapture.err ;;
