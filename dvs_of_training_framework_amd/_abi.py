@@ -46,6 +46,9 @@ AVG_TIMESTAMP_PATH = HEADER_PATH.with_name('dvsof_avg_timestamp.h')
 # And that term on every flow scale (AVG_TIMESTAMP_PYRAMID_FUNCTIONS): functions only, which take
 # the level table of dvsof_contrast_pyramid.h
 AVG_TIMESTAMP_PYRAMID_PATH = HEADER_PATH.with_name('dvsof_avg_timestamp_pyramid.h')
+# And the two events-only terms on the encoded event columns (EVENT_TERMS_ENCODED_FUNCTIONS):
+# functions only, the twins of calls of the four headers before it
+EVENT_TERMS_ENCODED_PATH = HEADER_PATH.with_name('dvsof_event_terms_encoded.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -233,3 +236,8 @@ AVG_TIMESTAMP_PYRAMID_FUNCTIONS = _read_extension(
     AVG_TIMESTAMP_PYRAMID_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
     | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS)
     | set(AVG_TIMESTAMP_FUNCTIONS), base=_struct_headers[CONTRAST_PYRAMID_PATH])
+EVENT_TERMS_ENCODED_FUNCTIONS = _read_extension(
+    EVENT_TERMS_ENCODED_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
+    | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS)
+    | set(AVG_TIMESTAMP_FUNCTIONS) | set(AVG_TIMESTAMP_PYRAMID_FUNCTIONS),
+    base=_struct_headers[CONTRAST_PYRAMID_PATH])

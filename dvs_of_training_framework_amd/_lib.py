@@ -16,7 +16,9 @@ tests/golden/abi_signatures_contrast_pyramid.json; _abi.AVG_TIMESTAMP_PATH:
 include/dvsof_avg_timestamp.h, recorded in
 tests/golden/abi_signatures_avg_timestamp.json; _abi.AVG_TIMESTAMP_PYRAMID_PATH:
 include/dvsof_avg_timestamp_pyramid.h, recorded in
-tests/golden/abi_signatures_avg_timestamp_pyramid.json).
+tests/golden/abi_signatures_avg_timestamp_pyramid.json;
+_abi.EVENT_TERMS_ENCODED_PATH: include/dvsof_event_terms_encoded.h, recorded in
+tests/golden/abi_signatures_event_terms_encoded.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -55,6 +57,8 @@ ContrastLevels = _abi.CONTRAST_PYRAMID_STRUCTS['dvsof_contrast_levels_t']
 _AVG_TIMESTAMP_SIGNATURES = _abi.AVG_TIMESTAMP_FUNCTIONS
 # and of include/dvsof_avg_timestamp_pyramid.h, which takes the level table above
 _AVG_TIMESTAMP_PYRAMID_SIGNATURES = _abi.AVG_TIMESTAMP_PYRAMID_FUNCTIONS
+# and of include/dvsof_event_terms_encoded.h, the two terms on the encoded event columns
+_EVENT_TERMS_ENCODED_SIGNATURES = _abi.EVENT_TERMS_ENCODED_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -110,6 +114,11 @@ def declared_avg_timestamp_pyramid_symbols():
     return _declared_in((_abi.AVG_TIMESTAMP_PYRAMID_PATH,))
 
 
+def declared_event_terms_encoded_symbols():
+    """Names of all entry points include/dvsof_event_terms_encoded.h declares."""
+    return _declared_in((_abi.EVENT_TERMS_ENCODED_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -126,7 +135,8 @@ def lib():
         for name, (res, args) in {**_SIGNATURES, **_EXTENSION_SIGNATURES, **_CONTRAST_MULTI_SIGNATURES,
                                   **_IWE_MULTI_SIGNATURES, **_LOSS_FRAMELESS_SIGNATURES,
                                   **_CONTRAST_PYRAMID_SIGNATURES, **_AVG_TIMESTAMP_SIGNATURES,
-                                  **_AVG_TIMESTAMP_PYRAMID_SIGNATURES}.items():
+                                  **_AVG_TIMESTAMP_PYRAMID_SIGNATURES,
+                                  **_EVENT_TERMS_ENCODED_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -28,9 +28,10 @@
 // 11-15, include/dvsof_avg_timestamp_pyramid.h).  What one event does to the
 // images of a frame, forward and backward, is stated once (avgts_splat_event,
 // avgts_bwd_event) and used by the one-level kernels and by those.
-#include "event_images.h"
+#include "event_columns.h"
 #include "../../include/dvsof_avg_timestamp.h"
 #include "../../include/dvsof_avg_timestamp_pyramid.h"
+#include "../../include/dvsof_event_terms_encoded.h"
 
 namespace {
 
@@ -102,10 +103,9 @@ __device__ __forceinline__ void avgts_splat_event(const Refs &refs, int f, int c
 }
 
 // The event loop and the frame rule of contrast_splat_kernel.
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void avgts_splat_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
     unsigned long long *__restrict__ q, unsigned long long *__restrict__ s, unsigned long long *__restrict__ base,
     uint32_t *__restrict__ count)
@@ -113,12 +113,13 @@ __global__ __launch_bounds__(NT) void avgts_splat_kernel(
     const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // the -1 slots of cropped and padded events
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t smp = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t smp = ev.sample;
         const size_t pix = (size_t)yi * w + (size_t)xi;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != smp) continue;
@@ -264,10 +265,9 @@ __device__ __forceinline__ void avgts_bwd_event(const Refs &refs, int f, int c, 
     }
 }
 
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void avgts_bwd_events_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
     const int64_t *__restrict__ q, const int64_t *__restrict__ s, const ImageRec *__restrict__ rec,
     const double *__restrict__ unit, unsigned long long *__restrict__ acc)
@@ -275,12 +275,13 @@ __global__ __launch_bounds__(NT) void avgts_bwd_events_kernel(
     const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t smp = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t smp = ev.sample;
         const size_t pix = (size_t)yi * w + (size_t)xi;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != smp) continue;
@@ -341,16 +342,78 @@ Layout layout_of(int F, int h, int w, const Plan &pl)
 
 // The refusals both calls share, in the order of dvsof_contrast_multi_fwd; outputs: the call's
 // own pointers are all there.  DVSOF_OK with F == 0: nothing to do.
-int check_call(const int64_t *x, const int64_t *y, const float *t, const int64_t *p, const int64_t *sample_index,
-               int64_t n_events, const float *frame_ts, const int64_t *frame_sample, const float *flow, int F, int h,
-               int w, int reference_mask, int polarity, bool outputs, const void *workspace, size_t workspace_bytes,
-               Plan &pl)
+template <class Cols>
+int check_call(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+               const float *flow, int F, int h, int w, int reference_mask, int polarity, bool outputs,
+               const void *workspace, size_t workspace_bytes, Plan &pl)
 {
     if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
     if (F == 0) return DVSOF_OK;
     if (bad_frame_sizes(F, h, w) || !outputs || !frame_ts || !frame_sample || !flow) return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
+    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
     if (!workspace || workspace_bytes < layout_of(F, h, w, pl).bytes) return DVSOF_ENOSPACE;
+    return DVSOF_OK;
+}
+
+// dvsof_avg_timestamp_fwd / _bwd on either form of the event columns (event_columns.h)
+template <class Cols>
+int one_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+            const float *flow, int F, int h, int w, int reference_mask, int polarity, float *term, void *workspace,
+            size_t workspace_bytes, void *stream)
+{
+    Plan pl;
+    const int rc = check_call(cols, n_events, frame_ts, frame_sample, flow, F, h, w, reference_mask, polarity,
+                              term != nullptr, workspace, workspace_bytes, pl);
+    if (rc != DVSOF_OK || F == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const Layout lay = layout_of(F, h, w, pl);
+    char *ws = (char *)workspace;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, lay.zeroed_bytes, st));
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
+                                (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
+                                (unsigned long long *)(ws + lay.base), (uint32_t *)(ws + lay.count));
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(avgts_stats_partial_kernel, dim3((unsigned)lay.nb, (unsigned)pl.M), dim3(NT), 0, st,
+                       (const int64_t *)ws, (const int64_t *)(ws + lay.s), (const int64_t *)(ws + lay.base),
+                       (const uint32_t *)(ws + lay.count), h, w, lay.nb, (StatRow *)(ws + lay.part));
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(frame_final_kernel<AvgSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
+                       (const StatRow *)(ws + lay.part), lay.nb, (StatRow *)(ws + lay.rows));
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(avgts_close_kernel, dim3(1), dim3(kWave), 0, st, (const StatRow *)(ws + lay.rows), F,
+                       pl.R * pl.C, pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, (ImageRec *)(ws + lay.rec),
+                       (double *)(ws + lay.unit), term);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+template <class Cols>
+int one_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+            const float *flow, int F, int h, int w, int reference_mask, int polarity, void *workspace,
+            size_t workspace_bytes, const float *seed, float weight, float *grad_flow, void *stream)
+{
+    Plan pl;
+    const int rc = check_call(cols, n_events, frame_ts, frame_sample, flow, F, h, w, reference_mask, polarity,
+                              seed && grad_flow, workspace, workspace_bytes, pl);
+    if (rc != DVSOF_OK || F == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const Layout lay = layout_of(F, h, w, pl);
+    char *ws = (char *)workspace;
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(avgts_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, (const int64_t *)ws,
+                                (const int64_t *)(ws + lay.s), (const ImageRec *)(ws + lay.rec),
+                                (const double *)(ws + lay.unit), (unsigned long long *)(ws + lay.sums));
+        DVSOF_LAUNCH_CHECK();
+    }
+    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
+    hipLaunchKernelGGL(avgts_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
+                       (long long *)(ws + lay.sums), (const double *)(ws + lay.unit), seed, weight, F, pl.M,
+                       per_frame, grad_flow);
+    DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
 
@@ -371,33 +434,8 @@ int dvsof_avg_timestamp_fwd(const int64_t *x, const int64_t *y, const float *t, 
                             int reference_mask, int polarity, float *term, void *workspace,
                             size_t workspace_bytes, void *stream)
 {
-    Plan pl;
-    const int rc = check_call(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w,
-                              reference_mask, polarity, term != nullptr, workspace, workspace_bytes, pl);
-    if (rc != DVSOF_OK || F == 0) return rc;
-    hipStream_t st = as_stream(stream);
-    const Layout lay = layout_of(F, h, w, pl);
-    char *ws = (char *)workspace;
-    DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, lay.zeroed_bytes, st));
-    if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t, p,
-                                sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
-                                (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
-                                (unsigned long long *)(ws + lay.base), (uint32_t *)(ws + lay.count));
-        DVSOF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(avgts_stats_partial_kernel, dim3((unsigned)lay.nb, (unsigned)pl.M), dim3(NT), 0, st,
-                       (const int64_t *)ws, (const int64_t *)(ws + lay.s), (const int64_t *)(ws + lay.base),
-                       (const uint32_t *)(ws + lay.count), h, w, lay.nb, (StatRow *)(ws + lay.part));
-    DVSOF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frame_final_kernel<AvgSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
-                       (const StatRow *)(ws + lay.part), lay.nb, (StatRow *)(ws + lay.rows));
-    DVSOF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(avgts_close_kernel, dim3(1), dim3(kWave), 0, st, (const StatRow *)(ws + lay.rows), F,
-                       pl.R * pl.C, pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, (ImageRec *)(ws + lay.rec),
-                       (double *)(ws + lay.unit), term);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return one_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                   reference_mask, polarity, term, workspace, workspace_bytes, stream);
 }
 
 int dvsof_avg_timestamp_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
@@ -406,27 +444,31 @@ int dvsof_avg_timestamp_bwd(const int64_t *x, const int64_t *y, const float *t, 
                             int reference_mask, int polarity, void *workspace, size_t workspace_bytes,
                             const float *seed, float weight, float *grad_flow, void *stream)
 {
-    Plan pl;
-    const int rc = check_call(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w,
-                              reference_mask, polarity, seed && grad_flow, workspace, workspace_bytes, pl);
-    if (rc != DVSOF_OK || F == 0) return rc;
-    hipStream_t st = as_stream(stream);
-    const Layout lay = layout_of(F, h, w, pl);
-    char *ws = (char *)workspace;
-    if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
-                                p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
-                                (const int64_t *)ws, (const int64_t *)(ws + lay.s),
-                                (const ImageRec *)(ws + lay.rec), (const double *)(ws + lay.unit),
-                                (unsigned long long *)(ws + lay.sums));
-        DVSOF_LAUNCH_CHECK();
-    }
-    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
-    hipLaunchKernelGGL(avgts_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
-                       (long long *)(ws + lay.sums), (const double *)(ws + lay.unit), seed, weight, F, pl.M,
-                       per_frame, grad_flow);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return one_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                   reference_mask, polarity, workspace, workspace_bytes, seed, weight, grad_flow, stream);
+}
+
+// The encoded twins (include/dvsof_event_terms_encoded.h)
+int dvsof_avg_timestamp_fwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                    const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                    const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
+                                    int h, int w, int reference_mask, int polarity_channels, float *term,
+                                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    return one_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                   flow, F, h, w, reference_mask, polarity_channels, term, workspace, workspace_bytes, stream);
+}
+
+int dvsof_avg_timestamp_bwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                    const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                    const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
+                                    int h, int w, int reference_mask, int polarity_channels, void *workspace,
+                                    size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
+                                    void *stream)
+{
+    return one_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                   flow, F, h, w, reference_mask, polarity_channels, workspace, workspace_bytes, seed, weight,
+                   grad_flow, stream);
 }
 
 }  // extern "C"
@@ -446,22 +488,22 @@ constexpr int kMaxLevels = 8;
 constexpr int kMaxShift = 15;
 static_assert(sizeof(Levels::level) / sizeof(Level) == kMaxLevels, "the table holds eight levels");
 
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void avgts_pyramid_splat_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
     unsigned long long *__restrict__ q, unsigned long long *__restrict__ s, unsigned long long *__restrict__ base,
     uint32_t *__restrict__ count)
 {
     const int64_t stride = (int64_t)gridDim.x * NT;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // at full resolution, before any shift
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t smp = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t smp = ev.sample;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != smp) continue;
             const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
@@ -510,10 +552,9 @@ __global__ __launch_bounds__(kWave) void avgts_pyramid_close_kernel(const StatRo
     }
 }
 
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void avgts_pyramid_bwd_events_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
     const int64_t *__restrict__ q, const int64_t *__restrict__ s, const ImageRec *__restrict__ rec,
     const double *__restrict__ unit, unsigned long long *__restrict__ acc)
@@ -521,12 +562,13 @@ __global__ __launch_bounds__(NT) void avgts_pyramid_bwd_events_kernel(
     const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t M = (size_t)F * R * (POL ? 2 : 1);
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t smp = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t smp = ev.sample;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != smp) continue;
             const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
@@ -615,9 +657,9 @@ bool pyramid_layout(int F, int h, int w, const Plan &pl, const Levels &lv, bool 
 
 // The refusals both calls share, in the order of the header; outputs: the call's own pointers
 // are all there.  DVSOF_OK with F == 0: nothing to do.
-int pyramid_check(const int64_t *x, const int64_t *y, const float *t, const int64_t *p, const int64_t *sample_index,
-                  int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h, int w,
-                  int reference_mask, int polarity, const Levels &lv, bool backward, bool outputs,
+template <class Cols>
+int pyramid_check(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F,
+                  int h, int w, int reference_mask, int polarity, const Levels &lv, bool backward, bool outputs,
                   const void *workspace, size_t workspace_bytes, Plan &pl, PyramidLayout &lay)
 {
     if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
@@ -626,42 +668,28 @@ int pyramid_check(const int64_t *x, const int64_t *y, const float *t, const int6
     if (!pyramid_layout(F, h, w, pl, lv, true, lay) || !outputs || !frame_ts || !frame_sample) return DVSOF_EINVAL;
     for (int k = 0; k < lv.K; ++k)
         if (!lv.level[k].flow || (backward && !lv.level[k].grad_flow)) return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
+    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
     if (!workspace || workspace_bytes < lay.bytes) return DVSOF_ENOSPACE;
     return DVSOF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t dvsof_avg_timestamp_pyramid_workspace_bytes(int F, int reference_mask, int polarity, int h, int w,
-                                                   dvsof_contrast_levels_t levels)
+// dvsof_avg_timestamp_pyramid_fwd / _bwd on either form of the event columns
+template <class Cols>
+int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
+                int w, int reference_mask, int polarity, const Levels &levels, float *terms, float *value,
+                void *workspace, size_t workspace_bytes, void *stream)
 {
     Plan pl;
     PyramidLayout lay;
-    if (F < 1 || !plan_of(F, reference_mask, polarity, pl) || !pyramid_layout(F, h, w, pl, levels, false, lay))
-        return 0;
-    return lay.bytes;
-}
-
-int dvsof_avg_timestamp_pyramid_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
-                                    const int64_t *sample_index, int64_t n_events, const float *frame_ts,
-                                    const int64_t *frame_sample, int F, int h, int w, int reference_mask,
-                                    int polarity, dvsof_contrast_levels_t levels, float *terms, float *value,
-                                    void *workspace, size_t workspace_bytes, void *stream)
-{
-    Plan pl;
-    PyramidLayout lay;
-    const int rc = pyramid_check(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, reference_mask,
-                                 polarity, levels, false, terms && value, workspace, workspace_bytes, pl, lay);
+    const int rc = pyramid_check(cols, n_events, frame_ts, frame_sample, F, h, w, reference_mask, polarity, levels,
+                                 false, terms && value, workspace, workspace_bytes, pl, lay);
     if (rc != DVSOF_OK || F == 0) return rc;
     hipStream_t st = as_stream(stream);
     char *ws = (char *)workspace;
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, lay.zeroed_bytes, st));
     if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_pyramid_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y,
-                                t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
+        DVSOF_REFS_POL_DISPATCH(avgts_pyramid_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
                                 (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
                                 (unsigned long long *)(ws + lay.base), (uint32_t *)(ws + lay.count));
         DVSOF_LAUNCH_CHECK();
@@ -687,22 +715,21 @@ int dvsof_avg_timestamp_pyramid_fwd(const int64_t *x, const int64_t *y, const fl
     return DVSOF_OK;
 }
 
-int dvsof_avg_timestamp_pyramid_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
-                                    const int64_t *sample_index, int64_t n_events, const float *frame_ts,
-                                    const int64_t *frame_sample, int F, int h, int w, int reference_mask,
-                                    int polarity, dvsof_contrast_levels_t levels, void *workspace,
-                                    size_t workspace_bytes, const float *seed, void *stream)
+template <class Cols>
+int pyramid_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
+                int w, int reference_mask, int polarity, const Levels &levels, void *workspace,
+                size_t workspace_bytes, const float *seed, void *stream)
 {
     Plan pl;
     PyramidLayout lay;
-    const int rc = pyramid_check(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, reference_mask,
-                                 polarity, levels, true, seed != nullptr, workspace, workspace_bytes, pl, lay);
+    const int rc = pyramid_check(cols, n_events, frame_ts, frame_sample, F, h, w, reference_mask, polarity, levels,
+                                 true, seed != nullptr, workspace, workspace_bytes, pl, lay);
     if (rc != DVSOF_OK || F == 0) return rc;
     hipStream_t st = as_stream(stream);
     char *ws = (char *)workspace;
     if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_pyramid_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x,
-                                y, t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
+        DVSOF_REFS_POL_DISPATCH(avgts_pyramid_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
+                                cols, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
                                 (const int64_t *)ws, (const int64_t *)(ws + lay.s),
                                 (const ImageRec *)(ws + lay.rec), (const double *)(ws + lay.unit),
                                 (unsigned long long *)(ws + lay.sums));
@@ -713,6 +740,63 @@ int dvsof_avg_timestamp_pyramid_bwd(const int64_t *x, const int64_t *y, const fl
                        lay.sums_elems);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dvsof_avg_timestamp_pyramid_workspace_bytes(int F, int reference_mask, int polarity, int h, int w,
+                                                   dvsof_contrast_levels_t levels)
+{
+    Plan pl;
+    PyramidLayout lay;
+    if (F < 1 || !plan_of(F, reference_mask, polarity, pl) || !pyramid_layout(F, h, w, pl, levels, false, lay))
+        return 0;
+    return lay.bytes;
+}
+
+int dvsof_avg_timestamp_pyramid_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                    const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                    const int64_t *frame_sample, int F, int h, int w, int reference_mask,
+                                    int polarity, dvsof_contrast_levels_t levels, float *terms, float *value,
+                                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    return pyramid_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                       reference_mask, polarity, levels, terms, value, workspace, workspace_bytes, stream);
+}
+
+int dvsof_avg_timestamp_pyramid_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                    const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                    const int64_t *frame_sample, int F, int h, int w, int reference_mask,
+                                    int polarity, dvsof_contrast_levels_t levels, void *workspace,
+                                    size_t workspace_bytes, const float *seed, void *stream)
+{
+    return pyramid_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                       reference_mask, polarity, levels, workspace, workspace_bytes, seed, stream);
+}
+
+int dvsof_avg_timestamp_pyramid_fwd_encoded(const int16_t *x, const int16_t *y, const float *t,
+                                            const uint8_t *polarity, const int64_t *sample_event_offsets, int B,
+                                            int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+                                            int F, int h, int w, int reference_mask, int polarity_channels,
+                                            dvsof_contrast_levels_t levels, float *terms, float *value,
+                                            void *workspace, size_t workspace_bytes, void *stream)
+{
+    return pyramid_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                       F, h, w, reference_mask, polarity_channels, levels, terms, value, workspace, workspace_bytes,
+                       stream);
+}
+
+int dvsof_avg_timestamp_pyramid_bwd_encoded(const int16_t *x, const int16_t *y, const float *t,
+                                            const uint8_t *polarity, const int64_t *sample_event_offsets, int B,
+                                            int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+                                            int F, int h, int w, int reference_mask, int polarity_channels,
+                                            dvsof_contrast_levels_t levels, void *workspace, size_t workspace_bytes,
+                                            const float *seed, void *stream)
+{
+    return pyramid_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                       F, h, w, reference_mask, polarity_channels, levels, workspace, workspace_bytes, seed, stream);
 }
 
 }  // extern "C"

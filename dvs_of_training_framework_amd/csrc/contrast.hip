@@ -26,10 +26,11 @@
 // At the end of the file: the term on every flow scale of the network by one
 // splat, one closing wave and one backward for all levels (sections 19-23,
 // include/dvsof_contrast_pyramid.h); the kernels above are not touched by it.
-#include "event_images.h"
+#include "event_columns.h"
 #include "../../include/dvsof_contrast.h"
 #include "../../include/dvsof_contrast_multi.h"
 #include "../../include/dvsof_contrast_pyramid.h"
+#include "../../include/dvsof_event_terms_encoded.h"
 
 namespace {
 
@@ -51,22 +52,22 @@ static_assert(sizeof(ImageRec) == 32, "the workspace holds 32 bytes per image");
 // sample whose window holds its time (both ends included), in the channel of
 // the sign of p.
 // ---------------------------------------------------------------------------
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void contrast_splat_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
     unsigned long long *__restrict__ q, uint32_t *__restrict__ count)
 {
     const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // the -1 slots of cropped and padded events
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t s = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t s = ev.sample;
         const size_t pix = (size_t)yi * w + (size_t)xi;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != s) continue;
@@ -133,10 +134,9 @@ __global__ __launch_bounds__(kWave) void contrast_close_kernel(const dvsof_iwe_r
 // the derivative of the bilinear weights, -sig of it to the event's own pixel
 // of the flow, in float64, truncated to the frame's unit.
 // ---------------------------------------------------------------------------
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void contrast_bwd_events_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
     const int64_t *__restrict__ q, const ImageRec *__restrict__ rec, const double *__restrict__ unit,
     unsigned long long *__restrict__ acc)
@@ -144,12 +144,13 @@ __global__ __launch_bounds__(NT) void contrast_bwd_events_kernel(
     const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t s = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t s = ev.sample;
         const size_t pix = (size_t)yi * w + (size_t)xi;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != s) continue;
@@ -212,6 +213,8 @@ __global__ __launch_bounds__(NT) void contrast_bwd_close_kernel(long long *__res
 
 size_t sums_bytes(int F, int h, int w) { return sizeof(int64_t) * 2 * (size_t)F * h * w; }
 
+size_t multi_workspace_bytes(int F, int reference_mask, int polarity, int h, int w);
+
 // the workspace: the sums, M records, F units, the statistics' partials
 struct Workspace {
     unsigned long long *sums;
@@ -233,11 +236,7 @@ Workspace carve(void *workspace, int F, int h, int w, const Plan &pl)
     return o;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t dvsof_contrast_multi_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
+size_t multi_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
 {
     Plan pl;
     if (F < 1 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return 0;
@@ -245,20 +244,19 @@ size_t dvsof_contrast_multi_workspace_bytes(int F, int reference_mask, int polar
            dvsof_iwe_stats_workspace_bytes(pl.M, h, w);
 }
 
-int dvsof_contrast_multi_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
-                             const int64_t *sample_index, int64_t n_events, const float *frame_ts,
-                             const int64_t *frame_sample, const float *flow, int F, int h, int w,
-                             int reference_mask, int polarity, int64_t *q, uint32_t *count,
-                             dvsof_iwe_result_t *result, float *term, void *workspace, size_t workspace_bytes,
-                             void *stream)
+// dvsof_contrast_multi_fwd / _bwd on either form of the event columns (event_columns.h)
+template <class Cols>
+int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+              const float *flow, int F, int h, int w, int reference_mask, int polarity, int64_t *q, uint32_t *count,
+              dvsof_iwe_result_t *result, float *term, void *workspace, size_t workspace_bytes, void *stream)
 {
     Plan pl;
     if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
     if (F == 0) return DVSOF_OK;
     if (bad_frame_sizes(F, h, w) || !q || !count || !result || !term || !frame_ts || !frame_sample || !flow)
         return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
-    if (!workspace || workspace_bytes < dvsof_contrast_multi_workspace_bytes(F, reference_mask, polarity, h, w))
+    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < multi_workspace_bytes(F, reference_mask, polarity, h, w))
         return DVSOF_ENOSPACE;
     hipStream_t st = as_stream(stream);
     const size_t pixels = (size_t)pl.M * h * w;
@@ -267,9 +265,9 @@ int dvsof_contrast_multi_fwd(const int64_t *x, const int64_t *y, const float *t,
     DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws.sums, 0u, sums_bytes(F, h, w), st));
     if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t, p,
-                                sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
-                                (unsigned long long *)q, count);
+        DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, (unsigned long long *)q,
+                                count);
         DVSOF_LAUNCH_CHECK();
     }
     const int rc = dvsof_iwe_stats(q, count, pl.M, h, w, result, ws.stats, ws.stats_bytes, stream);
@@ -280,26 +278,25 @@ int dvsof_contrast_multi_fwd(const int64_t *x, const int64_t *y, const float *t,
     return DVSOF_OK;
 }
 
-int dvsof_contrast_multi_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
-                             const int64_t *sample_index, int64_t n_events, const float *frame_ts,
-                             const int64_t *frame_sample, const float *flow, int F, int h, int w,
-                             int reference_mask, int polarity, const int64_t *q, void *workspace,
-                             size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
-                             void *stream)
+template <class Cols>
+int multi_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+              const float *flow, int F, int h, int w, int reference_mask, int polarity, const int64_t *q,
+              void *workspace, size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
+              void *stream)
 {
     Plan pl;
     if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
     if (F == 0) return DVSOF_OK;
     if (bad_frame_sizes(F, h, w) || !q || !seed || !grad_flow || !frame_ts || !frame_sample || !flow)
         return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
-    if (!workspace || workspace_bytes < dvsof_contrast_multi_workspace_bytes(F, reference_mask, polarity, h, w))
+    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < multi_workspace_bytes(F, reference_mask, polarity, h, w))
         return DVSOF_ENOSPACE;
     hipStream_t st = as_stream(stream);
     const Workspace ws = carve(workspace, F, h, w, pl);
     if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(contrast_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y,
-                                t, p, sample_index, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, q,
+        DVSOF_REFS_POL_DISPATCH(contrast_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, q,
                                 (const ImageRec *)ws.rec, (const double *)ws.unit, ws.sums);
         DVSOF_LAUNCH_CHECK();
     }
@@ -308,6 +305,62 @@ int dvsof_contrast_multi_bwd(const int64_t *x, const int64_t *y, const float *t,
                        (long long *)ws.sums, (const double *)ws.unit, seed, weight, F, pl.M, per_frame, grad_flow);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dvsof_contrast_multi_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
+{
+    return multi_workspace_bytes(F, reference_mask, polarity, h, w);
+}
+
+int dvsof_contrast_multi_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                             const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                             const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                             int reference_mask, int polarity, int64_t *q, uint32_t *count,
+                             dvsof_iwe_result_t *result, float *term, void *workspace, size_t workspace_bytes,
+                             void *stream)
+{
+    return multi_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                     reference_mask, polarity, q, count, result, term, workspace, workspace_bytes, stream);
+}
+
+int dvsof_contrast_multi_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                             const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                             const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                             int reference_mask, int polarity, const int64_t *q, void *workspace,
+                             size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
+                             void *stream)
+{
+    return multi_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                     reference_mask, polarity, q, workspace, workspace_bytes, seed, weight, grad_flow, stream);
+}
+
+// The encoded twins (include/dvsof_event_terms_encoded.h)
+int dvsof_contrast_multi_fwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                     const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                     const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
+                                     int h, int w, int reference_mask, int polarity_channels, int64_t *q,
+                                     uint32_t *count, dvsof_iwe_result_t *result, float *term, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
+    return multi_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                     flow, F, h, w, reference_mask, polarity_channels, q, count, result, term, workspace,
+                     workspace_bytes, stream);
+}
+
+int dvsof_contrast_multi_bwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                     const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                     const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
+                                     int h, int w, int reference_mask, int polarity_channels, const int64_t *q,
+                                     void *workspace, size_t workspace_bytes, const float *seed, float weight,
+                                     float *grad_flow, void *stream)
+{
+    return multi_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                     flow, F, h, w, reference_mask, polarity_channels, q, workspace, workspace_bytes, seed, weight,
+                     grad_flow, stream);
 }
 
 // The term as it was before the references and the polarities: one image per frame, of all its
@@ -353,21 +406,21 @@ constexpr int kMaxLevels = 8;
 constexpr int kMaxShift = 15;
 static_assert(sizeof(Levels::level) / sizeof(Level) == kMaxLevels, "the table holds eight levels");
 
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void contrast_pyramid_splat_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
     unsigned long long *__restrict__ q, uint32_t *__restrict__ count)
 {
     const int64_t stride = (int64_t)gridDim.x * NT;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // at full resolution, before any shift
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t s = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t s = ev.sample;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != s) continue;
             const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
@@ -433,10 +486,9 @@ __global__ __launch_bounds__(kWave) void contrast_pyramid_close_kernel(const dvs
     }
 }
 
-template <int R, bool POL>
+template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void contrast_pyramid_bwd_events_kernel(
-    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
-    const int64_t *__restrict__ pol, const int64_t *__restrict__ sample, int64_t n, const float *__restrict__ ts,
+    const Cols cols, int64_t n, const float *__restrict__ ts,
     const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
     const int64_t *__restrict__ q, const ImageRec *__restrict__ rec, const double *__restrict__ unit,
     unsigned long long *__restrict__ acc)
@@ -444,12 +496,13 @@ __global__ __launch_bounds__(NT) void contrast_pyramid_bwd_events_kernel(
     const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t M = (size_t)F * R * (POL ? 2 : 1);
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const int64_t xi = x[e], yi = y[e];
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
         if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
         int c;
-        if (!event_channel<POL>(pol, e, c)) continue;
-        const float te = t[e];
-        const int64_t s = sample[e];
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t s = ev.sample;
         for (int f = 0; f < F; ++f) {
             if (frame_sample[f] != s) continue;
             const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
@@ -581,9 +634,9 @@ PyramidWorkspace carve_pyramid(void *workspace, const PyramidLayout &l)
 
 // The refusals both calls share, in the order of the header; outputs: the call's own pointers
 // are all there.  DVSOF_OK with F == 0: nothing to do.
-int pyramid_check(const int64_t *x, const int64_t *y, const float *t, const int64_t *p, const int64_t *sample_index,
-                  int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h, int w,
-                  int reference_mask, int polarity, const Levels &lv, bool backward, bool outputs,
+template <class Cols>
+int pyramid_check(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F,
+                  int h, int w, int reference_mask, int polarity, const Levels &lv, bool backward, bool outputs,
                   const void *workspace, size_t workspace_bytes, Plan &pl, PyramidLayout &lay)
 {
     if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
@@ -592,8 +645,63 @@ int pyramid_check(const int64_t *x, const int64_t *y, const float *t, const int6
     if (!pyramid_layout(F, h, w, pl, lv, true, lay) || !outputs || !frame_ts || !frame_sample) return DVSOF_EINVAL;
     for (int k = 0; k < lv.K; ++k)
         if (!lv.level[k].flow || (backward && !lv.level[k].grad_flow)) return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || !sample_index || (polarity && !p))) return DVSOF_EINVAL;
+    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
     if (!workspace || workspace_bytes < lay.bytes) return DVSOF_ENOSPACE;
+    return DVSOF_OK;
+}
+
+// dvsof_contrast_pyramid_fwd / _bwd on either form of the event columns
+template <class Cols>
+int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
+                int w, int reference_mask, int polarity, const Levels &levels, dvsof_iwe_result_t *result,
+                float *terms, float *value, void *workspace, size_t workspace_bytes, void *stream)
+{
+    Plan pl;
+    PyramidLayout lay;
+    const int rc = pyramid_check(cols, n_events, frame_ts, frame_sample, F, h, w, reference_mask, polarity, levels,
+                                 false, result && terms && value, workspace, workspace_bytes, pl, lay);
+    if (rc != DVSOF_OK || F == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const PyramidWorkspace ws = carve_pyramid(workspace, lay);
+    DVSOF_HIP_TRY((hipError_t)fill_u32(ws.q, 0u, lay.zeroed_bytes, st));
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(contrast_pyramid_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
+                                cols, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels, ws.q, ws.count);
+        DVSOF_LAUNCH_CHECK();
+    }
+    for (int k = 0; k < levels.K; ++k) {
+        const Level &L = levels.level[k];
+        const int rs = dvsof_iwe_stats((const int64_t *)ws.q + L.image_offset, ws.count + L.image_offset, pl.M, L.h,
+                                       L.w, result + L.row_offset, ws.stats, lay.stats_bytes, stream);
+        if (rs != DVSOF_OK) return rs;
+    }
+    hipLaunchKernelGGL(contrast_pyramid_close_kernel, dim3(1), dim3(kWave), 0, st, result, F, pl.R * pl.C,
+                       pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, levels, ws.rec, ws.unit, terms, value);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+template <class Cols>
+int pyramid_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
+                int w, int reference_mask, int polarity, const Levels &levels, void *workspace,
+                size_t workspace_bytes, const float *seed, void *stream)
+{
+    Plan pl;
+    PyramidLayout lay;
+    const int rc = pyramid_check(cols, n_events, frame_ts, frame_sample, F, h, w, reference_mask, polarity, levels,
+                                 true, seed != nullptr, workspace, workspace_bytes, pl, lay);
+    if (rc != DVSOF_OK || F == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const PyramidWorkspace ws = carve_pyramid(workspace, lay);
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(contrast_pyramid_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
+                                cols, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
+                                (const int64_t *)ws.q, (const ImageRec *)ws.rec, (const double *)ws.unit, ws.sums);
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(contrast_pyramid_bwd_close_kernel, dim3(event_blocks((int64_t)lay.sums_elems)), dim3(NT), 0,
+                       st, (long long *)ws.sums, (const double *)ws.unit, seed, F, pl.M, levels, lay.sums_elems);
+    DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
 
@@ -617,31 +725,8 @@ int dvsof_contrast_pyramid_fwd(const int64_t *x, const int64_t *y, const float *
                                dvsof_contrast_levels_t levels, dvsof_iwe_result_t *result, float *terms,
                                float *value, void *workspace, size_t workspace_bytes, void *stream)
 {
-    Plan pl;
-    PyramidLayout lay;
-    const int rc = pyramid_check(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, reference_mask,
-                                 polarity, levels, false, result && terms && value, workspace, workspace_bytes, pl,
-                                 lay);
-    if (rc != DVSOF_OK || F == 0) return rc;
-    hipStream_t st = as_stream(stream);
-    const PyramidWorkspace ws = carve_pyramid(workspace, lay);
-    DVSOF_HIP_TRY((hipError_t)fill_u32(ws.q, 0u, lay.zeroed_bytes, st));
-    if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(contrast_pyramid_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x,
-                                y, t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
-                                ws.q, ws.count);
-        DVSOF_LAUNCH_CHECK();
-    }
-    for (int k = 0; k < levels.K; ++k) {
-        const Level &L = levels.level[k];
-        const int rs = dvsof_iwe_stats((const int64_t *)ws.q + L.image_offset, ws.count + L.image_offset, pl.M, L.h,
-                                       L.w, result + L.row_offset, ws.stats, lay.stats_bytes, stream);
-        if (rs != DVSOF_OK) return rs;
-    }
-    hipLaunchKernelGGL(contrast_pyramid_close_kernel, dim3(1), dim3(kWave), 0, st, result, F, pl.R * pl.C,
-                       pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, levels, ws.rec, ws.unit, terms, value);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return pyramid_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                       reference_mask, polarity, levels, result, terms, value, workspace, workspace_bytes, stream);
 }
 
 int dvsof_contrast_pyramid_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
@@ -650,23 +735,30 @@ int dvsof_contrast_pyramid_bwd(const int64_t *x, const int64_t *y, const float *
                                dvsof_contrast_levels_t levels, void *workspace, size_t workspace_bytes,
                                const float *seed, void *stream)
 {
-    Plan pl;
-    PyramidLayout lay;
-    const int rc = pyramid_check(x, y, t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, reference_mask,
-                                 polarity, levels, true, seed != nullptr, workspace, workspace_bytes, pl, lay);
-    if (rc != DVSOF_OK || F == 0) return rc;
-    hipStream_t st = as_stream(stream);
-    const PyramidWorkspace ws = carve_pyramid(workspace, lay);
-    if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(contrast_pyramid_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
-                                x, y, t, p, sample_index, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
-                                (const int64_t *)ws.q, (const ImageRec *)ws.rec, (const double *)ws.unit, ws.sums);
-        DVSOF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(contrast_pyramid_bwd_close_kernel, dim3(event_blocks((int64_t)lay.sums_elems)), dim3(NT), 0,
-                       st, (long long *)ws.sums, (const double *)ws.unit, seed, F, pl.M, levels, lay.sums_elems);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return pyramid_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                       reference_mask, polarity, levels, workspace, workspace_bytes, seed, stream);
+}
+
+int dvsof_contrast_pyramid_fwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                       const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                       const float *frame_ts, const int64_t *frame_sample, int F, int h, int w,
+                                       int reference_mask, int polarity_channels, dvsof_contrast_levels_t levels,
+                                       dvsof_iwe_result_t *result, float *terms, float *value, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    return pyramid_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                       F, h, w, reference_mask, polarity_channels, levels, result, terms, value, workspace,
+                       workspace_bytes, stream);
+}
+
+int dvsof_contrast_pyramid_bwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                       const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                       const float *frame_ts, const int64_t *frame_sample, int F, int h, int w,
+                                       int reference_mask, int polarity_channels, dvsof_contrast_levels_t levels,
+                                       void *workspace, size_t workspace_bytes, const float *seed, void *stream)
+{
+    return pyramid_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                       F, h, w, reference_mask, polarity_channels, levels, workspace, workspace_bytes, seed, stream);
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, voxel
 from .timer import FakeTimer
 
 
@@ -506,6 +506,72 @@ def contrast_multi_bwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, fl
     return sw * value.astype(_F32), sums
 
 
+def wire_event_columns(events):
+    """The wire columns a compact event dict (voxel.is_compact) stands for, on
+    the dict's device, by the definition of include/dvsof_event_terms_encoded.h:
+    x, y widened to int64, polarity ? +1 : -1, and sample_index[i] the largest
+    b in [0, B) with sample_event_offsets[b] <= i (empty samples are repeated
+    offsets; a slot at or past the last offset falls to sample B - 1).  -> dict
+    of x, y, timestamp, polarity, sample_index.  A wire dict is returned as it
+    is.  For the host restatements and the tests: the encoded entry points give
+    the bytes of their wire twins on these columns."""
+    if not voxel.is_compact(events):
+        return events
+    off = torch.as_tensor(events['sample_event_offsets']).long().reshape(-1)
+    x = torch.as_tensor(events['x'])
+    B = off.numel() - 1
+    assert B >= 1 or x.numel() == 0, 'one offset per sample plus the end'
+    index = torch.arange(x.numel(), dtype=torch.long, device=x.device)
+    sample = (torch.searchsorted(off[:max(B, 0)].to(x.device), index, right=True) - 1).clamp_(min=0)
+    return {'x': x.long(), 'y': torch.as_tensor(events['y']).long(),
+            'timestamp': torch.as_tensor(events['timestamp']).float(),
+            'polarity': torch.as_tensor(events['polarity']).bool().long() * 2 - 1,
+            'sample_index': sample}
+
+
+def _as_bytes(polarity):
+    """The bool polarity column as the uint8 the entry points read: a view of
+    the same bytes (no launch, which matters inside a captured step); another
+    dtype is cast as voxel.voxelize_compact casts it."""
+    return polarity.view(torch.uint8) if polarity.dtype == torch.bool else polarity.to(torch.uint8)
+
+
+def _term_columns(events, polarity):
+    """-> (x, y, timestamp, polarity or None, sample) of an event dict for the
+    four autograd functions below: the wire columns as they are, or the compact
+    ones (voxel.is_compact) with the casts of voxel.voxelize_compact, where
+    ``sample`` is sample_event_offsets and x is int16, which is how the
+    functions tell the two forms apart."""
+    if not voxel.is_compact(events):
+        cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
+        return cols[:3] + (events['polarity'] if polarity else None, cols[3])
+    return (events['x'].to(torch.short).contiguous(), events['y'].to(torch.short).contiguous(),
+            events['timestamp'].to(torch.float32).contiguous(),
+            _as_bytes(events['polarity']).contiguous() if polarity else None,
+            events['sample_event_offsets'].to(torch.long).contiguous())
+
+
+def _bind_columns(x, y, t, p, sample, polarity):
+    """The event-column arguments of an entry point and of its encoded twin
+    (include/dvsof_event_terms_encoded.h) -> (suffix of the entry point's name,
+    the leading arguments up to and including n_events, the tensors they point
+    into).  int16 x: the compact columns, ``sample`` their B + 1 offsets."""
+    cols = tuple(c.contiguous() for c in (x, y, t, sample))
+    pol = p.contiguous() if polarity else None
+    n = cols[0].numel()
+    assert cols[0].numel() == cols[1].numel() == cols[2].numel() and cols[2].dtype == torch.float32
+    assert pol is None or pol.numel() == n
+    if cols[0].dtype == torch.short:
+        assert cols[1].dtype == torch.short and cols[3].dtype == torch.long
+        assert pol is None or pol.dtype == torch.uint8
+        B = cols[3].numel() - 1
+        assert B >= 1, 'one offset per sample plus the end'
+        return '_encoded', [c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), B, n], (cols, pol)
+    assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[3].numel() == n
+    assert pol is None or pol.dtype == torch.long
+    return '', [c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), n], (cols, pol)
+
+
 class _Contrast(torch.autograd.Function):
     """(weight * term, term) of the finest flow; the gradient of the first
     enters the flow (dvsof_contrast_multi_fwd / dvsof_contrast_multi_bwd, with
@@ -527,19 +593,14 @@ class _Contrast(torch.autograd.Function):
             torch.empty((), dtype=torch.float32, device=dev)
         nbytes = lib.dvsof_contrast_multi_workspace_bytes(F, mask, int(polarity), h, w)
         ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
-        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
-        pol = p.contiguous() if polarity else None
         tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
         assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flow.shape, frame_ts.shape)
-        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
-        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
-        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
-        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
-                                                        tables[0].data_ptr(), tables[1].data_ptr(),
-                                                        flow.data_ptr(), F, h, w, mask, int(polarity)])
-        _lib.check(lib.dvsof_contrast_multi_fwd(
+        ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
+        ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
+                       flow.data_ptr(), F, h, w, mask, int(polarity)])
+        _lib.check(getattr(lib, 'dvsof_contrast_multi_fwd' + ctx.form)(
             *ctx.args, q.data_ptr(), count.data_ptr(), result.data_ptr(), term.data_ptr(), ws.data_ptr(),
-            nbytes, _lib.stream()), 'dvsof_contrast_multi_fwd')
+            nbytes, _lib.stream()), 'dvsof_contrast_multi_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flow, q, ws, nbytes)
         ctx.weight = float(weight)
         ctx.mark_non_differentiable(term)
@@ -553,9 +614,9 @@ class _Contrast(torch.autograd.Function):
         flow, q, ws, nbytes = ctx.held[3:]
         grad = torch.empty_like(flow)
         seed = g_value.contiguous().float()
-        _lib.check(_lib.lib().dvsof_contrast_multi_bwd(
+        _lib.check(getattr(_lib.lib(), 'dvsof_contrast_multi_bwd' + ctx.form)(
             *ctx.args, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(),
-            _lib.stream()), 'dvsof_contrast_multi_bwd')
+            _lib.stream()), 'dvsof_contrast_multi_bwd' + ctx.form)
         return (grad,) + (None,) * 10
 
 
@@ -690,19 +751,14 @@ class _ContrastPyramid(torch.autograd.Function):
         h, w = (int(v) for v in shape)
         nbytes = lib.dvsof_contrast_pyramid_workspace_bytes(F, mask, int(polarity), h, w, table)
         ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
-        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
-        pol = p.contiguous() if polarity else None
         tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
         assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flows[0].shape, frame_ts.shape)
-        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
-        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
-        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
-        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
-                                                        tables[0].data_ptr(), tables[1].data_ptr(),
-                                                        F, h, w, mask, int(polarity)])
-        _lib.check(lib.dvsof_contrast_pyramid_fwd(
+        ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
+        ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
+                       F, h, w, mask, int(polarity)])
+        _lib.check(getattr(lib, 'dvsof_contrast_pyramid_fwd' + ctx.form)(
             *ctx.args, table, result.data_ptr(), terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes,
-            _lib.stream()), 'dvsof_contrast_pyramid_fwd')
+            _lib.stream()), 'dvsof_contrast_pyramid_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flows, ws, nbytes, table)
         ctx.mark_non_differentiable(terms)
         ctx.set_materialize_grads(False)
@@ -717,9 +773,9 @@ class _ContrastPyramid(torch.autograd.Function):
         for k, g in enumerate(grads):
             table.level[k].grad_flow = g.data_ptr()
         seed = g_value.contiguous().float()
-        _lib.check(_lib.lib().dvsof_contrast_pyramid_bwd(
+        _lib.check(getattr(_lib.lib(), 'dvsof_contrast_pyramid_bwd' + ctx.form)(
             *ctx.args, table, ws.data_ptr(), nbytes, seed.data_ptr(), _lib.stream()),
-            'dvsof_contrast_pyramid_bwd')
+            'dvsof_contrast_pyramid_bwd' + ctx.form)
         return (None,) * 11 + grads
 
 
@@ -875,18 +931,13 @@ class _AvgTimestamp(torch.autograd.Function):
             torch.empty((), dtype=torch.float32, device=dev)
         nbytes = lib.dvsof_avg_timestamp_workspace_bytes(F, mask, int(polarity), h, w)
         ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
-        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
-        pol = p.contiguous() if polarity else None
         tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
         assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flow.shape, frame_ts.shape)
-        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
-        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
-        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
-        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
-                                                        tables[0].data_ptr(), tables[1].data_ptr(),
-                                                        flow.data_ptr(), F, h, w, mask, int(polarity)])
-        _lib.check(lib.dvsof_avg_timestamp_fwd(*ctx.args, term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
-                   'dvsof_avg_timestamp_fwd')
+        ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
+        ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
+                       flow.data_ptr(), F, h, w, mask, int(polarity)])
+        _lib.check(getattr(lib, 'dvsof_avg_timestamp_fwd' + ctx.form)(
+            *ctx.args, term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_avg_timestamp_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flow, ws, nbytes)
         ctx.weight = float(weight)
         ctx.mark_non_differentiable(term)
@@ -900,9 +951,9 @@ class _AvgTimestamp(torch.autograd.Function):
         flow, ws, nbytes = ctx.held[3:]
         grad = torch.empty_like(flow)
         seed = g_value.contiguous().float()
-        _lib.check(_lib.lib().dvsof_avg_timestamp_bwd(
+        _lib.check(getattr(_lib.lib(), 'dvsof_avg_timestamp_bwd' + ctx.form)(
             *ctx.args, ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(), _lib.stream()),
-            'dvsof_avg_timestamp_bwd')
+            'dvsof_avg_timestamp_bwd' + ctx.form)
         return (grad,) + (None,) * 10
 
 
@@ -1001,19 +1052,14 @@ class _AvgTimestampPyramid(torch.autograd.Function):
         h, w = (int(v) for v in shape)
         nbytes = lib.dvsof_avg_timestamp_pyramid_workspace_bytes(F, mask, int(polarity), h, w, table)
         ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
-        cols = tuple(c.contiguous() for c in (x, y, t, sample_index))
-        pol = p.contiguous() if polarity else None
         tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
         assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flows[0].shape, frame_ts.shape)
-        assert cols[0].dtype == cols[1].dtype == cols[3].dtype == torch.long and cols[2].dtype == torch.float32
-        assert cols[0].numel() == cols[1].numel() == cols[2].numel() == cols[3].numel()
-        assert pol is None or (pol.dtype == torch.long and pol.numel() == cols[0].numel())
-        ctx.args = ([c.data_ptr() for c in cols[:3]] + [_lib.ptr(pol), cols[3].data_ptr(), cols[0].numel(),
-                                                        tables[0].data_ptr(), tables[1].data_ptr(),
-                                                        F, h, w, mask, int(polarity)])
-        _lib.check(lib.dvsof_avg_timestamp_pyramid_fwd(
+        ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
+        ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
+                       F, h, w, mask, int(polarity)])
+        _lib.check(getattr(lib, 'dvsof_avg_timestamp_pyramid_fwd' + ctx.form)(
             *ctx.args, table, terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
-            'dvsof_avg_timestamp_pyramid_fwd')
+            'dvsof_avg_timestamp_pyramid_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flows, ws, nbytes, table)
         ctx.mark_non_differentiable(terms)
         ctx.set_materialize_grads(False)
@@ -1028,9 +1074,9 @@ class _AvgTimestampPyramid(torch.autograd.Function):
         for k, g in enumerate(grads):
             table.level[k].grad_flow = g.data_ptr()
         seed = g_value.contiguous().float()
-        _lib.check(_lib.lib().dvsof_avg_timestamp_pyramid_bwd(
+        _lib.check(getattr(_lib.lib(), 'dvsof_avg_timestamp_pyramid_bwd' + ctx.form)(
             *ctx.args, table, ws.data_ptr(), nbytes, seed.data_ptr(), _lib.stream()),
-            'dvsof_avg_timestamp_pyramid_bwd')
+            'dvsof_avg_timestamp_pyramid_bwd' + ctx.form)
         return (None,) * 11 + grads
 
 
@@ -1169,7 +1215,9 @@ class Losses:
         (docs/CONTRAST_SPEC.md): the mean over the predictions of
         1 - var(image of warped events) / var(count image), negative where the
         flow sharpens the events of its own window.  events: the wire columns
-        on the device.  -> the 0-dim term, differentiable with respect to
+        on the device, or the compact ones (voxel.is_compact), which go to the
+        encoded entry points as they are and give the same bytes
+        (``wire_event_columns``).  -> the 0-dim term, differentiable with respect to
         ``flows[-1]``; with a ``weight`` -> (weight * term, term), the first
         differentiable (the weight is applied inside the backward kernel), the
         second detached for logging.  Nothing waits for the device.
@@ -1196,11 +1244,11 @@ class Losses:
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the contrast term of scale {self.shapes[-1]}'
-        cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
+        *cols, pol, sample = _term_columns(events, polarity)
+        cols.append(sample)
         _lib.require_cuda(flow, flow_ts, flow_sample_idx, *cols)
         mask = contrast_reference_mask(references)
         weight_ = 1.0 if weight is None else float(weight)
-        pol = events['polarity'] if polarity else None
         _lib.require_cuda(pol)
         value, term = _Contrast.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
                                       bool(polarity))
@@ -1226,11 +1274,11 @@ class Losses:
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the average-timestamp term of scale {self.shapes[-1]}'
-        cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
+        *cols, pol, sample = _term_columns(events, polarity)
+        cols.append(sample)
         _lib.require_cuda(flow, flow_ts, flow_sample_idx, *cols)
         mask = contrast_reference_mask(references)
         weight_ = 1.0 if weight is None else float(weight)
-        pol = events['polarity'] if polarity else None
         _lib.require_cuda(pol)
         value, term = _AvgTimestamp.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
                                           bool(polarity))
@@ -1263,13 +1311,13 @@ class Losses:
 
     def _event_term_all(self, function, flows, flow_ts, flow_sample_idx, events, weight, references, polarity):
         self._check_flows(flows)
-        cols = tuple(events[k] for k in ('x', 'y', 'timestamp', 'sample_index'))
+        *cols, pol, sample = _term_columns(events, polarity)
+        cols.append(sample)
         _lib.require_cuda(flow_ts, flow_sample_idx, *flows, *cols)
         mask = contrast_reference_mask(references)
         for shape in self.shapes:                       # a level that is no halving is refused here
             contrast_level_shift(self.shapes[-1], shape)
         weights = contrast_level_weights(1.0 if weight is None else weight, len(flows))
-        pol = events['polarity'] if polarity else None
         _lib.require_cuda(pol)
         value, terms = function.apply(*cols[:3], pol, cols[3], flow_ts, flow_sample_idx,
                                       self.shapes[-1], weights, mask, bool(polarity), *flows)

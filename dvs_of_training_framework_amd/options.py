@@ -307,8 +307,8 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'count image, negative where the flow sharpens the events '
                              '(docs/CONTRAST_SPEC.md); logged as Train/contrast and '
                              'Validation/contrast.  Needs the raw events in their wire '
-                             'columns on the device (not --ev_images, not '
-                             '--compact-events); --capture replays such a run only with '
+                             'columns on the device (not --ev_images; --compact-events only '
+                             'with --compact-event-terms); --capture replays such a run only with '
                              '--capture-event-terms.  0: off')
     parser.add_argument('--contrast-references', dest='contrast_references',
                         default='start', type=str,
@@ -339,8 +339,9 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              '(docs/AVG_TIMESTAMP_SPEC.md; Zhu et al. 2019); logged as '
                              'Train/avg timestamp and Validation/avg timestamp.  With or '
                              'without --contrast-weight.  Needs the raw events in their wire '
-                             'columns on the device (not --ev_images, not --compact-events); '
-                             '--capture replays such a run only with --capture-event-terms.  Absent or 0: '
+                             'columns on the device (not --ev_images; --compact-events only with '
+                             '--compact-event-terms); --capture replays such a run only with '
+                             '--capture-event-terms.  Absent or 0: '
                              'off')
     parser.add_argument('--avg-timestamp-references', dest='avg_timestamp_references',
                         default=argparse.SUPPRESS, type=str,
@@ -367,6 +368,14 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'with all their options, and the frameless batches of --recording, '
                              'instead of running the loop eagerly for them; bit-identical to '
                              'the eager step.  Opt-in: without it --capture decides as before')
+    parser.add_argument('--compact-event-terms', dest='compact_event_terms',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='with --compact-events and a positive --contrast-weight or '
+                             '--avg-timestamp-weight: those terms read the 9 B/event encoded '
+                             'columns as they are (include/dvsof_event_terms_encoded.h), with all '
+                             'their options, and give the bytes they give on the decoded wire '
+                             'columns.  Opt-in: without it the terms refuse --compact-events as '
+                             'before')
     parser.add_argument('--recording', dest='recording', default=None, type=Path,
                         help='train from ONE event-only recording kept on the device: a '
                              '.npz or .hdf5 file with the arrays x, y, t, p (sorted by t) and '
@@ -444,8 +453,25 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_capture_event_terms_args(validate_frameless_args(validate_sharpness_args(
-        validate_avg_timestamp_args(validate_contrast_args(args)))))
+    return validate_compact_event_terms_args(validate_capture_event_terms_args(validate_frameless_args(
+        validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args))))))
+
+
+def validate_compact_event_terms_args(args):
+    """--compact-event-terms (absent from ``args`` unless given) against what
+    it needs: --compact-events, and a term to read those columns.  With it the
+    two terms do not refuse --compact-events (validate_contrast_args,
+    validate_avg_timestamp_args)."""
+    if not getattr(args, 'compact_event_terms', False):
+        return args
+    if not getattr(args, 'compact_events', False):
+        raise SystemExit('--compact-event-terms needs --compact-events: it says what reads the '
+                         'encoded event columns')
+    if not (getattr(args, 'contrast_weight', 0.0) > 0 or getattr(args, 'avg_timestamp_weight', 0.0) > 0):
+        raise SystemExit('--compact-event-terms needs a positive --contrast-weight or '
+                         '--avg-timestamp-weight: without either there is no events-only term to '
+                         'feed')
+    return args
 
 
 def validate_capture_event_terms_args(args):
@@ -498,7 +524,7 @@ def validate_contrast_args(args):
         raise SystemExit('--contrast-weight cannot be combined with --ev_images: the term is '
                          'computed from the raw events on the device, and a batch of '
                          'preprocessed event images carries none')
-    if weight > 0 and getattr(args, 'compact_events', False):
+    if weight > 0 and getattr(args, 'compact_events', False) and not getattr(args, 'compact_event_terms', False):
         raise SystemExit('--contrast-weight cannot be combined with --compact-events: the term '
                          'reads the int64 / float32 wire columns, not the 9 B/event encoded ones')
     return args
@@ -529,7 +555,7 @@ def validate_avg_timestamp_args(args):
         raise SystemExit('--avg-timestamp-weight cannot be combined with --ev_images: the term is '
                          'computed from the raw events on the device, and a batch of '
                          'preprocessed event images carries none')
-    if weight > 0 and getattr(args, 'compact_events', False):
+    if weight > 0 and getattr(args, 'compact_events', False) and not getattr(args, 'compact_event_terms', False):
         raise SystemExit('--avg-timestamp-weight cannot be combined with --compact-events: the term '
                          'reads the int64 / float32 wire columns, not the 9 B/event encoded ones')
     return args

@@ -121,8 +121,9 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     gradients come out of one sweep (loss.Losses.fused).
 
     contrast_weight > 0: plus contrast_weight * the contrast-maximisation term
-    of the finest flow over ``events``, the wire columns on the device
-    (loss.Losses.contrast, docs/CONTRAST_SPEC.md); the term rides on the
+    of the finest flow over ``events``, the wire columns on the device or the
+    compact ones (voxel.is_compact; the same bytes either way, CONTRAST_SPEC
+    section 24) (loss.Losses.contrast, docs/CONTRAST_SPEC.md); the term rides on the
     returned terms as ``.contrast``.  At 0 nothing of that is constructed and
     ``events`` is not looked at.  contrast_references, contrast_polarity: the
     reference times of the term and whether ON and OFF events are kept apart
@@ -313,8 +314,9 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
-    """batch (SURVEY 8b wire format) -> (loss, terms, tags[, outputs]).
-    contrast_weight > 0 (raw events only), contrast_references,
+    """batch (SURVEY 8b wire format, or compact event columns:
+    voxel.is_compact) -> (loss, terms, tags[, outputs]).
+    contrast_weight > 0 (raw events only, in either column form), contrast_references,
     contrast_polarity, contrast_scales, and avg_timestamp_weight > 0 (raw
     events only) with its references, polarity and scales: see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes

@@ -56,6 +56,13 @@
 #                                     frameless + contrast on every scale, the same + average timestamp, f32 and bf16s,
 #                                     eager loop against executor replay in alternating blocks of one run after a
 #                                     bitwise comparison of the two (profiles/event_terms_capture/README.md)
+#   eventencoded [event_terms_encoded_bench.py args]  the events-only terms on the 9 B/event encoded columns
+#                                     (--compact-event-terms; tools/event_terms_encoded_bench.py): the eight encoded
+#                                     entry points against their wire twins after a bitwise comparison, and the train
+#                                     loop fed through feed.DeviceFeeder with the contrast term on every scale, compact
+#                                     against wire batches, eager and replayed, in alternating blocks of one run; on a
+#                                     commit without the entry points the wire legs alone
+#                                     (profiles/event_terms_encoded/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -139,6 +146,9 @@ avgts_pyramid)
 eventcapture)
   timeout -k 10 560 env "${envs[@]}" python tools/event_terms_capture_bench.py "$@" > $O/eventcapture.jsonl 2> $O/eventcapture.err
   echo "eventcapture rc=$?"; cut -c1-900 $O/eventcapture.jsonl; tail -3 $O/eventcapture.err ;;
+eventencoded)
+  timeout -k 10 560 env "${envs[@]}" python tools/event_terms_encoded_bench.py "$@" > $O/eventencoded.jsonl 2> $O/eventencoded.err
+  echo "eventencoded rc=$?"; cut -c1-700 $O/eventencoded.jsonl; tail -3 $O/eventencoded.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err
