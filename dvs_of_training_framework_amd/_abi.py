@@ -49,6 +49,8 @@ AVG_TIMESTAMP_PYRAMID_PATH = HEADER_PATH.with_name('dvsof_avg_timestamp_pyramid.
 # And the two events-only terms on the encoded event columns (EVENT_TERMS_ENCODED_FUNCTIONS):
 # functions only, the twins of calls of the four headers before it
 EVENT_TERMS_ENCODED_PATH = HEADER_PATH.with_name('dvsof_event_terms_encoded.h')
+# And the average-timestamp images of the validation metric (IWE_AVG_TIMESTAMP_FUNCTIONS), functions only
+IWE_AVG_TIMESTAMP_PATH = HEADER_PATH.with_name('dvsof_iwe_avg_timestamp.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -241,3 +243,7 @@ EVENT_TERMS_ENCODED_FUNCTIONS = _read_extension(
     | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS)
     | set(AVG_TIMESTAMP_FUNCTIONS) | set(AVG_TIMESTAMP_PYRAMID_FUNCTIONS),
     base=_struct_headers[CONTRAST_PYRAMID_PATH])
+IWE_AVG_TIMESTAMP_FUNCTIONS = _read_extension(
+    IWE_AVG_TIMESTAMP_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
+    | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS)
+    | set(AVG_TIMESTAMP_FUNCTIONS) | set(AVG_TIMESTAMP_PYRAMID_FUNCTIONS) | set(EVENT_TERMS_ENCODED_FUNCTIONS))

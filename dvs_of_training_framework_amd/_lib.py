@@ -18,7 +18,9 @@ tests/golden/abi_signatures_avg_timestamp.json; _abi.AVG_TIMESTAMP_PYRAMID_PATH:
 include/dvsof_avg_timestamp_pyramid.h, recorded in
 tests/golden/abi_signatures_avg_timestamp_pyramid.json;
 _abi.EVENT_TERMS_ENCODED_PATH: include/dvsof_event_terms_encoded.h, recorded in
-tests/golden/abi_signatures_event_terms_encoded.json).
+tests/golden/abi_signatures_event_terms_encoded.json;
+_abi.IWE_AVG_TIMESTAMP_PATH: include/dvsof_iwe_avg_timestamp.h, recorded in
+tests/golden/abi_signatures_iwe_avg_timestamp.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -59,6 +61,8 @@ _AVG_TIMESTAMP_SIGNATURES = _abi.AVG_TIMESTAMP_FUNCTIONS
 _AVG_TIMESTAMP_PYRAMID_SIGNATURES = _abi.AVG_TIMESTAMP_PYRAMID_FUNCTIONS
 # and of include/dvsof_event_terms_encoded.h, the two terms on the encoded event columns
 _EVENT_TERMS_ENCODED_SIGNATURES = _abi.EVENT_TERMS_ENCODED_FUNCTIONS
+# and of include/dvsof_iwe_avg_timestamp.h, the average-timestamp images of the validation metric
+_IWE_AVG_TIMESTAMP_SIGNATURES = _abi.IWE_AVG_TIMESTAMP_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -119,6 +123,11 @@ def declared_event_terms_encoded_symbols():
     return _declared_in((_abi.EVENT_TERMS_ENCODED_PATH,))
 
 
+def declared_iwe_avg_timestamp_symbols():
+    """Names of all entry points include/dvsof_iwe_avg_timestamp.h declares."""
+    return _declared_in((_abi.IWE_AVG_TIMESTAMP_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -136,7 +145,8 @@ def lib():
                                   **_IWE_MULTI_SIGNATURES, **_LOSS_FRAMELESS_SIGNATURES,
                                   **_CONTRAST_PYRAMID_SIGNATURES, **_AVG_TIMESTAMP_SIGNATURES,
                                   **_AVG_TIMESTAMP_PYRAMID_SIGNATURES,
-                                  **_EVENT_TERMS_ENCODED_SIGNATURES}.items():
+                                  **_EVENT_TERMS_ENCODED_SIGNATURES,
+                                  **_IWE_AVG_TIMESTAMP_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -26,9 +26,11 @@
 // At the end of the file: the term on every flow scale of the network by one
 // fill, one splat, one closing wave and one backward for all levels (sections
 // 11-15, include/dvsof_avg_timestamp_pyramid.h).  What one event does to the
-// images of a frame, forward and backward, is stated once (avgts_splat_event,
-// avgts_bwd_event) and used by the one-level kernels and by those.
+// images of a frame, forward and backward, is stated once (avgts_splat_event
+// of avg_timestamp_images.h, avgts_bwd_event) and used by the one-level
+// kernels and by those.
 #include "event_columns.h"
+#include "avg_timestamp_images.h"
 #include "../../include/dvsof_avg_timestamp.h"
 #include "../../include/dvsof_avg_timestamp_pyramid.h"
 #include "../../include/dvsof_event_terms_encoded.h"
@@ -38,7 +40,6 @@ namespace {
 constexpr int NT = kFrameNT;
 constexpr int kUnitBits = 40;    // R = 1: |one event's addend| < 2^(kUnitBits + 1) units
 constexpr int kSharedBits = 2;   // R > 1: up to three addends of a pixel's event share a sum
-constexpr double kEps = 0x1p-10;  // T = A / (I + kEps): 1 / (I + kEps) <= 1024
 
 // one per image, in the workspace behind the zeroed region
 struct ImageRec {
@@ -51,58 +52,12 @@ struct ImageRec {
 };
 static_assert(sizeof(ImageRec) == 64, "the workspace holds 64 bytes per image");
 
-// the accumulator of the statistics
-struct StatRow {
-    double S, S0, peak;
-    uint32_t n, n0;  // at most h w < 2^30
-};
-static_assert(sizeof(StatRow) == 32, "the workspace holds 32 bytes per statistics row");
-
 // ---------------------------------------------------------------------------
-// Forward.  An event at (xi, yi) = pixel pix inside an h x w frame, of channel
-// c, at tau of the window of its frame f, with the flow (u, v) at its own pixel
-// (read once for all references): per reference the count and the distance at
-// the event's own pixel, and at the corners inside the image the weight and the
-// weight times the distance.  plane: h w; q, s, base and count start at the
-// images of this shape.
+// Forward.  What an event does to the images of its frame (avgts_splat_event)
+// and the statistics of an image (StatRow, AvgSum, avgts_stats_partial_kernel)
+// are those of avg_timestamp_images.h, which the validation metric of iwe.hip
+// shares.  Here: the event loop and the frame rule of contrast_splat_kernel.
 // ---------------------------------------------------------------------------
-template <int R, bool POL>
-__device__ __forceinline__ void avgts_splat_event(const Refs &refs, int f, int c, float tau, float u, float v,
-                                                  int64_t xi, int64_t yi, size_t pix, size_t plane, int h, int w,
-                                                  unsigned long long *__restrict__ q,
-                                                  unsigned long long *__restrict__ s,
-                                                  unsigned long long *__restrict__ base,
-                                                  uint32_t *__restrict__ count)
-{
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const size_t m = image_of<R, POL>(f, r, c);
-        Warp p;
-        const bool inside = warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p);
-        const float a = fabsf(p.tau);  // p.tau holds sig, set before the inside test; 0 <= a <= 1
-        atomicAdd(count + m * plane + pix, 1u);
-        const int64_t B = (int64_t)(a * kOne);  // exact; 0 <= B <= 2^32
-        if (B > 0) atomicAdd(base + m * plane + pix, (unsigned long long)B);
-        if (!inside) continue;
-        unsigned long long *qm = q + m * plane, *sm = s + m * plane;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int xx = p.cx + i, yy = p.cy + j;
-                if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
-                const float wgt = p.wy[j] * p.wx[i];
-                const int64_t Q = (int64_t)(wgt * kOne);         // the addend of splat_corners
-                const int64_t QA = (int64_t)((wgt * a) * kOne);  // one float32 product, then exact; QA <= Q
-                const size_t at = (size_t)yy * w + (size_t)xx;
-                if (Q > 0) atomicAdd(qm + at, (unsigned long long)Q);
-                if (QA > 0) atomicAdd(sm + at, (unsigned long long)QA);
-            }
-        }
-    }
-}
-
-// The event loop and the frame rule of contrast_splat_kernel.
 template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void avgts_splat_kernel(
     const Cols cols, int64_t n, const float *__restrict__ ts,
@@ -131,42 +86,6 @@ __global__ __launch_bounds__(NT) void avgts_splat_kernel(
             avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, s, base, count);
         }
     }
-}
-
-// ---------------------------------------------------------------------------
-// Statistics, by the fixed-order reduction of frame_common.h.
-// ---------------------------------------------------------------------------
-struct AvgSum {
-    using Row = StatRow;
-    static __device__ __forceinline__ Row zero() { return Row{0.0, 0.0, 0.0, 0u, 0u}; }
-    static __device__ __forceinline__ Row add(const Row &a, const Row &b)
-    {
-        return Row{a.S + b.S, a.S0 + b.S0, a.peak > b.peak ? a.peak : b.peak, a.n + b.n, a.n0 + b.n0};
-    }
-};
-
-__global__ __launch_bounds__(NT) void avgts_stats_partial_kernel(
-    const int64_t *__restrict__ q, const int64_t *__restrict__ s, const int64_t *__restrict__ base,
-    const uint32_t *__restrict__ count, int h, int w, int nb, StatRow *__restrict__ part)
-{
-    const int m = blockIdx.y;
-    const int n = h * w;
-    const int64_t *qm = q + (size_t)m * n, *sm = s + (size_t)m * n, *bm = base + (size_t)m * n;
-    const uint32_t *cm = count + (size_t)m * n;
-    frame_partial<AvgSum>(n, nb, part, [=](StatRow &a, int p) {
-        const int64_t Q = qm[p];
-        const uint32_t c = cm[p];
-        const double den = (double)Q * 0x1p-32 + kEps;
-        const double T = (double)sm[p] * 0x1p-32 / den;
-        const double D = 1.0 / den;
-        const double T0 = (double)bm[p] * 0x1p-32 / ((double)c + kEps);
-        const double pk = 2.0 * T * D;
-        a.S += T * T;
-        a.S0 += T0 * T0;
-        a.peak = a.peak > pk ? a.peak : pk;
-        a.n += Q > 0;
-        a.n0 += c > 0;
-    });
 }
 
 // 2^k: the flow gradient of a frame is summed in units of 1/unit; |G_m| <= gmax < 2^e for every image of the frame

@@ -19,10 +19,18 @@
 // are those of event_images.h, which contrast.hip shares): it then writes the
 // count image of every channel too, repeated per reference, so that
 // dvsof_iwe_stats and dvsof_iwe_render take the M images as M frames.
+//
+// Beside the flow warp loss, the ratio of squared average timestamps
+// (docs/IWE_SPEC.md sections 14-21, include/dvsof_iwe_avg_timestamp.h): the
+// same events by the same frame rule, what each does to q, s, base and count
+// and the statistics of an image those of the training term
+// (avg_timestamp_images.h, which avg_timestamp.hip shares), so that one splat
+// serves both metrics.
 // This file relies on -ffp-contract=off.
 #include "render_common.h"
-#include "event_images.h"
+#include "avg_timestamp_images.h"
 #include "../../include/dvsof_iwe_multi.h"
+#include "../../include/dvsof_iwe_avg_timestamp.h"
 
 static_assert(sizeof(dvsof_iwe_result_t) == 48, "result rows are 48 bytes (eval.py reads them as such)");
 
@@ -54,6 +62,30 @@ __global__ __launch_bounds__(NT) void iwe_splat_kernel(
         const float *fl = flow + (size_t)f * 2 * plane + pix;
         const float u = fl[0], v = fl[plane];
         splat_event<R, POL, COUNT>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, count);
+    });
+}
+
+// The same events by the same rule, each doing to the four average-timestamp
+// images what it does in the training term (avgts_splat_event): per reference
+// one 32-bit atomic and up to nine 64-bit integer atomics.
+template <int R, bool POL>
+__global__ __launch_bounds__(NT) void iwe_avgts_splat_kernel(
+    const int64_t *__restrict__ x, const int64_t *__restrict__ y, const float *__restrict__ t,
+    const int64_t *__restrict__ pol, int64_t n, const int64_t *__restrict__ begin, const float *__restrict__ ts,
+    const float *__restrict__ flow, int F, int h, int w, Refs refs, unsigned long long *__restrict__ q,
+    unsigned long long *__restrict__ s, unsigned long long *__restrict__ base, uint32_t *__restrict__ count)
+{
+    const size_t plane = (size_t)h * w;
+    for_each_frame_event(n, begin, F, [=](int64_t e, int f) {
+        const int64_t xi = x[e], yi = y[e];
+        if (xi < 0 || xi >= w || yi < 0 || yi >= h) return;  // the -1 slots of cropped and padded events
+        int c;
+        if (!event_channel<POL>(pol, e, c)) return;
+        const size_t pix = (size_t)yi * w + (size_t)xi;
+        const float tau = event_tau(t[e], ts[2 * f], ts[2 * f + 1]);
+        const float *fl = flow + (size_t)f * 2 * plane + pix;
+        const float u = fl[0], v = fl[plane];
+        avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, s, base, count);
     });
 }
 
@@ -141,6 +173,55 @@ __global__ __launch_bounds__(kRenderNT) void iwe_render_kernel(
         emit_rows(it, canvas, IweGrey{q + (size_t)f * n, (float)((double)result[f].max_q * 0x1p-32)});
 }
 
+// The average distance in time at zero flow on the left, after the warp on the
+// right, on the fixed scale [0, 1): T < 1 on every pixel.
+struct AvgtsGrey {
+    const int64_t *q, *s, *base;
+    const uint32_t *count;
+    bool warped;
+    __device__ __forceinline__ Bgr operator()(size_t p) const
+    {
+        const AvgPixel px = avgts_pixel(q[p], s[p], base[p], count[p]);
+        const uint32_t g = grey_of((float)(warped ? px.T : px.T0), 1.f);
+        return Bgr{g, g, g};
+    }
+};
+
+__global__ __launch_bounds__(kRenderNT) void iwe_avgts_render_kernel(
+    const int64_t *__restrict__ q, const int64_t *__restrict__ s, const int64_t *__restrict__ base,
+    const uint32_t *__restrict__ count, int h, int w, int step, int chunks, uint8_t *__restrict__ canvas)
+{
+    const int c = blockIdx.x % chunks, mk = blockIdx.x / chunks;
+    const int m = mk / kPanels, panel = mk % kPanels;
+    const size_t at = (size_t)m * h * w;
+    dvsof_render_item_t it = {};
+    it.dst_stride = (int64_t)kPanels * 3 * w;
+    it.dst_offset = (int64_t)m * h * it.dst_stride;
+    it.h = h;
+    it.w = w;
+    it.x0 = panel * w;
+    it.row0 = c * step;
+    it.rows = min(step, h - it.row0);
+    emit_rows(it, canvas, AvgtsGrey{q + at, s + at, base + at, count + at, panel == 1});
+}
+
+// the region of images as byte offsets, in the order of the header
+struct AvgtsLayout {
+    size_t s, base, count, zeroed_bytes, bytes;
+};
+
+AvgtsLayout avgts_layout(int h, int w, const Plan &pl)
+{
+    const size_t P = (size_t)pl.M * h * w;
+    AvgtsLayout o;
+    o.s = sizeof(int64_t) * P;
+    o.base = o.s + sizeof(int64_t) * P;
+    o.count = o.base + sizeof(int64_t) * P;
+    o.zeroed_bytes = o.count + sizeof(uint32_t) * P;
+    o.bytes = (o.zeroed_bytes + 7) / 8 * 8;
+    return o;
+}
+
 }  // namespace
 
 extern "C" {
@@ -225,6 +306,73 @@ int dvsof_iwe_render(const int64_t *q, const uint32_t *count, const dvsof_iwe_re
     const int step = chunk_rows(h, w), chunks = (h + step - 1) / step;
     hipLaunchKernelGGL(iwe_render_kernel, dim3((unsigned)F * kPanels * chunks), dim3(kRenderNT), 0,
                        as_stream(stream), q, count, result, h, w, step, chunks, canvas);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+size_t dvsof_iwe_avg_timestamp_image_bytes(int F, int h, int w, int reference_mask, int polarity)
+{
+    Plan pl;
+    if (F < 1 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return 0;
+    return avgts_layout(h, w, pl).bytes;
+}
+
+size_t dvsof_iwe_avg_timestamp_workspace_bytes(int F, int h, int w, int reference_mask, int polarity)
+{
+    Plan pl;
+    if (F < 1 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return 0;
+    return sizeof(StatRow) * (size_t)pl.M * partial_blocks(h, w);
+}
+
+int dvsof_iwe_avg_timestamp(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                            int64_t n_events, const int64_t *frame_event_begin, const float *frame_ts,
+                            const float *flow, int F, int h, int w, int reference_mask, int polarity, void *images,
+                            size_t image_bytes, void *rows, void *workspace, size_t workspace_bytes, void *stream)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !images || !rows || !frame_event_begin || !frame_ts || !flow)
+        return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !t || (polarity && !p))) return DVSOF_EINVAL;
+    const AvgtsLayout lay = avgts_layout(h, w, pl);
+    const int nb = partial_blocks(h, w);
+    if (image_bytes < lay.bytes) return DVSOF_ENOSPACE;
+    if (!workspace || workspace_bytes < sizeof(StatRow) * (size_t)pl.M * nb) return DVSOF_ENOSPACE;
+    hipStream_t st = as_stream(stream);
+    char *im = (char *)images;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(im, 0u, lay.zeroed_bytes, st));
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(iwe_avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
+                                p, n_events, frame_event_begin, frame_ts, flow, F, h, w, pl.refs,
+                                (unsigned long long *)im, (unsigned long long *)(im + lay.s),
+                                (unsigned long long *)(im + lay.base), (uint32_t *)(im + lay.count));
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(avgts_stats_partial_kernel, dim3((unsigned)nb, (unsigned)pl.M), dim3(NT), 0, st,
+                       (const int64_t *)im, (const int64_t *)(im + lay.s), (const int64_t *)(im + lay.base),
+                       (const uint32_t *)(im + lay.count), h, w, nb, (StatRow *)workspace);
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(frame_final_kernel<AvgSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
+                       (const StatRow *)workspace, nb, (StatRow *)rows);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int dvsof_iwe_avg_timestamp_render(const void *images, int F, int h, int w, int reference_mask, int polarity,
+                                   uint8_t *canvas, void *stream)
+{
+    Plan pl;
+    if (F < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !images || !canvas) return DVSOF_EINVAL;
+    const AvgtsLayout lay = avgts_layout(h, w, pl);
+    const char *im = (const char *)images;
+    const int step = chunk_rows(h, w), chunks = (h + step - 1) / step;
+    hipLaunchKernelGGL(iwe_avgts_render_kernel, dim3((unsigned)pl.M * kPanels * chunks), dim3(kRenderNT), 0,
+                       as_stream(stream), (const int64_t *)im, (const int64_t *)(im + lay.s),
+                       (const int64_t *)(im + lay.base), (const uint32_t *)(im + lay.count), h, w, step, chunks,
+                       canvas);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }

@@ -12,6 +12,10 @@ Without ground truth: ``iwe_splat``, ``iwe_stats``, ``iwe_render`` and
 ``derive_fwl`` (csrc/iwe.hip, docs/IWE_SPEC.md), the image of warped events
 and its flow warp loss, driven by ``testing.flow_warp_loss``; for host arrays
 they run the numpy float32 restatement ``iwe_*_host`` the kernels are pinned to.
+Beside it ``iwe_avg_timestamp``, ``iwe_avg_timestamp_render`` and
+``derive_rsat`` (IWE_SPEC sections 14-21): the average-timestamp images of the
+same events and the ratio of squared average timestamps, from one splat that
+serves both metrics; ``testing.event_alignment`` drives them.
 """
 import numpy as np
 import torch
@@ -628,3 +632,211 @@ def derive_fwl(res, n_pixels):
         fwl = np.where(var_cnt == 0, np.nan, var_iwe / var_cnt)
         kept = res['sum_q'].astype(np.float64) / (count_sum * 2.0 ** 32)
     return fwl, kept
+
+
+# ---------------------------------------------------------------------------
+# Average-timestamp images of the warped events and their ratio (RSAT),
+# csrc/iwe.hip, docs/IWE_SPEC.md sections 14-21
+# ---------------------------------------------------------------------------
+def _avg_timestamp_row_dtype():
+    from .loss import AVG_TIMESTAMP_ROW_DTYPE      # S, S0, peak, n, n0: the row of the training term
+    assert AVG_TIMESTAMP_ROW_DTYPE.itemsize == 32
+    return AVG_TIMESTAMP_ROW_DTYPE
+
+
+def iwe_avg_timestamp_image_bytes(M, h, w):
+    """The region of include/dvsof_iwe_avg_timestamp.h: q, s, base int64 and count uint32, padded to 8."""
+    return (28 * M * h * w + 7) // 8 * 8
+
+
+def _avg_timestamp_views(buffer, M, h, w):
+    """q, s, base (int64) and count (int32 on the device, uint32 on the host) [M,h,w] as views of the region."""
+    P = M * h * w
+    cut = [buffer[8 * k * P:8 * (k + 1) * P] for k in range(3)] + [buffer[24 * P:28 * P]]
+    if isinstance(buffer, torch.Tensor):
+        return tuple(c.view(torch.long).view(M, h, w) for c in cut[:3]) + (cut[3].view(torch.int32).view(M, h, w),)
+    return tuple(c.view(np.int64).reshape(M, h, w) for c in cut[:3]) + (cut[3].view(np.uint32).reshape(M, h, w),)
+
+
+def iwe_avg_timestamp_host(x, y, t, p, frame_event_begin, frame_ts, flow, references=('start',), polarity=False):
+    """IWE_SPEC sections 14-16 in numpy float32: what ``iwe_avg_timestamp``
+    runs without a GPU and what ``dvsof_iwe_avg_timestamp`` is pinned to, byte
+    for byte.  The arguments of ``iwe_splat_multi_host``: the events of a frame
+    are those of its slots (section 2), what each does to the images is
+    AVG_TIMESTAMP_SPEC section 2 (``loss.avg_timestamp_splat_host``, which the
+    training term's restatement runs).  With M = F R C images -> (q, s, base
+    int64 [M,h,w], count uint32 [M,h,w]), views of one buffer laid out as
+    include/dvsof_iwe_avg_timestamp.h lays the region out."""
+    from .loss import avg_timestamp_splat_host, contrast_reference_mask
+    mask = contrast_reference_mask(references)
+    x, y = np.asarray(x, np.int64).reshape(-1), np.asarray(y, np.int64).reshape(-1)
+    t = np.asarray(t, _F).reshape(-1)
+    begin = np.asarray(frame_event_begin, np.int64).reshape(-1)
+    ts = np.asarray(frame_ts, _F).reshape(-1)
+    flow = np.asarray(flow, _F)
+    F, _, h, w = flow.shape
+    assert begin.size == F + 1 and ts.size == 2 * F and x.size == y.size == t.size
+    e = np.arange(x.size, dtype=np.int64)
+    keep = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+    if F:
+        keep &= (e >= begin[0]) & (e < begin[F])
+    else:
+        keep &= False
+    chan = np.zeros(x.size, np.int64)
+    if polarity:
+        p = np.asarray(p, np.int64).reshape(-1)
+        assert p.size == x.size
+        keep &= p != 0
+        chan = (p < 0).astype(np.int64)
+    e = e[keep]
+    f = np.searchsorted(begin[:F], e, side='right') - 1     # the last f with begin[f] <= e
+    x, y, t = x[keep], y[keep], t[keep]
+    t0 = ts[2 * f]
+    d = ts[2 * f + 1] - t0
+    with np.errstate(all='ignore'):
+        tau = np.where(d > 0, np.fmin(np.fmax((t - t0) / d, _F(0)), _F(1)), _F(0)).astype(_F)
+    pairs = dict(f=f, c=chan[keep], x=x, y=y, tau=tau, u=flow[f, 0, y, x], v=flow[f, 1, y, x])
+    images = avg_timestamp_splat_host(pairs, mask, polarity, F, h, w)
+    M = images[0].shape[0]
+    buffer = np.zeros(iwe_avg_timestamp_image_bytes(M, h, w), np.uint8)
+    views = _avg_timestamp_views(buffer, M, h, w)
+    for view, image in zip(views, images):
+        view[...] = image
+    return views
+
+
+def iwe_avg_timestamp_rows_host(q, s, base, count):
+    """IWE_SPEC section 17 on the host -> the M statistics rows
+    (loss.AVG_TIMESTAMP_ROW_DTYPE: S, S0, peak, n, n0), S and S0 through
+    ``kernel_order_sum``: the bits ``dvsof_iwe_avg_timestamp`` stores, by
+    ``loss.avg_timestamp_rows_host``, which the training term's restatement
+    runs."""
+    from .loss import avg_timestamp_rows_host
+    q, s, base = (np.asarray(_np(a), np.int64) for a in (q, s, base))
+    c = _counts(count)
+    assert q.ndim == 3 and s.shape == base.shape == c.shape == q.shape
+    return avg_timestamp_rows_host(q, s, base, c)
+
+
+def iwe_avg_timestamp(events, win_out, frame_ts, flow, references=('start',), polarity=False):
+    """The average-timestamp images of the warped events of a batch of frames
+    and their statistics (csrc/iwe.hip, IWE_SPEC sections 14-18).  The
+    arguments of ``iwe_splat_multi``.  With M = F R C images ->
+    ((q, s, base int64 [M,h,w], count int32 [M,h,w] holding the uint32
+    counts), rows uint8 [M,32]) on the device, the four images views of one
+    buffer; q and count hold the bytes of ``iwe_splat_multi``, so that
+    ``iwe_stats`` and ``iwe_render`` take them.  For host input the images of
+    ``iwe_avg_timestamp_host`` (count uint32) and the rows of
+    ``iwe_avg_timestamp_rows_host`` as a numpy uint8 [M,32]."""
+    from .loss import contrast_reference_mask
+    mask, polarity = contrast_reference_mask(references), bool(polarity)
+    x, y, t = events['x'], events['y'], events['timestamp']
+    if polarity and events.get('polarity') is None:
+        raise ValueError('polarity=True needs the events\' polarity column')
+    p = events['polarity'] if polarity else None
+    if not _on_device(flow):
+        images = iwe_avg_timestamp_host(_np(x), _np(y), _np(t), None if p is None else _np(p), _np(win_out),
+                                        _np(frame_ts), _np(flow), mask, polarity)
+        rows = iwe_avg_timestamp_rows_host(*images)
+        return images, rows.view(np.uint8).reshape(-1, rows.dtype.itemsize)
+    _lib.require_cuda(x, y, t, p, frame_ts)
+    x, y, t = x.contiguous(), y.contiguous(), t.contiguous()
+    flow, frame_ts = flow.contiguous(), frame_ts.contiguous()
+    assert x.dtype == y.dtype == torch.long and t.dtype == flow.dtype == frame_ts.dtype == torch.float32
+    assert x.numel() == y.numel() == t.numel()
+    if p is not None:
+        p = p.contiguous()
+        assert p.dtype == torch.long and p.numel() == x.numel()
+    begin = torch.as_tensor(win_out, dtype=torch.long).to(flow.device).contiguous()
+    F, two, h, w = flow.shape
+    assert two == 2 and begin.numel() == F + 1 and frame_ts.numel() == 2 * F, \
+        (flow.shape, begin.shape, frame_ts.shape)
+    lib = _lib.lib()
+    M = lib.dvsof_iwe_multi_images(F, mask, int(polarity))
+    if F > 0 and M == 0:
+        raise ValueError(f'{F} frames at {bin(mask).count("1")} reference times'
+                         f'{" and two polarities" if polarity else ""} are more than 65535 images')
+    nbytes = lib.dvsof_iwe_avg_timestamp_image_bytes(F, h, w, mask, int(polarity))
+    assert nbytes == iwe_avg_timestamp_image_bytes(M, h, w), (nbytes, M, h, w)
+    # int64 storage: the region and the rows are 8-byte aligned
+    buffer = torch.empty(nbytes // 8, dtype=torch.long, device=flow.device).view(torch.uint8)
+    rows = torch.empty(M * 4, dtype=torch.long, device=flow.device).view(torch.uint8).view(M, 32)
+    ws_bytes = lib.dvsof_iwe_avg_timestamp_workspace_bytes(F, h, w, mask, int(polarity))
+    ws = torch.empty(max(ws_bytes, 32) // 8, dtype=torch.long, device=flow.device)
+    _lib.check(lib.dvsof_iwe_avg_timestamp(
+        x.data_ptr(), y.data_ptr(), t.data_ptr(), _lib.ptr(p), x.numel(), begin.data_ptr(),
+        frame_ts.data_ptr(), flow.data_ptr(), F, h, w, mask, int(polarity), buffer.data_ptr(), nbytes,
+        rows.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream()), 'dvsof_iwe_avg_timestamp')
+    return _avg_timestamp_views(buffer, M, h, w), rows
+
+
+def read_avg_timestamp_rows(rows):
+    """Rows of ``iwe_avg_timestamp`` -> numpy structured array [M]
+    (loss.AVG_TIMESTAMP_ROW_DTYPE): the one device-to-host copy of a batch."""
+    dtype = _avg_timestamp_row_dtype()
+    a = _np(rows)
+    if a.dtype == dtype:
+        return a.reshape(-1)
+    return np.ascontiguousarray(a).view(dtype).reshape(-1)
+
+
+def iwe_avg_timestamp_render_host(q, s, base, count):
+    """IWE_SPEC section 19 in numpy -> uint8 [M,h,2w,3]: the average distance
+    in time at zero flow T0 on the left, the average distance T after the warp
+    on the right, float64 as the statistics form them, converted once to
+    float32, grey on the fixed scale [0, 1)."""
+    from .loss import avg_timestamp_pixels_host
+    q, s, base = (np.asarray(_np(a), np.int64) for a in (q, s, base))
+    c = _counts(count)
+    M, h, w = q.shape
+    T, _, T0 = avg_timestamp_pixels_host(q, s, base, c)
+    canvas = np.empty((M, h, 2 * w, 3), np.uint8)
+    canvas[:, :, :w] = _grey_host(T0.astype(_F), _F(1))[..., None]
+    canvas[:, :, w:] = _grey_host(T.astype(_F), _F(1))[..., None]
+    return canvas
+
+
+def iwe_avg_timestamp_render(q, s, base, count):
+    """Per image the average distance in time at zero flow beside that after
+    the warp, grey on the fixed scale [0, 1) -> uint8 [M,h,2w,3] on the device;
+    ``iwe_avg_timestamp_render_host`` for host input.  q, s, base, count: the
+    images of ``iwe_avg_timestamp`` or a selection of them (gathered into one
+    region of the layout the kernel reads)."""
+    if not _on_device(q):
+        return iwe_avg_timestamp_render_host(q, s, base, count)
+    _lib.require_cuda(s, base, count)
+    M, h, w = q.shape
+    assert q.dtype == s.dtype == base.dtype == torch.long and count.element_size() == 4
+    assert tuple(s.shape) == tuple(base.shape) == tuple(count.shape) == (M, h, w)
+    nbytes = iwe_avg_timestamp_image_bytes(M, h, w)
+    P = M * h * w
+    contiguous = all(a.is_contiguous() for a in (q, s, base, count)) and \
+        s.data_ptr() == q.data_ptr() + 8 * P and base.data_ptr() == q.data_ptr() + 16 * P and \
+        count.data_ptr() == q.data_ptr() + 24 * P
+    if contiguous:
+        region = q
+    else:
+        region = torch.empty(nbytes // 8, dtype=torch.long, device=q.device).view(torch.uint8)
+        for dst, src in zip(_avg_timestamp_views(region, M, h, w), (q, s, base, count)):
+            dst.copy_(src.view(dst.dtype) if src.dtype != dst.dtype else src)
+    canvas = torch.empty(M, h, 2 * w, 3, dtype=torch.uint8, device=q.device)
+    # the images as M frames of one reference and no polarity: the kernel reads the layout alone
+    _lib.check(_lib.lib().dvsof_iwe_avg_timestamp_render(region.data_ptr(), M, h, w, 1, 0, canvas.data_ptr(),
+                                                          _lib.stream()), 'dvsof_iwe_avg_timestamp_render')
+    return canvas
+
+
+def derive_rsat(rows):
+    """-> RSAT float64 [M] of per-image rows (``read_avg_timestamp_rows``): the
+    ratio of the mean squared average timestamp of the warped events over that
+    at zero flow, (S / n) / (S0 / n0), the per-image value of
+    AVG_TIMESTAMP_SPEC section 1.  NaN where S0 <= 0 (no events, or all of them
+    on the reference: left out of means, as the NaN of ``derive_fwl`` is); 1.0
+    where S0 > 0 and n = 0 (every event left the image: never rewarded)."""
+    rows = read_avg_timestamp_rows(rows)
+    S, S0 = rows['S'].astype(np.float64), rows['S0'].astype(np.float64)
+    n, n0 = rows['n'].astype(np.float64), rows['n0'].astype(np.float64)
+    live, stayed = S0 > 0, rows['n'] > 0
+    with np.errstate(all='ignore'):
+        value = (S / n) / (S0 / n0)
+    return np.where(live, np.where(stayed, value, 1.0), np.nan)

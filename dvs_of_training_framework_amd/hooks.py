@@ -271,10 +271,21 @@ class SharpnessHook:
     anything but the defaults the hook also logs ``Sharpness/mean FWL/<reference>``
     for every chosen reference and, with ``polarity``, ``Sharpness/mean FWL/ON``
     and ``/OFF``; a drawn frame is one picture of its images below one another
-    in image order, and its ``.yml`` lists the statistics per image."""
+    in image order, and its ``.yml`` lists the statistics per image.
+
+    rsat: beside the flow warp loss the ratio of squared average timestamps
+    (``testing.event_alignment``, ``eval.derive_rsat``; docs/IWE_SPEC.md
+    sections 14-21), from one splat for both.  The tags above carry the values
+    they carry without it; the hook adds ``Sharpness/mean RSAT`` (the mean over
+    the images that have one; NaN if none has) and, with anything but the
+    default references and polarity, ``Sharpness/mean RSAT/<reference>``,
+    ``/ON`` and ``/OFF``.  A drawn image row becomes count image | image of
+    warped events | average timestamp at zero flow | average timestamp after
+    the warp, and the ``.yml`` gains ``RSAT``, ``pixels_with_events`` and
+    ``pixels_with_warped_events`` per image.  Off: nothing of it is built."""
 
     def __init__(self, model, sequence, logger, shape, directory, frame_step=1, pictures=4,
-                 rank=0, batch_size=8, references=('start',), polarity=False):
+                 rank=0, batch_size=8, references=('start',), polarity=False, rsat=False):
         from .eval import iwe_image_names
         from .loss import contrast_reference_mask
         self.model, self.sequence, self.logger = model, sequence, logger
@@ -283,6 +294,7 @@ class SharpnessHook:
         self.shape = (int(shape[0]), int(shape[1]))
         self.directory, self.rank = Path(directory), rank
         self.batch_size = int(batch_size)
+        self.rsat = bool(rsat)
         self.frames = self.chosen = ()
         if rank != 0:
             return
@@ -299,23 +311,34 @@ class SharpnessHook:
 
     def evaluate(self):
         """-> (result rows of every image, [(frames, their pictures)]) with the
-        model as it stands; pictures on the device."""
+        model as it stands; pictures on the device.  With ``rsat`` a third
+        entry, the average-timestamp rows of every image."""
         from . import eval as dev_eval, testing
         from .of import OpticalFlow
         of = OpticalFlow.from_model(self.model, self.shape)
         drawn = []
         per = len(self.image_names)
 
-        def observer(first, q, count, results):
+        def draw(first, q, count, results, more=None):
             mine = [i for i in self.chosen if first <= i < first + q.shape[0] // per]
             if not mine:
                 return
             local = torch.tensor([(i - first) * per + k for i in mine for k in range(per)], device=q.device)
             canvas = dev_eval.iwe_render(q[local], count[local], results[local])
+            if more is not None:
+                s, base = more
+                canvas = torch.cat([canvas, dev_eval.iwe_avg_timestamp_render(
+                    q[local], s[local], base[local], count[local])], 2)
             # the images of a frame are contiguous: below one another, one picture
             drawn.append((mine, canvas.view(len(mine), per * canvas.shape[1], *canvas.shape[2:])))
+        if self.rsat:
+            rows, avg_rows = testing.event_alignment(
+                of, self.sequence, self.frames, self.box, self.batch_size,
+                observer=lambda first, images, results, _: draw(first, images[0], images[3], results, images[1:3]),
+                references=self.reference_mask, polarity=self.polarity)
+            return rows, drawn, avg_rows
         rows = testing.flow_warp_loss(of, self.sequence, self.frames, self.box, self.batch_size,
-                                      observer=observer, references=self.reference_mask,
+                                      observer=draw, references=self.reference_mask,
                                       polarity=self.polarity)
         return rows, drawn
 
@@ -326,7 +349,7 @@ class SharpnessHook:
         with model_left_as_found(self.model) as m:
             m.eval()
             with torch.no_grad():
-                rows, drawn = self.evaluate()
+                rows, drawn, *avg_rows = self.evaluate()
         fwl, kept = dev_eval.derive_fwl(rows, self.shape[0] * self.shape[1])
         valid = ~np.isnan(fwl)
         has_events = rows['count_sum'] > 0
@@ -347,10 +370,24 @@ class SharpnessHook:
             for group in groups:
                 pick = np.isin(kind, [k for k, (r, c) in enumerate(names) if group in (r, c)])
                 self.logger.add_scalar(f'Sharpness/mean FWL/{group}', mean_fwl(pick), samples)
+        if self.rsat:
+            avg_rows, = avg_rows
+            rsat = dev_eval.derive_rsat(avg_rows)
+            has_rsat = ~np.isnan(rsat)
+
+            def mean_rsat(pick):
+                return float(rsat[has_rsat & pick].mean()) if (has_rsat & pick).any() else float('nan')
+            self.logger.add_scalar('Sharpness/mean RSAT', mean_rsat(True), samples)
+            if multi:
+                for group in groups:
+                    pick = np.isin(kind, [k for k, (r, c) in enumerate(names) if group in (r, c)])
+                    self.logger.add_scalar(f'Sharpness/mean RSAT/{group}', mean_rsat(pick), samples)
 
         def image_statistics(m):
+            more = {'RSAT': float(rsat[m]), 'pixels_with_events': int(avg_rows['n0'][m]),
+                    'pixels_with_warped_events': int(avg_rows['n'][m])} if self.rsat else {}
             return {'FWL': float(fwl[m]), 'kept_mass': float(kept[m]), 'count_max': int(rows['count_max'][m]),
-                    'iwe_max': float(rows['max_q'][m]) * 2.0 ** -32}
+                    'iwe_max': float(rows['max_q'][m]) * 2.0 ** -32, **more}
         out = self.directory / f'step_{steps}'
         k = 0
         for mine, images in drawn:

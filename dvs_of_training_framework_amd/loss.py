@@ -808,23 +808,15 @@ def _avg_timestamp_pixels(q, s):
     return s.astype(np.float64) * 2.0 ** -32 / den, 1.0 / den
 
 
-def avg_timestamp_fwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flow, references=('start', 'end'),
-                           polarity=False):
-    """AVG_TIMESTAMP_SPEC sections 2-5 on the host: what
-    ``dvsof_avg_timestamp_fwd`` is pinned to, byte for byte.  The arguments of
-    ``contrast_multi_fwd_host``.  With M = F R C images, m = (f R + r) C + c ->
-    dict: q, s, base int64 [M,h,w], count uint32 [M,h,w], rows (M statistics
-    rows, AVG_TIMESTAMP_ROW_DTYPE, the sums in the kernels' order), rec (M
-    records, AVG_TIMESTAMP_REC_DTYPE), image_value float64 [M], unit float64
-    [F], term float32, and mask, R, C."""
+def avg_timestamp_splat_host(pr, mask, polarity, F, h, w):
+    """AVG_TIMESTAMP_SPEC section 2, steps 1-3 (``avgts_splat_event`` of
+    csrc/avg_timestamp_images.h) for the (event, frame) pairs pr that take part
+    (the dict of ``_contrast_multi_pairs``; which pairs those are is the
+    caller's frame rule) -> q, s, base int64 [M,h,w], count uint32 [M,h,w]."""
     from . import eval as ev
-    flow = np.asarray(flow, _F32)
-    F, _, h, w = flow.shape
-    mask = contrast_reference_mask(references)
     rhos, C = _contrast_rhos(mask), 2 if polarity else 1
     R = len(rhos)
     M = F * R * C
-    pr = _contrast_multi_pairs(x, y, t, p, sample_index, frame_ts, frame_sample, flow, polarity)
     q, s, base = (np.zeros((M, h, w), np.int64) for _ in range(3))
     count = np.zeros((M, h, w), np.uint32)
     one = _F32(ev.IWE_ONE)
@@ -845,16 +837,52 @@ def avg_timestamp_fwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flo
                 ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
                 np.add.at(q, (mk[ok], yy[ok], xx[ok]), Q[ok])
                 np.add.at(s, (mk[ok], yy[ok], xx[ok]), QA[ok])
-    # the statistics, in float64 and in the kernels' order
+    return q, s, base, count
+
+
+def avg_timestamp_pixels_host(q, s, base, count):
+    """AVG_TIMESTAMP_SPEC section 3 per pixel, in float64 -> (T, D, T0), each
+    of the images' shape: ``avgts_pixel`` of csrc/avg_timestamp_images.h."""
+    T, D = _avg_timestamp_pixels(q, s)
+    T0 = base.astype(np.float64) * 2.0 ** -32 / (count.astype(np.float64) + AVG_TIMESTAMP_EPS)
+    return T, D, T0
+
+
+def avg_timestamp_rows_host(q, s, base, count):
+    """The statistics rows of M images (AVG_TIMESTAMP_ROW_DTYPE), the sums in
+    the kernels' order (``eval.kernel_order_sum``): the bits
+    ``avgts_stats_partial_kernel`` and the closing reduction store."""
+    from . import eval as ev
+    M, h, w = q.shape
     N, nb = h * w, ev.partial_blocks(h * w)
-    T, D = _avg_timestamp_pixels(q.reshape(M, N), s.reshape(M, N))
-    T0 = base.reshape(M, N).astype(np.float64) * 2.0 ** -32 / (count.reshape(M, N).astype(np.float64)
-                                                              + AVG_TIMESTAMP_EPS)
+    T, D, T0 = avg_timestamp_pixels_host(q.reshape(M, N), s.reshape(M, N), base.reshape(M, N),
+                                         count.reshape(M, N))
     rows = np.zeros(M, AVG_TIMESTAMP_ROW_DTYPE)
     if M:
         rows['S'], rows['S0'] = ev.kernel_order_sum(T * T, nb), ev.kernel_order_sum(T0 * T0, nb)
         rows['peak'] = (2.0 * T * D).max(1)
         rows['n'], rows['n0'] = (q.reshape(M, N) > 0).sum(1), (count.reshape(M, N) > 0).sum(1)
+    return rows
+
+
+def avg_timestamp_fwd_host(x, y, t, p, sample_index, frame_ts, frame_sample, flow, references=('start', 'end'),
+                           polarity=False):
+    """AVG_TIMESTAMP_SPEC sections 2-5 on the host: what
+    ``dvsof_avg_timestamp_fwd`` is pinned to, byte for byte.  The arguments of
+    ``contrast_multi_fwd_host``.  With M = F R C images, m = (f R + r) C + c ->
+    dict: q, s, base int64 [M,h,w], count uint32 [M,h,w], rows (M statistics
+    rows, AVG_TIMESTAMP_ROW_DTYPE, the sums in the kernels' order), rec (M
+    records, AVG_TIMESTAMP_REC_DTYPE), image_value float64 [M], unit float64
+    [F], term float32, and mask, R, C."""
+    flow = np.asarray(flow, _F32)
+    F, _, h, w = flow.shape
+    mask = contrast_reference_mask(references)
+    rhos, C = _contrast_rhos(mask), 2 if polarity else 1
+    R = len(rhos)
+    M = F * R * C
+    pr = _contrast_multi_pairs(x, y, t, p, sample_index, frame_ts, frame_sample, flow, polarity)
+    q, s, base, count = avg_timestamp_splat_host(pr, mask, polarity, F, h, w)
+    rows = avg_timestamp_rows_host(q, s, base, count)
     # the closing wave
     rec = np.zeros(M, AVG_TIMESTAMP_REC_DTYPE)
     for k_ in ('S', 'S0', 'n', 'n0', 'peak'):

@@ -299,6 +299,15 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                         help='accumulate ON and OFF events in images of their own in the '
                              'sharpness measurement, and log Sharpness/mean FWL/ON and /OFF.  '
                              'Needs --sharpness-period')
+    parser.add_argument('--sharpness-rsat', dest='sharpness_rsat',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='beside the flow warp loss, log Sharpness/mean RSAT (ratio of the '
+                             'squared average timestamps of the warped events over those at '
+                             'zero flow: 1 at zero flow, below 1 where the flow aligns the '
+                             'events of an edge, never below 0, so a collapsing flow is not '
+                             'rewarded as it is by the FWL), from one splat for both, and draw '
+                             'the average-timestamp images beside the two the pictures have '
+                             '(docs/IWE_SPEC.md section 14).  Needs --sharpness-period')
     parser.add_argument('--contrast-weight', dest='contrast_weight', default=0.0,
                         type=float,
                         help='add this times the contrast-maximisation term to the '
@@ -586,6 +595,8 @@ def validate_sharpness_args(args):
             raise SystemExit('--sharpness-references needs a positive --sharpness-period')
         if args.sharpness_polarity:
             raise SystemExit('--sharpness-polarity needs a positive --sharpness-period')
+        if getattr(args, 'sharpness_rsat', False):
+            raise SystemExit('--sharpness-rsat needs a positive --sharpness-period')
     return args
 
 

@@ -300,31 +300,10 @@ def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None, 
     m = (f R + r) C + c (``eval.iwe_image_names``); the observer gets the
     tensors of the batch's images."""
     from .loss import contrast_reference_mask
-    from .sequence import EventSequence, check_box
     mask, polarity = contrast_reference_mask(references), bool(polarity)
     multi = mask != 1 or polarity
-    if not isinstance(sequence, EventSequence):
-        raise TypeError('flow_warp_loss takes a sequence.EventSequence (the events stay on '
-                        f'the device), not {type(sequence).__name__}')
-    if not hasattr(of, 'flow_sequence'):
-        raise TypeError('flow_warp_loss needs an `of` with flow_sequence (OpticalFlow)')
-    if box is not None:
-        box = check_box(box, sequence.shape)
-    frames = np.array(frames, dtype=np.float64)
-    if frames.size == 0:
-        return np.zeros(0, dev_eval.IWE_RESULT_DTYPE)
-    frames = frames.reshape(-1, 2)
-    batch_size = max(int(batch_size), 1)
     out = []
-    for b0 in range(0, len(frames), batch_size):
-        fr = frames[b0:b0 + batch_size]
-        pred, collated = of.flow_sequence(sequence, list(fr[:, 0]), list(fr[:, 1]), box=box,
-                                          return_events=True)
-        pred = pred.to(torch.float32).contiguous()
-        h, w = pred.shape[-2:]
-        eh, ew = box[2:] if box is not None else sequence.shape
-        if (eh, ew) != (h, w):
-            raise ValueError(f'the flow is {(h, w)}, the events cover {(eh, ew)}')
+    for b0, pred, collated, (h, w) in _warped_event_batches('flow_warp_loss', of, sequence, frames, box, batch_size):
         ev = collated.events
         if multi:
             q, count = dev_eval.iwe_splat_multi(ev, collated.win_out, collated.timestamps, pred, mask, polarity)
@@ -336,7 +315,69 @@ def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None, 
         out.append(dev_eval.read_iwe_results(res))      # the batch's one copy back
         if observer is not None:
             observer(b0, q, count, res)
-    return np.concatenate(out)
+    return np.concatenate(out) if out else np.zeros(0, dev_eval.IWE_RESULT_DTYPE)
+
+
+def event_alignment(of, sequence, frames, box=None, batch_size=8, observer=None, references=('start',),
+                    polarity=False):
+    """``flow_warp_loss`` and, from the same splat, the statistics of the
+    average-timestamp images of the warped events (docs/IWE_SPEC.md sections
+    14-21) -> (IWE rows, average-timestamp rows): numpy structured arrays
+    (eval.IWE_RESULT_DTYPE, loss.AVG_TIMESTAMP_ROW_DTYPE) with R C rows per
+    frame, in image order; ``eval.derive_fwl`` and ``eval.derive_rsat`` make
+    the two metrics of them.  The IWE rows are those of ``flow_warp_loss`` with
+    the same arguments, bit for bit.  Per batch of frames: one
+    ``of.flow_sequence``, one ``eval.iwe_avg_timestamp`` (in place of the count
+    image and the splat), one ``eval.iwe_stats`` on its q and count, and two
+    copies back, of 48 and of 32 bytes per image.
+
+    The arguments of ``flow_warp_loss``;
+    observer(first, images, iwe_results, avg_rows): called once per batch with
+    the index of its first frame and the device tensors, images = (q, s, base,
+    count)."""
+    from .loss import AVG_TIMESTAMP_ROW_DTYPE, contrast_reference_mask
+    mask, polarity = contrast_reference_mask(references), bool(polarity)
+    iwe, avg = [], []
+    for b0, pred, collated, _ in _warped_event_batches('event_alignment', of, sequence, frames, box, batch_size):
+        images, rows = dev_eval.iwe_avg_timestamp(collated.events, collated.win_out, collated.timestamps, pred,
+                                                  mask, polarity)
+        res = dev_eval.iwe_stats(images[0], images[3])
+        iwe.append(dev_eval.read_iwe_results(res))          # the batch's two copies back
+        avg.append(dev_eval.read_avg_timestamp_rows(rows))
+        if observer is not None:
+            observer(b0, images, res, rows)
+    if not iwe:
+        return np.zeros(0, dev_eval.IWE_RESULT_DTYPE), np.zeros(0, AVG_TIMESTAMP_ROW_DTYPE)
+    return np.concatenate(iwe), np.concatenate(avg)
+
+
+def _warped_event_batches(name, of, sequence, frames, box, batch_size):
+    """The batch loop ``flow_warp_loss`` and ``event_alignment`` share: yields
+    (index of the batch's first frame, pred float32 [F,2,h,w], the collated
+    events, (h, w)) after one ``of.flow_sequence`` per batch of frames."""
+    from .sequence import EventSequence, check_box
+    if not isinstance(sequence, EventSequence):
+        raise TypeError(f'{name} takes a sequence.EventSequence (the events stay on '
+                        f'the device), not {type(sequence).__name__}')
+    if not hasattr(of, 'flow_sequence'):
+        raise TypeError(f'{name} needs an `of` with flow_sequence (OpticalFlow)')
+    if box is not None:
+        box = check_box(box, sequence.shape)
+    frames = np.array(frames, dtype=np.float64)
+    if frames.size == 0:
+        return
+    frames = frames.reshape(-1, 2)
+    batch_size = max(int(batch_size), 1)
+    for b0 in range(0, len(frames), batch_size):
+        fr = frames[b0:b0 + batch_size]
+        pred, collated = of.flow_sequence(sequence, list(fr[:, 0]), list(fr[:, 1]), box=box,
+                                          return_events=True)
+        pred = pred.to(torch.float32).contiguous()
+        h, w = pred.shape[-2:]
+        eh, ew = box[2:] if box is not None else sequence.shape
+        if (eh, ew) != (h, w):
+            raise ValueError(f'the flow is {(h, w)}, the events cover {(eh, ew)}')
+        yield b0, pred, collated, (h, w)
 
 
 def summarize(rows):

@@ -358,7 +358,8 @@ def add_evaluation(args, hooks, periodic, model, device, logger, rank):
 def add_sharpness(args, hooks, periodic, model, device, logger, rank):
     """--sharpness-period N > 0: a ``SharpnessHook`` every N optimizer steps
     (flow warp loss of the validation sequence's own events, and pictures; no
-    ground truth) at --sharpness-references, with --sharpness-polarity.  0
+    ground truth) at --sharpness-references, with --sharpness-polarity, and
+    with --sharpness-rsat the ratio of squared average timestamps beside it.  0
     constructs nothing.  Rank 0 alone holds the sequence,
     and shares the one an ``EvaluationHook`` has already uploaded.  With
     --validation-recording the sequence is a ``WindowedEvents``: the hook needs
@@ -382,7 +383,8 @@ def add_sharpness(args, hooks, periodic, model, device, logger, rank):
         model, sequence, logger, args.shape, args.model / 'sharpness',
         frame_step=args.sharpness_frame_step, pictures=args.sharpness_pictures, rank=rank,
         references=getattr(args, 'sharpness_references', ('start',)),
-        polarity=getattr(args, 'sharpness_polarity', False))
+        polarity=getattr(args, 'sharpness_polarity', False),
+        **({'rsat': True} if getattr(args, 'sharpness_rsat', False) else {}))
     periodic['sharpness'] = make_hook_periodic(hooks['sharpness'], args.sharpness_period)
 
 
