@@ -84,10 +84,14 @@ struct Exec {
     std::vector<hipStream_t> side;   // lanes 1.. (lane 0 is the stream of the launch call)
     hipEvent_t fork = nullptr;
     std::vector<hipEvent_t> join;    // per side lane
+    std::vector<char> join_needed;   // ... and whether the launch has to end with it (rewire)
     int n_kernels = 0, n_marks = 0;
     void *comm = nullptr;            // dvsof_comm_create handle (not owned)
     hipStream_t xstream = nullptr;   // exchange stream (not owned)
     hipEvent_t xdone = nullptr;      // exchange stream's progress at a JOIN mark
+    std::vector<int> pending;        // BUCKET marks met whose collectives are still to be issued (issue_pending)
+    hipStream_t pending_st = nullptr;    // ... and the lane that closed them
+    bool dry = false;                // a dry pass (walk): no-op kernels for kernels and collectives
     hipStream_t ustream = nullptr;   // UPDATE stream: lane of the update nodes (own stream: on the exchange
                                      // stream the updates would sit between the collectives -- under the
                                      // loopback exchange that stream is the step's longest chain)
@@ -107,6 +111,15 @@ int rewire(Exec *x)
         DVSOF_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         x->join.push_back(e);
     }
+    // `stream` continues behind every lane.  Where a node of lane 0 already waits for the LAST
+    // node of a lane (the optimizer behind the last weight gradient), it does: no join for it.
+    x->join_needed.assign(std::max(x->w.n_lanes - 1, 0), 1);
+    std::vector<int> last(x->w.n_lanes, -1);
+    for (int id : x->plan.order) last[x->w.lane[id]] = id;
+    for (int id : x->plan.order)
+        if (x->w.lane[id] == 0)
+            for (int d : x->w.wait[id])
+                if (x->w.lane[d] > 0 && last[x->w.lane[d]] == d) x->join_needed[x->w.lane[d] - 1] = 0;
     return DVSOF_OK;
 }
 
@@ -146,23 +159,61 @@ int launch_node(const XNode &n, hipStream_t st)
     return DVSOF_OK;
 }
 
+// A wait of one stream for another costs the host as much as six launches (two barrier packets
+// of the runtime), so the exchange stream waits once for every MARK_GROUP buckets: a bucket's
+// collective is issued when the next bucket of its lane closes -- at most one weight gradient
+// later -- or at the next WAIT / JOIN mark, whichever comes first; always in capture order.  The
+// kernels launched in between belong to the windows of the buckets held back (exec_sched.h), so
+// they run beside the collectives as they did.
+constexpr int MARK_GROUP = 2;
+#ifndef DVSOF_EXEC_DRY_PASSES
+#define DVSOF_EXEC_DRY_PASSES 12  // walks of the wiring at the end of a calibration under an exchange
+#endif
+
+int noop(hipStream_t st)
+{
+    hipLaunchKernelGGL(exec_mark_kernel, dim3(1), dim3(1), 0, st, 0, 0, (float *)nullptr, (size_t)0);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+int issue_pending(Exec *x)
+{
+    if (x->pending.empty()) return DVSOF_OK;
+    const std::vector<int> ids = std::move(x->pending);
+    x->pending.clear();
+    hipStream_t st = x->pending_st, xs = x->xstream ? x->xstream : st;
+    if (xs != st) {
+        const XNode &last = x->nodes[ids.back()];
+        DVSOF_HIP_TRY(hipEventRecord(last.mark_ev, st));
+        DVSOF_HIP_TRY(hipStreamWaitEvent(xs, last.mark_ev, 0));
+    }
+    for (int id : ids) {
+        const XNode &n = x->nodes[id];
+        const int rc = x->dry ? noop(xs) : dvsof_allreduce_bucket(x->comm, n.mark_ptr, n.mark_n, (void *)xs);
+        if (rc) return rc;
+        if (xs != st && x->w.xdone_used[id]) DVSOF_HIP_TRY(hipEventRecord(n.xdone_ev, xs));
+    }
+    return DVSOF_OK;
+}
+
 // The mark `id` at its place in the launch order, on the stream `st` of its lane.
 int run_mark(Exec *x, int id, hipStream_t st)
 {
     if (!x->comm) return DVSOF_OK;   // one GPU: nothing to exchange
-    const XNode &n = x->nodes[id];
     const int kind = x->s.nodes[id].kind;
     hipStream_t xs = x->xstream ? x->xstream : st;
     if (kind == BUCKET) {
-        if (xs != st) {
-            DVSOF_HIP_TRY(hipEventRecord(n.mark_ev, st));
-            DVSOF_HIP_TRY(hipStreamWaitEvent(xs, n.mark_ev, 0));
+        if (!x->pending.empty() && x->pending_st != st) {
+            const int rc = issue_pending(x);
+            if (rc) return rc;
         }
-        const int rc = dvsof_allreduce_bucket(x->comm, n.mark_ptr, n.mark_n, (void *)xs);
-        if (rc) return rc;
-        if (xs != st && x->w.xdone_used[id]) DVSOF_HIP_TRY(hipEventRecord(n.xdone_ev, xs));
-        return DVSOF_OK;
+        x->pending.push_back(id);
+        x->pending_st = st;
+        return (int)x->pending.size() >= MARK_GROUP ? issue_pending(x) : DVSOF_OK;
     }
+    const int rc = issue_pending(x);    // a WAIT / JOIN mark follows the collectives it waits for
+    if (rc) return rc;
     if (kind == WAIT) {
         const int b = x->w.wait_for[id];
         if (xs != st && b >= 0) DVSOF_HIP_TRY(hipStreamWaitEvent(st, x->nodes[b].xdone_ev, 0));
@@ -171,6 +222,40 @@ int run_mark(Exec *x, int id, hipStream_t st)
     if (kind == JOIN && xs != st) {
         DVSOF_HIP_TRY(hipEventRecord(x->xdone, xs));
         DVSOF_HIP_TRY(hipStreamWaitEvent(st, x->xdone, 0));
+    }
+    return DVSOF_OK;
+}
+
+// One step in the plan in effect on `main` and the lanes' streams.  dry: a no-op kernel in place
+// of every kernel and collective -- every event recorded, every cross-stream wait issued, nothing
+// computed (dvsof_exec_calibrate).
+int walk(Exec *x, hipStream_t main, bool dry)
+{
+    x->dry = dry;
+    x->pending.clear();     // (of a launch that ended in an error)
+    const int L = x->w.n_lanes;
+    auto lane_stream = [&](int l) { return l == 0 ? main : l <= (int)x->side.size() ? x->side[l - 1] : x->ustream; };
+    if (L > 1) {   // the side lanes start behind whatever precedes the step on `stream`
+        DVSOF_HIP_TRY(hipEventRecord(x->fork, main));
+        for (int l = 1; l < L; ++l) DVSOF_HIP_TRY(hipStreamWaitEvent(lane_stream(l), x->fork, 0));
+    }
+    for (int id : x->plan.order) {
+        const XNode &n = x->nodes[id];
+        const int kind = x->s.nodes[id].kind;
+        hipStream_t st = lane_stream(x->w.lane[id]);
+        for (int d : x->w.wait[id]) DVSOF_HIP_TRY(hipStreamWaitEvent(st, x->nodes[d].ev, 0));
+        const int rc_ = kind == KERNEL ? (dry ? noop(st) : launch_node(n, st)) : is_mark(kind) ? run_mark(x, id, st) : DVSOF_OK;
+        if (rc_) return rc_;
+        if (x->w.need_event[id]) DVSOF_HIP_TRY(hipEventRecord(n.ev, st));
+    }
+    {   // (a capture without a JOIN mark behind its last bucket)
+        const int rc_ = issue_pending(x);
+        if (rc_) return rc_;
+    }
+    for (int l = 1; l < L; ++l) {   // `stream` continues behind every lane
+        if (!x->join_needed[l - 1]) continue;
+        DVSOF_HIP_TRY(hipEventRecord(x->join[l - 1], lane_stream(l)));
+        DVSOF_HIP_TRY(hipStreamWaitEvent(main, x->join[l - 1], 0));
     }
     return DVSOF_OK;
 }
@@ -404,7 +489,20 @@ int dvsof_exec_calibrate(void *exec, void *stream)
     // measure the other ranks' arrival at the collectives as much as this rank's kernels, ranks
     // could settle on different plans, and the trial steps themselves (host waits for a step's
     // end) are one more place where ranks wait for each other.
-    if (x->comm) return use(x, plan_chain(x->s));
+    if (x->comm) {
+        // The runtime's launch and cross-stream paths cost the host up to twice as much while they
+        // are new to a process (18-24 against 10-14 us per wait) and get cheaper over the first
+        // few hundred uses: the timed host cost of the next replays fell from 0.79 ms after 4 dry
+        // walks to 0.63 ms after 12 (f32, ~20 waits and ~100 launches a walk).  Without an
+        // exchange the plan trials take that up; here there are none, so this pass -- which
+        // waits for the device anyway -- walks the wiring dry.  It serves the first replays
+        // only: a long run gains nothing.
+        int rc_ = use(x, plan_chain(x->s));
+        for (int k = 0; k < DVSOF_EXEC_DRY_PASSES && !rc_; ++k) rc_ = walk(x, st, true);
+        if (rc_) return rc_;
+        DVSOF_HIP_TRY(hipStreamSynchronize(st));
+        return DVSOF_OK;
+    }
     x->cands = {plan_paths(x->s), plan_list(x->s, hop), plan_chain(x->s)};
     x->best_us.assign(x->cands.size(), 3.0e38f);
     if (!x->t0) DVSOF_HIP_TRY(hipEventCreate(&x->t0));
@@ -442,26 +540,9 @@ int dvsof_exec_launch(void *exec, void *stream)
         const int rc_ = next_trial(x);
         if (rc_) return rc_;
     }
-    const int L = x->w.n_lanes;
-    auto lane_stream = [&](int l) { return l == 0 ? main : l <= (int)x->side.size() ? x->side[l - 1] : x->ustream; };
     if (x->trial_cur >= 0) DVSOF_HIP_TRY(hipEventRecord(x->t0, main));
-    if (L > 1) {   // the side lanes start behind whatever precedes the step on `stream`
-        DVSOF_HIP_TRY(hipEventRecord(x->fork, main));
-        for (int l = 1; l < L; ++l) DVSOF_HIP_TRY(hipStreamWaitEvent(lane_stream(l), x->fork, 0));
-    }
-    for (int id : x->plan.order) {
-        const XNode &n = x->nodes[id];
-        const int kind = x->s.nodes[id].kind;
-        hipStream_t st = lane_stream(x->w.lane[id]);
-        for (int d : x->w.wait[id]) DVSOF_HIP_TRY(hipStreamWaitEvent(st, x->nodes[d].ev, 0));
-        const int rc_ = kind == KERNEL ? launch_node(n, st) : is_mark(kind) ? run_mark(x, id, st) : DVSOF_OK;
-        if (rc_) return rc_;
-        if (x->w.need_event[id]) DVSOF_HIP_TRY(hipEventRecord(n.ev, st));
-    }
-    for (int l = 1; l < L; ++l) {   // `stream` continues behind every lane
-        DVSOF_HIP_TRY(hipEventRecord(x->join[l - 1], lane_stream(l)));
-        DVSOF_HIP_TRY(hipStreamWaitEvent(main, x->join[l - 1], 0));
-    }
+    const int rc = walk(x, main, false);
+    if (rc) return rc;
     if (x->trial_cur >= 0) DVSOF_HIP_TRY(hipEventRecord(x->t1, main));
     return DVSOF_OK;
 }
