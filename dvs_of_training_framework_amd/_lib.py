@@ -20,7 +20,9 @@ tests/golden/abi_signatures_avg_timestamp_pyramid.json;
 _abi.EVENT_TERMS_ENCODED_PATH: include/dvsof_event_terms_encoded.h, recorded in
 tests/golden/abi_signatures_event_terms_encoded.json;
 _abi.IWE_AVG_TIMESTAMP_PATH: include/dvsof_iwe_avg_timestamp.h, recorded in
-tests/golden/abi_signatures_iwe_avg_timestamp.json).
+tests/golden/abi_signatures_iwe_avg_timestamp.json;
+_abi.EVENT_IMAGES_TILED_PATH: include/dvsof_event_images_tiled.h, recorded in
+tests/golden/abi_signatures_event_images_tiled.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -63,6 +65,8 @@ _AVG_TIMESTAMP_PYRAMID_SIGNATURES = _abi.AVG_TIMESTAMP_PYRAMID_FUNCTIONS
 _EVENT_TERMS_ENCODED_SIGNATURES = _abi.EVENT_TERMS_ENCODED_FUNCTIONS
 # and of include/dvsof_iwe_avg_timestamp.h, the average-timestamp images of the validation metric
 _IWE_AVG_TIMESTAMP_SIGNATURES = _abi.IWE_AVG_TIMESTAMP_FUNCTIONS
+# and of include/dvsof_event_images_tiled.h, the tiled schedule of the splat into the images of warped events
+_EVENT_IMAGES_TILED_SIGNATURES = _abi.EVENT_IMAGES_TILED_FUNCTIONS
 
 _lib = None
 LOADED_STAT = None
@@ -128,6 +132,11 @@ def declared_iwe_avg_timestamp_symbols():
     return _declared_in((_abi.IWE_AVG_TIMESTAMP_PATH,))
 
 
+def declared_event_images_tiled_symbols():
+    """Names of all entry points include/dvsof_event_images_tiled.h declares."""
+    return _declared_in((_abi.EVENT_IMAGES_TILED_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -146,7 +155,8 @@ def lib():
                                   **_CONTRAST_PYRAMID_SIGNATURES, **_AVG_TIMESTAMP_SIGNATURES,
                                   **_AVG_TIMESTAMP_PYRAMID_SIGNATURES,
                                   **_EVENT_TERMS_ENCODED_SIGNATURES,
-                                  **_IWE_AVG_TIMESTAMP_SIGNATURES}.items():
+                                  **_IWE_AVG_TIMESTAMP_SIGNATURES,
+                                  **_EVENT_IMAGES_TILED_SIGNATURES}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -27,10 +27,12 @@
 // splat, one closing wave and one backward for all levels (sections 19-23,
 // include/dvsof_contrast_pyramid.h); the kernels above are not touched by it.
 #include "event_columns.h"
+#include "event_images_tiled.h"
 #include "../../include/dvsof_contrast.h"
 #include "../../include/dvsof_contrast_multi.h"
 #include "../../include/dvsof_contrast_pyramid.h"
 #include "../../include/dvsof_event_terms_encoded.h"
+#include "../../include/dvsof_event_images_tiled.h"
 
 namespace {
 
@@ -244,11 +246,23 @@ size_t multi_workspace_bytes(int F, int reference_mask, int polarity, int h, int
            dvsof_iwe_stats_workspace_bytes(pl.M, h, w);
 }
 
+// the columns as the tiled splat's launcher takes them (event_images_tiled.h)
+TiledTermColumns plain(const WireColumns &c) { return TiledTermColumns{0, c.x, c.y, c.t, c.pol, c.sample, 0}; }
+TiledTermColumns plain(const EncodedColumns &c) { return TiledTermColumns{1, c.x, c.y, c.t, c.pol, c.ev_off, c.B}; }
+
+// the tiled twins' three arguments; mode < 0: the calls that have none
+struct TiledSplat {
+    void *workspace;
+    size_t bytes;
+    int mode;
+};
+
 // dvsof_contrast_multi_fwd / _bwd on either form of the event columns (event_columns.h)
 template <class Cols>
 int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
               const float *flow, int F, int h, int w, int reference_mask, int polarity, int64_t *q, uint32_t *count,
-              dvsof_iwe_result_t *result, float *term, void *workspace, size_t workspace_bytes, void *stream)
+              dvsof_iwe_result_t *result, float *term, void *workspace, size_t workspace_bytes, void *stream,
+              const TiledSplat tiled = TiledSplat{nullptr, 0, -1})
 {
     Plan pl;
     if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
@@ -258,13 +272,21 @@ int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const i
     if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
     if (!workspace || workspace_bytes < multi_workspace_bytes(F, reference_mask, polarity, h, w))
         return DVSOF_ENOSPACE;
+    TilePlan tp;
+    const int by_tiles = tiled.mode < 0 ? 1 : tile_decide(tiled.mode, F, reference_mask, polarity, h, w, n_events,
+                                                          tiled.workspace, tiled.bytes, tp);
+    if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
     hipStream_t st = as_stream(stream);
     const size_t pixels = (size_t)pl.M * h * w;
     const Workspace ws = carve(workspace, F, h, w, pl);
     DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
     DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws.sums, 0u, sums_bytes(F, h, w), st));
-    if (n_events > 0) {
+    if (by_tiles == DVSOF_OK) {
+        const int rs = event_images_tiled_term_splat(plain(cols), n_events, frame_ts, frame_sample, flow, F, h, w,
+                                                     reference_mask, polarity, tp, q, count, tiled.workspace, st);
+        if (rs != DVSOF_OK) return rs;
+    } else if (n_events > 0) {
         DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
                                 n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, (unsigned long long *)q,
                                 count);
@@ -361,6 +383,35 @@ int dvsof_contrast_multi_bwd_encoded(const int16_t *x, const int16_t *y, const f
     return multi_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
                      flow, F, h, w, reference_mask, polarity_channels, q, workspace, workspace_bytes, seed, weight,
                      grad_flow, stream);
+}
+
+// The tiled twins (include/dvsof_event_images_tiled.h): the forward above with the splat by tiles
+int dvsof_contrast_multi_fwd_tiled(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                   const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                   const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                                   int reference_mask, int polarity, int64_t *q, uint32_t *count,
+                                   dvsof_iwe_result_t *result, float *term, void *workspace, size_t workspace_bytes,
+                                   void *stream, void *tile_workspace, size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return multi_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                     reference_mask, polarity, q, count, result, term, workspace, workspace_bytes, stream,
+                     TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+}
+
+int dvsof_contrast_multi_fwd_encoded_tiled(const int16_t *x, const int16_t *y, const float *t,
+                                           const uint8_t *polarity, const int64_t *sample_event_offsets, int B,
+                                           int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+                                           const float *flow, int F, int h, int w, int reference_mask,
+                                           int polarity_channels, int64_t *q, uint32_t *count,
+                                           dvsof_iwe_result_t *result, float *term, void *workspace,
+                                           size_t workspace_bytes, void *stream, void *tile_workspace,
+                                           size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return multi_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                     flow, F, h, w, reference_mask, polarity_channels, q, count, result, term, workspace,
+                     workspace_bytes, stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
 }
 
 // The term as it was before the references and the polarities: one image per frame, of all its

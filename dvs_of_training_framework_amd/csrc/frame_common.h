@@ -157,6 +157,20 @@ __device__ __forceinline__ float event_tau(float te, float t0, float t1)
     return d > 0.f ? fminf(fmaxf((te - t0) / d, 0.f), 1.f) : 0.f;
 }
 
+// Step 6: the weights of the 2x2 footprint from the fractions fx = xw - floor(xw),
+// fy = yw - floor(yw).  fx and fy are wx[1] and wy[1], so a schedule that keeps
+// their bits (event_images_tiled.hip) gets the four weights back bit for bit.
+__device__ __forceinline__ void corner_weights(float fx, float fy, float (&wx)[2], float (&wy)[2])
+{
+    wx[0] = 1.f - fx;
+    wx[1] = fx;
+    wy[0] = 1.f - fy;
+    wy[1] = fy;
+}
+
+// Step 7: what one corner adds, in units of 2^-32; truncates; 0 <= Q <= 2^32
+__device__ __forceinline__ int64_t corner_units(float wy, float wx) { return (int64_t)(wy * wx * kOne); }
+
 // Steps 2-6 for an event that takes part in a frame, carried to the reference
 // time rho in [0, 1] of the window (docs/CONTRAST_SPEC.md section 11) over
 // sig = tau - rho; rho = 0 is the start of the window of IWE_SPEC section 2,
@@ -172,11 +186,7 @@ __device__ __forceinline__ bool warp_event_to(float tau, float rho, float u, flo
     // in float, before any conversion: false for a NaN, an infinity, 1e30
     if (!(xw > -1.f && xw < (float)w && yw > -1.f && yw < (float)h)) return false;
     const float flx = floorf(xw), fly = floorf(yw);  // in [-1, side - 1]
-    const float fx = xw - flx, fy = yw - fly;
-    o.wx[0] = 1.f - fx;
-    o.wx[1] = fx;
-    o.wy[0] = 1.f - fy;
-    o.wy[1] = fy;
+    corner_weights(xw - flx, yw - fly, o.wx, o.wy);
     o.cx = (int)flx;
     o.cy = (int)fly;
     return true;
@@ -191,7 +201,7 @@ __device__ __forceinline__ void splat_corners(const Warp &p, int h, int w, unsig
         for (int i = 0; i < 2; ++i) {
             const int xx = p.cx + i, yy = p.cy + j;
             if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
-            const int64_t Q = (int64_t)(p.wy[j] * p.wx[i] * kOne);  // truncates; 0 <= Q <= 2^32
+            const int64_t Q = corner_units(p.wy[j], p.wx[i]);
             if (Q > 0) atomicAdd(img + (size_t)yy * w + (size_t)xx, (unsigned long long)Q);
         }
     }

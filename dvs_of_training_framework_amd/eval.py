@@ -526,7 +526,28 @@ def iwe_splat(events, win_out, frame_ts, flow):
     return q
 
 
-def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), polarity=False):
+def event_images_tiled_mode(tiled):
+    """The ``mode`` of include/dvsof_event_images_tiled.h for a ``tiled``
+    keyword: True -> 0 (the entry point decides by the measured event count),
+    'force' -> 1 (tiled wherever the plan applies: tests and benchmarks)."""
+    if tiled is True:
+        return 0
+    if tiled == 'force':
+        return 1
+    raise ValueError(f'tiled is False, True or \'force\', got {tiled!r}')
+
+
+def event_images_tiled_workspace(F, mask, polarity, h, w, n_events, device):
+    """-> (tensor or None, bytes): the tile workspace of a tiled call with
+    these arguments; (None, 0) where the plan is refused and the call runs the
+    kernel of its twin."""
+    nbytes = _lib.lib().dvsof_event_images_tiled_workspace_bytes(F, mask, int(polarity), h, w, n_events)
+    if not nbytes:
+        return None, 0
+    return torch.empty((nbytes + 7) // 8, dtype=torch.long, device=device), nbytes
+
+
+def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), polarity=False, tiled=False):
     """``iwe_splat`` at several reference times of the window and with ON and
     OFF events apart (csrc/iwe.hip, IWE_SPEC sections 8-13).  events,
     win_out, frame_ts, flow as ``iwe_splat`` takes them, and the column
@@ -535,7 +556,12 @@ def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), pola
     m = (f R + r) C + c -> (q int64 [M,h,w] in units of 2^-32, count int32
     [M,h,w] holding the uint32 counts of the image's channel) on the device;
     ``iwe_splat_multi_host`` (numpy arrays, count uint32) for host input.
-    ``iwe_stats`` and ``iwe_render`` take them as M frames."""
+    ``iwe_stats`` and ``iwe_render`` take them as M frames.
+
+    tiled: True or 'force' (``event_images_tiled_mode``) runs
+    ``dvsof_iwe_splat_multi_tiled``, the same images and the same bytes by the
+    tiled schedule for dense frames (IWE_SPEC section 22); False, the default,
+    makes the call above and constructs nothing else."""
     from .loss import contrast_reference_mask
     mask, polarity = contrast_reference_mask(references), bool(polarity)
     x, y, t = events['x'], events['y'], events['timestamp']
@@ -564,10 +590,16 @@ def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), pola
                          f'{" and two polarities" if polarity else ""} are more than 65535 images')
     q = torch.empty(M, h, w, dtype=torch.long, device=flow.device)
     count = torch.empty(M, h, w, dtype=torch.int32, device=flow.device)
-    _lib.check(lib.dvsof_iwe_splat_multi(
-        x.data_ptr(), y.data_ptr(), t.data_ptr(), _lib.ptr(p), x.numel(), begin.data_ptr(),
-        frame_ts.data_ptr(), flow.data_ptr(), F, h, w, mask, int(polarity), q.data_ptr(), count.data_ptr(),
-        _lib.stream()), 'dvsof_iwe_splat_multi')
+    args = (x.data_ptr(), y.data_ptr(), t.data_ptr(), _lib.ptr(p), x.numel(), begin.data_ptr(),
+            frame_ts.data_ptr(), flow.data_ptr(), F, h, w, mask, int(polarity), q.data_ptr(), count.data_ptr(),
+            _lib.stream())
+    if tiled:
+        mode = event_images_tiled_mode(tiled)
+        ws, nbytes = event_images_tiled_workspace(F, mask, polarity, h, w, x.numel(), flow.device)
+        _lib.check(lib.dvsof_iwe_splat_multi_tiled(*args, _lib.ptr(ws), nbytes, mode),
+                   'dvsof_iwe_splat_multi_tiled')
+        return q, count
+    _lib.check(lib.dvsof_iwe_splat_multi(*args), 'dvsof_iwe_splat_multi')
     return q, count
 
 

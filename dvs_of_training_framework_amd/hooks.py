@@ -87,8 +87,9 @@ class ValidationHook:
 
     def __init__(self, model, device, loader, logger, losses, weights, is_raw,
                  contrast_weight=0.0, contrast_references=('start',), contrast_polarity=False,
-                 contrast_scales='finest', avg_timestamp_scales='finest', avg_timestamp_weight=0.0,
-                 avg_timestamp_references=('start', 'end'), avg_timestamp_polarity=False):
+                 contrast_scales='finest', avg_timestamp_scales='finest', contrast_tiled=False,
+                 avg_timestamp_weight=0.0, avg_timestamp_references=('start', 'end'),
+                 avg_timestamp_polarity=False):
         self.model, self.device, self.loader = model, device, loader
         self.logger, self.losses = logger, losses
         self.weights = deepcopy(weights)
@@ -97,6 +98,8 @@ class ValidationHook:
                       'contrast_polarity': bool(contrast_polarity)} if contrast_weight else {}
         if contrast_weight and contrast_scales != 'finest':
             self.extra['contrast_scales'] = contrast_scales
+        if contrast_weight and contrast_tiled:
+            self.extra['contrast_tiled'] = contrast_tiled
         if avg_timestamp_weight:
             self.extra.update(avg_timestamp_weight=avg_timestamp_weight,
                               avg_timestamp_references=tuple(avg_timestamp_references),
@@ -282,10 +285,14 @@ class SharpnessHook:
     ``/ON`` and ``/OFF``.  A drawn image row becomes count image | image of
     warped events | average timestamp at zero flow | average timestamp after
     the warp, and the ``.yml`` gains ``RSAT``, ``pixels_with_events`` and
-    ``pixels_with_warped_events`` per image.  Off: nothing of it is built."""
+    ``pixels_with_warped_events`` per image.  Off: nothing of it is built.
+
+    tiled: True or 'force': the splat by the tiled schedule for dense frames
+    (``testing.flow_warp_loss``); the same rows and pictures, bit for bit.  Not
+    with ``rsat``, whose splat has no tiled form."""
 
     def __init__(self, model, sequence, logger, shape, directory, frame_step=1, pictures=4,
-                 rank=0, batch_size=8, references=('start',), polarity=False, rsat=False):
+                 rank=0, batch_size=8, references=('start',), polarity=False, rsat=False, tiled=False):
         from .eval import iwe_image_names
         from .loss import contrast_reference_mask
         self.model, self.sequence, self.logger = model, sequence, logger
@@ -295,6 +302,9 @@ class SharpnessHook:
         self.directory, self.rank = Path(directory), rank
         self.batch_size = int(batch_size)
         self.rsat = bool(rsat)
+        if tiled and self.rsat:
+            raise ValueError('tiled has no form for rsat: the average-timestamp images are splatted per event')
+        self.tiled = tiled
         self.frames = self.chosen = ()
         if rank != 0:
             return
@@ -339,7 +349,7 @@ class SharpnessHook:
             return rows, drawn, avg_rows
         rows = testing.flow_warp_loss(of, self.sequence, self.frames, self.box, self.batch_size,
                                       observer=draw, references=self.reference_mask,
-                                      polarity=self.polarity)
+                                      polarity=self.polarity, **({'tiled': self.tiled} if self.tiled else {}))
         return rows, drawn
 
     def __call__(self, steps, samples):

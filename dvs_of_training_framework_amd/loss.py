@@ -576,10 +576,12 @@ class _Contrast(torch.autograd.Function):
     """(weight * term, term) of the finest flow; the gradient of the first
     enters the flow (dvsof_contrast_multi_fwd / dvsof_contrast_multi_bwd, with
     the reference times of ``mask`` and the polarities apart or not).  The
-    weight is applied inside the backward's closing kernel."""
+    weight is applied inside the backward's closing kernel.  tiled: the
+    forward's splat by the tiled schedule (dvsof_contrast_multi_fwd_tiled, mode
+    ``eval.event_images_tiled_mode(tiled)``): the same q, so the same backward."""
 
     @staticmethod
-    def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity):
+    def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity, tiled=False):
         from .eval import IWE_RESULT_DTYPE
         dev = flow.device
         flow = flow.detach().contiguous().float()
@@ -598,9 +600,17 @@ class _Contrast(torch.autograd.Function):
         ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
         ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
                        flow.data_ptr(), F, h, w, mask, int(polarity)])
-        _lib.check(getattr(lib, 'dvsof_contrast_multi_fwd' + ctx.form)(
-            *ctx.args, q.data_ptr(), count.data_ptr(), result.data_ptr(), term.data_ptr(), ws.data_ptr(),
-            nbytes, _lib.stream()), 'dvsof_contrast_multi_fwd' + ctx.form)
+        out = (q.data_ptr(), count.data_ptr(), result.data_ptr(), term.data_ptr(), ws.data_ptr(), nbytes,
+               _lib.stream())
+        if tiled:
+            from .eval import event_images_tiled_mode, event_images_tiled_workspace
+            name = 'dvsof_contrast_multi_fwd' + ctx.form + '_tiled'
+            tiles, tile_bytes = event_images_tiled_workspace(F, mask, polarity, h, w, cols[0].numel(), dev)
+            _lib.check(getattr(lib, name)(*ctx.args, *out, _lib.ptr(tiles), tile_bytes,
+                                          event_images_tiled_mode(tiled)), name)
+        else:
+            _lib.check(getattr(lib, 'dvsof_contrast_multi_fwd' + ctx.form)(*ctx.args, *out),
+                       'dvsof_contrast_multi_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flow, q, ws, nbytes)
         ctx.weight = float(weight)
         ctx.mark_non_differentiable(term)
@@ -610,14 +620,14 @@ class _Contrast(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_value, _g_term):
         if g_value is None:
-            return (None,) * 11
+            return (None,) * 12
         flow, q, ws, nbytes = ctx.held[3:]
         grad = torch.empty_like(flow)
         seed = g_value.contiguous().float()
         _lib.check(getattr(_lib.lib(), 'dvsof_contrast_multi_bwd' + ctx.form)(
             *ctx.args, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(),
             _lib.stream()), 'dvsof_contrast_multi_bwd' + ctx.form)
-        return (grad,) + (None,) * 10
+        return (grad,) + (None,) * 11
 
 
 # The term on every flow scale (csrc/contrast.hip, CONTRAST_SPEC sections 19-23)
@@ -1238,7 +1248,7 @@ class Losses:
         return _FramelessLoss.apply(weights, loss_scale, *flows)
 
     def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None,
-                 references=('start',), polarity=False, scales='finest'):
+                 references=('start',), polarity=False, scales='finest', tiled=False):
         """The contrast-maximisation term of the finest flow ``flows[-1]``
         (docs/CONTRAST_SPEC.md): the mean over the predictions of
         1 - var(image of warped events) / var(count image), negative where the
@@ -1264,7 +1274,15 @@ class Losses:
         respect to every flow (without a ``weight``: the mean of the levels'
         terms); with a ``weight`` -> (that, terms [K]), the levels' unweighted
         terms detached for logging.  'finest', the default, is the call above
-        and constructs nothing else."""
+        and constructs nothing else.
+
+        tiled: True or 'force' (``eval.event_images_tiled_mode``): the
+        forward's splat by the tiled schedule for dense frames
+        (include/dvsof_event_images_tiled.h): the same images, so the same term
+        and gradient, bit for bit.  Not with scales='all', whose splat has no
+        tiled form.  False, the default: the calls above."""
+        if tiled and scales != 'finest':
+            raise ValueError('tiled has no form for scales=\'all\': the pyramid\'s splat is per event')
         if scales != 'finest':
             if scales not in CONTRAST_SCALES:
                 raise ValueError(f'unknown contrast scales "{scales}": one of {", ".join(CONTRAST_SCALES)}')
@@ -1279,7 +1297,7 @@ class Losses:
         weight_ = 1.0 if weight is None else float(weight)
         _lib.require_cuda(pol)
         value, term = _Contrast.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
-                                      bool(polarity))
+                                      bool(polarity), *((tiled,) if tiled else ()))
         return value if weight is None else (value, term)
 
     def avg_timestamp(self, flows, flow_ts, flow_sample_idx, events, weight=None,

@@ -377,6 +377,16 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'with all their options, and the frameless batches of --recording, '
                              'instead of running the loop eagerly for them; bit-identical to '
                              'the eager step.  Opt-in: without it --capture decides as before')
+    parser.add_argument('--event-images-tiled', dest='event_images_tiled',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='build the images of warped events of the contrast term '
+                             '(--contrast-weight) and of the sharpness measurement '
+                             '(--sharpness-period) by the tiled schedule for dense frames: events '
+                             'bucketed by image tile, sums in LDS, one store per pixel and tile; '
+                             'the same images bit for bit, and the kernels decide by the event '
+                             'count whether it pays (include/dvsof_event_images_tiled.h).  Not with '
+                             '--contrast-scales all, --sharpness-rsat or --capture-event-terms, '
+                             'which have no tiled form')
     parser.add_argument('--compact-event-terms', dest='compact_event_terms',
                         default=argparse.SUPPRESS, action='store_true',
                         help='with --compact-events and a positive --contrast-weight or '
@@ -462,8 +472,27 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_compact_event_terms_args(validate_capture_event_terms_args(validate_frameless_args(
-        validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args))))))
+    return validate_event_images_tiled_args(validate_compact_event_terms_args(
+        validate_capture_event_terms_args(validate_frameless_args(
+            validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args)))))))
+
+
+def validate_event_images_tiled_args(args):
+    """--event-images-tiled (absent from ``args`` unless given) against what
+    it needs, images of warped events to build, and against the options whose
+    splat has no tiled form."""
+    if not getattr(args, 'event_images_tiled', False):
+        return args
+    for given, flag in ((getattr(args, 'contrast_scales', 'finest') != 'finest', '--contrast-scales all'),
+                        (getattr(args, 'sharpness_rsat', False), '--sharpness-rsat'),
+                        (getattr(args, 'capture_event_terms', False), '--capture-event-terms')):
+        if given:
+            raise SystemExit(f'--event-images-tiled cannot be combined with {flag}: its splat has no '
+                             'tiled form')
+    if not (getattr(args, 'contrast_weight', 0.0) > 0 or getattr(args, 'sharpness_period', 0) > 0):
+        raise SystemExit('--event-images-tiled needs a positive --contrast-weight or --sharpness-period: '
+                         'without either no image of warped events is built')
+    return args
 
 
 def validate_compact_event_terms_args(args):

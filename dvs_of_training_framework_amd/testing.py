@@ -278,7 +278,7 @@ def evaluate_frames(of, events, frames, gt, event_preproc_fun=None,
 
 
 def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None, references=('start',),
-                   polarity=False):
+                   polarity=False, tiled=False):
     """Label-free quality of ``of`` on a device-resident
     ``sequence.EventSequence``: per frame the statistics of the image of warped
     events and of the count image (docs/IWE_SPEC.md) as a numpy structured
@@ -298,15 +298,21 @@ def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None, 
     defaults a batch makes one ``eval.iwe_splat_multi`` call in place of the
     count image and the splat, and every frame has R C rows, in image order
     m = (f R + r) C + c (``eval.iwe_image_names``); the observer gets the
-    tensors of the batch's images."""
+    tensors of the batch's images.
+
+    tiled: True or 'force' (``eval.iwe_splat_multi``): every batch makes that
+    one call by the tiled schedule, at the defaults too (its q and count hold
+    the bytes of the two calls it stands for), and the rows are the same bits.
+    False, the default: the calls above."""
     from .loss import contrast_reference_mask
     mask, polarity = contrast_reference_mask(references), bool(polarity)
-    multi = mask != 1 or polarity
+    multi = mask != 1 or polarity or bool(tiled)
     out = []
     for b0, pred, collated, (h, w) in _warped_event_batches('flow_warp_loss', of, sequence, frames, box, batch_size):
         ev = collated.events
         if multi:
-            q, count = dev_eval.iwe_splat_multi(ev, collated.win_out, collated.timestamps, pred, mask, polarity)
+            q, count = dev_eval.iwe_splat_multi(ev, collated.win_out, collated.timestamps, pred, mask, polarity,
+                                                **({'tiled': tiled} if tiled else {}))
         else:
             count = dev_eval.count_image_batched(ev['x'], ev['y'], collated.win_out, (h, w),
                                                  (0, 0, h, w))

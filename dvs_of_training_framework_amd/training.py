@@ -60,10 +60,10 @@ class _TermsAndContrast(tuple):
         return self
 
 
-def _contrast_options(references, polarity, scales='finest'):
+def _contrast_options(references, polarity, scales='finest', tiled=False):
     """The keywords of ``Losses.contrast`` that differ from its defaults, so
     that a run without them makes the call it always made."""
-    out = {}
+    out = {'tiled': tiled} if tiled else {}
     if scales != 'finest':
         out['scales'] = scales
     if tuple(references) != ('start',):
@@ -73,13 +73,13 @@ def _contrast_options(references, polarity, scales='finest'):
     return out
 
 
-def _contrast_keywords(weight, references, polarity, scales='finest'):
+def _contrast_keywords(weight, references, polarity, scales='finest', tiled=False):
     """What a call down the chain gets: nothing at weight 0, and the options
     only where they differ from the defaults."""
     if not weight:
         return {}
     return dict({'contrast_weight': weight},
-                **{'contrast_' + k: v for k, v in _contrast_options(references, polarity, scales).items()})
+                **{'contrast_' + k: v for k, v in _contrast_options(references, polarity, scales, tiled).items()})
 
 
 AVG_TIMESTAMP_REFERENCES = ('start', 'end')
@@ -113,7 +113,7 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   frame_indices=None, contrast_weight=0.0, events=None,
                   contrast_references=('start',), contrast_polarity=False,
                   contrast_scales='finest', avg_timestamp_scales='finest',
-                  avg_timestamp_weight=0.0,
+                  contrast_tiled=False, avg_timestamp_weight=0.0,
                   avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                   avg_timestamp_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
@@ -131,7 +131,9 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     contrast_scales='all': the term of every flow, each level weighing
     contrast_weight / K (CONTRAST_SPEC sections 19-23); ``.contrast`` is then
     the [K] tensor of the levels' terms.  'finest', the default, is the call
-    as it was.
+    as it was.  contrast_tiled: True or 'force': the term's splat by the tiled
+    schedule for dense frames (``Losses.contrast``, the same bits); False, the
+    default, passes nothing on.
 
     avg_timestamp_weight > 0: plus avg_timestamp_weight * the average-timestamp
     term of the finest flow over ``events`` (loss.Losses.avg_timestamp,
@@ -184,7 +186,8 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                              '(is_raw=True); preprocessed voxel grids carry none')
         value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events,
                                          weight=contrast_weight, **_contrast_options(
-                                             contrast_references, contrast_polarity, contrast_scales))
+                                             contrast_references, contrast_polarity, contrast_scales,
+                                             contrast_tiled))
         loss = loss + value
     if avg_timestamp_weight:
         if avg_timestamp_weight < 0:
@@ -311,7 +314,7 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       weights, return_prediction=False, contrast_weight=0.0,
                       contrast_references=('start',), contrast_polarity=False,
                       contrast_scales='finest', avg_timestamp_scales='finest',
-                      avg_timestamp_weight=0.0,
+                      contrast_tiled=False, avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
     """batch (SURVEY 8b wire format, or compact event columns:
@@ -321,7 +324,8 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
     events only) with its references, polarity and scales: see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
     the frame size from ``'shape'`` and the loss that reads no frame."""
-    contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales)
+    contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales,
+                                  contrast_tiled)
     if contrast and not is_raw:
         raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
     avg = _avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references, avg_timestamp_polarity,
@@ -570,7 +574,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           contrast_weight: float = 0.0, contrast_references=('start',),
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
           capture_event_terms: bool = False, avg_timestamp_scales: str = 'finest',
-          avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+          contrast_tiled=False, avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
@@ -614,6 +618,12 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                weighing contrast_weight / K; ``Train/contrast`` is then the
                mean of the levels' terms and ``Train/contrast/<tag>`` each
                level's.  'finest' (the default): the finest flow alone
+    contrast_tiled:  True or 'force': that term's splat by the tiled schedule
+               for dense frames (``loss.Losses.contrast``; the same bits).  Not
+               with contrast_scales='all' and not in a step captured with
+               ``capture_event_terms``, which have no tiled form (ValueError).
+               False (the default): the step launches what it launches
+               without it
     avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
                the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
                events only), logged as ``Train/avg timestamp``, beside the
@@ -655,6 +665,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     captured = None
     # the opt-in: the captured step carries the events-only terms that are asked for
     event_terms = {}
+    if contrast_tiled and contrast_weight and ((capture and capture_event_terms) or contrast_scales != 'finest'):
+        raise ValueError('contrast_tiled has no form for contrast_scales=\'all\' or a step captured with '
+                         'capture_event_terms')
     if capture and capture_event_terms:
         event_terms = dict(
             _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales),
@@ -708,7 +721,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
             loss, terms, tags = process_minibatch(
                 model, batch, timers, device, is_raw, evaluator, weights,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
-                                     contrast_scales),
+                                     contrast_scales, contrast_tiled),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
                                           avg_timestamp_polarity, avg_timestamp_scales))
             with _timed(timers, 'backprop'):
@@ -787,8 +800,9 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
 def validate(model, device, loader, samples_passed, logger, evaluator,
              weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
              contrast_references=('start',), contrast_polarity=False,
-             contrast_scales='finest', avg_timestamp_scales='finest', avg_timestamp_weight=0.0,
-             avg_timestamp_references=AVG_TIMESTAMP_REFERENCES, avg_timestamp_polarity=False):
+             contrast_scales='finest', avg_timestamp_scales='finest', contrast_tiled=False,
+             avg_timestamp_weight=0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+             avg_timestamp_polarity=False):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
     the loss holds the contrast-maximisation term (of those reference times
@@ -797,7 +811,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
     avg_timestamp_weight > 0 it holds the average-timestamp term as well,
     written as ``Validation/avg timestamp``; with avg_timestamp_scales='all'
     that is the mean of the levels' terms, each written as ``Validation/avg
-    timestamp/<tag>`` beside it."""
+    timestamp/<tag>`` beside it.  contrast_tiled: as ``train`` takes it."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -806,7 +820,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
             loss, terms, tags = process_minibatch(
                 model, batch, quiet, device, is_raw, evaluator, weights,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
-                                     contrast_scales),
+                                     contrast_scales, contrast_tiled),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
                                           avg_timestamp_polarity, avg_timestamp_scales))
             sums.add(loss, terms, tags)

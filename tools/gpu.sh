@@ -63,6 +63,10 @@
 #                                     against wire batches, eager and replayed, in alternating blocks of one run; on a
 #                                     commit without the entry points the wire legs alone
 #                                     (profiles/event_terms_encoded/README.md)
+#   eventtiled [event_images_tiled_bench.py args]  the tiled schedule of the images of warped events
+#                                     (--event-images-tiled; tools/event_images_tiled_bench.py): the metric's splat and
+#                                     the contrast forward, per-event against tiled in alternating blocks of one run
+#                                     after a bitwise comparison (profiles/event_images_tiled/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -149,6 +153,9 @@ eventcapture)
 eventencoded)
   timeout -k 10 560 env "${envs[@]}" python tools/event_terms_encoded_bench.py "$@" > $O/eventencoded.jsonl 2> $O/eventencoded.err
   echo "eventencoded rc=$?"; cut -c1-700 $O/eventencoded.jsonl; tail -3 $O/eventencoded.err ;;
+eventtiled)
+  timeout -k 10 420 env "${envs[@]}" python tools/event_images_tiled_bench.py "$@" > $O/eventtiled.jsonl 2> $O/eventtiled.err
+  echo "eventtiled rc=$?"; cut -c1-700 $O/eventtiled.jsonl; tail -3 $O/eventtiled.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

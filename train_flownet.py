@@ -384,7 +384,8 @@ def add_sharpness(args, hooks, periodic, model, device, logger, rank):
         frame_step=args.sharpness_frame_step, pictures=args.sharpness_pictures, rank=rank,
         references=getattr(args, 'sharpness_references', ('start',)),
         polarity=getattr(args, 'sharpness_polarity', False),
-        **({'rsat': True} if getattr(args, 'sharpness_rsat', False) else {}))
+        **({'rsat': True} if getattr(args, 'sharpness_rsat', False) else {}),
+        **({'tiled': True} if getattr(args, 'event_images_tiled', False) else {}))
     periodic['sharpness'] = make_hook_periodic(hooks['sharpness'], args.sharpness_period)
 
 
@@ -498,7 +499,8 @@ def main(argv=None):
             **({'contrast_weight': args.contrast_weight,
                 'contrast_references': getattr(args, 'contrast_references', ('start',)),
                 'contrast_polarity': getattr(args, 'contrast_polarity', False),
-                'contrast_scales': getattr(args, 'contrast_scales', 'finest')}
+                'contrast_scales': getattr(args, 'contrast_scales', 'finest'),
+                **({'contrast_tiled': True} if getattr(args, 'event_images_tiled', False) else {})}
                if getattr(args, 'contrast_weight', 0.0) else {}),
             **avg_timestamp_keywords(args))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
@@ -531,6 +533,8 @@ def main(argv=None):
                   contrast_polarity=getattr(args, 'contrast_polarity', False),
                   contrast_scales=getattr(args, 'contrast_scales', 'finest'),
                   **avg_timestamp_keywords(args),
+                  **({'contrast_tiled': True} if getattr(args, 'event_images_tiled', False)
+                     and getattr(args, 'contrast_weight', 0.0) else {}),
                   **({'capture_event_terms': True}
                      if getattr(args, 'capture_event_terms', False) else {}))
             samples = samples_passed + remaining * args.bs
