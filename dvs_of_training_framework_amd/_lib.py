@@ -22,7 +22,9 @@ tests/golden/abi_signatures_event_terms_encoded.json;
 _abi.IWE_AVG_TIMESTAMP_PATH: include/dvsof_iwe_avg_timestamp.h, recorded in
 tests/golden/abi_signatures_iwe_avg_timestamp.json;
 _abi.EVENT_IMAGES_TILED_PATH: include/dvsof_event_images_tiled.h, recorded in
-tests/golden/abi_signatures_event_images_tiled.json).
+tests/golden/abi_signatures_event_images_tiled.json;
+_abi.AVG_TIMESTAMP_TILED_PATH: include/dvsof_avg_timestamp_tiled.h, recorded in
+tests/golden/abi_signatures_avg_timestamp_tiled.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -137,6 +139,11 @@ def declared_event_images_tiled_symbols():
     return _declared_in((_abi.EVENT_IMAGES_TILED_PATH,))
 
 
+def declared_avg_timestamp_tiled_symbols():
+    """Names of all entry points include/dvsof_avg_timestamp_tiled.h declares."""
+    return _declared_in((_abi.AVG_TIMESTAMP_TILED_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -156,7 +163,9 @@ def lib():
                                   **_AVG_TIMESTAMP_PYRAMID_SIGNATURES,
                                   **_EVENT_TERMS_ENCODED_SIGNATURES,
                                   **_IWE_AVG_TIMESTAMP_SIGNATURES,
-                                  **_EVENT_IMAGES_TILED_SIGNATURES}.items():
+                                  **_EVENT_IMAGES_TILED_SIGNATURES,
+                                  # include/dvsof_avg_timestamp_tiled.h: bound from its table directly
+                                  **_abi.AVG_TIMESTAMP_TILED_FUNCTIONS}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

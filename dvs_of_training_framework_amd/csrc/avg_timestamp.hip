@@ -31,9 +31,11 @@
 // kernels and by those.
 #include "event_columns.h"
 #include "avg_timestamp_images.h"
+#include "avg_timestamp_tiled.h"
 #include "../../include/dvsof_avg_timestamp.h"
 #include "../../include/dvsof_avg_timestamp_pyramid.h"
 #include "../../include/dvsof_event_terms_encoded.h"
+#include "../../include/dvsof_avg_timestamp_tiled.h"
 
 namespace {
 
@@ -274,21 +276,42 @@ int check_call(const Cols &cols, int64_t n_events, const float *frame_ts, const 
     return DVSOF_OK;
 }
 
+// the columns as the tiled splat's launcher takes them (event_images_tiled.h)
+TiledTermColumns plain(const WireColumns &c) { return TiledTermColumns{0, c.x, c.y, c.t, c.pol, c.sample, 0}; }
+TiledTermColumns plain(const EncodedColumns &c) { return TiledTermColumns{1, c.x, c.y, c.t, c.pol, c.ev_off, c.B}; }
+
+// the tiled twins' three arguments; mode < 0: the calls that have none
+struct TiledSplat {
+    void *workspace;
+    size_t bytes;
+    int mode;
+};
+
 // dvsof_avg_timestamp_fwd / _bwd on either form of the event columns (event_columns.h)
 template <class Cols>
 int one_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
             const float *flow, int F, int h, int w, int reference_mask, int polarity, float *term, void *workspace,
-            size_t workspace_bytes, void *stream)
+            size_t workspace_bytes, void *stream, const TiledSplat tiled = TiledSplat{nullptr, 0, -1})
 {
     Plan pl;
     const int rc = check_call(cols, n_events, frame_ts, frame_sample, flow, F, h, w, reference_mask, polarity,
                               term != nullptr, workspace, workspace_bytes, pl);
     if (rc != DVSOF_OK || F == 0) return rc;
+    TilePlan tp;
+    const int by_tiles = tiled.mode < 0 ? 1 : avgts_tile_decide(tiled.mode, F, reference_mask, polarity, h, w,
+                                                                n_events, tiled.workspace, tiled.bytes, tp);
+    if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
     hipStream_t st = as_stream(stream);
     const Layout lay = layout_of(F, h, w, pl);
     char *ws = (char *)workspace;
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, lay.zeroed_bytes, st));
-    if (n_events > 0) {
+    if (by_tiles == DVSOF_OK) {
+        const AvgtsImages img{(int64_t *)ws, (int64_t *)(ws + lay.s), (int64_t *)(ws + lay.base),
+                              (uint32_t *)(ws + lay.count)};
+        const int rs = avg_timestamp_tiled_term_splat(plain(cols), n_events, frame_ts, frame_sample, flow, F, h, w,
+                                                      reference_mask, polarity, tp, img, tiled.workspace, st);
+        if (rs != DVSOF_OK) return rs;
+    } else if (n_events > 0) {
         DVSOF_REFS_POL_DISPATCH(avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
                                 n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
                                 (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
@@ -388,6 +411,34 @@ int dvsof_avg_timestamp_bwd_encoded(const int16_t *x, const int16_t *y, const fl
     return one_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
                    flow, F, h, w, reference_mask, polarity_channels, workspace, workspace_bytes, seed, weight,
                    grad_flow, stream);
+}
+
+// The tiled twins (include/dvsof_avg_timestamp_tiled.h): the forward above with the splat by tiles
+int dvsof_avg_timestamp_fwd_tiled(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                  const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                  const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                                  int reference_mask, int polarity, float *term, void *workspace,
+                                  size_t workspace_bytes, void *stream, void *tile_workspace,
+                                  size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return one_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                   reference_mask, polarity, term, workspace, workspace_bytes, stream,
+                   TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+}
+
+int dvsof_avg_timestamp_fwd_encoded_tiled(const int16_t *x, const int16_t *y, const float *t,
+                                          const uint8_t *polarity, const int64_t *sample_event_offsets, int B,
+                                          int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+                                          const float *flow, int F, int h, int w, int reference_mask,
+                                          int polarity_channels, float *term, void *workspace,
+                                          size_t workspace_bytes, void *stream, void *tile_workspace,
+                                          size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return one_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                   flow, F, h, w, reference_mask, polarity_channels, term, workspace, workspace_bytes, stream,
+                   TiledSplat{tile_workspace, tile_workspace_bytes, mode});
 }
 
 }  // extern "C"

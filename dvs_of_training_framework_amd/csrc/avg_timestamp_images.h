@@ -20,6 +20,39 @@ struct StatRow {
 static_assert(sizeof(StatRow) == 32, "a statistics row is 32 bytes");
 
 // ---------------------------------------------------------------------------
+// The corners of a warped event, a = |sig| from the reference: at every corner
+// inside the h x w images qm and sm the weight and the weight times the
+// distance, in units of 2^-32.  Every schedule of the splat calls this
+// (avgts_splat_event; an overflowing bucket of avg_timestamp_tiled.hip), and
+// avgts_corner_units is what its tile pass adds in LDS.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void avgts_corner_units(float wy, float wx, float a, int64_t &Q, int64_t &QA)
+{
+    const float wgt = wy * wx;
+    Q = (int64_t)(wgt * kOne);         // the addend of splat_corners
+    QA = (int64_t)((wgt * a) * kOne);  // one float32 product, then exact; QA <= Q
+}
+
+__device__ __forceinline__ void avgts_splat_corners(const Warp &p, float a, int h, int w,
+                                                    unsigned long long *__restrict__ qm,
+                                                    unsigned long long *__restrict__ sm)
+{
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int xx = p.cx + i, yy = p.cy + j;
+            if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
+            int64_t Q, QA;
+            avgts_corner_units(p.wy[j], p.wx[i], a, Q, QA);
+            const size_t at = (size_t)yy * w + (size_t)xx;
+            if (Q > 0) atomicAdd(qm + at, (unsigned long long)Q);
+            if (QA > 0) atomicAdd(sm + at, (unsigned long long)QA);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // An event at (xi, yi) = pixel pix inside an h x w frame, of channel c, at tau
 // of the window of its frame f, with the flow (u, v) at its own pixel (read
 // once for all references): per reference the count and the distance at the
@@ -45,21 +78,7 @@ __device__ __forceinline__ void avgts_splat_event(const Refs &refs, int f, int c
         const int64_t B = (int64_t)(a * kOne);  // exact; 0 <= B <= 2^32
         if (B > 0) atomicAdd(base + m * plane + pix, (unsigned long long)B);
         if (!inside) continue;
-        unsigned long long *qm = q + m * plane, *sm = s + m * plane;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int xx = p.cx + i, yy = p.cy + j;
-                if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
-                const float wgt = p.wy[j] * p.wx[i];
-                const int64_t Q = (int64_t)(wgt * kOne);         // the addend of splat_corners
-                const int64_t QA = (int64_t)((wgt * a) * kOne);  // one float32 product, then exact; QA <= Q
-                const size_t at = (size_t)yy * w + (size_t)xx;
-                if (Q > 0) atomicAdd(qm + at, (unsigned long long)Q);
-                if (QA > 0) atomicAdd(sm + at, (unsigned long long)QA);
-            }
-        }
+        avgts_splat_corners(p, a, h, w, q + m * plane, s + m * plane);
     }
 }
 

@@ -70,17 +70,24 @@ inline bool tile_plan(int F, int reference_mask, int polarity, int h, int w, int
 inline size_t tile_cursor_bytes(const TilePlan &p) { return (size_t)p.tiles * kCursorStride * 4; }
 
 // the cursors, then per tile three columns of cap words: the corner, the bits of fx, of fy
-inline size_t tile_workspace_bytes(const TilePlan &p) { return tile_cursor_bytes(p) + (size_t)p.tiles * p.cap * 12; }
+// (record_bytes = 16 for the average-timestamp splat of avg_timestamp_tiled.h: a fourth column)
+constexpr int kTileRecordBytes = 12;
+inline size_t tile_workspace_bytes(const TilePlan &p, int record_bytes = kTileRecordBytes)
+{
+    return tile_cursor_bytes(p) + (size_t)p.tiles * p.cap * record_bytes;
+}
 
 // Which schedule a call runs.  DVSOF_OK: tiled (plan filled in); 1: the one-thread-per-event
 // kernel (no events, mode 0 below the threshold, or a refused plan); else the error to return.
+// record_bytes, from_events: those of the splat that asks (the defaults: the images of event_images.h).
 inline int tile_decide(int mode, int F, int reference_mask, int polarity, int h, int w, int64_t n_events,
-                       const void *tile_workspace, size_t tile_workspace_bytes_, TilePlan &tp)
+                       const void *tile_workspace, size_t tile_workspace_bytes_, TilePlan &tp,
+                       int record_bytes = kTileRecordBytes, int64_t from_events = kTiledFromEvents)
 {
     if (mode != 0 && mode != 1) return DVSOF_EINVAL;
-    if (n_events == 0 || (mode == 0 && n_events < kTiledFromEvents)) return 1;
+    if (n_events == 0 || (mode == 0 && n_events < from_events)) return 1;
     if (!tile_plan(F, reference_mask, polarity, h, w, n_events, tp)) return 1;
-    if (!tile_workspace || tile_workspace_bytes_ < tile_workspace_bytes(tp)) return DVSOF_ENOSPACE;
+    if (!tile_workspace || tile_workspace_bytes_ < tile_workspace_bytes(tp, record_bytes)) return DVSOF_ENOSPACE;
     return DVSOF_OK;
 }
 

@@ -29,8 +29,10 @@
 // This file relies on -ffp-contract=off.
 #include "render_common.h"
 #include "avg_timestamp_images.h"
+#include "avg_timestamp_tiled.h"
 #include "../../include/dvsof_iwe_multi.h"
 #include "../../include/dvsof_iwe_avg_timestamp.h"
+#include "../../include/dvsof_avg_timestamp_tiled.h"
 
 static_assert(sizeof(dvsof_iwe_result_t) == 48, "result rows are 48 bytes (eval.py reads them as such)");
 
@@ -222,6 +224,54 @@ AvgtsLayout avgts_layout(int h, int w, const Plan &pl)
     return o;
 }
 
+// dvsof_iwe_avg_timestamp; mode >= 0: its tiled twin (include/dvsof_avg_timestamp_tiled.h), the
+// same call with the splat by tiles where avgts_tile_decide says so
+int iwe_avg_timestamp(const int64_t *x, const int64_t *y, const float *t, const int64_t *p, int64_t n_events,
+                      const int64_t *frame_event_begin, const float *frame_ts, const float *flow, int F, int h,
+                      int w, int reference_mask, int polarity, void *images, size_t image_bytes, void *rows,
+                      void *workspace, size_t workspace_bytes, void *stream, void *tile_workspace,
+                      size_t tile_workspace_bytes, int mode)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !images || !rows || !frame_event_begin || !frame_ts || !flow)
+        return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !t || (polarity && !p))) return DVSOF_EINVAL;
+    const AvgtsLayout lay = avgts_layout(h, w, pl);
+    const int nb = partial_blocks(h, w);
+    if (image_bytes < lay.bytes) return DVSOF_ENOSPACE;
+    if (!workspace || workspace_bytes < sizeof(StatRow) * (size_t)pl.M * nb) return DVSOF_ENOSPACE;
+    TilePlan tp;
+    const int by_tiles = mode < 0 ? 1 : avgts_tile_decide(mode, F, reference_mask, polarity, h, w, n_events,
+                                                          tile_workspace, tile_workspace_bytes, tp);
+    if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
+    hipStream_t st = as_stream(stream);
+    char *im = (char *)images;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(im, 0u, lay.zeroed_bytes, st));
+    if (by_tiles == DVSOF_OK) {
+        const AvgtsImages img{(int64_t *)im, (int64_t *)(im + lay.s), (int64_t *)(im + lay.base),
+                              (uint32_t *)(im + lay.count)};
+        const int rs = avg_timestamp_tiled_frames_splat(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F,
+                                                        h, w, reference_mask, polarity, tp, img, tile_workspace, st);
+        if (rs != DVSOF_OK) return rs;
+    } else if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(iwe_avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
+                                p, n_events, frame_event_begin, frame_ts, flow, F, h, w, pl.refs,
+                                (unsigned long long *)im, (unsigned long long *)(im + lay.s),
+                                (unsigned long long *)(im + lay.base), (uint32_t *)(im + lay.count));
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(avgts_stats_partial_kernel, dim3((unsigned)nb, (unsigned)pl.M), dim3(NT), 0, st,
+                       (const int64_t *)im, (const int64_t *)(im + lay.s), (const int64_t *)(im + lay.base),
+                       (const uint32_t *)(im + lay.count), h, w, nb, (StatRow *)workspace);
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(frame_final_kernel<AvgSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
+                       (const StatRow *)workspace, nb, (StatRow *)rows);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -329,34 +379,22 @@ int dvsof_iwe_avg_timestamp(const int64_t *x, const int64_t *y, const float *t, 
                             const float *flow, int F, int h, int w, int reference_mask, int polarity, void *images,
                             size_t image_bytes, void *rows, void *workspace, size_t workspace_bytes, void *stream)
 {
-    Plan pl;
-    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
-    if (F == 0) return DVSOF_OK;
-    if (bad_frame_sizes(F, h, w) || !images || !rows || !frame_event_begin || !frame_ts || !flow)
-        return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || (polarity && !p))) return DVSOF_EINVAL;
-    const AvgtsLayout lay = avgts_layout(h, w, pl);
-    const int nb = partial_blocks(h, w);
-    if (image_bytes < lay.bytes) return DVSOF_ENOSPACE;
-    if (!workspace || workspace_bytes < sizeof(StatRow) * (size_t)pl.M * nb) return DVSOF_ENOSPACE;
-    hipStream_t st = as_stream(stream);
-    char *im = (char *)images;
-    DVSOF_HIP_TRY((hipError_t)fill_u32(im, 0u, lay.zeroed_bytes, st));
-    if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(iwe_avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
-                                p, n_events, frame_event_begin, frame_ts, flow, F, h, w, pl.refs,
-                                (unsigned long long *)im, (unsigned long long *)(im + lay.s),
-                                (unsigned long long *)(im + lay.base), (uint32_t *)(im + lay.count));
-        DVSOF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(avgts_stats_partial_kernel, dim3((unsigned)nb, (unsigned)pl.M), dim3(NT), 0, st,
-                       (const int64_t *)im, (const int64_t *)(im + lay.s), (const int64_t *)(im + lay.base),
-                       (const uint32_t *)(im + lay.count), h, w, nb, (StatRow *)workspace);
-    DVSOF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frame_final_kernel<AvgSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
-                       (const StatRow *)workspace, nb, (StatRow *)rows);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return iwe_avg_timestamp(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F, h, w, reference_mask,
+                             polarity, images, image_bytes, rows, workspace, workspace_bytes, stream, nullptr, 0, -1);
+}
+
+// The tiled twin (include/dvsof_avg_timestamp_tiled.h)
+int dvsof_iwe_avg_timestamp_tiled(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                  int64_t n_events, const int64_t *frame_event_begin, const float *frame_ts,
+                                  const float *flow, int F, int h, int w, int reference_mask, int polarity,
+                                  void *images, size_t image_bytes, void *rows, void *workspace,
+                                  size_t workspace_bytes, void *stream, void *tile_workspace,
+                                  size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return iwe_avg_timestamp(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F, h, w, reference_mask,
+                             polarity, images, image_bytes, rows, workspace, workspace_bytes, stream, tile_workspace,
+                             tile_workspace_bytes, mode);
 }
 
 int dvsof_iwe_avg_timestamp_render(const void *images, int F, int h, int w, int reference_mask, int polarity,

@@ -547,6 +547,15 @@ def event_images_tiled_workspace(F, mask, polarity, h, w, n_events, device):
     return torch.empty((nbytes + 7) // 8, dtype=torch.long, device=device), nbytes
 
 
+def avg_timestamp_tiled_workspace(F, mask, polarity, h, w, n_events, device):
+    """``event_images_tiled_workspace`` for the tiled calls of
+    include/dvsof_avg_timestamp_tiled.h, whose records are 16 bytes."""
+    nbytes = _lib.lib().dvsof_avg_timestamp_tiled_workspace_bytes(F, mask, int(polarity), h, w, n_events)
+    if not nbytes:
+        return None, 0
+    return torch.empty((nbytes + 7) // 8, dtype=torch.long, device=device), nbytes
+
+
 def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), polarity=False, tiled=False):
     """``iwe_splat`` at several reference times of the window and with ON and
     OFF events apart (csrc/iwe.hip, IWE_SPEC sections 8-13).  events,
@@ -750,7 +759,7 @@ def iwe_avg_timestamp_rows_host(q, s, base, count):
     return avg_timestamp_rows_host(q, s, base, c)
 
 
-def iwe_avg_timestamp(events, win_out, frame_ts, flow, references=('start',), polarity=False):
+def iwe_avg_timestamp(events, win_out, frame_ts, flow, references=('start',), polarity=False, tiled=False):
     """The average-timestamp images of the warped events of a batch of frames
     and their statistics (csrc/iwe.hip, IWE_SPEC sections 14-18).  The
     arguments of ``iwe_splat_multi``.  With M = F R C images ->
@@ -759,7 +768,12 @@ def iwe_avg_timestamp(events, win_out, frame_ts, flow, references=('start',), po
     buffer; q and count hold the bytes of ``iwe_splat_multi``, so that
     ``iwe_stats`` and ``iwe_render`` take them.  For host input the images of
     ``iwe_avg_timestamp_host`` (count uint32) and the rows of
-    ``iwe_avg_timestamp_rows_host`` as a numpy uint8 [M,32]."""
+    ``iwe_avg_timestamp_rows_host`` as a numpy uint8 [M,32].
+
+    tiled: True or 'force' (``event_images_tiled_mode``) runs
+    ``dvsof_iwe_avg_timestamp_tiled``, the same images and rows, byte for byte,
+    with the splat into q and s by the tiled schedule for dense frames
+    (IWE_SPEC section 23); False, the default, the call as it was."""
     from .loss import contrast_reference_mask
     mask, polarity = contrast_reference_mask(references), bool(polarity)
     x, y, t = events['x'], events['y'], events['timestamp']
@@ -795,10 +809,16 @@ def iwe_avg_timestamp(events, win_out, frame_ts, flow, references=('start',), po
     rows = torch.empty(M * 4, dtype=torch.long, device=flow.device).view(torch.uint8).view(M, 32)
     ws_bytes = lib.dvsof_iwe_avg_timestamp_workspace_bytes(F, h, w, mask, int(polarity))
     ws = torch.empty(max(ws_bytes, 32) // 8, dtype=torch.long, device=flow.device)
-    _lib.check(lib.dvsof_iwe_avg_timestamp(
-        x.data_ptr(), y.data_ptr(), t.data_ptr(), _lib.ptr(p), x.numel(), begin.data_ptr(),
-        frame_ts.data_ptr(), flow.data_ptr(), F, h, w, mask, int(polarity), buffer.data_ptr(), nbytes,
-        rows.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream()), 'dvsof_iwe_avg_timestamp')
+    args = (x.data_ptr(), y.data_ptr(), t.data_ptr(), _lib.ptr(p), x.numel(), begin.data_ptr(),
+            frame_ts.data_ptr(), flow.data_ptr(), F, h, w, mask, int(polarity), buffer.data_ptr(), nbytes,
+            rows.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+    if tiled:
+        mode = event_images_tiled_mode(tiled)
+        tiles, tile_bytes = avg_timestamp_tiled_workspace(F, mask, polarity, h, w, x.numel(), flow.device)
+        _lib.check(lib.dvsof_iwe_avg_timestamp_tiled(*args, _lib.ptr(tiles), tile_bytes, mode),
+                   'dvsof_iwe_avg_timestamp_tiled')
+    else:
+        _lib.check(lib.dvsof_iwe_avg_timestamp(*args), 'dvsof_iwe_avg_timestamp')
     return _avg_timestamp_views(buffer, M, h, w), rows
 
 

@@ -88,7 +88,7 @@ class ValidationHook:
     def __init__(self, model, device, loader, logger, losses, weights, is_raw,
                  contrast_weight=0.0, contrast_references=('start',), contrast_polarity=False,
                  contrast_scales='finest', avg_timestamp_scales='finest', contrast_tiled=False,
-                 avg_timestamp_weight=0.0, avg_timestamp_references=('start', 'end'),
+                 avg_timestamp_tiled=False, avg_timestamp_weight=0.0, avg_timestamp_references=('start', 'end'),
                  avg_timestamp_polarity=False):
         self.model, self.device, self.loader = model, device, loader
         self.logger, self.losses = logger, losses
@@ -106,6 +106,8 @@ class ValidationHook:
                               avg_timestamp_polarity=bool(avg_timestamp_polarity))
             if avg_timestamp_scales != 'finest':
                 self.extra['avg_timestamp_scales'] = avg_timestamp_scales
+            if avg_timestamp_tiled:
+                self.extra['avg_timestamp_tiled'] = avg_timestamp_tiled
 
     def __call__(self, steps, samples):
         with model_left_as_found(self.model):
@@ -288,8 +290,9 @@ class SharpnessHook:
     ``pixels_with_warped_events`` per image.  Off: nothing of it is built.
 
     tiled: True or 'force': the splat by the tiled schedule for dense frames
-    (``testing.flow_warp_loss``); the same rows and pictures, bit for bit.  Not
-    with ``rsat``, whose splat has no tiled form."""
+    (``testing.flow_warp_loss``; with ``rsat`` that of the average-timestamp
+    images, ``testing.event_alignment``); the same rows and pictures, bit for
+    bit."""
 
     def __init__(self, model, sequence, logger, shape, directory, frame_step=1, pictures=4,
                  rank=0, batch_size=8, references=('start',), polarity=False, rsat=False, tiled=False):
@@ -302,8 +305,6 @@ class SharpnessHook:
         self.directory, self.rank = Path(directory), rank
         self.batch_size = int(batch_size)
         self.rsat = bool(rsat)
-        if tiled and self.rsat:
-            raise ValueError('tiled has no form for rsat: the average-timestamp images are splatted per event')
         self.tiled = tiled
         self.frames = self.chosen = ()
         if rank != 0:
@@ -345,7 +346,8 @@ class SharpnessHook:
             rows, avg_rows = testing.event_alignment(
                 of, self.sequence, self.frames, self.box, self.batch_size,
                 observer=lambda first, images, results, _: draw(first, images[0], images[3], results, images[1:3]),
-                references=self.reference_mask, polarity=self.polarity)
+                references=self.reference_mask, polarity=self.polarity,
+                **({'tiled': self.tiled} if self.tiled else {}))
             return rows, drawn, avg_rows
         rows = testing.flow_warp_loss(of, self.sequence, self.frames, self.box, self.batch_size,
                                       observer=draw, references=self.reference_mask,

@@ -957,10 +957,12 @@ class _AvgTimestamp(torch.autograd.Function):
     """(weight * term, term) of the finest flow; the gradient of the first
     enters the flow (dvsof_avg_timestamp_fwd / dvsof_avg_timestamp_bwd).  The
     images live in the workspace; the weight is applied inside the backward's
-    closing kernel."""
+    closing kernel.  tiled: the forward's splat by the tiled schedule
+    (dvsof_avg_timestamp_fwd_tiled, mode ``eval.event_images_tiled_mode(tiled)``):
+    the same workspace, so the same backward."""
 
     @staticmethod
-    def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity):
+    def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity, tiled=False):
         dev = flow.device
         flow = flow.detach().contiguous().float()
         F, _, h, w = flow.shape
@@ -974,8 +976,16 @@ class _AvgTimestamp(torch.autograd.Function):
         ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
         ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
                        flow.data_ptr(), F, h, w, mask, int(polarity)])
-        _lib.check(getattr(lib, 'dvsof_avg_timestamp_fwd' + ctx.form)(
-            *ctx.args, term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_avg_timestamp_fwd' + ctx.form)
+        out = (term.data_ptr(), ws.data_ptr(), nbytes, _lib.stream())
+        if tiled:
+            from .eval import avg_timestamp_tiled_workspace, event_images_tiled_mode
+            name = 'dvsof_avg_timestamp_fwd' + ctx.form + '_tiled'
+            tiles, tile_bytes = avg_timestamp_tiled_workspace(F, mask, polarity, h, w, cols[0].numel(), dev)
+            _lib.check(getattr(lib, name)(*ctx.args, *out, _lib.ptr(tiles), tile_bytes,
+                                          event_images_tiled_mode(tiled)), name)
+        else:
+            _lib.check(getattr(lib, 'dvsof_avg_timestamp_fwd' + ctx.form)(*ctx.args, *out),
+                       'dvsof_avg_timestamp_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flow, ws, nbytes)
         ctx.weight = float(weight)
         ctx.mark_non_differentiable(term)
@@ -985,14 +995,14 @@ class _AvgTimestamp(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_value, _g_term):
         if g_value is None:
-            return (None,) * 11
+            return (None,) * 12
         flow, ws, nbytes = ctx.held[3:]
         grad = torch.empty_like(flow)
         seed = g_value.contiguous().float()
         _lib.check(getattr(_lib.lib(), 'dvsof_avg_timestamp_bwd' + ctx.form)(
             *ctx.args, ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(), _lib.stream()),
             'dvsof_avg_timestamp_bwd' + ctx.form)
-        return (grad,) + (None,) * 10
+        return (grad,) + (None,) * 11
 
 
 # The term on every flow scale (csrc/avg_timestamp.hip, AVG_TIMESTAMP_SPEC sections 11-15)
@@ -1316,7 +1326,24 @@ class Losses:
         to both ends of the window (Zhu et al., CVPR 2019): at one end alone
         the events that need no warp carry no distance.  polarity: ON and OFF
         events in images of their own.  The term on every flow scale is
-        ``avg_timestamp_scales``."""
+        ``avg_timestamp_scales``, the splat by tiles ``avg_timestamp_tiled``."""
+        return self._avg_timestamp(flows, flow_ts, flow_sample_idx, events, weight, references, polarity)
+
+    def avg_timestamp_tiled(self, flows, flow_ts, flow_sample_idx, events, weight=None,
+                            references=('start', 'end'), polarity=False, tiled=True):
+        """``avg_timestamp`` with the choice of the splat's schedule (a method
+        of its own: the signature of ``avg_timestamp`` is held as it is).
+        tiled: True or 'force' (``eval.event_images_tiled_mode``): the forward's
+        splat into q and s by the tiled schedule for dense frames
+        (include/dvsof_avg_timestamp_tiled.h, AVG_TIMESTAMP_SPEC section 17):
+        the same images, so the same term and gradient, bit for bit.  False is
+        ``avg_timestamp`` and constructs nothing else.  The term on every flow
+        scale has no tiled form."""
+        if not tiled:
+            return self.avg_timestamp(flows, flow_ts, flow_sample_idx, events, weight, references, polarity)
+        return self._avg_timestamp(flows, flow_ts, flow_sample_idx, events, weight, references, polarity, tiled)
+
+    def _avg_timestamp(self, flows, flow_ts, flow_sample_idx, events, weight, references, polarity, tiled=False):
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the average-timestamp term of scale {self.shapes[-1]}'
@@ -1327,7 +1354,7 @@ class Losses:
         weight_ = 1.0 if weight is None else float(weight)
         _lib.require_cuda(pol)
         value, term = _AvgTimestamp.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
-                                          bool(polarity))
+                                          bool(polarity), *((tiled,) if tiled else ()))
         return value if weight is None else (value, term)
 
     def avg_timestamp_scales(self, flows, flow_ts, flow_sample_idx, events, weight=None,

@@ -386,7 +386,18 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'the same images bit for bit, and the kernels decide by the event '
                              'count whether it pays (include/dvsof_event_images_tiled.h).  Not with '
                              '--contrast-scales all, --sharpness-rsat or --capture-event-terms, '
-                             'which have no tiled form')
+                             'which have no tiled form here (--sharpness-rsat is tiled by '
+                             '--avg-timestamp-tiled)')
+    parser.add_argument('--avg-timestamp-tiled', dest='avg_timestamp_tiled',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='build the average-timestamp images of the average-timestamp term '
+                             '(--avg-timestamp-weight) and of --sharpness-rsat by the tiled '
+                             'schedule for dense frames: the corner adds bucketed by image tile, '
+                             'both sums of a pixel in LDS, one store per pixel and tile; the same '
+                             'images bit for bit, and the kernels decide by the event count '
+                             'whether it pays (include/dvsof_avg_timestamp_tiled.h).  Not with '
+                             '--avg-timestamp-scales all or --capture-event-terms, which have no '
+                             'tiled form')
     parser.add_argument('--compact-event-terms', dest='compact_event_terms',
                         default=argparse.SUPPRESS, action='store_true',
                         help='with --compact-events and a positive --contrast-weight or '
@@ -472,9 +483,27 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_event_images_tiled_args(validate_compact_event_terms_args(
+    return validate_avg_timestamp_tiled_args(validate_event_images_tiled_args(validate_compact_event_terms_args(
         validate_capture_event_terms_args(validate_frameless_args(
-            validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args)))))))
+            validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args))))))))
+
+
+def validate_avg_timestamp_tiled_args(args):
+    """--avg-timestamp-tiled (absent from ``args`` unless given) against what
+    it needs, average-timestamp images to build, and against the options whose
+    splat has no tiled form."""
+    if not getattr(args, 'avg_timestamp_tiled', False):
+        return args
+    for given, flag in ((getattr(args, 'avg_timestamp_scales', 'finest') != 'finest', '--avg-timestamp-scales all'),
+                        (getattr(args, 'capture_event_terms', False), '--capture-event-terms')):
+        if given:
+            raise SystemExit(f'--avg-timestamp-tiled cannot be combined with {flag}: its splat has no '
+                             'tiled form')
+    rsat = getattr(args, 'sharpness_rsat', False) and getattr(args, 'sharpness_period', 0) > 0
+    if not (getattr(args, 'avg_timestamp_weight', 0.0) > 0 or rsat):
+        raise SystemExit('--avg-timestamp-tiled needs a positive --avg-timestamp-weight, or --sharpness-rsat '
+                         'with --sharpness-period: without either no average-timestamp image is built')
+    return args
 
 
 def validate_event_images_tiled_args(args):
@@ -610,6 +639,8 @@ def avg_timestamp_keywords(args):
            'avg_timestamp_polarity': bool(getattr(args, 'avg_timestamp_polarity', False))}
     if getattr(args, 'avg_timestamp_scales', 'finest') != 'finest':     # only where it differs from the default
         out['avg_timestamp_scales'] = args.avg_timestamp_scales
+    if getattr(args, 'avg_timestamp_tiled', False):                     # --avg-timestamp-tiled: likewise
+        out['avg_timestamp_tiled'] = True
     return out
 
 

@@ -325,7 +325,7 @@ def flow_warp_loss(of, sequence, frames, box=None, batch_size=8, observer=None, 
 
 
 def event_alignment(of, sequence, frames, box=None, batch_size=8, observer=None, references=('start',),
-                    polarity=False):
+                    polarity=False, tiled=False):
     """``flow_warp_loss`` and, from the same splat, the statistics of the
     average-timestamp images of the warped events (docs/IWE_SPEC.md sections
     14-21) -> (IWE rows, average-timestamp rows): numpy structured arrays
@@ -340,13 +340,17 @@ def event_alignment(of, sequence, frames, box=None, batch_size=8, observer=None,
     The arguments of ``flow_warp_loss``;
     observer(first, images, iwe_results, avg_rows): called once per batch with
     the index of its first frame and the device tensors, images = (q, s, base,
-    count)."""
+    count).
+
+    tiled: True or 'force' (``eval.iwe_avg_timestamp``): every batch's splat
+    into q and s by the tiled schedule; the same images and rows, bit for bit.
+    False, the default: the call above."""
     from .loss import AVG_TIMESTAMP_ROW_DTYPE, contrast_reference_mask
     mask, polarity = contrast_reference_mask(references), bool(polarity)
     iwe, avg = [], []
     for b0, pred, collated, _ in _warped_event_batches('event_alignment', of, sequence, frames, box, batch_size):
         images, rows = dev_eval.iwe_avg_timestamp(collated.events, collated.win_out, collated.timestamps, pred,
-                                                  mask, polarity)
+                                                  mask, polarity, **({'tiled': tiled} if tiled else {}))
         res = dev_eval.iwe_stats(images[0], images[3])
         iwe.append(dev_eval.read_iwe_results(res))          # the batch's two copies back
         avg.append(dev_eval.read_avg_timestamp_rows(rows))

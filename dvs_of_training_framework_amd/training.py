@@ -85,10 +85,11 @@ def _contrast_keywords(weight, references, polarity, scales='finest', tiled=Fals
 AVG_TIMESTAMP_REFERENCES = ('start', 'end')
 
 
-def _avg_timestamp_options(references, polarity, scales='finest'):
+def _avg_timestamp_options(references, polarity, scales='finest', tiled=False):
     """The keywords of ``Losses.avg_timestamp`` that differ from its defaults;
-    with 'scales' among them the call goes to ``Losses.avg_timestamp_scales``."""
-    out = {}
+    with 'scales' among them the call goes to ``Losses.avg_timestamp_scales``,
+    with 'tiled' to ``Losses.avg_timestamp_tiled``."""
+    out = {'tiled': tiled} if tiled else {}
     if scales != 'finest':
         out['scales'] = scales
     if tuple(references) != AVG_TIMESTAMP_REFERENCES:
@@ -98,14 +99,14 @@ def _avg_timestamp_options(references, polarity, scales='finest'):
     return out
 
 
-def _avg_timestamp_keywords(weight, references, polarity, scales='finest'):
+def _avg_timestamp_keywords(weight, references, polarity, scales='finest', tiled=False):
     """What a call down the chain gets: nothing at weight 0, and the options
     only where they differ from the defaults."""
     if not weight:
         return {}
     return dict({'avg_timestamp_weight': weight},
                 **{'avg_timestamp_' + k: v
-                   for k, v in _avg_timestamp_options(references, polarity, scales).items()})
+                   for k, v in _avg_timestamp_options(references, polarity, scales, tiled).items()})
 
 
 def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
@@ -113,7 +114,8 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   frame_indices=None, contrast_weight=0.0, events=None,
                   contrast_references=('start',), contrast_polarity=False,
                   contrast_scales='finest', avg_timestamp_scales='finest',
-                  contrast_tiled=False, avg_timestamp_weight=0.0,
+                  contrast_tiled=False, avg_timestamp_tiled=False,
+                  avg_timestamp_weight=0.0,
                   avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                   avg_timestamp_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
@@ -144,6 +146,10 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     avg_timestamp_weight / K (loss.Losses.avg_timestamp_scales,
     AVG_TIMESTAMP_SPEC sections 11-15); ``.avg_timestamp`` is then the [K]
     tensor of the levels' terms.  'finest', the default, is the call as it was.
+    avg_timestamp_tiled: True or 'force': the term's splat by the tiled
+    schedule for dense frames (``Losses.avg_timestamp_tiled``, the same bits;
+    not with avg_timestamp_scales='all': ValueError); False, the default,
+    passes nothing on.
 
     images=None with an evaluator that has ``frameless`` (loss.Losses): a
     frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
@@ -195,8 +201,13 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         if events is None:
             raise ValueError('avg_timestamp_weight > 0 needs the raw events of the batch on the device '
                              '(is_raw=True); preprocessed voxel grids carry none')
-        options = _avg_timestamp_options(avg_timestamp_references, avg_timestamp_polarity, avg_timestamp_scales)
-        method = evaluator.avg_timestamp_scales if 'scales' in options else evaluator.avg_timestamp
+        options = _avg_timestamp_options(avg_timestamp_references, avg_timestamp_polarity, avg_timestamp_scales,
+                                         avg_timestamp_tiled)
+        if 'scales' in options and 'tiled' in options:
+            raise ValueError('avg_timestamp_tiled has no form for avg_timestamp_scales=\'all\': the pyramid\'s '
+                             'splat is per event')
+        method = evaluator.avg_timestamp_scales if 'scales' in options else \
+            evaluator.avg_timestamp_tiled if 'tiled' in options else evaluator.avg_timestamp
         value, avg_term = method(flows, flow_ts, flow_sample_idx, events, weight=avg_timestamp_weight, **options)
         loss = loss + value
     return loss, _TermsAndContrast(terms, term, avg_term)
@@ -314,14 +325,15 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       weights, return_prediction=False, contrast_weight=0.0,
                       contrast_references=('start',), contrast_polarity=False,
                       contrast_scales='finest', avg_timestamp_scales='finest',
-                      contrast_tiled=False, avg_timestamp_weight=0.0,
+                      contrast_tiled=False, avg_timestamp_tiled=False,
+                      avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
     """batch (SURVEY 8b wire format, or compact event columns:
     voxel.is_compact) -> (loss, terms, tags[, outputs]).
     contrast_weight > 0 (raw events only, in either column form), contrast_references,
     contrast_polarity, contrast_scales, and avg_timestamp_weight > 0 (raw
-    events only) with its references, polarity and scales: see ``combined_loss``.  A frameless batch
+    events only) with its references, polarity, scales and avg_timestamp_tiled: see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
     the frame size from ``'shape'`` and the loss that reads no frame."""
     contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales,
@@ -329,7 +341,7 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
     if contrast and not is_raw:
         raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
     avg = _avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references, avg_timestamp_polarity,
-                                  avg_timestamp_scales)
+                                  avg_timestamp_scales, avg_timestamp_tiled)
     if avg and not is_raw:
         raise ValueError('avg_timestamp_weight > 0 needs raw events (is_raw=True)')
     if avg:
@@ -574,7 +586,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           contrast_weight: float = 0.0, contrast_references=('start',),
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
           capture_event_terms: bool = False, avg_timestamp_scales: str = 'finest',
-          contrast_tiled=False, avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+          contrast_tiled=False, avg_timestamp_tiled=False, avg_timestamp_weight: float = 0.0,
+          avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
@@ -624,6 +637,10 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                ``capture_event_terms``, which have no tiled form (ValueError).
                False (the default): the step launches what it launches
                without it
+    avg_timestamp_tiled:  the same for the average-timestamp term
+               (``loss.Losses.avg_timestamp_tiled``): not with
+               avg_timestamp_scales='all' and not in a step captured with
+               ``capture_event_terms`` (ValueError)
     avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
                the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
                events only), logged as ``Train/avg timestamp``, beside the
@@ -668,6 +685,10 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     if contrast_tiled and contrast_weight and ((capture and capture_event_terms) or contrast_scales != 'finest'):
         raise ValueError('contrast_tiled has no form for contrast_scales=\'all\' or a step captured with '
                          'capture_event_terms')
+    if avg_timestamp_tiled and avg_timestamp_weight and ((capture and capture_event_terms)
+                                                         or avg_timestamp_scales != 'finest'):
+        raise ValueError('avg_timestamp_tiled has no form for avg_timestamp_scales=\'all\' or a step captured '
+                         'with capture_event_terms')
     if capture and capture_event_terms:
         event_terms = dict(
             _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales),
@@ -723,7 +744,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
                                      contrast_scales, contrast_tiled),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
-                                          avg_timestamp_polarity, avg_timestamp_scales))
+                                          avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass
@@ -801,8 +822,8 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
              weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
              contrast_references=('start',), contrast_polarity=False,
              contrast_scales='finest', avg_timestamp_scales='finest', contrast_tiled=False,
-             avg_timestamp_weight=0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
-             avg_timestamp_polarity=False):
+             avg_timestamp_tiled=False, avg_timestamp_weight=0.0,
+             avg_timestamp_references=AVG_TIMESTAMP_REFERENCES, avg_timestamp_polarity=False):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
     the loss holds the contrast-maximisation term (of those reference times
@@ -811,7 +832,8 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
     avg_timestamp_weight > 0 it holds the average-timestamp term as well,
     written as ``Validation/avg timestamp``; with avg_timestamp_scales='all'
     that is the mean of the levels' terms, each written as ``Validation/avg
-    timestamp/<tag>`` beside it.  contrast_tiled: as ``train`` takes it."""
+    timestamp/<tag>`` beside it.  contrast_tiled, avg_timestamp_tiled: as
+    ``train`` takes them."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -822,7 +844,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
                                      contrast_scales, contrast_tiled),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
-                                          avg_timestamp_polarity, avg_timestamp_scales))
+                                          avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled))
             sums.add(loss, terms, tags)
     logger.add_scalar('General/Validation loss', sums.loss / n_batches,
                       samples_passed)

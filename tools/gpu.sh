@@ -67,6 +67,11 @@
 #                                     (--event-images-tiled; tools/event_images_tiled_bench.py): the metric's splat and
 #                                     the contrast forward, per-event against tiled in alternating blocks of one run
 #                                     after a bitwise comparison (profiles/event_images_tiled/README.md)
+#   avgtiled [avg_timestamp_tiled_bench.py args]  the tiled schedule of the average-timestamp images
+#                                     (--avg-timestamp-tiled; tools/avg_timestamp_tiled_bench.py): the term's forward
+#                                     and the metric's call, per-event against tiled in alternating blocks of one run
+#                                     after a bitwise comparison, and one eager Ranger step either way
+#                                     (profiles/avg_timestamp_tiled/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -156,6 +161,9 @@ eventencoded)
 eventtiled)
   timeout -k 10 420 env "${envs[@]}" python tools/event_images_tiled_bench.py "$@" > $O/eventtiled.jsonl 2> $O/eventtiled.err
   echo "eventtiled rc=$?"; cut -c1-700 $O/eventtiled.jsonl; tail -3 $O/eventtiled.err ;;
+avgtiled)
+  timeout -k 10 540 env "${envs[@]}" python tools/avg_timestamp_tiled_bench.py "$@" > $O/avgtiled.jsonl 2> $O/avgtiled.err
+  echo "avgtiled rc=$?"; cut -c1-700 $O/avgtiled.jsonl; tail -3 $O/avgtiled.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

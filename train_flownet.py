@@ -385,7 +385,8 @@ def add_sharpness(args, hooks, periodic, model, device, logger, rank):
         references=getattr(args, 'sharpness_references', ('start',)),
         polarity=getattr(args, 'sharpness_polarity', False),
         **({'rsat': True} if getattr(args, 'sharpness_rsat', False) else {}),
-        **({'tiled': True} if getattr(args, 'event_images_tiled', False) else {}))
+        **({'tiled': True} if getattr(args, 'event_images_tiled', False) or
+           (getattr(args, 'avg_timestamp_tiled', False) and getattr(args, 'sharpness_rsat', False)) else {}))
     periodic['sharpness'] = make_hook_periodic(hooks['sharpness'], args.sharpness_period)
 
 
