@@ -29,9 +29,8 @@
 // images of a frame, forward and backward, is stated once (avgts_splat_event
 // of avg_timestamp_images.h, avgts_bwd_event) and used by the one-level
 // kernels and by those.
-#include "event_columns.h"
 #include "avg_timestamp_images.h"
-#include "avg_timestamp_tiled.h"
+#include "tiled_splat.h"
 #include "../../include/dvsof_avg_timestamp.h"
 #include "../../include/dvsof_avg_timestamp_pyramid.h"
 #include "../../include/dvsof_event_terms_encoded.h"
@@ -67,27 +66,14 @@ __global__ __launch_bounds__(NT) void avgts_splat_kernel(
     unsigned long long *__restrict__ q, unsigned long long *__restrict__ s, unsigned long long *__restrict__ base,
     uint32_t *__restrict__ count)
 {
-    const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // the -1 slots of cropped and padded events
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t smp = ev.sample;
+    const auto splat = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
         const size_t pix = (size_t)yi * w + (size_t)xi;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != smp) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;  // a test, not a clamp; false for a NaN
-            const float tau = event_tau(te, t0, t1);
-            const float *fl = flow + (size_t)f * 2 * plane + pix;
-            const float u = fl[0], v = fl[plane];
-            avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, s, base, count);
-        }
-    }
+        float u, v;
+        flow_at(flow, f, plane, pix, u, v);
+        avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, s, base, count);
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
 }
 
 // 2^k: the flow gradient of a frame is summed in units of 1/unit; |G_m| <= gmax < 2^e for every image of the frame
@@ -193,31 +179,18 @@ __global__ __launch_bounds__(NT) void avgts_bwd_events_kernel(
     const int64_t *__restrict__ q, const int64_t *__restrict__ s, const ImageRec *__restrict__ rec,
     const double *__restrict__ unit, unsigned long long *__restrict__ acc)
 {
-    const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t smp = ev.sample;
+    const auto addends = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
         const size_t pix = (size_t)yi * w + (size_t)xi;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != smp) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;
-            const float tau = event_tau(te, t0, t1);
-            const float *fl = flow + (size_t)f * 2 * plane + pix;
-            const float u = fl[0], v = fl[plane];
-            long long su = 0, sv = 0;
-            avgts_bwd_event<R, POL>(refs, f, c, tau, u, v, xi, yi, plane, h, w, q, s, rec, unit[f], su, sv);
-            unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
-            if (su != 0) atomicAdd(dst, (unsigned long long)su);
-            if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
-        }
-    }
+        float u, v;
+        flow_at(flow, f, plane, pix, u, v);
+        long long su = 0, sv = 0;
+        avgts_bwd_event<R, POL>(refs, f, c, tau, u, v, xi, yi, plane, h, w, q, s, rec, unit[f], su, sv);
+        unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
+        if (su != 0) atomicAdd(dst, (unsigned long long)su);
+        if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
 }
 
 // One thread per element of grad_flow: convert, clear the sum for the next
@@ -276,17 +249,6 @@ int check_call(const Cols &cols, int64_t n_events, const float *frame_ts, const 
     return DVSOF_OK;
 }
 
-// the columns as the tiled splat's launcher takes them (event_images_tiled.h)
-TiledTermColumns plain(const WireColumns &c) { return TiledTermColumns{0, c.x, c.y, c.t, c.pol, c.sample, 0}; }
-TiledTermColumns plain(const EncodedColumns &c) { return TiledTermColumns{1, c.x, c.y, c.t, c.pol, c.ev_off, c.B}; }
-
-// the tiled twins' three arguments; mode < 0: the calls that have none
-struct TiledSplat {
-    void *workspace;
-    size_t bytes;
-    int mode;
-};
-
 // dvsof_avg_timestamp_fwd / _bwd on either form of the event columns (event_columns.h)
 template <class Cols>
 int one_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
@@ -298,8 +260,7 @@ int one_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int
                               term != nullptr, workspace, workspace_bytes, pl);
     if (rc != DVSOF_OK || F == 0) return rc;
     TilePlan tp;
-    const int by_tiles = tiled.mode < 0 ? 1 : avgts_tile_decide(tiled.mode, F, reference_mask, polarity, h, w,
-                                                                n_events, tiled.workspace, tiled.bytes, tp);
+    const int by_tiles = tile_decide<AvgtsImages>(tiled, F, reference_mask, polarity, h, w, n_events, tp);
     if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
     hipStream_t st = as_stream(stream);
     const Layout lay = layout_of(F, h, w, pl);
@@ -308,7 +269,7 @@ int one_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int
     if (by_tiles == DVSOF_OK) {
         const AvgtsImages img{(int64_t *)ws, (int64_t *)(ws + lay.s), (int64_t *)(ws + lay.base),
                               (uint32_t *)(ws + lay.count)};
-        const int rs = avg_timestamp_tiled_term_splat(plain(cols), n_events, frame_ts, frame_sample, flow, F, h, w,
+        const int rs = TiledLaunch<AvgtsImages>::term(plain(cols), n_events, frame_ts, frame_sample, flow, F, h, w,
                                                       reference_mask, polarity, tp, img, tiled.workspace, st);
         if (rs != DVSOF_OK) return rs;
     } else if (n_events > 0) {
@@ -465,33 +426,20 @@ __global__ __launch_bounds__(NT) void avgts_pyramid_splat_kernel(
     unsigned long long *__restrict__ q, unsigned long long *__restrict__ s, unsigned long long *__restrict__ base,
     uint32_t *__restrict__ count)
 {
-    const int64_t stride = (int64_t)gridDim.x * NT;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // at full resolution, before any shift
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t smp = ev.sample;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != smp) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;
-            const float tau = event_tau(te, t0, t1);
+    const auto splat = [=, &lv](int64_t xi, int64_t yi, int c, int f, float tau) {
 #pragma unroll 1
-            for (int k = 0; k < lv.K; ++k) {
-                const Level &L = lv.level[k];
-                const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
-                const size_t plane = (size_t)L.h * L.w;
-                const size_t pix = (size_t)ys * L.w + (size_t)xs;
-                const float *fl = L.flow + (size_t)f * 2 * plane + pix;
-                const float u = fl[0], v = fl[plane];
-                avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
-                                          s + L.image_offset, base + L.image_offset, count + L.image_offset);
-            }
+        for (int k = 0; k < lv.K; ++k) {
+            const Level &L = lv.level[k];
+            const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
+            const size_t plane = (size_t)L.h * L.w;
+            const size_t pix = (size_t)ys * L.w + (size_t)xs;
+            float u, v;
+            flow_at(L.flow, f, plane, pix, u, v);
+            avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
+                                      s + L.image_offset, base + L.image_offset, count + L.image_offset);
         }
-    }
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
 }
 
 // avgts_close_kernel over the K M images and K F units of all levels (image i = k M + m, unit
@@ -529,38 +477,25 @@ __global__ __launch_bounds__(NT) void avgts_pyramid_bwd_events_kernel(
     const int64_t *__restrict__ q, const int64_t *__restrict__ s, const ImageRec *__restrict__ rec,
     const double *__restrict__ unit, unsigned long long *__restrict__ acc)
 {
-    const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t M = (size_t)F * R * (POL ? 2 : 1);
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t smp = ev.sample;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != smp) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;
-            const float tau = event_tau(te, t0, t1);
+    const auto addends = [=, &lv](int64_t xi, int64_t yi, int c, int f, float tau) {
 #pragma unroll 1
-            for (int k = 0; k < lv.K; ++k) {
-                const Level &L = lv.level[k];
-                const int64_t xs = xi >> L.shift, ys = yi >> L.shift;
-                const size_t plane = (size_t)L.h * L.w;
-                const size_t pix = (size_t)ys * L.w + (size_t)xs;
-                const float *fl = L.flow + (size_t)f * 2 * plane + pix;
-                const float u = fl[0], v = fl[plane];
-                long long su = 0, sv = 0;
-                avgts_bwd_event<R, POL>(refs, f, c, tau, u, v, xs, ys, plane, L.h, L.w, q + L.image_offset,
-                                        s + L.image_offset, rec + (size_t)k * M, unit[(size_t)k * F + f], su, sv);
-                unsigned long long *dst = acc + L.sums_offset + (size_t)f * 2 * plane + pix;
-                if (su != 0) atomicAdd(dst, (unsigned long long)su);
-                if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
-            }
+        for (int k = 0; k < lv.K; ++k) {
+            const Level &L = lv.level[k];
+            const int64_t xs = xi >> L.shift, ys = yi >> L.shift;
+            const size_t plane = (size_t)L.h * L.w;
+            const size_t pix = (size_t)ys * L.w + (size_t)xs;
+            float u, v;
+            flow_at(L.flow, f, plane, pix, u, v);
+            long long su = 0, sv = 0;
+            avgts_bwd_event<R, POL>(refs, f, c, tau, u, v, xs, ys, plane, L.h, L.w, q + L.image_offset,
+                                    s + L.image_offset, rec + (size_t)k * M, unit[(size_t)k * F + f], su, sv);
+            unsigned long long *dst = acc + L.sums_offset + (size_t)f * 2 * plane + pix;
+            if (su != 0) atomicAdd(dst, (unsigned long long)su);
+            if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
         }
-    }
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
 }
 
 // One thread per element of every level's grad_flow: avgts_bwd_close_kernel with the level

@@ -23,7 +23,7 @@ static_assert(sizeof(StatRow) == 32, "a statistics row is 32 bytes");
 // The corners of a warped event, a = |sig| from the reference: at every corner
 // inside the h x w images qm and sm the weight and the weight times the
 // distance, in units of 2^-32.  Every schedule of the splat calls this
-// (avgts_splat_event; an overflowing bucket of avg_timestamp_tiled.hip), and
+// (avgts_splat_event; an overflowing bucket of tiled_splat.hip), and
 // avgts_corner_units is what its tile pass adds in LDS.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void avgts_corner_units(float wy, float wx, float a, int64_t &Q, int64_t &QA)

@@ -26,8 +26,7 @@
 // At the end of the file: the term on every flow scale of the network by one
 // splat, one closing wave and one backward for all levels (sections 19-23,
 // include/dvsof_contrast_pyramid.h); the kernels above are not touched by it.
-#include "event_columns.h"
-#include "event_images_tiled.h"
+#include "tiled_splat.h"
 #include "../../include/dvsof_contrast.h"
 #include "../../include/dvsof_contrast_multi.h"
 #include "../../include/dvsof_contrast_pyramid.h"
@@ -60,27 +59,14 @@ __global__ __launch_bounds__(NT) void contrast_splat_kernel(
     const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
     unsigned long long *__restrict__ q, uint32_t *__restrict__ count)
 {
-    const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // the -1 slots of cropped and padded events
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t s = ev.sample;
+    const auto splat = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
         const size_t pix = (size_t)yi * w + (size_t)xi;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != s) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;  // a test, not a clamp; false for a NaN
-            const float tau = event_tau(te, t0, t1);
-            const float *fl = flow + (size_t)f * 2 * plane + pix;
-            const float u = fl[0], v = fl[plane];
-            splat_event<R, POL, true>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, count);
-        }
-    }
+        float u, v;
+        flow_at(flow, f, plane, pix, u, v);
+        splat_event<R, POL, true>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, count);
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
 }
 
 // 2^k: the flow gradient of a frame is summed in units of 1/unit; |G_m| <= gmax < 2^e for every image of the frame
@@ -143,57 +129,44 @@ __global__ __launch_bounds__(NT) void contrast_bwd_events_kernel(
     const int64_t *__restrict__ q, const ImageRec *__restrict__ rec, const double *__restrict__ unit,
     unsigned long long *__restrict__ acc)
 {
-    const int64_t stride = (int64_t)gridDim.x * NT;
     const size_t plane = (size_t)h * w;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t s = ev.sample;
+    const auto addends = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
         const size_t pix = (size_t)yi * w + (size_t)xi;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != s) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;
-            const float tau = event_tau(te, t0, t1);
-            const float *fl = flow + (size_t)f * 2 * plane + pix;
-            const float u = fl[0], v = fl[plane];
-            const double un = unit[f];
-            // R = 1: |ms g| < 2^(e+1) (1 + 2^-22), so |a| < 2^41 (1 + 2^-22); R > 1: at most three addends
-            // below 2^39 (1 + 2^-22) each; the product with the unit is exact
-            long long su = 0, sv = 0;
+        float u, v;
+        flow_at(flow, f, plane, pix, u, v);
+        const double un = unit[f];
+        // R = 1: |ms g| < 2^(e+1) (1 + 2^-22), so |a| < 2^41 (1 + 2^-22); R > 1: at most three addends
+        // below 2^39 (1 + 2^-22) each; the product with the unit is exact
+        long long su = 0, sv = 0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const size_t m = image_of<R, POL>(f, r, c);
-                const ImageRec a = rec[m];
-                if (a.coef == 0.0) continue;  // var(c_m) = 0: every addend would be 0
-                Warp p;
-                if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
-                const int64_t *img = q + m * plane;
-                double G[2][2];
+        for (int r = 0; r < R; ++r) {
+            const size_t m = image_of<R, POL>(f, r, c);
+            const ImageRec a = rec[m];
+            if (a.coef == 0.0) continue;  // var(c_m) = 0: every addend would be 0
+            Warp p;
+            if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
+            const int64_t *img = q + m * plane;
+            double G[2][2];
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
+            for (int j = 0; j < 2; ++j) {
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const int xx = p.cx + i, yy = p.cy + j;
-                        const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
-                        G[j][i] = in ? a.coef * ((double)img[(size_t)yy * w + (size_t)xx] * 0x1p-32 - a.mean) : 0.0;
-                    }
+                for (int i = 0; i < 2; ++i) {
+                    const int xx = p.cx + i, yy = p.cy + j;
+                    const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
+                    G[j][i] = in ? a.coef * ((double)img[(size_t)yy * w + (size_t)xx] * 0x1p-32 - a.mean) : 0.0;
                 }
-                const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
-                const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
-                const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
-                su += (long long)(ms * gx * un);
-                sv += (long long)(ms * gy * un);
             }
-            unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
-            if (su != 0) atomicAdd(dst, (unsigned long long)su);
-            if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
+            const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
+            const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
+            const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
+            su += (long long)(ms * gx * un);
+            sv += (long long)(ms * gy * un);
         }
-    }
+        unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
+        if (su != 0) atomicAdd(dst, (unsigned long long)su);
+        if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
 }
 
 // One thread per element of grad_flow: convert, clear the sum for the next
@@ -246,17 +219,6 @@ size_t multi_workspace_bytes(int F, int reference_mask, int polarity, int h, int
            dvsof_iwe_stats_workspace_bytes(pl.M, h, w);
 }
 
-// the columns as the tiled splat's launcher takes them (event_images_tiled.h)
-TiledTermColumns plain(const WireColumns &c) { return TiledTermColumns{0, c.x, c.y, c.t, c.pol, c.sample, 0}; }
-TiledTermColumns plain(const EncodedColumns &c) { return TiledTermColumns{1, c.x, c.y, c.t, c.pol, c.ev_off, c.B}; }
-
-// the tiled twins' three arguments; mode < 0: the calls that have none
-struct TiledSplat {
-    void *workspace;
-    size_t bytes;
-    int mode;
-};
-
 // dvsof_contrast_multi_fwd / _bwd on either form of the event columns (event_columns.h)
 template <class Cols>
 int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
@@ -273,8 +235,7 @@ int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const i
     if (!workspace || workspace_bytes < multi_workspace_bytes(F, reference_mask, polarity, h, w))
         return DVSOF_ENOSPACE;
     TilePlan tp;
-    const int by_tiles = tiled.mode < 0 ? 1 : tile_decide(tiled.mode, F, reference_mask, polarity, h, w, n_events,
-                                                          tiled.workspace, tiled.bytes, tp);
+    const int by_tiles = tile_decide<EventImages>(tiled, F, reference_mask, polarity, h, w, n_events, tp);
     if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
     hipStream_t st = as_stream(stream);
     const size_t pixels = (size_t)pl.M * h * w;
@@ -283,8 +244,9 @@ int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const i
     DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws.sums, 0u, sums_bytes(F, h, w), st));
     if (by_tiles == DVSOF_OK) {
-        const int rs = event_images_tiled_term_splat(plain(cols), n_events, frame_ts, frame_sample, flow, F, h, w,
-                                                     reference_mask, polarity, tp, q, count, tiled.workspace, st);
+        const int rs = TiledLaunch<EventImages>::term(plain(cols), n_events, frame_ts, frame_sample, flow, F, h, w,
+                                                      reference_mask, polarity, tp, EventImages{q, count},
+                                                      tiled.workspace, st);
         if (rs != DVSOF_OK) return rs;
     } else if (n_events > 0) {
         DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
@@ -463,32 +425,19 @@ __global__ __launch_bounds__(NT) void contrast_pyramid_splat_kernel(
     const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
     unsigned long long *__restrict__ q, uint32_t *__restrict__ count)
 {
-    const int64_t stride = (int64_t)gridDim.x * NT;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // at full resolution, before any shift
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t s = ev.sample;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != s) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;
-            const float tau = event_tau(te, t0, t1);
-            for (int k = 0; k < lv.K; ++k) {
-                const Level &L = lv.level[k];
-                const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
-                const size_t plane = (size_t)L.h * L.w;
-                const size_t pix = (size_t)ys * L.w + (size_t)xs;
-                const float *fl = L.flow + (size_t)f * 2 * plane + pix;
-                const float u = fl[0], v = fl[plane];
-                splat_event<R, POL, true>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
-                                          count + L.image_offset);
-            }
+    const auto splat = [=, &lv](int64_t xi, int64_t yi, int c, int f, float tau) {
+        for (int k = 0; k < lv.K; ++k) {
+            const Level &L = lv.level[k];
+            const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
+            const size_t plane = (size_t)L.h * L.w;
+            const size_t pix = (size_t)ys * L.w + (size_t)xs;
+            float u, v;
+            flow_at(L.flow, f, plane, pix, u, v);
+            splat_event<R, POL, true>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
+                                      count + L.image_offset);
         }
-    }
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
 }
 
 // contrast_close_kernel over the K M images and K F units of all levels (image i = k M + m,
@@ -537,6 +486,8 @@ __global__ __launch_bounds__(kWave) void contrast_pyramid_close_kernel(const dvs
     }
 }
 
+// The one kernel of the terms that writes the walk of for_each_window_event out: through the walk
+// its <3, true> instances take 74-76 VGPRs for 70, seven waves a SIMD down to six.
 template <int R, bool POL, class Cols>
 __global__ __launch_bounds__(NT) void contrast_pyramid_bwd_events_kernel(
     const Cols cols, int64_t n, const float *__restrict__ ts,
@@ -565,8 +516,8 @@ __global__ __launch_bounds__(NT) void contrast_pyramid_bwd_events_kernel(
                 const int64_t xs = xi >> L.shift, ys = yi >> L.shift;
                 const size_t plane = (size_t)lh * lw;
                 const size_t pix = (size_t)ys * lw + (size_t)xs;
-                const float *fl = L.flow + (size_t)f * 2 * plane + pix;
-                const float u = fl[0], v = fl[plane];
+                float u, v;
+                flow_at(L.flow, f, plane, pix, u, v);
                 const double un = unit[(size_t)k * F + f];
                 long long su = 0, sv = 0;  // the bounds of contrast_bwd_events_kernel, per level
 #pragma unroll

@@ -82,4 +82,33 @@ __device__ __forceinline__ bool event_channel(int sign, int &c)
     return true;
 }
 
+// The terms' frame rule, for every kernel that walks events by it (the splats and the backwards
+// of contrast.hip and avg_timestamp.hip on one scale and on all, the splats by tiles of
+// tiled_splat.hip).  One thread per event, grid-stride: an event inside the h x w frame (tested at
+// full resolution, before any level's shift) and in a channel takes part in every frame of its
+// sample whose window holds its time, both ends included.  body(xi, yi, c, f, tau): the event's
+// pixel, its channel, such a frame and the event's time within its window.
+template <bool POL, class Cols, class Body>
+__device__ __forceinline__ void for_each_window_event(const Cols &cols, int64_t n, const float *__restrict__ ts,
+                                                      const int64_t *__restrict__ frame_sample, int F, int h, int w,
+                                                      Body body)
+{
+    const int64_t stride = (int64_t)gridDim.x * kFrameNT;
+    for (int64_t e = (int64_t)blockIdx.x * kFrameNT + threadIdx.x; e < n; e += stride) {
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
+        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;  // the -1 slots of cropped and padded events
+        int c;
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t s = ev.sample;
+        for (int f = 0; f < F; ++f) {
+            if (frame_sample[f] != s) continue;
+            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
+            if (!(t0 <= te && te <= t1)) continue;  // a test, not a clamp; false for a NaN
+            body(xi, yi, c, f, event_tau(te, t0, t1));
+        }
+    }
+}
+
 }  // namespace

@@ -66,6 +66,25 @@ __device__ __forceinline__ bool event_channel(const int64_t *__restrict__ pol, i
     return true;
 }
 
+// The metric's frame rule (iwe.hip; its schedule by tiles in tiled_splat.hip): an event belongs
+// to the frame its position in the columns says (for_each_frame_event), where it lies inside
+// the h x w frame and in a channel.  body(xi, yi, c, f, tau): the event's pixel, its channel, its
+// frame and its time within the frame's window ts[2 f], ts[2 f + 1].
+template <bool POL, class Body>
+__device__ __forceinline__ void for_each_position_event(const int64_t *__restrict__ x, const int64_t *__restrict__ y,
+                                                        const float *__restrict__ t, const int64_t *__restrict__ pol,
+                                                        int64_t n, const int64_t *__restrict__ begin,
+                                                        const float *__restrict__ ts, int F, int h, int w, Body body)
+{
+    for_each_frame_event(n, begin, F, [=](int64_t e, int f) {
+        const int64_t xi = x[e], yi = y[e];
+        if (xi < 0 || xi >= w || yi < 0 || yi >= h) return;  // the -1 slots of cropped and padded events
+        int c;
+        if (!event_channel<POL>(pol, e, c)) return;
+        body(xi, yi, c, f, event_tau(t[e], ts[2 * f], ts[2 * f + 1]));
+    });
+}
+
 // The image of frame f, reference r and channel c
 template <int R, bool POL>
 __device__ __forceinline__ size_t image_of(int f, int r, int c)

@@ -141,6 +141,16 @@ inline unsigned event_blocks(int64_t n)
     return (unsigned)(blocks < kMaxEventBlocks ? blocks : kMaxEventBlocks);
 }
 
+// The flow (u, v) of frame f at pixel pix of its h x w = plane map: the one read per (event,
+// frame) of every kernel that warps events, on one scale or inside a pyramid's level loop
+__device__ __forceinline__ void flow_at(const float *__restrict__ flow, int f, size_t plane, size_t pix, float &u,
+                                        float &v)
+{
+    const float *fl = flow + (size_t)f * 2 * plane + pix;
+    u = fl[0];
+    v = fl[plane];
+}
+
 // ---------------------------------------------------------------------------
 // Warp and splat, IWE_SPEC section 2.
 // ---------------------------------------------------------------------------
@@ -159,7 +169,7 @@ __device__ __forceinline__ float event_tau(float te, float t0, float t1)
 
 // Step 6: the weights of the 2x2 footprint from the fractions fx = xw - floor(xw),
 // fy = yw - floor(yw).  fx and fy are wx[1] and wy[1], so a schedule that keeps
-// their bits (event_images_tiled.hip) gets the four weights back bit for bit.
+// their bits (tiled_splat.hip) gets the four weights back bit for bit.
 __device__ __forceinline__ void corner_weights(float fx, float fy, float (&wx)[2], float (&wy)[2])
 {
     wx[0] = 1.f - fx;

@@ -29,9 +29,10 @@
 // This file relies on -ffp-contract=off.
 #include "render_common.h"
 #include "avg_timestamp_images.h"
-#include "avg_timestamp_tiled.h"
+#include "tiled_splat.h"
 #include "../../include/dvsof_iwe_multi.h"
 #include "../../include/dvsof_iwe_avg_timestamp.h"
+#include "../../include/dvsof_event_images_tiled.h"
 #include "../../include/dvsof_avg_timestamp_tiled.h"
 
 static_assert(sizeof(dvsof_iwe_result_t) == 48, "result rows are 48 bytes (eval.py reads them as such)");
@@ -54,17 +55,13 @@ __global__ __launch_bounds__(NT) void iwe_splat_kernel(
     uint32_t *__restrict__ count)
 {
     const size_t plane = (size_t)h * w;
-    for_each_frame_event(n, begin, F, [=](int64_t e, int f) {
-        const int64_t xi = x[e], yi = y[e];
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) return;  // the -1 slots of cropped and padded events
-        int c;
-        if (!event_channel<POL>(pol, e, c)) return;
+    const auto splat = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
         const size_t pix = (size_t)yi * w + (size_t)xi;
-        const float tau = event_tau(t[e], ts[2 * f], ts[2 * f + 1]);
-        const float *fl = flow + (size_t)f * 2 * plane + pix;
-        const float u = fl[0], v = fl[plane];
+        float u, v;
+        flow_at(flow, f, plane, pix, u, v);
         splat_event<R, POL, COUNT>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, count);
-    });
+    };
+    for_each_position_event<POL>(x, y, t, pol, n, begin, ts, F, h, w, splat);
 }
 
 // The same events by the same rule, each doing to the four average-timestamp
@@ -78,17 +75,13 @@ __global__ __launch_bounds__(NT) void iwe_avgts_splat_kernel(
     unsigned long long *__restrict__ s, unsigned long long *__restrict__ base, uint32_t *__restrict__ count)
 {
     const size_t plane = (size_t)h * w;
-    for_each_frame_event(n, begin, F, [=](int64_t e, int f) {
-        const int64_t xi = x[e], yi = y[e];
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) return;  // the -1 slots of cropped and padded events
-        int c;
-        if (!event_channel<POL>(pol, e, c)) return;
+    const auto splat = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
         const size_t pix = (size_t)yi * w + (size_t)xi;
-        const float tau = event_tau(t[e], ts[2 * f], ts[2 * f + 1]);
-        const float *fl = flow + (size_t)f * 2 * plane + pix;
-        const float u = fl[0], v = fl[plane];
+        float u, v;
+        flow_at(flow, f, plane, pix, u, v);
         avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, s, base, count);
-    });
+    };
+    for_each_position_event<POL>(x, y, t, pol, n, begin, ts, F, h, w, splat);
 }
 
 // ---------------------------------------------------------------------------
@@ -224,13 +217,43 @@ AvgtsLayout avgts_layout(int h, int w, const Plan &pl)
     return o;
 }
 
-// dvsof_iwe_avg_timestamp; mode >= 0: its tiled twin (include/dvsof_avg_timestamp_tiled.h), the
-// same call with the splat by tiles where avgts_tile_decide says so
+// dvsof_iwe_splat_multi; tiled.mode >= 0: its tiled twin (include/dvsof_event_images_tiled.h), the
+// same call with the splat by tiles where tile_decide says so
+int iwe_splat_multi(const int64_t *x, const int64_t *y, const float *t, const int64_t *p, int64_t n_events,
+                    const int64_t *frame_event_begin, const float *frame_ts, const float *flow, int F, int h, int w,
+                    int reference_mask, int polarity, int64_t *q, uint32_t *count, void *stream,
+                    const TiledSplat tiled)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !q || !count || !frame_event_begin || !frame_ts || !flow) return DVSOF_EINVAL;
+    if (n_events > 0 && (!x || !y || !t || (polarity && !p))) return DVSOF_EINVAL;
+    TilePlan tp;
+    const int by_tiles = tile_decide<EventImages>(tiled, F, reference_mask, polarity, h, w, n_events, tp);
+    if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
+    hipStream_t st = as_stream(stream);
+    const size_t pixels = (size_t)pl.M * h * w;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
+    DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
+    if (by_tiles == DVSOF_OK)
+        return TiledLaunch<EventImages>::frames(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F, h, w,
+                                                reference_mask, polarity, tp, EventImages{q, count},
+                                                tiled.workspace, st);
+    if (n_events == 0) return DVSOF_OK;
+    DVSOF_REFS_POL_DISPATCH(iwe_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t, p,
+                            n_events, frame_event_begin, frame_ts, flow, F, h, w, pl.refs,
+                            (unsigned long long *)q, count);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+// dvsof_iwe_avg_timestamp; tiled.mode >= 0: its tiled twin (include/dvsof_avg_timestamp_tiled.h),
+// likewise
 int iwe_avg_timestamp(const int64_t *x, const int64_t *y, const float *t, const int64_t *p, int64_t n_events,
                       const int64_t *frame_event_begin, const float *frame_ts, const float *flow, int F, int h,
                       int w, int reference_mask, int polarity, void *images, size_t image_bytes, void *rows,
-                      void *workspace, size_t workspace_bytes, void *stream, void *tile_workspace,
-                      size_t tile_workspace_bytes, int mode)
+                      void *workspace, size_t workspace_bytes, void *stream, const TiledSplat tiled)
 {
     Plan pl;
     if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
@@ -243,8 +266,7 @@ int iwe_avg_timestamp(const int64_t *x, const int64_t *y, const float *t, const 
     if (image_bytes < lay.bytes) return DVSOF_ENOSPACE;
     if (!workspace || workspace_bytes < sizeof(StatRow) * (size_t)pl.M * nb) return DVSOF_ENOSPACE;
     TilePlan tp;
-    const int by_tiles = mode < 0 ? 1 : avgts_tile_decide(mode, F, reference_mask, polarity, h, w, n_events,
-                                                          tile_workspace, tile_workspace_bytes, tp);
+    const int by_tiles = tile_decide<AvgtsImages>(tiled, F, reference_mask, polarity, h, w, n_events, tp);
     if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
     hipStream_t st = as_stream(stream);
     char *im = (char *)images;
@@ -252,8 +274,8 @@ int iwe_avg_timestamp(const int64_t *x, const int64_t *y, const float *t, const 
     if (by_tiles == DVSOF_OK) {
         const AvgtsImages img{(int64_t *)im, (int64_t *)(im + lay.s), (int64_t *)(im + lay.base),
                               (uint32_t *)(im + lay.count)};
-        const int rs = avg_timestamp_tiled_frames_splat(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F,
-                                                        h, w, reference_mask, polarity, tp, img, tile_workspace, st);
+        const int rs = TiledLaunch<AvgtsImages>::frames(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F,
+                                                        h, w, reference_mask, polarity, tp, img, tiled.workspace, st);
         if (rs != DVSOF_OK) return rs;
     } else if (n_events > 0) {
         DVSOF_REFS_POL_DISPATCH(iwe_avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t,
@@ -306,21 +328,20 @@ int dvsof_iwe_splat_multi(const int64_t *x, const int64_t *y, const float *t, co
                           const float *flow, int F, int h, int w, int reference_mask, int polarity, int64_t *q,
                           uint32_t *count, void *stream)
 {
-    Plan pl;
-    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
-    if (F == 0) return DVSOF_OK;
-    if (bad_frame_sizes(F, h, w) || !q || !count || !frame_event_begin || !frame_ts || !flow) return DVSOF_EINVAL;
-    if (n_events > 0 && (!x || !y || !t || (polarity && !p))) return DVSOF_EINVAL;
-    hipStream_t st = as_stream(stream);
-    const size_t pixels = (size_t)pl.M * h * w;
-    DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
-    DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
-    if (n_events == 0) return DVSOF_OK;
-    DVSOF_REFS_POL_DISPATCH(iwe_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, x, y, t, p,
-                            n_events, frame_event_begin, frame_ts, flow, F, h, w, pl.refs,
-                            (unsigned long long *)q, count);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
+    return iwe_splat_multi(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F, h, w, reference_mask,
+                           polarity, q, count, stream, TiledSplat{nullptr, 0, -1});
+}
+
+// The tiled twin (include/dvsof_event_images_tiled.h)
+int dvsof_iwe_splat_multi_tiled(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                int64_t n_events, const int64_t *frame_event_begin, const float *frame_ts,
+                                const float *flow, int F, int h, int w, int reference_mask, int polarity, int64_t *q,
+                                uint32_t *count, void *stream, void *tile_workspace, size_t tile_workspace_bytes,
+                                int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return iwe_splat_multi(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F, h, w, reference_mask,
+                           polarity, q, count, stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
 }
 
 size_t dvsof_iwe_stats_workspace_bytes(int F, int h, int w)
@@ -380,7 +401,8 @@ int dvsof_iwe_avg_timestamp(const int64_t *x, const int64_t *y, const float *t, 
                             size_t image_bytes, void *rows, void *workspace, size_t workspace_bytes, void *stream)
 {
     return iwe_avg_timestamp(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F, h, w, reference_mask,
-                             polarity, images, image_bytes, rows, workspace, workspace_bytes, stream, nullptr, 0, -1);
+                             polarity, images, image_bytes, rows, workspace, workspace_bytes, stream,
+                             TiledSplat{nullptr, 0, -1});
 }
 
 // The tiled twin (include/dvsof_avg_timestamp_tiled.h)
@@ -393,8 +415,8 @@ int dvsof_iwe_avg_timestamp_tiled(const int64_t *x, const int64_t *y, const floa
 {
     if (mode != 0 && mode != 1) return DVSOF_EINVAL;
     return iwe_avg_timestamp(x, y, t, p, n_events, frame_event_begin, frame_ts, flow, F, h, w, reference_mask,
-                             polarity, images, image_bytes, rows, workspace, workspace_bytes, stream, tile_workspace,
-                             tile_workspace_bytes, mode);
+                             polarity, images, image_bytes, rows, workspace, workspace_bytes, stream,
+                             TiledSplat{tile_workspace, tile_workspace_bytes, mode});
 }
 
 int dvsof_iwe_avg_timestamp_render(const void *images, int F, int h, int w, int reference_mask, int polarity,

@@ -2,7 +2,7 @@
  * dvsof_avg_timestamp_tiled.h -- extension of the C ABI of libdvsof_hip.so
  * (dvsof.h, whose conventions hold here): the splat into the average-timestamp
  * images of dvsof_avg_timestamp.h and dvsof_iwe_avg_timestamp.h by a second
- * schedule, for dense frames (csrc/avg_timestamp_tiled.hip,
+ * schedule, for dense frames (csrc/tiled_splat.hip,
  * docs/AVG_TIMESTAMP_SPEC.md section 17, docs/IWE_SPEC.md section 23).  The
  * corner adds into q and s -- eight of an event's up to ten atomics per
  * reference -- are bucketed by the tile of the image they land in, every tile

@@ -2,7 +2,7 @@
  * dvsof_event_images_tiled.h -- extension of the C ABI of libdvsof_hip.so
  * (dvsof.h, whose conventions hold here): the splat into the images of warped
  * events of dvsof_iwe_multi.h and dvsof_contrast_multi.h by a second schedule,
- * for dense frames (csrc/event_images_tiled.hip, docs/IWE_SPEC.md section 22).
+ * for dense frames (csrc/tiled_splat.hip, docs/IWE_SPEC.md section 22).
  * Events are bucketed by the tile of the image they land in, every tile is
  * summed in LDS by one workgroup, and a touched pixel costs one global atomic
  * per tile in place of one per corner per event.

@@ -1,5 +1,5 @@
 """The tiled schedule of the splat into the average-timestamp images
-(csrc/avg_timestamp_tiled.hip, include/dvsof_avg_timestamp_tiled.h) against the
+(csrc/tiled_splat.hip, include/dvsof_avg_timestamp_tiled.h) against the
 numpy restatements the per-event kernels are pinned to
 (loss.avg_timestamp_fwd_host, eval.iwe_avg_timestamp_host), byte for byte, at
 mode 1 and from buffers of 0x5A: tile seams and ragged edges, a bucket past its

@@ -1,5 +1,5 @@
 """The tiled schedule of the splat into the images of warped events
-(csrc/event_images_tiled.hip, include/dvsof_event_images_tiled.h) against the
+(csrc/tiled_splat.hip, include/dvsof_event_images_tiled.h) against the
 numpy restatements the per-event kernels are pinned to
 (eval.iwe_splat_multi_host, loss.contrast_multi_fwd_host), byte for byte, at
 mode 1: tile seams and ragged edges, a bucket past its capacity, a refused
