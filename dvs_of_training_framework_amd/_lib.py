@@ -24,7 +24,9 @@ tests/golden/abi_signatures_iwe_avg_timestamp.json;
 _abi.EVENT_IMAGES_TILED_PATH: include/dvsof_event_images_tiled.h, recorded in
 tests/golden/abi_signatures_event_images_tiled.json;
 _abi.AVG_TIMESTAMP_TILED_PATH: include/dvsof_avg_timestamp_tiled.h, recorded in
-tests/golden/abi_signatures_avg_timestamp_tiled.json).
+tests/golden/abi_signatures_avg_timestamp_tiled.json;
+_abi.EVENT_PYRAMIDS_TILED_PATH: include/dvsof_event_pyramids_tiled.h, recorded in
+tests/golden/abi_signatures_event_pyramids_tiled.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -144,6 +146,11 @@ def declared_avg_timestamp_tiled_symbols():
     return _declared_in((_abi.AVG_TIMESTAMP_TILED_PATH,))
 
 
+def declared_event_pyramids_tiled_symbols():
+    """Names of all entry points include/dvsof_event_pyramids_tiled.h declares."""
+    return _declared_in((_abi.EVENT_PYRAMIDS_TILED_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -165,7 +172,9 @@ def lib():
                                   **_IWE_AVG_TIMESTAMP_SIGNATURES,
                                   **_EVENT_IMAGES_TILED_SIGNATURES,
                                   # include/dvsof_avg_timestamp_tiled.h: bound from its table directly
-                                  **_abi.AVG_TIMESTAMP_TILED_FUNCTIONS}.items():
+                                  **_abi.AVG_TIMESTAMP_TILED_FUNCTIONS,
+                                  # include/dvsof_event_pyramids_tiled.h: likewise
+                                  **_abi.EVENT_PYRAMIDS_TILED_FUNCTIONS}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

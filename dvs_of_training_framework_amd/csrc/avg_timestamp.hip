@@ -35,6 +35,7 @@
 #include "../../include/dvsof_avg_timestamp_pyramid.h"
 #include "../../include/dvsof_event_terms_encoded.h"
 #include "../../include/dvsof_avg_timestamp_tiled.h"
+#include "../../include/dvsof_event_pyramids_tiled.h"
 
 namespace {
 
@@ -582,17 +583,29 @@ int pyramid_check(const Cols &cols, int64_t n_events, const float *frame_ts, con
 template <class Cols>
 int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
                 int w, int reference_mask, int polarity, const Levels &levels, float *terms, float *value,
-                void *workspace, size_t workspace_bytes, void *stream)
+                void *workspace, size_t workspace_bytes, void *stream,
+                const TiledSplat tiled = TiledSplat{nullptr, 0, -1})
 {
     Plan pl;
     PyramidLayout lay;
     const int rc = pyramid_check(cols, n_events, frame_ts, frame_sample, F, h, w, reference_mask, polarity, levels,
                                  false, terms && value, workspace, workspace_bytes, pl, lay);
     if (rc != DVSOF_OK || F == 0) return rc;
+    PyramidTilePlan tp;
+    const int by_tiles =
+        pyramid_tile_decide<AvgtsImages>(tiled, F, reference_mask, polarity, h, w, levels, n_events, tp);
+    if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
     hipStream_t st = as_stream(stream);
     char *ws = (char *)workspace;
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, lay.zeroed_bytes, st));
-    if (n_events > 0) {
+    if (by_tiles == DVSOF_OK) {
+        const AvgtsImages img{(int64_t *)ws, (int64_t *)(ws + lay.s), (int64_t *)(ws + lay.base),
+                              (uint32_t *)(ws + lay.count)};
+        const int rs = TiledLaunch<AvgtsImages>::pyramid(plain(cols), n_events, frame_ts, frame_sample, F, h, w,
+                                                         reference_mask, polarity, levels, tp, img, tiled.workspace,
+                                                         st);
+        if (rs != DVSOF_OK) return rs;
+    } else if (n_events > 0) {
         DVSOF_REFS_POL_DISPATCH(avgts_pyramid_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
                                 n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
                                 (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
@@ -702,6 +715,35 @@ int dvsof_avg_timestamp_pyramid_bwd_encoded(const int16_t *x, const int16_t *y, 
 {
     return pyramid_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
                        F, h, w, reference_mask, polarity_channels, levels, workspace, workspace_bytes, seed, stream);
+}
+
+// The tiled twins (include/dvsof_event_pyramids_tiled.h): the forward above with the splat by tiles
+int dvsof_avg_timestamp_pyramid_fwd_tiled(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                          const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                          const int64_t *frame_sample, int F, int h, int w, int reference_mask,
+                                          int polarity, dvsof_contrast_levels_t levels, float *terms, float *value,
+                                          void *workspace, size_t workspace_bytes, void *stream,
+                                          void *tile_workspace, size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return pyramid_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                       reference_mask, polarity, levels, terms, value, workspace, workspace_bytes, stream,
+                       TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+}
+
+int dvsof_avg_timestamp_pyramid_fwd_encoded_tiled(const int16_t *x, const int16_t *y, const float *t,
+                                                  const uint8_t *polarity, const int64_t *sample_event_offsets,
+                                                  int B, int64_t n_events, const float *frame_ts,
+                                                  const int64_t *frame_sample, int F, int h, int w,
+                                                  int reference_mask, int polarity_channels,
+                                                  dvsof_contrast_levels_t levels, float *terms, float *value,
+                                                  void *workspace, size_t workspace_bytes, void *stream,
+                                                  void *tile_workspace, size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return pyramid_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
+                       F, h, w, reference_mask, polarity_channels, levels, terms, value, workspace, workspace_bytes,
+                       stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
 }
 
 }  // extern "C"

@@ -47,13 +47,17 @@
 // record took can be seen in the bytes.  The schedule is written once; a family
 // of images (Family below) supplies what an event adds at its own pixel, its
 // record's last column, its accumulator and its flush, all resolved at compile
-// time.  Not here: bucketing count and base by the event's own tile, an LDS
-// histogram for the reservations, the pyramid splats, the captured step.  This
-// file relies on -ffp-contract=off.
+// time.  Behind the one-level passes: the same schedule over the level table of
+// the terms on every flow scale (include/dvsof_event_pyramids_tiled.h), with
+// tiles summed in slices, reservations agreed within a wave and the own-pixel
+// sums folded from the finest level.  Not here: bucketing count and base by the
+// event's own tile at one level, an LDS histogram for the reservations, the
+// captured step.  This file relies on -ffp-contract=off.
 #include "avg_timestamp_images.h"
 #include "tiled_splat.h"
 #include "../../include/dvsof_event_images_tiled.h"
 #include "../../include/dvsof_avg_timestamp_tiled.h"
+#include "../../include/dvsof_event_pyramids_tiled.h"
 
 namespace {
 
@@ -283,7 +287,229 @@ int term_splat(const Cols &cols, int64_t n_events, const float *frame_ts, const 
     });
 }
 
+// ---------------------------------------------------------------------------
+// The schedule over a level table (the terms on every flow scale).  Three
+// things differ from the one-level passes above.  A coarse level has few
+// tiles and huge buckets, so pass 2 sums a tile in slices of kSlice records,
+// one workgroup each; integer sums let any number of workgroups flush the same
+// pixel.  Almost every lane of a wave reserves in the same one or two tiles
+// there, so the lanes that are active together agree on one cursor atomic per
+// distinct tile.  And the sums at the events' own pixels, which collide at a
+// coarse level as the corners did, are taken at the table's finest level
+// alone: which events take part and a = |tau - rho| do not depend on the level,
+// so count and base of level k at (Y, X) are the sums of the source level's
+// over the block (Y << d .., X << d ..), d = shift_k - shift_source, clipped at
+// the source's edge -- integers, exact, count modulo 2^32 either way.
+// ---------------------------------------------------------------------------
+using Levels = dvsof_contrast_levels_t;
+using Level = dvsof_contrast_level_t;
+
+struct PyramidBuckets {
+    uint32_t *cursor;  // [tiles of all levels * kCursorStride]
+    uint32_t *rec;     // per level [tiles_k][kCols][cap_k], level k at record rec_base[k]
+    PyramidTilePlan tp;
+};
+
+// One slot per calling lane in the bucket behind `cursor`, which is the same word for all lanes
+// with the same `tile`.  The lanes that are active here together take one atomic per distinct
+// tile: the first of them names its tile, those with that tile count themselves, the lowest adds
+// their number and the others stand behind it by rank.  Called under divergence (the frame walk,
+// a dropped warp), so every step is over the active lanes only.
+__device__ __forceinline__ uint32_t reserve_agreed(uint32_t *cursor, int tile)
+{
+    const unsigned lane = __lane_id();
+    uint32_t slot = 0;
+    for (bool done = false; !done;) {
+        if (tile == __builtin_amdgcn_readfirstlane(tile)) {
+            const unsigned long long peers = __ballot(1);
+            const unsigned rank = __popcll(peers & ((1ull << lane) - 1ull));
+            uint32_t first = 0;
+            if (rank == 0) first = atomicAdd(cursor, (uint32_t)__popcll(peers));
+            slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)first) + rank;  // the first active lane has rank 0
+            done = true;
+        }
+    }
+    return slot;
+}
+
+// bucket_event at level k of the table: the own-pixel adds at the source level only, the record
+// into the bucket of the level's destination tile
+template <int R, bool POL, class Fam>
+__device__ __forceinline__ void bucket_level_event(const PyramidBuckets &bk, int k, const Level &L, const Fam &fam,
+                                                   const Refs &refs, int f, int c, float tau, int64_t xi, int64_t yi)
+{
+    const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
+    const size_t plane = (size_t)L.h * L.w;
+    const size_t pix = (size_t)ys * L.w + (size_t)xs;
+    float u, v;
+    flow_at(L.flow, f, plane, pix, u, v);
+    const int TX = bk.tp.TX[k], TY = bk.tp.TY[k], cap = bk.tp.cap[k];
+    const bool agree = TX * TY <= kAggregateTiles;  // the same for the whole wave
+    const bool own = k == bk.tp.source;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const size_t m = image_of<R, POL>(f, r, c);
+        const float a = fabsf(tau - refs.rho[r]);
+        if (own) fam.own_pixel(L.image_offset + m * plane + pix, a);
+        Warp p;
+        if (!warp_event_to(tau, refs.rho[r], u, v, xs, ys, L.h, L.w, p)) continue;
+        const int tx = max(p.cx, 0) / kTileW, ty = max(p.cy, 0) / kTileH;
+        const int in_level = ((int)m * TY + ty) * TX + tx;  // below tiles[k] <= 8192
+        const int tile = bk.tp.tile_base[k] + in_level;
+        uint32_t *cursor = bk.cursor + (size_t)tile * kCursorStride;
+        const uint32_t slot = agree ? reserve_agreed(cursor, tile) : atomicAdd(cursor, 1u);
+        if (slot < (uint32_t)cap) {
+            uint32_t *rec = bk.rec + (bk.tp.rec_base[k] + (size_t)in_level * cap) * Fam::kCols + slot;
+            rec[0] = (uint32_t)(p.cx - tx * kTileW + 1) | (uint32_t)(p.cy - ty * kTileH + 1) << 16;
+            rec[cap] = __float_as_uint(p.wx[1]);
+            rec[2 * cap] = __float_as_uint(p.wy[1]);
+            if constexpr (Fam::kCols == 4) rec[3 * cap] = __float_as_uint(a);
+        } else {
+            fam.overflowed(p, a, L.h, L.w, L.image_offset + m * plane);
+        }
+    }
+}
+
+// Pass 1 over the table: one walk by the terms' frame rule, the levels a loop inside it
+template <int R, bool POL, class Fam, class Cols>
+__global__ __launch_bounds__(NT) void bucket_pyramid_kernel(const Cols cols, int64_t n, const float *__restrict__ ts,
+                                                            const int64_t *__restrict__ frame_sample, int F, int h,
+                                                            int w, Refs refs, const Levels lv,
+                                                            const PyramidBuckets bk, Fam fam)
+{
+    const auto bucket = [=, &lv, &bk](int64_t xi, int64_t yi, int c, int f, float tau) {
+#pragma unroll 1
+        for (int k = 0; k < lv.K; ++k) bucket_level_event<R, POL>(bk, k, lv.level[k], fam, refs, f, c, tau, xi, yi);
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, bucket);
+}
+
+// Pass 2 over the table: workgroup = (level, tile, slice of kSlice records), tile_sum_kernel on
+// its slice.  A slice past the cursor has nothing to do.
+template <class Fam>
+__global__ __launch_bounds__(NT) void slice_sum_kernel(const PyramidBuckets bk, const Levels lv, Fam fam)
+{
+    using Acc = typename Fam::Acc;
+    int k = 0;
+    while (k + 1 < bk.tp.K && (int)blockIdx.x >= bk.tp.block_base[k + 1]) ++k;
+    const int slices = bk.tp.slices[k], cap = bk.tp.cap[k], TX = bk.tp.TX[k], TY = bk.tp.TY[k];
+    const int local = (int)blockIdx.x - bk.tp.block_base[k];
+    const int in_level = local / slices;
+    const uint32_t n = min(bk.cursor[(size_t)(bk.tp.tile_base[k] + in_level) * kCursorStride], (uint32_t)cap);
+    const uint32_t from = (uint32_t)(local % slices) * kSlice;
+    if (from >= n) return;
+    const uint32_t to = min(n, from + kSlice);
+    const Level &L = lv.level[k];
+    const int h = L.h, w = L.w;
+    __shared__ Acc acc[kAccH * kAccW];
+    for (int i = threadIdx.x; i < kAccH * kAccW; i += NT) acc[i] = Fam::zero();
+    __syncthreads();
+    const int per_image = TX * TY, in_image = in_level % per_image;
+    const int x0 = in_image % TX * kTileW, y0 = in_image / TX * kTileH;
+    const uint32_t *rec = bk.rec + (bk.tp.rec_base[k] + (size_t)in_level * cap) * Fam::kCols;
+    for (uint32_t e = from + threadIdx.x; e < to; e += NT) {
+        const uint32_t corner = rec[e];
+        const float fx = __uint_as_float(rec[cap + e]), fy = __uint_as_float(rec[2 * cap + e]);
+        float a = 0.f;
+        if constexpr (Fam::kCols == 4) a = __uint_as_float(rec[3 * cap + e]);
+        const int lx = (int)(corner & 0xffffu) - 1, ly = (int)(corner >> 16) - 1;  // in [-1, side - 1]
+        float wx[2], wy[2];
+        corner_weights(fx, fy, wx, wy);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int ax = lx + i, ay = ly + j;  // in [-1, side]; -1 only outside the image
+                const int xx = x0 + ax, yy = y0 + ay;
+                if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
+                Fam::add(acc + ay * kAccW + ax, wy[j], wx[i], a);
+            }
+        }
+    }
+    __syncthreads();
+    const size_t image = L.image_offset + (size_t)(in_level / per_image) * ((size_t)h * w);
+    for (int i = threadIdx.x; i < kAccH * kAccW; i += NT) {
+        const int xx = x0 + i % kAccW, yy = y0 + i / kAccW;
+        if (xx < w && yy < h) fam.flush(acc[i], image + (size_t)yy * w + (size_t)xx);
+    }
+}
+
+// The fold: one thread per pixel of every image of every level but the source, which sums the
+// source level's count (and base) over its block.  No atomics: nothing else writes these pixels.
+template <class Fam>
+__global__ __launch_bounds__(NT) void fold_own_pixels_kernel(const Levels lv, int source, size_t M, size_t total,
+                                                             Fam fam)
+{
+    const size_t stride = (size_t)gridDim.x * NT;
+    const Level &S = lv.level[source];
+    const size_t src_plane = (size_t)S.h * S.w;
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < total; i += stride) {
+        int k = 0;
+        while (k + 1 < lv.K && i >= lv.level[k + 1].image_offset) ++k;
+        if (k == source) continue;
+        const Level &L = lv.level[k];
+        const size_t local = i - L.image_offset, plane = (size_t)L.h * L.w;
+        const size_t m = local / plane, pix = local % plane;
+        const int Y = (int)(pix / L.w), X = (int)(pix % L.w), d = L.shift - S.shift;
+        const int y1 = min((Y + 1) << d, S.h), x1 = min((X + 1) << d, S.w);
+        const size_t from = S.image_offset + m * src_plane;
+        uint32_t n = 0;
+        unsigned long long b = 0;
+        for (int y = Y << d; y < y1; ++y) {
+            for (int x = X << d; x < x1; ++x) {
+                const size_t at = from + (size_t)y * S.w + (size_t)x;
+                n += fam.count[at];
+                if constexpr (Fam::kCols == 4) b += fam.base[at];
+            }
+        }
+        fam.count[i] = n;
+        if constexpr (Fam::kCols == 4) fam.base[i] = b;
+    }
+}
+
+// the cursors cleared, pass 1, the fold and pass 2 of a term over a level table
+template <class Fam, class Cols>
+int pyramid_splat(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
+                  int w, const Plan &pl, const Levels &lv, const PyramidTilePlan &tp, const Fam &fam,
+                  void *tile_workspace, hipStream_t st)
+{
+    const PyramidBuckets bk{(uint32_t *)tile_workspace,
+                            (uint32_t *)((char *)tile_workspace + pyramid_cursor_bytes(tp)), tp};
+    DVSOF_HIP_TRY((hipError_t)fill_u32(bk.cursor, 0u, pyramid_cursor_bytes(tp), st));
+    DVSOF_REFS_POL_DISPATCH(bucket_pyramid_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols, n_events,
+                            frame_ts, frame_sample, F, h, w, pl.refs, lv, bk, fam);
+    DVSOF_LAUNCH_CHECK();
+    if (lv.K > 1) {
+        const Level &last = lv.level[lv.K - 1];
+        const size_t total = last.image_offset + (size_t)pl.M * last.h * last.w;
+        hipLaunchKernelGGL(fold_own_pixels_kernel<Fam>, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st, lv,
+                           tp.source, (size_t)pl.M, total, fam);
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(slice_sum_kernel<Fam>, dim3((unsigned)tp.block_base[tp.K]), dim3(NT), 0, st, bk, lv, fam);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
 }  // namespace
+
+template <class Images>
+int TiledLaunch<Images>::pyramid(const TiledTermColumns &c, int64_t n_events, const float *frame_ts,
+                                 const int64_t *frame_sample, int F, int h, int w, int reference_mask, int polarity,
+                                 const dvsof_contrast_levels_t &levels, const PyramidTilePlan &tp, const Images &img,
+                                 void *tile_workspace, hipStream_t stream)
+{
+    Plan pl;
+    if (!plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    const Family<Images> fam(img);
+    if (c.encoded)
+        return pyramid_splat(EncodedColumns{(const int16_t *)c.x, (const int16_t *)c.y, c.t, (const uint8_t *)c.pol,
+                                            c.sample, c.B},
+                             n_events, frame_ts, frame_sample, F, h, w, pl, levels, tp, fam, tile_workspace, stream);
+    return pyramid_splat(WireColumns{(const int64_t *)c.x, (const int64_t *)c.y, c.t, (const int64_t *)c.pol,
+                                     c.sample},
+                         n_events, frame_ts, frame_sample, F, h, w, pl, levels, tp, fam, tile_workspace, stream);
+}
 
 template <class Images>
 int TiledLaunch<Images>::term(const TiledTermColumns &c, int64_t n_events, const float *frame_ts,
@@ -347,6 +573,44 @@ size_t dvsof_avg_timestamp_tiled_workspace_bytes(int F, int reference_mask, int 
 {
     TilePlan tp;
     return tile_plan(F, reference_mask, polarity, h, w, n_events, tp) ? tile_workspace_bytes<AvgtsImages>(tp) : 0;
+}
+
+// include/dvsof_event_pyramids_tiled.h: the plan over a level table
+int dvsof_event_pyramids_tiled_plan(int F, int reference_mask, int polarity, int h, int w,
+                                    dvsof_contrast_levels_t levels, int64_t n_events, int32_t *out)
+{
+    PyramidTilePlan tp;
+    if (!out || !pyramid_tile_plan(F, reference_mask, polarity, h, w, levels, n_events, tp)) return 0;
+    out[0] = kTileW;
+    out[1] = kTileH;
+    out[2] = tp.tile_base[tp.K];
+    out[3] = kSlice;
+    out[4] = kAggregateTiles;
+    out[5] = tp.source;
+    for (int k = 0; k < tp.K; ++k) {
+        out[6 + 3 * k] = tp.tiles[k];
+        out[7 + 3 * k] = tp.cap[k];
+        out[8 + 3 * k] = tp.slices[k];
+    }
+    return 1;
+}
+
+size_t dvsof_contrast_pyramid_tiled_workspace_bytes(int F, int reference_mask, int polarity, int h, int w,
+                                                    dvsof_contrast_levels_t levels, int64_t n_events)
+{
+    PyramidTilePlan tp;
+    return pyramid_tile_plan(F, reference_mask, polarity, h, w, levels, n_events, tp)
+               ? pyramid_tile_workspace_bytes<EventImages>(tp)
+               : 0;
+}
+
+size_t dvsof_avg_timestamp_pyramid_tiled_workspace_bytes(int F, int reference_mask, int polarity, int h, int w,
+                                                         dvsof_contrast_levels_t levels, int64_t n_events)
+{
+    PyramidTilePlan tp;
+    return pyramid_tile_plan(F, reference_mask, polarity, h, w, levels, n_events, tp)
+               ? pyramid_tile_workspace_bytes<AvgtsImages>(tp)
+               : 0;
 }
 
 }  // extern "C"

@@ -556,6 +556,17 @@ def avg_timestamp_tiled_workspace(F, mask, polarity, h, w, n_events, device):
     return torch.empty((nbytes + 7) // 8, dtype=torch.long, device=device), nbytes
 
 
+def event_pyramids_tiled_workspace(family, F, mask, polarity, h, w, table, n_events, device):
+    """``event_images_tiled_workspace`` for the tiled calls over a level table
+    (include/dvsof_event_pyramids_tiled.h).  family: 'contrast' or
+    'avg_timestamp'; table: the level table of the call."""
+    size = getattr(_lib.lib(), f'dvsof_{family}_pyramid_tiled_workspace_bytes')
+    nbytes = size(F, mask, int(polarity), h, w, table, n_events)
+    if not nbytes:
+        return None, 0
+    return torch.empty((nbytes + 7) // 8, dtype=torch.long, device=device), nbytes
+
+
 def iwe_splat_multi(events, win_out, frame_ts, flow, references=('start',), polarity=False, tiled=False):
     """``iwe_splat`` at several reference times of the window and with ON and
     OFF events apart (csrc/iwe.hip, IWE_SPEC sections 8-13).  events,

@@ -740,11 +740,17 @@ class _ContrastPyramid(torch.autograd.Function):
     """(sum_k weight_k term_k, terms [K]) of all flows; the gradient of the
     first enters every flow (dvsof_contrast_pyramid_fwd /
     dvsof_contrast_pyramid_bwd: one splat and one backward for all levels).
-    The weights are applied inside the kernels."""
+    The weights are applied inside the kernels.  A last argument behind the
+    flows that is no tensor is ``tiled``: the forward's splat by the tiled
+    schedule over the level table (dvsof_contrast_pyramid_fwd_tiled, mode
+    ``eval.event_images_tiled_mode(tiled)``): the same workspace, so the same
+    backward."""
 
     @staticmethod
     def forward(ctx, x, y, t, p, sample_index, frame_ts, frame_sample, shape, weights, mask, polarity, *flows):
         from .eval import IWE_RESULT_DTYPE
+        ctx.tiled = None if torch.is_tensor(flows[-1]) else flows[-1]
+        flows = flows if ctx.tiled is None else flows[:-1]
         dev = flows[0].device
         flows = tuple(f.detach().contiguous().float() for f in flows)
         K, F = len(flows), flows[0].shape[0]
@@ -766,9 +772,17 @@ class _ContrastPyramid(torch.autograd.Function):
         ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
         ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
                        F, h, w, mask, int(polarity)])
-        _lib.check(getattr(lib, 'dvsof_contrast_pyramid_fwd' + ctx.form)(
-            *ctx.args, table, result.data_ptr(), terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes,
-            _lib.stream()), 'dvsof_contrast_pyramid_fwd' + ctx.form)
+        out = (table, result.data_ptr(), terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes, _lib.stream())
+        if ctx.tiled is not None:
+            from .eval import event_images_tiled_mode, event_pyramids_tiled_workspace
+            name = 'dvsof_contrast_pyramid_fwd' + ctx.form + '_tiled'
+            tiles, tile_bytes = event_pyramids_tiled_workspace('contrast', F, mask, polarity, h, w, table,
+                                                               cols[0].numel(), dev)
+            _lib.check(getattr(lib, name)(*ctx.args, *out, _lib.ptr(tiles), tile_bytes,
+                                          event_images_tiled_mode(ctx.tiled)), name)
+        else:
+            _lib.check(getattr(lib, 'dvsof_contrast_pyramid_fwd' + ctx.form)(*ctx.args, *out),
+                       'dvsof_contrast_pyramid_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flows, ws, nbytes, table)
         ctx.mark_non_differentiable(terms)
         ctx.set_materialize_grads(False)
@@ -778,7 +792,7 @@ class _ContrastPyramid(torch.autograd.Function):
     def backward(ctx, g_value, _g_terms):
         flows, ws, nbytes, table = ctx.held[3:]
         if g_value is None:
-            return (None,) * (11 + len(flows))
+            return (None,) * (11 + len(flows) + (ctx.tiled is not None))
         grads = tuple(torch.empty_like(f) for f in flows)
         for k, g in enumerate(grads):
             table.level[k].grad_flow = g.data_ptr()
@@ -786,7 +800,7 @@ class _ContrastPyramid(torch.autograd.Function):
         _lib.check(getattr(_lib.lib(), 'dvsof_contrast_pyramid_bwd' + ctx.form)(
             *ctx.args, table, ws.data_ptr(), nbytes, seed.data_ptr(), _lib.stream()),
             'dvsof_contrast_pyramid_bwd' + ctx.form)
-        return (None,) * 11 + grads
+        return (None,) * 11 + grads + (None,) * (ctx.tiled is not None)
 
 
 # ---------------------------------------------------------------------------
@@ -1081,10 +1095,14 @@ class _AvgTimestampPyramid(torch.autograd.Function):
     first enters every flow (dvsof_avg_timestamp_pyramid_fwd /
     dvsof_avg_timestamp_pyramid_bwd: one splat and one backward for all
     levels).  The images live in the workspace; the weights are applied inside
-    the kernels."""
+    the kernels.  A last argument behind the flows that is no tensor is
+    ``tiled``, as for ``_ContrastPyramid``
+    (dvsof_avg_timestamp_pyramid_fwd_tiled)."""
 
     @staticmethod
     def forward(ctx, x, y, t, p, sample_index, frame_ts, frame_sample, shape, weights, mask, polarity, *flows):
+        ctx.tiled = None if torch.is_tensor(flows[-1]) else flows[-1]
+        flows = flows if ctx.tiled is None else flows[:-1]
         dev = flows[0].device
         flows = tuple(f.detach().contiguous().float() for f in flows)
         K, F = len(flows), flows[0].shape[0]
@@ -1105,9 +1123,17 @@ class _AvgTimestampPyramid(torch.autograd.Function):
         ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
         ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
                        F, h, w, mask, int(polarity)])
-        _lib.check(getattr(lib, 'dvsof_avg_timestamp_pyramid_fwd' + ctx.form)(
-            *ctx.args, table, terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
-            'dvsof_avg_timestamp_pyramid_fwd' + ctx.form)
+        out = (table, terms.data_ptr(), value.data_ptr(), ws.data_ptr(), nbytes, _lib.stream())
+        if ctx.tiled is not None:
+            from .eval import event_images_tiled_mode, event_pyramids_tiled_workspace
+            name = 'dvsof_avg_timestamp_pyramid_fwd' + ctx.form + '_tiled'
+            tiles, tile_bytes = event_pyramids_tiled_workspace('avg_timestamp', F, mask, polarity, h, w, table,
+                                                               cols[0].numel(), dev)
+            _lib.check(getattr(lib, name)(*ctx.args, *out, _lib.ptr(tiles), tile_bytes,
+                                          event_images_tiled_mode(ctx.tiled)), name)
+        else:
+            _lib.check(getattr(lib, 'dvsof_avg_timestamp_pyramid_fwd' + ctx.form)(*ctx.args, *out),
+                       'dvsof_avg_timestamp_pyramid_fwd' + ctx.form)
         ctx.held = (cols, pol, tables, flows, ws, nbytes, table)
         ctx.mark_non_differentiable(terms)
         ctx.set_materialize_grads(False)
@@ -1117,7 +1143,7 @@ class _AvgTimestampPyramid(torch.autograd.Function):
     def backward(ctx, g_value, _g_terms):
         flows, ws, nbytes, table = ctx.held[3:]
         if g_value is None:
-            return (None,) * (11 + len(flows))
+            return (None,) * (11 + len(flows) + (ctx.tiled is not None))
         grads = tuple(torch.empty_like(f) for f in flows)
         for k, g in enumerate(grads):
             table.level[k].grad_flow = g.data_ptr()
@@ -1125,7 +1151,7 @@ class _AvgTimestampPyramid(torch.autograd.Function):
         _lib.check(getattr(_lib.lib(), 'dvsof_avg_timestamp_pyramid_bwd' + ctx.form)(
             *ctx.args, table, ws.data_ptr(), nbytes, seed.data_ptr(), _lib.stream()),
             'dvsof_avg_timestamp_pyramid_bwd' + ctx.form)
-        return (None,) * 11 + grads
+        return (None,) * 11 + grads + (None,) * (ctx.tiled is not None)
 
 
 class Loss:
@@ -1289,14 +1315,14 @@ class Losses:
         tiled: True or 'force' (``eval.event_images_tiled_mode``): the
         forward's splat by the tiled schedule for dense frames
         (include/dvsof_event_images_tiled.h): the same images, so the same term
-        and gradient, bit for bit.  Not with scales='all', whose splat has no
-        tiled form.  False, the default: the calls above."""
-        if tiled and scales != 'finest':
-            raise ValueError('tiled has no form for scales=\'all\': the pyramid\'s splat is per event')
+        and gradient, bit for bit.  With scales='all' the schedule runs over the
+        level table (include/dvsof_event_pyramids_tiled.h, CONTRAST_SPEC section
+        25).  False, the default: the calls above."""
         if scales != 'finest':
             if scales not in CONTRAST_SCALES:
                 raise ValueError(f'unknown contrast scales "{scales}": one of {", ".join(CONTRAST_SCALES)}')
-            return self._contrast_all(flows, flow_ts, flow_sample_idx, events, weight, references, polarity)
+            return self._event_term_all(_ContrastPyramid, flows, flow_ts, flow_sample_idx, events, weight,
+                                        references, polarity, tiled)
         flow = flows[-1]
         assert tuple(flow.shape[-2:]) == self.shapes[-1] and flow.shape[1] == 2, \
             f'flow of size {tuple(flow.shape)} given to the contrast term of scale {self.shapes[-1]}'
@@ -1370,19 +1396,36 @@ class Losses:
         the levels' unweighted terms detached for logging.  A level that is no
         halving of the finest is refused (``contrast_level_shift``).
         'finest', the default, is ``avg_timestamp`` and constructs nothing
-        else; any other name raises ValueError."""
+        else; any other name raises ValueError.  The splat by tiles is
+        ``avg_timestamp_scales_tiled``."""
+        return self.avg_timestamp_scales_tiled(flows, flow_ts, flow_sample_idx, events, weight, references,
+                                               polarity, scales, False)
+
+    def avg_timestamp_scales_tiled(self, flows, flow_ts, flow_sample_idx, events, weight=None,
+                                   references=('start', 'end'), polarity=False, scales='finest', tiled=True):
+        """``avg_timestamp_scales`` with the choice of the splat's schedule (a
+        method of its own: the signature of ``avg_timestamp_scales`` is held as
+        it is, like that of ``avg_timestamp``).  tiled: True or 'force'
+        (``eval.event_images_tiled_mode``): the forward's splat by the tiled
+        schedule, over the level table with scales='all'
+        (include/dvsof_event_pyramids_tiled.h, AVG_TIMESTAMP_SPEC section 18),
+        as ``avg_timestamp_tiled`` with 'finest': the same bits.  False is
+        ``avg_timestamp_scales`` and constructs nothing else."""
         if scales == 'finest':
+            if tiled:
+                return self.avg_timestamp_tiled(flows, flow_ts, flow_sample_idx, events, weight, references,
+                                                polarity, tiled)
             return self.avg_timestamp(flows, flow_ts, flow_sample_idx, events, weight, references, polarity)
         if scales not in AVG_TIMESTAMP_SCALES:
             raise ValueError(f'unknown avg-timestamp scales "{scales}": one of {", ".join(AVG_TIMESTAMP_SCALES)}')
         return self._event_term_all(_AvgTimestampPyramid, flows, flow_ts, flow_sample_idx, events, weight,
-                                    references, polarity)
+                                    references, polarity, tiled)
 
-    def _contrast_all(self, flows, flow_ts, flow_sample_idx, events, weight, references, polarity):
-        return self._event_term_all(_ContrastPyramid, flows, flow_ts, flow_sample_idx, events, weight,
-                                    references, polarity)
-
-    def _event_term_all(self, function, flows, flow_ts, flow_sample_idx, events, weight, references, polarity):
+    def _event_term_all(self, function, flows, flow_ts, flow_sample_idx, events, weight, references, polarity,
+                        tiled=False):
+        if tiled:
+            from .eval import event_images_tiled_mode
+            event_images_tiled_mode(tiled)              # ValueError for anything but True and 'force'
         self._check_flows(flows)
         *cols, pol, sample = _term_columns(events, polarity)
         cols.append(sample)
@@ -1393,7 +1436,8 @@ class Losses:
         weights = contrast_level_weights(1.0 if weight is None else weight, len(flows))
         _lib.require_cuda(pol)
         value, terms = function.apply(*cols[:3], pol, cols[3], flow_ts, flow_sample_idx,
-                                      self.shapes[-1], weights, mask, bool(polarity), *flows)
+                                      self.shapes[-1], weights, mask, bool(polarity), *flows,
+                                      *((tiled,) if tiled else ()))
         return value if weight is None else (value, terms)
 
 

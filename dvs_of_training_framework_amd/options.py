@@ -398,6 +398,17 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'whether it pays (include/dvsof_avg_timestamp_tiled.h).  Not with '
                              '--avg-timestamp-scales all or --capture-event-terms, which have no '
                              'tiled form')
+    parser.add_argument('--event-pyramids-tiled', dest='event_pyramids_tiled',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='with --contrast-scales all or --avg-timestamp-scales all (and the '
+                             'term\'s weight): the splat of those terms by the tiled schedule over '
+                             'all flow scales: one walk of the events buckets them by image tile '
+                             'of every level, a tile is summed in LDS in slices, and the sums at '
+                             'the events\' own pixels are taken at the finest level and folded into '
+                             'the others; the same images bit for bit '
+                             '(include/dvsof_event_pyramids_tiled.h).  The kernels decide by the '
+                             'event count whether it pays (from 64 000 events a batch on, for either term).  Not with '
+                             '--capture-event-terms, which has no tiled form')
     parser.add_argument('--compact-event-terms', dest='compact_event_terms',
                         default=argparse.SUPPRESS, action='store_true',
                         help='with --compact-events and a positive --contrast-weight or '
@@ -483,9 +494,27 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_avg_timestamp_tiled_args(validate_event_images_tiled_args(validate_compact_event_terms_args(
-        validate_capture_event_terms_args(validate_frameless_args(
-            validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args))))))))
+    return validate_event_pyramids_tiled_args(validate_avg_timestamp_tiled_args(validate_event_images_tiled_args(
+        validate_compact_event_terms_args(validate_capture_event_terms_args(validate_frameless_args(
+            validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args)))))))))
+
+
+def validate_event_pyramids_tiled_args(args):
+    """--event-pyramids-tiled (absent from ``args`` unless given) against what
+    it needs, a term on every flow scale, and against the captured step, which
+    has no tiled form."""
+    if not getattr(args, 'event_pyramids_tiled', False):
+        return args
+    if getattr(args, 'capture_event_terms', False):
+        raise SystemExit('--event-pyramids-tiled cannot be combined with --capture-event-terms: its splat has '
+                         'no tiled form')
+    contrast = getattr(args, 'contrast_weight', 0.0) > 0 and getattr(args, 'contrast_scales', 'finest') == 'all'
+    avg = getattr(args, 'avg_timestamp_weight', 0.0) > 0 and getattr(args, 'avg_timestamp_scales', 'finest') == 'all'
+    if not (contrast or avg):
+        raise SystemExit('--event-pyramids-tiled needs --contrast-weight with --contrast-scales all, or '
+                         '--avg-timestamp-weight with --avg-timestamp-scales all: without either no term runs '
+                         'on every flow scale')
+    return args
 
 
 def validate_avg_timestamp_tiled_args(args):

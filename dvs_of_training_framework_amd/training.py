@@ -114,7 +114,7 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   frame_indices=None, contrast_weight=0.0, events=None,
                   contrast_references=('start',), contrast_polarity=False,
                   contrast_scales='finest', avg_timestamp_scales='finest',
-                  contrast_tiled=False, avg_timestamp_tiled=False,
+                  contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
                   avg_timestamp_weight=0.0,
                   avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                   avg_timestamp_polarity=False):
@@ -150,6 +150,13 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     schedule for dense frames (``Losses.avg_timestamp_tiled``, the same bits;
     not with avg_timestamp_scales='all': ValueError); False, the default,
     passes nothing on.
+
+    event_pyramids_tiled: True or 'force': the splat of whichever of the two
+    terms runs with scales='all' by the tiled schedule over the level table
+    (``Losses.contrast(scales='all', tiled=)``,
+    ``Losses.avg_timestamp_scales_tiled``; the same bits); a term on the
+    finest flow alone is not touched by it.  False, the default, passes
+    nothing on.
 
     images=None with an evaluator that has ``frameless`` (loss.Losses): a
     frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
@@ -190,10 +197,10 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         if events is None:
             raise ValueError('contrast_weight > 0 needs the raw events of the batch on the device '
                              '(is_raw=True); preprocessed voxel grids carry none')
-        value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events,
-                                         weight=contrast_weight, **_contrast_options(
-                                             contrast_references, contrast_polarity, contrast_scales,
-                                             contrast_tiled))
+        options = _contrast_options(contrast_references, contrast_polarity, contrast_scales, contrast_tiled)
+        if event_pyramids_tiled and 'scales' in options:
+            options['tiled'] = event_pyramids_tiled
+        value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events, weight=contrast_weight, **options)
         loss = loss + value
     if avg_timestamp_weight:
         if avg_timestamp_weight < 0:
@@ -206,7 +213,10 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         if 'scales' in options and 'tiled' in options:
             raise ValueError('avg_timestamp_tiled has no form for avg_timestamp_scales=\'all\': the pyramid\'s '
                              'splat is per event')
-        method = evaluator.avg_timestamp_scales if 'scales' in options else \
+        if event_pyramids_tiled and 'scales' in options:
+            options['tiled'] = event_pyramids_tiled
+        method = evaluator.avg_timestamp_scales_tiled if 'scales' in options and 'tiled' in options else \
+            evaluator.avg_timestamp_scales if 'scales' in options else \
             evaluator.avg_timestamp_tiled if 'tiled' in options else evaluator.avg_timestamp
         value, avg_term = method(flows, flow_ts, flow_sample_idx, events, weight=avg_timestamp_weight, **options)
         loss = loss + value
@@ -325,7 +335,7 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       weights, return_prediction=False, contrast_weight=0.0,
                       contrast_references=('start',), contrast_polarity=False,
                       contrast_scales='finest', avg_timestamp_scales='finest',
-                      contrast_tiled=False, avg_timestamp_tiled=False,
+                      contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
                       avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
@@ -346,6 +356,8 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
         raise ValueError('avg_timestamp_weight > 0 needs raw events (is_raw=True)')
     if avg:
         contrast = dict(contrast, **avg)
+    if event_pyramids_tiled and contrast:       # the tiled splat of the terms that run on every scale
+        contrast = dict(contrast, event_pyramids_tiled=event_pyramids_tiled)
     with _timed(timers, 'batch2gpu'):
         timestamps, sample_idx, images, payload = _to_device(batch, device,
                                                              is_raw)
@@ -586,8 +598,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           contrast_weight: float = 0.0, contrast_references=('start',),
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
           capture_event_terms: bool = False, avg_timestamp_scales: str = 'finest',
-          contrast_tiled=False, avg_timestamp_tiled=False, avg_timestamp_weight: float = 0.0,
-          avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+          contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
+          avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
@@ -641,6 +653,12 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                (``loss.Losses.avg_timestamp_tiled``): not with
                avg_timestamp_scales='all' and not in a step captured with
                ``capture_event_terms`` (ValueError)
+    event_pyramids_tiled:  True or 'force': the splat of whichever of the two
+               terms runs on every flow scale (contrast_scales='all',
+               avg_timestamp_scales='all') by the tiled schedule over the
+               level table (``combined_loss``; the same bits).  Needs one of
+               them, and not in a step captured with ``capture_event_terms``
+               (ValueError).  (By name)
     avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
                the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
                events only), logged as ``Train/avg timestamp``, beside the
@@ -689,6 +707,13 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                                                          or avg_timestamp_scales != 'finest'):
         raise ValueError('avg_timestamp_tiled has no form for avg_timestamp_scales=\'all\' or a step captured '
                          'with capture_event_terms')
+    if event_pyramids_tiled:
+        if not ((contrast_weight and contrast_scales == 'all')
+                or (avg_timestamp_weight and avg_timestamp_scales == 'all')):
+            raise ValueError('event_pyramids_tiled needs a term on every flow scale: contrast_scales=\'all\' or '
+                             'avg_timestamp_scales=\'all\' with its weight')
+        if capture and capture_event_terms:
+            raise ValueError('event_pyramids_tiled has no form for a step captured with capture_event_terms')
     if capture and capture_event_terms:
         event_terms = dict(
             _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales),
@@ -744,7 +769,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
                                      contrast_scales, contrast_tiled),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
-                                          avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled))
+                                          avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled),
+                **({'event_pyramids_tiled': event_pyramids_tiled} if event_pyramids_tiled else {}))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass

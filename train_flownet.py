@@ -537,7 +537,9 @@ def main(argv=None):
                   **({'contrast_tiled': True} if getattr(args, 'event_images_tiled', False)
                      and getattr(args, 'contrast_weight', 0.0) else {}),
                   **({'capture_event_terms': True}
-                     if getattr(args, 'capture_event_terms', False) else {}))
+                     if getattr(args, 'capture_event_terms', False) else {}),
+                  **({'event_pyramids_tiled': True}
+                     if getattr(args, 'event_pyramids_tiled', False) else {}))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
