@@ -26,7 +26,9 @@ tests/golden/abi_signatures_event_images_tiled.json;
 _abi.AVG_TIMESTAMP_TILED_PATH: include/dvsof_avg_timestamp_tiled.h, recorded in
 tests/golden/abi_signatures_avg_timestamp_tiled.json;
 _abi.EVENT_PYRAMIDS_TILED_PATH: include/dvsof_event_pyramids_tiled.h, recorded in
-tests/golden/abi_signatures_event_pyramids_tiled.json).
+tests/golden/abi_signatures_event_pyramids_tiled.json;
+_abi.EVENT_TERMS_JOINT_PATH: include/dvsof_event_terms_joint.h, recorded in
+tests/golden/abi_signatures_event_terms_joint.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -151,6 +153,11 @@ def declared_event_pyramids_tiled_symbols():
     return _declared_in((_abi.EVENT_PYRAMIDS_TILED_PATH,))
 
 
+def declared_event_terms_joint_symbols():
+    """Names of all entry points include/dvsof_event_terms_joint.h declares."""
+    return _declared_in((_abi.EVENT_TERMS_JOINT_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -174,7 +181,9 @@ def lib():
                                   # include/dvsof_avg_timestamp_tiled.h: bound from its table directly
                                   **_abi.AVG_TIMESTAMP_TILED_FUNCTIONS,
                                   # include/dvsof_event_pyramids_tiled.h: likewise
-                                  **_abi.EVENT_PYRAMIDS_TILED_FUNCTIONS}.items():
+                                  **_abi.EVENT_PYRAMIDS_TILED_FUNCTIONS,
+                                  # include/dvsof_event_terms_joint.h: likewise
+                                  **_abi.EVENT_TERMS_JOINT_FUNCTIONS}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -111,6 +111,17 @@ struct AvgSum {
     }
 };
 
+// what a pixel of Q units and c events adds to the row
+__device__ __forceinline__ void avgts_stats_pixel(StatRow &a, int64_t Q, uint32_t c, const AvgPixel &px)
+{
+    const double pk = 2.0 * px.T * px.D;
+    a.S += px.T * px.T;
+    a.S0 += px.T0 * px.T0;
+    a.peak = a.peak > pk ? a.peak : pk;
+    a.n += Q > 0;
+    a.n0 += c > 0;
+}
+
 __global__ __launch_bounds__(kFrameNT) void avgts_stats_partial_kernel(
     const int64_t *__restrict__ q, const int64_t *__restrict__ s, const int64_t *__restrict__ base,
     const uint32_t *__restrict__ count, int h, int w, int nb, StatRow *__restrict__ part)
@@ -122,13 +133,7 @@ __global__ __launch_bounds__(kFrameNT) void avgts_stats_partial_kernel(
     frame_partial<AvgSum>(n, nb, part, [=](StatRow &a, int p) {
         const int64_t Q = qm[p];
         const uint32_t c = cm[p];
-        const AvgPixel px = avgts_pixel(Q, sm[p], bm[p], c);
-        const double pk = 2.0 * px.T * px.D;
-        a.S += px.T * px.T;
-        a.S0 += px.T0 * px.T0;
-        a.peak = a.peak > pk ? a.peak : pk;
-        a.n += Q > 0;
-        a.n0 += c > 0;
+        avgts_stats_pixel(a, Q, c, avgts_pixel(Q, sm[p], bm[p], c));
     });
 }
 

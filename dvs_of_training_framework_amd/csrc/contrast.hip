@@ -26,6 +26,7 @@
 // At the end of the file: the term on every flow scale of the network by one
 // splat, one closing wave and one backward for all levels (sections 19-23,
 // include/dvsof_contrast_pyramid.h); the kernels above are not touched by it.
+#include "event_term_records.h"
 #include "tiled_splat.h"
 #include "../../include/dvsof_contrast.h"
 #include "../../include/dvsof_contrast_multi.h"
@@ -37,17 +38,8 @@
 namespace {
 
 constexpr int NT = kFrameNT;
-constexpr int kUnitBits = 40;   // R = 1: |one event's addend| < 2^(kUnitBits + 1) units
-constexpr int kSharedBits = 2;  // R > 1: up to three addends of a pixel's event share a sum
-
-// one per image, in the workspace behind the fixed-point sums
-struct ImageRec {
-    double mean;  // of I_m
-    double coef;  // -2 / (N var(c_m)); 0 where var(c_m) is not positive
-    double gmax;  // |coef (I_m - mean)| <= gmax on every pixel
-    double term;  // 1 - var(I_m)/var(c_m); 0 where var(c_m) is not positive
-};
-static_assert(sizeof(ImageRec) == 32, "the workspace holds 32 bytes per image");
+// the unit bits, unit_of and the record of an image: event_term_records.h
+using ImageRec = ContrastRec;
 
 // ---------------------------------------------------------------------------
 // Forward.  One thread per event; an event takes part in every frame of its
@@ -70,14 +62,6 @@ __global__ __launch_bounds__(NT) void contrast_splat_kernel(
     for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
 }
 
-// 2^k: the flow gradient of a frame is summed in units of 1/unit; |G_m| <= gmax < 2^e for every image of the frame
-__device__ __forceinline__ double unit_of(double gmax, int unit_bits)
-{
-    int e = 0;
-    if (gmax > 0.0) (void)frexp(gmax, &e);
-    return ldexp(1.0, unit_bits - e);
-}
-
 // One wave: the record of every image (lane k takes images k, k + 64, ...);
 // after a barrier the unit of every frame (lane k takes frames k, k + 64, ...;
 // a maximum has no order) and, in lane 0, the images' terms in image order.
@@ -89,16 +73,7 @@ __global__ __launch_bounds__(kWave) void contrast_close_kernel(const dvsof_iwe_r
     const double N = (double)h * (double)w;
     const int M = F * RC;
     for (int m = threadIdx.x; m < M; m += kWave) {
-        const dvsof_iwe_result_t r = result[m];
-        const double mean = (double)r.sum_q * 0x1p-32 / N;
-        const double var_i = r.sum_sq / N - mean * mean;
-        const double cmean = (double)r.count_sum / N;
-        const double var_c = (double)r.count_sq / N - cmean * cmean;
-        ImageRec o;
-        o.mean = mean;
-        o.coef = var_c > 0.0 ? -2.0 / (N * var_c) : 0.0;
-        o.term = var_c > 0.0 ? 1.0 - var_i / var_c : 0.0;
-        o.gmax = fabs(o.coef) * fmax((double)r.max_q * 0x1p-32 - mean, mean);
+        const ImageRec o = contrast_record_of(result[m], N);
         rec[m] = o;
         if (RC == 1) unit[m] = unit_of(o.gmax, unit_bits);
     }
@@ -453,16 +428,7 @@ __global__ __launch_bounds__(kWave) void contrast_pyramid_close_kernel(const dvs
     for (int i = threadIdx.x; i < K * M; i += kWave) {
         const Level &L = lv.level[i / M];
         const double N = (double)L.h * (double)L.w;
-        const dvsof_iwe_result_t r = result[i];
-        const double mean = (double)r.sum_q * 0x1p-32 / N;
-        const double var_i = r.sum_sq / N - mean * mean;
-        const double cmean = (double)r.count_sum / N;
-        const double var_c = (double)r.count_sq / N - cmean * cmean;
-        ImageRec o;
-        o.mean = mean;
-        o.coef = var_c > 0.0 ? -2.0 / (N * var_c) : 0.0;
-        o.term = var_c > 0.0 ? 1.0 - var_i / var_c : 0.0;
-        o.gmax = fabs(o.coef) * fmax((double)r.max_q * 0x1p-32 - mean, mean);
+        const ImageRec o = contrast_record_of(result[i], N);
         rec[i] = o;
         if (RC == 1) unit[i] = unit_of(o.gmax, unit_bits);
     }

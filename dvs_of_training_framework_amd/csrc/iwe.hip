@@ -29,6 +29,7 @@
 // This file relies on -ffp-contract=off.
 #include "render_common.h"
 #include "avg_timestamp_images.h"
+#include "event_term_records.h"
 #include "tiled_splat.h"
 #include "../../include/dvsof_iwe_multi.h"
 #include "../../include/dvsof_iwe_avg_timestamp.h"
@@ -86,19 +87,9 @@ __global__ __launch_bounds__(NT) void iwe_avgts_splat_kernel(
 
 // ---------------------------------------------------------------------------
 // Statistics, by the fixed-order reduction of frame_common.h; the result row
-// is the accumulator.
+// is the accumulator (IweSum and iwe_stats_pixel of event_term_records.h, which
+// the joint call of the two training terms shares).
 // ---------------------------------------------------------------------------
-struct IweSum {
-    using Row = dvsof_iwe_result_t;
-    static __device__ __forceinline__ Row zero() { return Row{0.0, 0, 0, 0, 0, 0}; }
-    static __device__ __forceinline__ Row add(const Row &a, const Row &b)
-    {
-        return Row{a.sum_sq + b.sum_sq, a.sum_q + b.sum_q, a.max_q > b.max_q ? a.max_q : b.max_q,
-                   a.count_sum + b.count_sum, a.count_sq + b.count_sq,
-                   a.count_max > b.count_max ? a.count_max : b.count_max};
-    }
-};
-
 __global__ __launch_bounds__(NT) void iwe_stats_partial_kernel(
     const int64_t *__restrict__ q, const uint32_t *__restrict__ count, int h, int w, int nb,
     dvsof_iwe_result_t *__restrict__ part)
@@ -108,14 +99,7 @@ __global__ __launch_bounds__(NT) void iwe_stats_partial_kernel(
     const int64_t *qf = q + (size_t)f * n;
     const uint32_t *cf = count + (size_t)f * n;
     frame_partial<IweSum>(n, nb, part, [=](dvsof_iwe_result_t &a, int p) {
-        const int64_t Q = qf[p], c = cf[p];
-        const double I = (double)Q * 0x1p-32;
-        a.sum_sq += I * I;
-        a.sum_q += Q;
-        a.max_q = a.max_q > Q ? a.max_q : Q;
-        a.count_sum += c;
-        a.count_sq += c * c;
-        a.count_max = a.count_max > c ? a.count_max : c;
+        iwe_stats_pixel(a, qf[p], cf[p]);
     });
 }
 

@@ -1154,6 +1154,83 @@ class _AvgTimestampPyramid(torch.autograd.Function):
         return (None,) * 11 + grads + (None,) * (ctx.tiled is not None)
 
 
+class _EventTermsJoint(torch.autograd.Function):
+    """Both events-only terms of the same flows from one splat, one statistics
+    pass and one backward (dvsof_event_terms_joint_fwd / _bwd,
+    include/dvsof_event_terms_joint.h) -> (contrast value, contrast terms,
+    avg-timestamp value, avg-timestamp terms), the bits of ``_ContrastPyramid``
+    and ``_AvgTimestampPyramid`` on the same inputs.  The flows are passed
+    twice, once per term: each term's gradient is returned for its own copy, so
+    autograd adds the two exactly as it adds those of the two functions.
+
+    options = (contrast weights [K], avg-timestamp weights [K], contrast mask,
+    avg-timestamp mask, polarity, tiled, finest).  finest: None, or the two
+    weights of the one-level form, whose values are then ``term * weight`` and
+    whose terms are 0-dim, as ``_Contrast`` and ``_AvgTimestamp`` return them."""
+
+    @staticmethod
+    def forward(ctx, x, y, t, p, sample_index, frame_ts, frame_sample, shape, options, *flows):
+        from .eval import IWE_RESULT_DTYPE, event_images_tiled_mode, event_pyramids_tiled_workspace
+        cweights, aweights, cmask, amask, polarity, tiled, finest = options
+        K = len(flows) // 2
+        dev = flows[0].device
+        flows = tuple(f.detach().contiguous().float() for f in flows[:K])
+        F = flows[0].shape[0]
+        assert all(f.shape[0] == F and f.shape[1] == 2 for f in flows)
+        lib = _lib.lib()
+        C = 2 if polarity else 1
+        Mc, Ma = F * bin(cmask).count('1') * C, F * bin(amask).count('1') * C
+        shapes = [tuple(f.shape[-2:]) for f in flows]
+        ptrs = [f.data_ptr() for f in flows]
+        ctable = contrast_level_table(shape, shapes, F, Mc, cweights, ptrs)
+        atable = contrast_level_table(shape, shapes, F, Ma, aweights, ptrs)
+        new = torch.zeros if F == 0 else torch.empty
+        cterms, aterms = (new(K, dtype=torch.float32, device=dev) for _ in range(2))
+        cvalue, avalue = (new((), dtype=torch.float32, device=dev) for _ in range(2))
+        result = torch.empty(K * Mc, IWE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        h, w = (int(v) for v in shape)
+        nbytes = lib.dvsof_event_terms_joint_workspace_bytes(F, cmask, amask, int(polarity), h, w, ctable, atable)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
+        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
+        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flows[0].shape, frame_ts.shape)
+        ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
+        ctx.args = head + [tables[0].data_ptr(), tables[1].data_ptr(), F, h, w, cmask, amask, int(polarity)]
+        tiles, tile_bytes, mode = None, 0, -1
+        if tiled:
+            mode = event_images_tiled_mode(tiled)
+            tiles, tile_bytes = event_pyramids_tiled_workspace('avg_timestamp', F, amask, polarity, h, w, atable,
+                                                               cols[0].numel(), dev)
+        name = 'dvsof_event_terms_joint_fwd' + ctx.form
+        _lib.check(getattr(lib, name)(*ctx.args, ctable, atable, result.data_ptr(), cterms.data_ptr(),
+                                      cvalue.data_ptr(), aterms.data_ptr(), avalue.data_ptr(), ws.data_ptr(), nbytes,
+                                      _lib.stream(), _lib.ptr(tiles), tile_bytes, mode), name)
+        ctx.held = (cols, pol, tables, flows, ws, nbytes, ctable, atable)
+        if finest is not None:      # the values of the two one-level functions
+            cterms, aterms = cterms.reshape(()), aterms.reshape(())
+            cvalue, avalue = cterms * float(finest[0]), aterms * float(finest[1])
+        ctx.mark_non_differentiable(cterms, aterms)
+        ctx.set_materialize_grads(False)
+        return cvalue, cterms, avalue, aterms
+
+    @staticmethod
+    def backward(ctx, g_contrast, _g_cterms, g_avg, _g_aterms):
+        flows, ws, nbytes, ctable, atable = ctx.held[3:]
+        K = len(flows)
+        if g_contrast is None and g_avg is None:
+            return (None,) * (9 + 2 * K)
+        grads = tuple(torch.empty_like(f) for f in flows + flows)
+        for k in range(K):
+            ctable.level[k].grad_flow = grads[k].data_ptr()
+            atable.level[k].grad_flow = grads[K + k].data_ptr()
+        seeds = [torch.zeros((), device=flows[0].device) if g is None else g.contiguous().float()
+                 for g in (g_contrast, g_avg)]
+        name = 'dvsof_event_terms_joint_bwd' + ctx.form
+        _lib.check(getattr(_lib.lib(), name)(*ctx.args, ctable, atable, ws.data_ptr(), nbytes, seeds[0].data_ptr(),
+                                             seeds[1].data_ptr(), _lib.stream()), name)
+        return (None,) * 9 + tuple(None if g is None else grad
+                                   for g, part in ((g_contrast, grads[:K]), (g_avg, grads[K:])) for grad in part)
+
+
 class Loss:
     """Single-scale evaluator (reference utils/loss.py:38-171)."""
 
@@ -1439,6 +1516,64 @@ class Losses:
                                       self.shapes[-1], weights, mask, bool(polarity), *flows,
                                       *((tiled,) if tiled else ()))
         return value if weight is None else (value, terms)
+
+    def event_terms(self, flows, flow_ts, flow_sample_idx, events, contrast, avg_timestamp, tiled=False):
+        """Both events-only terms of one batch by the joint calls
+        (include/dvsof_event_terms_joint.h, CONTRAST_SPEC section 26,
+        AVG_TIMESTAMP_SPEC section 19): one splat, one statistics pass and one
+        backward for both.  contrast, avg_timestamp: dicts of the keywords
+        ``weight`` (required), ``references``, ``polarity`` and ``scales`` of
+        ``contrast`` and ``avg_timestamp_scales``, with their defaults.  ->
+        (contrast value, contrast term, avg-timestamp value, avg-timestamp
+        term): what ``contrast(..., weight=)`` and ``avg_timestamp_scales(...,
+        weight=)`` return, bit for bit, and the same gradients into the flows.
+        events: the wire or the compact columns.
+
+        The contrast references must be among the average-timestamp ones, and
+        the two terms must agree in ``polarity`` and in ``scales``: ValueError
+        otherwise.  tiled: True or 'force', the splat by the tiled schedule
+        over the level table, on one scale too."""
+        for name, options in (('contrast', contrast), ('avg_timestamp', avg_timestamp)):
+            unknown = set(options) - {'weight', 'references', 'polarity', 'scales'}
+            if unknown or options.get('weight') is None:
+                raise ValueError(f'event_terms: {name} takes weight (required), references, polarity and scales, '
+                                 f'got {sorted(options)}')
+        cmask = contrast_reference_mask(contrast.get('references', ('start',)))
+        amask = contrast_reference_mask(avg_timestamp.get('references', ('start', 'end')))
+        if cmask & ~amask:
+            raise ValueError('event_terms: the contrast references are not a subset of the average-timestamp '
+                             'references: the joint call takes the contrast images from the average-timestamp splat')
+        polarity = bool(contrast.get('polarity', False))
+        if polarity != bool(avg_timestamp.get('polarity', False)):
+            raise ValueError('event_terms: the two terms differ in polarity: one splat keeps ON and OFF events '
+                             'apart for both or for neither')
+        scales = contrast.get('scales', 'finest')
+        if scales != avg_timestamp.get('scales', 'finest'):
+            raise ValueError('event_terms: the two terms differ in scales: one level table serves both')
+        if scales not in CONTRAST_SCALES:
+            raise ValueError(f'unknown scales "{scales}": one of {", ".join(CONTRAST_SCALES)}')
+        if tiled:
+            from .eval import event_images_tiled_mode
+            event_images_tiled_mode(tiled)              # ValueError for anything but True and 'force'
+        finest = None
+        if scales == 'finest':
+            flows = flows[-1:]
+            assert tuple(flows[0].shape[-2:]) == self.shapes[-1] and flows[0].shape[1] == 2, \
+                f'flow of size {tuple(flows[0].shape)} given to the event terms of scale {self.shapes[-1]}'
+            finest = (float(contrast['weight']), float(avg_timestamp['weight']))
+            cweights, aweights = [finest[0]], [finest[1]]
+        else:
+            self._check_flows(flows)
+            for shape in self.shapes:                   # a level that is no halving is refused here
+                contrast_level_shift(self.shapes[-1], shape)
+            cweights = contrast_level_weights(contrast['weight'], len(flows))
+            aweights = contrast_level_weights(avg_timestamp['weight'], len(flows))
+        *cols, pol, sample = _term_columns(events, polarity)
+        cols.append(sample)
+        _lib.require_cuda(flow_ts, flow_sample_idx, *flows, *cols)
+        _lib.require_cuda(pol)
+        return _EventTermsJoint.apply(*cols[:3], pol, cols[3], flow_ts, flow_sample_idx, self.shapes[-1],
+                                      (cweights, aweights, cmask, amask, polarity, tiled, finest), *flows, *flows)
 
 
 def init_losses(shape, batch_size, model, device, sequence_length,

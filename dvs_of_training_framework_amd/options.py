@@ -409,6 +409,18 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              '(include/dvsof_event_pyramids_tiled.h).  The kernels decide by the '
                              'event count whether it pays (from 64 000 events a batch on, for either term).  Not with '
                              '--capture-event-terms, which has no tiled form')
+    parser.add_argument('--event-terms-joint', dest='event_terms_joint',
+                        default=argparse.SUPPRESS, action='store_true',
+                        help='with both --contrast-weight and --avg-timestamp-weight: the two terms '
+                             'from one splat, one statistics pass and one backward walk of the '
+                             'events (include/dvsof_event_terms_joint.h); the same loss and '
+                             'gradients bit for bit.  Needs the --contrast-references among the '
+                             '--avg-timestamp-references and the same polarity and scales options '
+                             'for both terms.  Its splat is tiled by --event-pyramids-tiled, on the '
+                             'finest scale too; not with --event-images-tiled, --avg-timestamp-tiled '
+                             'or --capture-event-terms.  Measured on 8 frames of 256 x 256 '
+                             '(profiles/event_terms_joint/README.md); it is not decided by the event '
+                             'count, so a run with few events a batch should measure first')
     parser.add_argument('--compact-event-terms', dest='compact_event_terms',
                         default=argparse.SUPPRESS, action='store_true',
                         help='with --compact-events and a positive --contrast-weight or '
@@ -494,9 +506,38 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_event_pyramids_tiled_args(validate_avg_timestamp_tiled_args(validate_event_images_tiled_args(
-        validate_compact_event_terms_args(validate_capture_event_terms_args(validate_frameless_args(
-            validate_sharpness_args(validate_avg_timestamp_args(validate_contrast_args(args)))))))))
+    return validate_event_terms_joint_args(validate_event_pyramids_tiled_args(validate_avg_timestamp_tiled_args(
+        validate_event_images_tiled_args(validate_compact_event_terms_args(validate_capture_event_terms_args(
+            validate_frameless_args(validate_sharpness_args(validate_avg_timestamp_args(
+                validate_contrast_args(args))))))))))
+
+
+def validate_event_terms_joint_args(args):
+    """--event-terms-joint (absent from ``args`` unless given) against what the
+    joint calls need of the two terms' options, and against the flags whose
+    path it does not take."""
+    if not getattr(args, 'event_terms_joint', False):
+        return args
+    if not (getattr(args, 'contrast_weight', 0.0) > 0 and getattr(args, 'avg_timestamp_weight', 0.0) > 0):
+        raise SystemExit('--event-terms-joint needs both terms: a positive --contrast-weight and a positive '
+                         '--avg-timestamp-weight')
+    contrast = getattr(args, 'contrast_references', ('start',))
+    avg = getattr(args, 'avg_timestamp_references', AVG_TIMESTAMP_REFERENCES)
+    if not set(contrast) <= set(avg):
+        raise SystemExit(f'--event-terms-joint needs the --contrast-references ({",".join(contrast)}) to be a '
+                         f'subset of the --avg-timestamp-references ({",".join(avg)}): the contrast images are '
+                         'taken from the average-timestamp splat')
+    if bool(getattr(args, 'contrast_polarity', False)) != bool(getattr(args, 'avg_timestamp_polarity', False)):
+        raise SystemExit('--event-terms-joint needs the same polarity option for both terms: --contrast-polarity '
+                         'and --avg-timestamp-polarity together or neither')
+    if getattr(args, 'contrast_scales', 'finest') != getattr(args, 'avg_timestamp_scales', 'finest'):
+        raise SystemExit('--event-terms-joint needs the same scales for both terms: --contrast-scales and '
+                         '--avg-timestamp-scales differ')
+    for flag in ('capture_event_terms', 'event_images_tiled', 'avg_timestamp_tiled'):
+        if getattr(args, flag, False):
+            raise SystemExit(f'--event-terms-joint cannot be combined with --{flag.replace("_", "-")}: the joint '
+                             'path has no captured form yet and takes its schedule from --event-pyramids-tiled')
+    return args
 
 
 def validate_event_pyramids_tiled_args(args):
@@ -510,6 +551,8 @@ def validate_event_pyramids_tiled_args(args):
                          'no tiled form')
     contrast = getattr(args, 'contrast_weight', 0.0) > 0 and getattr(args, 'contrast_scales', 'finest') == 'all'
     avg = getattr(args, 'avg_timestamp_weight', 0.0) > 0 and getattr(args, 'avg_timestamp_scales', 'finest') == 'all'
+    if getattr(args, 'event_terms_joint', False):       # the joint calls tile their one splat on one scale too
+        return args
     if not (contrast or avg):
         raise SystemExit('--event-pyramids-tiled needs --contrast-weight with --contrast-scales all, or '
                          '--avg-timestamp-weight with --avg-timestamp-scales all: without either no term runs '

@@ -99,6 +99,28 @@ def _avg_timestamp_options(references, polarity, scales='finest', tiled=False):
     return out
 
 
+def event_terms_joint_refusal(contrast_weight, avg_timestamp_weight, contrast_references, avg_timestamp_references,
+                              contrast_polarity, avg_timestamp_polarity, contrast_scales, avg_timestamp_scales,
+                              capture_event_terms=False, contrast_tiled=False, avg_timestamp_tiled=False):
+    """Why these options cannot run by the joint calls of the two events-only
+    terms (``combined_loss(event_terms_joint=True)``), each naming its
+    condition, or None.  ``train`` and the command line ask this."""
+    from .loss import contrast_reference_mask
+    if not contrast_weight or not avg_timestamp_weight:
+        return 'needs both terms: a positive contrast weight and a positive avg-timestamp weight'
+    if contrast_reference_mask(contrast_references) & ~contrast_reference_mask(avg_timestamp_references):
+        return 'needs the contrast references to be a subset of the avg-timestamp references'
+    if bool(contrast_polarity) != bool(avg_timestamp_polarity):
+        return 'needs the same polarity option for both terms'
+    if contrast_scales != avg_timestamp_scales:
+        return 'needs the same scales for both terms'
+    if capture_event_terms:
+        return 'has no form for a step captured with capture_event_terms'
+    if contrast_tiled or avg_timestamp_tiled:
+        return 'takes its schedule from event_pyramids_tiled, not from contrast_tiled or avg_timestamp_tiled'
+    return None
+
+
 def _avg_timestamp_keywords(weight, references, polarity, scales='finest', tiled=False):
     """What a call down the chain gets: nothing at weight 0, and the options
     only where they differ from the defaults."""
@@ -115,7 +137,7 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   contrast_references=('start',), contrast_polarity=False,
                   contrast_scales='finest', avg_timestamp_scales='finest',
                   contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-                  avg_timestamp_weight=0.0,
+                  event_terms_joint=False, avg_timestamp_weight=0.0,
                   avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                   avg_timestamp_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
@@ -158,6 +180,15 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     finest flow alone is not touched by it.  False, the default, passes
     nothing on.
 
+    event_terms_joint: True: both terms by one call, one splat, one statistics
+    pass and one backward (``Losses.event_terms``; the same bits, added to the
+    loss in the same order).  Needs both weights (ValueError with one term
+    only), the contrast references among the average-timestamp ones and the
+    same polarity and scales for both; its splat is tiled by
+    event_pyramids_tiled, on the finest flow alone too; contrast_tiled and
+    avg_timestamp_tiled are refused with it.  False, the default, constructs
+    nothing new.
+
     images=None with an evaluator that has ``frameless`` (loss.Losses): a
     frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
     and out-of-border with the weights (weights[0], weights[2]) and a
@@ -188,9 +219,28 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         loss = 0
         for weight, per_scale in zip(weights, terms):
             loss = loss + weight * mean(per_scale)
+    if event_terms_joint and not (contrast_weight and avg_timestamp_weight):
+        raise ValueError('event_terms_joint needs both terms: contrast_weight > 0 and avg_timestamp_weight > 0')
     if not contrast_weight and not avg_timestamp_weight:
         return loss, terms
     term = avg_term = None
+    if event_terms_joint:
+        if contrast_weight < 0 or avg_timestamp_weight < 0:
+            raise ValueError(f'the weights must not be negative, got {contrast_weight} and {avg_timestamp_weight}')
+        if contrast_tiled or avg_timestamp_tiled:
+            raise ValueError('event_terms_joint takes its schedule from event_pyramids_tiled, not from '
+                             'contrast_tiled or avg_timestamp_tiled')
+        if events is None:
+            raise ValueError('event_terms_joint needs the raw events of the batch on the device '
+                             '(is_raw=True); preprocessed voxel grids carry none')
+        value, term, avg_value, avg_term = evaluator.event_terms(
+            flows, flow_ts, flow_sample_idx, events,
+            contrast=dict(weight=contrast_weight, references=tuple(contrast_references),
+                          polarity=bool(contrast_polarity), scales=contrast_scales),
+            avg_timestamp=dict(weight=avg_timestamp_weight, references=tuple(avg_timestamp_references),
+                               polarity=bool(avg_timestamp_polarity), scales=avg_timestamp_scales),
+            **({'tiled': event_pyramids_tiled} if event_pyramids_tiled else {}))
+        return loss + value + avg_value, _TermsAndContrast(terms, term, avg_term)
     if contrast_weight:
         if contrast_weight < 0:
             raise ValueError(f'contrast_weight must not be negative, got {contrast_weight}')
@@ -336,7 +386,7 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       contrast_references=('start',), contrast_polarity=False,
                       contrast_scales='finest', avg_timestamp_scales='finest',
                       contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-                      avg_timestamp_weight=0.0,
+                      event_terms_joint=False, avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
     """batch (SURVEY 8b wire format, or compact event columns:
@@ -358,6 +408,8 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
         contrast = dict(contrast, **avg)
     if event_pyramids_tiled and contrast:       # the tiled splat of the terms that run on every scale
         contrast = dict(contrast, event_pyramids_tiled=event_pyramids_tiled)
+    if event_terms_joint:                       # both terms by one call (``combined_loss``)
+        contrast = dict(contrast, event_terms_joint=True)
     with _timed(timers, 'batch2gpu'):
         timestamps, sample_idx, images, payload = _to_device(batch, device,
                                                              is_raw)
@@ -599,7 +651,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
           capture_event_terms: bool = False, avg_timestamp_scales: str = 'finest',
           contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-          avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+          event_terms_joint=False, avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
@@ -659,6 +711,14 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                level table (``combined_loss``; the same bits).  Needs one of
                them, and not in a step captured with ``capture_event_terms``
                (ValueError).  (By name)
+    event_terms_joint:  True: both events-only terms by one call, one splat,
+               one statistics pass and one backward (``combined_loss``; the
+               same bits).  Needs both weights, the contrast references among
+               the average-timestamp ones and the same polarity and scales for
+               both; takes its schedule from event_pyramids_tiled (on the
+               finest flow too) and refuses contrast_tiled, avg_timestamp_tiled
+               and a step captured with ``capture_event_terms`` (ValueError).
+               (By name)
     avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
                the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
                events only), logged as ``Train/avg timestamp``, beside the
@@ -707,9 +767,16 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                                                          or avg_timestamp_scales != 'finest'):
         raise ValueError('avg_timestamp_tiled has no form for avg_timestamp_scales=\'all\' or a step captured '
                          'with capture_event_terms')
+    if event_terms_joint:
+        refusal = event_terms_joint_refusal(
+            contrast_weight, avg_timestamp_weight, contrast_references, avg_timestamp_references, contrast_polarity,
+            avg_timestamp_polarity, contrast_scales, avg_timestamp_scales, capture and capture_event_terms,
+            contrast_tiled, avg_timestamp_tiled)
+        if refusal:
+            raise ValueError('event_terms_joint ' + refusal)
     if event_pyramids_tiled:
         if not ((contrast_weight and contrast_scales == 'all')
-                or (avg_timestamp_weight and avg_timestamp_scales == 'all')):
+                or (avg_timestamp_weight and avg_timestamp_scales == 'all') or event_terms_joint):
             raise ValueError('event_pyramids_tiled needs a term on every flow scale: contrast_scales=\'all\' or '
                              'avg_timestamp_scales=\'all\' with its weight')
         if capture and capture_event_terms:
@@ -770,7 +837,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                                      contrast_scales, contrast_tiled),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
                                           avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled),
-                **({'event_pyramids_tiled': event_pyramids_tiled} if event_pyramids_tiled else {}))
+                **({'event_pyramids_tiled': event_pyramids_tiled} if event_pyramids_tiled else {}),
+                **({'event_terms_joint': True} if event_terms_joint else {}))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass

@@ -539,7 +539,9 @@ def main(argv=None):
                   **({'capture_event_terms': True}
                      if getattr(args, 'capture_event_terms', False) else {}),
                   **({'event_pyramids_tiled': True}
-                     if getattr(args, 'event_pyramids_tiled', False) else {}))
+                     if getattr(args, 'event_pyramids_tiled', False) else {}),
+                  **({'event_terms_joint': True}
+                     if getattr(args, 'event_terms_joint', False) else {}))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
