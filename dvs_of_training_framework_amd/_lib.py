@@ -28,7 +28,9 @@ tests/golden/abi_signatures_avg_timestamp_tiled.json;
 _abi.EVENT_PYRAMIDS_TILED_PATH: include/dvsof_event_pyramids_tiled.h, recorded in
 tests/golden/abi_signatures_event_pyramids_tiled.json;
 _abi.EVENT_TERMS_JOINT_PATH: include/dvsof_event_terms_joint.h, recorded in
-tests/golden/abi_signatures_event_terms_joint.json).
+tests/golden/abi_signatures_event_terms_joint.json;
+_abi.CONTRAST_GRADIENT_PATH: include/dvsof_contrast_gradient.h, recorded in
+tests/golden/abi_signatures_contrast_gradient.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -158,6 +160,11 @@ def declared_event_terms_joint_symbols():
     return _declared_in((_abi.EVENT_TERMS_JOINT_PATH,))
 
 
+def declared_contrast_gradient_symbols():
+    """Names of all entry points include/dvsof_contrast_gradient.h declares."""
+    return _declared_in((_abi.CONTRAST_GRADIENT_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -183,7 +190,9 @@ def lib():
                                   # include/dvsof_event_pyramids_tiled.h: likewise
                                   **_abi.EVENT_PYRAMIDS_TILED_FUNCTIONS,
                                   # include/dvsof_event_terms_joint.h: likewise
-                                  **_abi.EVENT_TERMS_JOINT_FUNCTIONS}.items():
+                                  **_abi.EVENT_TERMS_JOINT_FUNCTIONS,
+                                  # include/dvsof_contrast_gradient.h: likewise
+                                  **_abi.CONTRAST_GRADIENT_FUNCTIONS}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -26,6 +26,8 @@
 // At the end of the file: the term on every flow scale of the network by one
 // splat, one closing wave and one backward for all levels (sections 19-23,
 // include/dvsof_contrast_pyramid.h); the kernels above are not touched by it.
+// After that: the gradient-magnitude objective on the same images (sections
+// 27-31, include/dvsof_contrast_gradient.h), a stencil over q through LDS.
 #include "event_term_records.h"
 #include "tiled_splat.h"
 #include "../../include/dvsof_contrast.h"
@@ -34,6 +36,7 @@
 #include "../../include/dvsof_event_terms_encoded.h"
 #include "../../include/dvsof_event_images_tiled.h"
 #include "../../include/dvsof_event_pyramids_tiled.h"
+#include "../../include/dvsof_contrast_gradient.h"
 
 namespace {
 
@@ -767,6 +770,350 @@ int dvsof_contrast_pyramid_fwd_encoded_tiled(const int16_t *x, const int16_t *y,
     return pyramid_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
                        F, h, w, reference_mask, polarity_channels, levels, result, terms, value, workspace,
                        workspace_bytes, stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The gradient-magnitude objective (docs/CONTRAST_SPEC.md sections 27-31;
+// Gallego et al., CVPR 2019): term_m = 1 - GM(I_m)/GM(c_m), GM the sum of the
+// squared differences of every adjacent pair of pixels.  The images, the splat
+// and the backward's closing kernel are those above.  New here: the statistics,
+// a 5-point stencil over q and count by tiles through LDS, which also stores
+// the integer Laplacian of q, the adjoint of the differences; one closing wave;
+// the backward over events, which gathers that plane where the variance's
+// gathers q.  Differences of q are integers, so Lap and GM(c) are exact and
+// only GM(I) is a float64 sum, in a fixed order.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int kTileW = 64, kTileH = 16;              // owned pixels of a workgroup
+constexpr int kHaloW = kTileW + 2, kHaloH = kTileH + 2;
+constexpr int kTileRows = kTileH / (NT / kTileW);    // owned pixels of a thread, one per row
+static_assert(NT % kTileW == 0 && kTileH % (NT / kTileW) == 0, "a thread keeps its column");
+
+// what a tile adds to an image, and an image's sums: the reduction's accumulator
+struct GradRow {
+    double gm_i;             // GM(I): sum over owned pairs of ((double)d 2^-32)^2
+    unsigned long long gm_c; // GM(c): the same pairs of the count image, exact
+    long long lap_max;       // max |Lap| in units of 2^-32
+};
+static_assert(sizeof(GradRow) == 24, "rows are 24 bytes");
+
+struct GradSum {
+    using Row = GradRow;
+    static __device__ __forceinline__ Row zero() { return Row{0.0, 0ull, 0ll}; }
+    static __device__ __forceinline__ Row add(const Row &a, const Row &b)
+    {
+        return Row{a.gm_i + b.gm_i, a.gm_c + b.gm_c, a.lap_max > b.lap_max ? a.lap_max : b.lap_max};
+    }
+};
+
+// the record of an image in the workspace (include/dvsof_contrast_gradient.h)
+struct GradRec {
+    double coef;  // -2 / GM(c_m); 0 where GM(c_m) is 0
+    double gmax;  // |coef Lap 2^-32| <= gmax on every pixel
+    double term;  // 1 - GM(I_m)/GM(c_m); 0 where GM(c_m) is 0
+    double gm_i;
+    unsigned long long gm_c;
+    long long lap_max;
+};
+static_assert(sizeof(GradRec) == 48, "the workspace holds 48 bytes per image");
+
+inline int tiles_across(int w) { return (w + kTileW - 1) / kTileW; }
+inline int tiles_down(int h) { return (h + kTileH - 1) / kTileH; }
+
+// Grid (tiles, M), NT threads.  Staging: halo position k = thread, thread + NT, ... of the
+// 66 x 18 window whose corner is one pixel up and left of the tile; a row of the window is a
+// run of consecutive addresses.  A position outside the image is filled with 0 and not read;
+// whether a neighbour exists is asked of its coordinates, never of the filled value.  Thread t
+// owns column t % 64 of rows t / 64 + 4 j, j ascending: a pixel inside the image stores its
+// Laplacian and adds the pair to its right, then the pair below it, where the neighbour is
+// inside the image, in this tile or the next (every pair once, by its left or upper pixel).
+__global__ __launch_bounds__(NT) void contrast_gradient_stats_kernel(const int64_t *__restrict__ q,
+                                                                     const uint32_t *__restrict__ count, int h,
+                                                                     int w, int tx, int64_t *__restrict__ lap,
+                                                                     GradRow *__restrict__ part)
+{
+    __shared__ int64_t sq[kHaloH][kHaloW];
+    __shared__ uint32_t sc[kHaloH][kHaloW];
+    const int m = blockIdx.y, tile = blockIdx.x;
+    const int x0 = (tile % tx) * kTileW, y0 = (tile / tx) * kTileH;
+    const size_t plane = (size_t)h * w;
+    const int64_t *qm = q + (size_t)m * plane;
+    const uint32_t *cm = count + (size_t)m * plane;
+    for (int k = threadIdx.x; k < kHaloH * kHaloW; k += NT) {
+        const int ly = k / kHaloW, lx = k % kHaloW;
+        const int gx = x0 + lx - 1, gy = y0 + ly - 1;
+        const bool in = gx >= 0 && gx < w && gy >= 0 && gy < h;
+        const size_t at = in ? (size_t)gy * w + (size_t)gx : 0;
+        sq[ly][lx] = in ? qm[at] : 0;
+        sc[ly][lx] = in ? cm[at] : 0u;
+    }
+    __syncthreads();
+    GradRow a = GradSum::zero();
+    const int lx = threadIdx.x % kTileW + 1, gx = x0 + lx - 1;
+#pragma unroll
+    for (int j = 0; j < kTileRows; ++j) {
+        const int ly = threadIdx.x / kTileW + j * (NT / kTileW) + 1, gy = y0 + ly - 1;
+        if (gx >= w || gy >= h) continue;
+        const int64_t qc = sq[ly][lx];
+        const int64_t cc = (int64_t)sc[ly][lx];
+        int64_t L = 0;
+        if (gx > 0) L += qc - sq[ly][lx - 1];
+        if (gy > 0) L += qc - sq[ly - 1][lx];
+        if (gx + 1 < w) {
+            const int64_t d = sq[ly][lx + 1] - qc, dc = (int64_t)sc[ly][lx + 1] - cc;
+            const double di = (double)d * 0x1p-32;
+            a.gm_i += di * di;
+            a.gm_c += (unsigned long long)(dc * dc);
+            L -= d;
+        }
+        if (gy + 1 < h) {
+            const int64_t d = sq[ly + 1][lx] - qc, dc = (int64_t)sc[ly + 1][lx] - cc;
+            const double di = (double)d * 0x1p-32;
+            a.gm_i += di * di;
+            a.gm_c += (unsigned long long)(dc * dc);
+            L -= d;
+        }
+        lap[(size_t)m * plane + (size_t)gy * w + (size_t)gx] = L;
+        const long long mag = L < 0 ? -L : L;
+        a.lap_max = a.lap_max > mag ? a.lap_max : mag;
+    }
+    a = block_tree<GradSum>(a);
+    if (threadIdx.x == 0) part[(size_t)m * gridDim.x + tile] = a;
+}
+
+// One wave, on the pattern of contrast_close_kernel: the record of every image from its row,
+// after a barrier the unit of every frame from the largest gmax of its images, and in lane 0
+// the images' terms in image order.
+__global__ __launch_bounds__(kWave) void contrast_gradient_close_kernel(const GradRow *__restrict__ row, int F,
+                                                                        int RC, int unit_bits, GradRec *rec,
+                                                                        double *unit, float *term)
+{
+    const int M = F * RC;
+    for (int m = threadIdx.x; m < M; m += kWave) {
+        const GradRow r = row[m];
+        const bool edges = r.gm_c > 0;
+        const double gc = (double)r.gm_c;
+        GradRec o;
+        o.coef = edges ? -2.0 / gc : 0.0;
+        o.gmax = fabs(o.coef) * ((double)r.lap_max * 0x1p-32);
+        o.term = edges ? 1.0 - r.gm_i / gc : 0.0;
+        o.gm_i = r.gm_i;
+        o.gm_c = r.gm_c;
+        o.lap_max = r.lap_max;
+        rec[m] = o;
+    }
+    __syncthreads();
+    for (int f = threadIdx.x; f < F; f += kWave) {
+        double gmax = 0.0;
+        for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[f * RC + k].gmax);
+        unit[f] = unit_of(gmax, unit_bits);
+    }
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int m = 0; m < M; ++m) s += rec[m].term;
+        *term = (float)(s / (double)M);
+    }
+}
+
+// contrast_bwd_events_kernel with G = coef Lap 2^-32 gathered from the Laplacian plane: the
+// same factors, the same truncation to the frame's unit, the same sums and bounds (|G| <= gmax).
+template <int R, bool POL, class Cols>
+__global__ __launch_bounds__(NT) void contrast_gradient_bwd_events_kernel(
+    const Cols cols, int64_t n, const float *__restrict__ ts,
+    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
+    const int64_t *__restrict__ lap, const GradRec *__restrict__ rec, const double *__restrict__ unit,
+    unsigned long long *__restrict__ acc)
+{
+    const size_t plane = (size_t)h * w;
+    const auto addends = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
+        const size_t pix = (size_t)yi * w + (size_t)xi;
+        float u, v;
+        flow_at(flow, f, plane, pix, u, v);
+        const double un = unit[f];
+        long long su = 0, sv = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const size_t m = image_of<R, POL>(f, r, c);
+            const double coef = rec[m].coef;
+            if (coef == 0.0) continue;  // GM(c_m) = 0: every addend would be 0
+            Warp p;
+            if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
+            const int64_t *img = lap + m * plane;
+            double G[2][2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int xx = p.cx + i, yy = p.cy + j;
+                    const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
+                    G[j][i] = in ? coef * ((double)img[(size_t)yy * w + (size_t)xx] * 0x1p-32) : 0.0;
+                }
+            }
+            const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
+            const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
+            const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
+            su += (long long)(ms * gx * un);
+            sv += (long long)(ms * gy * un);
+        }
+        unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
+        if (su != 0) atomicAdd(dst, (unsigned long long)su);
+        if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
+    };
+    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
+}
+
+// the workspace as byte offsets, in the order of the header
+struct GradLayout {
+    size_t lap, rec, unit, row, part, bytes;
+    int tx, tiles;
+};
+
+GradLayout gradient_layout(int F, int h, int w, const Plan &pl)
+{
+    GradLayout o;
+    o.tx = tiles_across(w);
+    o.tiles = o.tx * tiles_down(h);
+    o.lap = sums_bytes(F, h, w);
+    o.rec = o.lap + sizeof(int64_t) * (size_t)pl.M * h * w;
+    o.unit = o.rec + sizeof(GradRec) * (size_t)pl.M;
+    o.row = o.unit + sizeof(double) * (size_t)F;
+    o.part = o.row + sizeof(GradRow) * (size_t)pl.M;
+    o.bytes = o.part + sizeof(GradRow) * (size_t)pl.M * o.tiles;
+    return o;
+}
+
+size_t gradient_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
+{
+    Plan pl;
+    if (F < 1 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return 0;
+    return gradient_layout(F, h, w, pl).bytes;
+}
+
+// dvsof_contrast_gradient_fwd / _bwd on either form of the event columns
+template <class Cols>
+int gradient_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+                 const float *flow, int F, int h, int w, int reference_mask, int polarity, int64_t *q,
+                 uint32_t *count, float *term, void *workspace, size_t workspace_bytes, void *stream)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !q || !count || !term || !frame_ts || !frame_sample || !flow) return DVSOF_EINVAL;
+    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < gradient_workspace_bytes(F, reference_mask, polarity, h, w))
+        return DVSOF_ENOSPACE;
+    hipStream_t st = as_stream(stream);
+    const size_t pixels = (size_t)pl.M * h * w;
+    const GradLayout lay = gradient_layout(F, h, w, pl);
+    char *ws = (char *)workspace;
+    DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
+    DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
+    DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, sums_bytes(F, h, w), st));
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, (unsigned long long *)q,
+                                count);
+        DVSOF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(contrast_gradient_stats_kernel, dim3((unsigned)lay.tiles, (unsigned)pl.M), dim3(NT), 0, st,
+                       (const int64_t *)q, (const uint32_t *)count, h, w, lay.tx, (int64_t *)(ws + lay.lap),
+                       (GradRow *)(ws + lay.part));
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(frame_final_kernel<GradSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
+                       (const GradRow *)(ws + lay.part), lay.tiles, (GradRow *)(ws + lay.row));
+    DVSOF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(contrast_gradient_close_kernel, dim3(1), dim3(kWave), 0, st, (const GradRow *)(ws + lay.row),
+                       F, pl.R * pl.C, pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, (GradRec *)(ws + lay.rec),
+                       (double *)(ws + lay.unit), term);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+template <class Cols>
+int gradient_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+                 const float *flow, int F, int h, int w, int reference_mask, int polarity, const int64_t *q,
+                 void *workspace, size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
+                 void *stream)
+{
+    Plan pl;
+    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
+    if (F == 0) return DVSOF_OK;
+    if (bad_frame_sizes(F, h, w) || !q || !seed || !grad_flow || !frame_ts || !frame_sample || !flow) return DVSOF_EINVAL;
+    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
+    if (!workspace || workspace_bytes < gradient_workspace_bytes(F, reference_mask, polarity, h, w))
+        return DVSOF_ENOSPACE;
+    hipStream_t st = as_stream(stream);
+    const GradLayout lay = gradient_layout(F, h, w, pl);
+    char *ws = (char *)workspace;
+    if (n_events > 0) {
+        DVSOF_REFS_POL_DISPATCH(contrast_gradient_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
+                                cols, n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
+                                (const int64_t *)(ws + lay.lap), (const GradRec *)(ws + lay.rec),
+                                (const double *)(ws + lay.unit), (unsigned long long *)ws);
+        DVSOF_LAUNCH_CHECK();
+    }
+    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
+    hipLaunchKernelGGL(contrast_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
+                       (long long *)ws, (const double *)(ws + lay.unit), seed, weight, F, pl.M, per_frame, grad_flow);
+    DVSOF_LAUNCH_CHECK();
+    return DVSOF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dvsof_contrast_gradient_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
+{
+    return gradient_workspace_bytes(F, reference_mask, polarity, h, w);
+}
+
+int dvsof_contrast_gradient_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                                int reference_mask, int polarity, int64_t *q, uint32_t *count, float *term,
+                                void *workspace, size_t workspace_bytes, void *stream)
+{
+    return gradient_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                        reference_mask, polarity, q, count, term, workspace, workspace_bytes, stream);
+}
+
+int dvsof_contrast_gradient_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                                int reference_mask, int polarity, const int64_t *q, void *workspace,
+                                size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
+                                void *stream)
+{
+    return gradient_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
+                        reference_mask, polarity, q, workspace, workspace_bytes, seed, weight, grad_flow, stream);
+}
+
+int dvsof_contrast_gradient_fwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                        const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                        const float *frame_ts, const int64_t *frame_sample, const float *flow,
+                                        int F, int h, int w, int reference_mask, int polarity_channels, int64_t *q,
+                                        uint32_t *count, float *term, void *workspace, size_t workspace_bytes,
+                                        void *stream)
+{
+    return gradient_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts,
+                        frame_sample, flow, F, h, w, reference_mask, polarity_channels, q, count, term, workspace,
+                        workspace_bytes, stream);
+}
+
+int dvsof_contrast_gradient_bwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                        const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                        const float *frame_ts, const int64_t *frame_sample, const float *flow,
+                                        int F, int h, int w, int reference_mask, int polarity_channels,
+                                        const int64_t *q, void *workspace, size_t workspace_bytes,
+                                        const float *seed, float weight, float *grad_flow, void *stream)
+{
+    return gradient_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts,
+                        frame_sample, flow, F, h, w, reference_mask, polarity_channels, q, workspace,
+                        workspace_bytes, seed, weight, grad_flow, stream);
 }
 
 }  // extern "C"

@@ -630,6 +630,69 @@ class _Contrast(torch.autograd.Function):
         return (grad,) + (None,) * 11
 
 
+# The gradient-magnitude objective (csrc/contrast.hip, CONTRAST_SPEC sections 27-31)
+CONTRAST_OBJECTIVES = ('variance', 'gradient')
+# the record of an image in the workspace (include/dvsof_contrast_gradient.h)
+CONTRAST_GRADIENT_RECORD = np.dtype([('coef', '<f8'), ('gmax', '<f8'), ('term', '<f8'), ('gm_i', '<f8'),
+                                     ('gm_c', '<u8'), ('lap_max', '<i8')])
+
+
+def contrast_gradient_workspace(ws, F, M, h, w):
+    """The parts of the workspace of dvsof_contrast_gradient_fwd a caller may
+    read, as views of the int64 tensor ``ws``: -> (sums [F, 2, h, w], lap [M, h,
+    w], the M records as int64 [M, 6]: ``CONTRAST_GRADIENT_RECORD`` on the host)."""
+    sums, lap = 2 * F * h * w, M * h * w
+    words = CONTRAST_GRADIENT_RECORD.itemsize // 8
+    return (ws[:sums].view(F, 2, h, w), ws[sums:sums + lap].view(M, h, w),
+            ws[sums + lap:sums + lap + words * M].view(M, words))
+
+
+class _ContrastGradient(torch.autograd.Function):
+    """``_Contrast`` with the gradient-magnitude objective: (weight * term,
+    term) of the finest flow by dvsof_contrast_gradient_fwd / _bwd, whose
+    workspace holds the Laplacian plane the backward gathers."""
+
+    @staticmethod
+    def forward(ctx, flow, x, y, t, p, sample_index, frame_ts, frame_sample, weight, mask, polarity):
+        dev = flow.device
+        flow = flow.detach().contiguous().float()
+        F, _, h, w = flow.shape
+        lib = _lib.lib()
+        M = F * bin(mask).count('1') * (2 if polarity else 1)
+        q = torch.empty(M, h, w, dtype=torch.long, device=dev)
+        count = torch.empty(M, h, w, dtype=torch.int32, device=dev)
+        term = torch.zeros((), dtype=torch.float32, device=dev) if F == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+        nbytes = lib.dvsof_contrast_gradient_workspace_bytes(F, mask, int(polarity), h, w)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.long, device=dev)
+        tables = (frame_ts.contiguous().float(), frame_sample.contiguous().long())
+        assert tables[0].numel() == 2 * F and tables[1].numel() == F, (flow.shape, frame_ts.shape)
+        ctx.form, head, (cols, pol) = _bind_columns(x, y, t, p, sample_index, polarity)
+        ctx.args = (head + [tables[0].data_ptr(), tables[1].data_ptr(),
+                       flow.data_ptr(), F, h, w, mask, int(polarity)])
+        name = 'dvsof_contrast_gradient_fwd' + ctx.form
+        _lib.check(getattr(lib, name)(*ctx.args, q.data_ptr(), count.data_ptr(), term.data_ptr(), ws.data_ptr(),
+                                      nbytes, _lib.stream()), name)
+        ctx.held = (cols, pol, tables, flow, q, ws, nbytes)
+        ctx.weight = float(weight)
+        ctx.mark_non_differentiable(term)
+        ctx.set_materialize_grads(False)
+        return term * ctx.weight, term
+
+    @staticmethod
+    def backward(ctx, g_value, _g_term):
+        if g_value is None:
+            return (None,) * 11
+        flow, q, ws, nbytes = ctx.held[3:]
+        grad = torch.empty_like(flow)
+        seed = g_value.contiguous().float()
+        name = 'dvsof_contrast_gradient_bwd' + ctx.form
+        _lib.check(getattr(_lib.lib(), name)(
+            *ctx.args, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(),
+            _lib.stream()), name)
+        return (grad,) + (None,) * 10
+
+
 # The term on every flow scale (csrc/contrast.hip, CONTRAST_SPEC sections 19-23)
 CONTRAST_SCALES = ('finest', 'all')
 CONTRAST_MAX_LEVELS = 8
@@ -1361,7 +1424,7 @@ class Losses:
         return _FramelessLoss.apply(weights, loss_scale, *flows)
 
     def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None,
-                 references=('start',), polarity=False, scales='finest', tiled=False):
+                 references=('start',), polarity=False, scales='finest', tiled=False, objective='variance'):
         """The contrast-maximisation term of the finest flow ``flows[-1]``
         (docs/CONTRAST_SPEC.md): the mean over the predictions of
         1 - var(image of warped events) / var(count image), negative where the
@@ -1394,7 +1457,23 @@ class Losses:
         (include/dvsof_event_images_tiled.h): the same images, so the same term
         and gradient, bit for bit.  With scales='all' the schedule runs over the
         level table (include/dvsof_event_pyramids_tiled.h, CONTRAST_SPEC section
-        25).  False, the default: the calls above."""
+        25).  False, the default: the calls above.
+
+        objective='gradient': per image 1 - GM(image of warped events) /
+        GM(count image), GM the sum of the squared differences of adjacent
+        pixels (CONTRAST_SPEC sections 27-31,
+        include/dvsof_contrast_gradient.h): the same images, references and
+        polarity, a stencil in place of the variance.  On the finest scale and
+        with the plain splat only: ValueError with scales='all' or ``tiled``.
+        'variance', the default, is everything above and constructs nothing
+        else."""
+        if objective != 'variance':
+            if objective not in CONTRAST_OBJECTIVES:
+                raise ValueError(f'unknown contrast objective "{objective}": one of '
+                                 f'{", ".join(CONTRAST_OBJECTIVES)}')
+            if scales != 'finest' or tiled is not False:
+                raise ValueError(f'the contrast objective "{objective}" runs on the finest scale with the plain '
+                                 f'splat: scales="{scales}" and tiled={tiled!r} are not built for it')
         if scales != 'finest':
             if scales not in CONTRAST_SCALES:
                 raise ValueError(f'unknown contrast scales "{scales}": one of {", ".join(CONTRAST_SCALES)}')
@@ -1409,6 +1488,10 @@ class Losses:
         mask = contrast_reference_mask(references)
         weight_ = 1.0 if weight is None else float(weight)
         _lib.require_cuda(pol)
+        if objective == 'gradient':
+            value, term = _ContrastGradient.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_,
+                                                  mask, bool(polarity))
+            return value if weight is None else (value, term)
         value, term = _Contrast.apply(flow, *cols[:3], pol, cols[3], flow_ts, flow_sample_idx, weight_, mask,
                                       bool(polarity), *((tiled,) if tiled else ()))
         return value if weight is None else (value, term)
@@ -1533,6 +1616,10 @@ class Losses:
         the two terms must agree in ``polarity`` and in ``scales``: ValueError
         otherwise.  tiled: True or 'force', the splat by the tiled schedule
         over the level table, on one scale too."""
+        if contrast.get('objective', 'variance') != 'variance':
+            raise ValueError(f'event_terms: the contrast objective "{contrast["objective"]}" has no joint call: the '
+                             'joint statistics pass computes the variance objective')
+        contrast = {k: v for k, v in contrast.items() if k != 'objective'}
         for name, options in (('contrast', contrast), ('avg_timestamp', avg_timestamp)):
             unknown = set(options) - {'weight', 'references', 'polarity', 'scales'}
             if unknown or options.get('weight') is None:

@@ -338,6 +338,17 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              'level weighing --contrast-weight / K, and logs Train/contrast/<tag> '
                              'per level beside the mean (docs/CONTRAST_SPEC.md sections 19-23).  '
                              'Needs --contrast-weight')
+    parser.add_argument('--contrast-objective', dest='contrast_objective',
+                        default=argparse.SUPPRESS, choices=('variance', 'gradient'),
+                        help='the focus function of the contrast term: variance (the default) is '
+                             '1 - var(I)/var(c); gradient is 1 - GM(I)/GM(c), GM the sum of the squared '
+                             'differences of adjacent pixels (the mean squared gradient magnitude of '
+                             'Gallego et al. 2019; docs/CONTRAST_SPEC.md sections 27-31), which rewards '
+                             'edges and not events piled on a pixel.  Logged under the same '
+                             'Train/contrast and Validation/contrast.  gradient needs a positive '
+                             '--contrast-weight and runs on the finest flow, eagerly: not with '
+                             '--contrast-scales all, --event-images-tiled, --event-pyramids-tiled, '
+                             '--event-terms-joint or --capture-event-terms')
     parser.add_argument('--avg-timestamp-weight', dest='avg_timestamp_weight',
                         default=argparse.SUPPRESS, type=float,
                         help='add this times the average-timestamp term to the training '
@@ -506,10 +517,30 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
-    return validate_event_terms_joint_args(validate_event_pyramids_tiled_args(validate_avg_timestamp_tiled_args(
-        validate_event_images_tiled_args(validate_compact_event_terms_args(validate_capture_event_terms_args(
-            validate_frameless_args(validate_sharpness_args(validate_avg_timestamp_args(
-                validate_contrast_args(args))))))))))
+    return validate_contrast_objective_args(validate_event_terms_joint_args(validate_event_pyramids_tiled_args(
+        validate_avg_timestamp_tiled_args(validate_event_images_tiled_args(validate_compact_event_terms_args(
+            validate_capture_event_terms_args(validate_frameless_args(validate_sharpness_args(
+                validate_avg_timestamp_args(validate_contrast_args(args)))))))))))
+
+
+def validate_contrast_objective_args(args):
+    """--contrast-objective (absent from ``args`` unless given) against what
+    the gradient-magnitude objective needs, the contrast term, and against the
+    flags whose path it does not take.  variance is refused nothing."""
+    if getattr(args, 'contrast_objective', 'variance') == 'variance':
+        return args
+    if not getattr(args, 'contrast_weight', 0.0) > 0:
+        raise SystemExit(f'--contrast-objective {args.contrast_objective} needs a positive --contrast-weight')
+    for given, flag in ((getattr(args, 'contrast_scales', 'finest') != 'finest', '--contrast-scales all'),
+                        (getattr(args, 'event_images_tiled', False), '--event-images-tiled'),
+                        (getattr(args, 'event_pyramids_tiled', False), '--event-pyramids-tiled'),
+                        (getattr(args, 'event_terms_joint', False), '--event-terms-joint'),
+                        (getattr(args, 'capture_event_terms', False), '--capture-event-terms')):
+        if given:
+            raise SystemExit(f'--contrast-objective {args.contrast_objective} cannot be combined with {flag}: the '
+                             'objective runs on the finest flow, eagerly, by its own calls '
+                             '(include/dvsof_contrast_gradient.h)')
+    return args
 
 
 def validate_event_terms_joint_args(args):

@@ -60,10 +60,12 @@ class _TermsAndContrast(tuple):
         return self
 
 
-def _contrast_options(references, polarity, scales='finest', tiled=False):
+def _contrast_options(references, polarity, scales='finest', tiled=False, objective='variance'):
     """The keywords of ``Losses.contrast`` that differ from its defaults, so
     that a run without them makes the call it always made."""
     out = {'tiled': tiled} if tiled else {}
+    if objective != 'variance':
+        out['objective'] = objective
     if scales != 'finest':
         out['scales'] = scales
     if tuple(references) != ('start',):
@@ -73,13 +75,37 @@ def _contrast_options(references, polarity, scales='finest', tiled=False):
     return out
 
 
-def _contrast_keywords(weight, references, polarity, scales='finest', tiled=False):
+def _contrast_keywords(weight, references, polarity, scales='finest', tiled=False, objective='variance'):
     """What a call down the chain gets: nothing at weight 0, and the options
     only where they differ from the defaults."""
     if not weight:
         return {}
     return dict({'contrast_weight': weight},
-                **{'contrast_' + k: v for k, v in _contrast_options(references, polarity, scales, tiled).items()})
+                **{'contrast_' + k: v
+                   for k, v in _contrast_options(references, polarity, scales, tiled, objective).items()})
+
+
+def contrast_objective_refusal(contrast_objective, contrast_weight=0.0, contrast_scales='finest',
+                               contrast_tiled=False, event_pyramids_tiled=False, event_terms_joint=False,
+                               capture_event_terms=False):
+    """Why these options cannot run with this objective of the contrast term
+    (``loss.Losses.contrast(objective=)``), naming the condition, or None.
+    ``train`` and the command line ask this.  'variance' is refused nothing."""
+    from .loss import CONTRAST_OBJECTIVES
+    if contrast_objective not in CONTRAST_OBJECTIVES:
+        return f'"{contrast_objective}" is not one of {", ".join(CONTRAST_OBJECTIVES)}'
+    if contrast_objective == 'variance':
+        return None
+    if not contrast_weight or contrast_weight < 0:
+        return f'{contrast_objective} needs a positive contrast weight'
+    for given, what in ((contrast_scales != 'finest', 'contrast_scales=\'all\' (--contrast-scales all)'),
+                        (contrast_tiled, 'contrast_tiled (--event-images-tiled)'),
+                        (event_pyramids_tiled, 'event_pyramids_tiled (--event-pyramids-tiled)'),
+                        (event_terms_joint, 'event_terms_joint (--event-terms-joint)'),
+                        (capture_event_terms, 'capture_event_terms (--capture-event-terms)')):
+        if given:
+            return f'{contrast_objective} has no form for {what}: it runs on the finest flow, eagerly, by its own calls'
+    return None
 
 
 AVG_TIMESTAMP_REFERENCES = ('start', 'end')
@@ -137,7 +163,7 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   contrast_references=('start',), contrast_polarity=False,
                   contrast_scales='finest', avg_timestamp_scales='finest',
                   contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-                  event_terms_joint=False, avg_timestamp_weight=0.0,
+                  event_terms_joint=False, contrast_objective='variance', avg_timestamp_weight=0.0,
                   avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                   avg_timestamp_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
@@ -157,7 +183,10 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     the [K] tensor of the levels' terms.  'finest', the default, is the call
     as it was.  contrast_tiled: True or 'force': the term's splat by the tiled
     schedule for dense frames (``Losses.contrast``, the same bits); False, the
-    default, passes nothing on.
+    default, passes nothing on.  contrast_objective='gradient': the term's
+    gradient-magnitude objective (``Losses.contrast(objective=)``, CONTRAST_SPEC
+    sections 27-31), on the finest flow with the plain splat and not by the
+    joint call (ValueError); 'variance', the default, passes nothing on.
 
     avg_timestamp_weight > 0: plus avg_timestamp_weight * the average-timestamp
     term of the finest flow over ``events`` (loss.Losses.avg_timestamp,
@@ -221,6 +250,11 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
             loss = loss + weight * mean(per_scale)
     if event_terms_joint and not (contrast_weight and avg_timestamp_weight):
         raise ValueError('event_terms_joint needs both terms: contrast_weight > 0 and avg_timestamp_weight > 0')
+    if contrast_objective != 'variance' and contrast_weight:
+        refusal = contrast_objective_refusal(contrast_objective, contrast_weight, contrast_scales, contrast_tiled,
+                                             False, event_terms_joint)
+        if refusal:
+            raise ValueError('contrast_objective ' + refusal)
     if not contrast_weight and not avg_timestamp_weight:
         return loss, terms
     term = avg_term = None
@@ -247,7 +281,8 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
         if events is None:
             raise ValueError('contrast_weight > 0 needs the raw events of the batch on the device '
                              '(is_raw=True); preprocessed voxel grids carry none')
-        options = _contrast_options(contrast_references, contrast_polarity, contrast_scales, contrast_tiled)
+        options = _contrast_options(contrast_references, contrast_polarity, contrast_scales, contrast_tiled,
+                                    contrast_objective)
         if event_pyramids_tiled and 'scales' in options:
             options['tiled'] = event_pyramids_tiled
         value, term = evaluator.contrast(flows, flow_ts, flow_sample_idx, events, weight=contrast_weight, **options)
@@ -386,18 +421,18 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       contrast_references=('start',), contrast_polarity=False,
                       contrast_scales='finest', avg_timestamp_scales='finest',
                       contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-                      event_terms_joint=False, avg_timestamp_weight=0.0,
+                      event_terms_joint=False, contrast_objective='variance', avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
     """batch (SURVEY 8b wire format, or compact event columns:
     voxel.is_compact) -> (loss, terms, tags[, outputs]).
     contrast_weight > 0 (raw events only, in either column form), contrast_references,
-    contrast_polarity, contrast_scales, and avg_timestamp_weight > 0 (raw
+    contrast_polarity, contrast_scales, contrast_objective, and avg_timestamp_weight > 0 (raw
     events only) with its references, polarity, scales and avg_timestamp_tiled: see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
     the frame size from ``'shape'`` and the loss that reads no frame."""
     contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales,
-                                  contrast_tiled)
+                                  contrast_tiled, contrast_objective)
     if contrast and not is_raw:
         raise ValueError('contrast_weight > 0 needs raw events (is_raw=True)')
     avg = _avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references, avg_timestamp_polarity,
@@ -651,7 +686,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
           capture_event_terms: bool = False, avg_timestamp_scales: str = 'finest',
           contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-          event_terms_joint=False, avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+          event_terms_joint=False, contrast_objective: str = 'variance',
+          avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
     micro-batches per optimizer step (each loss scaled by 1/accumulation_steps),
@@ -719,6 +755,14 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                finest flow too) and refuses contrast_tiled, avg_timestamp_tiled
                and a step captured with ``capture_event_terms`` (ValueError).
                (By name)
+    contrast_objective:  'gradient': the contrast term's gradient-magnitude
+               objective (``loss.Losses.contrast(objective=)``), logged under
+               the same ``Train/contrast``.  Needs a positive contrast_weight
+               and has no form for contrast_scales='all', contrast_tiled,
+               event_pyramids_tiled, event_terms_joint or capture_event_terms
+               (ValueError, ``contrast_objective_refusal``); with ``capture``
+               the loop runs eagerly and says so.  'variance' (the default):
+               the step launches what it launches without it.  (By name)
     avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
                the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
                events only), logged as ``Train/avg timestamp``, beside the
@@ -760,6 +804,11 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     captured = None
     # the opt-in: the captured step carries the events-only terms that are asked for
     event_terms = {}
+    if contrast_objective != 'variance':
+        refusal = contrast_objective_refusal(contrast_objective, contrast_weight, contrast_scales, contrast_tiled,
+                                             event_pyramids_tiled, event_terms_joint, capture and capture_event_terms)
+        if refusal:
+            raise ValueError('contrast_objective ' + refusal)
     if contrast_tiled and contrast_weight and ((capture and capture_event_terms) or contrast_scales != 'finest'):
         raise ValueError('contrast_tiled has no form for contrast_scales=\'all\' or a step captured with '
                          'capture_event_terms')
@@ -794,6 +843,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
     else:
         refused = (avg_timestamp_capture_refusal(avg_timestamp_weight)
                    or capture_refusal(optimizer, is_raw, model, contrast_weight)) if capture else None
+        if refused and contrast_objective != 'variance':
+            refused += f' (contrast objective {contrast_objective}: dvsof_contrast_gradient_fwd / _bwd)'
     if refused:
         import sys
         print(f'capture: not used, the loop runs eagerly: {refused}', file=sys.stderr)
@@ -834,7 +885,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
             loss, terms, tags = process_minibatch(
                 model, batch, timers, device, is_raw, evaluator, weights,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
-                                     contrast_scales, contrast_tiled),
+                                     contrast_scales, contrast_tiled, contrast_objective),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
                                           avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled),
                 **({'event_pyramids_tiled': event_pyramids_tiled} if event_pyramids_tiled else {}),
@@ -916,7 +967,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
              weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
              contrast_references=('start',), contrast_polarity=False,
              contrast_scales='finest', avg_timestamp_scales='finest', contrast_tiled=False,
-             avg_timestamp_tiled=False, avg_timestamp_weight=0.0,
+             avg_timestamp_tiled=False, contrast_objective='variance', avg_timestamp_weight=0.0,
              avg_timestamp_references=AVG_TIMESTAMP_REFERENCES, avg_timestamp_polarity=False):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
@@ -926,8 +977,8 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
     avg_timestamp_weight > 0 it holds the average-timestamp term as well,
     written as ``Validation/avg timestamp``; with avg_timestamp_scales='all'
     that is the mean of the levels' terms, each written as ``Validation/avg
-    timestamp/<tag>`` beside it.  contrast_tiled, avg_timestamp_tiled: as
-    ``train`` takes them."""
+    timestamp/<tag>`` beside it.  contrast_tiled, avg_timestamp_tiled,
+    contrast_objective: as ``train`` takes them."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -936,7 +987,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
             loss, terms, tags = process_minibatch(
                 model, batch, quiet, device, is_raw, evaluator, weights,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
-                                     contrast_scales, contrast_tiled),
+                                     contrast_scales, contrast_tiled, contrast_objective),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
                                           avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled))
             sums.add(loss, terms, tags)

@@ -501,7 +501,9 @@ def main(argv=None):
                 'contrast_references': getattr(args, 'contrast_references', ('start',)),
                 'contrast_polarity': getattr(args, 'contrast_polarity', False),
                 'contrast_scales': getattr(args, 'contrast_scales', 'finest'),
-                **({'contrast_tiled': True} if getattr(args, 'event_images_tiled', False) else {})}
+                **({'contrast_tiled': True} if getattr(args, 'event_images_tiled', False) else {}),
+                **({'contrast_objective': args.contrast_objective}
+                   if getattr(args, 'contrast_objective', 'variance') != 'variance' else {})}
                if getattr(args, 'contrast_weight', 0.0) else {}),
             **avg_timestamp_keywords(args))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
@@ -541,7 +543,9 @@ def main(argv=None):
                   **({'event_pyramids_tiled': True}
                      if getattr(args, 'event_pyramids_tiled', False) else {}),
                   **({'event_terms_joint': True}
-                     if getattr(args, 'event_terms_joint', False) else {}))
+                     if getattr(args, 'event_terms_joint', False) else {}),
+                  **({'contrast_objective': args.contrast_objective}
+                     if getattr(args, 'contrast_objective', 'variance') != 'variance' else {}))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
