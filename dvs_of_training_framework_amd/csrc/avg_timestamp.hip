@@ -23,15 +23,19 @@
 // element converts and clears.  No floating-point atomics, kernels only.  This
 // file relies on -ffp-contract=off.
 //
-// At the end of the file: the term on every flow scale of the network by one
-// fill, one splat, one closing wave and one backward for all levels (sections
-// 11-15, include/dvsof_avg_timestamp_pyramid.h).  What one event does to the
-// images of a frame, forward and backward, is stated once (avgts_splat_event
-// of avg_timestamp_images.h, avgts_bwd_event) and used by the one-level
-// kernels and by those.  Behind that: this term and the contrast term of
+// The term on every flow scale of the network (sections 11-15,
+// include/dvsof_avg_timestamp_pyramid.h) is the same kernels and the same host
+// functions over a level table: each is written once against a view of the
+// call's levels (event_term_levels.h) and instantiated for one flow and for a
+// table, with one fill, one splat, one closing wave and one backward for all
+// levels.  What one event does to the images of a frame, forward and backward,
+// is stated once (avgts_splat_event of avg_timestamp_images.h,
+// avgts_bwd_event).  Behind that: this term and the contrast term of
 // contrast.hip together, from this term's splat (section 19,
 // include/dvsof_event_terms_joint.h).
+#include <type_traits>
 #include "avg_timestamp_images.h"
+#include "event_term_levels.h"
 #include "event_term_records.h"
 #include "tiled_splat.h"
 #include "../../include/dvsof_avg_timestamp.h"
@@ -62,20 +66,29 @@ static_assert(sizeof(ImageRec) == 64, "the workspace holds 64 bytes per image");
 // and the statistics of an image (StatRow, AvgSum, avgts_stats_partial_kernel)
 // are those of avg_timestamp_images.h, which the validation metric of iwe.hip
 // shares.  Here: the event loop and the frame rule of contrast_splat_kernel.
+// The columns are read, the frames walked and tau computed once per event; the
+// levels are a runtime loop around avgts_splat_event with the event's level
+// pixel (y >> s, x >> s), the level's flow, plane and images.
 // ---------------------------------------------------------------------------
-template <int R, bool POL, class Cols>
+template <int R, bool POL, class Cols, class View>
 __global__ __launch_bounds__(NT) void avgts_splat_kernel(
     const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
+    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const View view,
     unsigned long long *__restrict__ q, unsigned long long *__restrict__ s, unsigned long long *__restrict__ base,
     uint32_t *__restrict__ count)
 {
-    const size_t plane = (size_t)h * w;
-    const auto splat = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
-        const size_t pix = (size_t)yi * w + (size_t)xi;
-        float u, v;
-        flow_at(flow, f, plane, pix, u, v);
-        avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, s, base, count);
+    const auto splat = [=, &view](int64_t xi, int64_t yi, int c, int f, float tau) {
+#pragma unroll 1
+        for (int k = 0; k < view.levels(); ++k) {
+            const Level &L = view.at(k);
+            const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
+            const size_t plane = (size_t)L.h * L.w;
+            const size_t pix = (size_t)ys * L.w + (size_t)xs;
+            float u, v;
+            flow_at(L.flow, f, plane, pix, u, v);
+            avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
+                                      s + L.image_offset, base + L.image_offset, count + L.image_offset);
+        }
     };
     for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
 }
@@ -96,24 +109,34 @@ __device__ __forceinline__ ImageRec record_of(const StatRow &r)
     return o;
 }
 
-// One wave: the record of every image (lane k takes images k, k + 64, ...);
-// after a barrier the unit of every frame (lane k takes frames k, k + 64, ...;
-// a maximum has no order) and, in lane 0, the images' values in image order.
+// One wave over the K M images and K F units of all levels (image i = k M + m, unit j = k F + f,
+// whose images are i = j RC ...): the record of every image (lane k takes images k, k + 64, ...);
+// after a barrier the unit of every frame (lane k takes frames k, k + 64, ...; a maximum has no
+// order) and, in lane 0, every level's term in image order.  Over a table also the weighted sum
+// in level order; on one flow terms is the call's term and value is not written.
+template <class View>
 __global__ __launch_bounds__(kWave) void avgts_close_kernel(const StatRow *__restrict__ rows, int F, int RC,
-                                                            int unit_bits, ImageRec *rec, double *unit, float *term)
+                                                            int unit_bits, const View view, ImageRec *rec,
+                                                            double *unit, float *terms, float *value)
 {
-    const int M = F * RC;
-    for (int m = threadIdx.x; m < M; m += kWave) rec[m] = record_of(rows[m]);
+    const int M = F * RC, K = view.levels();
+    for (int i = threadIdx.x; i < K * M; i += kWave) rec[i] = record_of(rows[i]);
     __syncthreads();
-    for (int f = threadIdx.x; f < F; f += kWave) {
+    for (int j = threadIdx.x; j < K * F; j += kWave) {
         double gmax = 0.0;
-        for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[f * RC + k].gmax);
-        unit[f] = unit_of(gmax, unit_bits);
+        for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[(size_t)j * RC + k].gmax);
+        unit[j] = unit_of(gmax, unit_bits);
     }
     if (threadIdx.x == 0) {
-        double sum = 0.0;
-        for (int m = 0; m < M; ++m) sum += rec[m].value;
-        *term = (float)(sum / (double)M);
+        double total = 0.0;
+        for (int k = 0; k < K; ++k) {
+            double sum = 0.0;
+            for (int m = 0; m < M; ++m) sum += rec[(size_t)k * M + m].value;
+            const double term = sum / (double)M;
+            terms[k] = (float)term;
+            if (View::kTable) total += (double)view.at(k).weight * term;
+        }
+        if (View::kTable) *value = (float)total;
     }
 }
 
@@ -122,8 +145,9 @@ __global__ __launch_bounds__(kWave) void avgts_close_kernel(const StatRow *__res
 // G = 2 k T D (a - T) at the four corners of the image of its channel (0
 // outside the image), the derivative of the bilinear weights, -sig of it to
 // the event's own pixel of the flow, in float64, truncated to the frame's unit
-// un.  The event of avgts_splat_event; q, s and rec start at the images of this
-// shape.  The R addends are added to su, sv in registers (integers: no order).
+// un (corner_addends of event_term_levels.h).  The event of avgts_splat_event;
+// q, s and rec start at the images of this shape.  The R addends are added to
+// su, sv in registers (integers: no order).
 // ---------------------------------------------------------------------------
 template <int R, bool POL>
 __device__ __forceinline__ void avgts_bwd_event(const Refs &refs, int f, int c, float tau, float u, float v,
@@ -142,342 +166,29 @@ __device__ __forceinline__ void avgts_bwd_event(const Refs &refs, int f, int c, 
         if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
         const double a = (double)fabsf(p.tau);
         const int64_t *qm = q + m * plane, *sm = s + m * plane;
-        double G[2][2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int xx = p.cx + i, yy = p.cy + j;
-                const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
-                double g = 0.0;
-                if (in) {
-                    const size_t at = (size_t)yy * w + (size_t)xx;
-                    const double den = (double)qm[at] * 0x1p-32 + kEps;
-                    const double T = (double)sm[at] * 0x1p-32 / den;
-                    const double D = 1.0 / den;
-                    g = k2 * T * D * (a - T);
-                }
-                G[j][i] = g;
-            }
-        }
-        const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
-        const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
-        const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
-        su += (long long)(ms * gx * un);
-        sv += (long long)(ms * gy * un);
+        const auto G_at = [&](size_t at) {
+            const double den = (double)qm[at] * 0x1p-32 + kEps;
+            const double T = (double)sm[at] * 0x1p-32 / den;
+            const double D = 1.0 / den;
+            return k2 * T * D * (a - T);
+        };
+        corner_addends(p, h, w, un, G_at, su, sv);
     }
 }
 
-template <int R, bool POL, class Cols>
+// per level as in the splat; the sums of a level start at its sums_offset
+template <int R, bool POL, class Cols, class View>
 __global__ __launch_bounds__(NT) void avgts_bwd_events_kernel(
     const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
-    const int64_t *__restrict__ q, const int64_t *__restrict__ s, const ImageRec *__restrict__ rec,
-    const double *__restrict__ unit, unsigned long long *__restrict__ acc)
-{
-    const size_t plane = (size_t)h * w;
-    const auto addends = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
-        const size_t pix = (size_t)yi * w + (size_t)xi;
-        float u, v;
-        flow_at(flow, f, plane, pix, u, v);
-        long long su = 0, sv = 0;
-        avgts_bwd_event<R, POL>(refs, f, c, tau, u, v, xi, yi, plane, h, w, q, s, rec, unit[f], su, sv);
-        unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
-        if (su != 0) atomicAdd(dst, (unsigned long long)su);
-        if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
-    };
-    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
-}
-
-// One thread per element of grad_flow: convert, clear the sum for the next
-// backward of the same forward, store.
-__global__ __launch_bounds__(NT) void avgts_bwd_close_kernel(long long *__restrict__ acc,
-                                                             const double *__restrict__ unit,
-                                                             const float *__restrict__ seed, float weight, int F,
-                                                             int M, size_t per_frame, float *__restrict__ grad)
-{
-    const size_t total = (size_t)F * per_frame, stride = (size_t)gridDim.x * NT;
-    const float sw = seed[0] * weight;
-    for (size_t k = (size_t)blockIdx.x * NT + threadIdx.x; k < total; k += stride) {
-        const long long a = acc[k];
-        acc[k] = 0;
-        const double value = (double)a / unit[k / per_frame] / (double)M;  // the first division is exact
-        grad[k] = sw * (float)value;
-    }
-}
-
-// the workspace as byte offsets, in the order of the header
-struct Layout {
-    size_t s, base, sums, count, zeroed_bytes, rec, unit, rows, part, bytes;
-    int nb;
-};
-
-Layout layout_of(int F, int h, int w, const Plan &pl)
-{
-    const size_t P = (size_t)pl.M * h * w, S = 2 * (size_t)F * h * w;
-    Layout o;
-    o.nb = partial_blocks(h, w);
-    o.s = sizeof(int64_t) * P;
-    o.base = o.s + sizeof(int64_t) * P;
-    o.sums = o.base + sizeof(int64_t) * P;
-    o.count = o.sums + sizeof(int64_t) * S;
-    o.zeroed_bytes = o.count + sizeof(uint32_t) * P;
-    o.rec = (o.zeroed_bytes + 7) / 8 * 8;
-    o.unit = o.rec + sizeof(ImageRec) * (size_t)pl.M;
-    o.rows = o.unit + sizeof(double) * (size_t)F;
-    o.part = o.rows + sizeof(StatRow) * (size_t)pl.M;
-    o.bytes = o.part + sizeof(StatRow) * (size_t)pl.M * o.nb;
-    return o;
-}
-
-// The refusals both calls share, in the order of dvsof_contrast_multi_fwd; outputs: the call's
-// own pointers are all there.  DVSOF_OK with F == 0: nothing to do.
-template <class Cols>
-int check_call(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
-               const float *flow, int F, int h, int w, int reference_mask, int polarity, bool outputs,
-               const void *workspace, size_t workspace_bytes, Plan &pl)
-{
-    if (F < 0 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return DVSOF_EINVAL;
-    if (F == 0) return DVSOF_OK;
-    if (bad_frame_sizes(F, h, w) || !outputs || !frame_ts || !frame_sample || !flow) return DVSOF_EINVAL;
-    if (n_events > 0 && !cols.given(polarity)) return DVSOF_EINVAL;
-    if (!workspace || workspace_bytes < layout_of(F, h, w, pl).bytes) return DVSOF_ENOSPACE;
-    return DVSOF_OK;
-}
-
-// dvsof_avg_timestamp_fwd / _bwd on either form of the event columns (event_columns.h)
-template <class Cols>
-int one_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
-            const float *flow, int F, int h, int w, int reference_mask, int polarity, float *term, void *workspace,
-            size_t workspace_bytes, void *stream, const TiledSplat tiled = TiledSplat{nullptr, 0, -1})
-{
-    Plan pl;
-    const int rc = check_call(cols, n_events, frame_ts, frame_sample, flow, F, h, w, reference_mask, polarity,
-                              term != nullptr, workspace, workspace_bytes, pl);
-    if (rc != DVSOF_OK || F == 0) return rc;
-    TilePlan tp;
-    const int by_tiles = tile_decide<AvgtsImages>(tiled, F, reference_mask, polarity, h, w, n_events, tp);
-    if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
-    hipStream_t st = as_stream(stream);
-    const Layout lay = layout_of(F, h, w, pl);
-    char *ws = (char *)workspace;
-    DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, lay.zeroed_bytes, st));
-    if (by_tiles == DVSOF_OK) {
-        const AvgtsImages img{(int64_t *)ws, (int64_t *)(ws + lay.s), (int64_t *)(ws + lay.base),
-                              (uint32_t *)(ws + lay.count)};
-        const int rs = TiledLaunch<AvgtsImages>::term(plain(cols), n_events, frame_ts, frame_sample, flow, F, h, w,
-                                                      reference_mask, polarity, tp, img, tiled.workspace, st);
-        if (rs != DVSOF_OK) return rs;
-    } else if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
-                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs,
-                                (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
-                                (unsigned long long *)(ws + lay.base), (uint32_t *)(ws + lay.count));
-        DVSOF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(avgts_stats_partial_kernel, dim3((unsigned)lay.nb, (unsigned)pl.M), dim3(NT), 0, st,
-                       (const int64_t *)ws, (const int64_t *)(ws + lay.s), (const int64_t *)(ws + lay.base),
-                       (const uint32_t *)(ws + lay.count), h, w, lay.nb, (StatRow *)(ws + lay.part));
-    DVSOF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frame_final_kernel<AvgSum>, dim3((unsigned)pl.M), dim3(kWave), 0, st,
-                       (const StatRow *)(ws + lay.part), lay.nb, (StatRow *)(ws + lay.rows));
-    DVSOF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(avgts_close_kernel, dim3(1), dim3(kWave), 0, st, (const StatRow *)(ws + lay.rows), F,
-                       pl.R * pl.C, pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, (ImageRec *)(ws + lay.rec),
-                       (double *)(ws + lay.unit), term);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
-}
-
-template <class Cols>
-int one_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
-            const float *flow, int F, int h, int w, int reference_mask, int polarity, void *workspace,
-            size_t workspace_bytes, const float *seed, float weight, float *grad_flow, void *stream)
-{
-    Plan pl;
-    const int rc = check_call(cols, n_events, frame_ts, frame_sample, flow, F, h, w, reference_mask, polarity,
-                              seed && grad_flow, workspace, workspace_bytes, pl);
-    if (rc != DVSOF_OK || F == 0) return rc;
-    hipStream_t st = as_stream(stream);
-    const Layout lay = layout_of(F, h, w, pl);
-    char *ws = (char *)workspace;
-    if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
-                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, (const int64_t *)ws,
-                                (const int64_t *)(ws + lay.s), (const ImageRec *)(ws + lay.rec),
-                                (const double *)(ws + lay.unit), (unsigned long long *)(ws + lay.sums));
-        DVSOF_LAUNCH_CHECK();
-    }
-    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
-    hipLaunchKernelGGL(avgts_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
-                       (long long *)(ws + lay.sums), (const double *)(ws + lay.unit), seed, weight, F, pl.M,
-                       per_frame, grad_flow);
-    DVSOF_LAUNCH_CHECK();
-    return DVSOF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t dvsof_avg_timestamp_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
-{
-    Plan pl;
-    if (F < 1 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return 0;
-    return layout_of(F, h, w, pl).bytes;
-}
-
-int dvsof_avg_timestamp_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
-                            const int64_t *sample_index, int64_t n_events, const float *frame_ts,
-                            const int64_t *frame_sample, const float *flow, int F, int h, int w,
-                            int reference_mask, int polarity, float *term, void *workspace,
-                            size_t workspace_bytes, void *stream)
-{
-    return one_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
-                   reference_mask, polarity, term, workspace, workspace_bytes, stream);
-}
-
-int dvsof_avg_timestamp_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
-                            const int64_t *sample_index, int64_t n_events, const float *frame_ts,
-                            const int64_t *frame_sample, const float *flow, int F, int h, int w,
-                            int reference_mask, int polarity, void *workspace, size_t workspace_bytes,
-                            const float *seed, float weight, float *grad_flow, void *stream)
-{
-    return one_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
-                   reference_mask, polarity, workspace, workspace_bytes, seed, weight, grad_flow, stream);
-}
-
-// The encoded twins (include/dvsof_event_terms_encoded.h)
-int dvsof_avg_timestamp_fwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
-                                    const int64_t *sample_event_offsets, int B, int64_t n_events,
-                                    const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
-                                    int h, int w, int reference_mask, int polarity_channels, float *term,
-                                    void *workspace, size_t workspace_bytes, void *stream)
-{
-    return one_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
-                   flow, F, h, w, reference_mask, polarity_channels, term, workspace, workspace_bytes, stream);
-}
-
-int dvsof_avg_timestamp_bwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
-                                    const int64_t *sample_event_offsets, int B, int64_t n_events,
-                                    const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
-                                    int h, int w, int reference_mask, int polarity_channels, void *workspace,
-                                    size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
-                                    void *stream)
-{
-    return one_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
-                   flow, F, h, w, reference_mask, polarity_channels, workspace, workspace_bytes, seed, weight,
-                   grad_flow, stream);
-}
-
-// The tiled twins (include/dvsof_avg_timestamp_tiled.h): the forward above with the splat by tiles
-int dvsof_avg_timestamp_fwd_tiled(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
-                                  const int64_t *sample_index, int64_t n_events, const float *frame_ts,
-                                  const int64_t *frame_sample, const float *flow, int F, int h, int w,
-                                  int reference_mask, int polarity, float *term, void *workspace,
-                                  size_t workspace_bytes, void *stream, void *tile_workspace,
-                                  size_t tile_workspace_bytes, int mode)
-{
-    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
-    return one_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, flow, F, h, w,
-                   reference_mask, polarity, term, workspace, workspace_bytes, stream,
-                   TiledSplat{tile_workspace, tile_workspace_bytes, mode});
-}
-
-int dvsof_avg_timestamp_fwd_encoded_tiled(const int16_t *x, const int16_t *y, const float *t,
-                                          const uint8_t *polarity, const int64_t *sample_event_offsets, int B,
-                                          int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
-                                          const float *flow, int F, int h, int w, int reference_mask,
-                                          int polarity_channels, float *term, void *workspace,
-                                          size_t workspace_bytes, void *stream, void *tile_workspace,
-                                          size_t tile_workspace_bytes, int mode)
-{
-    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
-    return one_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
-                   flow, F, h, w, reference_mask, polarity_channels, term, workspace, workspace_bytes, stream,
-                   TiledSplat{tile_workspace, tile_workspace_bytes, mode});
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// The term on every flow scale (docs/AVG_TIMESTAMP_SPEC.md sections 11-15).
-// The columns are read, the frames walked and tau computed once per event; the
-// levels are a runtime loop around avgts_splat_event / avgts_bwd_event with the
-// event's level pixel (y >> s, x >> s), the level's flow, plane and images.
-// Per level the bytes are those of the kernels above at the level's shape.
-// ---------------------------------------------------------------------------
-namespace {
-
-using Levels = dvsof_contrast_levels_t;
-using Level = dvsof_contrast_level_t;
-constexpr int kMaxLevels = 8;
-constexpr int kMaxShift = 15;
-static_assert(sizeof(Levels::level) / sizeof(Level) == kMaxLevels, "the table holds eight levels");
-
-template <int R, bool POL, class Cols>
-__global__ __launch_bounds__(NT) void avgts_pyramid_splat_kernel(
-    const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
-    unsigned long long *__restrict__ q, unsigned long long *__restrict__ s, unsigned long long *__restrict__ base,
-    uint32_t *__restrict__ count)
-{
-    const auto splat = [=, &lv](int64_t xi, int64_t yi, int c, int f, float tau) {
-#pragma unroll 1
-        for (int k = 0; k < lv.K; ++k) {
-            const Level &L = lv.level[k];
-            const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
-            const size_t plane = (size_t)L.h * L.w;
-            const size_t pix = (size_t)ys * L.w + (size_t)xs;
-            float u, v;
-            flow_at(L.flow, f, plane, pix, u, v);
-            avgts_splat_event<R, POL>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
-                                      s + L.image_offset, base + L.image_offset, count + L.image_offset);
-        }
-    };
-    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
-}
-
-// avgts_close_kernel over the K M images and K F units of all levels (image i = k M + m, unit
-// j = k F + f, whose images are i = j RC ...), then in lane 0 every level's term in image order
-// and the weighted sum in level order.
-__global__ __launch_bounds__(kWave) void avgts_pyramid_close_kernel(const StatRow *__restrict__ rows, int F, int RC,
-                                                                    int unit_bits, const Levels lv, ImageRec *rec,
-                                                                    double *unit, float *terms, float *value)
-{
-    const int M = F * RC, K = lv.K;
-    for (int i = threadIdx.x; i < K * M; i += kWave) rec[i] = record_of(rows[i]);
-    __syncthreads();
-    for (int j = threadIdx.x; j < K * F; j += kWave) {
-        double gmax = 0.0;
-        for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[(size_t)j * RC + k].gmax);
-        unit[j] = unit_of(gmax, unit_bits);
-    }
-    if (threadIdx.x == 0) {
-        double total = 0.0;
-        for (int k = 0; k < K; ++k) {
-            double sum = 0.0;
-            for (int m = 0; m < M; ++m) sum += rec[(size_t)k * M + m].value;
-            const double term = sum / (double)M;
-            terms[k] = (float)term;
-            total += (double)lv.level[k].weight * term;
-        }
-        *value = (float)total;
-    }
-}
-
-template <int R, bool POL, class Cols>
-__global__ __launch_bounds__(NT) void avgts_pyramid_bwd_events_kernel(
-    const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
+    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const View view,
     const int64_t *__restrict__ q, const int64_t *__restrict__ s, const ImageRec *__restrict__ rec,
     const double *__restrict__ unit, unsigned long long *__restrict__ acc)
 {
     const size_t M = (size_t)F * R * (POL ? 2 : 1);
-    const auto addends = [=, &lv](int64_t xi, int64_t yi, int c, int f, float tau) {
+    const auto addends = [=, &view](int64_t xi, int64_t yi, int c, int f, float tau) {
 #pragma unroll 1
-        for (int k = 0; k < lv.K; ++k) {
-            const Level &L = lv.level[k];
+        for (int k = 0; k < view.levels(); ++k) {
+            const Level &L = view.at(k);
             const int64_t xs = xi >> L.shift, ys = yi >> L.shift;
             const size_t plane = (size_t)L.h * L.w;
             const size_t pix = (size_t)ys * L.w + (size_t)xs;
@@ -494,51 +205,21 @@ __global__ __launch_bounds__(NT) void avgts_pyramid_bwd_events_kernel(
     for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
 }
 
-// One thread per element of every level's grad_flow: avgts_bwd_close_kernel with the level
-// found from the element's place in the sums.
-__global__ __launch_bounds__(NT) void avgts_pyramid_bwd_close_kernel(long long *__restrict__ acc,
-                                                                     const double *__restrict__ unit,
-                                                                     const float *__restrict__ seed, int F, int M,
-                                                                     const Levels lv, size_t total)
-{
-    const size_t stride = (size_t)gridDim.x * NT;
-    const float s0 = seed[0];
-    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < total; i += stride) {
-        int k = 0;
-        while (k + 1 < lv.K && i >= lv.level[k + 1].sums_offset) ++k;
-        const Level &L = lv.level[k];
-        const size_t local = i - L.sums_offset, per_frame = 2 * (size_t)L.h * L.w;
-        const float sw = s0 * L.weight;
-        const long long a = acc[i];
-        acc[i] = 0;
-        const double value = (double)a / unit[(size_t)k * F + local / per_frame] / (double)M;
-        L.grad_flow[local] = sw * (float)value;
-    }
-}
-
-// the workspace as byte offsets, in the order of the header
+// the workspace as byte offsets, in the order of the headers (a call on one flow: K = 1)
 struct PyramidLayout {
     size_t s, base, sums, count, zeroed_bytes, rec, unit, rows, part, bytes;
     size_t sums_elems;
 };
 
 // false: a table the calls refuse.  The offsets are looked at only where check_offsets is set
-// (dvsof_avg_timestamp_pyramid_workspace_bytes reads the shapes alone).
+// (the workspace_bytes calls read the shapes alone).
 bool pyramid_layout(int F, int h, int w, const Plan &pl, const Levels &lv, bool check_offsets, PyramidLayout &o)
 {
-    if (lv.K < 1 || lv.K > kMaxLevels || bad_frame_sizes(F, h, w)) return false;
-    size_t pixels = 0;
+    const size_t pixels = level_table_pixels(F, h, w, lv, check_offsets ? pl.M : 0);
+    if (pixels == 0) return false;
     int nb = 0;
     for (int k = 0; k < lv.K; ++k) {
-        const Level &L = lv.level[k];
-        if (bad_frame_sizes(F, L.h, L.w) || L.shift < 0 || L.shift > kMaxShift) return false;
-        const int round = (1 << L.shift) - 1;
-        if (L.h != (h + round) >> L.shift || L.w != (w + round) >> L.shift) return false;
-        if (check_offsets && (L.image_offset != (size_t)pl.M * pixels || L.row_offset != (size_t)k * pl.M ||
-                              L.sums_offset != 2 * (size_t)F * pixels))
-            return false;
-        pixels += (size_t)L.h * L.w;
-        const int need = partial_blocks(L.h, L.w);
+        const int need = partial_blocks(lv.level[k].h, lv.level[k].w);
         nb = need > nb ? need : nb;
     }
     const size_t P = (size_t)pl.M * pixels, KM = (size_t)lv.K * pl.M;
@@ -556,10 +237,13 @@ bool pyramid_layout(int F, int h, int w, const Plan &pl, const Levels &lv, bool 
     return true;
 }
 
-// The refusals both calls share up to the workspace, in the order of the header; outputs: the
-// call's own pointers are all there.  DVSOF_OK with F == 0: nothing to do.  The level table of
-// the contrast term has the same packed offsets at its own M and the same refusals
-// (dvsof_contrast_pyramid.h), so the joint calls at the end of the file ask this for either term.
+// The refusals both calls share up to the workspace, in the order of the headers; outputs: the
+// call's own pointers are all there.  DVSOF_OK with F == 0: nothing to do.  A call on one flow
+// asks with its table of one level: its flow and grad_flow are the level's, and every refusal
+// between F == 0 and the columns is DVSOF_EINVAL, so code and order are those of
+// dvsof_contrast_multi_fwd.  The level table of the contrast term has the same packed offsets at
+// its own M and the same refusals (dvsof_contrast_pyramid.h), so the joint calls at the end of
+// the file ask this for either term.
 template <class Cols>
 int pyramid_refusals(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F,
                      int h, int w, int reference_mask, int polarity, const Levels &lv, bool backward, bool outputs,
@@ -587,21 +271,36 @@ int pyramid_check(const Cols &cols, int64_t n_events, const float *frame_ts, con
     return DVSOF_OK;
 }
 
-// dvsof_avg_timestamp_pyramid_fwd / _bwd on either form of the event columns
-template <class Cols>
-int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
-                int w, int reference_mask, int polarity, const Levels &levels, float *terms, float *value,
-                void *workspace, size_t workspace_bytes, void *stream,
-                const TiledSplat tiled = TiledSplat{nullptr, 0, -1})
+// 0 for arguments the calls refuse
+size_t term_workspace_bytes(int F, int reference_mask, int polarity, int h, int w, const Levels &levels)
 {
     Plan pl;
     PyramidLayout lay;
+    if (F < 1 || !plan_of(F, reference_mask, polarity, pl) || !pyramid_layout(F, h, w, pl, levels, false, lay))
+        return 0;
+    return lay.bytes;
+}
+
+// dvsof_avg_timestamp_fwd / _bwd (View: OneLevel; terms is the call's term, value is null) and
+// dvsof_avg_timestamp_pyramid_fwd / _bwd (TableView) on either form of the event columns
+// (event_columns.h).  The two tiled schedules stay apart (tiled_splat.h): the view picks one.
+template <class Cols, class View>
+int term_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
+             int w, int reference_mask, int polarity, const View &view, float *terms, float *value, void *workspace,
+             size_t workspace_bytes, void *stream, const TiledSplat tiled = TiledSplat{nullptr, 0, -1})
+{
+    const Levels levels = view.table();
+    Plan pl;
+    PyramidLayout lay;
     const int rc = pyramid_check(cols, n_events, frame_ts, frame_sample, F, h, w, reference_mask, polarity, levels,
-                                 false, terms && value, workspace, workspace_bytes, pl, lay);
+                                 false, terms && (value || !View::kTable), workspace, workspace_bytes, pl, lay);
     if (rc != DVSOF_OK || F == 0) return rc;
-    PyramidTilePlan tp;
-    const int by_tiles =
-        pyramid_tile_decide<AvgtsImages>(tiled, F, reference_mask, polarity, h, w, levels, n_events, tp);
+    std::conditional_t<View::kTable, PyramidTilePlan, TilePlan> tp;
+    int by_tiles;
+    if constexpr (View::kTable)
+        by_tiles = pyramid_tile_decide<AvgtsImages>(tiled, F, reference_mask, polarity, h, w, levels, n_events, tp);
+    else
+        by_tiles = tile_decide<AvgtsImages>(tiled, F, reference_mask, polarity, h, w, n_events, tp);
     if (by_tiles != DVSOF_OK && by_tiles != 1) return by_tiles;
     hipStream_t st = as_stream(stream);
     char *ws = (char *)workspace;
@@ -609,18 +308,22 @@ int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const
     if (by_tiles == DVSOF_OK) {
         const AvgtsImages img{(int64_t *)ws, (int64_t *)(ws + lay.s), (int64_t *)(ws + lay.base),
                               (uint32_t *)(ws + lay.count)};
-        const int rs = TiledLaunch<AvgtsImages>::pyramid(plain(cols), n_events, frame_ts, frame_sample, F, h, w,
-                                                         reference_mask, polarity, levels, tp, img, tiled.workspace,
-                                                         st);
+        int rs;
+        if constexpr (View::kTable)
+            rs = TiledLaunch<AvgtsImages>::pyramid(plain(cols), n_events, frame_ts, frame_sample, F, h, w,
+                                                   reference_mask, polarity, levels, tp, img, tiled.workspace, st);
+        else
+            rs = TiledLaunch<AvgtsImages>::term(plain(cols), n_events, frame_ts, frame_sample, view.flow, F, h, w,
+                                                reference_mask, polarity, tp, img, tiled.workspace, st);
         if (rs != DVSOF_OK) return rs;
     } else if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_pyramid_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
-                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
+        DVSOF_REFS_POL_DISPATCH(avgts_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, view,
                                 (unsigned long long *)ws, (unsigned long long *)(ws + lay.s),
                                 (unsigned long long *)(ws + lay.base), (uint32_t *)(ws + lay.count));
         DVSOF_LAUNCH_CHECK();
     }
-    // per level the two launches of the one-level call with its own nb: that order makes the bytes
+    // per level the two launches of the statistics with its own nb: that order makes the bytes
     for (int k = 0; k < levels.K; ++k) {
         const Level &L = levels.level[k];
         const int nb = partial_blocks(L.h, L.w);
@@ -634,18 +337,19 @@ int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const
                            (const StatRow *)(ws + lay.part), nb, (StatRow *)(ws + lay.rows) + L.row_offset);
         DVSOF_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(avgts_pyramid_close_kernel, dim3(1), dim3(kWave), 0, st, (const StatRow *)(ws + lay.rows), F,
-                       pl.R * pl.C, pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, levels,
-                       (ImageRec *)(ws + lay.rec), (double *)(ws + lay.unit), terms, value);
+    hipLaunchKernelGGL(avgts_close_kernel<View>, dim3(1), dim3(kWave), 0, st, (const StatRow *)(ws + lay.rows), F,
+                       pl.R * pl.C, pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, view, (ImageRec *)(ws + lay.rec),
+                       (double *)(ws + lay.unit), terms, value);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
 
-template <class Cols>
-int pyramid_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
-                int w, int reference_mask, int polarity, const Levels &levels, void *workspace,
-                size_t workspace_bytes, const float *seed, void *stream)
+template <class Cols, class View>
+int term_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const int64_t *frame_sample, int F, int h,
+             int w, int reference_mask, int polarity, const View &view, void *workspace, size_t workspace_bytes,
+             const float *seed, void *stream)
 {
+    const Levels levels = view.table();
     Plan pl;
     PyramidLayout lay;
     const int rc = pyramid_check(cols, n_events, frame_ts, frame_sample, F, h, w, reference_mask, polarity, levels,
@@ -654,15 +358,14 @@ int pyramid_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const
     hipStream_t st = as_stream(stream);
     char *ws = (char *)workspace;
     if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_pyramid_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
-                                cols, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
-                                (const int64_t *)ws, (const int64_t *)(ws + lay.s),
-                                (const ImageRec *)(ws + lay.rec), (const double *)(ws + lay.unit),
-                                (unsigned long long *)(ws + lay.sums));
+        DVSOF_REFS_POL_DISPATCH(avgts_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, view, (const int64_t *)ws,
+                                (const int64_t *)(ws + lay.s), (const ImageRec *)(ws + lay.rec),
+                                (const double *)(ws + lay.unit), (unsigned long long *)(ws + lay.sums));
         DVSOF_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(avgts_pyramid_bwd_close_kernel, dim3(event_blocks((int64_t)lay.sums_elems)), dim3(NT), 0, st,
-                       (long long *)(ws + lay.sums), (const double *)(ws + lay.unit), seed, F, pl.M, levels,
+    hipLaunchKernelGGL(event_term_bwd_close_kernel<View>, dim3(event_blocks((int64_t)lay.sums_elems)), dim3(NT), 0, st,
+                       (long long *)(ws + lay.sums), (const double *)(ws + lay.unit), seed, F, pl.M, view,
                        lay.sums_elems);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
@@ -672,14 +375,90 @@ int pyramid_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const
 
 extern "C" {
 
+size_t dvsof_avg_timestamp_workspace_bytes(int F, int reference_mask, int polarity, int h, int w)
+{
+    return term_workspace_bytes(F, reference_mask, polarity, h, w, OneLevel{h, w, nullptr, 0.f, nullptr}.table());
+}
+
+int dvsof_avg_timestamp_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                            const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                            const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                            int reference_mask, int polarity, float *term, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    return term_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                    reference_mask, polarity, OneLevel{h, w, flow, 0.f, nullptr}, term, nullptr, workspace,
+                    workspace_bytes, stream);
+}
+
+int dvsof_avg_timestamp_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                            const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                            const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                            int reference_mask, int polarity, void *workspace, size_t workspace_bytes,
+                            const float *seed, float weight, float *grad_flow, void *stream)
+{
+    return term_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                    reference_mask, polarity, OneLevel{h, w, flow, weight, grad_flow}, workspace, workspace_bytes,
+                    seed, stream);
+}
+
+// The encoded twins (include/dvsof_event_terms_encoded.h)
+int dvsof_avg_timestamp_fwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                    const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                    const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
+                                    int h, int w, int reference_mask, int polarity_channels, float *term,
+                                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    return term_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample, F,
+                    h, w, reference_mask, polarity_channels, OneLevel{h, w, flow, 0.f, nullptr}, term, nullptr,
+                    workspace, workspace_bytes, stream);
+}
+
+int dvsof_avg_timestamp_bwd_encoded(const int16_t *x, const int16_t *y, const float *t, const uint8_t *polarity,
+                                    const int64_t *sample_event_offsets, int B, int64_t n_events,
+                                    const float *frame_ts, const int64_t *frame_sample, const float *flow, int F,
+                                    int h, int w, int reference_mask, int polarity_channels, void *workspace,
+                                    size_t workspace_bytes, const float *seed, float weight, float *grad_flow,
+                                    void *stream)
+{
+    return term_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample, F,
+                    h, w, reference_mask, polarity_channels, OneLevel{h, w, flow, weight, grad_flow}, workspace,
+                    workspace_bytes, seed, stream);
+}
+
+// The tiled twins (include/dvsof_avg_timestamp_tiled.h): the forward above with the splat by tiles
+int dvsof_avg_timestamp_fwd_tiled(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
+                                  const int64_t *sample_index, int64_t n_events, const float *frame_ts,
+                                  const int64_t *frame_sample, const float *flow, int F, int h, int w,
+                                  int reference_mask, int polarity, float *term, void *workspace,
+                                  size_t workspace_bytes, void *stream, void *tile_workspace,
+                                  size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return term_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                    reference_mask, polarity, OneLevel{h, w, flow, 0.f, nullptr}, term, nullptr, workspace,
+                    workspace_bytes, stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+}
+
+int dvsof_avg_timestamp_fwd_encoded_tiled(const int16_t *x, const int16_t *y, const float *t,
+                                          const uint8_t *polarity, const int64_t *sample_event_offsets, int B,
+                                          int64_t n_events, const float *frame_ts, const int64_t *frame_sample,
+                                          const float *flow, int F, int h, int w, int reference_mask,
+                                          int polarity_channels, float *term, void *workspace,
+                                          size_t workspace_bytes, void *stream, void *tile_workspace,
+                                          size_t tile_workspace_bytes, int mode)
+{
+    if (mode != 0 && mode != 1) return DVSOF_EINVAL;
+    return term_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample, F,
+                    h, w, reference_mask, polarity_channels, OneLevel{h, w, flow, 0.f, nullptr}, term, nullptr,
+                    workspace, workspace_bytes, stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+}
+
+// The term on every flow scale (include/dvsof_avg_timestamp_pyramid.h)
 size_t dvsof_avg_timestamp_pyramid_workspace_bytes(int F, int reference_mask, int polarity, int h, int w,
                                                    dvsof_contrast_levels_t levels)
 {
-    Plan pl;
-    PyramidLayout lay;
-    if (F < 1 || !plan_of(F, reference_mask, polarity, pl) || !pyramid_layout(F, h, w, pl, levels, false, lay))
-        return 0;
-    return lay.bytes;
+    return term_workspace_bytes(F, reference_mask, polarity, h, w, levels);
 }
 
 int dvsof_avg_timestamp_pyramid_fwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
@@ -688,8 +467,8 @@ int dvsof_avg_timestamp_pyramid_fwd(const int64_t *x, const int64_t *y, const fl
                                     int polarity, dvsof_contrast_levels_t levels, float *terms, float *value,
                                     void *workspace, size_t workspace_bytes, void *stream)
 {
-    return pyramid_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
-                       reference_mask, polarity, levels, terms, value, workspace, workspace_bytes, stream);
+    return term_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                    reference_mask, polarity, TableView{levels}, terms, value, workspace, workspace_bytes, stream);
 }
 
 int dvsof_avg_timestamp_pyramid_bwd(const int64_t *x, const int64_t *y, const float *t, const int64_t *p,
@@ -698,8 +477,8 @@ int dvsof_avg_timestamp_pyramid_bwd(const int64_t *x, const int64_t *y, const fl
                                     int polarity, dvsof_contrast_levels_t levels, void *workspace,
                                     size_t workspace_bytes, const float *seed, void *stream)
 {
-    return pyramid_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
-                       reference_mask, polarity, levels, workspace, workspace_bytes, seed, stream);
+    return term_bwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                    reference_mask, polarity, TableView{levels}, workspace, workspace_bytes, seed, stream);
 }
 
 int dvsof_avg_timestamp_pyramid_fwd_encoded(const int16_t *x, const int16_t *y, const float *t,
@@ -709,9 +488,9 @@ int dvsof_avg_timestamp_pyramid_fwd_encoded(const int16_t *x, const int16_t *y, 
                                             dvsof_contrast_levels_t levels, float *terms, float *value,
                                             void *workspace, size_t workspace_bytes, void *stream)
 {
-    return pyramid_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
-                       F, h, w, reference_mask, polarity_channels, levels, terms, value, workspace, workspace_bytes,
-                       stream);
+    return term_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample, F,
+                    h, w, reference_mask, polarity_channels, TableView{levels}, terms, value, workspace,
+                    workspace_bytes, stream);
 }
 
 int dvsof_avg_timestamp_pyramid_bwd_encoded(const int16_t *x, const int16_t *y, const float *t,
@@ -721,8 +500,9 @@ int dvsof_avg_timestamp_pyramid_bwd_encoded(const int16_t *x, const int16_t *y, 
                                             dvsof_contrast_levels_t levels, void *workspace, size_t workspace_bytes,
                                             const float *seed, void *stream)
 {
-    return pyramid_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
-                       F, h, w, reference_mask, polarity_channels, levels, workspace, workspace_bytes, seed, stream);
+    return term_bwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample, F,
+                    h, w, reference_mask, polarity_channels, TableView{levels}, workspace, workspace_bytes, seed,
+                    stream);
 }
 
 // The tiled twins (include/dvsof_event_pyramids_tiled.h): the forward above with the splat by tiles
@@ -734,9 +514,9 @@ int dvsof_avg_timestamp_pyramid_fwd_tiled(const int64_t *x, const int64_t *y, co
                                           void *tile_workspace, size_t tile_workspace_bytes, int mode)
 {
     if (mode != 0 && mode != 1) return DVSOF_EINVAL;
-    return pyramid_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
-                       reference_mask, polarity, levels, terms, value, workspace, workspace_bytes, stream,
-                       TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+    return term_fwd(WireColumns{x, y, t, p, sample_index}, n_events, frame_ts, frame_sample, F, h, w,
+                    reference_mask, polarity, TableView{levels}, terms, value, workspace, workspace_bytes, stream,
+                    TiledSplat{tile_workspace, tile_workspace_bytes, mode});
 }
 
 int dvsof_avg_timestamp_pyramid_fwd_encoded_tiled(const int16_t *x, const int16_t *y, const float *t,
@@ -749,9 +529,9 @@ int dvsof_avg_timestamp_pyramid_fwd_encoded_tiled(const int16_t *x, const int16_
                                                   void *tile_workspace, size_t tile_workspace_bytes, int mode)
 {
     if (mode != 0 && mode != 1) return DVSOF_EINVAL;
-    return pyramid_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample,
-                       F, h, w, reference_mask, polarity_channels, levels, terms, value, workspace, workspace_bytes,
-                       stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
+    return term_fwd(EncodedColumns{x, y, t, polarity, sample_event_offsets, B}, n_events, frame_ts, frame_sample, F,
+                    h, w, reference_mask, polarity_channels, TableView{levels}, terms, value, workspace,
+                    workspace_bytes, stream, TiledSplat{tile_workspace, tile_workspace_bytes, mode});
 }
 
 }  // extern "C"
@@ -832,7 +612,7 @@ __global__ __launch_bounds__(NT) void joint_stats_partial_kernel(
     });
 }
 
-// avgts_pyramid_close_kernel and contrast_pyramid_close_kernel of contrast.hip in one wave: the
+// avgts_close_kernel and contrast_close_kernel of contrast.hip over a table in one wave: the
 // records of both terms from the joint rows (the contrast term's rows go to its result), after a
 // barrier both units of every level and frame, each the maximum over its own term's images, and
 // the terms and values, the contrast term's in lane 0 and this term's in lane 1.
@@ -887,7 +667,7 @@ __global__ __launch_bounds__(kWave) void joint_close_kernel(const JointRow *__re
     }
 }
 
-// avgts_pyramid_bwd_events_kernel and contrast_pyramid_bwd_events_kernel in one walk: per event,
+// avgts_bwd_events_kernel and contrast_bwd_events_kernel over a table in one walk: per event,
 // frame and level one flow read, per reference one warp and one set of corners, at each corner
 // inside the image T and D (this term: G = k2 T D (a - T), the stored T and D being what
 // avgts_bwd_event computes) and, where the reference is also the contrast term's, q
@@ -976,7 +756,7 @@ __global__ __launch_bounds__(NT) void joint_bwd_events_kernel(
     for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
 }
 
-// avgts_pyramid_bwd_close_kernel for both terms: one thread per element of a level's grad_flow
+// event_term_bwd_close_kernel for both terms: one thread per element of a level's grad_flow
 // converts, clears and stores this term's sum and the contrast term's, each with its own unit,
 // M, weight, seed and grad_flow.
 __global__ __launch_bounds__(NT) void joint_bwd_close_kernel(long long *__restrict__ aacc, long long *__restrict__ cacc,
@@ -1100,8 +880,8 @@ int joint_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const i
                                                          avg_mask, polarity, la, tp, img, tiled.workspace, st);
         if (rs != DVSOF_OK) return rs;
     } else if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(avgts_pyramid_splat_kernel, pa, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
-                                n_events, frame_ts, frame_sample, F, h, w, pa.refs, la, (unsigned long long *)ws,
+        DVSOF_REFS_POL_DISPATCH(avgts_splat_kernel, pa, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols, n_events,
+                                frame_ts, frame_sample, F, h, w, pa.refs, TableView{la}, (unsigned long long *)ws,
                                 (unsigned long long *)(ws + lay.s), (unsigned long long *)(ws + lay.base),
                                 (uint32_t *)(ws + lay.count));
         DVSOF_LAUNCH_CHECK();

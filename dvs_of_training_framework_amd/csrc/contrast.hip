@@ -23,11 +23,15 @@
 // atomic per component, and one thread per element converts once.  No
 // floating-point atomics anywhere.  This file relies on -ffp-contract=off.
 //
-// At the end of the file: the term on every flow scale of the network by one
-// splat, one closing wave and one backward for all levels (sections 19-23,
-// include/dvsof_contrast_pyramid.h); the kernels above are not touched by it.
-// After that: the gradient-magnitude objective on the same images (sections
-// 27-31, include/dvsof_contrast_gradient.h), a stencil over q through LDS.
+// The term on every flow scale of the network (sections 19-23,
+// include/dvsof_contrast_pyramid.h) is the same three kernels over a level
+// table: every kernel is written once against a view of the call's levels
+// (event_term_levels.h) and instantiated for one flow and for a table, with
+// one splat, one closing wave and one backward for all levels.  Then the host
+// side of the calls on one flow, that of the calls over a table, and the
+// gradient-magnitude objective on the same images (sections 27-31,
+// include/dvsof_contrast_gradient.h), a stencil over q through LDS.
+#include "event_term_levels.h"
 #include "event_term_records.h"
 #include "tiled_splat.h"
 #include "../../include/dvsof_contrast.h"
@@ -47,51 +51,68 @@ using ImageRec = ContrastRec;
 // ---------------------------------------------------------------------------
 // Forward.  One thread per event; an event takes part in every frame of its
 // sample whose window holds its time (both ends included), in the channel of
-// the sign of p.
+// the sign of p.  The columns are read, the frames walked and tau computed once
+// per event; the levels are a loop around splat_event with the event's level
+// pixel (y >> s, x >> s), the level's flow, plane and base.
 // ---------------------------------------------------------------------------
-template <int R, bool POL, class Cols>
+template <int R, bool POL, class Cols, class View>
 __global__ __launch_bounds__(NT) void contrast_splat_kernel(
     const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
+    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const View view,
     unsigned long long *__restrict__ q, uint32_t *__restrict__ count)
 {
-    const size_t plane = (size_t)h * w;
-    const auto splat = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
-        const size_t pix = (size_t)yi * w + (size_t)xi;
-        float u, v;
-        flow_at(flow, f, plane, pix, u, v);
-        splat_event<R, POL, true>(refs, f, c, tau, u, v, xi, yi, pix, plane, h, w, q, count);
+    const auto splat = [=, &view](int64_t xi, int64_t yi, int c, int f, float tau) {
+        for (int k = 0; k < view.levels(); ++k) {
+            const Level &L = view.at(k);
+            const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
+            const size_t plane = (size_t)L.h * L.w;
+            const size_t pix = (size_t)ys * L.w + (size_t)xs;
+            float u, v;
+            flow_at(L.flow, f, plane, pix, u, v);
+            splat_event<R, POL, true>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
+                                      count + L.image_offset);
+        }
     };
     for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
 }
 
-// One wave: the record of every image (lane k takes images k, k + 64, ...);
-// after a barrier the unit of every frame (lane k takes frames k, k + 64, ...;
-// a maximum has no order) and, in lane 0, the images' terms in image order.
-// A frame of one image has its unit from the gmax its lane holds.
+// One wave over the K M images and K F units of all levels (image i = k M + m, unit j = k F + f):
+// the record of every image (lane k takes images k, k + 64, ...); after a barrier the unit of
+// every frame (lane k takes frames k, k + 64, ...; a maximum has no order; a frame of one image
+// has its unit from the gmax its lane holds) and, in lane 0, every level's term in image order.
+// Over a table also the weighted sum in level order; on one flow terms is the call's term and
+// value is not written.
+template <class View>
 __global__ __launch_bounds__(kWave) void contrast_close_kernel(const dvsof_iwe_result_t *__restrict__ result, int F,
-                                                               int RC, int h, int w, int unit_bits, ImageRec *rec,
-                                                               double *unit, float *term)
+                                                               int RC, int unit_bits, const View view, ImageRec *rec,
+                                                               double *unit, float *terms, float *value)
 {
-    const double N = (double)h * (double)w;
-    const int M = F * RC;
-    for (int m = threadIdx.x; m < M; m += kWave) {
-        const ImageRec o = contrast_record_of(result[m], N);
-        rec[m] = o;
-        if (RC == 1) unit[m] = unit_of(o.gmax, unit_bits);
+    const int M = F * RC, K = view.levels();
+    for (int i = threadIdx.x; i < K * M; i += kWave) {
+        const Level &L = view.at(K == 1 ? 0 : i / M);
+        const double N = (double)L.h * (double)L.w;
+        const ImageRec o = contrast_record_of(result[i], N);
+        rec[i] = o;
+        if (RC == 1) unit[i] = unit_of(o.gmax, unit_bits);
     }
     __syncthreads();
     if (RC > 1) {
-        for (int f = threadIdx.x; f < F; f += kWave) {
+        for (int j = threadIdx.x; j < K * F; j += kWave) {
             double gmax = 0.0;
-            for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[f * RC + k].gmax);
-            unit[f] = unit_of(gmax, unit_bits);
+            for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[(size_t)j * RC + k].gmax);
+            unit[j] = unit_of(gmax, unit_bits);
         }
     }
     if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int m = 0; m < M; ++m) s += rec[m].term;
-        *term = (float)(s / (double)M);
+        double total = 0.0;
+        for (int k = 0; k < K; ++k) {
+            double s = 0.0;
+            for (int m = 0; m < M; ++m) s += rec[(size_t)k * M + m].term;
+            const double term = s / (double)M;
+            terms[k] = (float)term;
+            if (View::kTable) total += (double)view.at(k).weight * term;
+        }
+        if (View::kTable) *value = (float)total;
     }
 }
 
@@ -99,69 +120,78 @@ __global__ __launch_bounds__(kWave) void contrast_close_kernel(const dvsof_iwe_r
 // Backward.  One thread per event and frame: for every reference G = coef (I -
 // mean) at the four corners of the image of its channel (0 outside the image),
 // the derivative of the bilinear weights, -sig of it to the event's own pixel
-// of the flow, in float64, truncated to the frame's unit.
+// of the flow, in float64, truncated to the frame's unit (corner_addends of
+// event_term_levels.h, per level as in the splat); then one thread per element
+// converts (event_term_bwd_close_kernel, likewise).
 // ---------------------------------------------------------------------------
-template <int R, bool POL, class Cols>
+// The one kernel of the terms that writes the walk of for_each_window_event out: through the walk
+// its <3, true> instances over a table take 74-76 VGPRs for 70, seven waves a SIMD down to six.
+template <int R, bool POL, class Cols, class View>
 __global__ __launch_bounds__(NT) void contrast_bwd_events_kernel(
     const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, const float *__restrict__ flow, int F, int h, int w, Refs refs,
+    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const View view,
     const int64_t *__restrict__ q, const ImageRec *__restrict__ rec, const double *__restrict__ unit,
     unsigned long long *__restrict__ acc)
 {
-    const size_t plane = (size_t)h * w;
-    const auto addends = [=](int64_t xi, int64_t yi, int c, int f, float tau) {
-        const size_t pix = (size_t)yi * w + (size_t)xi;
-        float u, v;
-        flow_at(flow, f, plane, pix, u, v);
-        const double un = unit[f];
-        // R = 1: |ms g| < 2^(e+1) (1 + 2^-22), so |a| < 2^41 (1 + 2^-22); R > 1: at most three addends
-        // below 2^39 (1 + 2^-22) each; the product with the unit is exact
-        long long su = 0, sv = 0;
+    const int64_t stride = (int64_t)gridDim.x * NT;
+    const size_t M = (size_t)F * R * (POL ? 2 : 1);
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
+        const EventRow ev = cols.template load<POL>(e);
+        const int64_t xi = ev.x, yi = ev.y;
+        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
+        int c;
+        if (!event_channel<POL>(ev.sign, c)) continue;
+        const float te = ev.t;
+        const int64_t s = ev.sample;
+        for (int f = 0; f < F; ++f) {
+            if (frame_sample[f] != s) continue;
+            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
+            if (!(t0 <= te && te <= t1)) continue;
+            const float tau = event_tau(te, t0, t1);
+            for (int k = 0; k < view.levels(); ++k) {
+                const Level &L = view.at(k);
+                const int lh = L.h, lw = L.w;
+                const int64_t xs = xi >> L.shift, ys = yi >> L.shift;
+                const size_t plane = (size_t)lh * lw;
+                const size_t pix = (size_t)ys * lw + (size_t)xs;
+                float u, v;
+                flow_at(L.flow, f, plane, pix, u, v);
+                const double un = unit[(size_t)k * F + f];
+                // R = 1: |ms g| < 2^(e+1) (1 + 2^-22), so |a| < 2^41 (1 + 2^-22); R > 1: at most three
+                // addends below 2^39 (1 + 2^-22) each; the product with the unit is exact
+                long long su = 0, sv = 0;
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const size_t m = image_of<R, POL>(f, r, c);
-            const ImageRec a = rec[m];
-            if (a.coef == 0.0) continue;  // var(c_m) = 0: every addend would be 0
-            Warp p;
-            if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
-            const int64_t *img = q + m * plane;
-            double G[2][2];
+                for (int r = 0; r < R; ++r) {
+                    const size_t m = image_of<R, POL>(f, r, c);
+                    const ImageRec a = rec[(size_t)k * M + m];
+                    if (a.coef == 0.0) continue;  // var(c_m) = 0: every addend would be 0
+                    Warp p;
+                    if (!warp_event_to(tau, refs.rho[r], u, v, xs, ys, lh, lw, p)) continue;
+                    const int64_t *img = q + L.image_offset + m * plane;
+                    // corner_addends written out: through it the <3, true, WireColumns> table instance
+                    // took 224.9 us for 219.3 (spread 3.2) at the same 70 VGPRs
+                    double G[2][2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
+                    for (int j = 0; j < 2; ++j) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int xx = p.cx + i, yy = p.cy + j;
-                    const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
-                    G[j][i] = in ? a.coef * ((double)img[(size_t)yy * w + (size_t)xx] * 0x1p-32 - a.mean) : 0.0;
+                        for (int i = 0; i < 2; ++i) {
+                            const int xx = p.cx + i, yy = p.cy + j;
+                            const bool in = xx >= 0 && xx < lw && yy >= 0 && yy < lh;
+                            G[j][i] =
+                                in ? a.coef * ((double)img[(size_t)yy * lw + (size_t)xx] * 0x1p-32 - a.mean) : 0.0;
+                        }
+                    }
+                    const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
+                    const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
+                    const double ms = -(double)p.tau;
+                    su += (long long)(ms * gx * un);
+                    sv += (long long)(ms * gy * un);
                 }
+                unsigned long long *dst = acc + L.sums_offset + (size_t)f * 2 * plane + pix;
+                if (su != 0) atomicAdd(dst, (unsigned long long)su);
+                if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
             }
-            const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
-            const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
-            const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
-            su += (long long)(ms * gx * un);
-            sv += (long long)(ms * gy * un);
         }
-        unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
-        if (su != 0) atomicAdd(dst, (unsigned long long)su);
-        if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
-    };
-    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, addends);
-}
-
-// One thread per element of grad_flow: convert, clear the sum for the next
-// backward of the same forward, store.
-__global__ __launch_bounds__(NT) void contrast_bwd_close_kernel(long long *__restrict__ acc,
-                                                                const double *__restrict__ unit,
-                                                                const float *__restrict__ seed, float weight, int F,
-                                                                int M, size_t per_frame, float *__restrict__ grad)
-{
-    const size_t total = (size_t)F * per_frame, stride = (size_t)gridDim.x * NT;
-    const float sw = seed[0] * weight;
-    for (size_t k = (size_t)blockIdx.x * NT + threadIdx.x; k < total; k += stride) {
-        const long long a = acc[k];
-        acc[k] = 0;
-        const double value = (double)a / unit[k / per_frame] / (double)M;  // the first division is exact
-        grad[k] = sw * (float)value;
     }
 }
 
@@ -219,6 +249,7 @@ int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const i
     hipStream_t st = as_stream(stream);
     const size_t pixels = (size_t)pl.M * h * w;
     const Workspace ws = carve(workspace, F, h, w, pl);
+    const OneLevel view{h, w, flow, 0.f, nullptr};
     DVSOF_HIP_TRY((hipError_t)fill_u32(q, 0u, sizeof(int64_t) * pixels, st));
     DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws.sums, 0u, sums_bytes(F, h, w), st));
@@ -229,14 +260,14 @@ int multi_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const i
         if (rs != DVSOF_OK) return rs;
     } else if (n_events > 0) {
         DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
-                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, (unsigned long long *)q,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, view, (unsigned long long *)q,
                                 count);
         DVSOF_LAUNCH_CHECK();
     }
     const int rc = dvsof_iwe_stats(q, count, pl.M, h, w, result, ws.stats, ws.stats_bytes, stream);
     if (rc != DVSOF_OK) return rc;
-    hipLaunchKernelGGL(contrast_close_kernel, dim3(1), dim3(kWave), 0, st, result, F, pl.R * pl.C, h, w,
-                       pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, ws.rec, ws.unit, term);
+    hipLaunchKernelGGL(contrast_close_kernel<OneLevel>, dim3(1), dim3(kWave), 0, st, result, F, pl.R * pl.C,
+                       pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, view, ws.rec, ws.unit, term, (float *)nullptr);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
@@ -257,15 +288,16 @@ int multi_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const i
         return DVSOF_ENOSPACE;
     hipStream_t st = as_stream(stream);
     const Workspace ws = carve(workspace, F, h, w, pl);
+    const OneLevel view{h, w, flow, weight, grad_flow};
     if (n_events > 0) {
         DVSOF_REFS_POL_DISPATCH(contrast_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
-                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, q,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, view, q,
                                 (const ImageRec *)ws.rec, (const double *)ws.unit, ws.sums);
         DVSOF_LAUNCH_CHECK();
     }
-    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
-    hipLaunchKernelGGL(contrast_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
-                       (long long *)ws.sums, (const double *)ws.unit, seed, weight, F, pl.M, per_frame, grad_flow);
+    const size_t total = 2 * (size_t)F * h * w;
+    hipLaunchKernelGGL(event_term_bwd_close_kernel<OneLevel>, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
+                       (long long *)ws.sums, (const double *)ws.unit, seed, F, pl.M, view, total);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
@@ -385,165 +417,11 @@ int dvsof_contrast_bwd(const int64_t *x, const int64_t *y, const float *t, const
 
 // ---------------------------------------------------------------------------
 // The term on every flow scale (docs/CONTRAST_SPEC.md sections 19-23).  The
-// columns are read, the frames walked and tau computed once per event; the
-// levels are a loop around splat_event / the backward's addends with the
-// event's level pixel (y >> s, x >> s), the level's flow, plane and base.  Per
-// level the bytes are those of the kernels above at the level's shape.
+// kernels are those above over the table's view; the workspace holds q and
+// count of all levels, so the bytes of a level are those of the calls on one
+// flow at the level's shape.
 // ---------------------------------------------------------------------------
 namespace {
-
-using Levels = dvsof_contrast_levels_t;
-using Level = dvsof_contrast_level_t;
-constexpr int kMaxLevels = 8;
-constexpr int kMaxShift = 15;
-static_assert(sizeof(Levels::level) / sizeof(Level) == kMaxLevels, "the table holds eight levels");
-
-template <int R, bool POL, class Cols>
-__global__ __launch_bounds__(NT) void contrast_pyramid_splat_kernel(
-    const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
-    unsigned long long *__restrict__ q, uint32_t *__restrict__ count)
-{
-    const auto splat = [=, &lv](int64_t xi, int64_t yi, int c, int f, float tau) {
-        for (int k = 0; k < lv.K; ++k) {
-            const Level &L = lv.level[k];
-            const int64_t xs = xi >> L.shift, ys = yi >> L.shift;  // xs <= (w - 1) >> s <= L.w - 1
-            const size_t plane = (size_t)L.h * L.w;
-            const size_t pix = (size_t)ys * L.w + (size_t)xs;
-            float u, v;
-            flow_at(L.flow, f, plane, pix, u, v);
-            splat_event<R, POL, true>(refs, f, c, tau, u, v, xs, ys, pix, plane, L.h, L.w, q + L.image_offset,
-                                      count + L.image_offset);
-        }
-    };
-    for_each_window_event<POL>(cols, n, ts, frame_sample, F, h, w, splat);
-}
-
-// contrast_close_kernel over the K M images and K F units of all levels (image i = k M + m,
-// unit j = k F + f), then in lane 0 every level's term in image order and the weighted sum in
-// level order.
-__global__ __launch_bounds__(kWave) void contrast_pyramid_close_kernel(const dvsof_iwe_result_t *__restrict__ result,
-                                                                       int F, int RC, int unit_bits, const Levels lv,
-                                                                       ImageRec *rec, double *unit, float *terms,
-                                                                       float *value)
-{
-    const int M = F * RC, K = lv.K;
-    for (int i = threadIdx.x; i < K * M; i += kWave) {
-        const Level &L = lv.level[i / M];
-        const double N = (double)L.h * (double)L.w;
-        const ImageRec o = contrast_record_of(result[i], N);
-        rec[i] = o;
-        if (RC == 1) unit[i] = unit_of(o.gmax, unit_bits);
-    }
-    __syncthreads();
-    if (RC > 1) {
-        for (int j = threadIdx.x; j < K * F; j += kWave) {
-            double gmax = 0.0;
-            for (int k = 0; k < RC; ++k) gmax = fmax(gmax, rec[(size_t)j * RC + k].gmax);
-            unit[j] = unit_of(gmax, unit_bits);
-        }
-    }
-    if (threadIdx.x == 0) {
-        double total = 0.0;
-        for (int k = 0; k < K; ++k) {
-            double s = 0.0;
-            for (int m = 0; m < M; ++m) s += rec[(size_t)k * M + m].term;
-            const double term = s / (double)M;
-            terms[k] = (float)term;
-            total += (double)lv.level[k].weight * term;
-        }
-        *value = (float)total;
-    }
-}
-
-// The one kernel of the terms that writes the walk of for_each_window_event out: through the walk
-// its <3, true> instances take 74-76 VGPRs for 70, seven waves a SIMD down to six.
-template <int R, bool POL, class Cols>
-__global__ __launch_bounds__(NT) void contrast_pyramid_bwd_events_kernel(
-    const Cols cols, int64_t n, const float *__restrict__ ts,
-    const int64_t *__restrict__ frame_sample, int F, int h, int w, Refs refs, const Levels lv,
-    const int64_t *__restrict__ q, const ImageRec *__restrict__ rec, const double *__restrict__ unit,
-    unsigned long long *__restrict__ acc)
-{
-    const int64_t stride = (int64_t)gridDim.x * NT;
-    const size_t M = (size_t)F * R * (POL ? 2 : 1);
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += stride) {
-        const EventRow ev = cols.template load<POL>(e);
-        const int64_t xi = ev.x, yi = ev.y;
-        if (xi < 0 || xi >= w || yi < 0 || yi >= h) continue;
-        int c;
-        if (!event_channel<POL>(ev.sign, c)) continue;
-        const float te = ev.t;
-        const int64_t s = ev.sample;
-        for (int f = 0; f < F; ++f) {
-            if (frame_sample[f] != s) continue;
-            const float t0 = ts[2 * f], t1 = ts[2 * f + 1];
-            if (!(t0 <= te && te <= t1)) continue;
-            const float tau = event_tau(te, t0, t1);
-            for (int k = 0; k < lv.K; ++k) {
-                const Level &L = lv.level[k];
-                const int lh = L.h, lw = L.w;
-                const int64_t xs = xi >> L.shift, ys = yi >> L.shift;
-                const size_t plane = (size_t)lh * lw;
-                const size_t pix = (size_t)ys * lw + (size_t)xs;
-                float u, v;
-                flow_at(L.flow, f, plane, pix, u, v);
-                const double un = unit[(size_t)k * F + f];
-                long long su = 0, sv = 0;  // the bounds of contrast_bwd_events_kernel, per level
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const size_t m = image_of<R, POL>(f, r, c);
-                    const ImageRec a = rec[(size_t)k * M + m];
-                    if (a.coef == 0.0) continue;
-                    Warp p;
-                    if (!warp_event_to(tau, refs.rho[r], u, v, xs, ys, lh, lw, p)) continue;
-                    const int64_t *img = q + L.image_offset + m * plane;
-                    double G[2][2];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            const int xx = p.cx + i, yy = p.cy + j;
-                            const bool in = xx >= 0 && xx < lw && yy >= 0 && yy < lh;
-                            G[j][i] =
-                                in ? a.coef * ((double)img[(size_t)yy * lw + (size_t)xx] * 0x1p-32 - a.mean) : 0.0;
-                        }
-                    }
-                    const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
-                    const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
-                    const double ms = -(double)p.tau;
-                    su += (long long)(ms * gx * un);
-                    sv += (long long)(ms * gy * un);
-                }
-                unsigned long long *dst = acc + L.sums_offset + (size_t)f * 2 * plane + pix;
-                if (su != 0) atomicAdd(dst, (unsigned long long)su);
-                if (sv != 0) atomicAdd(dst + plane, (unsigned long long)sv);
-            }
-        }
-    }
-}
-
-// One thread per element of every level's grad_flow: contrast_bwd_close_kernel with the
-// level found from the element's place in the sums.
-__global__ __launch_bounds__(NT) void contrast_pyramid_bwd_close_kernel(long long *__restrict__ acc,
-                                                                        const double *__restrict__ unit,
-                                                                        const float *__restrict__ seed, int F, int M,
-                                                                        const Levels lv, size_t total)
-{
-    const size_t stride = (size_t)gridDim.x * NT;
-    const float s0 = seed[0];
-    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < total; i += stride) {
-        int k = 0;
-        while (k + 1 < lv.K && i >= lv.level[k + 1].sums_offset) ++k;
-        const Level &L = lv.level[k];
-        const size_t local = i - L.sums_offset, per_frame = 2 * (size_t)L.h * L.w;
-        const float sw = s0 * L.weight;
-        const long long a = acc[i];
-        acc[i] = 0;
-        const double value = (double)a / unit[(size_t)k * F + local / per_frame] / (double)M;
-        L.grad_flow[local] = sw * (float)value;
-    }
-}
 
 // the workspace as byte offsets: q at 0, sums, count (one zeroed region), K M records, K F
 // units, the statistics' partials
@@ -556,19 +434,11 @@ struct PyramidLayout {
 // (dvsof_contrast_pyramid_workspace_bytes reads the shapes alone).
 bool pyramid_layout(int F, int h, int w, const Plan &pl, const Levels &lv, bool check_offsets, PyramidLayout &o)
 {
-    if (lv.K < 1 || lv.K > kMaxLevels || bad_frame_sizes(F, h, w)) return false;
-    size_t pixels = 0;
+    const size_t pixels = level_table_pixels(F, h, w, lv, check_offsets ? pl.M : 0);
+    if (pixels == 0) return false;
     o.stats_bytes = 0;
     for (int k = 0; k < lv.K; ++k) {
-        const Level &L = lv.level[k];
-        if (bad_frame_sizes(F, L.h, L.w) || L.shift < 0 || L.shift > kMaxShift) return false;
-        const int round = (1 << L.shift) - 1;
-        if (L.h != (h + round) >> L.shift || L.w != (w + round) >> L.shift) return false;
-        if (check_offsets && (L.image_offset != (size_t)pl.M * pixels || L.row_offset != (size_t)k * pl.M ||
-                              L.sums_offset != 2 * (size_t)F * pixels))
-            return false;
-        pixels += (size_t)L.h * L.w;
-        const size_t need = dvsof_iwe_stats_workspace_bytes(pl.M, L.h, L.w);
+        const size_t need = dvsof_iwe_stats_workspace_bytes(pl.M, lv.level[k].h, lv.level[k].w);
         o.stats_bytes = need > o.stats_bytes ? need : o.stats_bytes;
     }
     const size_t P = (size_t)pl.M * pixels;
@@ -647,8 +517,8 @@ int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const
                                                          EventImages{(int64_t *)ws.q, ws.count}, tiled.workspace, st);
         if (rs != DVSOF_OK) return rs;
     } else if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(contrast_pyramid_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
-                                cols, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels, ws.q, ws.count);
+        DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, TableView{levels}, ws.q, ws.count);
         DVSOF_LAUNCH_CHECK();
     }
     for (int k = 0; k < levels.K; ++k) {
@@ -657,8 +527,9 @@ int pyramid_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, const
                                        L.w, result + L.row_offset, ws.stats, lay.stats_bytes, stream);
         if (rs != DVSOF_OK) return rs;
     }
-    hipLaunchKernelGGL(contrast_pyramid_close_kernel, dim3(1), dim3(kWave), 0, st, result, F, pl.R * pl.C,
-                       pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, levels, ws.rec, ws.unit, terms, value);
+    hipLaunchKernelGGL(contrast_close_kernel<TableView>, dim3(1), dim3(kWave), 0, st, result, F, pl.R * pl.C,
+                       pl.R > 1 ? kUnitBits - kSharedBits : kUnitBits, TableView{levels}, ws.rec, ws.unit, terms,
+                       value);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
@@ -676,13 +547,14 @@ int pyramid_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, const
     hipStream_t st = as_stream(stream);
     const PyramidWorkspace ws = carve_pyramid(workspace, lay);
     if (n_events > 0) {
-        DVSOF_REFS_POL_DISPATCH(contrast_pyramid_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st,
-                                cols, n_events, frame_ts, frame_sample, F, h, w, pl.refs, levels,
+        DVSOF_REFS_POL_DISPATCH(contrast_bwd_events_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, TableView{levels},
                                 (const int64_t *)ws.q, (const ImageRec *)ws.rec, (const double *)ws.unit, ws.sums);
         DVSOF_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(contrast_pyramid_bwd_close_kernel, dim3(event_blocks((int64_t)lay.sums_elems)), dim3(NT), 0,
-                       st, (long long *)ws.sums, (const double *)ws.unit, seed, F, pl.M, levels, lay.sums_elems);
+    hipLaunchKernelGGL(event_term_bwd_close_kernel<TableView>, dim3(event_blocks((int64_t)lay.sums_elems)), dim3(NT),
+                       0, st, (long long *)ws.sums, (const double *)ws.unit, seed, F, pl.M, TableView{levels},
+                       lay.sums_elems);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }
@@ -942,21 +814,7 @@ __global__ __launch_bounds__(NT) void contrast_gradient_bwd_events_kernel(
             Warp p;
             if (!warp_event_to(tau, refs.rho[r], u, v, xi, yi, h, w, p)) continue;
             const int64_t *img = lap + m * plane;
-            double G[2][2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int xx = p.cx + i, yy = p.cy + j;
-                    const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h;
-                    G[j][i] = in ? coef * ((double)img[(size_t)yy * w + (size_t)xx] * 0x1p-32) : 0.0;
-                }
-            }
-            const double gx = (double)p.wy[0] * (G[0][1] - G[0][0]) + (double)p.wy[1] * (G[1][1] - G[1][0]);
-            const double gy = (double)p.wx[0] * (G[1][0] - G[0][0]) + (double)p.wx[1] * (G[1][1] - G[0][1]);
-            const double ms = -(double)p.tau;  // p.tau holds sig; d xw / d u = -sig
-            su += (long long)(ms * gx * un);
-            sv += (long long)(ms * gy * un);
+            corner_addends(p, h, w, un, [&](size_t at) { return coef * ((double)img[at] * 0x1p-32); }, su, sv);
         }
         unsigned long long *dst = acc + (size_t)f * 2 * plane + pix;
         if (su != 0) atomicAdd(dst, (unsigned long long)su);
@@ -1013,8 +871,9 @@ int gradient_fwd(const Cols &cols, int64_t n_events, const float *frame_ts, cons
     DVSOF_HIP_TRY((hipError_t)fill_u32(count, 0u, sizeof(uint32_t) * pixels, st));
     DVSOF_HIP_TRY((hipError_t)fill_u32(ws, 0u, sums_bytes(F, h, w), st));
     if (n_events > 0) {
+        const OneLevel view{h, w, flow, 0.f, nullptr};
         DVSOF_REFS_POL_DISPATCH(contrast_splat_kernel, pl, dim3(event_blocks(n_events)), dim3(NT), 0, st, cols,
-                                n_events, frame_ts, frame_sample, flow, F, h, w, pl.refs, (unsigned long long *)q,
+                                n_events, frame_ts, frame_sample, F, h, w, pl.refs, view, (unsigned long long *)q,
                                 count);
         DVSOF_LAUNCH_CHECK();
     }
@@ -1055,9 +914,10 @@ int gradient_bwd(const Cols &cols, int64_t n_events, const float *frame_ts, cons
                                 (const double *)(ws + lay.unit), (unsigned long long *)ws);
         DVSOF_LAUNCH_CHECK();
     }
-    const size_t per_frame = 2 * (size_t)h * w, total = (size_t)F * per_frame;
-    hipLaunchKernelGGL(contrast_bwd_close_kernel, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
-                       (long long *)ws, (const double *)(ws + lay.unit), seed, weight, F, pl.M, per_frame, grad_flow);
+    const size_t total = 2 * (size_t)F * h * w;
+    hipLaunchKernelGGL(event_term_bwd_close_kernel<OneLevel>, dim3(event_blocks((int64_t)total)), dim3(NT), 0, st,
+                       (long long *)ws, (const double *)(ws + lay.unit), seed, F, pl.M,
+                       OneLevel{h, w, flow, weight, grad_flow}, total);
     DVSOF_LAUNCH_CHECK();
     return DVSOF_OK;
 }

@@ -23,9 +23,8 @@
 // kSlice records, and the sums at the events' own pixels are taken at the
 // finest level of the table alone and folded into the others.
 #pragma once
-#include "event_columns.h"
+#include "event_term_levels.h"
 #include "voxel_tiles.h"
-#include "../../include/dvsof_contrast_pyramid.h"
 
 // 64 x 16: a row of the tile's accumulators is one 520-byte run of LDS, a row of its flush 64
 // contiguous pixels of q; 65 x 17 x 8 bytes = 8.6 KiB of LDS, so the workgroups of a CU are
@@ -57,7 +56,6 @@ constexpr int kSlice = 4096;
 // too many tiles for the agreement loop to pay.  Without it (0) the whole forward call of the
 // benchmark batch takes 2.5-6 times as long: almost every lane then hits one of two words
 constexpr int kAggregateTiles = 4;
-constexpr int kPyramidLevels = 8;
 // mode 0 of the level-table calls runs the tiled schedule from this many events on, per family:
 // the smallest measured count at which every row of profiles/event_pyramids_tiled/README.md wins
 // by more than the spread of its block means.  The images of warped events: 8 frames of 8 000
@@ -108,9 +106,9 @@ struct TilePlan {
 // own-pixel sums pass 1 takes.
 struct PyramidTilePlan {
     int K, source;
-    int TX[kPyramidLevels], TY[kPyramidLevels], tiles[kPyramidLevels], cap[kPyramidLevels], slices[kPyramidLevels];
-    int tile_base[kPyramidLevels + 1], block_base[kPyramidLevels + 1];
-    size_t rec_base[kPyramidLevels + 1];
+    int TX[kMaxLevels], TY[kMaxLevels], tiles[kMaxLevels], cap[kMaxLevels], slices[kMaxLevels];
+    int tile_base[kMaxLevels + 1], block_base[kMaxLevels + 1];
+    size_t rec_base[kMaxLevels + 1];
 };
 
 namespace {
@@ -176,18 +174,15 @@ inline bool pyramid_tile_plan(int F, int reference_mask, int polarity, int h, in
                               int64_t n_events, PyramidTilePlan &o)
 {
     Plan pl;
-    if (F < 1 || n_events < 0 || bad_frame_sizes(F, h, w) || !plan_of(F, reference_mask, polarity, pl)) return false;
-    if (lv.K < 1 || lv.K > kPyramidLevels) return false;
+    if (F < 1 || n_events < 0 || !plan_of(F, reference_mask, polarity, pl)) return false;
+    if (level_table_pixels(F, h, w, lv, 0) == 0) return false;
     o.K = lv.K;
     o.source = 0;
     o.tile_base[0] = o.block_base[0] = 0;
     o.rec_base[0] = 0;
     int64_t total = 0, blocks = 0;
     for (int k = 0; k < lv.K; ++k) {
-        const dvsof_contrast_level_t &L = lv.level[k];
-        if (L.shift < 0 || L.shift > 15 || bad_frame_sizes(F, L.h, L.w)) return false;
-        const int round = (1 << L.shift) - 1;
-        if (L.h != (h + round) >> L.shift || L.w != (w + round) >> L.shift) return false;
+        const Level &L = lv.level[k];
         if (L.shift < lv.level[o.source].shift) o.source = k;
         o.TX[k] = (L.w + kTileW - 1) / kTileW;
         o.TY[k] = (L.h + kTileH - 1) / kTileH;
@@ -233,7 +228,7 @@ inline int pyramid_tile_decide(const TiledSplat &tiled, int F, int reference_mas
 }  // namespace
 
 // The launchers of the family Images (EventImages or AvgtsImages), defined in tiled_splat.hip.
-// term: the splat of the term's one-thread-per-event kernel (contrast_splat_kernel,
+// term: the splat of the term's one-thread-per-event kernel on one flow (contrast_splat_kernel,
 // avgts_splat_kernel: sample and time window, either form of the columns) by the tiled schedule;
 // frames: that of the metric's (iwe_splat_kernel, iwe_avgts_splat_kernel: position in the
 // columns).  The same bytes in the images, all zeroed by the caller; tp: the plan of these
@@ -247,8 +242,8 @@ struct __attribute__((visibility("hidden"))) TiledLaunch {
                       const int64_t *frame_event_begin, const float *frame_ts, const float *flow, int F, int h,
                       int w, int reference_mask, int polarity, const TilePlan &tp, const Images &img,
                       void *tile_workspace, hipStream_t stream);
-    // pyramid: the splat of the term's kernel over a level table (contrast_pyramid_splat_kernel,
-    // avgts_pyramid_splat_kernel); img: the images of all levels, a level's at its image_offset
+    // pyramid: the splat of the same kernels over a level table (their TableView instances);
+    // img: the images of all levels, a level's at its image_offset
     static int pyramid(const TiledTermColumns &cols, int64_t n_events, const float *frame_ts,
                        const int64_t *frame_sample, int F, int h, int w, int reference_mask, int polarity,
                        const dvsof_contrast_levels_t &levels, const PyramidTilePlan &tp, const Images &img,

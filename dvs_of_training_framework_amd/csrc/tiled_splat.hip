@@ -301,9 +301,6 @@ int term_splat(const Cols &cols, int64_t n_events, const float *frame_ts, const 
 // over the block (Y << d .., X << d ..), d = shift_k - shift_source, clipped at
 // the source's edge -- integers, exact, count modulo 2^32 either way.
 // ---------------------------------------------------------------------------
-using Levels = dvsof_contrast_levels_t;
-using Level = dvsof_contrast_level_t;
-
 struct PyramidBuckets {
     uint32_t *cursor;  // [tiles of all levels * kCursorStride]
     uint32_t *rec;     // per level [tiles_k][kCols][cap_k], level k at record rec_base[k]

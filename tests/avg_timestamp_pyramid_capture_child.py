@@ -30,8 +30,7 @@ STEPS, ACCUM = 5, 2
 # events per sample: 3072 a batch in buffers of 4096 (padded slots), then 5120, which they do not hold;
 # the first micro-batch of the larger kind
 SMALL, LARGE, GROWS_AT = 1536, 2560, 6
-PYRAMID = ('avgts_pyramid_splat_kernel', 'avgts_pyramid_close_kernel', 'avgts_pyramid_bwd_events_kernel',
-           'avgts_pyramid_bwd_close_kernel')
+PYRAMID = ('avgts_splat_kernel<TableView>', 'avgts_close_kernel<TableView>', 'avgts_bwd_events_kernel<TableView>')
 OPTIONS = {
     'framed': {'avg_timestamp_weight': 0.5, 'avg_timestamp_scales': 'all',
                'avg_timestamp_references': ('start', 'middle', 'end'), 'avg_timestamp_polarity': True},

@@ -46,17 +46,34 @@ CONTRAST = {'contrast_weight': 0.25}
 WIDE = {'contrast_weight': 0.25, 'contrast_scales': 'all',
         'contrast_references': ('start', 'middle', 'end'), 'contrast_polarity': True,
         'avg_timestamp_weight': 0.5, 'avg_timestamp_polarity': True}
-# the library's kernels of the terms, by the option set that launches them
+# the library's kernels of the terms, by the option set that launches them: 'name<View>' is the
+# kernel 'name' instantiated for that view of the call's levels (csrc/event_term_levels.h), on
+# one flow (OneLevel) or over a level table (TableView)
 KERNELS = {
-    'contrast': ('contrast_splat_kernel', 'contrast_close_kernel', 'contrast_bwd_events_kernel',
-                 'contrast_bwd_close_kernel'),
-    'pyramid': ('contrast_pyramid_splat_kernel', 'contrast_pyramid_close_kernel',
-                'contrast_pyramid_bwd_events_kernel', 'contrast_pyramid_bwd_close_kernel'),
-    'avg_timestamp': ('avgts_splat_kernel', 'avgts_close_kernel', 'avgts_bwd_events_kernel',
-                      'avgts_bwd_close_kernel'),
+    'contrast': ('contrast_splat_kernel<OneLevel>', 'contrast_close_kernel<OneLevel>',
+                 'contrast_bwd_events_kernel<OneLevel>'),
+    'pyramid': ('contrast_splat_kernel<TableView>', 'contrast_close_kernel<TableView>',
+                'contrast_bwd_events_kernel<TableView>'),
+    'avg_timestamp': ('avgts_splat_kernel<OneLevel>', 'avgts_close_kernel<OneLevel>',
+                      'avgts_bwd_events_kernel<OneLevel>'),
     'frameless': ('frameless_sweep_kernel',),
+    # the backward's closing kernel, which both terms share
+    'bwd_close': ('event_term_bwd_close_kernel<OneLevel>', 'event_term_bwd_close_kernel<TableView>'),
 }
-OURS = ('contrast_', 'avgts_', 'frameless_', 'fill_u32', 'frame_final_kernel')
+OURS = ('contrast_', 'avgts_', 'event_term_', 'frameless_', 'fill_u32', 'frame_final_kernel')
+
+
+def node_count(key, names):
+    """How many of the node names are the kernel ``key`` ('name' or 'name<View>')."""
+    name, _, view = key.rstrip('>').partition('<')
+    return sum(name in n and view in n for n in names)
+
+
+def closings_match(counts):
+    """Per view: one closing kernel for every backward over events of either term."""
+    return all(counts[close] == sum(v for k, v in counts.items()
+                                    if 'bwd_events_kernel' in k and k.endswith(close[close.index('<'):]))
+               for close in KERNELS['bwd_close'])
 
 
 def frameless(batch):
@@ -141,8 +158,7 @@ def run_loop(args, data, seed, capture, opts, red=None, event_terms=True):
             names = [n[3] for n in step.executor.nodes()]
             # per micro-batch (one step is one): how often each kernel of the terms is a node
             # (no name of KERNELS is part of another)
-            info['kernels'][role] = {k: sum(k in n for n in names)
-                                     for group in KERNELS.values() for k in group}
+            info['kernels'][role] = {k: node_count(k, names) for group in KERNELS.values() for k in group}
             info['marks'] = step.executor.marks
             info['violations'] += len(getattr(step, 'exchange_audit', {}).get('violations', []))
         info['failed'] = str(self.failed) if self.failed else None

@@ -66,7 +66,8 @@ def run_loop(args, data, seed, capture, feeder):
             info['unheld'] += len(a['unheld'])
             info['ours_foreign'] += [n for n in a['foreign'] if any(o in n for o in OURS)]
             names = [n[3] for n in step.executor.nodes()]
-            terms = [n for n in names if 'contrast_pyramid_' in n or 'avgts_' in n]
+            # the contrast term on every scale: its kernels over a level table (csrc/event_term_levels.h)
+            terms = [n for n in names if ('contrast_' in n and 'TableView' in n) or 'avgts_' in n]
             info['encoded_nodes'] += sum('EncodedColumns' in n for n in terms)
             info['wire_nodes'] += sum('WireColumns' in n for n in terms)
         info['failed'] = str(self.failed) if self.failed else None

@@ -50,6 +50,7 @@ def test_the_captured_loop_with_the_term_on_every_scale_is_the_eager_loop(scenar
     for role in ('first', 'last'):
         counts = r['kernels'][role]
         assert all(counts[k] == 1 for k in child.PYRAMID), (role, counts)
+        assert child.base.closings_match(counts), (role, counts)
         assert all(counts[k] == 0 for k in child.base.KERNELS['avg_timestamp']), (role, counts)
         assert all(counts[k] == 0 for k in child.base.KERNELS['pyramid']), (role, counts)
         assert all((counts[k] >= 1) == (scenario == 'frameless')

@@ -53,6 +53,7 @@ def check_loop(r, steps, accum, active, idle=()):
             assert all(counts[k] >= 1 for k in child.KERNELS[group]), (role, group, counts)
         for group in idle:
             assert all(counts[k] == 0 for k in child.KERNELS[group]), (role, group, counts)
+        assert child.closings_match(counts) and sum(counts[k] for k in child.KERNELS['bwd_close']) >= 1, (role, counts)
 
 
 # ------------------------------------------- 1. captured loop = eager loop
