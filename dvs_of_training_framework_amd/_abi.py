@@ -65,6 +65,8 @@ EVENT_PYRAMIDS_TILED_PATH = HEADER_PATH.with_name('dvsof_event_pyramids_tiled.h'
 EVENT_TERMS_JOINT_PATH = HEADER_PATH.with_name('dvsof_event_terms_joint.h')
 # And the gradient-magnitude objective of the contrast term (CONTRAST_GRADIENT_FUNCTIONS), functions only
 CONTRAST_GRADIENT_PATH = HEADER_PATH.with_name('dvsof_contrast_gradient.h')
+# And the census term of the framed loss (CENSUS_FUNCTIONS): functions only, which take dvsof.h's level table
+CENSUS_PATH = HEADER_PATH.with_name('dvsof_census.h')
 
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
@@ -289,3 +291,9 @@ CONTRAST_GRADIENT_FUNCTIONS = _read_extension(
     | set(AVG_TIMESTAMP_FUNCTIONS) | set(AVG_TIMESTAMP_PYRAMID_FUNCTIONS) | set(EVENT_TERMS_ENCODED_FUNCTIONS)
     | set(IWE_AVG_TIMESTAMP_FUNCTIONS) | set(EVENT_IMAGES_TILED_FUNCTIONS) | set(AVG_TIMESTAMP_TILED_FUNCTIONS)
     | set(EVENT_PYRAMIDS_TILED_FUNCTIONS) | set(EVENT_TERMS_JOINT_FUNCTIONS))
+CENSUS_FUNCTIONS = _read_extension(
+    CENSUS_PATH, set(FUNCTIONS) | set(EXTENSION_FUNCTIONS) | set(CONTRAST_MULTI_FUNCTIONS)
+    | set(IWE_MULTI_FUNCTIONS) | set(LOSS_FRAMELESS_FUNCTIONS) | set(CONTRAST_PYRAMID_FUNCTIONS)
+    | set(AVG_TIMESTAMP_FUNCTIONS) | set(AVG_TIMESTAMP_PYRAMID_FUNCTIONS) | set(EVENT_TERMS_ENCODED_FUNCTIONS)
+    | set(IWE_AVG_TIMESTAMP_FUNCTIONS) | set(EVENT_IMAGES_TILED_FUNCTIONS) | set(AVG_TIMESTAMP_TILED_FUNCTIONS)
+    | set(EVENT_PYRAMIDS_TILED_FUNCTIONS) | set(EVENT_TERMS_JOINT_FUNCTIONS) | set(CONTRAST_GRADIENT_FUNCTIONS))

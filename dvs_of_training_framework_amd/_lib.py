@@ -30,7 +30,9 @@ tests/golden/abi_signatures_event_pyramids_tiled.json;
 _abi.EVENT_TERMS_JOINT_PATH: include/dvsof_event_terms_joint.h, recorded in
 tests/golden/abi_signatures_event_terms_joint.json;
 _abi.CONTRAST_GRADIENT_PATH: include/dvsof_contrast_gradient.h, recorded in
-tests/golden/abi_signatures_contrast_gradient.json).
+tests/golden/abi_signatures_contrast_gradient.json;
+_abi.CENSUS_PATH: include/dvsof_census.h, recorded in
+tests/golden/abi_signatures_census.json).
 
 There is NO fallback: if the library is missing or a call fails the product
 raises.  PyTorch is used only for device memory and streams; every entry
@@ -165,6 +167,11 @@ def declared_contrast_gradient_symbols():
     return _declared_in((_abi.CONTRAST_GRADIENT_PATH,))
 
 
+def declared_census_symbols():
+    """Names of all entry points include/dvsof_census.h declares."""
+    return _declared_in((_abi.CENSUS_PATH,))
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -192,7 +199,9 @@ def lib():
                                   # include/dvsof_event_terms_joint.h: likewise
                                   **_abi.EVENT_TERMS_JOINT_FUNCTIONS,
                                   # include/dvsof_contrast_gradient.h: likewise
-                                  **_abi.CONTRAST_GRADIENT_FUNCTIONS}.items():
+                                  **_abi.CONTRAST_GRADIENT_FUNCTIONS,
+                                  # include/dvsof_census.h: likewise
+                                  **_abi.CENSUS_FUNCTIONS}.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib

@@ -88,8 +88,9 @@ class ValidationHook:
     def __init__(self, model, device, loader, logger, losses, weights, is_raw,
                  contrast_weight=0.0, contrast_references=('start',), contrast_polarity=False,
                  contrast_scales='finest', avg_timestamp_scales='finest', contrast_tiled=False,
-                 avg_timestamp_tiled=False, contrast_objective='variance', avg_timestamp_weight=0.0,
-                 avg_timestamp_references=('start', 'end'), avg_timestamp_polarity=False):
+                 avg_timestamp_tiled=False, contrast_objective='variance', census_weight=0.0,
+                 avg_timestamp_weight=0.0, avg_timestamp_references=('start', 'end'),
+                 avg_timestamp_polarity=False):
         self.model, self.device, self.loader = model, device, loader
         self.logger, self.losses = logger, losses
         self.weights = deepcopy(weights)
@@ -102,6 +103,8 @@ class ValidationHook:
             self.extra['contrast_tiled'] = contrast_tiled
         if contrast_weight and contrast_objective != 'variance':
             self.extra['contrast_objective'] = contrast_objective
+        if census_weight:
+            self.extra['census_weight'] = census_weight
         if avg_timestamp_weight:
             self.extra.update(avg_timestamp_weight=avg_timestamp_weight,
                               avg_timestamp_references=tuple(avg_timestamp_references),

@@ -18,7 +18,9 @@ Differences that are deliberate (MI355X-first):
     events alone, on the finest flow or, with ``scales='all'``
     (``Losses.avg_timestamp_scales`` for the second), on every flow
     (csrc/contrast.hip, csrc/avg_timestamp.hip; docs/CONTRAST_SPEC.md,
-    docs/AVG_TIMESTAMP_SPEC.md).
+    docs/AVG_TIMESTAMP_SPEC.md);
+  * ``Losses.census`` is an opt-in fourth term of the framed loss, the ternary
+    census loss on every flow scale (csrc/census.hip, docs/CENSUS_SPEC.md).
 """
 import ctypes
 
@@ -691,6 +693,63 @@ class _ContrastGradient(torch.autograd.Function):
             *ctx.args, q.data_ptr(), ws.data_ptr(), nbytes, seed.data_ptr(), ctx.weight, grad.data_ptr(),
             _lib.stream()), name)
         return (grad,) + (None,) * 10
+
+
+# ---------------------------------------------------------------------------
+# Census term of the framed loss (csrc/census.hip, docs/CENSUS_SPEC.md)
+# ---------------------------------------------------------------------------
+CENSUS_HEADER_WORDS = 40    # float32 words in front of the planes (include/dvsof_census.h)
+
+
+def census_workspace(ws, shapes, N):
+    """The planes of the workspace of dvsof_census_fwd a caller may read, as
+    views of the float32 tensor ``ws``: per level (Bw [N, h, w], r [N, h, w])."""
+    out, o = [], CENSUS_HEADER_WORDS
+    for h, w in shapes:
+        n = N * h * w
+        out.append((ws[o:o + n].view(N, h, w), ws[o + n:o + 2 * n].view(N, h, w)))
+        o += 2 * n
+    return out
+
+
+class _Census(torch.autograd.Function):
+    """(weight * mean_k term_k, terms[K]) of all flows by dvsof_census_fwd /
+    _bwd, whose workspace holds the warped frames and the Charbonnier
+    derivatives the backward gathers."""
+
+    @staticmethod
+    def forward(ctx, frames, start, stop, weight, *flows):
+        K, N = len(flows), flows[0].shape[0]
+        dev = flows[0].device
+        flows = tuple(f.detach().contiguous().float() for f in flows)
+        arr = _scale_array(frames, flows, None)
+        lib = _lib.lib()
+        nbytes = lib.dvsof_census_workspace_bytes(arr, K, N)
+        if nbytes == 0:
+            raise RuntimeError('dvsof_census_workspace_bytes: invalid scales')
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        terms = torch.empty(K, dtype=torch.float32, device=dev)
+        value = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.check(lib.dvsof_census_fwd(
+            arr, K, N, start.data_ptr(), stop.data_ptr(), float(weight), terms.data_ptr(), value.data_ptr(),
+            ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_census_fwd')
+        ctx.held = (frames, start, stop, flows, ws, nbytes)
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)
+        return value, terms
+
+    @staticmethod
+    def backward(ctx, g_value, _g_terms):
+        frames, start, stop, flows, ws, nbytes = ctx.held
+        if g_value is None:
+            return (None,) * (4 + len(flows))
+        grads = tuple(torch.empty_like(f) for f in flows)
+        arr = _scale_array(frames, flows, grads)
+        seed = g_value.contiguous().float()
+        _lib.check(_lib.lib().dvsof_census_bwd(
+            arr, len(flows), flows[0].shape[0], start.data_ptr(), stop.data_ptr(), seed.data_ptr(),
+            ws.data_ptr(), nbytes, _lib.stream()), 'dvsof_census_bwd')
+        return (None,) * 4 + grads
 
 
 # The term on every flow scale (csrc/contrast.hip, CONTRAST_SPEC sections 19-23)
@@ -1422,6 +1481,22 @@ class Losses:
         weights = tuple(weights)
         assert len(weights) == 2, 'weights = (smoothness, out-of-border)'
         return _FramelessLoss.apply(weights, loss_scale, *flows)
+
+    def census(self, flows, flow_ts, flow_sample_idx, images, timestamps, sample_idx, weight=None,
+               frame_indices=None):
+        """The ternary census term of every flow (docs/CENSUS_SPEC.md): per
+        level the Charbonnier of the soft Hamming distance between the 7x7
+        ternary transforms of the first frame and of the warped second frame,
+        averaged over the pixels whose patch and sample position are inside the
+        image; invariant to additive and monotone brightness changes between
+        the frames.  -> (value, terms [K]): value = weight * the mean of the
+        levels' terms (weight=None: the mean itself), differentiable with
+        respect to every flow (the weight is applied inside the kernels);
+        terms detached for logging.  The frames are the levels of
+        ``_pyramid``.  Nothing waits for the device."""
+        frames, start, stop = self._prepare(flows, flow_ts, flow_sample_idx, images, timestamps, sample_idx,
+                                            frame_indices)
+        return _Census.apply(frames, start, stop, 1.0 if weight is None else float(weight), *flows)
 
     def contrast(self, flows, flow_ts, flow_sample_idx, events, weight=None,
                  references=('start',), polarity=False, scales='finest', tiled=False, objective='variance'):

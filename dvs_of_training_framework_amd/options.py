@@ -349,6 +349,18 @@ def add_train_arguments(parser):           # utils/options.py:204-302
                              '--contrast-weight and runs on the finest flow, eagerly: not with '
                              '--contrast-scales all, --event-images-tiled, --event-pyramids-tiled, '
                              '--event-terms-joint or --capture-event-terms')
+    parser.add_argument('--census-weight', dest='census_weight',
+                        default=argparse.SUPPRESS, type=float,
+                        help='add this times the ternary census term to the training loss: per flow '
+                             'scale the Charbonnier of the soft Hamming distance between the 7x7 '
+                             'ternary census transforms of the first frame and of the second frame '
+                             'warped by the flow, over the pixels whose patch and sample position '
+                             'are inside the image (Meister et al. 2018; docs/CENSUS_SPEC.md); '
+                             'invariant to exposure changes between the frames, which the '
+                             'photometric term is not.  Logged as Train/census, Validation/census '
+                             'and per level .../census/<tag>.  Needs frames: not with --recording '
+                             'or --validation-recording; --capture runs such a run eagerly.  '
+                             'Independent of the events-only terms.  Absent or 0: off')
     parser.add_argument('--avg-timestamp-weight', dest='avg_timestamp_weight',
                         default=argparse.SUPPRESS, type=float,
                         help='add this times the average-timestamp term to the training '
@@ -517,10 +529,26 @@ def validate_train_args(args):             # utils/options.py:318-325
     if getattr(args, 'representation_deterministic', False) and \
             not getattr(args, 'learnable_representation', False):
         raise SystemExit('--representation-deterministic needs --learnable-representation')
+    # (the census term first: a recording refuses it by its own name, before what else the recording needs)
     return validate_contrast_objective_args(validate_event_terms_joint_args(validate_event_pyramids_tiled_args(
         validate_avg_timestamp_tiled_args(validate_event_images_tiled_args(validate_compact_event_terms_args(
             validate_capture_event_terms_args(validate_frameless_args(validate_sharpness_args(
-                validate_avg_timestamp_args(validate_contrast_args(args)))))))))))
+                validate_avg_timestamp_args(validate_contrast_args(validate_census_args(args))))))))))))
+
+
+def validate_census_args(args):
+    """--census-weight (absent from ``args`` unless given): not negative, and
+    not with the recordings that carry no frames."""
+    weight = getattr(args, 'census_weight', 0.0)
+    if weight < 0:
+        raise SystemExit(f'--census-weight must not be negative, got {weight}')
+    if not weight:
+        return args
+    for flag, dest in (('--recording', 'recording'), ('--validation-recording', 'validation_recording')):
+        if getattr(args, dest, None) is not None:
+            raise SystemExit(f'--census-weight {weight} cannot be combined with {flag}: the census term '
+                             'compares two frames and an event-only recording has none')
+    return args
 
 
 def validate_contrast_objective_args(args):

@@ -51,12 +51,15 @@ class _TermsAndContrast(tuple):
     of the micro-batch beside it (``contrast``: a 0-dim device tensor) and,
     where the loss has one, the average-timestamp term (``avg_timestamp``,
     likewise; either is None where the loss has none, and the [K] tensor of
-    the levels' terms where it is taken on every scale)."""
-    def __new__(cls, terms, contrast, avg_timestamp=None):
+    the levels' terms where it is taken on every scale) and the census term
+    (``census``: the [K] tensor of the levels' terms, None where the loss has
+    none; ``contrast`` may be None beside it)."""
+    def __new__(cls, terms, contrast, avg_timestamp=None, census=None):
         self = super().__new__(cls, terms)
         self.packed = getattr(terms, 'packed', None)
         self.contrast = contrast
         self.avg_timestamp = avg_timestamp
+        self.census = census
         return self
 
 
@@ -163,7 +166,8 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                   contrast_references=('start',), contrast_polarity=False,
                   contrast_scales='finest', avg_timestamp_scales='finest',
                   contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-                  event_terms_joint=False, contrast_objective='variance', avg_timestamp_weight=0.0,
+                  event_terms_joint=False, contrast_objective='variance', census_weight=0.0,
+                  avg_timestamp_weight=0.0,
                   avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                   avg_timestamp_polarity=False):
     """-> (sum_t weights[t] * mean_k term[t][k], terms).  With an evaluator
@@ -218,6 +222,14 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     avg_timestamp_tiled are refused with it.  False, the default, constructs
     nothing new.
 
+    census_weight > 0: plus census_weight * the mean over the flow scales of
+    the ternary census term of the two frames (loss.Losses.census,
+    docs/CENSUS_SPEC.md), added right after the terms above and before the
+    events-only ones; the [K] tensor of the levels' terms rides on the returned
+    terms as ``.census`` (``.contrast`` is None there unless that term runs
+    too).  It reads frames: ValueError with images=None, and for a negative
+    weight.  At 0 nothing is constructed and the call returns what it returned.
+
     images=None with an evaluator that has ``frameless`` (loss.Losses): a
     frameless batch (docs/FRAMELESS_SPEC.md).  That method gives smoothness
     and out-of-border with the weights (weights[0], weights[2]) and a
@@ -227,6 +239,12 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
     no data term)."""
     extra = {} if frame_indices is None else {'frame_indices': frame_indices}
     call = (flows, flow_ts, flow_sample_idx, images, timestamps, sample_idx)
+    if census_weight:
+        if census_weight < 0:
+            raise ValueError(f'census_weight must not be negative, got {census_weight}')
+        if images is None:
+            raise ValueError('census_weight > 0 needs frames: the census term compares two images, a '
+                             'frameless batch (images=None) has none')
     trainable = torch.is_grad_enabled() and \
         any(f.requires_grad for f in flows)
     if images is None and hasattr(evaluator, 'frameless'):
@@ -255,8 +273,12 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
                                              False, event_terms_joint)
         if refusal:
             raise ValueError('contrast_objective ' + refusal)
+    census = None
+    if census_weight:
+        value, census = evaluator.census(*call, weight=census_weight, **extra)
+        loss = loss + value
     if not contrast_weight and not avg_timestamp_weight:
-        return loss, terms
+        return (loss, terms) if census is None else (loss, _TermsAndContrast(terms, None, census=census))
     term = avg_term = None
     if event_terms_joint:
         if contrast_weight < 0 or avg_timestamp_weight < 0:
@@ -274,7 +296,7 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
             avg_timestamp=dict(weight=avg_timestamp_weight, references=tuple(avg_timestamp_references),
                                polarity=bool(avg_timestamp_polarity), scales=avg_timestamp_scales),
             **({'tiled': event_pyramids_tiled} if event_pyramids_tiled else {}))
-        return loss + value + avg_value, _TermsAndContrast(terms, term, avg_term)
+        return loss + value + avg_value, _TermsAndContrast(terms, term, avg_term, census=census)
     if contrast_weight:
         if contrast_weight < 0:
             raise ValueError(f'contrast_weight must not be negative, got {contrast_weight}')
@@ -305,7 +327,7 @@ def combined_loss(evaluator, flows, flow_ts, flow_sample_idx, images,
             evaluator.avg_timestamp_tiled if 'tiled' in options else evaluator.avg_timestamp
         value, avg_term = method(flows, flow_ts, flow_sample_idx, events, weight=avg_timestamp_weight, **options)
         loss = loss + value
-    return loss, _TermsAndContrast(terms, term, avg_term)
+    return loss, _TermsAndContrast(terms, term, avg_term, census=census)
 
 
 class TermReadback:
@@ -325,6 +347,20 @@ class TermReadback:
         self._contrast_levels = None
         self._avg_timestamp = getattr(terms, 'avg_timestamp', None)
         self._avg_timestamp_levels = None
+        self._census = getattr(terms, 'census', None)
+
+    def census_levels(self):
+        """The levels' census terms as host floats (one small copy), coarsest
+        first; None when the loss has none."""
+        if isinstance(self._census, torch.Tensor):
+            self._census = self._census.tolist()
+        return self._census
+
+    def census(self):
+        """The census term as a host float, the mean of the levels' terms;
+        None when the loss has none."""
+        levels = self.census_levels()
+        return None if levels is None else sum(levels) / len(levels)
 
     def avg_timestamp(self):
         """The average-timestamp term as a host float (one small copy), None
@@ -421,14 +457,16 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
                       contrast_references=('start',), contrast_polarity=False,
                       contrast_scales='finest', avg_timestamp_scales='finest',
                       contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-                      event_terms_joint=False, contrast_objective='variance', avg_timestamp_weight=0.0,
+                      event_terms_joint=False, contrast_objective='variance', census_weight=0.0,
+                      avg_timestamp_weight=0.0,
                       avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
                       avg_timestamp_polarity=False):
     """batch (SURVEY 8b wire format, or compact event columns:
     voxel.is_compact) -> (loss, terms, tags[, outputs]).
     contrast_weight > 0 (raw events only, in either column form), contrast_references,
     contrast_polarity, contrast_scales, contrast_objective, and avg_timestamp_weight > 0 (raw
-    events only) with its references, polarity, scales and avg_timestamp_tiled: see ``combined_loss``.  A frameless batch
+    events only) with its references, polarity, scales and avg_timestamp_tiled, and census_weight > 0 (framed
+    batches only): see ``combined_loss``.  A frameless batch
     (``'images': None``, ``'shape': (h, w)``; sequence.EventWindowLoader) takes
     the frame size from ``'shape'`` and the loss that reads no frame."""
     contrast = _contrast_keywords(contrast_weight, contrast_references, contrast_polarity, contrast_scales,
@@ -462,7 +500,8 @@ def process_minibatch(model, batch, timers, device, is_raw, evaluator,
             evaluator, flows, flow_ts, flow_sample_idx, images, timestamps,
             sample_idx, features, weights=weights,
             frame_indices=getattr(model, 'last_frame_indices', None),
-            **(dict(contrast, events=payload) if contrast else {}))
+            **(dict(contrast, events=payload) if contrast else {}),
+            **({'census_weight': census_weight} if census_weight else {}))
         terms = TermReadback(terms)
     if not return_prediction:
         return loss, terms, tags
@@ -499,6 +538,8 @@ class ScaleSums:
         self.contrast_levels = None  # and per level, if it is taken on every scale
         self.avg_timestamp = None   # sum of the average-timestamp term, if the loss has one
         self.avg_timestamp_levels = None    # and per level, if it is taken on every scale
+        self.census = None          # sum of the census term, if the loss has one
+        self.census_levels = None   # and per level
         self.tags = None
 
     def add(self, loss, readback, tags):
@@ -522,6 +563,10 @@ class ScaleSums:
             if levels is not None:
                 self.avg_timestamp_levels = [a + b for a, b in
                                              zip(self.avg_timestamp_levels or [0.0] * len(levels), levels)]
+        levels = readback.census_levels() if hasattr(readback, 'census_levels') else None
+        if levels is not None:
+            self.census = (self.census or 0.0) + readback.census()
+            self.census_levels = [a + b for a, b in zip(self.census_levels or [0.0] * len(levels), levels)]
         self.tags = list(tags)
 
     def write(self, logger, x, divisor, families):
@@ -655,6 +700,15 @@ def avg_timestamp_capture_refusal(avg_timestamp_weight=0.0):
     return None
 
 
+def census_capture_refusal(census_weight=0.0):
+    """Why ``train(capture=True)`` cannot replay a step that holds the census
+    term (None: there is none); asked before the other refusals."""
+    if census_weight:
+        return (f'--census-weight {census_weight}: the captured step does not carry the census term '
+                '(dvsof_census_fwd / dvsof_census_bwd)')
+    return None
+
+
 EVENT_TERM_METHODS = ('contrast', 'avg_timestamp', 'frameless')
 
 
@@ -686,7 +740,7 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
           contrast_polarity: bool = False, contrast_scales: str = 'finest',
           capture_event_terms: bool = False, avg_timestamp_scales: str = 'finest',
           contrast_tiled=False, avg_timestamp_tiled=False, event_pyramids_tiled=False,
-          event_terms_joint=False, contrast_objective: str = 'variance',
+          event_terms_joint=False, contrast_objective: str = 'variance', census_weight: float = 0.0,
           avg_timestamp_weight: float = 0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
           avg_timestamp_polarity: bool = False):
     """Semantics of utils/training.py:89-235: ``accumulation_steps``
@@ -763,6 +817,13 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                (ValueError, ``contrast_objective_refusal``); with ``capture``
                the loop runs eagerly and says so.  'variance' (the default):
                the step launches what it launches without it.  (By name)
+    census_weight:  > 0 adds this times the ternary census term of the two
+               frames, the mean over the flow scales, to the loss
+               (docs/CENSUS_SPEC.md; framed batches only), logged as
+               ``Train/census`` and ``Train/census/<tag>`` per level.  With
+               ``capture`` the loop runs eagerly and says so
+               (``census_capture_refusal``).  0 (the default): the step
+               launches what it launches without it.  (By name)
     avg_timestamp_weight:  > 0 adds this times the average-timestamp term of
                the finest flow to the loss (docs/AVG_TIMESTAMP_SPEC.md; raw
                events only), logged as ``Train/avg timestamp``, beside the
@@ -845,6 +906,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                    or capture_refusal(optimizer, is_raw, model, contrast_weight)) if capture else None
         if refused and contrast_objective != 'variance':
             refused += f' (contrast objective {contrast_objective}: dvsof_contrast_gradient_fwd / _bwd)'
+    if capture and census_weight:
+        refused = census_capture_refusal(census_weight)
     if refused:
         import sys
         print(f'capture: not used, the loop runs eagerly: {refused}', file=sys.stderr)
@@ -889,7 +952,8 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
                                           avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled),
                 **({'event_pyramids_tiled': event_pyramids_tiled} if event_pyramids_tiled else {}),
-                **({'event_terms_joint': True} if event_terms_joint else {}))
+                **({'event_terms_joint': True} if event_terms_joint else {}),
+                **({'census_weight': census_weight} if census_weight else {}))
             with _timed(timers, 'backprop'):
                 if accumulation_steps == 1:
                     unit_backward(loss)     # seed 1.0: no fill, no scaling pass
@@ -931,6 +995,10 @@ def train(model, device, loader, optimizer, num_steps: int, scheduler, logger,
                         for tag, level in zip(sums.tags, sums.avg_timestamp_levels or ()):
                             logger.add_scalar(f'Train/avg timestamp/{tag}',
                                               level / accumulation_steps, x)
+                    if sums.census is not None:
+                        logger.add_scalar('Train/census', sums.census / accumulation_steps, x)
+                        for tag, level in zip(sums.tags, sums.census_levels):
+                            logger.add_scalar(f'Train/census/{tag}', level / accumulation_steps, x)
                     for g, group in enumerate(optimizer.param_groups):
                         logger.add_scalar(f'General/learning rate/{g}',
                                           group['lr'], x)
@@ -967,8 +1035,9 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
              weights=[0.5, 1, 1], is_raw=True, contrast_weight=0.0,
              contrast_references=('start',), contrast_polarity=False,
              contrast_scales='finest', avg_timestamp_scales='finest', contrast_tiled=False,
-             avg_timestamp_tiled=False, contrast_objective='variance', avg_timestamp_weight=0.0,
-             avg_timestamp_references=AVG_TIMESTAMP_REFERENCES, avg_timestamp_polarity=False):
+             avg_timestamp_tiled=False, contrast_objective='variance', census_weight=0.0,
+             avg_timestamp_weight=0.0, avg_timestamp_references=AVG_TIMESTAMP_REFERENCES,
+             avg_timestamp_polarity=False):
     """Mean loss and per-scale mean terms over ``loader`` (eval mode,
     no_grad), written against ``samples_passed``; with contrast_weight > 0
     the loss holds the contrast-maximisation term (of those reference times
@@ -978,7 +1047,9 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
     written as ``Validation/avg timestamp``; with avg_timestamp_scales='all'
     that is the mean of the levels' terms, each written as ``Validation/avg
     timestamp/<tag>`` beside it.  contrast_tiled, avg_timestamp_tiled,
-    contrast_objective: as ``train`` takes them."""
+    contrast_objective: as ``train`` takes them.  With census_weight > 0 the
+    loss holds the census term, written as ``Validation/census`` and, per
+    level, ``Validation/census/<tag>``."""
     model.eval()
     sums, quiet = ScaleSums(), FakeTimer()
     n_batches = len(loader)
@@ -989,7 +1060,8 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
                 **_contrast_keywords(contrast_weight, contrast_references, contrast_polarity,
                                      contrast_scales, contrast_tiled, contrast_objective),
                 **_avg_timestamp_keywords(avg_timestamp_weight, avg_timestamp_references,
-                                          avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled))
+                                          avg_timestamp_polarity, avg_timestamp_scales, avg_timestamp_tiled),
+                **({'census_weight': census_weight} if census_weight else {}))
             sums.add(loss, terms, tags)
     logger.add_scalar('General/Validation loss', sums.loss / n_batches,
                       samples_passed)
@@ -1002,3 +1074,7 @@ def validate(model, device, loader, samples_passed, logger, evaluator,
                           samples_passed)
         for tag, level in zip(sums.tags, sums.avg_timestamp_levels or ()):
             logger.add_scalar(f'Validation/avg timestamp/{tag}', level / n_batches, samples_passed)
+    if sums.census is not None:
+        logger.add_scalar('Validation/census', sums.census / n_batches, samples_passed)
+        for tag, level in zip(sums.tags, sums.census_levels):
+            logger.add_scalar(f'Validation/census/{tag}', level / n_batches, samples_passed)

@@ -72,6 +72,10 @@
 #                                     and the metric's call, per-event against tiled in alternating blocks of one run
 #                                     after a bitwise comparison, and one eager Ranger step either way
 #                                     (profiles/avg_timestamp_tiled/README.md)
+#   census [census_bench.py args]    the census term of the framed loss (--census-weight; tools/census_bench.py):
+#                                     dvsof_census_fwd / _bwd alone beside dvsof_loss_fused and dvsof_loss_pyramid at
+#                                     batch 8, 256x256, four scales, and one eager Ranger step with and without the
+#                                     term, in alternating blocks of one run (profiles/census/README.md)
 #   learned [learned_voxel_bench.py args]  learnable representation: forward against the fixed voxeliser, table gradient,
 #                                     enc.0 data gradient, eager step with and without it, executor replay of the
 #                                     resident model against its eager loop, the same under DVSOF_LOOPBACK=8:50;
@@ -164,6 +168,9 @@ eventtiled)
 avgtiled)
   timeout -k 10 540 env "${envs[@]}" python tools/avg_timestamp_tiled_bench.py "$@" > $O/avgtiled.jsonl 2> $O/avgtiled.err
   echo "avgtiled rc=$?"; cut -c1-700 $O/avgtiled.jsonl; tail -3 $O/avgtiled.err ;;
+census)
+  timeout -k 10 420 env "${envs[@]}" python tools/census_bench.py "$@" > $O/census.jsonl 2> $O/census.err
+  echo "census rc=$?"; cut -c1-1200 $O/census.jsonl; tail -3 $O/census.err ;;
 learned)
   timeout -k 10 420 env "${envs[@]}" python tools/learned_voxel_bench.py "$@" > $O/learned.json 2> $O/learned.err
   rc=$?; echo "learned rc=$rc"; cut -c1-2000 $O/learned.json; tail -3 $O/learned.err

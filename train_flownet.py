@@ -505,6 +505,7 @@ def main(argv=None):
                 **({'contrast_objective': args.contrast_objective}
                    if getattr(args, 'contrast_objective', 'variance') != 'variance' else {})}
                if getattr(args, 'contrast_weight', 0.0) else {}),
+            **({'census_weight': args.census_weight} if getattr(args, 'census_weight', 0.0) else {}),
             **avg_timestamp_keywords(args))
         periodic['validation'] = make_hook_periodic(hooks['validation'], args.vp)
     elif not args.skip_validation:
@@ -545,7 +546,8 @@ def main(argv=None):
                   **({'event_terms_joint': True}
                      if getattr(args, 'event_terms_joint', False) else {}),
                   **({'contrast_objective': args.contrast_objective}
-                     if getattr(args, 'contrast_objective', 'variance') != 'variance' else {}))
+                     if getattr(args, 'contrast_objective', 'variance') != 'variance' else {}),
+                  **({'census_weight': args.census_weight} if getattr(args, 'census_weight', 0.0) else {}))
             samples = samples_passed + remaining * args.bs
             if args.training_steps % args.checkpointing_interval != 0:
                 # (otherwise the periodic hook has just written this step)
